@@ -106,6 +106,9 @@ def parse():
     ap.add_argument("--asg", action="store_true", help="ASG criterion (no blank, synthetic transitions; the lexicon without "
                                                         "doubled letters, as replabels guarantee) -- a secondary line")
     ap.add_argument("--log-add", action="store_true", help="logAdd merges -- a secondary line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write the n-best of the last timed step as DIR/<name>.npy (a fixed "
+                         "sample of utterances, at most 64 MB; rank 0's shard): two builds compared output for output")
     return ap.parse_args()
 
 
@@ -142,6 +145,42 @@ def nbest_same(got, want):
         if not (np.array_equal(g.tokens, h.tokens) and np.array_equal(g.words, h.words)):
             return False
     return True
+
+
+DUMP_BYTES = 60 * 10 ** 6  # (under 64 MB, with room for the .npy headers)
+
+
+def dump_outputs(path, B, K, T, with_words, results):
+    """--dump-outputs: the n-best a caller receives for a fixed sample of the batch's utterances (all of them when
+    they fit), results(b) -> [Hyp].  Files (float64, or float32 for token / word ids, exact below 2^24):
+      utterances [S]           the sampled utterance indices (seeded: fixed by the arguments, not by the results)
+      n_hyp, length [S]        hypotheses of each utterance, and their length (finalFrame + 1)
+      scores [S, K, 3]         score, emitting-model score, LM score of hypothesis k; NaN past n_hyp
+      tokens, words [S, K, T + 2]  the hypotheses' rows, NaN-padded; words only for the lexicon decoder"""
+    per_utt = 8 * 3 + K * 3 * 8 + K * (T + 2) * 4 * (2 if with_words else 1)
+    S = max(1, min(B, DUMP_BYTES // per_utt))
+    utts = np.sort(np.random.default_rng(0).permutation(B)[:S])
+    n_hyp, length = np.zeros(S), np.zeros(S)
+    scores = np.full((S, K, 3), np.nan)
+    tokens = np.full((S, K, T + 2), np.nan, dtype=np.float32)
+    words = np.full((S, K, T + 2), np.nan, dtype=np.float32) if with_words else None
+    for j, b in enumerate(utts):
+        hyps = results(int(b))
+        n_hyp[j] = len(hyps)
+        length[j] = len(hyps[0].tokens) if hyps else 0
+        if length[j] > T + 2:
+            raise SystemExit("bench.py --dump-outputs: utterance %d has hypotheses of %d frames (T = %d)" % (b, length[j], T))
+        for k, h in enumerate(hyps):
+            scores[j, k] = (h.score, h.am, h.lm)
+            tokens[j, k, :len(h.tokens)] = h.tokens
+            if words is not None:
+                words[j, k, :len(h.words)] = h.words
+    os.makedirs(path, exist_ok=True)
+    arrays = dict(utterances=utts.astype(np.float64), n_hyp=n_hyp, length=length, scores=scores, tokens=tokens)
+    if words is not None:
+        arrays["words"] = words
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 class Job:
@@ -356,6 +395,8 @@ def measure(a, torch, dist, rank, local, world, primary):
     dt = timed(step, a.steps, a.warmup)
     for i in range(len(decs)):
         read_events(i)
+    if primary and a.dump_outputs and rank == 0:  # (before any later leg decodes on these decoder objects again)
+        dump_outputs(a.dump_outputs, B, K, T, job.lex, decs[(turn[0] - 1) % len(decs)].results)
     # (with "defer_check" = 1 every decode_batch above first settled the batch its decoder object had in flight: the
     # look at the utterances' statuses -- and the second pass of whatever a fast path flagged -- is inside the clock
     # for every timed batch; `unread_redone` counts what those looks decoded again)
@@ -622,6 +663,8 @@ def group_mode(a):
         step()
     grp.synchronize()
     dt = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, n * B, K, T, j0.lex, grp.results)
     parts = grp.parts()
     out = {"metric": "decoded frames/sec (whole node), T=%d N=%d beam=%d; hyp bit-exact vs CPU" % (T, N, K),
            "value": n * B * T * a.steps / dt, "unit": "frames/s", "n_gpus": n, "steps": a.steps, "warmup": a.warmup,
@@ -710,13 +753,32 @@ def pmc_traffic(workload, threads, B, T, N, K, engine=None):
     return None
 
 
+_NGRAM_DIR = []
+
+
+def ngram_dir():
+    """Where the synthetic ARPA files go: $FLTX_NGRAM_CACHE (kept between runs), else a directory of this process's
+    own, removed at exit -- the tree bench.py runs from need not be writable, and nothing is shared with other runs."""
+    if not _NGRAM_DIR:
+        d = os.environ.get("FLTX_NGRAM_CACHE")
+        if d:
+            os.makedirs(d, exist_ok=True)
+        else:
+            import atexit
+            import shutil
+            import tempfile
+            d = tempfile.mkdtemp(prefix="fltx_ngram_")
+            atexit.register(shutil.rmtree, d, True)
+        _NGRAM_DIR.append(d)
+    return _NGRAM_DIR[0]
+
+
 def synthetic_arpa(W):
     """Deterministic synthetic 4-gram ARPA file over the lexicon's words (SURVEY.md
-    section 8d), cached under /tmp -> (path, vocabulary in LM-index order)."""
+    section 8d), written once under ngram_dir() -> (path, vocabulary in LM-index order)."""
     from text_amd import ngram_synth
     vocab = ngram_synth.words(W) + ["<unk>"]
-    d = os.environ.get("FLTX_NGRAM_CACHE", "/tmp/fltx_ngram_cache")
-    os.makedirs(d, exist_ok=True)
+    d = ngram_dir()
     path = os.path.join(d, "lm_o4_s4242_v%d.arpa" % len(vocab))
     if not os.path.exists(path):
         tmp = "%s.tmp%d" % (path, os.getpid())
@@ -730,8 +792,7 @@ def synthetic_token_arpa(N, order, seed):
     ("ngram", order, seed) token LM) -> (path, vocabulary in token order)."""
     from text_amd import ngram_synth
     vocab = ngram_synth.words(N, "t")
-    d = os.environ.get("FLTX_NGRAM_CACHE", "/tmp/fltx_ngram_cache")
-    os.makedirs(d, exist_ok=True)
+    d = ngram_dir()
     path = os.path.join(d, "lm_o%d_s%d_v%d.arpa" % (order, seed, len(vocab)))
     if not os.path.exists(path):
         tmp = "%s.tmp%d" % (path, os.getpid())

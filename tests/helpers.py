@@ -73,7 +73,7 @@ def case_inputs(c):
 
 
 # ---- n-gram LM plumbing -----------------------------------------------------
-NGRAM_DIR = os.environ.get("FLTX_NGRAM_CACHE", "/tmp/fltx_ngram_cache")  # synthetic ARPA files, regenerated on demand
+NGRAM_DIR = os.environ.get("FLTX_NGRAM_CACHE", os.path.join(ROOT, ".ngram_cache"))  # synthetic ARPA files, regenerated on demand
 
 
 def lm_vocab(c, inp):
