@@ -1,26 +1,21 @@
-/* tests/emu/fltx_emu_launch.inc -- the emulator's dispatch over the kernel variants (host threads instead of
- * hipLaunchKernelGGL); included by launchDecode() of text_amd/csrc/fltx_api.cpp under FLTX_EMU only.  It lives here, with
- * the rest of the emulator, so that the product source keeps one dispatch table: the HIP one.
- * In scope: d (fltx_decoder*), P (const DecodeParams&), W (threads per workgroup). */
+/* tests/emu/fltx_emu_launch.inc -- the emulator's launch (host threads instead of hipLaunchKernel); included by
+ * launchDecode() of text_amd/csrc/fltx_api.cpp under FLTX_EMU only.  A lane engine runs the host function its entry of
+ * kLaneKernels names (the same entries as the HIP build's kernels, so a key the HIP build has no kernel for fails
+ * here too); the generic engine's variants are chosen as genericKernel<W> chooses its kernels.
+ * In scope: d (fltx_decoder*), P (const DecodeParams&), key, lane, W, nGrid, lds (as the HIP launch). */
   const DecodeParams* pp = &P;
+  if (key.fam == kWlane && d->wlMaxT > 0) { /* the front-end kernel of fltx_wlane.h: grid (rows / 4, utterances), four waves per workgroup */
+    emuLaunch(pp->tokRowBlocks * nGrid, 256, 4 * sizeof(WlFrontLds), [pp](char* smem) { wlTokBeamRows(*pp, smem); });
+  }
+  if (lane) {
+    const LaneFn fn = lane->fn;
+    emuLaunch(nGrid, W, lds, [pp, fn](char* smem) { fn(*pp, smem); });
+    return FLTX_OK;
+  }
   const int gmax = d->lean;
   const int gt = d->lane;
-  const int wl = (d->wlane && !d->sstreamLaunch) ? d->slane : 0;
-  const int sl = (d->sstreamLaunch || d->wlane) ? 0 : (d->mlaneNG > 1 ? 0 : d->slane);
-  const int ml = (d->sstreamLaunch || d->mlaneNG <= 1) ? 0 : ((d->slane * 10 + d->mlaneNG) * 10 + d->mlaneGPW) * 10 + d->mlaneSPW;
-  const int ss = d->sstreamLaunch ? d->sstream : 0;
-  const bool ts = d->sstreamLaunch && d->tstream;
-  const int xl = d->xlane;
-  const bool xs = d->xlane && d->yshare;
-  const int yl = d->ylane ? d->ylane * 100 + d->ylaneLm + (d->yshare ? 1000 : 0) : 0; /* (as launchDecode's switch) */
   const bool hot = !d->wsInLds && d->hotBytes > 0;
-  if (wl && d->wlMaxT > 0) { /* the front-end kernel of fltx_wlane.h: grid (rows / 4, utterances), four waves per workgroup */
-    const int nUtt = d->nLaunch > 0 ? d->nLaunch : d->B;
-    emuLaunch(pp->tokRowBlocks * nUtt, 256, 4 * sizeof(WlFrontLds), [pp](char* smem) { wlTokBeamRows(*pp, smem); });
-  }
-  emuLaunch(d->nLaunch > 0 ? d->nLaunch : d->B, W,
-            ss ? (ts ? sizeof(TlaneLds) + 10 * kTlGatherBytes : sizeof(SlaneLds)) : (d->wsInLds ? d->wsBytes : (hot ? d->hotBytes : 16)),
-            [pp, gmax, gt, sl, ml, ss, ts, xl, xs, yl, hot, wl](char* smem) {
+  emuLaunch(nGrid, W, lds, [pp, gmax, gt, hot](char* smem) {
     char* base = pp->gws ? pp->gws + (size_t)blockIdx.x * pp->gwsStride : smem;
     if (hot) {
       if (gmax == 255) {
@@ -30,274 +25,8 @@
       }
       return;
     }
-#ifdef FLTX_EMU_YLANE_ML_ONLY /* a quick-to-build emulator for work on fltx_ylane.h's LMK bit 2 (EMU_EXTRA=-DFLTX_EMU_YLANE_ML_ONLY) */
-    if (yl == 1105) {
-      ylaneUtterance<1, 2, 5, 1, false>(*pp, smem);
-    } else if (yl == 1107) {
-      ylaneUtterance<1, 2, 7, 1, false>(*pp, smem);
-    } else if (yl == 1205) {
-      ylaneUtterance<2, 4, 5, 1, false>(*pp, smem);
-    } else if (yl == 1207) {
-      ylaneUtterance<2, 4, 7, 1, false>(*pp, smem);
-    } else {
-      decodeUtterance<0>(*pp, base);
-    }
-    return;
-#endif
-#ifdef FLTX_EMU_YLANE_LA_ONLY /* ... for work on fltx_ylane.h's LMK bit 3 */
-    if (yl == 108 || yl == 1108) {
-      ylaneUtterance<1, 2, 8, 1, false>(*pp, smem);
-    } else if (yl == 109 || yl == 1109) {
-      ylaneUtterance<1, 2, 9, 1, false>(*pp, smem);
-    } else if (yl == 208 || yl == 1208) {
-      ylaneUtterance<2, 4, 8, 1, false>(*pp, smem);
-    } else if (yl == 209 || yl == 1209) {
-      ylaneUtterance<2, 4, 9, 1, false>(*pp, smem);
-    } else if (yl == 1408) {
-      ylaneUtterance<4, 4, 8, 1, false>(*pp, smem);
-    } else if (yl == 1409) {
-      ylaneUtterance<4, 4, 9, 1, false>(*pp, smem);
-    } else if (yl == 1110) {
-      ylaneUtterance<1, 2, 10, 1, false>(*pp, smem);
-    } else if (yl == 1111) {
-      ylaneUtterance<1, 2, 11, 1, false>(*pp, smem);
-    } else if (yl == 1210) {
-      ylaneUtterance<2, 4, 10, 1, false>(*pp, smem);
-    } else if (yl == 1211) {
-      ylaneUtterance<2, 4, 11, 1, false>(*pp, smem);
-    } else if (yl == 1410) {
-      ylaneUtterance<4, 4, 10, 1, false>(*pp, smem);
-    } else if (yl == 1411) {
-      ylaneUtterance<4, 4, 11, 1, false>(*pp, smem);
-    } else if (yl == 1113) {
-      ylaneUtterance<1, 2, 13, 1, false>(*pp, smem);
-    } else if (yl == 1115) {
-      ylaneUtterance<1, 2, 15, 1, false>(*pp, smem);
-    } else if (yl == 1213) {
-      ylaneUtterance<2, 4, 13, 1, false>(*pp, smem);
-    } else if (yl == 1215) {
-      ylaneUtterance<2, 4, 15, 1, false>(*pp, smem);
-    } else {
-      decodeUtterance<0>(*pp, base);
-    }
-    return;
-#endif
-#ifdef FLTX_EMU_TLANE_ONLY /* ... for work on fltx_slane.h's token-LM variant (EMU_EXTRA=-DFLTX_EMU_TLANE_ONLY) */
-    if (sl && pp->tokLm) {
-      if (sl <= 5) {
-        pp->logAdd ? slaneUtterance<5, true, false, false, true>(*pp, smem) : slaneUtterance<5, false, false, false, true>(*pp, smem);
-      } else {
-        pp->logAdd ? slaneUtterance<12, true, false, false, true>(*pp, smem) : slaneUtterance<12, false, false, false, true>(*pp, smem);
-      }
-    } else {
-      decodeUtterance<0>(*pp, base);
-    }
-    return;
-#endif
-#ifdef FLTX_EMU_XLANE_ONLY /* ... for work on fltx_xlane.h (EMU_EXTRA=-DFLTX_EMU_XLANE_ONLY) */
-    if (xl == 2 || xl == 3) {
-      if (pp->logAdd) {
-        xs ? xlaneUtterance<3, 1, false, true>(*pp, smem) : xlaneUtterance<3, 0, false, true>(*pp, smem);
-      } else {
-        xs ? xlaneUtterance<3, 1, false>(*pp, smem) : xlaneUtterance<3, 0, false>(*pp, smem);
-      }
-    } else if (xl == 5 || xl == 10) {
-      if (pp->logAdd) {
-        xs ? xlaneUtterance<10, 1, false, true>(*pp, smem) : xlaneUtterance<10, 0, false, true>(*pp, smem);
-      } else {
-        xs ? xlaneUtterance<10, 1, false>(*pp, smem) : xlaneUtterance<10, 0, false>(*pp, smem);
-      }
-    } else {
-      decodeUtterance<0>(*pp, base);
-    }
-    return;
-#endif
     const bool ft = pp->Kt >= pp->N;
-    if (wl == 5) {
-      wlaneUtterance<5>(*pp, smem);
-    } else if (wl == 8) {
-      wlaneUtterance<8>(*pp, smem);
-    } else if (wl == 10) {
-      wlaneUtterance<10>(*pp, smem);
-    } else if (ss && ts) { /* stream chunks with a token LM */
-      if (ss == 4) {
-        slaneUtterance<4, false, true, false, true>(*pp, smem);
-      } else if (ss == 5) {
-        slaneUtterance<5, false, true, false, true>(*pp, smem);
-      } else {
-        slaneUtterance<10, false, true, false, true>(*pp, smem);
-      }
-    } else if (ss == 4) {
-      slaneUtterance<4, false, true, false>(*pp, smem);
-    } else if (ss == 5) {
-      slaneUtterance<5, false, true, false>(*pp, smem);
-    } else if (ss == 10) {
-      slaneUtterance<10, false, true, false>(*pp, smem);
-    } else if (yl == 100) {
-      ylaneUtterance<1, 2, 0, 0, false>(*pp, smem);
-    } else if (yl == 101) {
-      ylaneUtterance<1, 2, 1, 0, false>(*pp, smem);
-    } else if (yl == 200) {
-      ylaneUtterance<2, 4, 0, 0, false>(*pp, smem);
-    } else if (yl == 201) {
-      ylaneUtterance<2, 4, 1, 0, false>(*pp, smem);
-    } else if (yl == 102) {
-      ylaneUtterance<1, 2, 2, 0, false>(*pp, smem);
-    } else if (yl == 103) {
-      ylaneUtterance<1, 2, 3, 0, false>(*pp, smem);
-    } else if (yl == 202) {
-      ylaneUtterance<2, 4, 2, 0, false>(*pp, smem);
-    } else if (yl == 203) {
-      ylaneUtterance<2, 4, 3, 0, false>(*pp, smem);
-    } else if (yl == 1102) {
-      ylaneUtterance<1, 2, 2, 1, false>(*pp, smem);
-    } else if (yl == 1103) {
-      ylaneUtterance<1, 2, 3, 1, false>(*pp, smem);
-    } else if (yl == 1202) {
-      ylaneUtterance<2, 4, 2, 1, false>(*pp, smem);
-    } else if (yl == 1203) {
-      ylaneUtterance<2, 4, 3, 1, false>(*pp, smem);
-    } else if (yl == 1402) {
-      ylaneUtterance<4, 4, 2, 1, false>(*pp, smem);
-    } else if (yl == 1403) {
-      ylaneUtterance<4, 4, 3, 1, false>(*pp, smem);
-    } else if (yl == 1400) {
-      ylaneUtterance<4, 4, 0, 1, false>(*pp, smem);
-    } else if (yl == 1401) {
-      ylaneUtterance<4, 4, 1, 1, false>(*pp, smem);
-    } else if (yl == 1100) {
-      ylaneUtterance<1, 2, 0, 1, false>(*pp, smem);
-    } else if (yl == 1101) {
-      ylaneUtterance<1, 2, 1, 1, false>(*pp, smem);
-    } else if (yl == 1200) {
-      ylaneUtterance<2, 4, 0, 1, false>(*pp, smem);
-    } else if (yl == 1201) {
-      ylaneUtterance<2, 4, 1, 1, false>(*pp, smem);
-    } else if (yl == 1105) {
-      ylaneUtterance<1, 2, 5, 1, false>(*pp, smem);
-    } else if (yl == 1107) {
-      ylaneUtterance<1, 2, 7, 1, false>(*pp, smem);
-    } else if (yl == 1205) {
-      ylaneUtterance<2, 4, 5, 1, false>(*pp, smem);
-    } else if (yl == 1207) {
-      ylaneUtterance<2, 4, 7, 1, false>(*pp, smem);
-    } else if (yl == 108) {
-      ylaneUtterance<1, 2, 8, 0, false>(*pp, smem);
-    } else if (yl == 109) {
-      ylaneUtterance<1, 2, 9, 0, false>(*pp, smem);
-    } else if (yl == 208) {
-      ylaneUtterance<2, 4, 8, 0, false>(*pp, smem);
-    } else if (yl == 209) {
-      ylaneUtterance<2, 4, 9, 0, false>(*pp, smem);
-    } else if (yl == 1108) {
-      ylaneUtterance<1, 2, 8, 1, false>(*pp, smem);
-    } else if (yl == 1109) {
-      ylaneUtterance<1, 2, 9, 1, false>(*pp, smem);
-    } else if (yl == 1208) {
-      ylaneUtterance<2, 4, 8, 1, false>(*pp, smem);
-    } else if (yl == 1209) {
-      ylaneUtterance<2, 4, 9, 1, false>(*pp, smem);
-    } else if (yl == 1408) {
-      ylaneUtterance<4, 4, 8, 1, false>(*pp, smem);
-    } else if (yl == 1409) {
-      ylaneUtterance<4, 4, 9, 1, false>(*pp, smem);
-    } else if (yl == 110) {
-      ylaneUtterance<1, 2, 10, 0, false>(*pp, smem);
-    } else if (yl == 111) {
-      ylaneUtterance<1, 2, 11, 0, false>(*pp, smem);
-    } else if (yl == 210) {
-      ylaneUtterance<2, 4, 10, 0, false>(*pp, smem);
-    } else if (yl == 211) {
-      ylaneUtterance<2, 4, 11, 0, false>(*pp, smem);
-    } else if (yl == 1110) {
-      ylaneUtterance<1, 2, 10, 1, false>(*pp, smem);
-    } else if (yl == 1111) {
-      ylaneUtterance<1, 2, 11, 1, false>(*pp, smem);
-    } else if (yl == 1210) {
-      ylaneUtterance<2, 4, 10, 1, false>(*pp, smem);
-    } else if (yl == 1211) {
-      ylaneUtterance<2, 4, 11, 1, false>(*pp, smem);
-    } else if (yl == 1410) {
-      ylaneUtterance<4, 4, 10, 1, false>(*pp, smem);
-    } else if (yl == 1411) {
-      ylaneUtterance<4, 4, 11, 1, false>(*pp, smem);
-    } else if (yl == 1113) {
-      ylaneUtterance<1, 2, 13, 1, false>(*pp, smem);
-    } else if (yl == 1115) {
-      ylaneUtterance<1, 2, 15, 1, false>(*pp, smem);
-    } else if (yl == 1213) {
-      ylaneUtterance<2, 4, 13, 1, false>(*pp, smem);
-    } else if (yl == 1215) {
-      ylaneUtterance<2, 4, 15, 1, false>(*pp, smem);
-    } else if (xl == 3) {
-      if (pp->logAdd) {
-        xs ? xlaneUtterance<3, 1, false, true>(*pp, smem) : xlaneUtterance<3, 0, false, true>(*pp, smem);
-      } else {
-        xs ? xlaneUtterance<3, 1, false>(*pp, smem) : xlaneUtterance<3, 0, false>(*pp, smem);
-      }
-    } else if (xl == 5) {
-      if (pp->logAdd) {
-        xs ? xlaneUtterance<5, 1, false, true>(*pp, smem) : xlaneUtterance<5, 0, false, true>(*pp, smem);
-      } else {
-        xs ? xlaneUtterance<5, 1, false>(*pp, smem) : xlaneUtterance<5, 0, false>(*pp, smem);
-      }
-    } else if (xl == 10) {
-      if (pp->logAdd) {
-        xs ? xlaneUtterance<10, 1, false, true>(*pp, smem) : xlaneUtterance<10, 0, false, true>(*pp, smem);
-      } else {
-        xs ? xlaneUtterance<10, 1, false>(*pp, smem) : xlaneUtterance<10, 0, false>(*pp, smem);
-      }
-    } else if (xl == 2) {
-      if (pp->logAdd) {
-        xs ? xlaneUtterance<2, 1, false, true>(*pp, smem) : xlaneUtterance<2, 0, false, true>(*pp, smem);
-      } else {
-        xs ? xlaneUtterance<2, 1, false>(*pp, smem) : xlaneUtterance<2, 0, false>(*pp, smem);
-      }
-    } else if (ml && pp->tokLm) { /* token-level n-gram LM at beams beyond 64 */
-      switch (ml) {
-        case 5211: pp->logAdd ? mlaneUtterance<5, 2, 1, 1, true, true>(*pp, smem) : mlaneUtterance<5, 2, 1, 1, false, true>(*pp, smem); break;
-        case 5422: pp->logAdd ? mlaneUtterance<5, 4, 2, 2, true, true>(*pp, smem) : mlaneUtterance<5, 4, 2, 2, false, true>(*pp, smem); break;
-        case 11211: pp->logAdd ? mlaneUtterance<11, 2, 1, 1, true, true>(*pp, smem) : mlaneUtterance<11, 2, 1, 1, false, true>(*pp, smem); break;
-        case 11422: pp->logAdd ? mlaneUtterance<11, 4, 2, 2, true, true>(*pp, smem) : mlaneUtterance<11, 4, 2, 2, false, true>(*pp, smem); break;
-        default: pp->logAdd ? mlaneUtterance<10, 8, 2, 4, true, true>(*pp, smem) : mlaneUtterance<10, 8, 2, 4, false, true>(*pp, smem); break;
-      }
-    } else if (ml == 4221) {
-      pp->logAdd ? mlaneUtterance<4, 2, 2, 1, true>(*pp, smem) : mlaneUtterance<4, 2, 2, 1, false>(*pp, smem);
-    } else if (ml == 5211) {
-      pp->logAdd ? mlaneUtterance<5, 2, 1, 1, true>(*pp, smem) : mlaneUtterance<5, 2, 1, 1, false>(*pp, smem);
-    } else if (ml == 10221) {
-      pp->logAdd ? mlaneUtterance<10, 2, 2, 1, true>(*pp, smem) : mlaneUtterance<10, 2, 2, 1, false>(*pp, smem);
-    } else if (ml == 4441) {
-      pp->logAdd ? mlaneUtterance<4, 4, 4, 1, true>(*pp, smem) : mlaneUtterance<4, 4, 4, 1, false>(*pp, smem);
-    } else if (ml == 5422) {
-      pp->logAdd ? mlaneUtterance<5, 4, 2, 2, true>(*pp, smem) : mlaneUtterance<5, 4, 2, 2, false>(*pp, smem);
-    } else if (ml == 11422) {
-      pp->logAdd ? mlaneUtterance<11, 4, 2, 2, true>(*pp, smem) : mlaneUtterance<11, 4, 2, 2, false>(*pp, smem);
-    } else if (ml == 10824) {
-      pp->logAdd ? mlaneUtterance<10, 8, 2, 4, true>(*pp, smem) : mlaneUtterance<10, 8, 2, 4, false>(*pp, smem);
-    } else if (sl && pp->tokLm) { /* token-level n-gram LM (TL) */
-      switch (sl) {
-        case 4: pp->logAdd ? slaneUtterance<4, true, false, false, true>(*pp, smem) : slaneUtterance<4, false, false, false, true>(*pp, smem); break;
-        case 5: pp->logAdd ? slaneUtterance<5, true, false, false, true>(*pp, smem) : slaneUtterance<5, false, false, false, true>(*pp, smem); break;
-        case 6: pp->logAdd ? slaneUtterance<6, true, false, false, true>(*pp, smem) : slaneUtterance<6, false, false, false, true>(*pp, smem); break;
-        case 7: pp->logAdd ? slaneUtterance<7, true, false, false, true>(*pp, smem) : slaneUtterance<7, false, false, false, true>(*pp, smem); break;
-        case 10: pp->logAdd ? slaneUtterance<10, true, false, false, true>(*pp, smem) : slaneUtterance<10, false, false, false, true>(*pp, smem); break;
-        default: pp->logAdd ? slaneUtterance<12, true, false, false, true>(*pp, smem) : slaneUtterance<12, false, false, false, true>(*pp, smem); break;
-      }
-    } else if (sl == 4) {
-      pp->logAdd ? slaneUtterance<4, true, false, false>(*pp, smem) : slaneUtterance<4, false, false, false>(*pp, smem);
-    } else if (sl == 5) {
-      pp->logAdd ? slaneUtterance<5, true, false, false>(*pp, smem) : slaneUtterance<5, false, false, false>(*pp, smem);
-    } else if (sl == 6) {
-      pp->logAdd ? slaneUtterance<6, true, false, false>(*pp, smem) : slaneUtterance<6, false, false, false>(*pp, smem);
-    } else if (sl == 7) {
-      pp->logAdd ? slaneUtterance<7, true, false, false>(*pp, smem) : slaneUtterance<7, false, false, false>(*pp, smem);
-    } else if (sl == 10) {
-      pp->logAdd ? slaneUtterance<10, true, false, false>(*pp, smem) : slaneUtterance<10, false, false, false>(*pp, smem);
-    } else if (sl == 12) {
-      pp->logAdd ? slaneUtterance<12, true, false, false>(*pp, smem) : slaneUtterance<12, false, false, false>(*pp, smem);
-
-    } else if (gt == 4) {
+    if (gt == 4) {
       if (pp->logAdd) {
         ft ? decodeUtterance<1, 4, true, true>(*pp, base) : decodeUtterance<1, 4, true, false>(*pp, base);
       } else {

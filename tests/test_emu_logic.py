@@ -539,3 +539,10 @@ def _deferred_look(sess, golden, T_wp):
 
 def test_emulated_deferred_status_look(emu_session, golden):
     _deferred_look(emu_session, golden, 12)
+
+
+def test_emulated_engine_choices_match_the_table(emu_session):
+    """engine, geometry, threads and workspace of every configuration of tests/engine_choices.py as committed"""
+    import engine_choices
+    diff = engine_choices.differences(emu_session)
+    assert not diff, "%d differences, first: %s" % (len(diff), diff[:10])

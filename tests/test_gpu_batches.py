@@ -830,3 +830,10 @@ def test_word_piece_row_without_a_defined_token_beam(gpu_session, oracle_lib):
 def test_deferred_status_look(gpu_session, golden):
     import test_emu_logic
     test_emu_logic._deferred_look(gpu_session, golden, 40)
+
+
+def test_engine_choices_match_the_table(gpu_session):
+    """the HIP library chooses as the emulator does (tests/engine_choices.py, tests/golden/engine_choices.json)"""
+    import engine_choices
+    diff = engine_choices.differences(gpu_session)
+    assert not diff, "%d differences, first: %s" % (len(diff), diff[:10])

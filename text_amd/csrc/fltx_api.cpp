@@ -28,6 +28,7 @@
 
 #include "fltx.h"
 #include "fltx_kernel_entry.h"
+#include "fltx_engines.h"
 
 using namespace fltx;
 
@@ -1585,6 +1586,8 @@ int fltx_decoder_get(fltx_decoder* d, const char* key, int64_t* value) {
     *value = d->CAP2;
   } else if (!strcmp(key, "items")) {
     *value = d->itemCap;
+  } else if (!strcmp(key, "ws_bytes")) { /* d->wsBytes: the workspace bytes of one utterance that prepare() sized */
+    *value = (int64_t)d->wsBytes;
   } else {
     return fail(FLTX_ERR_INVALID, "fltx_decoder_get: unknown key '%s'", key);
   }
@@ -1760,13 +1763,30 @@ namespace {
 
 /* geometry + buffers for B streams of up to maxFrames frames (plus seed and
  * decodeEnd slots) */
-/* fltx_mlane.h geometries that are compiled (fltx_instances.h, FLTX_MLANE_SET); "mlane_geo" = row */
+/* the compiled geometries of the lane engines (fltx_engines.h) */
+struct LaneGeo {
+  int threads, gt;
+};
 struct MlaneGeo {
   int threads, gt, ng, gpw, spw;
 };
-static const MlaneGeo kMlaneGeo[] = {{640, 4, 2, 2, 1}, {960, 5, 2, 1, 1}, {640, 10, 2, 2, 1}, {768, 4, 4, 4, 1},
-                                     {960, 5, 4, 2, 2}, {960, 11, 4, 2, 2}, {960, 10, 8, 2, 4}};
+#define FLTX_GEO2(WW, GG) {WW, GG},
+#define FLTX_GEO5(WW, GG, NG, GPW, SPW) {WW, GG, NG, GPW, SPW},
+static const LaneGeo kSlaneGeo[] = {FLTX_SLANE_GEOS(FLTX_GEO2)};
+static const LaneGeo kSstreamGeo[] = {FLTX_SSTREAM_GEOS(FLTX_GEO2)};
+static const LaneGeo kWlaneGeo[] = {FLTX_WLANE_GEOS(FLTX_GEO2)};
+static const LaneGeo kXlaneGeo[] = {FLTX_XLANE_GEOS(FLTX_GEO2)};
+static const MlaneGeo kMlaneGeo[] = {FLTX_MLANE_GEOS(FLTX_GEO5)}; /* "mlane_geo" = row */
+static const MlaneGeo kTmlaneGeo[] = {FLTX_TMLANE_GEOS(FLTX_GEO5)};
+#undef FLTX_GEO2
+#undef FLTX_GEO5
 constexpr int kMlaneGeoCount = (int)(sizeof(kMlaneGeo) / sizeof(kMlaneGeo[0]));
+constexpr int kSlaneGeoCount = (int)(sizeof(kSlaneGeo) / sizeof(kSlaneGeo[0]));
+/* kSlaneGeo rows, fastest first (C2: 1.95, 2.11, 2.14 ms ...); more utterances than CUs: 512 threads (104 VGPRs: four
+ * waves per SIMD) let two utterances share a CU -- C2 at 512 utterances: 162.7 M frames/s against 119.3 M with nine
+ * waves each */
+static const int kSlaneOrderOne[kSlaneGeoCount] = {4, 3, 2, 1, 0, 5, 6, 7};
+static const int kSlaneOrderTwo[kSlaneGeoCount] = {3, 2, 1, 4, 0, 5, 6, 7};
 
 int engineOf(const fltx_decoder* d) {
   return d->ylane ? 6 : d->xlane ? 5 : (d->slane ? 4 : (d->lane ? 3 : (d->lean ? 2 : (d->dense ? 1 : 0))));
@@ -1842,6 +1862,10 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
   }
   /* candidate capacity */
   const int nTok = std::min(d->opt.beam_size_token, N);
+  /* tokens a lane engine lists per frame (CTC with the whole token set: the blank is not listed) */
+  const int nList = nTok - ((d->opt.criterion == FLTX_CRITERION_CTC && d->opt.beam_size_token >= N) ? 1 : 0);
+  /* (sil and blank are in range: checked above) */
+  const bool optionsOk = d->opt.beam_threshold >= 0.0;
   /* lexicon-free frames merge through the dense (hash-free) path: one slot per
    * (LM state, token) group plus one per orphan repeat; the hash is then only
    * used by decodeEnd (<= K candidates) */
@@ -1877,25 +1901,18 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
   /* lane = LM state decode (fltx_slane.h): offline lexicon-free + ZeroLM max-merge, beam and
    * tokens within one wave's lanes; the history rows are its LM-state memo (23-bit ids) */
   d->slane = 0;
+  const int* slaneOrder = B > d->ctx->numCUs ? kSlaneOrderTwo : kSlaneOrderOne;
   if (d->lane && !d->noSlane && d->offlineCall && !d->keepScores && !forceWorstCaseCap &&
-      d->opt.beam_threshold >= 0.0 && d->sil >= 0 && d->sil < N &&
-      (d->opt.criterion != FLTX_CRITERION_CTC || (d->blank >= 0 && d->blank < N)) &&
-      (int64_t)K * (maxT + 2) < (1 << 23) - 1) {
-    /* (threads, list positions per token wave) pairs that are compiled (fltx_instances.h); two of the
-     * waves do not evaluate tokens (own groups of the lanes / row staging and housekeeping) */
-    static const int geoOne[][2] = {{576, 4}, {512, 5}, {448, 6}, {384, 7}, {320, 10}, {640, 4}, {512, 12}, {576, 10}}; /* fastest first (C2: 1.95, 2.11, 2.14 ms ...) */
-    /* more utterances than CUs: 512 threads (104 VGPRs: four waves per SIMD) let two utterances share a CU --
-     * C2 at 512 utterances: 162.7 M frames/s against 119.3 M with nine waves each */
-    static const int geoTwo[][2] = {{512, 5}, {448, 6}, {384, 7}, {576, 4}, {320, 10}, {640, 4}, {512, 12}, {576, 10}};
-    const auto& geo = B > d->ctx->numCUs ? geoTwo : geoOne;
-    const int nList = nTok - ((d->opt.criterion == FLTX_CRITERION_CTC && d->opt.beam_size_token >= N) ? 1 : 0);
-    for (const auto& g : geo) {
-      if ((d->userThreads && d->threads != g[0]) || (d->slaneThreads && d->slaneThreads != g[0])) {
+      optionsOk && (int64_t)K * (maxT + 2) < (1 << 23) - 1) {
+    for (int oi = 0; oi < kSlaneGeoCount; ++oi) {
+      const int gi = slaneOrder[oi];
+      const LaneGeo& g = kSlaneGeo[gi];
+      if ((d->userThreads && d->threads != g.threads) || (d->slaneThreads && d->slaneThreads != g.threads)) {
         continue;
       }
-      if (nList <= g[1] * (g[0] / 64 - 2)) {
-        d->slane = g[1];
-        d->threads = g[0];
+      if (nList <= g.gt * (g.threads / 64 - 2)) {
+        d->slane = g.gt;
+        d->threads = g.threads;
         break;
       }
     }
@@ -1923,29 +1940,22 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
   }
   if (tab && d->kind == FLTX_DECODER_LEXFREE && !d->noSlane && !d->noTlane && !d->genericAsked &&
       !d->noDense && d->offlineCall && !d->keepScores && !forceWorstCaseCap && !d->forceGlobalWs && K <= 64 &&
-      d->opt.beam_threshold >= 0.0 && d->sil >= 0 && d->sil < N &&
-      (d->opt.criterion != FLTX_CRITERION_CTC || (d->blank >= 0 && d->blank < N)) &&
-      (int64_t)K * (maxT + 2) < (1 << 23) - 1) {
-    {
-      static const int geoOne[][2] = {{576, 4}, {512, 5}, {448, 6}, {384, 7}, {320, 10}, {640, 4}, {512, 12}, {576, 10}};
-      static const int geoTwo[][2] = {{512, 5}, {448, 6}, {384, 7}, {576, 4}, {320, 10}, {640, 4}, {512, 12}, {576, 10}};
-      const auto& geo = B > d->ctx->numCUs ? geoTwo : geoOne;
-      const int nList = nTok - ((d->opt.criterion == FLTX_CRITERION_CTC && d->opt.beam_size_token >= N) ? 1 : 0);
-      for (const auto& g : geo) {
-        if ((d->userThreads && d->threads != g[0]) || (d->slaneThreads && d->slaneThreads != g[0])) {
-          continue;
-        }
-        if (nList <= g[1] * (g[0] / 64 - 2)) {
-          d->slane = g[1];
-          d->tlane = 1;
-          /* the re-entry memos in LDS: 4 096 edges + 2 048 child masks (75 KB: two workgroups fit a CU) when the batch
-           * has more utterances than CUs, twice as many of both (131 KB) when a workgroup has the CU to itself */
-          const bool shareCu = B > d->ctx->numCUs || (d->deferCheck && g[0] == 512); /* (defer_check: the caller keeps two batches in flight) */
-          d->tlEdgeSlots = shareCu ? 4096 : 8192;
-          d->tlMaskSlots = shareCu ? 2048 : 4096;
-          d->threads = g[0];
-          break;
-        }
+      optionsOk && (int64_t)K * (maxT + 2) < (1 << 23) - 1) {
+    for (int oi = 0; oi < kSlaneGeoCount; ++oi) {
+      const LaneGeo& g = kSlaneGeo[slaneOrder[oi]];
+      if ((d->userThreads && d->threads != g.threads) || (d->slaneThreads && d->slaneThreads != g.threads)) {
+        continue;
+      }
+      if (nList <= g.gt * (g.threads / 64 - 2)) {
+        d->slane = g.gt;
+        d->tlane = 1;
+        /* the re-entry memos in LDS: 4 096 edges + 2 048 child masks (75 KB: two workgroups fit a CU) when the batch
+         * has more utterances than CUs, twice as many of both (131 KB) when a workgroup has the CU to itself */
+        const bool shareCu = B > d->ctx->numCUs || (d->deferCheck && g.threads == 512); /* (defer_check: the caller keeps two batches in flight) */
+        d->tlEdgeSlots = shareCu ? 4096 : 8192;
+        d->tlMaskSlots = shareCu ? 2048 : 4096;
+        d->threads = g.threads;
+        break;
       }
     }
   }
@@ -1954,19 +1964,16 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
   d->wlane = 0;
   if (d->kind == FLTX_DECODER_LEXFREE && !d->noSlane && !d->noWlane && !d->genericAsked && d->offlineCall && !d->keepScores &&
       !forceWorstCaseCap && !d->forceGlobalWs && !d->opt.log_add && d->lm->kind == 0 && !d->isLmToken && N > 64 &&
-      N <= kWlMaxN && K <= 64 && nTok <= 64 && d->opt.beam_threshold >= 0.0 && d->sil >= 0 && d->sil < N &&
-      (d->opt.criterion != FLTX_CRITERION_CTC || (d->blank >= 0 && d->blank < N)) &&
-      (int64_t)K * (maxT + 2) < (1 << 23) - 1) {
-    static const int geoW[][2] = {{576, 5}, {576, 8}, {576, 10}};
-    for (const auto& g : geoW) {
-      if (d->userThreads && d->threads != g[0]) {
+      N <= kWlMaxN && K <= 64 && nTok <= 64 && optionsOk && (int64_t)K * (maxT + 2) < (1 << 23) - 1) {
+    for (const LaneGeo& g : kWlaneGeo) {
+      if (d->userThreads && d->threads != g.threads) {
         continue;
       }
-      if (nTok <= g[1] * (g[0] / 64 - 2)) {
-        d->slane = g[1];
+      if (nTok <= g.gt * (g.threads / 64 - 2)) {
+        d->slane = g.gt;
         d->wlane = 1;
         d->wlMaxT = maxT;
-        d->threads = g[0];
+        d->threads = g.threads;
         break;
       }
     }
@@ -1976,10 +1983,7 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
   d->mlaneNG = 0;
   if ((!d->slane || d->userLaneGroups > 1) && d->lean && !d->noSlane && d->userLaneGroups >= 0 && d->offlineCall && !d->keepScores &&
       !forceWorstCaseCap && K <= 64 * kMlMaxGroups && (K > 64 || d->userLaneGroups > 1) && N <= 64 &&
-      d->opt.beam_threshold >= 0.0 && d->sil >= 0 && d->sil < N &&
-      (d->opt.criterion != FLTX_CRITERION_CTC || (d->blank >= 0 && d->blank < N)) &&
-      (int64_t)K * (maxT + 2) < (1ll << 31) - 1) {
-    const int nList = nTok - ((d->opt.criterion == FLTX_CRITERION_CTC && d->opt.beam_size_token >= N) ? 1 : 0);
+      optionsOk && (int64_t)K * (maxT + 2) < (1ll << 31) - 1) {
     const int needNG = std::max((K + 63) / 64, d->userLaneGroups);
     /* fastest first per group count (C2 shape, profiles/r04: beam 100 3.17 ms on row 1 against 3.23 on row 0, beam 200
      * 5.79 on row 4 against 6.21 on row 3; the wide rows 2 / 5 spill registers and are for token lists beyond 30) */
@@ -2006,13 +2010,9 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
    * of up to 64 at beams up to 256, of up to 30 beyond (the five geometries compiled for it) */
   if (tab && !d->slane && d->kind == FLTX_DECODER_LEXFREE && !d->noSlane && !d->noTlane && !d->genericAsked && !d->noDense &&
       d->userLaneGroups >= 0 && d->offlineCall && !d->keepScores && !forceWorstCaseCap && !d->forceGlobalWs &&
-      K > 64 && K <= 64 * kMlMaxGroups && d->opt.beam_threshold >= 0.0 && d->sil >= 0 && d->sil < N &&
-      (d->opt.criterion != FLTX_CRITERION_CTC || (d->blank >= 0 && d->blank < N)) &&
-      (int64_t)K * (maxT + 2) < (1ll << 27)) {
-    const int nList = nTok - ((d->opt.criterion == FLTX_CRITERION_CTC && d->opt.beam_size_token >= N) ? 1 : 0);
+      K > 64 && K <= 64 * kMlMaxGroups && optionsOk && (int64_t)K * (maxT + 2) < (1ll << 27)) {
     const int needNG = std::max((K + 63) / 64, d->userLaneGroups);
-    static const MlaneGeo geoT[] = {{960, 5, 2, 1, 1}, {960, 11, 2, 1, 1}, {960, 5, 4, 2, 2}, {960, 11, 4, 2, 2}, {960, 10, 8, 2, 4}};
-    for (const MlaneGeo& g : geoT) {
+    for (const MlaneGeo& g : kTmlaneGeo) {
       const int nBlk = (g.threads / 64 - g.ng / g.spw - 1) / (g.ng / g.gpw);
       if (g.ng >= needNG && nList <= g.gt * nBlk && (!d->userThreads || d->threads == g.threads)) {
         uint32_t slots = 1024;
@@ -2036,18 +2036,18 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
   /* ... and the frames of a stream's decodeStep chunks on the same engine (the parked beam, the (parent, token) ->
    * id tables and the history rows keep the lane-per-slot engine's format) */
   d->sstream = 0;
-  if (d->lane && !d->noSlane && !d->noSstream && !d->offlineCall && d->keepScores && !d->opt.log_add &&
-      d->opt.beam_threshold >= 0.0 && d->sil >= 0 && d->sil < N &&
-      (d->opt.criterion != FLTX_CRITERION_CTC || (d->blank >= 0 && d->blank < N))) {
-    static const int geoS[][2] = {{576, 4}, {512, 5}, {576, 10}};
-    const int nList = nTok - ((d->opt.criterion == FLTX_CRITERION_CTC && d->opt.beam_size_token >= N) ? 1 : 0);
-    for (const auto& g : geoS) {
-      if (nList <= g[1] * (g[0] / 64 - 2)) {
-        d->sstream = g[1];
-        d->sstreamThreads = g[0];
-        break;
+  const auto chooseSstream = [&]() {
+    for (const LaneGeo& g : kSstreamGeo) {
+      if (nList <= g.gt * (g.threads / 64 - 2)) {
+        d->sstream = g.gt;
+        d->sstreamThreads = g.threads;
+        return true;
       }
     }
+    return false;
+  };
+  if (d->lane && !d->noSlane && !d->noSstream && !d->offlineCall && d->keepScores && !d->opt.log_add && optionsOk) {
+    chooseSstream();
   }
   /* lane = (LM state, trie node) decode (fltx_xlane.h): offline LexiconDecoder + ZeroLM over a lexicon
    * without LM scores, CTC, max-merge or logAdd (round 5), one word per spelling, every word ending in sil, no <unk> */
@@ -2057,16 +2057,14 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
       !forceWorstCaseCap && !d->forceGlobalWs && d->lm->kind == 0 && !d->isLmToken && d->trie && d->trie->xOk &&
       !d->trie->xMulti && d->trie->xZeroSmear && d->trie->xEndTok == d->sil && d->sil != d->blank &&
       d->opt.criterion == FLTX_CRITERION_CTC && !(d->opt.unk_score > -std::numeric_limits<double>::infinity()) &&
-      K <= 64 && N <= 64 && d->opt.beam_threshold >= 0.0 && d->sil >= 0 && d->sil < N && d->blank >= 0 &&
-      d->blank < N && (int64_t)K * (maxT + 2) < (1 << 23) - 1) {
-    static const int geo[][2] = {{512, 2}, {512, 3}, {640, 2}, {576, 5}, {640, 10}};
-    for (const auto& g : geo) {
-      if ((d->userThreads && d->threads != g[0]) || (d->slaneThreads && d->slaneThreads != g[0])) {
+      K <= 64 && N <= 64 && optionsOk && (int64_t)K * (maxT + 2) < (1 << 23) - 1) {
+    for (const LaneGeo& g : kXlaneGeo) {
+      if ((d->userThreads && d->threads != g.threads) || (d->slaneThreads && d->slaneThreads != g.threads)) {
         continue;
       }
-      if (nTok <= g[1] * (g[0] / 64 - 3)) {
-        d->xlane = g[1];
-        d->threads = g[0];
+      if (nTok <= g.gt * (g.threads / 64 - 3)) {
+        d->xlane = g.gt;
+        d->threads = g.threads;
         /* more utterances than CUs: the LM-state memo moves to HBM, 28 KB of LDS and 81 VGPRs let several
          * workgroups share a CU (see the lane engine with LM terms below) */
         d->yshare = (d->userYshare >= 0 ? d->userYshare != 0 : B > d->ctx->numCUs) ? 1 : 0;
@@ -2086,10 +2084,8 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
        * 1 024-thread workgroup leaves a wave, and the spills made it 2.3 x slower than the generic engine on the
        * reference's test lexicon at beam 256) */
       (!d->trie->xMulti || (d->lm->kind == 1 && K <= 128 && d->userYlaneGroups <= 2)) && d->trie->xEndTok == d->sil &&
-      (d->opt.criterion == FLTX_CRITERION_CTC ? (d->sil != d->blank && d->blank >= 0 && d->blank < N)
-                                               : (d->nTrans == N * N && !d->noYlaneAsg)) &&
-      !(d->opt.unk_score > -std::numeric_limits<double>::infinity()) && K <= 256 && N <= 64 &&
-      d->opt.beam_threshold >= 0.0 && d->sil >= 0 && d->sil < N) {
+      (d->opt.criterion == FLTX_CRITERION_CTC ? d->sil != d->blank : (d->nTrans == N * N && !d->noYlaneAsg)) &&
+      !(d->opt.unk_score > -std::numeric_limits<double>::infinity()) && K <= 256 && N <= 64 && optionsOk) {
     const int ng = std::max(K <= 64 ? 1 : (K <= 128 ? 2 : 4), d->userYlaneGroups);
     /* More utterances than CUs: the geometry of which two workgroups fit a CU (512 threads, <= 128
      * VGPRs, 77 KB of LDS: the LM-state memo moves to HBM) -- one utterance's waits are the other's
@@ -2128,20 +2124,6 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
                    (d->trie->xMulti ? 4 : 0) | (d->opt.log_add ? 8 : 0);
       d->threads = threads;
       d->xlane = 0;
-      if (d->lm->kind == 1 && (d->xlmwordTrie != d->trie || d->xlmwordLm != d->lm)) {
-        const std::vector<int32_t>& el = d->trie->xEndHost;
-        std::vector<int32_t> w(el.size());
-        for (size_t i = 0; i < el.size(); ++i) { /* KenLM::score: usrToLmIdxMap_, unknown words -> <unk> */
-          w[i] = el[i] < 0 ? -1 : ((size_t)el[i] < d->lm->hUsr.size() ? d->lm->hUsr[(size_t)el[i]] : d->lm->unk);
-        }
-        if (d->xlmword.ensure(sizeof(int32_t) * std::max<size_t>(1, w.size()), d->ctx->stream, false) ||
-            devCopyH2D(d->xlmword.p, w.data(), sizeof(int32_t) * w.size(), d->ctx->stream)) {
-          return fail(FLTX_ERR_OOM, "LM word ids of the lexicon: upload failed");
-        }
-        devSync(d->ctx->stream); /* (w is a local) */
-        d->xlmwordTrie = d->trie;
-        d->xlmwordLm = d->lm;
-      }
     }
   }
   /* ... and the chunks of a stream with a token-level n-gram LM (slaneUtterance<.., ST, TL>): begin / end / prune /
@@ -2149,25 +2131,14 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
    * and the chunk's frames take their state ids from that engine's (parent id, edge) -> id table */
   d->tstream = 0;
   if (d->tokLm && d->kind == FLTX_DECODER_LEXFREE && !d->noSlane && !d->noTlane && !d->noSstream && !d->genericAsked &&
-      !d->offlineCall && d->keepScores && !d->opt.log_add && K <= 64 && d->recycle && d->opt.beam_threshold >= 0.0 && d->sil >= 0 && d->sil < N &&
-      (d->opt.criterion != FLTX_CRITERION_CTC || (d->blank >= 0 && d->blank < N))) {
-    static const int geoS[][2] = {{576, 4}, {512, 5}, {576, 10}};
-    const int nList = nTok - ((d->opt.criterion == FLTX_CRITERION_CTC && d->opt.beam_size_token >= N) ? 1 : 0);
-    for (const auto& g : geoS) {
-      if (nList <= g[1] * (g[0] / 64 - 2)) {
-        d->sstream = g[1];
-        d->sstreamThreads = g[0];
-        d->tstream = 1;
-        break;
-      }
-    }
+      !d->offlineCall && d->keepScores && !d->opt.log_add && K <= 64 && d->recycle && optionsOk && chooseSstream()) {
+    d->tstream = 1;
   }
   { /* which eligibility terms kept this call off the lane engines (fltx_decoder_get "why_not_lane") */
     int64_t why = 0;
     if (!(d->slane || d->xlane || d->ylane || d->sstream)) {
       const bool lexi = d->kind == FLTX_DECODER_LEXICON;
       const bool unkOn = d->opt.unk_score > -std::numeric_limits<double>::infinity();
-      const int nListAll = nTok - ((d->opt.criterion == FLTX_CRITERION_CTC && d->opt.beam_size_token >= N) ? 1 : 0);
       why |= (N > 64 && (lexi || N > kWlMaxN || nTok > 64)) ? FLTX_WHY_TOKENS : 0; /* (lexicon-free: the token BEAM has to fit, fltx_wlane.h) */
       why |= (lexi ? K > ((d->trie && d->trie->xMulti) ? 128 : 256) : K > 64 * kMlMaxGroups) ? FLTX_WHY_BEAM : 0;
       why |= (!d->offlineCall && (lexi || d->opt.log_add || d->lm->kind == 1)) ? FLTX_WHY_STREAM : 0;
@@ -2182,14 +2153,13 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
       why |= (lexi && unkOn) ? FLTX_WHY_UNK : 0;
       why |= (lexi && d->trie && (!d->trie->xOk || (d->trie->xMulti && d->lm->kind == 0))) ? FLTX_WHY_TRIE_SHAPE : 0;
       why |= (lexi && d->trie && d->trie->xOk && (d->trie->xEndTok != d->sil || d->sil == d->blank)) ? FLTX_WHY_WORD_END : 0;
-      why |= (!(d->opt.beam_threshold >= 0.0) || d->sil < 0 || d->sil >= N ||
-              (d->opt.criterion == FLTX_CRITERION_CTC && (d->blank < 0 || d->blank >= N))) ? FLTX_WHY_OPTIONS : 0;
+      why |= !optionsOk ? FLTX_WHY_OPTIONS : 0;
       why |= ((int64_t)K * (maxT + 2) >= (lexi || K <= 64 ? (1ll << 23) - 1 : (1ll << 31) - 1)) ? FLTX_WHY_LENGTH : 0;
       why |= (d->noSlane || d->noXlane || d->noYlane || d->genericAsked || d->forceGlobalWs || d->noLean || d->noDense ||
               d->userLaneGroups < 0 || forceWorstCaseCap || (d->offlineCall && d->keepScores) ||
               (!lexi && N > 64 && d->noWlane) || (!lexi && d->lm->kind == 1 && d->noTlane)) ? FLTX_WHY_SWITCHED_OFF : 0;
       why |= (!lexi && N > 64 && d->opt.log_add) ? FLTX_WHY_LOGADD : 0; /* (fltx_wlane.h has no logAdd variant) */
-      why |= (!lexi && nListAll > 70) ? FLTX_WHY_GEOMETRY : 0;
+      why |= (!lexi && nList > 70) ? FLTX_WHY_GEOMETRY : 0;
       if (!why) {
         why = FLTX_WHY_GEOMETRY; /* (no compiled geometry covers this token list / thread count) */
       }
@@ -2422,6 +2392,20 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
     d->cutRecompute = 0;
   }
   /* buffers */
+  if (d->ylane && d->lm->kind == 1 && (d->xlmwordTrie != d->trie || d->xlmwordLm != d->lm)) { /* LM word ids of the lexicon's words */
+    const std::vector<int32_t>& el = d->trie->xEndHost;
+    std::vector<int32_t> w(el.size());
+    for (size_t i = 0; i < el.size(); ++i) { /* KenLM::score: usrToLmIdxMap_, unknown words -> <unk> */
+      w[i] = el[i] < 0 ? -1 : ((size_t)el[i] < d->lm->hUsr.size() ? d->lm->hUsr[(size_t)el[i]] : d->lm->unk);
+    }
+    if (d->xlmword.ensure(sizeof(int32_t) * std::max<size_t>(1, w.size()), st, false) ||
+        devCopyH2D(d->xlmword.p, w.data(), sizeof(int32_t) * w.size(), st)) {
+      return fail(FLTX_ERR_OOM, "LM word ids of the lexicon: upload failed");
+    }
+    devSync(st); /* (w is a local) */
+    d->xlmwordTrie = d->trie;
+    d->xlmwordLm = d->lm;
+  }
   bool grewTab = false;
   int rc = 0;
   rc |= d->histOffD.ensure(sizeof(int64_t) * (B + 1), st, false);
@@ -2643,8 +2627,164 @@ void fillParams(fltx_decoder* d, DecodeParams& P) {
   }
 }
 
-int launchDecode(fltx_decoder* d, const DecodeParams& P) {
+/* The lane-engine kernels, one entry per (family, variant, geometry) of fltx_engines.h.  The emulator build maps the
+ * same entries to the host functions the kernels are made of (tests/emu/fltx_emu_launch.inc). */
+enum LaneFamily { kGeneric, kSlane, kTlane, kSstream, kTstream, kMlane, kTmlane, kWlane, kXlane, kYlane };
+enum { kVarLA = 1, kVarProf = 2, kVarHM = 4 }; /* logAdd merges, phase clocks, memo in HBM */
+struct LaneKey {
+  int fam, var, threads, g[4];
+};
+#ifdef FLTX_EMU
+using LaneFn = void (*)(const DecodeParams&, char*);
+#define FLTX_LK(FAM, VAR, WW, A, B, C, D, KERNEL, EMU) {{FAM, VAR, WW, {A, B, C, D}}, EMU},
+#else
+using LaneFn = const void*;
+#define FLTX_LK(FAM, VAR, WW, A, B, C, D, KERNEL, EMU) {{FAM, VAR, WW, {A, B, C, D}}, (const void*)KERNEL},
+#endif
+struct LaneKernel {
+  LaneKey key;
+  LaneFn fn;
+};
+#define FLTX_LK_SLANE(WW, GG)                                                                                       \
+  FLTX_LK(kSlane, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_slane<WW, GG, false, false>), (slaneUtterance<GG, false, false, false>)) \
+  FLTX_LK(kSlane, kVarProf, WW, GG, 0, 0, 0, (fltx_decode_kernel_slane<WW, GG, false, true>), (slaneUtterance<GG, false, false, false>)) \
+  FLTX_LK(kSlane, kVarLA, WW, GG, 0, 0, 0, (fltx_decode_kernel_slane<WW, GG, true, false>), (slaneUtterance<GG, true, false, false>)) \
+  FLTX_LK(kTlane, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_tlane<WW, GG, false>), (slaneUtterance<GG, false, false, false, true>)) \
+  FLTX_LK(kTlane, kVarLA, WW, GG, 0, 0, 0, (fltx_decode_kernel_tlane<WW, GG, true>), (slaneUtterance<GG, true, false, false, true>))
+#define FLTX_LK_TLANE_PROF(WW, GG) \
+  FLTX_LK(kTlane, kVarProf, WW, GG, 0, 0, 0, (fltx_decode_kernel_tlane<WW, GG, false, true>), (slaneUtterance<GG, false, false, false, true>))
+#define FLTX_LK_SSTREAM(WW, GG)                                                                                     \
+  FLTX_LK(kSstream, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_slane_stream<WW, GG>), (slaneUtterance<GG, false, true, false>)) \
+  FLTX_LK(kTstream, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_tlane_stream<WW, GG>), (slaneUtterance<GG, false, true, false, true>))
+#define FLTX_LK_MLANE(WW, GG, NG, GPW, SPW)                                                                        \
+  FLTX_LK(kMlane, 0, WW, GG, NG, GPW, SPW, (fltx_decode_kernel_mlane<WW, GG, NG, GPW, SPW, false>), (mlaneUtterance<GG, NG, GPW, SPW, false>)) \
+  FLTX_LK(kMlane, kVarLA, WW, GG, NG, GPW, SPW, (fltx_decode_kernel_mlane<WW, GG, NG, GPW, SPW, true>), (mlaneUtterance<GG, NG, GPW, SPW, true>))
+#define FLTX_LK_TMLANE(WW, GG, NG, GPW, SPW)                                                                       \
+  FLTX_LK(kTmlane, 0, WW, GG, NG, GPW, SPW, (fltx_decode_kernel_tmlane<WW, GG, NG, GPW, SPW, false>), (mlaneUtterance<GG, NG, GPW, SPW, false, true>)) \
+  FLTX_LK(kTmlane, kVarLA, WW, GG, NG, GPW, SPW, (fltx_decode_kernel_tmlane<WW, GG, NG, GPW, SPW, true>), (mlaneUtterance<GG, NG, GPW, SPW, true, true>))
+#define FLTX_LK_WLANE(WW, GG) FLTX_LK(kWlane, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_wlane<WW, GG>), (wlaneUtterance<GG>))
+#define FLTX_LK_XLANE(WW, GG)                                                                                       \
+  FLTX_LK(kXlane, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane<WW, GG, 0, false>), (xlaneUtterance<GG, 0, false>))  \
+  FLTX_LK(kXlane, kVarProf, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane<WW, GG, 0, true>), (xlaneUtterance<GG, 0, false>)) \
+  FLTX_LK(kXlane, kVarHM, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane<WW, GG, 1, false>), (xlaneUtterance<GG, 1, false>)) \
+  FLTX_LK(kXlane, kVarLA, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane<WW, GG, 0, false, true>), (xlaneUtterance<GG, 0, false, true>)) \
+  FLTX_LK(kXlane, kVarLA | kVarHM, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane<WW, GG, 1, false, true>), (xlaneUtterance<GG, 1, false, true>))
+#define FLTX_LK_YLANE(WW, NG, RR, HM, LMK) \
+  FLTX_LK(kYlane, HM ? kVarHM : 0, WW, NG, RR, LMK, 0, (fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, false>), (ylaneUtterance<NG, RR, LMK, HM, false>))
+#define FLTX_LK_YLANE_PROF(WW, NG, RR, HM, LMK) \
+  FLTX_LK(kYlane, (HM ? kVarHM : 0) | kVarProf, WW, NG, RR, LMK, 0, (fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, true>), (ylaneUtterance<NG, RR, LMK, HM, false>))
+static const LaneKernel kLaneKernels[] = {
+    FLTX_SLANE_GEOS(FLTX_LK_SLANE) FLTX_TLANE_PROF_GEOS(FLTX_LK_TLANE_PROF) FLTX_SSTREAM_GEOS(FLTX_LK_SSTREAM)
+    FLTX_MLANE_GEOS(FLTX_LK_MLANE) FLTX_TMLANE_GEOS(FLTX_LK_TMLANE) FLTX_WLANE_GEOS(FLTX_LK_WLANE)
+    FLTX_XLANE_GEOS(FLTX_LK_XLANE) FLTX_YLANE_KERNELS(FLTX_LK_YLANE) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_LK_YLANE_PROF)};
+#undef FLTX_LK
+#undef FLTX_LK_SLANE
+#undef FLTX_LK_TLANE_PROF
+#undef FLTX_LK_SSTREAM
+#undef FLTX_LK_MLANE
+#undef FLTX_LK_TMLANE
+#undef FLTX_LK_WLANE
+#undef FLTX_LK_XLANE
+#undef FLTX_LK_YLANE
+#undef FLTX_LK_YLANE_PROF
+
+/* what launchDecode runs: the lane engine's family, variant and geometry (kGeneric: the per-W kernels) */
+LaneKey laneKeyOf(const fltx_decoder* d) {
   const int W = d->sstreamLaunch ? d->sstreamThreads : d->threads;
+  const int la = d->opt.log_add ? kVarLA : 0, prof = d->profile ? kVarProf : 0, hm = d->yshare ? kVarHM : 0;
+  if (d->sstreamLaunch) {
+    return {d->tstream ? kTstream : kSstream, prof, W, {d->sstream, 0, 0, 0}};
+  } else if (d->ylane) { /* (logAdd: LMK bit 3) */
+    return {kYlane, prof | hm, W, {d->ylane, d->ylaneRounds, d->ylaneLm, 0}};
+  } else if (d->xlane) {
+    return {kXlane, la | prof | hm, W, {d->xlane, 0, 0, 0}};
+  } else if (d->slane && d->mlaneNG > 1) {
+    return {d->tlane ? kTmlane : kMlane, la | prof, W, {d->slane, d->mlaneNG, d->mlaneGPW, d->mlaneSPW}};
+  } else if (d->slane && d->wlane) {
+    return {kWlane, prof, W, {d->slane, 0, 0, 0}};
+  } else if (d->slane) {
+    return {d->tlane ? kTlane : kSlane, la | prof, W, {d->slane, 0, 0, 0}};
+  }
+  return {kGeneric, 0, W, {0, 0, 0, 0}};
+}
+
+/* the kernel of a lane engine's key; a variant without phase clocks stands in for a missing phase-clock variant */
+const LaneKernel* findLaneKernel(LaneKey k) {
+  for (int pass = 0; pass < 2; ++pass, k.var &= ~kVarProf) {
+    for (const LaneKernel& e : kLaneKernels) {
+      if (e.key.fam == k.fam && e.key.var == k.var && e.key.threads == k.threads && e.key.g[0] == k.g[0] &&
+          e.key.g[1] == k.g[1] && e.key.g[2] == k.g[2] && e.key.g[3] == k.g[3]) {
+        return &e;
+      }
+    }
+  }
+  return nullptr;
+}
+
+/* dynamic LDS of the launch */
+size_t launchLds(const fltx_decoder* d, const LaneKey& k) {
+  if (k.fam == kSstream) {
+    return sizeof(SlaneLds);
+  } else if (k.fam == kTstream) {
+    return sizeof(TlaneLds) + (size_t)(k.threads / 64) * kTlGatherBytes;
+  }
+  return (k.fam == kGeneric && !d->wsInLds) ? d->hotBytes : d->wsBytes;
+}
+
+#ifndef FLTX_EMU
+/* the generic / lean / lane-per-slot kernels of one workgroup size */
+template <int W>
+const void* genericKernel(const fltx_decoder* d) {
+  const bool la = d->opt.log_add, ft = d->opt.beam_size_token >= d->N;
+  if (!d->wsInLds) {
+    return d->lean ? (const void*)fltx_decode_kernel_gwslean<W> : (const void*)fltx_decode_kernel_gws<W>;
+  } else if (d->lane == 4) {
+    return la ? (ft ? (const void*)fltx_decode_kernel_lane<W, 4, true, true> : (const void*)fltx_decode_kernel_lane<W, 4, true, false>)
+              : (ft ? (const void*)fltx_decode_kernel_lane<W, 4, false, true> : (const void*)fltx_decode_kernel_lane<W, 4, false, false>);
+  } else if (d->lane == 8) {
+    return la ? (ft ? (const void*)fltx_decode_kernel_lane<W, 8, true, true> : (const void*)fltx_decode_kernel_lane<W, 8, true, false>)
+              : (ft ? (const void*)fltx_decode_kernel_lane<W, 8, false, true> : (const void*)fltx_decode_kernel_lane<W, 8, false, false>);
+  } else if (d->lean == 6) {
+    return (const void*)fltx_decode_kernel_lds<W, 6>;
+  } else if (d->lean == 12) {
+    return (const void*)fltx_decode_kernel_lds<W, 12>;
+  } else if (d->lean == 255) {
+    return (const void*)fltx_decode_kernel_lds<W, 255>;
+  } else if (d->kind == FLTX_DECODER_LEXICON && !d->isLmToken && d->lm->kind == 0) {
+    return (const void*)fltx_decode_kernel_lds_spec<W, true, true>;
+  } else if (d->kind == FLTX_DECODER_LEXICON && !d->isLmToken && d->lm->kind == 1) {
+    return (const void*)fltx_decode_kernel_lds_spec<W, true, false>;
+  } else if (d->lm->kind == 0 && !d->isLmToken) {
+    return (const void*)fltx_decode_kernel_lds_spec<W, false, true>;
+  }
+  return (const void*)fltx_decode_kernel_lds<W, 0>;
+}
+
+/* hipFuncAttributeMaxDynamicSharedMemorySize of a kernel: raised when a launch needs more than it was set to, once per
+ * (device, kernel, bytes) -- under defer_check two host threads launch */
+int raiseMaxLds(int device, const void* fn, size_t bytes) {
+  static std::mutex mu;
+  static std::map<std::pair<int, const void*>, size_t> set;
+  std::lock_guard<std::mutex> lock(mu);
+  auto it = set.find({device, fn});
+  if (it == set.end() || it->second < bytes) {
+    HIPCHK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    set[{device, fn}] = bytes;
+  }
+  return FLTX_OK;
+}
+#endif
+
+int launchDecode(fltx_decoder* d, const DecodeParams& P) {
+  const LaneKey key = laneKeyOf(d);
+  const LaneKernel* lane = key.fam == kGeneric ? nullptr : findLaneKernel(key);
+  if (key.fam != kGeneric && !lane) {
+    return fail(FLTX_ERR_INVALID, "no kernel of lane engine %d (variant %d) for %d threads x (%d, %d, %d, %d)", key.fam,
+                key.var, key.threads, key.g[0], key.g[1], key.g[2], key.g[3]);
+  }
+  const int W = key.threads;
+  const int nGrid = d->nLaunch > 0 ? d->nLaunch : d->B;
+  const size_t lds = launchLds(d, key);
 #ifdef FLTX_EMU
 #include "fltx_emu_launch.inc" /* tests/emu/: host-thread dispatch over the kernel variants */
 #else
@@ -2654,342 +2794,29 @@ int launchDecode(fltx_decoder* d, const DecodeParams& P) {
     }
   }
   HIPCHK(hipEventRecord(d->ev[0], d->ctx->stream));
-  const int nGrid = d->nLaunch > 0 ? d->nLaunch : d->B;
-#define FLTX_LAUNCH_LDS(WW, GG)                                                                  \
-  do {                                                                                           \
-    HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_lds<WW, GG>,                      \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->wsBytes));    \
-    hipLaunchKernelGGL((fltx_decode_kernel_lds<WW, GG>), dim3(nGrid), dim3(WW), d->wsBytes,      \
-                       d->ctx->stream, P);                                                       \
-  } while (0)
-#define FLTX_LAUNCH_SPEC(WW, LX, ZL)                                                             \
-  do {                                                                                           \
-    HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_lds_spec<WW, LX, ZL>,             \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->wsBytes));    \
-    hipLaunchKernelGGL((fltx_decode_kernel_lds_spec<WW, LX, ZL>), dim3(nGrid), dim3(WW),         \
-                       d->wsBytes, d->ctx->stream, P);                                           \
-  } while (0)
-#define FLTX_LAUNCH_LANE1(WW, GG, LA, FT)                                                        \
-  do {                                                                                           \
-    HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_lane<WW, GG, LA, FT>,             \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->wsBytes));    \
-    hipLaunchKernelGGL((fltx_decode_kernel_lane<WW, GG, LA, FT>), dim3(nGrid), dim3(WW),         \
-                       d->wsBytes, d->ctx->stream, P);                                           \
-  } while (0)
-#define FLTX_LAUNCH_LANE(WW, GG)                                                                 \
-  do {                                                                                           \
-    const bool ft_ = d->opt.beam_size_token >= d->N;                                             \
-    if (d->opt.log_add && ft_) {                                                                 \
-      FLTX_LAUNCH_LANE1(WW, GG, true, true);                                                     \
-    } else if (d->opt.log_add) {                                                                 \
-      FLTX_LAUNCH_LANE1(WW, GG, true, false);                                                    \
-    } else if (ft_) {                                                                            \
-      FLTX_LAUNCH_LANE1(WW, GG, false, true);                                                    \
-    } else {                                                                                     \
-      FLTX_LAUNCH_LANE1(WW, GG, false, false);                                                   \
-    }                                                                                            \
-  } while (0)
-#define FLTX_LAUNCH_SLANE(WW, GG)                                                                \
-  do {                                                                                           \
-    if (d->tlane && d->opt.log_add) {                                                            \
-      HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_tlane<WW, GG, true>,            \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->wsBytes));  \
-      hipLaunchKernelGGL((fltx_decode_kernel_tlane<WW, GG, true>), dim3(nGrid), dim3(WW),        \
-                         d->wsBytes, d->ctx->stream, P);                                         \
-    } else if (d->tlane && d->profile && ((WW == 576 && GG == 4) || (WW == 512 && GG == 5))) {   \
-      constexpr int PW_ = (WW == 576 && GG == 4) ? 576 : 512, PG_ = (WW == 576 && GG == 4) ? 4 : 5; \
-      HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_tlane<PW_, PG_, false, true>,   \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->wsBytes));  \
-      hipLaunchKernelGGL((fltx_decode_kernel_tlane<PW_, PG_, false, true>), dim3(nGrid), dim3(PW_), \
-                         d->wsBytes, d->ctx->stream, P);                                         \
-    } else if (d->tlane) {                                                                       \
-      HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_tlane<WW, GG, false>,           \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->wsBytes));  \
-      hipLaunchKernelGGL((fltx_decode_kernel_tlane<WW, GG, false>), dim3(nGrid), dim3(WW),       \
-                         d->wsBytes, d->ctx->stream, P);                                         \
-    } else if (d->opt.log_add) {                                                                        \
-      hipLaunchKernelGGL((fltx_decode_kernel_slane<WW, GG, true, false>), dim3(nGrid), dim3(WW), \
-                         d->wsBytes, d->ctx->stream, P);                                         \
-    } else if (d->profile) {                                                                     \
-      hipLaunchKernelGGL((fltx_decode_kernel_slane<WW, GG, false, true>), dim3(nGrid), dim3(WW), \
-                         d->wsBytes, d->ctx->stream, P);                                         \
-    } else {                                                                                     \
-      hipLaunchKernelGGL((fltx_decode_kernel_slane<WW, GG, false, false>), dim3(nGrid), dim3(WW),\
-                         d->wsBytes, d->ctx->stream, P);                                         \
-    }                                                                                            \
-  } while (0)
-#define FLTX_LAUNCH(WW)                                                                          \
-  do {                                                                                           \
-    if (!d->wsInLds && d->lean) {                                                                \
-      hipLaunchKernelGGL(fltx_decode_kernel_gwslean<WW>, dim3(nGrid), dim3(WW), d->hotBytes, d->ctx->stream, P); \
-    } else if (!d->wsInLds) {                                                                    \
-      HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_gws<WW>,                        \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->hotBytes)); \
-      hipLaunchKernelGGL(fltx_decode_kernel_gws<WW>, dim3(nGrid), dim3(WW), d->hotBytes, d->ctx->stream, P); \
-    } else if (d->lane == 4) {                                                                   \
-      FLTX_LAUNCH_LANE(WW, 4);                                                                   \
-    } else if (d->lane == 8) {                                                                   \
-      FLTX_LAUNCH_LANE(WW, 8);                                                                   \
-    } else if (d->lean == 6) {                                                                   \
-      FLTX_LAUNCH_LDS(WW, 6);                                                                    \
-    } else if (d->lean == 12) {                                                                  \
-      FLTX_LAUNCH_LDS(WW, 12);                                                                   \
-    } else if (d->lean == 255) {                                                                 \
-      FLTX_LAUNCH_LDS(WW, 255);                                                                  \
-    } else if (d->kind == FLTX_DECODER_LEXICON && !d->isLmToken && d->lm->kind == 0) {           \
-      FLTX_LAUNCH_SPEC(WW, true, true);                                                          \
-    } else if (d->kind == FLTX_DECODER_LEXICON && !d->isLmToken && d->lm->kind == 1) {           \
-      FLTX_LAUNCH_SPEC(WW, true, false);                                                         \
-    } else if (d->lm->kind == 0 && !d->isLmToken) {                                              \
-      FLTX_LAUNCH_SPEC(WW, false, true);                                                         \
-    } else {                                                                                     \
-      FLTX_LAUNCH_LDS(WW, 0);                                                                    \
-    }                                                                                            \
-  } while (0)
-  if (d->sstreamLaunch) {
-#define FLTX_LAUNCH_SSTREAM(WW, GG)                                                              \
-  do {                                                                                           \
-    if (d->tstream) {                                                                            \
-      hipLaunchKernelGGL((fltx_decode_kernel_tlane_stream<WW, GG>), dim3(nGrid), dim3(WW),       \
-                         sizeof(TlaneLds) + (size_t)(WW / 64) * kTlGatherBytes, d->ctx->stream, P); \
-    } else {                                                                                     \
-      hipLaunchKernelGGL((fltx_decode_kernel_slane_stream<WW, GG>), dim3(nGrid), dim3(WW), sizeof(SlaneLds), \
-                         d->ctx->stream, P);                                                     \
-    }                                                                                            \
-  } while (0)
-    switch (W * 100 + d->sstream) {
-      case 57604: FLTX_LAUNCH_SSTREAM(576, 4); break;
-      case 51205: FLTX_LAUNCH_SSTREAM(512, 5); break;
-      case 57610: FLTX_LAUNCH_SSTREAM(576, 10); break;
-      default: return fail(FLTX_ERR_INVALID, "no stream kernel for %d threads x %d positions", W, d->sstream);
-    }
-#undef FLTX_LAUNCH_SSTREAM
-  } else if (d->ylane) {
-#define FLTX_LAUNCH_YLANE(WW, NG, RR, LMK, HM)                                                          \
-  do {                                                                                                  \
-    HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, false>,       \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->wsBytes));           \
-    HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, true>,        \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->wsBytes));           \
-    if (d->profile) {                                                                                   \
-      hipLaunchKernelGGL((fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, true>), dim3(nGrid), dim3(WW),  \
-                         d->wsBytes, d->ctx->stream, P);                                                \
-    } else {                                                                                            \
-      hipLaunchKernelGGL((fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, false>), dim3(nGrid), dim3(WW), \
-                         d->wsBytes, d->ctx->stream, P);                                                \
-    }                                                                                                   \
-  } while (0)
-#define FLTX_LAUNCH_YLANE_NP(WW, NG, RR, LMK, HM) /* (no profiling variant) */                         \
-  do {                                                                                                  \
-    HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, false>,       \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->wsBytes));           \
-    hipLaunchKernelGGL((fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, false>), dim3(nGrid), dim3(WW),   \
-                       d->wsBytes, d->ctx->stream, P);                                                  \
-  } while (0)
-#define FLTX_LAUNCH_YLANE4(LMK)                                                                        \
-  do {                                                                                                  \
-    HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_ylane<1024, 4, 4, LMK, 1, false>,        \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->wsBytes));           \
-    hipLaunchKernelGGL((fltx_decode_kernel_ylane<1024, 4, 4, LMK, 1, false>), dim3(nGrid), dim3(1024),  \
-                       d->wsBytes, d->ctx->stream, P);                                                  \
-  } while (0)
-    switch (d->ylane * 100 + d->ylaneLm + (d->yshare ? 1000 : 0)) { /* lane groups, LMK, memo in HBM */
-      case 100: FLTX_LAUNCH_YLANE(512, 1, 2, 0, 0); break;
-      case 101: FLTX_LAUNCH_YLANE(512, 1, 2, 1, 0); break;
-      case 200: FLTX_LAUNCH_YLANE(768, 2, 4, 0, 0); break;
-      case 201: FLTX_LAUNCH_YLANE(768, 2, 4, 1, 0); break;
-      case 1100: FLTX_LAUNCH_YLANE(512, 1, 2, 0, 1); break;
-      case 1101: FLTX_LAUNCH_YLANE(512, 1, 2, 1, 1); break;
-      case 1200: FLTX_LAUNCH_YLANE(512, 2, 4, 0, 1); break;
-      case 1201: FLTX_LAUNCH_YLANE(512, 2, 4, 1, 1); break;
-      case 1400: FLTX_LAUNCH_YLANE4(0); break;
-      case 1401: FLTX_LAUNCH_YLANE4(1); break;
-      case 102: FLTX_LAUNCH_YLANE_NP(512, 1, 2, 2, 0); break; /* ASG (LMK bit 1) */
-      case 103: FLTX_LAUNCH_YLANE_NP(512, 1, 2, 3, 0); break;
-      case 202: FLTX_LAUNCH_YLANE_NP(768, 2, 4, 2, 0); break;
-      case 203: FLTX_LAUNCH_YLANE_NP(768, 2, 4, 3, 0); break;
-      case 1102: FLTX_LAUNCH_YLANE_NP(512, 1, 2, 2, 1); break;
-      case 1103: FLTX_LAUNCH_YLANE_NP(512, 1, 2, 3, 1); break;
-      case 1202: FLTX_LAUNCH_YLANE_NP(512, 2, 4, 2, 1); break;
-      case 1203: FLTX_LAUNCH_YLANE_NP(512, 2, 4, 3, 1); break;
-      case 1402: FLTX_LAUNCH_YLANE4(2); break;
-      case 1403: FLTX_LAUNCH_YLANE4(3); break;
-      /* logAdd merges (LMK bit 3; CTC) */
-      case 108: FLTX_LAUNCH_YLANE_NP(512, 1, 2, 8, 0); break;
-      case 109: FLTX_LAUNCH_YLANE_NP(512, 1, 2, 9, 0); break;
-      case 208: FLTX_LAUNCH_YLANE_NP(768, 2, 4, 8, 0); break;
-      case 209: FLTX_LAUNCH_YLANE_NP(768, 2, 4, 9, 0); break;
-      case 1108: FLTX_LAUNCH_YLANE_NP(512, 1, 2, 8, 1); break;
-      case 1109: FLTX_LAUNCH_YLANE_NP(512, 1, 2, 9, 1); break;
-      case 1208: FLTX_LAUNCH_YLANE_NP(512, 2, 4, 8, 1); break;
-      case 1209: FLTX_LAUNCH_YLANE_NP(512, 2, 4, 9, 1); break;
-      case 1408: FLTX_LAUNCH_YLANE4(8); break;
-      case 1409: FLTX_LAUNCH_YLANE4(9); break;
-      /* several words per spelling (LMK bit 2; with the LM terms) */
-      case 1105: FLTX_LAUNCH_YLANE_NP(512, 1, 2, 5, 1); break;
-      case 1107: FLTX_LAUNCH_YLANE_NP(512, 1, 2, 7, 1); break;
-      case 1205: FLTX_LAUNCH_YLANE_NP(768, 2, 4, 5, 1); break;
-      case 1207: FLTX_LAUNCH_YLANE_NP(768, 2, 4, 7, 1); break;
-            /* logAdd under ASG (LMK 10 / 11) and over spellings with several words (13 / 15) */
-      case 110: FLTX_LAUNCH_YLANE_NP(512, 1, 2, 10, 0); break;
-      case 111: FLTX_LAUNCH_YLANE_NP(512, 1, 2, 11, 0); break;
-      case 210: FLTX_LAUNCH_YLANE_NP(768, 2, 4, 10, 0); break;
-      case 211: FLTX_LAUNCH_YLANE_NP(768, 2, 4, 11, 0); break;
-      case 1110: FLTX_LAUNCH_YLANE_NP(512, 1, 2, 10, 1); break;
-      case 1111: FLTX_LAUNCH_YLANE_NP(512, 1, 2, 11, 1); break;
-      case 1210: FLTX_LAUNCH_YLANE_NP(512, 2, 4, 10, 1); break;
-      case 1211: FLTX_LAUNCH_YLANE_NP(512, 2, 4, 11, 1); break;
-      case 1410: FLTX_LAUNCH_YLANE4(10); break;
-      case 1411: FLTX_LAUNCH_YLANE4(11); break;
-      case 1113: FLTX_LAUNCH_YLANE_NP(512, 1, 2, 13, 1); break;
-      case 1115: FLTX_LAUNCH_YLANE_NP(512, 1, 2, 15, 1); break;
-      case 1213: FLTX_LAUNCH_YLANE_NP(768, 2, 4, 13, 1); break;
-      case 1215: FLTX_LAUNCH_YLANE_NP(768, 2, 4, 15, 1); break;
-      default: return fail(FLTX_ERR_INVALID, "no fltx_ylane.h kernel for %d lane groups", d->ylane);
-    }
-#undef FLTX_LAUNCH_YLANE
-#undef FLTX_LAUNCH_YLANE4
-#undef FLTX_LAUNCH_YLANE_NP
-  } else if (d->xlane) {
-#define FLTX_LAUNCH_XLANE(WW, GG)                                                                \
-  do {                                                                                           \
-    HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_xlane<WW, GG, 0, false>,          \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(XlaneLds))); \
-    HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_xlane<WW, GG, 0, true>,           \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(XlaneLds))); \
-    if (d->opt.log_add) { /* (logAdd merges: fltx_xlane.h LA) */                                \
-      HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_xlane<WW, GG, 0, false, true>,  \
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)sizeof(XlaneLds))); \
-      if (d->yshare) {                                                                           \
-        hipLaunchKernelGGL((fltx_decode_kernel_xlane<WW, GG, 1, false, true>), dim3(nGrid), dim3(WW), \
-                           d->wsBytes, d->ctx->stream, P);                                       \
-      } else {                                                                                   \
-        hipLaunchKernelGGL((fltx_decode_kernel_xlane<WW, GG, 0, false, true>), dim3(nGrid), dim3(WW), \
-                           d->wsBytes, d->ctx->stream, P);                                       \
-      }                                                                                          \
-    } else if (d->yshare) {                                                                      \
-      hipLaunchKernelGGL((fltx_decode_kernel_xlane<WW, GG, 1, false>), dim3(nGrid), dim3(WW),    \
-                         d->wsBytes, d->ctx->stream, P);                                         \
-    } else if (d->profile) {                                                                     \
-      hipLaunchKernelGGL((fltx_decode_kernel_xlane<WW, GG, 0, true>), dim3(nGrid), dim3(WW),     \
-                         d->wsBytes, d->ctx->stream, P);                                         \
-    } else {                                                                                     \
-      hipLaunchKernelGGL((fltx_decode_kernel_xlane<WW, GG, 0, false>), dim3(nGrid), dim3(WW),    \
-                         d->wsBytes, d->ctx->stream, P);                                         \
-    }                                                                                            \
-  } while (0)
-    switch (W * 100 + d->xlane) {
-      case 51202: FLTX_LAUNCH_XLANE(512, 2); break;
-      case 64002: FLTX_LAUNCH_XLANE(640, 2); break;
-      case 51203: FLTX_LAUNCH_XLANE(512, 3); break;
-      case 57605: FLTX_LAUNCH_XLANE(576, 5); break;
-      case 64010: FLTX_LAUNCH_XLANE(640, 10); break;
-      default: return fail(FLTX_ERR_INVALID, "no lane = (LM state, node) kernel for %d threads x %d positions", W, d->xlane);
-    }
-#undef FLTX_LAUNCH_XLANE
-  } else if (d->slane && d->mlaneNG > 1) {
-#define FLTX_LAUNCH_MLANE(WW, GG, NG, GPW, SPW)                                                          \
-  do {                                                                                                   \
-    HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_mlane<WW, GG, NG, GPW, SPW, false>,       \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->wsBytes));            \
-    HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_mlane<WW, GG, NG, GPW, SPW, true>,        \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->wsBytes));            \
-    if (d->opt.log_add) {                                                                                \
-      hipLaunchKernelGGL((fltx_decode_kernel_mlane<WW, GG, NG, GPW, SPW, true>), dim3(nGrid), dim3(WW),  \
-                         d->wsBytes, d->ctx->stream, P);                                                 \
-    } else {                                                                                             \
-      hipLaunchKernelGGL((fltx_decode_kernel_mlane<WW, GG, NG, GPW, SPW, false>), dim3(nGrid), dim3(WW), \
-                         d->wsBytes, d->ctx->stream, P);                                                 \
-    }                                                                                                    \
-  } while (0)
-#define FLTX_LAUNCH_TMLANE(WW, GG, NG, GPW, SPW)                                                         \
-  do {                                                                                                   \
-    HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_tmlane<WW, GG, NG, GPW, SPW, false>,      \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->wsBytes));            \
-    HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_tmlane<WW, GG, NG, GPW, SPW, true>,       \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->wsBytes));            \
-    if (d->opt.log_add) {                                                                                \
-      hipLaunchKernelGGL((fltx_decode_kernel_tmlane<WW, GG, NG, GPW, SPW, true>), dim3(nGrid), dim3(WW), \
-                         d->wsBytes, d->ctx->stream, P);                                                 \
-    } else {                                                                                             \
-      hipLaunchKernelGGL((fltx_decode_kernel_tmlane<WW, GG, NG, GPW, SPW, false>), dim3(nGrid), dim3(WW), \
-                         d->wsBytes, d->ctx->stream, P);                                                 \
-    }                                                                                                    \
-  } while (0)
-    if (d->tlane) {
-      switch (d->mlaneNG * 100 + d->slane) {
-        case 205: FLTX_LAUNCH_TMLANE(960, 5, 2, 1, 1); break;
-        case 405: FLTX_LAUNCH_TMLANE(960, 5, 4, 2, 2); break;
-        case 810: FLTX_LAUNCH_TMLANE(960, 10, 8, 2, 4); break;
-        case 211: FLTX_LAUNCH_TMLANE(960, 11, 2, 1, 1); break;
-        case 411: FLTX_LAUNCH_TMLANE(960, 11, 4, 2, 2); break;
-        default:
-          return fail(FLTX_ERR_INVALID, "no token-LM fltx_mlane.h kernel for %d lane groups x %d positions", d->mlaneNG, d->slane);
-      }
-    } else
-    switch (((W * 100 + d->slane) * 10 + d->mlaneNG) * 100 + d->mlaneGPW * 10 + d->mlaneSPW) {
-      case 64004221: FLTX_LAUNCH_MLANE(640, 4, 2, 2, 1); break;
-      case 96005211: FLTX_LAUNCH_MLANE(960, 5, 2, 1, 1); break;
-      case 64010221: FLTX_LAUNCH_MLANE(640, 10, 2, 2, 1); break;
-      case 76804441: FLTX_LAUNCH_MLANE(768, 4, 4, 4, 1); break;
-      case 96005422: FLTX_LAUNCH_MLANE(960, 5, 4, 2, 2); break;
-      case 96011422: FLTX_LAUNCH_MLANE(960, 11, 4, 2, 2); break;
-      case 96010824: FLTX_LAUNCH_MLANE(960, 10, 8, 2, 4); break;
-      default:
-        return fail(FLTX_ERR_INVALID, "no fltx_mlane.h kernel for %d threads x %d positions x %d lane groups", W, d->slane,
-                    d->mlaneNG);
-    }
-#undef FLTX_LAUNCH_MLANE
-#undef FLTX_LAUNCH_TMLANE
-  } else if (d->slane && d->wlane) {
-    { /* the token beams of all rows first (same stream) */
-      const int maxT = d->wlMaxT;
-      if (maxT > 0) {
-        hipLaunchKernelGGL(fltx_tokbeam_kernel, dim3((unsigned)(P.tokRowBlocks * nGrid)), dim3(256), 4 * sizeof(WlFrontLds),
-                           d->ctx->stream, P);
-      }
-    }
-#define FLTX_LAUNCH_WLANE(WW, GG)                                                                          \
-  do {                                                                                                     \
-    HIPCHK(hipFuncSetAttribute((const void*)fltx_decode_kernel_wlane<WW, GG>,                              \
-                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->wsBytes));              \
-    hipLaunchKernelGGL((fltx_decode_kernel_wlane<WW, GG>), dim3(nGrid), dim3(WW), d->wsBytes, d->ctx->stream, P); \
-  } while (0)
-    switch (W * 100 + d->slane) {
-      case 57605: FLTX_LAUNCH_WLANE(576, 5); break;
-      case 57608: FLTX_LAUNCH_WLANE(576, 8); break;
-      case 57610: FLTX_LAUNCH_WLANE(576, 10); break;
-      default: return fail(FLTX_ERR_INVALID, "no fltx_wlane.h kernel for %d threads x %d positions", W, d->slane);
-    }
-#undef FLTX_LAUNCH_WLANE
-  } else if (d->slane) {
-    const int key = W * 100 + d->slane;
-    switch (key) {
-      case 32010: FLTX_LAUNCH_SLANE(320, 10); break;
-      case 38407: FLTX_LAUNCH_SLANE(384, 7); break;
-      case 44806: FLTX_LAUNCH_SLANE(448, 6); break;
-      case 51205: FLTX_LAUNCH_SLANE(512, 5); break;
-      case 57604: FLTX_LAUNCH_SLANE(576, 4); break;
-      case 64004: FLTX_LAUNCH_SLANE(640, 4); break;
-      case 51212: FLTX_LAUNCH_SLANE(512, 12); break;
-      case 57610: FLTX_LAUNCH_SLANE(576, 10); break;
-      default: return fail(FLTX_ERR_INVALID, "no lane = LM state kernel for %d threads x %d positions", W, d->slane);
-    }
-  } else
-  switch (W) {
-    case 64: FLTX_LAUNCH(64); break;
-    case 128: FLTX_LAUNCH(128); break;
-    case 256: FLTX_LAUNCH(256); break;
-    case 512: FLTX_LAUNCH(512); break;
-    case 1024: FLTX_LAUNCH(1024); break;
+  const void* fn = lane ? lane->fn : nullptr;
+  switch (lane ? 0 : W) {
+    case 0: break;
+    case 64: fn = genericKernel<64>(d); break;
+    case 128: fn = genericKernel<128>(d); break;
+    case 256: fn = genericKernel<256>(d); break;
+    case 512: fn = genericKernel<512>(d); break;
+    case 1024: fn = genericKernel<1024>(d); break;
     default: return fail(FLTX_ERR_INVALID, "threads per utterance must be 64, 128, 256, 512 or 1024");
   }
-#undef FLTX_LAUNCH
-#undef FLTX_LAUNCH_LDS
-#undef FLTX_LAUNCH_LANE
-#undef FLTX_LAUNCH_LANE1
-#undef FLTX_LAUNCH_SPEC
-#undef FLTX_LAUNCH_SLANE
+  if (key.fam == kWlane && d->wlMaxT > 0) { /* the token beams of all rows first (same stream) */
+    hipLaunchKernelGGL(fltx_tokbeam_kernel, dim3((unsigned)(P.tokRowBlocks * nGrid)), dim3(256), 4 * sizeof(WlFrontLds),
+                       d->ctx->stream, P);
+  }
+  /* (slane, the stream chunks and gwslean launch within the default limit, as they always have) */
+  const bool defaultLimit = key.fam == kSlane || key.fam == kSstream || key.fam == kTstream ||
+                            (key.fam == kGeneric && !d->wsInLds && d->lean);
+  int rc;
+  if (!defaultLimit && (rc = raiseMaxLds(d->ctx->device, fn, lds))) {
+    return rc;
+  }
+  void* args[] = {(void*)&P};
+  HIPCHK(hipLaunchKernel(fn, dim3(nGrid), dim3(W), args, lds, d->ctx->stream));
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(d->ev[1], d->ctx->stream));
   d->timed = false;
