@@ -212,6 +212,9 @@ FLTX_DEV uint32_t waveGather32(uint32_t v, int src) { return waveShfl32(v, src);
 FLTX_DEV unsigned long long waveShfl64(unsigned long long v, int src) {
   return emuExchange(v, [src](const unsigned long long* s) { return s[src & 63]; });
 }
+FLTX_DEV unsigned long long waveShflXor64(unsigned long long v, int m) {
+  return waveShfl64(v, (int)(threadIdx.x & 63) ^ m);
+}
 /* lane i of a row of 16 takes the value of lane (i - R) mod 16 of its row (DPP row_ror) */
 template <int R>
 FLTX_DEV unsigned long long waveRowRor64(unsigned long long v) {

@@ -339,19 +339,23 @@ FLTX_DEV void wlTokBeamRow(const DecodeParams& P, WlFrontLds& S, const float* ro
         const unsigned long long h2 = ((vv + 1ull) << shift) - 1ull;
         bHi = h2 < bHi ? h2 : bHi;
       }
-      if (bLo >= bHi) { /* one value of the distance, and many of it: the next pass ranks them pairwise, or gives up */
+      if (bLo >= bHi && shift == 0) { /* bin bstar is one value of the distance, and many of it: the next pass ranks
+                                         them pairwise, or gives up */
         if (sc.cnt > kSlBCap) {
           giveUp = true;
           break;
         }
         continue;
       }
+      /* The bracket takes bins 1 .. 254; bin 0 holds what is nearer, 255 what is farther.  (With the bracket from bin 0
+       * on, bin 0 also held every nearer value: a cut on a value at the bracket's lower end counted them with its own
+       * ties, and a row with at most kSlBCap values of the distance at the cut was given up.) */
       int ns = 0;
-      while (((bHi >> ns) - (bLo >> ns)) > (unsigned long long)(kSlNB - 1)) {
+      while ((bHi >> ns) > (bLo >> ns) + (unsigned long long)(kSlNB - 3)) {
         ++ns;
       }
       shift = ns;
-      base = (int)(bLo >> ns);
+      base = (int)(bLo >> ns) - 1;
     }
   }
   /* pass C: the list, in token order */
