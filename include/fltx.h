@@ -41,11 +41,11 @@ enum {
   FLTX_ERR_CALLBACK = 7     /* a host-LM callback reported failure (the binding rethrows what the user's LM threw) */
 };
 
-/* CriterionType, decoder/Decoder.h:16 (S2S is out of scope). */
-enum { FLTX_CRITERION_ASG = 0, FLTX_CRITERION_CTC = 1 };
+/* CriterionType, decoder/Decoder.h:16. */
+enum { FLTX_CRITERION_ASG = 0, FLTX_CRITERION_CTC = 1, FLTX_CRITERION_S2S = 2 };
 /* SmearingMode, decoder/Trie.h:21-25. */
 enum { FLTX_SMEAR_NONE = 0, FLTX_SMEAR_MAX = 1, FLTX_SMEAR_LOGADD = 2 };
-enum { FLTX_DECODER_LEXFREE = 0, FLTX_DECODER_LEXICON = 1 };
+enum { FLTX_DECODER_LEXFREE = 0, FLTX_DECODER_LEXICON = 1, FLTX_DECODER_S2S_LEXFREE = 2 };
 
 /* LexiconDecoderOptions (decoder/LexiconDecoder.h:21-31); the lexicon-free
  * decoder (decoder/LexiconFreeDecoder.h:20-28) ignores word_score/unk_score. */
@@ -239,6 +239,56 @@ FLTX_API int fltx_stream_prune(fltx_decoder* dec, int32_t look_back);
 /* nDecodedFramesInBuffer (LexiconFreeDecoder.cpp:201-203). */
 FLTX_API int fltx_stream_frames_in_buffer(fltx_decoder* dec, int32_t b,
                                           int32_t* n);
+
+/* ---- seq2seq: LexiconFreeSeq2SeqDecoder as a batched device step ----------- */
+/* LexiconFreeSeq2SeqDecoderOptions (decoder/LexiconFreeSeq2SeqDecoder.h:23-30). */
+typedef struct fltx_s2s_options {
+  int32_t beam_size;
+  int32_t beam_size_token;
+  double beam_threshold;
+  double lm_weight;
+  double eos_score;
+  int32_t log_add; /* accepted and without effect: no two candidates of a step share an LM state, nothing merges */
+} fltx_s2s_options;
+
+/* LexiconFreeSeq2SeqDecoder(opt, lm, eos, emittingModelUpdateFunc, maxOutputLength)
+ * (decoder/LexiconFreeSeq2SeqDecoder.h:100-111, .cpp:20-165) for B utterances at once.  The emitting model stays the
+ * caller's: between two fltx_s2s_step calls it scores the rows the previous call listed.  The decoder is an
+ * fltx_decoder: fltx_result_count / fetch / fetch_batch / fetch_batch_compact / device / best read its n-best after
+ * fltx_s2s_end (rows of max_output_length + 3 tokens, right-aligned, -1 in front; words all -1); fltx_decode_batch and
+ * fltx_stream_* return FLTX_ERR_STATE on it.
+ * Limits (FLTX_ERR_UNSUPPORTED beyond them; there is no CPU fallback): beam_size <= 256, V <= 65 536,
+ * max_output_length <= 4 096, min(beam_size_token, V) <= 64 when the LM scores (an n-gram LM with lm_weight != 0; any
+ * beam_size_token under ZeroLM or lm_weight == 0), ZeroLM or n-gram LMs only (a host LM, fltx_lm_host_create, may hand
+ * out repeated states and would need merges). */
+FLTX_API int fltx_s2s_decoder_create(fltx_ctx* ctx, const fltx_s2s_options* opt, const fltx_lm* lm, int32_t eos,
+                                     int32_t max_output_length, fltx_decoder** out);
+/* decodeStep's start (LexiconFreeSeq2SeqDecoder.cpp:22-32) for B utterances whose model rows are V scores wide.
+ * Writes the first call's rows.  Row lists are caller-owned DEVICE buffers of B*K int32 (K = beam_size), n_rows of B:
+ * row k of utterance b is entry b*K + k, rows k >= n_rows[b] are padding (-1).  For row k:
+ *   next_token   the hypothesis' last token (rawY; -1 for the root);
+ *   next_beam_idx  its parent's index in the previous beam (rawBeamIdx: that beam includes finished hypotheses, so it
+ *                is not a row number; -1 for the root);
+ *   next_src_row the row of the previous step's call that produced the parent (b*K + k'; -1 for the root): the index a
+ *                model passes to index_select on its per-row state (rawPrevStates).
+ * A decoder may begin again after any step or end: the search restarts from the root. */
+FLTX_API int fltx_s2s_begin(fltx_decoder* dec, int32_t B, int32_t V, int32_t* next_token, int32_t* next_beam_idx,
+                            int32_t* next_src_row, int32_t* n_rows);
+/* One step of every utterance (:34-150): `scores` holds the model's rows, row b*K + k at scores + (b*K + k) *
+ * row_stride (row_stride >= V floats); a device pointer when on_device != 0, else a host pointer copied first.
+ * row_valid (may be NULL; device / host as scores) holds B*K bytes: 0 marks a row the model dropped (its state came
+ * back null, :86-89) -- it proposes nothing.  Padding rows and rows of row_valid 0 are never read.  The four outputs
+ * are the next call's rows, as fltx_s2s_begin writes them; an utterance that is done lists none.  Asynchronous on the
+ * context's stream.  A step after the last one (max_output_length steps, or every utterance done) changes nothing and
+ * lists no rows. */
+FLTX_API int fltx_s2s_step(fltx_decoder* dec, const float* scores, int32_t on_device, int64_t row_stride,
+                           const uint8_t* row_valid, int32_t* next_token, int32_t* next_beam_idx,
+                           int32_t* next_src_row, int32_t* n_rows);
+/* *done = 1 when every utterance is done (no live hypothesis, or max_output_length steps); synchronises. */
+FLTX_API int fltx_s2s_done(fltx_decoder* dec, int32_t* done);
+/* The back-trace (:152-163): every utterance's final beam -- the last non-empty one, which may hold unfinished
+ * hypotheses -- becomes the decoder's results. */
+FLTX_API int fltx_s2s_end(fltx_decoder* dec);
 
 /* ---- results (getAllFinalHypothesis / getBestHypothesis) ------------------ */
 /* Number of hypotheses of utterance b and the length (finalFrame + 1) of each

@@ -13,8 +13,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_LIB = os.path.join(_HERE, "lib", "libfltx.so")
 
 FLTX_OK, ERR_INVALID, ERR_HIP, ERR_OOM, ERR_UNSUPPORTED, ERR_RANGE, ERR_STATE = range(7)
-CRITERION = {"asg": 0, "ctc": 1}
-LEXFREE, LEXICON = 0, 1
+CRITERION = {"asg": 0, "ctc": 1, "s2s": 2}
+LEXFREE, LEXICON, S2S_LEXFREE = 0, 1, 2
 # fltx_decoder_get "why_not_lane" (include/fltx.h FLTX_WHY_*)
 (FLTX_WHY_TOKENS, FLTX_WHY_BEAM, FLTX_WHY_STREAM, FLTX_WHY_LM, FLTX_WHY_LOGADD, FLTX_WHY_ASG, FLTX_WHY_UNK,
  FLTX_WHY_TRIE_SHAPE, FLTX_WHY_WORD_END, FLTX_WHY_OPTIONS, FLTX_WHY_LENGTH, FLTX_WHY_SWITCHED_OFF,
@@ -34,6 +34,19 @@ class Options(C.Structure):
         ("sil_score", C.c_double),
         ("log_add", C.c_int32),
         ("criterion", C.c_int32),
+    ]
+
+
+class S2sOptions(C.Structure):
+    """fltx_s2s_options == LexiconFreeSeq2SeqDecoderOptions (decoder/LexiconFreeSeq2SeqDecoder.h:23-30)."""
+
+    _fields_ = [
+        ("beam_size", C.c_int32),
+        ("beam_size_token", C.c_int32),
+        ("beam_threshold", C.c_double),
+        ("lm_weight", C.c_double),
+        ("eos_score", C.c_double),
+        ("log_add", C.c_int32),
     ]
 
 
@@ -62,6 +75,7 @@ class Lib:
         "fltx_htrie_search", "fltx_htrie_smear", "fltx_htrie_num_nodes", "fltx_htrie_upload",
         "fltx_decoder_bytes", "fltx_htrie_node", "fltx_group_create", "fltx_group_destroy", "fltx_group_size", "fltx_group_decoder",
         "fltx_group_decode_batch", "fltx_group_result_count", "fltx_group_result_fetch", "fltx_group_synchronize",
+        "fltx_s2s_decoder_create", "fltx_s2s_begin", "fltx_s2s_step", "fltx_s2s_done", "fltx_s2s_end",
     ]
 
     def __init__(self, path=None):
@@ -131,6 +145,11 @@ class Lib:
             "fltx_group_result_count": [vp, i32, vp, vp],
             "fltx_group_result_fetch": [vp, i32, i32, vp, vp, vp, vp],
             "fltx_group_synchronize": [vp],
+            "fltx_s2s_decoder_create": [vp, C.POINTER(S2sOptions), vp, i32, i32, pvp],
+            "fltx_s2s_begin": [vp, i32, i32, vp, vp, vp, vp],
+            "fltx_s2s_step": [vp, vp, i32, i64, vp, vp, vp, vp, vp],
+            "fltx_s2s_done": [vp, vp],
+            "fltx_s2s_end": [vp],
         }
         for name, args in sig.items():
             fn = getattr(L, name)
@@ -754,6 +773,102 @@ class BatchDecoder:
             pass
 
 
+class Seq2SeqBatchDecoder(BatchDecoder):
+    """fltx_s2s_*: LexiconFreeSeq2SeqDecoder for B utterances at once, one device step per model call.
+
+    begin(B, V) and step(scores) return the next call's rows (token, beam_idx, src_row) as [B, K] int32 and n_rows as
+    [B] int32: torch tensors allocated on the context's device (numpy arrays on the emulator library).  Row k of
+    utterance b is row b*K + k of the scores the model returns; rows k >= n_rows[b] are padding.  src_row is what the
+    model passes to index_select on its per-row state (-1 for the root and padding).  After end(), the results*
+    methods of BatchDecoder read the n-best (rows of max_output_length + 3 tokens, -1 in front).  Create the context
+    on the torch stream the model runs on so that the model's kernels and the decoder's are ordered without a host
+    wait -- a stream of its own (torch.cuda.Stream()): the default stream's handle is NULL, and a context given NULL
+    makes a stream of its own."""
+
+    def __init__(self, ctx, options, lm, eos, max_output_length):
+        self.ctx, self.L = ctx, ctx.L
+        self.kind, self.options = S2S_LEXFREE, options
+        self._keep = (lm, None)
+        self.eos, self.max_output_length = int(eos), int(max_output_length)
+        h = C.c_void_p()
+        self.L.check(self.L.lib.fltx_s2s_decoder_create(ctx.h, C.byref(options), lm.h, self.eos,
+                                                        self.max_output_length, C.byref(h)))
+        self.h = h
+        self.B = 0
+        self.N = None
+        self.V = None
+        self._emu = "emulation" in self.L.version()
+        _live["dec"].add(self)
+
+    def _rows(self):
+        B, K = self.B, int(self.options.beam_size)
+        if self._emu:  # (the emulator's "device" memory is host memory)
+            return [np.empty((B, K), np.int32) for _ in range(3)] + [np.empty(B, np.int32)]
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device())
+        return [torch.empty((B, K), dtype=torch.int32, device=dev) for _ in range(3)] + \
+            [torch.empty(B, dtype=torch.int32, device=dev)]
+
+    @staticmethod
+    def _addr(a):
+        return a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
+
+    def begin(self, B, V):
+        self.B, self.V, self.N = int(B), int(V), None
+        out = self._rows()
+        self._chk(self.L.lib.fltx_s2s_begin(self.h, self.B, self.V, *[self._addr(o) for o in out]))
+        return tuple(out)
+
+    def step(self, scores, row_valid=None):
+        """scores: [B*K, >= V] float32 (rows b*K + k), a torch tensor on the device (any row stride, unit column
+        stride) or a host numpy array; row_valid: None or B*K bytes / bools (0: the model dropped the row)."""
+        out = self._rows()
+        ptrs = [self._addr(o) for o in out]
+        if isinstance(scores, np.ndarray):
+            sc = np.ascontiguousarray(scores, dtype=np.float32).reshape(self.B * int(self.options.beam_size), -1)
+            stride, ptr = sc.shape[1], sc.ctypes.data
+            on_dev = 1 if self._emu else 0
+            rv = None if row_valid is None else np.ascontiguousarray(row_valid, dtype=np.uint8)
+            rvp = None if rv is None else rv.ctypes.data
+        else:
+            import torch
+            sc = scores.reshape(-1, scores.shape[-1])
+            assert sc.dtype == torch.float32 and sc.stride(-1) == 1, "scores: float32 rows of unit column stride"
+            stride, ptr, on_dev = sc.stride(0), sc.data_ptr(), 1
+            rv = None if row_valid is None else row_valid.reshape(-1).to(torch.uint8).contiguous()
+            rvp = None if rv is None else rv.data_ptr()
+        self._chk(self.L.lib.fltx_s2s_step(self.h, ptr, on_dev, stride, rvp, *ptrs))
+        self._inputs = (sc, rv)  # (kept until the next step: the kernels read them asynchronously)
+        return tuple(out)
+
+    def done(self):
+        v = C.c_int32(0)
+        self.L.check(self.L.lib.fltx_s2s_done(self.h, C.addressof(v)))
+        return bool(v.value)
+
+    def end(self):
+        self._chk(self.L.lib.fltx_s2s_end(self.h))
+        self.N = self.V
+
+    def decode(self, step_fn, B, V, check_every=8):
+        """The whole search: step_fn(token [B*K], src_row [B*K], row_mask [B*K] bool, t) -> scores [B*K, V] (or
+        (scores, row_valid)) is called until every utterance is done; returns results_batch().  A step after the
+        last one is a no-op, so done() -- a host wait -- is asked every `check_every` steps only."""
+        import torch
+        K = int(self.options.beam_size)
+        tok, beam, src, n = self.begin(B, V)
+        ar = torch.arange(K, device=n.device, dtype=torch.int32)
+        for t in range(self.max_output_length):
+            if t % check_every == 0 and self.done():
+                break
+            mask = (ar[None, :] < n[:, None]).reshape(-1)
+            r = step_fn(tok.reshape(-1), src.reshape(-1), mask, t)
+            scores, valid = r if isinstance(r, tuple) else (r, None)
+            tok, beam, src, n = self.step(scores, valid)
+        self.end()
+        return self.results_batch()
+
+
 class DecoderGroup:
     """fltx_group: one batch sharded over several devices (one context, decoder
     and host thread per entry of `devices`; no inter-device traffic)."""
@@ -832,6 +947,10 @@ class DecoderGroup:
             self.close()
         except Exception:
             pass
+
+
+def make_s2s_options(beam_size, beam_size_token, beam_threshold=25.0, lm_weight=0.0, eos_score=0.0, log_add=False):
+    return S2sOptions(beam_size, beam_size_token, beam_threshold, lm_weight, eos_score, int(bool(log_add)))
 
 
 def make_options(beam_size, beam_size_token, beam_threshold=25.0, lm_weight=0.0, word_score=0.0,

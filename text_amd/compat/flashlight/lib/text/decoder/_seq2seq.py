@@ -1,0 +1,126 @@
+"""LexiconFreeSeq2SeqDecoder with the reference's Python surface (bindings/python/flashlight/lib/text/_decoder.cpp:
+128-160, 443-535) over the batched device step (fltx_s2s_*, text_amd._capi.Seq2SeqBatchDecoder) at B = 1.
+
+decode_step(emissions, T, N) calls the user's update_func once per step with the live hypotheses of the beam
+(rawY / rawBeamIdx / rawPrevStates, LexiconFreeSeq2SeqDecoder.cpp:44-60), uploads the rows it returns and runs one
+device step; the per-row states are permuted on the host by the step's src_row.  The path is host-bound by
+construction (one model call and one host wait per step): it exists for drop-in correctness.  Batches of utterances
+with the model on the GPU use Seq2SeqBatchDecoder directly.
+"""
+import numpy as np
+
+from text_amd import _capi
+from text_amd.flashlight_lib_text_decoder import DecodeResult, ZeroLM
+
+
+class EmittingModelState:
+    """EmittingModelStatePtr (decoder/Utils.h:92): an opaque holder of the model's Python object."""
+    __slots__ = ("obj",)
+
+    def __init__(self, obj):
+        self.obj = obj
+
+
+def create_emitting_model_state(obj):
+    return EmittingModelState(obj)
+
+
+def get_obj_from_emitting_model_state(state):
+    return state.obj
+
+
+class LexiconFreeSeq2SeqDecoderOptions:
+    """LexiconFreeSeq2SeqDecoderOptions (decoder/LexiconFreeSeq2SeqDecoder.h:23-30)."""
+    __slots__ = ("beam_size", "beam_size_token", "beam_threshold", "lm_weight", "eos_score", "log_add")
+
+    def __init__(self, beam_size, beam_size_token, beam_threshold, lm_weight, eos_score, log_add):
+        self.beam_size, self.beam_size_token = int(beam_size), int(beam_size_token)
+        self.beam_threshold, self.lm_weight = float(beam_threshold), float(lm_weight)
+        self.eos_score, self.log_add = float(eos_score), bool(log_add)
+
+    def __reduce__(self):
+        return (LexiconFreeSeq2SeqDecoderOptions, (self.beam_size, self.beam_size_token, self.beam_threshold,
+                                                   self.lm_weight, self.eos_score, self.log_add))
+
+
+_ctx = None
+
+
+def _context():
+    """One context per process, on a torch stream of its own (the default stream's handle is NULL)."""
+    global _ctx
+    if _ctx is None:
+        import torch
+        torch.cuda.init()
+        stream = torch.cuda.Stream()
+        _ctx = (_capi.Context(stream=stream.cuda_stream), stream)  # (the stream lives as long as the context)
+    return _ctx[0]
+
+
+class LexiconFreeSeq2SeqDecoder:
+    """LexiconFreeSeq2SeqDecoder(options, lm, eos_idx, update_func, max_output_length): ZeroLM, or an LM object of
+    text_amd._capi (ZeroLM / NgramLM / ArpaLM); a user-defined LM is refused (FLTX_ERR_UNSUPPORTED)."""
+
+    def __init__(self, options, lm, eos_idx, update_func, max_output_length):
+        self.options, self.eos = options, int(eos_idx)
+        self.update_func, self.max_output_length = update_func, int(max_output_length)
+        ctx = _context()
+        if isinstance(lm, ZeroLM):
+            self._lm = _capi.ZeroLM(ctx)
+        elif isinstance(lm, _capi.ZeroLM):  # (and its subclasses: n-gram tables)
+            self._lm = lm
+        else:
+            raise _capi.FltxError(_capi.ERR_UNSUPPORTED, "seq2seq: ZeroLM or n-gram LM tables only (a user-defined LM "
+                                  "may return repeated states and would need merges)")
+        opts = _capi.make_s2s_options(options.beam_size, options.beam_size_token, options.beam_threshold,
+                                      options.lm_weight, options.eos_score, options.log_add)
+        self._dec = _capi.Seq2SeqBatchDecoder(ctx, opts, self._lm, self.eos, self.max_output_length)
+        self._hyps = []
+
+    def decode_step(self, emissions, T, N):
+        dec, K = self._dec, self.options.beam_size
+        raw_y, raw_beam, prev_states = [-1], [-1], [None]
+        t = 0
+        begun = False
+        while t < self.max_output_length:
+            scores, out_states = self.update_func(emissions, N, T, raw_y, raw_beam, prev_states, t)
+            V = max(len(r) for r in scores)
+            if not begun:
+                dec.begin(1, V)
+                begun = True
+            rows = np.full((K, V), np.nan, dtype=np.float32)
+            valid = np.zeros(K, dtype=np.uint8)
+            for k, (r, s) in enumerate(zip(scores, out_states)):
+                rows[k, :len(r)] = np.asarray(r, dtype=np.float32)
+                valid[k] = s is not None
+            out = dec.step(rows, valid)
+            dec.ctx.synchronize()  # (the rows decide the next model call: one host wait per step)
+            tok, beam, src, n = (x.cpu().numpy() if hasattr(x, "cpu") else x for x in out)
+            t += 1
+            n = int(n[0])
+            if n == 0:
+                break
+            raw_y = tok[0, :n].tolist()
+            raw_beam = beam[0, :n].tolist()
+            prev_states = [out_states[int(s)] for s in src[0, :n]]
+        if not begun:  # maxOutputLength 0: the root alone
+            dec.begin(1, 1)
+        dec.end()
+        self._hyps = []
+        for h in dec.results(0):
+            r = DecodeResult(len(h.tokens))
+            r.score, r.emittingModelScore, r.lmScore = h.score, h.am, h.lm
+            r.tokens, r.words = h.tokens.tolist(), h.words.tolist()
+            self._hyps.append(r)
+
+    def prune(self, look_back=0):
+        return None
+
+    def n_decoded_frames_in_buffer(self):
+        return -1
+
+    def get_best_hypothesis(self, look_back=0):
+        return self._hyps[0] if self._hyps else DecodeResult(0)
+
+    def get_all_final_hypothesis(self):
+        return list(self._hyps)

@@ -29,6 +29,7 @@
 #include "fltx.h"
 #include "fltx_kernel_entry.h"
 #include "fltx_engines.h"
+#include "fltx_s2s.h"
 
 using namespace fltx;
 
@@ -134,6 +135,24 @@ __global__ void __launch_bounds__(256) fltx_pack_results_kernel(PackParams Q) {
       wd[i] = ws[i];
     }
   }
+}
+/* fltx_s2s.h: the seq2seq step (front end, step), its start and its back-trace */
+__global__ void __launch_bounds__(256) fltx_s2s_tokbeam_kernel(S2sParams P) {
+  __shared__ __attribute__((aligned(16))) S2sFrontLds fltx_s2s_front[4];
+  s2sTokBeamRows(P, (char*)fltx_s2s_front);
+}
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_s2s_step_kernel(S2sParams P) {
+  __shared__ __attribute__((aligned(16))) S2sStepLds fltx_s2s_lds;
+  s2sStepUtterance(P, (char*)&fltx_s2s_lds);
+}
+__global__ void __launch_bounds__(64) fltx_s2s_begin_kernel(S2sParams P) {
+  const int b = (int)(blockIdx.x * 64 + threadIdx.x);
+  if (b < P.B) {
+    s2sBeginUtterance(P, b);
+  }
+}
+__global__ void __launch_bounds__(256) fltx_s2s_end_kernel(S2sParams P) {
+  s2sEndUtterance(P, (int)blockIdx.x, (int)threadIdx.x, (int)blockDim.x);
 }
 __global__ void __launch_bounds__(1024) fltx_streamop_kernel(StreamOpParams Q) {
   __shared__ int32_t sh[kStreamOpLds / 4];
@@ -565,6 +584,13 @@ struct fltx_decoder {
   bool slotUsed[2] = {false, false};
 #endif
   bool timed = false;
+  /* seq2seq (kind FLTX_DECODER_S2S_LEXFREE, fltx_s2s_*: fltx_s2s.h) */
+  fltx_s2s_options s2sOpt{};
+  int s2sEos = 0, s2sMaxOut = 0, s2sT = 0, s2sCap = 0, s2sMSel = 0, s2sEosExtra = 0;
+  bool s2sBegun = false;
+  int32_t s2sCtx0[kS2sCtx] = {0};
+  DBuf s2sBeam, s2sBeamN, s2sHist, s2sRowsInt, s2sDone, s2sFinal, s2sRecTok, s2sRecAm, s2sRecN, s2sKey;
+  DBuf s2sScores, s2sValid; /* device copies of host inputs */
 };
 
 /* ------------------------------------------------------------------------ */
@@ -3544,6 +3570,9 @@ int fltx_decode_batch(fltx_decoder* d, const float* emissions, int32_t onDevice,
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
+  if (d && d->kind == FLTX_DECODER_S2S_LEXFREE) {
+    return fail(FLTX_ERR_STATE, "fltx_decode_batch: a seq2seq decoder steps with fltx_s2s_step");
+  }
   if (!d || !T || B <= 0 || N <= 0) {
     return fail(FLTX_ERR_INVALID, "fltx_decode_batch: bad argument");
   }
@@ -3772,6 +3801,9 @@ int fltx_stream_begin(fltx_decoder* d, int32_t B, int32_t N, int32_t maxFrames) 
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
+  if (d && d->kind == FLTX_DECODER_S2S_LEXFREE) {
+    return fail(FLTX_ERR_STATE, "fltx_stream_begin: a seq2seq decoder steps with fltx_s2s_step");
+  }
   if (!d || B <= 0 || N <= 0 || maxFrames < 0) {
     return fail(FLTX_ERR_INVALID, "fltx_stream_begin: bad argument");
   }
@@ -3857,6 +3889,9 @@ int fltx_stream_step(fltx_decoder* d, const float* emissions, int32_t onDevice, 
   DeviceScope devScope(d ? d->ctx : nullptr);
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  if (d && d->kind == FLTX_DECODER_S2S_LEXFREE) {
+    return fail(FLTX_ERR_STATE, "fltx_stream_step: a seq2seq decoder steps with fltx_s2s_step");
   }
   if (!d || !T) {
     return fail(FLTX_ERR_INVALID, "fltx_stream_step: bad argument");
@@ -3959,6 +3994,9 @@ int fltx_stream_end(fltx_decoder* d) {
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
+  if (d && d->kind == FLTX_DECODER_S2S_LEXFREE) {
+    return fail(FLTX_ERR_STATE, "fltx_stream_end: a seq2seq decoder steps with fltx_s2s_step");
+  }
   if (!d) {
     return fail(FLTX_ERR_INVALID, "null decoder");
   }
@@ -3997,6 +4035,9 @@ int fltx_stream_prune(fltx_decoder* d, int32_t lookBack) {
   DeviceScope devScope(d ? d->ctx : nullptr);
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  if (d && d->kind == FLTX_DECODER_S2S_LEXFREE) {
+    return fail(FLTX_ERR_STATE, "fltx_stream_prune: a seq2seq decoder steps with fltx_s2s_step");
   }
   if (!d || lookBack < 0) {
     return fail(FLTX_ERR_INVALID, "fltx_stream_prune: bad argument");
@@ -4350,6 +4391,21 @@ int fltx_result_best(fltx_decoder* d, int32_t b, int32_t lookBack, double* score
   if (!d->haveResults) {
     return fail(FLTX_ERR_STATE, "no decode has been run");
   }
+  if (d->kind == FLTX_DECODER_S2S_LEXFREE) { /* getBestHypothesis ignores lookBack: the final beam's first (:165-169) */
+    int32_t n = 0, len = 0;
+    int rc = fltx_result_count(d, b, &n, &len);
+    if (rc) {
+      return rc;
+    }
+    *length = n > 0 ? len : 0;
+    if (n == 0) {
+      return FLTX_OK;
+    }
+    if (len > capacity) {
+      return fail(FLTX_ERR_RANGE, "fltx_result_best: capacity %d < length %d", capacity, len);
+    }
+    return fltx_result_fetch(d, b, 1, scores, tokens, words, &n);
+  }
   if (!d->keepScores) {
     return fail(FLTX_ERR_STATE,
                 "getBestHypothesis needs the per-frame score history: use the streaming calls or "
@@ -4558,6 +4614,340 @@ int fltx_decoder_bytes(fltx_decoder* d, int64_t* decodeBytes, int64_t* epilogueB
   if (lmBytes) {
     *lmBytes = d->statLmBytes;
   }
+  return FLTX_OK;
+}
+
+
+/* ---- seq2seq (fltx_s2s.h) ------------------------------------------------------------------------------------------ */
+static int s2sCheck(fltx_decoder* d, const char* what) {
+  if (!d) {
+    return fail(FLTX_ERR_INVALID, "%s: null decoder", what);
+  }
+  if (d->kind != FLTX_DECODER_S2S_LEXFREE) {
+    return fail(FLTX_ERR_STATE, "%s: not a seq2seq decoder (fltx_s2s_decoder_create)", what);
+  }
+  return FLTX_OK;
+}
+
+static S2sParams s2sParams(fltx_decoder* d) {
+  S2sParams P;
+  memset(&P, 0, sizeof(P));
+  const fltx_lm* lm = d->lm;
+  if (lm->kind == 1) {
+    P.lmOn = 1;
+    P.lmp.lmKind = 1;
+    P.lmp.lmOrder = lm->order;
+    P.lmp.ngTab = d->lmDev->tab.as<NgramSlot>();
+    P.lmp.ngMask = lm->mask;
+    P.lmp.ngBackoff = d->lmDev->backoff.as<float>();
+    P.lmp.usrToLm = d->lmDev->usrToLm.as<int32_t>();
+    P.lmp.nUsr = lm->nUsr;
+    P.lmp.lmBos = lm->bos;
+    P.lmp.lmEos = lm->eos;
+    P.lmp.lmUnk = lm->unk;
+  }
+  P.B = d->B;
+  P.K = d->s2sOpt.beam_size;
+  P.Kt = d->s2sOpt.beam_size_token;
+  P.V = d->N;
+  P.eos = d->s2sEos;
+  P.maxOut = d->s2sMaxOut;
+  P.t = std::min(d->s2sT, d->s2sMaxOut);
+  P.cap = d->s2sCap;
+  P.mSel = d->s2sMSel;
+  P.eosExtra = d->s2sEosExtra;
+  P.beamThreshold = d->s2sOpt.beam_threshold;
+  P.lmWeight = d->s2sOpt.lm_weight;
+  P.eosScore = d->s2sOpt.eos_score;
+  P.beam = d->s2sBeam.as<S2sHyp>();
+  P.beamN = d->s2sBeamN.as<int32_t>();
+  P.hist = d->s2sHist.as<int2>();
+  P.nRowsInt = d->s2sRowsInt.as<int32_t>();
+  P.done = d->s2sDone.as<int32_t>();
+  P.finalStep = d->s2sFinal.as<int32_t>();
+  P.recTok = d->s2sRecTok.as<int32_t>();
+  P.recAm = d->s2sRecAm.as<float>();
+  P.recN = d->s2sRecN.as<int32_t>();
+  P.cKey = d->s2sKey.as<unsigned long long>();
+  P.nC = (int64_t)P.K * P.cap + P.K;
+  for (int j = 0; j < kS2sCtx; ++j) {
+    P.ctx0[j] = d->s2sCtx0[j];
+  }
+  P.len = d->s2sMaxOut + 3;
+  return P;
+}
+
+int fltx_s2s_decoder_create(fltx_ctx* ctx, const fltx_s2s_options* opt, const fltx_lm* lm, int32_t eos,
+                            int32_t maxOut, fltx_decoder** out) {
+  if (!ctx || !opt || !lm || !out) {
+    return fail(FLTX_ERR_INVALID, "fltx_s2s_decoder_create: null argument");
+  }
+  if (opt->beam_size < 1 || opt->beam_size_token < 1) {
+    return fail(FLTX_ERR_INVALID, "beam_size and beam_size_token must be >= 1");
+  }
+  if (opt->beam_size > kS2sMaxBeam) {
+    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq: beam_size %d > %d", opt->beam_size, kS2sMaxBeam);
+  }
+  if (maxOut < 0) {
+    return fail(FLTX_ERR_INVALID, "seq2seq: max_output_length < 0");
+  }
+  if (maxOut > kS2sMaxLen) {
+    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq: max_output_length %d > %d", maxOut, kS2sMaxLen);
+  }
+  if (eos < 0) {
+    return fail(FLTX_ERR_INVALID, "seq2seq: eos index %d < 0", eos);
+  }
+  if (lm->kind == 2) {
+    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq: a user-defined (host) LM is not supported; ZeroLM or n-gram tables only");
+  }
+  if (lm->kind == 1 && lm->order - 1 > kS2sCtx) {
+    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq: n-gram order %d > %d", lm->order, kS2sCtx + 1);
+  }
+  DeviceScope devScope(ctx);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  fltx_lm::Dev* lmDev = nullptr;
+  int rc = lmEnsureUploaded(const_cast<fltx_lm*>(lm), ctx, &lmDev);
+  if (rc) {
+    return rc;
+  }
+  auto* d = new fltx_decoder();
+  d->ctx = ctx;
+  d->lm = lm;
+  d->lmDev = lmDev;
+  d->kind = FLTX_DECODER_S2S_LEXFREE;
+  d->s2sOpt = *opt;
+  d->opt.beam_size = opt->beam_size;
+  d->opt.beam_size_token = opt->beam_size_token;
+  d->opt.beam_threshold = opt->beam_threshold;
+  d->opt.lm_weight = opt->lm_weight;
+  d->opt.log_add = opt->log_add;
+  d->opt.criterion = FLTX_CRITERION_S2S;
+  d->s2sEos = eos;
+  d->s2sMaxOut = maxOut;
+  if (lm->kind == 1) {
+    int32_t c[kMaxNgramOrder] = {0};
+    if ((rc = fltx_lm_start(const_cast<fltx_lm*>(lm), 0, c))) {
+      delete d;
+      return rc;
+    }
+    for (int j = 0; j < kS2sCtx; ++j) {
+      d->s2sCtx0[j] = j < lm->order - 1 ? c[j] : 0;
+    }
+  }
+  *out = d;
+  return FLTX_OK;
+}
+
+/* row lists out: a launch of `kernel` writes them; the emulator runs the same function on host threads */
+int fltx_s2s_begin(fltx_decoder* d, int32_t B, int32_t V, int32_t* nextTok, int32_t* nextBeam, int32_t* nextSrc,
+                   int32_t* nRows) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = s2sCheck(d, "fltx_s2s_begin");
+  if (rc) {
+    return rc;
+  }
+  if (B < 1 || V < 1 || !nextTok || !nextBeam || !nextSrc || !nRows) {
+    return fail(FLTX_ERR_INVALID, "fltx_s2s_begin: bad argument");
+  }
+  if (V > kS2sMaxV) {
+    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq: row width V = %d > %d", V, kS2sMaxV);
+  }
+  const int K = d->s2sOpt.beam_size, Kt = d->s2sOpt.beam_size_token;
+  const int ktEff = std::min(Kt, V);
+  /* without LM terms in the score a row contributes at most K survivors besides eos: its top min(Kt, K + 1) (one more
+   * than K: eos may be among them) and eos when it is in the top Kt are every candidate that can survive */
+  const bool lmTerms = d->lm->kind == 1 && d->s2sOpt.lm_weight != 0.0;
+  if (lmTerms && ktEff > kS2sMaxKtLm) {
+    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq: a token beam of %d (beam_size_token, V = %d) > %d with LM terms", ktEff, V,
+                kS2sMaxKtLm);
+  }
+  d->s2sMSel = lmTerms ? ktEff : std::min(ktEff, K + 1);
+  d->s2sEosExtra = d->s2sMSel < ktEff ? 1 : 0;
+  d->s2sCap = d->s2sMSel + d->s2sEosExtra;
+  Stream st = d->ctx->stream;
+  const size_t BK = (size_t)B * K;
+  const size_t nC = (size_t)K * d->s2sCap + K;
+  if (d->s2sBeam.ensure(2 * BK * sizeof(S2sHyp), st, false) || d->s2sBeamN.ensure(8 * (size_t)B, st, false) ||
+      d->s2sHist.ensure((size_t)(d->s2sMaxOut + 1) * BK * sizeof(int2), st, false) ||
+      d->s2sRowsInt.ensure(4 * (size_t)B, st, false) || d->s2sDone.ensure(4 * (size_t)B, st, false) ||
+      d->s2sFinal.ensure(4 * (size_t)B, st, false) || d->s2sRecTok.ensure(4 * BK * d->s2sCap, st, false) ||
+      d->s2sRecAm.ensure(4 * BK * d->s2sCap, st, false) || d->s2sRecN.ensure(4 * BK, st, false) ||
+      d->s2sKey.ensure(8 * (size_t)B * nC, st, false)) {
+    return fail(FLTX_ERR_OOM, "seq2seq workspace: device allocation failed (B=%d K=%d V=%d)", B, K, V);
+  }
+  d->B = B;
+  d->N = V;
+  d->s2sT = 0;
+  d->s2sBegun = true;
+  d->haveResults = false;
+  d->ended = false;
+  d->backtraced = false;
+  d->resultsSynced = false;
+  S2sParams P = s2sParams(d);
+  P.outTok = nextTok;
+  P.outBeam = nextBeam;
+  P.outSrc = nextSrc;
+  P.outN = nRows;
+#ifdef FLTX_EMU
+  const S2sParams* pp = &P;
+  emuLaunch((B + 63) / 64, 64, 0, [pp](char*) {
+    const int b = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (b < pp->B) {
+      s2sBeginUtterance(*pp, b);
+    }
+  });
+#else
+  hipLaunchKernelGGL(fltx_s2s_begin_kernel, dim3((B + 63) / 64), dim3(64), 0, st, P);
+  HIPCHK(hipGetLastError());
+#endif
+  return FLTX_OK;
+}
+
+int fltx_s2s_step(fltx_decoder* d, const float* scores, int32_t onDevice, int64_t rowStride, const uint8_t* rowValid,
+                  int32_t* nextTok, int32_t* nextBeam, int32_t* nextSrc, int32_t* nRows) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = s2sCheck(d, "fltx_s2s_step");
+  if (rc) {
+    return rc;
+  }
+  if (!d->s2sBegun) {
+    return fail(FLTX_ERR_STATE, "fltx_s2s_step: fltx_s2s_begin first");
+  }
+  if (!nextTok || !nextBeam || !nextSrc || !nRows || (!scores && d->s2sT < d->s2sMaxOut) || rowStride < d->N) {
+    return fail(FLTX_ERR_INVALID, "fltx_s2s_step: bad argument (row_stride %lld, V = %d)", (long long)rowStride, d->N);
+  }
+  Stream st = d->ctx->stream;
+  const size_t BK = (size_t)d->B * d->s2sOpt.beam_size;
+  const bool last = d->s2sT >= d->s2sMaxOut; /* nothing to score: the kernels only list no rows */
+  if (!onDevice && !last) {
+    const size_t nF = (BK - 1) * (size_t)rowStride + (size_t)d->N;
+    if (d->s2sScores.ensure(4 * nF, st, false) || (rowValid && d->s2sValid.ensure(BK, st, false))) {
+      return fail(FLTX_ERR_OOM, "seq2seq: staging allocation failed");
+    }
+    if (devCopyH2D(d->s2sScores.p, scores, 4 * nF, st) || (rowValid && devCopyH2D(d->s2sValid.p, rowValid, BK, st))) {
+      return fail(FLTX_ERR_HIP, "seq2seq: upload failed");
+    }
+    scores = d->s2sScores.as<float>();
+    rowValid = rowValid ? d->s2sValid.as<uint8_t>() : nullptr;
+  }
+  S2sParams P = s2sParams(d);
+  P.scores = scores;
+  P.rowStride = rowStride;
+  P.rowValid = rowValid;
+  P.outTok = nextTok;
+  P.outBeam = nextBeam;
+  P.outSrc = nextSrc;
+  P.outN = nRows;
+  const int nFront = (int)((BK + 3) / 4);
+#ifdef FLTX_EMU
+  const S2sParams* pp = &P;
+  if (!last) {
+    emuLaunch(nFront, 256, 4 * sizeof(S2sFrontLds), [pp](char* smem) { s2sTokBeamRows(*pp, smem); });
+  }
+  emuLaunch(d->B, kS2sStepThreads, sizeof(S2sStepLds), [pp](char* smem) { s2sStepUtterance(*pp, smem); });
+#else
+  if (!last) {
+    hipLaunchKernelGGL(fltx_s2s_tokbeam_kernel, dim3(nFront), dim3(256), 0, st, P);
+    HIPCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(fltx_s2s_step_kernel, dim3(d->B), dim3(kS2sStepThreads), 0, st, P);
+  HIPCHK(hipGetLastError());
+#endif
+  if (!last) {
+    ++d->s2sT;
+  }
+  return FLTX_OK;
+}
+
+int fltx_s2s_done(fltx_decoder* d, int32_t* done) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = s2sCheck(d, "fltx_s2s_done");
+  if (rc) {
+    return rc;
+  }
+  if (!done) {
+    return fail(FLTX_ERR_INVALID, "fltx_s2s_done: null argument");
+  }
+  if (!d->s2sBegun) {
+    return fail(FLTX_ERR_STATE, "fltx_s2s_done: fltx_s2s_begin first");
+  }
+  if (d->s2sT >= d->s2sMaxOut) {
+    *done = 1;
+    return FLTX_OK;
+  }
+  std::vector<int32_t> h((size_t)d->B);
+  if (devCopyD2H(h.data(), d->s2sDone.p, 4 * (size_t)d->B, d->ctx->stream) || devSync(d->ctx->stream)) {
+    return fail(FLTX_ERR_HIP, "fltx_s2s_done: copy failed: %s", devErr());
+  }
+  *done = 1;
+  for (int32_t v : h) {
+    *done = *done && v != 0;
+  }
+  return FLTX_OK;
+}
+
+int fltx_s2s_end(fltx_decoder* d) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = s2sCheck(d, "fltx_s2s_end");
+  if (rc) {
+    return rc;
+  }
+  if (!d->s2sBegun) {
+    return fail(FLTX_ERR_STATE, "fltx_s2s_end: fltx_s2s_begin first");
+  }
+  Stream st = d->ctx->stream;
+  const int B = d->B, K = d->s2sOpt.beam_size, len = d->s2sMaxOut + 3;
+  d->histOff.resize((size_t)B + 1);
+  for (int b = 0; b <= B; ++b) {
+    d->histOff[b] = (int64_t)b * K * len;
+  }
+  d->histRecords = (int64_t)B * K * len;
+  if (d->outScores.ensure(24 * (size_t)B * K, st, false) || d->tokens.ensure(4 * (size_t)d->histRecords, st, false) ||
+      d->outN.ensure(4 * (size_t)B, st, false) || d->uttNBeam.ensure(4 * (size_t)B, st, false) ||
+      d->uttFrame.ensure(4 * (size_t)B, st, false) || d->uttStatus.ensure(4 * (size_t)B, st, false) ||
+      d->histOffD.ensure(8 * ((size_t)B + 1), st, false)) {
+    return fail(FLTX_ERR_OOM, "seq2seq results: device allocation failed");
+  }
+  if (devCopyH2D(d->histOffD.p, d->histOff.data(), 8 * ((size_t)B + 1), st)) {
+    return fail(FLTX_ERR_HIP, "seq2seq results: upload failed");
+  }
+  S2sParams P = s2sParams(d);
+  P.outScores = d->outScores.as<double>();
+  P.tokens = d->tokens.as<int32_t>();
+  P.outNHyp = d->outN.as<int32_t>();
+  P.uttNBeam = d->uttNBeam.as<int32_t>();
+  P.uttFrame = d->uttFrame.as<int32_t>();
+  P.uttStatus = d->uttStatus.as<int32_t>();
+#ifdef FLTX_EMU
+  const S2sParams* pp = &P;
+  emuLaunch(B, 64, 0, [pp](char*) { s2sEndUtterance(*pp, (int)blockIdx.x, (int)threadIdx.x, 64); });
+#else
+  hipLaunchKernelGGL(fltx_s2s_end_kernel, dim3(B), dim3(256), 0, st, P);
+  HIPCHK(hipGetLastError());
+#endif
+  d->haveResults = true;
+  d->ended = true;
+  d->backtraced = true;
+  d->streaming = false;
+  d->resultsSynced = false;
+  d->hostFetched = false;
+  d->compactFetched = false;
+  d->scoresFetched = false;
+  d->offlinePending = false;
   return FLTX_OK;
 }
 

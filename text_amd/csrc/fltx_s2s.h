@@ -1,0 +1,538 @@
+/*
+ * fltx_s2s.h -- the lexicon-free seq2seq beam search (LexiconFreeSeq2SeqDecoder.cpp:20-165) as a batched device step.
+ *
+ * The emitting model is the caller's: it runs between two steps (a PyTorch attention decoder on the same stream) and
+ * leaves one row of V scores per live hypothesis in HBM.  A step is two kernels:
+ *   fltx_s2s_tokbeam_kernel  one wave per live row, all rows of the batch: the row's token beam (its largest scores,
+ *                            LexiconFreeSeq2SeqDecoder.cpp:87-107), written as a compact record;
+ *   fltx_s2s_step_kernel     one workgroup per utterance: the candidates of the step from the records and the carried
+ *                            finished hypotheses, their scores with the device LM (ZeroLM / the n-gram tables), the
+ *                            threshold and the top K (Utils.h:121-228), the new beam, one history record per
+ *                            hypothesis, and the next step's row list (what the model gathers its state with).
+ * fltx_s2s_end_kernel writes the n-best in the layout fltx_result_* read.
+ *
+ * Both selections are a most-significant-digit-first radix select over order keys (f32Key / f64Key, 256 bins per
+ * pass, slScan finds the bin that holds the cut): exact, the ties at the cut to the lower index.
+ *
+ * No merges: the reference compares LM-state OBJECTS (compareNoScoreStates), and ZeroLM / KenLM hand out a new child
+ * object per (state, token), so two candidates of one step never share a state and candidatesStore's merge -- logAdd
+ * with it -- never fires.  A hypothesis carries its n-gram context (the suffix node ids ngScore takes) in its record.
+ */
+#pragma once
+
+namespace fltx {
+
+constexpr int kS2sMaxBeam = 256;     /* beamSize */
+constexpr int kS2sMaxV = 65536;      /* row width */
+constexpr int kS2sMaxKtLm = 64;      /* min(beamSizeToken, V) with a scoring LM (lmWeight != 0, n-gram) */
+constexpr int kS2sMaxLen = 4096;     /* maxOutputLength */
+constexpr int kS2sCtx = kMaxNgramOrder - 1;
+constexpr int kS2sStepThreads = 256; /* the step kernel: one thread per beam slot */
+
+struct S2sHyp { /* one hypothesis of a beam, 56 B */
+  double score, am, lm;
+  int32_t token;  /* -1: the root */
+  int32_t parent; /* index in the previous beam (prevHypIdx) */
+  int32_t ctx[kS2sCtx];
+  int32_t pad;
+};
+
+struct S2sParams {
+  DecodeParams lmp; /* the LM fields only (ngScore reads them) */
+  int32_t B, K, Kt, V, eos, maxOut;
+  int32_t t;        /* steps taken before this one (beam parity t & 1 is the current beam) */
+  int32_t cap;      /* entries per row record */
+  int32_t mSel;     /* tokens per row the front end keeps */
+  int32_t eosExtra; /* 1: mSel < min(Kt, V) (exact shortcut without LM terms): eos is added when it is in the top Kt */
+  int32_t lmOn;     /* n-gram LM: score / finish on the device tables */
+  double beamThreshold, lmWeight, eosScore;
+  const float* scores;
+  int64_t rowStride;
+  const uint8_t* rowValid; /* may be null */
+  S2sHyp* beam;            /* [2][B*K] */
+  int32_t* beamN;          /* [2][B] */
+  int2* hist;              /* [maxOut + 1][B*K]: (token, parent) of the hypotheses of step s */
+  int32_t* nRowsInt;       /* [B] rows of the current step */
+  int32_t* done;           /* [B] */
+  int32_t* finalStep;      /* [B] the step whose beam is the final one (valid when done) */
+  int32_t* recTok;         /* [B*K][cap] */
+  float* recAm;
+  int32_t* recN;           /* [B*K] */
+  unsigned long long* cKey; /* [B][nC]: order keys of the step's candidates, 0 = none */
+  int64_t nC;
+  int32_t ctx0[kS2sCtx];   /* LM::start(false) */
+  int32_t *outTok, *outBeam, *outSrc, *outN; /* the caller's next-row lists [B*K], [B] */
+  /* end */
+  double* outScores;
+  int32_t* tokens;
+  int32_t *outNHyp, *uttNBeam, *uttFrame, *uttStatus;
+  int32_t len;
+};
+
+/* ---- LM ------------------------------------------------------------------------------------------------------- */
+/* LM::score (KenLM.cpp:63-75: child state per token) and LM::finish of the n-gram tables; ZeroLM: 0 */
+FLTX_DEV float s2sLm(const S2sParams& P, const int32_t* ctx, int tok, int32_t* ctxOut) {
+  if (!P.lmOn) {
+    return 0.0f;
+  }
+  const DecodeParams& L = P.lmp;
+  uint32_t word;
+  if (tok == P.eos) {
+    word = (uint32_t)L.lmEos;
+  } else {
+    word = (tok >= 0 && tok < L.nUsr) ? (uint32_t)L.usrToLm[tok] : (uint32_t)L.lmUnk;
+  }
+  return ngScore(L, ctx, word, ctxOut);
+}
+
+/* the candidate (hypothesis h, token tok, emitting-model score a): LexiconFreeSeq2SeqDecoder.cpp:113-141, the same
+ * double operations in the same order (the library is built with -ffp-contract=off) */
+FLTX_DEV double s2sScore(const S2sParams& P, const S2sHyp& h, int tok, float a, float lmS) {
+  if (tok == P.eos) {
+    return ((h.score + (double)a) + P.eosScore) + P.lmWeight * (double)lmS;
+  }
+  return (h.score + (double)a) + P.lmWeight * (double)lmS;
+}
+
+/* ---- front end: the token beam of every live row ----------------------------------------------------------------- */
+struct S2sFrontLds { /* per wave */
+  uint32_t hist[kSlNB];
+};
+
+/* key of a score: NaN is never a candidate (0) */
+FLTX_DEV uint32_t s2sKey32(float x) { return x == x ? f32Key(x + 0.0f) : 0u; }
+
+FLTX_DEV void s2sTokBeamRow(const S2sParams& P, S2sFrontLds& S, const float* row, int32_t* tok, float* am,
+                            int32_t* nOut) {
+  const int lane = laneId();
+  const int V = P.V, m = P.mSel;
+  /* passes over the digits, most significant first: pre / msk = the digits decided so far, `need` = how many of the
+   * values that share them the token beam still takes */
+  uint32_t pre = 0u, msk = 0u;
+  int need = m;
+  bool all = m >= V, allEq = false;
+  for (int shift = 24; shift >= 0 && !all && !allEq; shift -= 8) {
+    waveSync();
+    ((uint4*)S.hist)[lane] = make_uint4(0u, 0u, 0u, 0u);
+    waveSync();
+    for (int i = lane; i < V; i += 64) {
+      const uint32_t k = s2sKey32(row[i]);
+      if (k != 0u && (k & msk) == pre) {
+        atomAdd32(&S.hist[255u - ((k >> shift) & 255u)], 1u);
+      }
+    }
+    waveSync();
+    const SlScan sc = slScan(S.hist, need, false);
+    if (sc.total <= need) { /* (first pass: no more values than the beam takes) */
+      all = true;
+      break;
+    }
+    need -= sc.cum;
+    pre |= (uint32_t)(255 - sc.bstar) << shift;
+    msk |= 255u << shift;
+    allEq = sc.cnt == need;
+  }
+  /* the list, in token order: the values above the decided digits, and the first `need` of those equal to them */
+  int nList = 0, eqSeen = 0;
+  bool eosIn = false;
+  for (int c = 0; c < V; c += 64) {
+    const int i = c + lane;
+    const float x = i < V ? row[i] : 0.0f;
+    const uint32_t k = i < V ? s2sKey32(x) : 0u;
+    bool sel = k != 0u && (all || (k & msk) > pre);
+    if (!all) {
+      const bool eq = k != 0u && (k & msk) == pre;
+      const unsigned long long eb = waveBallot(eq);
+      sel = sel || (eq && (allEq || eqSeen + wavePrefixCount(eb) < need));
+      eqSeen += popc64(eb);
+    }
+    const unsigned long long sb = waveBallot(sel);
+    if (sel) {
+      const int pos = nList + wavePrefixCount(sb);
+      tok[pos] = i;
+      am[pos] = x;
+    }
+    const bool eosHere = waveBallot(sel && i == P.eos) != 0ull;
+    eosIn = eosIn || eosHere;
+    nList += popc64(sb);
+  }
+  /* the shortcut kept fewer than the token beam: eos still is a candidate when it is among the row's Kt best (ties to
+   * the lower token, as above) */
+  if (P.eosExtra && !eosIn && P.eos >= 0 && P.eos < V) {
+    const float xe = row[P.eos];
+    const uint32_t ke = s2sKey32(xe);
+    if (ke != 0u) {
+      int above = 0;
+      for (int i = lane; i < V; i += 64) {
+        const uint32_t k = s2sKey32(row[i]);
+        above += (k > ke || (k == ke && i < P.eos)) ? 1 : 0;
+      }
+      above = (int)waveReadLane32((uint32_t)waveInclusiveScan(above), 63);
+      if (above < P.Kt) {
+        if (lane == 0) {
+          tok[nList] = P.eos;
+          am[nList] = xe;
+        }
+        ++nList;
+      }
+    }
+  }
+  if (lane == 0) {
+    *nOut = nList;
+  }
+}
+
+/* workgroup = four waves, wave = row b*K + k of the step */
+FLTX_DEV void s2sTokBeamRows(const S2sParams& P, char* smem) {
+  const int wave = waveUniform(waveId());
+  const int64_t r = (int64_t)blockIdx.x * ((int)blockDim.x >> 6) + wave;
+  if (r >= (int64_t)P.B * P.K) {
+    return;
+  }
+  const int b = (int)(r / P.K), k = (int)(r % P.K);
+  const bool live = !P.done[b] && P.t < P.maxOut && k < P.nRowsInt[b] && (P.rowValid == nullptr || P.rowValid[r] != 0);
+  if (!live) {
+    if (laneId() == 0) {
+      P.recN[r] = 0;
+    }
+    return;
+  }
+  S2sFrontLds& S = ((S2sFrontLds*)smem)[wave];
+  s2sTokBeamRow(P, S, P.scores + r * P.rowStride, P.recTok + r * P.cap, P.recAm + r * P.cap, P.recN + r);
+}
+
+/* ---- the step: one workgroup of kS2sStepThreads per utterance ---------------------------------------------------- */
+struct S2sStepLds {
+  uint32_t hist[kSlNB];
+  unsigned long long wmax[kS2sStepThreads / 64];
+  int32_t wcnt[kS2sStepThreads / 64];
+  int32_t rowOfHyp[kS2sMaxBeam]; /* hypothesis of the current beam -> its row in this step's call, -1: finished */
+  int32_t hypOfRow[kS2sMaxBeam];
+  uint32_t selIdx[kS2sMaxBeam];
+  unsigned long long selKey[kS2sMaxBeam];
+  int32_t order[kS2sMaxBeam];
+  unsigned long long pre, msk;
+  int32_t need, allEq, nSel, nSurv;
+  int64_t eqCut;
+  int32_t scanBstar, scanCum, scanCnt, scanTotal;
+};
+
+/* position of this thread's flag among the set flags of threads before it; *total = flags of the workgroup */
+FLTX_DEV int s2sBlockRank(S2sStepLds& S, bool flag, int* total) {
+  const int wave = waveId(), lane = laneId();
+  const unsigned long long bl = waveBallot(flag);
+  __syncthreads();
+  if (lane == 0) {
+    S.wcnt[wave] = popc64(bl);
+  }
+  __syncthreads();
+  int base = 0, all = 0;
+  for (int w = 0; w < kS2sStepThreads / 64; ++w) {
+    base += w < wave ? S.wcnt[w] : 0;
+    all += S.wcnt[w];
+  }
+  *total = all;
+  return base + wavePrefixCount(bl);
+}
+
+/* sum of v over the workgroup, in every thread */
+FLTX_DEV int s2sBlockSum(S2sStepLds& S, int v) {
+  const int s = (int)waveReadLane32((uint32_t)waveInclusiveScan(v), 63);
+  __syncthreads();
+  if (laneId() == 0) {
+    S.wcnt[waveId()] = s;
+  }
+  __syncthreads();
+  int all = 0;
+  for (int w = 0; w < kS2sStepThreads / 64; ++w) {
+    all += S.wcnt[w];
+  }
+  return all;
+}
+
+/* candidate j of the utterance: row k = j / cap, entry e = j % cap for j < nRows*cap; then the carried hypotheses */
+FLTX_DEV void s2sStepUtterance(const S2sParams& P, char* smem) {
+  S2sStepLds& S = *(S2sStepLds*)smem;
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+  const int K = P.K;
+  const int64_t rb = (int64_t)b * K;
+  const int lane = laneId(), wave = waveId();
+  if (P.done[b] || P.t >= P.maxOut) { /* a step after the last one: nothing to score */
+    for (int k = tid; k < K; k += kS2sStepThreads) {
+      P.outTok[rb + k] = -1;
+      P.outBeam[rb + k] = -1;
+      P.outSrc[rb + k] = -1;
+    }
+    if (tid == 0) {
+      P.outN[b] = 0;
+    }
+    return;
+  }
+  const int par = P.t & 1;
+  const S2sHyp* prev = P.beam + (size_t)par * P.B * K + rb;
+  S2sHyp* next = P.beam + (size_t)(par ^ 1) * P.B * K + rb;
+  const int nPrev = P.beamN[par * P.B + b];
+  const int nRows = P.nRowsInt[b];
+  const int cap = P.cap;
+  /* 1. rows <-> hypotheses (the live ones in beam order: LexiconFreeSeq2SeqDecoder.cpp:44-55) */
+  {
+    const bool isLive = tid < nPrev && prev[tid].token != P.eos;
+    int tot;
+    const int q = s2sBlockRank(S, isLive, &tot);
+    if (tid < nPrev) {
+      S.rowOfHyp[tid] = isLive ? q : -1;
+      if (isLive) {
+        S.hypOfRow[q] = tid;
+      }
+    }
+    __syncthreads();
+  }
+  /* 2. the candidates' keys and the best of the step */
+  unsigned long long* cKey = P.cKey + (size_t)b * P.nC;
+  const int64_t nRowC = (int64_t)nRows * cap, n = nRowC + nPrev;
+  unsigned long long mx = 0ull;
+  for (int64_t j = tid; j < n; j += kS2sStepThreads) {
+    unsigned long long key = 0ull;
+    if (j < nRowC) {
+      const int k = (int)(j / cap), e = (int)(j % cap);
+      const int64_t r = rb + k;
+      if (e < P.recN[r]) {
+        const S2sHyp& h = prev[S.hypOfRow[k]];
+        const int tok = P.recTok[r * cap + e];
+        const float lmS = s2sLm(P, h.ctx, tok, nullptr);
+        const double s = s2sScore(P, h, tok, P.recAm[r * cap + e], lmS);
+        key = s == s ? f64Key(s + 0.0) : 0ull; /* (+0.0: -0 and +0 compare equal, as the reference's doubles do) */
+      }
+    } else {
+      const S2sHyp& h = prev[j - nRowC];
+      if (h.token == P.eos) { /* a finished hypothesis is carried unchanged (:68-82) */
+        key = h.score == h.score ? f64Key(h.score + 0.0) : 0ull;
+      }
+    }
+    cKey[j] = key;
+    mx = key > mx ? key : mx;
+  }
+  mx = waveMax64(mx);
+  if (lane == 0) {
+    S.wmax[wave] = mx;
+  }
+  __syncthreads();
+  for (int w = 0; w < kS2sStepThreads / 64; ++w) {
+    mx = S.wmax[w] > mx ? S.wmax[w] : mx;
+  }
+  /* 3. threshold (candidatesAdd / candidatesStore: score >= best - beamThreshold, best over the whole step) */
+  unsigned long long thrKey = 1ull;
+  if (mx != 0ull) {
+    const double thr = f64FromKey(mx) - P.beamThreshold;
+    thrKey = thr == thr ? f64Key(thr + 0.0) : ~0ull;
+    thrKey = thrKey == 0ull ? 1ull : thrKey;
+  }
+  int surv = 0;
+  for (int64_t j = tid; j < n; j += kS2sStepThreads) {
+    const unsigned long long key = cKey[j];
+    if (key != 0ull && key < thrKey) {
+      cKey[j] = 0ull;
+    } else if (key != 0ull) {
+      ++surv;
+    }
+  }
+  const int nSurv = s2sBlockSum(S, surv);
+  /* 4. the K best survivors: radix select over the 64-bit keys */
+  unsigned long long pre = 0ull, msk = 0ull;
+  bool all = nSurv <= K, allEq = false;
+  int need = K;
+  int64_t eqCut = -1;
+  for (int shift = 56; shift >= 0 && !all && !allEq; shift -= 8) {
+    __syncthreads();
+    S.hist[tid] = 0u; /* (kS2sStepThreads == kSlNB) */
+    __syncthreads();
+    for (int64_t j = tid; j < n; j += kS2sStepThreads) {
+      const unsigned long long key = cKey[j];
+      if (key != 0ull && (key & msk) == pre) {
+        atomAdd32(&S.hist[255u - (uint32_t)((key >> shift) & 255ull)], 1u);
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {
+      const SlScan sc = slScan(S.hist, need, false);
+      if (lane == 0) {
+        S.scanBstar = sc.bstar;
+        S.scanCum = sc.cum;
+        S.scanCnt = sc.cnt;
+      }
+    }
+    __syncthreads();
+    need -= S.scanCum;
+    pre |= (unsigned long long)(255 - S.scanBstar) << shift;
+    msk |= 255ull << shift;
+    allEq = S.scanCnt == need;
+  }
+  if (!all && !allEq) { /* equal keys at the cut (exact ties of the double scores): the lower candidate indices --
+                           * the need-th equal key in index order, 256 candidates per round */
+    int seen = 0;
+    for (int64_t j0 = 0; j0 < n && eqCut < 0; j0 += kS2sStepThreads) {
+      const int64_t j = j0 + tid;
+      const bool eq = j < n && cKey[j] == pre;
+      int tot;
+      const int r = s2sBlockRank(S, eq, &tot);
+      if (eq && seen + r == need - 1) {
+        S.eqCut = j;
+      }
+      __syncthreads();
+      if (seen + tot >= need) {
+        eqCut = S.eqCut;
+      }
+      seen += tot;
+    }
+  }
+  /* 5. the selected, then sorted best first (returnSorted: Utils.h:204-216) */
+  if (tid == 0) {
+    S.nSel = 0;
+  }
+  __syncthreads();
+  for (int64_t j = tid; j < n; j += kS2sStepThreads) {
+    const unsigned long long key = cKey[j];
+    const bool sel = key != 0ull && (all || (key & msk) > pre || ((key & msk) == pre && (allEq || j <= eqCut)));
+    if (sel) {
+      const uint32_t p = atomAdd32((uint32_t*)&S.nSel, 1u);
+      if (p < (uint32_t)K) { /* (exactly K are selected; the bound only guards the list) */
+        S.selIdx[p] = (uint32_t)j;
+        S.selKey[p] = key;
+      }
+    }
+  }
+  __syncthreads();
+  const int nSel = S.nSel < K ? S.nSel : K;
+  if (tid < nSel) {
+    const unsigned long long mk = S.selKey[tid];
+    const uint32_t mi = S.selIdx[tid];
+    int rank = 0;
+    for (int q = 0; q < nSel; ++q) {
+      const unsigned long long ok = S.selKey[q];
+      rank += (ok > mk || (ok == mk && S.selIdx[q] < mi)) ? 1 : 0;
+    }
+    S.order[rank] = tid;
+  }
+  __syncthreads();
+  /* 6. the new beam, its history records and the next call's rows */
+  S2sHyp nh;
+  bool isLive = false;
+  int srcRow = -1;
+  if (tid < nSel) {
+    const int64_t j = S.selIdx[S.order[tid]];
+    if (j < nRowC) {
+      const int k = (int)(j / cap), e = (int)(j % cap);
+      const int64_t r = rb + k;
+      const int i = S.hypOfRow[k];
+      const S2sHyp& h = prev[i];
+      const int tok = P.recTok[r * cap + e];
+      const float a = P.recAm[r * cap + e];
+      nh = h;
+      const float lmS = s2sLm(P, h.ctx, tok, tok == P.eos ? nullptr : nh.ctx);
+      nh.score = s2sScore(P, h, tok, a, lmS);
+      nh.am = h.am + (double)a;
+      nh.lm = h.lm + (double)lmS;
+      nh.token = tok;
+      nh.parent = i;
+      isLive = tok != P.eos;
+      srcRow = (int)rb + k;
+    } else {
+      const int i = (int)(j - nRowC);
+      nh = prev[i];
+      nh.parent = i;
+    }
+    next[tid] = nh;
+    P.hist[(size_t)(P.t + 1) * P.B * K + rb + tid] = make_int2(nh.token, nh.parent);
+  }
+  int nLive;
+  const int q = s2sBlockRank(S, isLive, &nLive);
+  const bool fin = nSel == 0 || nLive == 0 || P.t + 1 >= P.maxOut;
+  if (fin) {
+    nLive = 0;
+  }
+  if (isLive && !fin) {
+    P.outTok[rb + q] = nh.token;
+    P.outBeam[rb + q] = nh.parent;
+    P.outSrc[rb + q] = srcRow;
+  }
+  for (int k = nLive + tid; k < K; k += kS2sStepThreads) {
+    P.outTok[rb + k] = -1;
+    P.outBeam[rb + k] = -1;
+    P.outSrc[rb + k] = -1;
+  }
+  if (tid == 0) {
+    P.outN[b] = nLive;
+    P.nRowsInt[b] = nLive;
+    if (nSel > 0) {
+      P.beamN[(par ^ 1) * P.B + b] = nSel;
+    }
+    if (fin) {
+      P.done[b] = 1;
+      P.finalStep[b] = nSel > 0 ? P.t + 1 : P.t; /* the last non-empty beam (:152-158) */
+    }
+  }
+}
+
+/* decodeStep's start (:30-32): the root, and the first call's single row (token -1, beam index -1, no source row) */
+FLTX_DEV void s2sBeginUtterance(const S2sParams& P, int b) {
+  const int64_t rb = (int64_t)b * P.K;
+  S2sHyp h;
+  h.score = 0.0;
+  h.am = 0.0;
+  h.lm = 0.0;
+  h.token = -1;
+  h.parent = -1;
+  for (int j = 0; j < kS2sCtx; ++j) {
+    h.ctx[j] = P.ctx0[j];
+  }
+  h.pad = 0;
+  P.beam[rb] = h;
+  P.beamN[b] = 1;
+  const int live = P.maxOut > 0 ? 1 : 0;
+  P.nRowsInt[b] = live;
+  P.done[b] = live ? 0 : 1;
+  P.finalStep[b] = 0;
+  for (int k = 0; k < P.K; ++k) {
+    P.outTok[rb + k] = -1;
+    P.outBeam[rb + k] = -1;
+    P.outSrc[rb + k] = -1;
+  }
+  P.outN[b] = live;
+}
+
+/* getAllFinalHypothesis (:160-163, Utils.h:230-266): the final beam's paths, right-aligned in rows of `len` =
+ * maxOutputLength + 3 tokens with -1 in front; thread per hypothesis */
+FLTX_DEV void s2sEndUtterance(const S2sParams& P, int b, int tid, int nThreads) {
+  const int K = P.K;
+  const int64_t rb = (int64_t)b * K;
+  const int fs = P.done[b] ? P.finalStep[b] : P.t;
+  const int par = fs & 1;
+  const int n = P.beamN[par * P.B + b];
+  const S2sHyp* beam = P.beam + (size_t)par * P.B * K + rb;
+  const int len = P.len;
+  for (int k = tid; k < n; k += nThreads) {
+    const S2sHyp& h = beam[k];
+    double* sc = P.outScores + (rb + k) * 3;
+    sc[0] = h.score;
+    sc[1] = h.am;
+    sc[2] = h.lm;
+    int32_t* out = P.tokens + (rb + k) * len;
+    for (int f = 0; f < len - fs; ++f) {
+      out[f] = -1;
+    }
+    int p = k;
+    for (int s = fs; s >= 1; --s) {
+      const int2 rec = P.hist[(size_t)s * P.B * K + rb + p];
+      out[len - 1 - (fs - s)] = rec.x;
+      p = rec.y;
+    }
+  }
+  if (tid == 0) {
+    P.outNHyp[b] = n;
+    P.uttNBeam[b] = n;
+    P.uttFrame[b] = len - 1;
+    P.uttStatus[b] = 0;
+  }
+}
+
+} // namespace fltx

@@ -5,7 +5,8 @@
  * classes, so `from flashlight.lib.text.decoder import ...` code runs on the
  * MI355X path (see text_amd/compat/).  Same class names, constructor keywords,
  * method names, raw-address emissions (`ndarray.ctypes.data`) and pickle
- * support; seq2seq classes are out of scope.  Additive: decode_batch().
+ * support.  The lexicon-free seq2seq names are Python classes of the compat package
+ * (text_amd/compat/.../decoder/_seq2seq.py over fltx_s2s_*).  Additive: decode_batch().
  */
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
