@@ -45,7 +45,7 @@ enum {
 enum { FLTX_CRITERION_ASG = 0, FLTX_CRITERION_CTC = 1, FLTX_CRITERION_S2S = 2 };
 /* SmearingMode, decoder/Trie.h:21-25. */
 enum { FLTX_SMEAR_NONE = 0, FLTX_SMEAR_MAX = 1, FLTX_SMEAR_LOGADD = 2 };
-enum { FLTX_DECODER_LEXFREE = 0, FLTX_DECODER_LEXICON = 1, FLTX_DECODER_S2S_LEXFREE = 2 };
+enum { FLTX_DECODER_LEXFREE = 0, FLTX_DECODER_LEXICON = 1, FLTX_DECODER_S2S_LEXFREE = 2, FLTX_DECODER_S2S_LEXICON = 3 };
 
 /* LexiconDecoderOptions (decoder/LexiconDecoder.h:21-31); the lexicon-free
  * decoder (decoder/LexiconFreeDecoder.h:20-28) ignores word_score/unk_score. */
@@ -289,6 +289,42 @@ FLTX_API int fltx_s2s_done(fltx_decoder* dec, int32_t* done);
 /* The back-trace (:152-163): every utterance's final beam -- the last non-empty one, which may hold unfinished
  * hypotheses -- becomes the decoder's results. */
 FLTX_API int fltx_s2s_end(fltx_decoder* dec);
+
+/* ---- seq2seq: LexiconSeq2SeqDecoder as a batched device step --------------- */
+/* LexiconSeq2SeqDecoderOptions (decoder/LexiconSeq2SeqDecoder.h:23-31). */
+typedef struct fltx_s2s_lex_options {
+  int32_t beam_size;
+  int32_t beam_size_token;
+  double beam_threshold;
+  double lm_weight;
+  double word_score;
+  double eos_score;
+  int32_t log_add; /* how merged hypotheses combine: logAdd of their scores, else the max */
+} fltx_s2s_lex_options;
+
+/* LexiconSeq2SeqDecoder(opt, lexicon, lm, eos, emittingModelUpdateFunc, maxOutputLength, isLmToken)
+ * (decoder/LexiconSeq2SeqDecoder.h:116-133, .cpp:20-231) for B utterances at once: an attention model's output
+ * constrained to the spellings of `trie` (a host trie, already smeared; copied into a compact device layout -- per node
+ * its maxScore, labels and children sorted by token, bytes proportional to nodes + edges -- so the trie may be
+ * destroyed afterwards), whole words scored by `lm` over word ids (token ids when is_lm_token != 0).  The decoder runs
+ * through fltx_s2s_begin / step / done / end with the lexicon-free decoder's row contract (next_beam_idx: the parent's
+ * index in the previous beam), and its results carry words (fltx_result_*: the word a hypothesis ended at a token, -1
+ * elsewhere).  Candidates in one LM state, trie node and token merge exactly as candidatesStore does (Utils.h:146-225:
+ * max, or logAdd when log_add != 0).
+ * Limits (FLTX_ERR_UNSUPPORTED beyond them; there is no CPU fallback): beam_size <= 256, V <= 65 536,
+ * max_output_length <= 4 096, min(beam_size_token, V) <= 256 (fltx_s2s_begin), ZeroLM or n-gram LMs only (a host LM
+ * is refused).  Each utterance names its LM states in a table of min(beam_size * max_output_length + 1, max_states)
+ * entries (max_states: 65 536, or fltx_s2s_lex_set_max_states); an utterance that needs more stops, and
+ * fltx_result_count reports FLTX_ERR_UNSUPPORTED ("LM-state table full") for it. */
+FLTX_API int fltx_s2s_lex_decoder_create(fltx_ctx* ctx, const fltx_s2s_lex_options* opt, const fltx_htrie* trie,
+                                         const fltx_lm* lm, int32_t eos, int32_t max_output_length,
+                                         int32_t is_lm_token, fltx_decoder** out);
+/* LM states per utterance from the next fltx_s2s_begin on (>= 1). */
+FLTX_API int fltx_s2s_lex_set_max_states(fltx_decoder* dec, int32_t max_states);
+/* The device trie's bytes, nodes and edges; merges (may be NULL, else B entries, valid after fltx_s2s_begin): the
+ * candidates of each utterance folded into another since fltx_s2s_begin (synchronises). */
+FLTX_API int fltx_s2s_lex_info(fltx_decoder* dec, int64_t* trie_bytes, int64_t* n_nodes, int64_t* n_edges,
+                               int32_t* merges);
 
 /* ---- results (getAllFinalHypothesis / getBestHypothesis) ------------------ */
 /* Number of hypotheses of utterance b and the length (finalFrame + 1) of each

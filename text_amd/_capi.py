@@ -14,7 +14,7 @@ DEFAULT_LIB = os.path.join(_HERE, "lib", "libfltx.so")
 
 FLTX_OK, ERR_INVALID, ERR_HIP, ERR_OOM, ERR_UNSUPPORTED, ERR_RANGE, ERR_STATE = range(7)
 CRITERION = {"asg": 0, "ctc": 1, "s2s": 2}
-LEXFREE, LEXICON, S2S_LEXFREE = 0, 1, 2
+LEXFREE, LEXICON, S2S_LEXFREE, S2S_LEXICON = 0, 1, 2, 3
 # fltx_decoder_get "why_not_lane" (include/fltx.h FLTX_WHY_*)
 (FLTX_WHY_TOKENS, FLTX_WHY_BEAM, FLTX_WHY_STREAM, FLTX_WHY_LM, FLTX_WHY_LOGADD, FLTX_WHY_ASG, FLTX_WHY_UNK,
  FLTX_WHY_TRIE_SHAPE, FLTX_WHY_WORD_END, FLTX_WHY_OPTIONS, FLTX_WHY_LENGTH, FLTX_WHY_SWITCHED_OFF,
@@ -50,6 +50,20 @@ class S2sOptions(C.Structure):
     ]
 
 
+class S2sLexOptions(C.Structure):
+    """fltx_s2s_lex_options == LexiconSeq2SeqDecoderOptions (decoder/LexiconSeq2SeqDecoder.h:23-31)."""
+
+    _fields_ = [
+        ("beam_size", C.c_int32),
+        ("beam_size_token", C.c_int32),
+        ("beam_threshold", C.c_double),
+        ("lm_weight", C.c_double),
+        ("word_score", C.c_double),
+        ("eos_score", C.c_double),
+        ("log_add", C.c_int32),
+    ]
+
+
 class FltxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("fltx error %d: %s" % (code, msg))
@@ -76,6 +90,7 @@ class Lib:
         "fltx_decoder_bytes", "fltx_htrie_node", "fltx_group_create", "fltx_group_destroy", "fltx_group_size", "fltx_group_decoder",
         "fltx_group_decode_batch", "fltx_group_result_count", "fltx_group_result_fetch", "fltx_group_synchronize",
         "fltx_s2s_decoder_create", "fltx_s2s_begin", "fltx_s2s_step", "fltx_s2s_done", "fltx_s2s_end",
+        "fltx_s2s_lex_decoder_create", "fltx_s2s_lex_set_max_states", "fltx_s2s_lex_info",
     ]
 
     def __init__(self, path=None):
@@ -150,6 +165,9 @@ class Lib:
             "fltx_s2s_step": [vp, vp, i32, i64, vp, vp, vp, vp, vp],
             "fltx_s2s_done": [vp, vp],
             "fltx_s2s_end": [vp],
+            "fltx_s2s_lex_decoder_create": [vp, C.POINTER(S2sLexOptions), vp, vp, i32, i32, i32, pvp],
+            "fltx_s2s_lex_set_max_states": [vp, i32],
+            "fltx_s2s_lex_info": [vp, vp, vp, vp, vp],
         }
         for name, args in sig.items():
             fn = getattr(L, name)
@@ -869,6 +887,40 @@ class Seq2SeqBatchDecoder(BatchDecoder):
         return self.results_batch()
 
 
+class LexiconSeq2SeqBatchDecoder(Seq2SeqBatchDecoder):
+    """fltx_s2s_lex_*: LexiconSeq2SeqDecoder for B utterances at once, with Seq2SeqBatchDecoder's begin / step / done /
+    end / decode loop and row contract.  `trie` is a HostTrie (already smeared) or anything with an fltx_htrie handle
+    `.h`; `lm` a ZeroLM / n-gram LM of this module (words are its user ids, tokens when is_lm_token).  The results
+    carry words."""
+
+    def __init__(self, ctx, options, trie, lm, eos, max_output_length, is_lm_token=False):
+        self.ctx, self.L = ctx, ctx.L
+        self.kind, self.options = S2S_LEXICON, options
+        self._keep = (lm, trie)
+        self.eos, self.max_output_length = int(eos), int(max_output_length)
+        h = C.c_void_p()
+        self.L.check(self.L.lib.fltx_s2s_lex_decoder_create(ctx.h, C.byref(options), trie.h, lm.h, self.eos,
+                                                            self.max_output_length, int(bool(is_lm_token)),
+                                                            C.byref(h)))
+        self.h = h
+        self.B = 0
+        self.N = None
+        self.V = None
+        self._emu = "emulation" in self.L.version()
+        _live["dec"].add(self)
+
+    def set_max_states(self, n):
+        self.L.check(self.L.lib.fltx_s2s_lex_set_max_states(self.h, int(n)))
+
+    def info(self):
+        """-> dict(trie_bytes, nodes, edges, merges: per utterance since begin, or None before it)."""
+        tb, nn, ne = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        m = np.zeros(max(self.B, 1), np.int32)
+        self.L.check(self.L.lib.fltx_s2s_lex_info(self.h, C.addressof(tb), C.addressof(nn), C.addressof(ne),
+                                                  _ptr(m) if self.B else None))
+        return dict(trie_bytes=tb.value, nodes=nn.value, edges=ne.value, merges=m.tolist() if self.B else None)
+
+
 class DecoderGroup:
     """fltx_group: one batch sharded over several devices (one context, decoder
     and host thread per entry of `devices`; no inter-device traffic)."""
@@ -951,6 +1003,12 @@ class DecoderGroup:
 
 def make_s2s_options(beam_size, beam_size_token, beam_threshold=25.0, lm_weight=0.0, eos_score=0.0, log_add=False):
     return S2sOptions(beam_size, beam_size_token, beam_threshold, lm_weight, eos_score, int(bool(log_add)))
+
+
+def make_s2s_lex_options(beam_size, beam_size_token, beam_threshold=25.0, lm_weight=0.0, word_score=0.0,
+                        eos_score=0.0, log_add=False):
+    return S2sLexOptions(beam_size, beam_size_token, beam_threshold, lm_weight, word_score, eos_score,
+                         int(bool(log_add)))
 
 
 def make_options(beam_size, beam_size_token, beam_threshold=25.0, lm_weight=0.0, word_score=0.0,

@@ -1,5 +1,6 @@
-"""LexiconFreeSeq2SeqDecoder with the reference's Python surface (bindings/python/flashlight/lib/text/_decoder.cpp:
-128-160, 443-535) over the batched device step (fltx_s2s_*, text_amd._capi.Seq2SeqBatchDecoder) at B = 1.
+"""LexiconFreeSeq2SeqDecoder and LexiconSeq2SeqDecoder with the reference's Python surface
+(bindings/python/flashlight/lib/text/_decoder.cpp:128-160, 443-535) over the batched device steps (fltx_s2s_*,
+text_amd._capi.Seq2SeqBatchDecoder / LexiconSeq2SeqBatchDecoder) at B = 1.
 
 decode_step(emissions, T, N) calls the user's update_func once per step with the live hypotheses of the beam
 (rawY / rawBeamIdx / rawPrevStates, LexiconFreeSeq2SeqDecoder.cpp:44-60), uploads the rows it returns and runs one
@@ -57,6 +58,46 @@ def _context():
     return _ctx[0]
 
 
+def _decode(dec, K, update_func, max_output_length, emissions, T, N, raw_beam_idx):
+    """decodeStep over a batched decoder at B = 1: one update_func call and one device step per step.  raw_beam_idx:
+    update_func sees the parents' beam indices (LexiconFreeSeq2SeqDecoder.cpp:49), else -1 for every row (the
+    lexicon decoder's candidates never record prevHypIdx: LexiconSeq2SeqDecoder.cpp:49)."""
+    raw_y, raw_beam, prev_states = [-1], [-1], [None]
+    t = 0
+    begun = False
+    while t < max_output_length:
+        scores, out_states = update_func(emissions, N, T, raw_y, raw_beam, prev_states, t)
+        V = max(len(r) for r in scores)
+        if not begun:
+            dec.begin(1, V)
+            begun = True
+        rows = np.full((K, V), np.nan, dtype=np.float32)
+        valid = np.zeros(K, dtype=np.uint8)
+        for k, (r, s) in enumerate(zip(scores, out_states)):
+            rows[k, :len(r)] = np.asarray(r, dtype=np.float32)
+            valid[k] = s is not None
+        out = dec.step(rows, valid)
+        dec.ctx.synchronize()  # (the rows decide the next model call: one host wait per step)
+        tok, beam, src, n = (x.cpu().numpy() if hasattr(x, "cpu") else x for x in out)
+        t += 1
+        n = int(n[0])
+        if n == 0:
+            break
+        raw_y = tok[0, :n].tolist()
+        raw_beam = beam[0, :n].tolist() if raw_beam_idx else [-1] * n
+        prev_states = [out_states[int(s)] for s in src[0, :n]]
+    if not begun:  # maxOutputLength 0: the root alone
+        dec.begin(1, 1)
+    dec.end()
+    hyps = []
+    for h in dec.results(0):
+        r = DecodeResult(len(h.tokens))
+        r.score, r.emittingModelScore, r.lmScore = h.score, h.am, h.lm
+        r.tokens, r.words = h.tokens.tolist(), h.words.tolist()
+        hyps.append(r)
+    return hyps
+
+
 class LexiconFreeSeq2SeqDecoder:
     """LexiconFreeSeq2SeqDecoder(options, lm, eos_idx, update_func, max_output_length): ZeroLM, or an LM object of
     text_amd._capi (ZeroLM / NgramLM / ArpaLM); a user-defined LM is refused (FLTX_ERR_UNSUPPORTED)."""
@@ -78,40 +119,86 @@ class LexiconFreeSeq2SeqDecoder:
         self._hyps = []
 
     def decode_step(self, emissions, T, N):
-        dec, K = self._dec, self.options.beam_size
-        raw_y, raw_beam, prev_states = [-1], [-1], [None]
-        t = 0
-        begun = False
-        while t < self.max_output_length:
-            scores, out_states = self.update_func(emissions, N, T, raw_y, raw_beam, prev_states, t)
-            V = max(len(r) for r in scores)
-            if not begun:
-                dec.begin(1, V)
-                begun = True
-            rows = np.full((K, V), np.nan, dtype=np.float32)
-            valid = np.zeros(K, dtype=np.uint8)
-            for k, (r, s) in enumerate(zip(scores, out_states)):
-                rows[k, :len(r)] = np.asarray(r, dtype=np.float32)
-                valid[k] = s is not None
-            out = dec.step(rows, valid)
-            dec.ctx.synchronize()  # (the rows decide the next model call: one host wait per step)
-            tok, beam, src, n = (x.cpu().numpy() if hasattr(x, "cpu") else x for x in out)
-            t += 1
-            n = int(n[0])
-            if n == 0:
-                break
-            raw_y = tok[0, :n].tolist()
-            raw_beam = beam[0, :n].tolist()
-            prev_states = [out_states[int(s)] for s in src[0, :n]]
-        if not begun:  # maxOutputLength 0: the root alone
-            dec.begin(1, 1)
-        dec.end()
+        self._hyps = _decode(self._dec, self.options.beam_size, self.update_func, self.max_output_length, emissions, T,
+                             N, raw_beam_idx=True)
+
+    def prune(self, look_back=0):
+        return None
+
+    def n_decoded_frames_in_buffer(self):
+        return -1
+
+    def get_best_hypothesis(self, look_back=0):
+        return self._hyps[0] if self._hyps else DecodeResult(0)
+
+    def get_all_final_hypothesis(self):
+        return list(self._hyps)
+
+
+class LexiconSeq2SeqDecoderOptions:
+    """LexiconSeq2SeqDecoderOptions (decoder/LexiconSeq2SeqDecoder.h:23-31)."""
+    __slots__ = ("beam_size", "beam_size_token", "beam_threshold", "lm_weight", "word_score", "eos_score", "log_add")
+
+    def __init__(self, beam_size, beam_size_token, beam_threshold, lm_weight, word_score, eos_score, log_add):
+        self.beam_size, self.beam_size_token = int(beam_size), int(beam_size_token)
+        self.beam_threshold, self.lm_weight = float(beam_threshold), float(lm_weight)
+        self.word_score, self.eos_score, self.log_add = float(word_score), float(eos_score), bool(log_add)
+
+    def __reduce__(self):
+        return (LexiconSeq2SeqDecoderOptions, (self.beam_size, self.beam_size_token, self.beam_threshold,
+                                               self.lm_weight, self.word_score, self.eos_score, self.log_add))
+
+
+class _Handle:
+    """An fltx handle owned by another object (kept alive here)."""
+
+    def __init__(self, h, owner):
+        import ctypes
+        self.h, self.owner = ctypes.c_void_p(h), owner
+
+
+def _trie_handle(trie):
+    if isinstance(trie, _capi.HostTrie):
+        return trie
+    if hasattr(trie, "_fltx_host_handle"):  # (the compat package's Trie)
+        return _Handle(trie._fltx_host_handle(), trie)
+    raise TypeError("LexiconSeq2SeqDecoder: the lexicon must be a Trie")
+
+
+def _lm_handle(lm, ctx):
+    if isinstance(lm, ZeroLM):
+        return _capi.ZeroLM(ctx)
+    if isinstance(lm, _capi.ZeroLM):  # (and its subclasses: n-gram tables)
+        return lm
+    h = lm._fltx_device_handle() if hasattr(lm, "_fltx_device_handle") else 0
+    if not h:
+        raise _capi.FltxError(_capi.ERR_UNSUPPORTED, "seq2seq: ZeroLM or n-gram LM tables only (a user-defined LM is "
+                              "not supported)")
+    return _Handle(h, lm)
+
+
+class LexiconSeq2SeqDecoder:
+    """LexiconSeq2SeqDecoder with the reference binding's signature (bindings/python/.../_decoder.cpp:497-512):
+    (options, lm, trie, eos_idx, update_func, max_output_length, is_token_lm) -- the second parameter is named `lm`
+    and takes the Trie, the third is named `trie` and takes the LM, as there.  The trie is the compat package's Trie
+    (or a text_amd._capi.HostTrie), already smeared; the LM ZeroLM / KenLM (or a text_amd._capi LM object).
+    update_func sees -1 for every beam index, as the reference's does."""
+
+    def __init__(self, options, lm, trie, eos_idx, update_func, max_output_length, is_token_lm):
+        self.options, self.eos = options, int(eos_idx)
+        self.update_func, self.max_output_length = update_func, int(max_output_length)
+        ctx = _context()
+        self._trie = _trie_handle(lm)
+        self._lm = _lm_handle(trie, ctx)
+        opts = _capi.make_s2s_lex_options(options.beam_size, options.beam_size_token, options.beam_threshold,
+                                          options.lm_weight, options.word_score, options.eos_score, options.log_add)
+        self._dec = _capi.LexiconSeq2SeqBatchDecoder(ctx, opts, self._trie, self._lm, self.eos,
+                                                     self.max_output_length, bool(is_token_lm))
         self._hyps = []
-        for h in dec.results(0):
-            r = DecodeResult(len(h.tokens))
-            r.score, r.emittingModelScore, r.lmScore = h.score, h.am, h.lm
-            r.tokens, r.words = h.tokens.tolist(), h.words.tolist()
-            self._hyps.append(r)
+
+    def decode_step(self, emissions, T, N):
+        self._hyps = _decode(self._dec, self.options.beam_size, self.update_func, self.max_output_length, emissions, T,
+                             N, raw_beam_idx=False)
 
     def prune(self, look_back=0):
         return None

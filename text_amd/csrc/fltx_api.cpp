@@ -30,6 +30,7 @@
 #include "fltx_kernel_entry.h"
 #include "fltx_engines.h"
 #include "fltx_s2s.h"
+#include "fltx_s2s_lex.h"
 
 using namespace fltx;
 
@@ -153,6 +154,20 @@ __global__ void __launch_bounds__(64) fltx_s2s_begin_kernel(S2sParams P) {
 }
 __global__ void __launch_bounds__(256) fltx_s2s_end_kernel(S2sParams P) {
   s2sEndUtterance(P, (int)blockIdx.x, (int)threadIdx.x, (int)blockDim.x);
+}
+/* fltx_s2s_lex.h: the lexicon seq2seq step (its front end is fltx_s2s_tokbeam_kernel), start and back-trace */
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_s2s_lex_step_kernel(S2lParams Q) {
+  __shared__ __attribute__((aligned(16))) S2lStepLds fltx_s2l_lds;
+  s2lStepUtterance(Q, (char*)&fltx_s2l_lds);
+}
+__global__ void __launch_bounds__(64) fltx_s2s_lex_begin_kernel(S2lParams Q) {
+  const int b = (int)(blockIdx.x * 64 + threadIdx.x);
+  if (b < Q.s.B) {
+    s2lBeginUtterance(Q, b);
+  }
+}
+__global__ void __launch_bounds__(256) fltx_s2s_lex_end_kernel(S2lParams Q) {
+  s2lEndUtterance(Q, (int)blockIdx.x, (int)threadIdx.x, (int)blockDim.x);
 }
 __global__ void __launch_bounds__(1024) fltx_streamop_kernel(StreamOpParams Q) {
   __shared__ int32_t sh[kStreamOpLds / 4];
@@ -591,7 +606,19 @@ struct fltx_decoder {
   int32_t s2sCtx0[kS2sCtx] = {0};
   DBuf s2sBeam, s2sBeamN, s2sHist, s2sRowsInt, s2sDone, s2sFinal, s2sRecTok, s2sRecAm, s2sRecN, s2sKey;
   DBuf s2sScores, s2sValid; /* device copies of host inputs */
+  /* lexicon seq2seq (kind FLTX_DECODER_S2S_LEXICON, fltx_s2s_lex_decoder_create: fltx_s2s_lex.h) */
+  double s2lWordScore = 0.0;
+  bool s2lIsLmToken = false;
+  int s2lMaxLabels = 0, s2lS = 1, s2lMSize = 0, s2lSSize = 0, s2lSMax = 0, s2lMaxStates = 0;
+  int64_t s2lNodes = 0, s2lEdges = 0, s2lLabels = 0, s2lTrieBytes = 0;
+  DBuf s2lMax, s2lKidOff, s2lKidTok, s2lKidNode, s2lLabOff, s2lLab; /* the compact trie */
+  DBuf s2lBeam, s2lHist, s2lScore, s2lMk, s2lGrp, s2lList, s2lNext, s2lMTab, s2lSKey, s2lSVal, s2lSCount, s2lStatus,
+      s2lMerges;
 };
+
+static bool isS2sKind(int kind) { return kind == FLTX_DECODER_S2S_LEXFREE || kind == FLTX_DECODER_S2S_LEXICON; }
+/* decoders whose results carry words */
+static bool kindHasWords(int kind) { return kind == FLTX_DECODER_LEXICON || kind == FLTX_DECODER_S2S_LEXICON; }
 
 /* ------------------------------------------------------------------------ */
 extern "C" {
@@ -3570,7 +3597,7 @@ int fltx_decode_batch(fltx_decoder* d, const float* emissions, int32_t onDevice,
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
-  if (d && d->kind == FLTX_DECODER_S2S_LEXFREE) {
+  if (d && isS2sKind(d->kind)) {
     return fail(FLTX_ERR_STATE, "fltx_decode_batch: a seq2seq decoder steps with fltx_s2s_step");
   }
   if (!d || !T || B <= 0 || N <= 0) {
@@ -3801,7 +3828,7 @@ int fltx_stream_begin(fltx_decoder* d, int32_t B, int32_t N, int32_t maxFrames) 
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
-  if (d && d->kind == FLTX_DECODER_S2S_LEXFREE) {
+  if (d && isS2sKind(d->kind)) {
     return fail(FLTX_ERR_STATE, "fltx_stream_begin: a seq2seq decoder steps with fltx_s2s_step");
   }
   if (!d || B <= 0 || N <= 0 || maxFrames < 0) {
@@ -3890,7 +3917,7 @@ int fltx_stream_step(fltx_decoder* d, const float* emissions, int32_t onDevice, 
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
-  if (d && d->kind == FLTX_DECODER_S2S_LEXFREE) {
+  if (d && isS2sKind(d->kind)) {
     return fail(FLTX_ERR_STATE, "fltx_stream_step: a seq2seq decoder steps with fltx_s2s_step");
   }
   if (!d || !T) {
@@ -3994,7 +4021,7 @@ int fltx_stream_end(fltx_decoder* d) {
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
-  if (d && d->kind == FLTX_DECODER_S2S_LEXFREE) {
+  if (d && isS2sKind(d->kind)) {
     return fail(FLTX_ERR_STATE, "fltx_stream_end: a seq2seq decoder steps with fltx_s2s_step");
   }
   if (!d) {
@@ -4036,7 +4063,7 @@ int fltx_stream_prune(fltx_decoder* d, int32_t lookBack) {
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
-  if (d && d->kind == FLTX_DECODER_S2S_LEXFREE) {
+  if (d && isS2sKind(d->kind)) {
     return fail(FLTX_ERR_STATE, "fltx_stream_prune: a seq2seq decoder steps with fltx_s2s_step");
   }
   if (!d || lookBack < 0) {
@@ -4190,7 +4217,7 @@ int fltx_result_fetch(fltx_decoder* d, int32_t b, int32_t maxHyp, double* scores
       return fail(FLTX_ERR_HIP, "token copy failed");
     }
     if (words) {
-      if (d->kind == FLTX_DECODER_LEXICON) {
+      if (kindHasWords(d->kind)) {
         if (devCopyD2H(words, d->words.as<int32_t>() + base, 4 * (size_t)n * len, st)) {
           return fail(FLTX_ERR_HIP, "word copy failed");
         }
@@ -4231,12 +4258,12 @@ int fltx_result_fetch_batch(fltx_decoder* d, const int32_t** nHyp, const int32_t
     Stream st = d->ctx->stream;
     const size_t nRec = (size_t)std::max<int64_t>(d->histRecords, 1);
     if (d->hTokens.ensure(4 * nRec) || d->hScores.ensure(8 * 3 * (size_t)B * K) ||
-        (d->kind == FLTX_DECODER_LEXICON && d->hWords.ensure(4 * nRec))) {
+        (kindHasWords(d->kind) && d->hWords.ensure(4 * nRec))) {
       return fail(FLTX_ERR_OOM, "pinned result buffers: allocation failed");
     }
     if (devCopyD2H(d->hScores.p, d->outScores.p, 8 * 3 * (size_t)B * K, st) ||
         devCopyD2H(d->hTokens.p, d->tokens.p, 4 * nRec, st) ||
-        (d->kind == FLTX_DECODER_LEXICON && devCopyD2H(d->hWords.p, d->words.p, 4 * nRec, st))) {
+        (kindHasWords(d->kind) && devCopyD2H(d->hWords.p, d->words.p, 4 * nRec, st))) {
       return fail(FLTX_ERR_HIP, "result copy failed: %s", devErr());
     }
     d->hLen.resize(B);
@@ -4261,7 +4288,7 @@ int fltx_result_fetch_batch(fltx_decoder* d, const int32_t** nHyp, const int32_t
     *tokens = (const int32_t*)d->hTokens.p;
   }
   if (words) {
-    *words = d->kind == FLTX_DECODER_LEXICON ? (const int32_t*)d->hWords.p : nullptr;
+    *words = kindHasWords(d->kind) ? (const int32_t*)d->hWords.p : nullptr;
   }
   if (offsets) {
     *offsets = d->histOff.data();
@@ -4300,7 +4327,7 @@ int fltx_result_fetch_batch_compact(fltx_decoder* d, const int32_t** nHyp, const
       return rc;
     }
     Stream st = d->ctx->stream;
-    const bool lex = d->kind == FLTX_DECODER_LEXICON;
+    const bool lex = kindHasWords(d->kind);
     d->hLen.resize(B);
     d->hNHyp.resize(B);
     d->packOff.resize((size_t)B + 1);
@@ -4371,7 +4398,7 @@ int fltx_result_fetch_batch_compact(fltx_decoder* d, const int32_t** nHyp, const
     *tokensU8 = (const uint8_t*)d->hTok8.p;
   }
   if (words) {
-    *words = d->kind == FLTX_DECODER_LEXICON ? (const int32_t*)d->hWordsC.p : nullptr;
+    *words = kindHasWords(d->kind) ? (const int32_t*)d->hWordsC.p : nullptr;
   }
   if (offsets) {
     *offsets = d->packOff.data();
@@ -4391,7 +4418,7 @@ int fltx_result_best(fltx_decoder* d, int32_t b, int32_t lookBack, double* score
   if (!d->haveResults) {
     return fail(FLTX_ERR_STATE, "no decode has been run");
   }
-  if (d->kind == FLTX_DECODER_S2S_LEXFREE) { /* getBestHypothesis ignores lookBack: the final beam's first (:165-169) */
+  if (isS2sKind(d->kind)) { /* getBestHypothesis ignores lookBack: the final beam's first (:165-169) */
     int32_t n = 0, len = 0;
     int rc = fltx_result_count(d, b, &n, &len);
     if (rc) {
@@ -4491,7 +4518,7 @@ int fltx_result_device(fltx_decoder* d, const int32_t** nHyp, const double** sco
     *tokens = d->tokens.as<int32_t>();
   }
   if (words) {
-    *words = d->kind == FLTX_DECODER_LEXICON ? d->words.as<int32_t>() : nullptr;
+    *words = kindHasWords(d->kind) ? d->words.as<int32_t>() : nullptr;
   }
   if (tokOff) {
     *tokOff = d->histOffD.as<int64_t>();
@@ -4623,7 +4650,7 @@ static int s2sCheck(fltx_decoder* d, const char* what) {
   if (!d) {
     return fail(FLTX_ERR_INVALID, "%s: null decoder", what);
   }
-  if (d->kind != FLTX_DECODER_S2S_LEXFREE) {
+  if (!isS2sKind(d->kind)) {
     return fail(FLTX_ERR_STATE, "%s: not a seq2seq decoder (fltx_s2s_decoder_create)", what);
   }
   return FLTX_OK;
@@ -4740,6 +4767,260 @@ int fltx_s2s_decoder_create(fltx_ctx* ctx, const fltx_s2s_options* opt, const fl
   return FLTX_OK;
 }
 
+/* ---- lexicon seq2seq (fltx_s2s_lex.h) ---------------------------------------------------------------------------- */
+static S2lParams s2lParams(fltx_decoder* d) {
+  S2lParams Q;
+  memset(&Q, 0, sizeof(Q));
+  Q.s = s2sParams(d);
+  Q.s.nC = (int64_t)Q.s.K * Q.s.cap * d->s2lS + Q.s.K;
+  Q.trie.maxScore = d->s2lMax.as<float>();
+  Q.trie.kidOff = d->s2lKidOff.as<int32_t>();
+  Q.trie.kidTok = d->s2lKidTok.as<int32_t>();
+  Q.trie.kidNode = d->s2lKidNode.as<int32_t>();
+  Q.trie.labOff = d->s2lLabOff.as<int32_t>();
+  Q.trie.labels = d->s2lLab.as<int32_t>();
+  Q.isLmToken = d->s2lIsLmToken ? 1 : 0;
+  Q.S = d->s2lS;
+  Q.wordScore = d->s2lWordScore;
+  Q.logAdd = d->s2sOpt.log_add ? 1 : 0;
+  Q.beam = d->s2lBeam.as<S2lHyp>();
+  Q.hist = d->s2lHist.as<S2lRec>();
+  Q.cScore = d->s2lScore.as<double>();
+  Q.cMk = d->s2lMk.as<uint4>();
+  Q.cGrp = d->s2lGrp.as<int32_t>();
+  Q.cList = d->s2lList.as<int32_t>();
+  Q.cNext = d->s2lNext.as<int32_t>();
+  Q.mTab = d->s2lMTab.as<int32_t>();
+  Q.mSize = d->s2lMSize;
+  Q.sKey = d->s2lSKey.as<unsigned long long>();
+  Q.sVal = d->s2lSVal.as<int32_t>();
+  Q.sCount = d->s2lSCount.as<int32_t>();
+  Q.sSize = d->s2lSSize;
+  Q.sMax = d->s2lSMax;
+  Q.status = d->s2lStatus.as<int32_t>();
+  Q.merges = d->s2lMerges.as<int32_t>();
+  return Q;
+}
+
+static int s2lPow2AtLeast(int64_t n) {
+  int64_t p = 1;
+  while (p < n) {
+    p <<= 1;
+  }
+  return (int)p;
+}
+
+/* the compact trie: per node maxScore, children sorted by token (CSR) and labels; bytes ~ nodes + edges + labels */
+static int s2lUploadTrie(fltx_decoder* d, fltx_htrie* t) {
+  int64_t nn = 0;
+  int rc = fltx_htrie_num_nodes(t, &nn);
+  if (rc) {
+    return rc;
+  }
+  if (nn >= (int64_t)1 << 31) {
+    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq lexicon: %lld trie nodes", (long long)nn);
+  }
+  std::vector<float> mx((size_t)nn);
+  std::vector<int32_t> kidOff((size_t)nn + 1, 0), labOff((size_t)nn + 1, 0), kidTok, kidNode, lab;
+  std::vector<int32_t> ct;
+  std::vector<int64_t> cn;
+  std::vector<std::pair<int32_t, int32_t>> kids;
+  int maxLabels = 0;
+  for (int64_t i = 0; i < nn; ++i) {
+    int32_t nl = 0, nc = 0, labels[kS2lMaxLabels];
+    float ms = 0.0f;
+    if ((rc = fltx_htrie_node(t, i, nullptr, &ms, &nl, labels, nullptr, &nc, nullptr, nullptr, 0))) {
+      return rc;
+    }
+    ct.resize((size_t)std::max(nc, 1));
+    cn.resize((size_t)std::max(nc, 1));
+    if ((rc = fltx_htrie_node(t, i, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ct.data(), cn.data(), nc))) {
+      return rc;
+    }
+    kids.clear();
+    for (int c = 0; c < nc; ++c) {
+      kids.emplace_back(ct[c], (int32_t)cn[c]);
+    }
+    std::sort(kids.begin(), kids.end());
+    for (const auto& kv : kids) {
+      kidTok.push_back(kv.first);
+      kidNode.push_back(kv.second);
+    }
+    for (int l = 0; l < nl; ++l) {
+      lab.push_back(labels[l]);
+    }
+    maxLabels = std::max(maxLabels, (int)nl);
+    mx[(size_t)i] = ms;
+    kidOff[(size_t)i + 1] = (int32_t)kidTok.size();
+    labOff[(size_t)i + 1] = (int32_t)lab.size();
+  }
+  Stream st = d->ctx->stream;
+  const size_t nE = kidTok.size(), nL = lab.size();
+  if (d->s2lMax.ensure(4 * (size_t)nn, st, false) || d->s2lKidOff.ensure(4 * ((size_t)nn + 1), st, false) ||
+      d->s2lKidTok.ensure(4 * std::max<size_t>(nE, 1), st, false) ||
+      d->s2lKidNode.ensure(4 * std::max<size_t>(nE, 1), st, false) ||
+      d->s2lLabOff.ensure(4 * ((size_t)nn + 1), st, false) || d->s2lLab.ensure(4 * std::max<size_t>(nL, 1), st, false)) {
+    return fail(FLTX_ERR_OOM, "seq2seq lexicon: trie allocation failed (%lld nodes)", (long long)nn);
+  }
+  if (devCopyH2D(d->s2lMax.p, mx.data(), 4 * (size_t)nn, st) ||
+      devCopyH2D(d->s2lKidOff.p, kidOff.data(), 4 * ((size_t)nn + 1), st) ||
+      (nE && devCopyH2D(d->s2lKidTok.p, kidTok.data(), 4 * nE, st)) ||
+      (nE && devCopyH2D(d->s2lKidNode.p, kidNode.data(), 4 * nE, st)) ||
+      devCopyH2D(d->s2lLabOff.p, labOff.data(), 4 * ((size_t)nn + 1), st) ||
+      (nL && devCopyH2D(d->s2lLab.p, lab.data(), 4 * nL, st)) || devSync(st)) {
+    return fail(FLTX_ERR_HIP, "seq2seq lexicon: trie upload failed");
+  }
+  d->s2lNodes = nn;
+  d->s2lEdges = (int64_t)nE;
+  d->s2lLabels = (int64_t)nL;
+  d->s2lMaxLabels = maxLabels;
+  d->s2lTrieBytes = 4 * nn + 4 * 2 * (nn + 1) + 8 * (int64_t)nE + 4 * (int64_t)nL;
+  return FLTX_OK;
+}
+
+int fltx_s2s_lex_decoder_create(fltx_ctx* ctx, const fltx_s2s_lex_options* opt, const fltx_htrie* trie,
+                                const fltx_lm* lm, int32_t eos, int32_t maxOut, int32_t isLmToken, fltx_decoder** out) {
+  if (!ctx || !opt || !trie || !lm || !out) {
+    return fail(FLTX_ERR_INVALID, "fltx_s2s_lex_decoder_create: null argument");
+  }
+  fltx_s2s_options o{};
+  o.beam_size = opt->beam_size;
+  o.beam_size_token = opt->beam_size_token;
+  o.beam_threshold = opt->beam_threshold;
+  o.lm_weight = opt->lm_weight;
+  o.eos_score = opt->eos_score;
+  o.log_add = opt->log_add;
+  fltx_decoder* d = nullptr;
+  int rc = fltx_s2s_decoder_create(ctx, &o, lm, eos, maxOut, &d);
+  if (rc) {
+    return rc;
+  }
+  DeviceScope devScope(ctx);
+  if (devScope.failed) {
+    delete d;
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  d->kind = FLTX_DECODER_S2S_LEXICON;
+  d->opt.word_score = opt->word_score;
+  d->s2lWordScore = opt->word_score;
+  d->s2lIsLmToken = isLmToken != 0;
+  d->s2lMaxStates = kS2lDefaultStates;
+  if ((rc = s2lUploadTrie(d, const_cast<fltx_htrie*>(trie)))) {
+    delete d;
+    return rc;
+  }
+  d->s2lS = 1 + (d->s2lIsLmToken ? std::min(d->s2lMaxLabels, 1) : d->s2lMaxLabels);
+  *out = d;
+  return FLTX_OK;
+}
+
+int fltx_s2s_lex_set_max_states(fltx_decoder* d, int32_t maxStates) {
+  int rc = s2sCheck(d, "fltx_s2s_lex_set_max_states");
+  if (rc) {
+    return rc;
+  }
+  if (d->kind != FLTX_DECODER_S2S_LEXICON || maxStates < 1) {
+    return fail(FLTX_ERR_INVALID, "fltx_s2s_lex_set_max_states: a lexicon seq2seq decoder and a count >= 1");
+  }
+  d->s2lMaxStates = maxStates;
+  return FLTX_OK;
+}
+
+int fltx_s2s_lex_info(fltx_decoder* d, int64_t* trieBytes, int64_t* nNodes, int64_t* nEdges, int32_t* merges) {
+  int rc = s2sCheck(d, "fltx_s2s_lex_info");
+  if (rc) {
+    return rc;
+  }
+  if (d->kind != FLTX_DECODER_S2S_LEXICON) {
+    return fail(FLTX_ERR_STATE, "fltx_s2s_lex_info: not a lexicon seq2seq decoder");
+  }
+  DeviceScope devScope(d->ctx);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  if (trieBytes) {
+    *trieBytes = d->s2lTrieBytes;
+  }
+  if (nNodes) {
+    *nNodes = d->s2lNodes;
+  }
+  if (nEdges) {
+    *nEdges = d->s2lEdges;
+  }
+  if (merges && d->s2sBegun) {
+    if (devCopyD2H(merges, d->s2lMerges.p, 4 * (size_t)d->B, d->ctx->stream) || devSync(d->ctx->stream)) {
+      return fail(FLTX_ERR_HIP, "fltx_s2s_lex_info: copy failed: %s", devErr());
+    }
+  }
+  return FLTX_OK;
+}
+
+static int s2lBegin(fltx_decoder* d, int32_t B, int32_t V, int32_t* nextTok, int32_t* nextBeam, int32_t* nextSrc,
+                    int32_t* nRows) {
+  const int K = d->s2sOpt.beam_size, Kt = d->s2sOpt.beam_size_token;
+  const int ktEff = std::min(Kt, V);
+  if (ktEff > kS2lMaxKt) {
+    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq lexicon: a token beam of %d (beam_size_token, V = %d) > %d", ktEff, V,
+                kS2lMaxKt);
+  }
+  d->s2sMSel = ktEff; /* the exact token beam: the trie and word scores make the score non-monotone in the model's */
+  d->s2sEosExtra = 0;
+  d->s2sCap = ktEff;
+  const int64_t nC = (int64_t)K * ktEff * d->s2lS + K;
+  if (nC >= (int64_t)1 << 30) {
+    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq lexicon: %lld candidates per step", (long long)nC);
+  }
+  d->s2lMSize = s2lPow2AtLeast(2 * nC);
+  d->s2lSMax = (int)std::min<int64_t>((int64_t)K * d->s2sMaxOut + 1, d->s2lMaxStates);
+  d->s2lSSize = s2lPow2AtLeast(2 * (int64_t)d->s2lSMax);
+  Stream st = d->ctx->stream;
+  const size_t BK = (size_t)B * K, BC = (size_t)B * (size_t)nC;
+  if (d->s2lBeam.ensure(2 * BK * sizeof(S2lHyp), st, false) || d->s2sBeamN.ensure(8 * (size_t)B, st, false) ||
+      d->s2lHist.ensure((size_t)(d->s2sMaxOut + 1) * BK * sizeof(S2lRec), st, false) ||
+      d->s2sRowsInt.ensure(4 * (size_t)B, st, false) || d->s2sDone.ensure(4 * (size_t)B, st, false) ||
+      d->s2sFinal.ensure(4 * (size_t)B, st, false) || d->s2sRecTok.ensure(4 * BK * ktEff, st, false) ||
+      d->s2sRecAm.ensure(4 * BK * ktEff, st, false) || d->s2sRecN.ensure(4 * BK, st, false) ||
+      d->s2sKey.ensure(8 * BC, st, false) || d->s2lScore.ensure(8 * BC, st, false) ||
+      d->s2lMk.ensure(16 * BC, st, false) || d->s2lGrp.ensure(4 * BC, st, false) ||
+      d->s2lList.ensure(4 * BC, st, false) || d->s2lNext.ensure(4 * BC, st, false) ||
+      d->s2lMTab.ensure(4 * (size_t)B * d->s2lMSize, st, false) ||
+      d->s2lSKey.ensure(8 * (size_t)B * d->s2lSSize, st, false) ||
+      d->s2lSVal.ensure(4 * (size_t)B * d->s2lSSize, st, false) || d->s2lSCount.ensure(4 * (size_t)B, st, false) ||
+      d->s2lStatus.ensure(4 * (size_t)B, st, false) || d->s2lMerges.ensure(4 * (size_t)B, st, false)) {
+    return fail(FLTX_ERR_OOM, "seq2seq lexicon workspace: device allocation failed (B=%d K=%d V=%d)", B, K, V);
+  }
+  if (devMemset(d->s2lSKey.p, 0xFF, 8 * (size_t)B * d->s2lSSize, st)) { /* the state tables: empty */
+    return fail(FLTX_ERR_HIP, "seq2seq lexicon: memset failed");
+  }
+  d->B = B;
+  d->N = V;
+  d->s2sT = 0;
+  d->s2sBegun = true;
+  d->haveResults = false;
+  d->ended = false;
+  d->backtraced = false;
+  d->resultsSynced = false;
+  d->stateCap = (uint32_t)d->s2lSMax;
+  S2lParams Q = s2lParams(d);
+  Q.s.outTok = nextTok;
+  Q.s.outBeam = nextBeam;
+  Q.s.outSrc = nextSrc;
+  Q.s.outN = nRows;
+#ifdef FLTX_EMU
+  const S2lParams* qp = &Q;
+  emuLaunch((B + 63) / 64, 64, 0, [qp](char*) {
+    const int b = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (b < qp->s.B) {
+      s2lBeginUtterance(*qp, b);
+    }
+  });
+#else
+  hipLaunchKernelGGL(fltx_s2s_lex_begin_kernel, dim3((B + 63) / 64), dim3(64), 0, st, Q);
+  HIPCHK(hipGetLastError());
+#endif
+  return FLTX_OK;
+}
+
 /* row lists out: a launch of `kernel` writes them; the emulator runs the same function on host threads */
 int fltx_s2s_begin(fltx_decoder* d, int32_t B, int32_t V, int32_t* nextTok, int32_t* nextBeam, int32_t* nextSrc,
                    int32_t* nRows) {
@@ -4756,6 +5037,9 @@ int fltx_s2s_begin(fltx_decoder* d, int32_t B, int32_t V, int32_t* nextTok, int3
   }
   if (V > kS2sMaxV) {
     return fail(FLTX_ERR_UNSUPPORTED, "seq2seq: row width V = %d > %d", V, kS2sMaxV);
+  }
+  if (d->kind == FLTX_DECODER_S2S_LEXICON) {
+    return s2lBegin(d, B, V, nextTok, nextBeam, nextSrc, nRows);
   }
   const int K = d->s2sOpt.beam_size, Kt = d->s2sOpt.beam_size_token;
   const int ktEff = std::min(Kt, V);
@@ -4838,7 +5122,15 @@ int fltx_s2s_step(fltx_decoder* d, const float* scores, int32_t onDevice, int64_
     scores = d->s2sScores.as<float>();
     rowValid = rowValid ? d->s2sValid.as<uint8_t>() : nullptr;
   }
-  S2sParams P = s2sParams(d);
+  const bool lex = d->kind == FLTX_DECODER_S2S_LEXICON;
+  S2lParams Q;
+  if (lex) {
+    Q = s2lParams(d);
+  } else {
+    memset(&Q, 0, sizeof(Q));
+    Q.s = s2sParams(d);
+  }
+  S2sParams& P = Q.s;
   P.scores = scores;
   P.rowStride = rowStride;
   P.rowValid = rowValid;
@@ -4849,16 +5141,25 @@ int fltx_s2s_step(fltx_decoder* d, const float* scores, int32_t onDevice, int64_
   const int nFront = (int)((BK + 3) / 4);
 #ifdef FLTX_EMU
   const S2sParams* pp = &P;
+  const S2lParams* qp = &Q;
   if (!last) {
     emuLaunch(nFront, 256, 4 * sizeof(S2sFrontLds), [pp](char* smem) { s2sTokBeamRows(*pp, smem); });
   }
-  emuLaunch(d->B, kS2sStepThreads, sizeof(S2sStepLds), [pp](char* smem) { s2sStepUtterance(*pp, smem); });
+  if (lex) {
+    emuLaunch(d->B, kS2sStepThreads, sizeof(S2lStepLds), [qp](char* smem) { s2lStepUtterance(*qp, smem); });
+  } else {
+    emuLaunch(d->B, kS2sStepThreads, sizeof(S2sStepLds), [pp](char* smem) { s2sStepUtterance(*pp, smem); });
+  }
 #else
   if (!last) {
     hipLaunchKernelGGL(fltx_s2s_tokbeam_kernel, dim3(nFront), dim3(256), 0, st, P);
     HIPCHK(hipGetLastError());
   }
-  hipLaunchKernelGGL(fltx_s2s_step_kernel, dim3(d->B), dim3(kS2sStepThreads), 0, st, P);
+  if (lex) {
+    hipLaunchKernelGGL(fltx_s2s_lex_step_kernel, dim3(d->B), dim3(kS2sStepThreads), 0, st, Q);
+  } else {
+    hipLaunchKernelGGL(fltx_s2s_step_kernel, dim3(d->B), dim3(kS2sStepThreads), 0, st, P);
+  }
   HIPCHK(hipGetLastError());
 #endif
   if (!last) {
@@ -4925,7 +5226,19 @@ int fltx_s2s_end(fltx_decoder* d) {
   if (devCopyH2D(d->histOffD.p, d->histOff.data(), 8 * ((size_t)B + 1), st)) {
     return fail(FLTX_ERR_HIP, "seq2seq results: upload failed");
   }
-  S2sParams P = s2sParams(d);
+  const bool lex = d->kind == FLTX_DECODER_S2S_LEXICON;
+  if (lex && d->words.ensure(4 * (size_t)d->histRecords, st, false)) {
+    return fail(FLTX_ERR_OOM, "seq2seq results: device allocation failed");
+  }
+  S2lParams Q;
+  if (lex) {
+    Q = s2lParams(d);
+    Q.words = d->words.as<int32_t>();
+  } else {
+    memset(&Q, 0, sizeof(Q));
+    Q.s = s2sParams(d);
+  }
+  S2sParams& P = Q.s;
   P.outScores = d->outScores.as<double>();
   P.tokens = d->tokens.as<int32_t>();
   P.outNHyp = d->outN.as<int32_t>();
@@ -4934,9 +5247,18 @@ int fltx_s2s_end(fltx_decoder* d) {
   P.uttStatus = d->uttStatus.as<int32_t>();
 #ifdef FLTX_EMU
   const S2sParams* pp = &P;
-  emuLaunch(B, 64, 0, [pp](char*) { s2sEndUtterance(*pp, (int)blockIdx.x, (int)threadIdx.x, 64); });
+  const S2lParams* qp = &Q;
+  if (lex) {
+    emuLaunch(B, 64, 0, [qp](char*) { s2lEndUtterance(*qp, (int)blockIdx.x, (int)threadIdx.x, 64); });
+  } else {
+    emuLaunch(B, 64, 0, [pp](char*) { s2sEndUtterance(*pp, (int)blockIdx.x, (int)threadIdx.x, 64); });
+  }
 #else
-  hipLaunchKernelGGL(fltx_s2s_end_kernel, dim3(B), dim3(256), 0, st, P);
+  if (lex) {
+    hipLaunchKernelGGL(fltx_s2s_lex_end_kernel, dim3(B), dim3(256), 0, st, Q);
+  } else {
+    hipLaunchKernelGGL(fltx_s2s_end_kernel, dim3(B), dim3(256), 0, st, P);
+  }
   HIPCHK(hipGetLastError());
 #endif
   d->haveResults = true;

@@ -1,0 +1,665 @@
+/*
+ * fltx_s2s_lex.h -- the lexicon-constrained seq2seq beam search (LexiconSeq2SeqDecoder.cpp:20-202) as a batched
+ * device step, beside the lexicon-free one of fltx_s2s.h (whose front end, LM helpers and selection it reuses).
+ *
+ * A step is two kernels, as there:
+ *   fltx_s2s_tokbeam_kernel   one wave per live row: the row's exact token beam, its min(Kt, V) largest scores
+ *                             (:94-112), taken before the trie filter (tokens that are no children still use slots);
+ *   fltx_s2s_lex_step_kernel  one workgroup per utterance: every (row, token) of the records becomes up to 1 + labels
+ *                             candidates (stay in the trie, end a word per label: :142-200; eos at the root: :115-141),
+ *                             the finished hypotheses are carried (:68-83); then candidatesStore (Utils.h:146-225):
+ *                             the threshold, the MERGE of candidates in one LM state, trie node and token, and the
+ *                             sorted top K.
+ * fltx_s2s_lex_end_kernel writes the n-best with words.
+ *
+ * Merging.  compareNoScoreStates (LexiconSeq2SeqDecoder.h:85-97) compares LM-state OBJECTS, and LMState::child hands
+ * out the existing child (lm/LM.h:24-34), so two hypotheses in one state that end the same word, or two spellings of a
+ * token string under a token LM, meet again.  A hypothesis carries a canonical state id `sid` and the (parent sid,
+ * edge) pair its state was made by (edge: word / token id, -1 for KenLM's finish; the root is (-1, -1)).  child() is
+ * injective, so a candidate's state is named without a lookup: (h.sid, e) when it moves to child(h, e), h's own pair
+ * when it keeps h's state (smearing, ZeroLM's finish, a carried hypothesis).  Merge groups are found with a per-step
+ * hash table over the survivors of the threshold; a group of two or more is folded by one thread in descending score
+ * order (max, or logAdd's max + log1p(exp(min - max)) from the best), the best member's fields survive.  The <= K
+ * survivors that enter a new state get a canonical id from the utterance's lookup-or-insert table in HBM, which lives
+ * across steps (a state can be born again at a later step); a full table stops the utterance with ST_TABLE_FULL.
+ */
+#pragma once
+
+namespace fltx {
+
+constexpr int kS2lMaxKt = 256;     /* min(beamSizeToken, V): the records' width */
+constexpr int kS2lMaxLabels = 6;   /* kTrieMaxLabel (Trie.h:19) */
+constexpr int kS2lDefaultStates = 1 << 16; /* LM states per utterance (fltx_s2s_lex_set_max_states) */
+
+struct S2lHyp { /* one hypothesis of a beam, 72 B */
+  double score, am, lm;
+  int32_t token;  /* -1: the root */
+  int32_t word;   /* -1: none */
+  int32_t parent; /* index in the previous beam */
+  int32_t node;   /* trie node (0: the root) */
+  int32_t sid;    /* canonical LM state */
+  int32_t psid, edge; /* the state is child(psid, edge); (-1, -1): LM::start */
+  int32_t ctx[kS2sCtx];
+};
+
+struct S2lRec { /* a hypothesis' history record */
+  int32_t token, word, parent, pad;
+};
+
+/* the compact trie: children sorted by token per node (CSR), labels per node */
+struct S2lTrie {
+  const float* maxScore;  /* [nNodes] */
+  const int32_t* kidOff;  /* [nNodes + 1] */
+  const int32_t* kidTok;  /* [nEdges] */
+  const int32_t* kidNode; /* [nEdges] */
+  const int32_t* labOff;  /* [nNodes + 1] */
+  const int32_t* labels;  /* [nLabels] */
+};
+
+struct S2lParams {
+  S2sParams s;          /* the lexicon-free fields: rows, records, front end, outputs */
+  S2lTrie trie;
+  int32_t isLmToken;
+  int32_t S;            /* candidate slots per record entry: 1 + labels that can end a word */
+  double wordScore;
+  int32_t logAdd;
+  S2lHyp* beam;         /* [2][B*K] */
+  S2lRec* hist;         /* [maxOut + 1][B*K] */
+  double* cScore;       /* [B][nC] */
+  uint4* cMk;           /* [B][nC]: merge key (state pair, node, token) */
+  int32_t *cGrp, *cList, *cNext; /* [B][nC] */
+  int32_t* mTab;        /* [B][mSize]: per-step merge table (candidate index, -1 empty) */
+  int32_t mSize;
+  unsigned long long* sKey; /* [B][sSize]: (parent sid, edge) -> sid; ~0: empty */
+  int32_t* sVal;
+  int32_t* sCount;      /* [B] states handed out */
+  int32_t sSize, sMax;
+  int32_t* status;      /* [B] ST_* */
+  int32_t* merges;      /* [B] candidates folded into another (all steps) */
+  int32_t* words;       /* end: [B*K][len] */
+};
+
+FLTX_DEV uint64_t s2lMix(uint64_t x) {
+  x ^= x >> 33;
+  x *= 0xFF51AFD7ED558CCDull;
+  x ^= x >> 33;
+  x *= 0xC4CEB9FE1A85EC53ull;
+  return x ^ (x >> 33);
+}
+
+FLTX_DEV unsigned long long s2lPair(int32_t psid, int32_t edge) {
+  return ((unsigned long long)(uint32_t)psid << 32) | (uint32_t)edge;
+}
+
+/* TrieNode::children.find (binary search over the sorted tokens); -1: no child */
+FLTX_DEV int s2lChild(const S2lTrie& T, int node, int tok) {
+  int lo = T.kidOff[node], hi = T.kidOff[node + 1];
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    const int t = T.kidTok[mid];
+    if (t == tok) {
+      return T.kidNode[mid];
+    }
+    if (t < tok) {
+      lo = mid + 1;
+    } else {
+      hi = mid;
+    }
+  }
+  return -1;
+}
+
+/* LM::score over the LM's user ids (words, or tokens when isLmToken); finish when usr < 0 */
+FLTX_DEV float s2lLm(const S2lParams& Q, const int32_t* ctx, int usr, bool finish, int32_t* ctxOut) {
+  if (!Q.s.lmOn) {
+    return 0.0f;
+  }
+  const DecodeParams& L = Q.s.lmp;
+  const uint32_t w = finish ? (uint32_t)L.lmEos : (usr >= 0 && usr < L.nUsr) ? (uint32_t)L.usrToLm[usr] : (uint32_t)L.lmUnk;
+  return ngScore(L, ctx, w, ctxOut);
+}
+
+struct S2lCand {
+  double score;
+  float am, lmS;
+  int32_t hyp;       /* index in the previous beam */
+  int32_t token, word, node, src;
+  int32_t newEdge;   /* the state is child(prev.sid, newEdge) when isNew */
+  bool isNew;
+  int32_t usr;       /* the LM question that made the state (-2: finish) */
+};
+
+/* candidate j of the utterance: record slot j < nRowC (row k, entry e, sub-slot s: 0 = stay / eos, 1.. = the labels),
+ * then the carried hypotheses; false: no candidate */
+FLTX_DEV bool s2lCand(const S2lParams& Q, const S2lHyp* prev, const int32_t* hypOfRow, int64_t rb, int64_t nRowC,
+                      int64_t j, S2lCand& c) {
+  const S2sParams& P = Q.s;
+  if (j >= nRowC) {
+    const int i = (int)(j - nRowC);
+    const S2lHyp& h = prev[i];
+    if (h.token != P.eos) {
+      return false;
+    }
+    c.score = h.score;
+    c.am = 0.0f;
+    c.lmS = 0.0f;
+    c.hyp = i;
+    c.token = h.token;
+    c.word = -1;
+    c.node = h.node;
+    c.src = -1;
+    c.isNew = false;
+    return true;
+  }
+  const int cap = P.cap, S = Q.S;
+  const int k = (int)(j / ((int64_t)cap * S)), e = (int)((j / S) % cap), s = (int)(j % S);
+  const int64_t r = rb + k;
+  if (e >= P.recN[r]) {
+    return false;
+  }
+  const int i = hypOfRow[k];
+  const S2lHyp& h = prev[i];
+  const int tok = P.recTok[r * cap + e];
+  const float a = P.recAm[r * cap + e];
+  c.am = a;
+  c.hyp = i;
+  c.token = tok;
+  c.src = (int)r;
+  if (tok == P.eos) { /* (1) eos, at the root only (:115-141): finish(state) -- a new child with n-gram tables, the
+                       * same state with ZeroLM (lm/ZeroLM.cpp:24-25) */
+    if (s != 0 || h.node != 0) {
+      return false;
+    }
+    c.lmS = s2lLm(Q, h.ctx, -1, true, nullptr) - 0.0f; /* (lexMaxScore is 0 at the root) */
+    c.score = (((h.score + (double)a) + P.eosScore) + P.lmWeight * (double)c.lmS);
+    c.word = -1;
+    c.node = 0;
+    c.isNew = P.lmOn != 0;
+    c.newEdge = -1;
+    c.usr = -2;
+    return true;
+  }
+  const int child = s2lChild(Q.trie, h.node, tok); /* (2) a normal token: a child of the hypothesis' node */
+  if (child < 0) {
+    return false;
+  }
+  const float lexMax = h.node == 0 ? 0.0f : Q.trie.maxScore[h.node];
+  if (s == 0) { /* stay in the trie (:146-171) */
+    if (Q.isLmToken) {
+      c.lmS = s2lLm(Q, h.ctx, tok, false, nullptr);
+      c.isNew = true;
+      c.newEdge = tok;
+      c.usr = tok;
+    } else {
+      c.lmS = Q.trie.maxScore[child] - lexMax; /* smearing (float) */
+      c.isNew = false;
+    }
+    c.score = (h.score + (double)a) + P.lmWeight * (double)c.lmS;
+    c.word = -1;
+    c.node = child;
+    return true;
+  }
+  /* end a word: label s - 1 (:174-198; a token LM: the first label only, with the token's state and score) */
+  const int l0 = Q.trie.labOff[child], nl = Q.trie.labOff[child + 1] - l0;
+  if (s - 1 >= nl || (Q.isLmToken && s > 1)) {
+    return false;
+  }
+  const int word = Q.trie.labels[l0 + s - 1];
+  if (Q.isLmToken) {
+    c.lmS = s2lLm(Q, h.ctx, tok, false, nullptr);
+    c.newEdge = tok;
+    c.usr = tok;
+  } else {
+    c.lmS = s2lLm(Q, h.ctx, word, false, nullptr) - lexMax;
+    c.newEdge = word;
+    c.usr = word;
+  }
+  c.isNew = true;
+  c.score = ((h.score + (double)a) + Q.wordScore) + P.lmWeight * (double)c.lmS;
+  c.word = word;
+  c.node = 0;
+  return true;
+}
+
+/* the merge key: (the state's (parent sid, edge), trie node, token) */
+FLTX_DEV uint4 s2lMergeKey(const S2lCand& c, const S2lHyp& h) {
+  const unsigned long long st = c.isNew ? s2lPair(h.sid, c.newEdge) : s2lPair(h.psid, h.edge);
+  return make_uint4((uint32_t)(st >> 32), (uint32_t)st, (uint32_t)c.node, (uint32_t)c.token);
+}
+
+FLTX_DEV bool s2lSameKey(uint4 a, uint4 b) { return a.x == b.x && a.y == b.y && a.z == b.z && a.w == b.w; }
+
+/* the order of a group's fold: score descending, ties to the lower candidate index */
+FLTX_DEV bool s2lBefore(double sa, int64_t ja, double sb, int64_t jb) { return sa > sb || (sa == sb && ja < jb); }
+
+struct S2lStepLds {
+  S2sStepLds s;
+  int32_t full;
+};
+
+FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) {
+  const S2sParams& P = Q.s;
+  S2lStepLds& L = *(S2lStepLds*)smem;
+  S2sStepLds& S = L.s;
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+  const int K = P.K;
+  const int64_t rb = (int64_t)b * K;
+  const int lane = laneId(), wave = waveId();
+  if (P.done[b] || P.t >= P.maxOut) { /* a step after the last one: nothing to score */
+    for (int k = tid; k < K; k += kS2sStepThreads) {
+      P.outTok[rb + k] = -1;
+      P.outBeam[rb + k] = -1;
+      P.outSrc[rb + k] = -1;
+    }
+    if (tid == 0) {
+      P.outN[b] = 0;
+    }
+    return;
+  }
+  const int par = P.t & 1;
+  const S2lHyp* prev = Q.beam + (size_t)par * P.B * K + rb;
+  S2lHyp* next = Q.beam + (size_t)(par ^ 1) * P.B * K + rb;
+  const int nPrev = P.beamN[par * P.B + b];
+  const int nRows = P.nRowsInt[b];
+  /* 1. rows <-> hypotheses (the live ones in beam order: :42-52) */
+  {
+    const bool isLive = tid < nPrev && prev[tid].token != P.eos;
+    int tot;
+    const int q = s2sBlockRank(S, isLive, &tot);
+    if (tid < nPrev) {
+      S.rowOfHyp[tid] = isLive ? q : -1;
+      if (isLive) {
+        S.hypOfRow[q] = tid;
+      }
+    }
+    if (tid == 0) {
+      L.full = 0;
+    }
+    __syncthreads();
+  }
+  /* 2. the candidates: order keys, scores, merge keys; the best of the step */
+  const size_t cb = (size_t)b * P.nC;
+  unsigned long long* cKey = P.cKey + cb;
+  double* cScore = Q.cScore + cb;
+  uint4* cMk = Q.cMk + cb;
+  int32_t* cGrp = Q.cGrp + cb;
+  int32_t* cList = Q.cList + cb;
+  int32_t* cNext = Q.cNext + cb;
+  int32_t* mTab = Q.mTab + (size_t)b * Q.mSize;
+  const int64_t nRowC = (int64_t)nRows * P.cap * Q.S, n = nRowC + nPrev;
+  for (int j = tid; j < Q.mSize; j += kS2sStepThreads) {
+    mTab[j] = -1;
+  }
+  unsigned long long mx = 0ull;
+  for (int64_t j = tid; j < n; j += kS2sStepThreads) {
+    unsigned long long key = 0ull;
+    S2lCand c;
+    if (s2lCand(Q, prev, S.hypOfRow, rb, nRowC, j, c)) {
+      key = c.score == c.score ? f64Key(c.score + 0.0) : 0ull; /* (+0.0: -0 and +0 compare equal) */
+      cScore[j] = c.score;
+      cMk[j] = s2lMergeKey(c, prev[c.hyp]);
+    }
+    cKey[j] = key;
+    mx = key > mx ? key : mx;
+  }
+  mx = waveMax64(mx);
+  if (lane == 0) {
+    S.wmax[wave] = mx;
+  }
+  __syncthreads();
+  for (int w = 0; w < kS2sStepThreads / 64; ++w) {
+    mx = S.wmax[w] > mx ? S.wmax[w] : mx;
+  }
+  /* 3. threshold (candidatesStore step 1: score >= best - beamThreshold) */
+  unsigned long long thrKey = 1ull;
+  if (mx != 0ull) {
+    const double thr = f64FromKey(mx) - P.beamThreshold;
+    thrKey = thr == thr ? f64Key(thr + 0.0) : ~0ull;
+    thrKey = thrKey == 0ull ? 1ull : thrKey;
+  }
+  /* 4. merge (step 2): the first survivor of a key to claim its slot heads the group, the others join its list */
+  const uint32_t mMask = (uint32_t)Q.mSize - 1u;
+  for (int64_t j = tid; j < n; j += kS2sStepThreads) {
+    const unsigned long long key = cKey[j];
+    if (key != 0ull && key < thrKey) {
+      cKey[j] = 0ull;
+    } else if (key != 0ull) {
+      const uint4 mk = cMk[j];
+      uint32_t slot = (uint32_t)s2lMix(((unsigned long long)mk.x << 32 | mk.y) ^ s2lMix((unsigned long long)mk.z << 32 | mk.w)) & mMask;
+      for (;;) { /* (mSize >= 2 nC: a free slot always exists) */
+        const int32_t old = (int32_t)atomCas32((uint32_t*)&mTab[slot], 0xFFFFFFFFu, (uint32_t)j);
+        if (old == -1) {
+          cGrp[j] = (int32_t)j;
+          cList[j] = -1;
+          break;
+        }
+        if (s2lSameKey(cMk[old], mk)) {
+          cGrp[j] = old;
+          break;
+        }
+        slot = (slot + 1u) & mMask;
+      }
+    }
+  }
+  __syncthreads();
+  for (int64_t j = tid; j < n; j += kS2sStepThreads) {
+    if (cKey[j] != 0ull && cGrp[j] != (int32_t)j) {
+      cNext[j] = (int32_t)atomExch32((uint32_t*)&cList[cGrp[j]], (uint32_t)j);
+    }
+  }
+  __threadfence();
+  __syncthreads();
+  int nMerged = 0;
+  for (int64_t j = tid; j < n; j += kS2sStepThreads) {
+    if (cKey[j] == 0ull || cGrp[j] != (int32_t)j || cList[j] < 0) {
+      continue;
+    }
+    /* a group of two or more: the best member, then the fold in descending order from it */
+    int64_t best = j;
+    for (int32_t m = cList[j]; m >= 0; m = cNext[m]) {
+      best = s2lBefore(cScore[m], m, cScore[best], best) ? m : best;
+    }
+    double acc = cScore[best];
+    double lastS = acc;
+    int64_t lastJ = best;
+    for (;;) { /* the next member in the order after (lastS, lastJ) */
+      int64_t nx = -1;
+      double ns = 0.0;
+      for (int64_t m = j; m >= 0; m = (m == j ? cList[j] : cNext[m])) {
+        if (s2lBefore(lastS, lastJ, cScore[m], m) && (nx < 0 || s2lBefore(cScore[m], m, ns, nx))) {
+          nx = m;
+          ns = cScore[m];
+        }
+      }
+      if (nx < 0) {
+        break;
+      }
+      const double hi = acc > ns ? acc : ns, lo = acc < ns ? acc : ns;
+      acc = Q.logAdd ? hi + log1p(exp(lo - hi)) : hi;
+      lastS = ns;
+      lastJ = nx;
+      ++nMerged;
+    }
+    for (int64_t m = j; m >= 0; m = (m == j ? cList[j] : cNext[m])) {
+      cKey[m] = 0ull;
+    }
+    cScore[best] = acc;
+    cKey[best] = acc == acc ? f64Key(acc + 0.0) : 0ull;
+  }
+  __threadfence();
+  int surv = 0;
+  __syncthreads();
+  for (int64_t j = tid; j < n; j += kS2sStepThreads) {
+    surv += cKey[j] != 0ull ? 1 : 0;
+  }
+  const int nSurv = s2sBlockSum(S, surv);
+  nMerged = s2sBlockSum(S, nMerged);
+  /* 5. the K best: radix select over the 64-bit keys (as fltx_s2s.h) */
+  unsigned long long pre = 0ull, msk = 0ull;
+  bool all = nSurv <= K, allEq = false;
+  int need = K;
+  int64_t eqCut = -1;
+  for (int shift = 56; shift >= 0 && !all && !allEq; shift -= 8) {
+    __syncthreads();
+    S.hist[tid] = 0u;
+    __syncthreads();
+    for (int64_t j = tid; j < n; j += kS2sStepThreads) {
+      const unsigned long long key = cKey[j];
+      if (key != 0ull && (key & msk) == pre) {
+        atomAdd32(&S.hist[255u - (uint32_t)((key >> shift) & 255ull)], 1u);
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {
+      const SlScan sc = slScan(S.hist, need, false);
+      if (lane == 0) {
+        S.scanBstar = sc.bstar;
+        S.scanCum = sc.cum;
+        S.scanCnt = sc.cnt;
+      }
+    }
+    __syncthreads();
+    need -= S.scanCum;
+    pre |= (unsigned long long)(255 - S.scanBstar) << shift;
+    msk |= 255ull << shift;
+    allEq = S.scanCnt == need;
+  }
+  if (!all && !allEq) { /* equal keys at the cut: the lower candidate indices */
+    int seen = 0;
+    for (int64_t j0 = 0; j0 < n && eqCut < 0; j0 += kS2sStepThreads) {
+      const int64_t j = j0 + tid;
+      const bool eq = j < n && cKey[j] == pre;
+      int tot;
+      const int r = s2sBlockRank(S, eq, &tot);
+      if (eq && seen + r == need - 1) {
+        S.eqCut = j;
+      }
+      __syncthreads();
+      if (seen + tot >= need) {
+        eqCut = S.eqCut;
+      }
+      seen += tot;
+    }
+  }
+  if (tid == 0) {
+    S.nSel = 0;
+  }
+  __syncthreads();
+  for (int64_t j = tid; j < n; j += kS2sStepThreads) {
+    const unsigned long long key = cKey[j];
+    const bool sel = key != 0ull && (all || (key & msk) > pre || ((key & msk) == pre && (allEq || j <= eqCut)));
+    if (sel) {
+      const uint32_t p = atomAdd32((uint32_t*)&S.nSel, 1u);
+      if (p < (uint32_t)K) {
+        S.selIdx[p] = (uint32_t)j;
+        S.selKey[p] = key;
+      }
+    }
+  }
+  __syncthreads();
+  const int nSel = S.nSel < K ? S.nSel : K;
+  if (tid < nSel) {
+    const unsigned long long mk = S.selKey[tid];
+    const uint32_t mi = S.selIdx[tid];
+    int rank = 0;
+    for (int q = 0; q < nSel; ++q) {
+      const unsigned long long ok = S.selKey[q];
+      rank += (ok > mk || (ok == mk && S.selIdx[q] < mi)) ? 1 : 0;
+    }
+    S.order[rank] = tid;
+  }
+  __syncthreads();
+  /* 6. the new beam; survivors that enter a new state look it up (or insert it) in the utterance's state table */
+  S2lHyp nh;
+  S2lCand c;
+  bool isLive = false, claimed = false, hasNew = false;
+  uint32_t sslot = 0u;
+  unsigned long long skey = 0ull;
+  unsigned long long* sKey = Q.sKey + (size_t)b * Q.sSize;
+  int32_t* sVal = Q.sVal + (size_t)b * Q.sSize;
+  if (tid < nSel) {
+    const int64_t j = S.selIdx[S.order[tid]];
+    s2lCand(Q, prev, S.hypOfRow, rb, nRowC, j, c);
+    const S2lHyp& h = prev[c.hyp];
+    nh = h;
+    nh.parent = c.hyp;
+    nh.score = cScore[j];
+    if (j < nRowC) {
+      nh.am = h.am + (double)c.am;
+      nh.lm = h.lm + (double)c.lmS;
+      nh.token = c.token;
+      nh.word = c.word;
+      nh.node = c.node;
+      if (c.isNew) {
+        nh.psid = h.sid;
+        nh.edge = c.newEdge;
+        if (P.lmOn) {
+          (void)s2lLm(Q, h.ctx, c.usr, c.usr == -2, nh.ctx);
+        }
+        skey = s2lPair(nh.psid, nh.edge);
+        hasNew = true;
+        const uint32_t sMask = (uint32_t)Q.sSize - 1u;
+        uint32_t slot = (uint32_t)s2lMix(skey) & sMask;
+        int probes = 0;
+        for (; probes < Q.sSize; ++probes) {
+          const unsigned long long old = atomCas64(&sKey[slot], ~0ull, skey);
+          if (old == ~0ull || old == skey) {
+            claimed = old == ~0ull;
+            break;
+          }
+          slot = (slot + 1u) & sMask;
+        }
+        if (probes == Q.sSize) {
+          L.full = 1;
+        }
+        sslot = slot;
+      }
+      isLive = c.token != P.eos;
+    } else {
+      nh.word = -1;
+    }
+  }
+  __syncthreads();
+  if (claimed) {
+    const int32_t v = (int32_t)atomAdd32((uint32_t*)&Q.sCount[b], 1u);
+    if (v >= Q.sMax) {
+      L.full = 1;
+    }
+    sVal[sslot] = v;
+  }
+  __threadfence();
+  __syncthreads();
+  if (L.full) { /* the state table is full: the utterance stops, its status says so (never a silent wrong merge) */
+    for (int k = tid; k < K; k += kS2sStepThreads) {
+      P.outTok[rb + k] = -1;
+      P.outBeam[rb + k] = -1;
+      P.outSrc[rb + k] = -1;
+    }
+    if (tid == 0) {
+      Q.status[b] |= ST_TABLE_FULL;
+      P.outN[b] = 0;
+      P.nRowsInt[b] = 0;
+      P.done[b] = 1;
+      P.finalStep[b] = P.t;
+    }
+    return;
+  }
+  if (tid < nSel) {
+    if (hasNew) {
+      nh.sid = (int32_t)loadCoherent32((const uint32_t*)&sVal[sslot]);
+    }
+    next[tid] = nh;
+    {
+      S2lRec rec;
+      rec.token = nh.token;
+      rec.word = nh.word;
+      rec.parent = nh.parent;
+      rec.pad = 0;
+      Q.hist[(size_t)(P.t + 1) * P.B * K + rb + tid] = rec;
+    }
+  }
+  int nLive;
+  const int q = s2sBlockRank(S, isLive, &nLive);
+  const bool fin = nSel == 0 || nLive == 0 || P.t + 1 >= P.maxOut;
+  if (fin) {
+    nLive = 0;
+  }
+  if (isLive && !fin) {
+    P.outTok[rb + q] = nh.token;
+    P.outBeam[rb + q] = nh.parent;
+    P.outSrc[rb + q] = c.src;
+  }
+  for (int k = nLive + tid; k < K; k += kS2sStepThreads) {
+    P.outTok[rb + k] = -1;
+    P.outBeam[rb + k] = -1;
+    P.outSrc[rb + k] = -1;
+  }
+  if (tid == 0) {
+    P.outN[b] = nLive;
+    P.nRowsInt[b] = nLive;
+    Q.merges[b] += nMerged;
+    if (nSel > 0) {
+      P.beamN[(par ^ 1) * P.B + b] = nSel;
+    }
+    if (fin) {
+      P.done[b] = 1;
+      P.finalStep[b] = nSel > 0 ? P.t + 1 : P.t; /* the last non-empty beam (:204-207) */
+    }
+  }
+}
+
+/* decodeStep's start (:29-31): the root in LM::start's state (sid 0) at the trie's root */
+FLTX_DEV void s2lBeginUtterance(const S2lParams& Q, int b) {
+  const S2sParams& P = Q.s;
+  const int64_t rb = (int64_t)b * P.K;
+  S2lHyp h;
+  h.score = 0.0;
+  h.am = 0.0;
+  h.lm = 0.0;
+  h.token = -1;
+  h.word = -1;
+  h.parent = -1;
+  h.node = 0;
+  h.sid = 0;
+  h.psid = -1;
+  h.edge = -1;
+  for (int j = 0; j < kS2sCtx; ++j) {
+    h.ctx[j] = P.ctx0[j];
+  }
+  Q.beam[rb] = h;
+  P.beamN[b] = 1;
+  Q.sCount[b] = 1;
+  Q.status[b] = 0;
+  Q.merges[b] = 0;
+  const int live = P.maxOut > 0 ? 1 : 0;
+  P.nRowsInt[b] = live;
+  P.done[b] = live ? 0 : 1;
+  P.finalStep[b] = 0;
+  for (int k = 0; k < P.K; ++k) {
+    P.outTok[rb + k] = -1;
+    P.outBeam[rb + k] = -1;
+    P.outSrc[rb + k] = -1;
+  }
+  P.outN[b] = live;
+}
+
+/* getAllFinalHypothesis (:209-211, Utils.h:230-266): tokens and words of the final beam's paths, right-aligned in
+ * rows of maxOutputLength + 3 with -1 in front */
+FLTX_DEV void s2lEndUtterance(const S2lParams& Q, int b, int tid, int nThreads) {
+  const S2sParams& P = Q.s;
+  const int K = P.K;
+  const int64_t rb = (int64_t)b * K;
+  const int fs = P.done[b] ? P.finalStep[b] : P.t;
+  const int par = fs & 1;
+  const int n = P.beamN[par * P.B + b];
+  const S2lHyp* beam = Q.beam + (size_t)par * P.B * K + rb;
+  const int len = P.len;
+  for (int k = tid; k < n; k += nThreads) {
+    const S2lHyp& h = beam[k];
+    double* sc = P.outScores + (rb + k) * 3;
+    sc[0] = h.score;
+    sc[1] = h.am;
+    sc[2] = h.lm;
+    int32_t* out = P.tokens + (rb + k) * len;
+    int32_t* wout = Q.words + (rb + k) * len;
+    for (int f = 0; f < len - fs; ++f) {
+      out[f] = -1;
+      wout[f] = -1;
+    }
+    int p = k;
+    for (int s = fs; s >= 1; --s) {
+      const S2lRec rec = Q.hist[(size_t)s * P.B * K + rb + p];
+      out[len - 1 - (fs - s)] = rec.token;
+      wout[len - 1 - (fs - s)] = rec.word;
+      p = rec.parent;
+    }
+  }
+  if (tid == 0) {
+    P.outNHyp[b] = n;
+    P.uttNBeam[b] = n;
+    P.uttFrame[b] = len - 1;
+    P.uttStatus[b] = Q.status[b];
+  }
+}
+
+} // namespace fltx

@@ -5,8 +5,8 @@
  * classes, so `from flashlight.lib.text.decoder import ...` code runs on the
  * MI355X path (see text_amd/compat/).  Same class names, constructor keywords,
  * method names, raw-address emissions (`ndarray.ctypes.data`) and pickle
- * support.  The lexicon-free seq2seq names are Python classes of the compat package
- * (text_amd/compat/.../decoder/_seq2seq.py over fltx_s2s_*).  Additive: decode_batch().
+ * support.  The seq2seq names are Python classes of the compat package
+ * (text_amd/compat/.../decoder/_seq2seq.py over fltx_s2s_* / fltx_s2s_lex_*).  Additive: decode_batch().
  */
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
@@ -163,13 +163,17 @@ PYBIND11_MODULE(flashlight_lib_text_decoder, m) {
       .def("get_root", &Trie::getRoot, py::return_value_policy::reference_internal)
       .def("insert", &Trie::insert, "indices"_a, "label"_a, "score"_a)
       .def("search", &Trie::search, "indices"_a)
-      .def("smear", &Trie::smear, "smear_mode"_a);
+      .def("smear", &Trie::smear, "smear_mode"_a)
+      /* additive: the fltx_htrie handle, for decoders built over the C ABI (the compat LexiconSeq2SeqDecoder) */
+      .def("_fltx_host_handle", [](const Trie& t) { return (uintptr_t)t.hostHandle(); });
 
   py::class_<LM, LMPtr, PyLM>(m, "LM")
       .def(py::init<>())
       .def("start", &LM::start, "start_with_nothing"_a)
       .def("score", &LM::score, "state"_a, "usr_token_idx"_a)
-      .def("finish", &LM::finish, "state"_a);
+      .def("finish", &LM::finish, "state"_a)
+      /* additive: the fltx_lm handle of ZeroLM / KenLM (0 for a user-defined LM) */
+      .def("_fltx_device_handle", [](const LM& lm) { return (uintptr_t)lm.deviceHandle(); });
 
   py::class_<LMState, LMStatePtr>(m, "LMState")
       .def(py::init<>())
