@@ -284,6 +284,21 @@ FLTX_API int fltx_s2s_begin(fltx_decoder* dec, int32_t B, int32_t V, int32_t* ne
 FLTX_API int fltx_s2s_step(fltx_decoder* dec, const float* scores, int32_t on_device, int64_t row_stride,
                            const uint8_t* row_valid, int32_t* next_token, int32_t* next_beam_idx,
                            int32_t* next_src_row, int32_t* n_rows);
+/* Element types and kinds of the rows fltx_s2s_step_typed reads. */
+typedef enum fltx_dtype { FLTX_DTYPE_F32 = 0, FLTX_DTYPE_F16 = 1, FLTX_DTYPE_BF16 = 2 } fltx_dtype;
+enum { FLTX_S2S_LOG_PROBS = 0, FLTX_S2S_LOGITS = 1 };
+/* fltx_s2s_step on the model's output as the model produces it: rows of `dtype` (IEEE binary16 or bfloat16 bits, or
+ * float), row b*K + k at scores + (b*K + k) * row_stride ELEMENTS (row_stride >= V; rows of 2-byte types need only be
+ * 2-byte aligned).  kind FLTX_S2S_LOG_PROBS: the row holds the model's scores (widened exactly to float).
+ * kind FLTX_S2S_LOGITS: raw logits; the model score of token v is (float)((double)x_v - lse), lse = m + log(sum over
+ * the non-NaN entries of exp(x_v - m)), m their maximum (lse = m when m is not finite); a NaN score is never a
+ * candidate.  row_lse (may be NULL) is a device buffer of B*K doubles: in logits mode it receives each live row's lse
+ * and NaN for every other row; in log-probs mode it is left untouched.  Host rows (on_device == 0) are staged in their
+ * own type.  Row contract, asynchrony and the no-op step after the last one are those of fltx_s2s_step; works on both
+ * seq2seq decoder kinds.  FLTX_ERR_INVALID on a bad dtype or kind or row_stride < V. */
+FLTX_API int fltx_s2s_step_typed(fltx_decoder* dec, const void* scores, int32_t dtype, int32_t kind,
+                                 int32_t on_device, int64_t row_stride, const uint8_t* row_valid, double* row_lse,
+                                 int32_t* next_token, int32_t* next_beam_idx, int32_t* next_src_row, int32_t* n_rows);
 /* *done = 1 when every utterance is done (no live hypothesis, or max_output_length steps); synchronises. */
 FLTX_API int fltx_s2s_done(fltx_decoder* dec, int32_t* done);
 /* The back-trace (:152-163): every utterance's final beam -- the last non-empty one, which may hold unfinished

@@ -89,8 +89,8 @@ class Lib:
         "fltx_htrie_search", "fltx_htrie_smear", "fltx_htrie_num_nodes", "fltx_htrie_upload",
         "fltx_decoder_bytes", "fltx_htrie_node", "fltx_group_create", "fltx_group_destroy", "fltx_group_size", "fltx_group_decoder",
         "fltx_group_decode_batch", "fltx_group_result_count", "fltx_group_result_fetch", "fltx_group_synchronize",
-        "fltx_s2s_decoder_create", "fltx_s2s_begin", "fltx_s2s_step", "fltx_s2s_done", "fltx_s2s_end",
-        "fltx_s2s_lex_decoder_create", "fltx_s2s_lex_set_max_states", "fltx_s2s_lex_info",
+        "fltx_s2s_decoder_create", "fltx_s2s_begin", "fltx_s2s_step", "fltx_s2s_step_typed", "fltx_s2s_done",
+        "fltx_s2s_end", "fltx_s2s_lex_decoder_create", "fltx_s2s_lex_set_max_states", "fltx_s2s_lex_info",
     ]
 
     def __init__(self, path=None):
@@ -163,6 +163,7 @@ class Lib:
             "fltx_s2s_decoder_create": [vp, C.POINTER(S2sOptions), vp, i32, i32, pvp],
             "fltx_s2s_begin": [vp, i32, i32, vp, vp, vp, vp],
             "fltx_s2s_step": [vp, vp, i32, i64, vp, vp, vp, vp, vp],
+            "fltx_s2s_step_typed": [vp, vp, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp],
             "fltx_s2s_done": [vp, vp],
             "fltx_s2s_end": [vp],
             "fltx_s2s_lex_decoder_create": [vp, C.POINTER(S2sLexOptions), vp, vp, i32, i32, i32, pvp],
@@ -791,6 +792,12 @@ class BatchDecoder:
             pass
 
 
+# fltx_s2s_step_typed: element types (fltx_dtype) and kinds of the rows
+DTYPE_F32, DTYPE_F16, DTYPE_BF16 = 0, 1, 2
+S2S_KINDS = {"log_probs": 0, "logits": 1}
+_NP_DTYPES = {DTYPE_F32: np.float32, DTYPE_F16: np.float16, DTYPE_BF16: np.uint16}
+
+
 class Seq2SeqBatchDecoder(BatchDecoder):
     """fltx_s2s_*: LexiconFreeSeq2SeqDecoder for B utterances at once, one device step per model call.
 
@@ -837,13 +844,28 @@ class Seq2SeqBatchDecoder(BatchDecoder):
         self._chk(self.L.lib.fltx_s2s_begin(self.h, self.B, self.V, *[self._addr(o) for o in out]))
         return tuple(out)
 
-    def step(self, scores, row_valid=None):
-        """scores: [B*K, >= V] float32 (rows b*K + k), a torch tensor on the device (any row stride, unit column
-        stride) or a host numpy array; row_valid: None or B*K bytes / bools (0: the model dropped the row)."""
+    def step(self, scores, row_valid=None, *, kind="log_probs", lse_out=None, dtype=None):
+        """scores: [B*K, >= V] rows b*K + k: a torch tensor of float32, float16 or bfloat16 on the device or the host
+        (any row stride, unit column stride), or a numpy float32 / float16 array -- or uint16 holding bfloat16 bits
+        with dtype="bf16".  kind: "log_probs" (the model's scores) or "logits" (the step takes each row's
+        log-softmax itself, fltx_s2s_step_typed).  lse_out: None or a device float64 tensor of B*K that receives each
+        live row's log-sum-exp in logits mode (NaN for the other rows).  row_valid: None or B*K bytes / bools (0: the
+        model dropped the row).  float32 log-probs go through fltx_s2s_step exactly as before."""
+        if kind not in S2S_KINDS:
+            raise ValueError("kind: one of %s" % sorted(S2S_KINDS))
         out = self._rows()
         ptrs = [self._addr(o) for o in out]
+        BK = self.B * int(self.options.beam_size)
         if isinstance(scores, np.ndarray):
-            sc = np.ascontiguousarray(scores, dtype=np.float32).reshape(self.B * int(self.options.beam_size), -1)
+            if dtype is not None:
+                if dtype not in ("bf16", "bfloat16") or scores.dtype != np.uint16:
+                    raise TypeError("dtype=%r: numpy rows of bfloat16 bits are uint16 with dtype='bf16'" % (dtype,))
+                dt = DTYPE_BF16
+            elif scores.dtype == np.float16:
+                dt = DTYPE_F16
+            else:
+                dt = DTYPE_F32
+            sc = np.ascontiguousarray(scores, dtype=_NP_DTYPES[dt]).reshape(BK, -1)
             stride, ptr = sc.shape[1], sc.ctypes.data
             on_dev = 1 if self._emu else 0
             rv = None if row_valid is None else np.ascontiguousarray(row_valid, dtype=np.uint8)
@@ -851,11 +873,28 @@ class Seq2SeqBatchDecoder(BatchDecoder):
         else:
             import torch
             sc = scores.reshape(-1, scores.shape[-1])
-            assert sc.dtype == torch.float32 and sc.stride(-1) == 1, "scores: float32 rows of unit column stride"
-            stride, ptr, on_dev = sc.stride(0), sc.data_ptr(), 1
-            rv = None if row_valid is None else row_valid.reshape(-1).to(torch.uint8).contiguous()
-            rvp = None if rv is None else rv.data_ptr()
-        self._chk(self.L.lib.fltx_s2s_step(self.h, ptr, on_dev, stride, rvp, *ptrs))
+            dts = {torch.float32: DTYPE_F32, torch.float16: DTYPE_F16, torch.bfloat16: DTYPE_BF16}
+            assert sc.dtype in dts and sc.stride(-1) == 1, \
+                "scores: float32 / float16 / bfloat16 rows of unit column stride"
+            dt = dts[sc.dtype]
+            stride, ptr, on_dev = sc.stride(0), sc.data_ptr(), 0 if sc.device.type == "cpu" else 1
+            if sc.device.type == "cpu":
+                rv = None if row_valid is None else np.ascontiguousarray(
+                    row_valid.cpu().numpy() if hasattr(row_valid, "cpu") else row_valid, dtype=np.uint8)
+                rvp = None if rv is None else rv.ctypes.data
+            else:
+                rv = None if row_valid is None else row_valid.reshape(-1).to(torch.uint8).contiguous()
+                rvp = None if rv is None else rv.data_ptr()
+        if dt == DTYPE_F32 and kind == "log_probs":
+            self._chk(self.L.lib.fltx_s2s_step(self.h, ptr, on_dev, stride, rvp, *ptrs))
+        else:
+            lp = None
+            if lse_out is not None:
+                n_lse = lse_out.size if isinstance(lse_out, np.ndarray) else lse_out.numel()
+                assert n_lse >= BK and str(lse_out.dtype).endswith("float64"), "lse_out: B*K float64 on the device"
+                lp = self._addr(lse_out)
+            self._chk(self.L.lib.fltx_s2s_step_typed(self.h, ptr, dt, S2S_KINDS[kind], on_dev, stride, rvp, lp,
+                                                      *ptrs))
         self._inputs = (sc, rv)  # (kept until the next step: the kernels read them asynchronously)
         return tuple(out)
 
@@ -868,10 +907,11 @@ class Seq2SeqBatchDecoder(BatchDecoder):
         self._chk(self.L.lib.fltx_s2s_end(self.h))
         self.N = self.V
 
-    def decode(self, step_fn, B, V, check_every=8):
+    def decode(self, step_fn, B, V, check_every=8, *, kind="log_probs"):
         """The whole search: step_fn(token [B*K], src_row [B*K], row_mask [B*K] bool, t) -> scores [B*K, V] (or
         (scores, row_valid)) is called until every utterance is done; returns results_batch().  A step after the
-        last one is a no-op, so done() -- a host wait -- is asked every `check_every` steps only."""
+        last one is a no-op, so done() -- a host wait -- is asked every `check_every` steps only.  kind="logits":
+        step_fn returns the model's raw logits (float32 / float16 / bfloat16), see step()."""
         import torch
         K = int(self.options.beam_size)
         tok, beam, src, n = self.begin(B, V)
@@ -882,7 +922,7 @@ class Seq2SeqBatchDecoder(BatchDecoder):
             mask = (ar[None, :] < n[:, None]).reshape(-1)
             r = step_fn(tok.reshape(-1), src.reshape(-1), mask, t)
             scores, valid = r if isinstance(r, tuple) else (r, None)
-            tok, beam, src, n = self.step(scores, valid)
+            tok, beam, src, n = self.step(scores, valid, kind=kind)
         self.end()
         return self.results_batch()
 

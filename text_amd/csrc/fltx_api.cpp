@@ -155,6 +155,16 @@ __global__ void __launch_bounds__(64) fltx_s2s_begin_kernel(S2sParams P) {
 __global__ void __launch_bounds__(256) fltx_s2s_end_kernel(S2sParams P) {
   s2sEndUtterance(P, (int)blockIdx.x, (int)threadIdx.x, (int)blockDim.x);
 }
+/* the typed front end (fltx_s2s_step_typed): fp16 / bf16 rows, and logits of any of the three types */
+template <int DT, bool LOGITS>
+__global__ void __launch_bounds__(kS2sTypedThreads) fltx_s2s_typed_kernel(S2sTypedParams Q) {
+  __shared__ __attribute__((aligned(16))) S2sTypedLds fltx_s2s_typed_lds;
+  s2sTypedRows<DT, LOGITS>(Q, (char*)&fltx_s2s_typed_lds);
+}
+template <int DT, bool LOGITS>
+static void s2sTypedLaunch(int nRows, hipStream_t st, const S2sTypedParams& T) {
+  hipLaunchKernelGGL((fltx_s2s_typed_kernel<DT, LOGITS>), dim3(nRows), dim3(kS2sTypedThreads), 0, st, T);
+}
 /* fltx_s2s_lex.h: the lexicon seq2seq step (its front end is fltx_s2s_tokbeam_kernel), start and back-trace */
 __global__ void __launch_bounds__(kS2sStepThreads) fltx_s2s_lex_step_kernel(S2lParams Q) {
   __shared__ __attribute__((aligned(16))) S2lStepLds fltx_s2l_lds;
@@ -5153,6 +5163,122 @@ int fltx_s2s_step(fltx_decoder* d, const float* scores, int32_t onDevice, int64_
 #else
   if (!last) {
     hipLaunchKernelGGL(fltx_s2s_tokbeam_kernel, dim3(nFront), dim3(256), 0, st, P);
+    HIPCHK(hipGetLastError());
+  }
+  if (lex) {
+    hipLaunchKernelGGL(fltx_s2s_lex_step_kernel, dim3(d->B), dim3(kS2sStepThreads), 0, st, Q);
+  } else {
+    hipLaunchKernelGGL(fltx_s2s_step_kernel, dim3(d->B), dim3(kS2sStepThreads), 0, st, P);
+  }
+  HIPCHK(hipGetLastError());
+#endif
+  if (!last) {
+    ++d->s2sT;
+  }
+  return FLTX_OK;
+}
+
+/* the typed front end (fltx_s2s.h: s2sTypedRows) in place of fltx_s2s_tokbeam_kernel, then the same step kernel */
+int fltx_s2s_step_typed(fltx_decoder* d, const void* scores, int32_t dtype, int32_t kind, int32_t onDevice,
+                        int64_t rowStride, const uint8_t* rowValid, double* rowLse, int32_t* nextTok,
+                        int32_t* nextBeam, int32_t* nextSrc, int32_t* nRows) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = s2sCheck(d, "fltx_s2s_step_typed");
+  if (rc) {
+    return rc;
+  }
+  if (dtype != FLTX_DTYPE_F32 && dtype != FLTX_DTYPE_F16 && dtype != FLTX_DTYPE_BF16) {
+    return fail(FLTX_ERR_INVALID, "fltx_s2s_step_typed: dtype %d", dtype);
+  }
+  if (kind != FLTX_S2S_LOG_PROBS && kind != FLTX_S2S_LOGITS) {
+    return fail(FLTX_ERR_INVALID, "fltx_s2s_step_typed: kind %d", kind);
+  }
+  if (!d->s2sBegun) {
+    return fail(FLTX_ERR_STATE, "fltx_s2s_step_typed: fltx_s2s_begin first");
+  }
+  if (rowStride < d->N) {
+    return fail(FLTX_ERR_INVALID, "fltx_s2s_step_typed: row_stride %lld < V = %d", (long long)rowStride, d->N);
+  }
+  const bool logits = kind == FLTX_S2S_LOGITS;
+  if (dtype == FLTX_DTYPE_F32 && !logits) { /* float log-probs: exactly fltx_s2s_step */
+    return fltx_s2s_step(d, (const float*)scores, onDevice, rowStride, rowValid, nextTok, nextBeam, nextSrc, nRows);
+  }
+  if (!nextTok || !nextBeam || !nextSrc || !nRows || (!scores && d->s2sT < d->s2sMaxOut)) {
+    return fail(FLTX_ERR_INVALID, "fltx_s2s_step_typed: bad argument");
+  }
+  if (d->s2sMSel > kS2sTypedMaxList) { /* (not reachable within the limits of fltx_s2s_begin) */
+    return fail(FLTX_ERR_UNSUPPORTED, "fltx_s2s_step_typed: a token beam of %d > %d", d->s2sMSel, kS2sTypedMaxList);
+  }
+  Stream st = d->ctx->stream;
+  const size_t BK = (size_t)d->B * d->s2sOpt.beam_size;
+  const size_t elem = dtype == FLTX_DTYPE_F32 ? 4 : 2;
+  const bool last = d->s2sT >= d->s2sMaxOut; /* nothing to score: the kernels only list no rows */
+  if (!onDevice && !last) {
+    const size_t nE = (BK - 1) * (size_t)rowStride + (size_t)d->N;
+    if (d->s2sScores.ensure(elem * nE, st, false) || (rowValid && d->s2sValid.ensure(BK, st, false))) {
+      return fail(FLTX_ERR_OOM, "seq2seq: staging allocation failed");
+    }
+    if (devCopyH2D(d->s2sScores.p, scores, elem * nE, st) ||
+        (rowValid && devCopyH2D(d->s2sValid.p, rowValid, BK, st))) {
+      return fail(FLTX_ERR_HIP, "seq2seq: upload failed");
+    }
+    scores = d->s2sScores.p;
+    rowValid = rowValid ? d->s2sValid.as<uint8_t>() : nullptr;
+  }
+  if (last && logits && rowLse && devMemset(rowLse, 0xFF, 8 * BK, st)) { /* (all-ones: a NaN) */
+    return fail(FLTX_ERR_HIP, "fltx_s2s_step_typed: memset failed");
+  }
+  const bool lex = d->kind == FLTX_DECODER_S2S_LEXICON;
+  S2lParams Q;
+  if (lex) {
+    Q = s2lParams(d);
+  } else {
+    memset(&Q, 0, sizeof(Q));
+    Q.s = s2sParams(d);
+  }
+  S2sParams& P = Q.s;
+  P.rowStride = rowStride;
+  P.rowValid = rowValid;
+  P.outTok = nextTok;
+  P.outBeam = nextBeam;
+  P.outSrc = nextSrc;
+  P.outN = nRows;
+  S2sTypedParams T;
+  T.s = P;
+  T.x = scores;
+  T.rowLse = logits ? rowLse : nullptr;
+#ifdef FLTX_EMU
+  const S2sParams* pp = &P;
+  const S2lParams* qp = &Q;
+  const S2sTypedParams* tp = &T;
+  if (!last) {
+    std::function<void(char*)> fn;
+    switch (dtype * 2 + (logits ? 1 : 0)) {
+      case 1: fn = [tp](char* smem) { s2sTypedRows<kS2sDtF32, true>(*tp, smem); }; break;
+      case 2: fn = [tp](char* smem) { s2sTypedRows<kS2sDtF16, false>(*tp, smem); }; break;
+      case 3: fn = [tp](char* smem) { s2sTypedRows<kS2sDtF16, true>(*tp, smem); }; break;
+      case 4: fn = [tp](char* smem) { s2sTypedRows<kS2sDtBf16, false>(*tp, smem); }; break;
+      default: fn = [tp](char* smem) { s2sTypedRows<kS2sDtBf16, true>(*tp, smem); }; break;
+    }
+    emuLaunch((int)BK, kS2sTypedThreads, sizeof(S2sTypedLds), fn);
+  }
+  if (lex) {
+    emuLaunch(d->B, kS2sStepThreads, sizeof(S2lStepLds), [qp](char* smem) { s2lStepUtterance(*qp, smem); });
+  } else {
+    emuLaunch(d->B, kS2sStepThreads, sizeof(S2sStepLds), [pp](char* smem) { s2sStepUtterance(*pp, smem); });
+  }
+#else
+  if (!last) {
+    switch (dtype * 2 + (logits ? 1 : 0)) {
+      case 1: s2sTypedLaunch<kS2sDtF32, true>((int)BK, st, T); break;
+      case 2: s2sTypedLaunch<kS2sDtF16, false>((int)BK, st, T); break;
+      case 3: s2sTypedLaunch<kS2sDtF16, true>((int)BK, st, T); break;
+      case 4: s2sTypedLaunch<kS2sDtBf16, false>((int)BK, st, T); break;
+      default: s2sTypedLaunch<kS2sDtBf16, true>((int)BK, st, T); break;
+    }
     HIPCHK(hipGetLastError());
   }
   if (lex) {

@@ -201,6 +201,289 @@ FLTX_DEV void s2sTokBeamRows(const S2sParams& P, char* smem) {
   s2sTokBeamRow(P, S, P.scores + r * P.rowStride, P.recTok + r * P.cap, P.recAm + r * P.cap, P.recN + r);
 }
 
+/* ---- typed front end: the model's rows as it produces them (f32 / fp16 / bf16, log-probs or raw logits) ----------
+ * One workgroup of kS2sTypedThreads per live row; it writes the record s2sTokBeamRow writes.  Each element is widened
+ * to float with bit operations (no half-precision intrinsics: the emulator runs the same code); logits become
+ * a_v = (float)((double)x_v - lse) with lse the row's log-sum-exp (max, then the sum of f32 exp(x - max) in double).
+ * The token beam is taken over s2sKey32(a_v) with the ties to the lower token, as in the f32 path: a radix select over
+ * the 48-bit composite key32(a_v) << 16 | (0xFFFF - token), whose keys are distinct, so the cut is one element.
+ * A row of V <= kS2sTypedRegs * kS2sTypedThreads values is read from HBM once and kept in registers (64 per thread)
+ * between the max, sum, radix and listing passes; wider rows (up to kS2sMaxV) are re-read in every pass. */
+constexpr int kS2sTypedThreads = 256;
+constexpr int kS2sTypedRegs = 64;
+constexpr int kS2sTypedReadOnceV = kS2sTypedThreads * kS2sTypedRegs; /* 16 384 */
+constexpr int kS2sTypedMaxList = 264; /* >= the largest mSel: min(Kt, V, K + 1) <= 257, kS2lMaxKt = 256 */
+enum { kS2sDtF32 = 0, kS2sDtF16 = 1, kS2sDtBf16 = 2 };
+
+struct S2sTypedParams {
+  S2sParams s;     /* (s.scores is not read) */
+  const void* x;   /* the rows: element (r, i) at x + (r * s.rowStride + i) elements */
+  double* rowLse;  /* [B*K] or null: logits mode writes lse (live rows) or NaN */
+};
+
+struct S2sTypedLds {
+  uint32_t hist[kSlNB];
+  int32_t listTok[kS2sTypedMaxList];
+  float listAm[kS2sTypedMaxList];
+  double wsum[kS2sTypedThreads / 64];
+  uint32_t wmax[kS2sTypedThreads / 64];
+  int32_t wcnt[kS2sTypedThreads / 64];
+  uint32_t nList;
+  int32_t eosIn;
+  float eosA;
+};
+
+/* fp16 -> float, exact: normals and inf / NaN by moving the fields, subnormals as mantissa * 2^-24 (exact in f32) */
+FLTX_DEV float s2sWidenF16(uint32_t h) {
+  const uint32_t s = (h & 0x8000u) << 16, e = (h >> 10) & 31u, m = h & 1023u;
+  if (e == 31u) {
+    return __uint_as_float(s | 0x7F800000u | (m << 13));
+  }
+  if (e != 0u) {
+    return __uint_as_float(s | ((e + 112u) << 23) | (m << 13));
+  }
+  return __uint_as_float(s | __float_as_uint((float)m * 5.9604644775390625e-8f));
+}
+
+template <int DT>
+FLTX_DEV float s2sElem(const void* row, int i) {
+  if constexpr (DT == kS2sDtF32) {
+    return ((const float*)row)[i];
+  } else if constexpr (DT == kS2sDtF16) {
+    return s2sWidenF16((uint32_t)((const uint16_t*)row)[i]);
+  } else {
+    return __uint_as_float((uint32_t)((const uint16_t*)row)[i] << 16);
+  }
+}
+
+/* the order key of a raw element: f32Key, 0 for NaN (the max and the sum skip those) */
+FLTX_DEV uint32_t s2sRawKey(float x) { return x == x ? f32Key(x) : 0u; }
+
+/* the model score of token i: the widened element, minus lse for logits */
+template <int DT, bool LOGITS>
+FLTX_DEV float s2sTypedScore(const void* row, int i, double lse) {
+  const float x = s2sElem<DT>(row, i);
+  return LOGITS ? (float)((double)x - lse) : x;
+}
+
+/* f(token, key) for every token of the row -- with the registers, also for the padding slots beyond V, whose key is
+ * 0.  RAW: the raw element's s2sRawKey (logits before lse is known), else s2sKey32 of the model score */
+template <int DT, bool LOGITS, bool CACHED, bool RAW, typename F>
+FLTX_DEV void s2sTypedEach(const void* row, int V, double lse, const uint32_t* kr, F&& f) {
+  int tid = (int)threadIdx.x;
+  if constexpr (CACHED) {
+#ifndef FLTX_EMU
+    __asm__ volatile("" : "+v"(tid)); /* (a new value per pass: nothing per token is hoisted out of the passes) */
+#endif
+#pragma unroll
+    for (int j = 0; j < kS2sTypedRegs; ++j) {
+      if (j * kS2sTypedThreads < V) { /* (uniform: the slots a narrow row does not reach cost a scalar branch) */
+        f(tid + j * kS2sTypedThreads, kr[j]);
+      }
+    }
+  } else {
+    for (int i = tid; i < V; i += kS2sTypedThreads) {
+      f(i, RAW ? s2sRawKey(s2sElem<DT>(row, i)) : s2sKey32(s2sTypedScore<DT, LOGITS>(row, i, lse)));
+    }
+  }
+}
+
+FLTX_DEV int s2sTypedBlockSum(S2sTypedLds& S, int v) {
+  const int s = (int)waveReadLane32((uint32_t)waveInclusiveScan(v), 63);
+  __syncthreads();
+  if (laneId() == 0) {
+    S.wcnt[waveId()] = s;
+  }
+  __syncthreads();
+  int all = 0;
+  for (int w = 0; w < kS2sTypedThreads / 64; ++w) {
+    all += S.wcnt[w];
+  }
+  return all;
+}
+
+template <int DT, bool LOGITS, bool CACHED>
+FLTX_DEV void s2sTypedRow(const S2sTypedParams& Q, S2sTypedLds& S, int64_t r) {
+  const S2sParams& P = Q.s;
+  const int tid = (int)threadIdx.x, lane = laneId(), wave = waveId();
+  const int V = P.V, m = P.mSel;
+  const void* row = (const char*)Q.x + r * P.rowStride * (DT == kS2sDtF32 ? 4 : 2);
+  /* the row's keys, 64 per thread: raw keys for logits (model-score keys once lse is known), model-score keys else */
+  uint32_t kr[CACHED ? kS2sTypedRegs : 1];
+  if constexpr (CACHED) {
+#pragma unroll
+    for (int j = 0; j < kS2sTypedRegs; ++j) {
+      const int i = tid + j * kS2sTypedThreads;
+      kr[j] = 0u;
+      if (j * kS2sTypedThreads < V) {
+        const float x = i < V ? s2sElem<DT>(row, i) : __uint_as_float(0x7FC00000u);
+        kr[j] = LOGITS ? s2sRawKey(x) : s2sKey32(x);
+      }
+    }
+  }
+  /* logits: lse = max + log(sum exp(x - max)) over the non-NaN entries; lse = max when that is not finite */
+  double lse = 0.0;
+  if constexpr (LOGITS) {
+    uint32_t mk = 0u;
+    s2sTypedEach<DT, LOGITS, CACHED, true>(row, V, 0.0, kr, [&](int, uint32_t k) { mk = k > mk ? k : mk; });
+    mk = waveMax32(mk);
+    if (lane == 0) {
+      S.wmax[wave] = mk;
+    }
+    __syncthreads();
+    for (int w = 0; w < kS2sTypedThreads / 64; ++w) {
+      mk = S.wmax[w] > mk ? S.wmax[w] : mk;
+    }
+    const float mx = mk != 0u ? f32FromKey(mk) : -__builtin_huge_valf();
+    lse = (double)mx;
+    if (mx - mx == 0.0f) { /* finite */
+      double s = 0.0;
+      s2sTypedEach<DT, LOGITS, CACHED, true>(row, V, 0.0, kr, [&](int, uint32_t k) {
+        if (k != 0u) {
+          s += (double)expf(f32FromKey(k) - mx);
+        }
+      });
+      for (int d = 32; d >= 1; d >>= 1) { /* (a fixed butterfly: the same sum in every lane, run to run) */
+        s += __longlong_as_double((long long)waveShflXor64((unsigned long long)__double_as_longlong(s), d));
+      }
+      if (lane == 0) {
+        S.wsum[wave] = s;
+      }
+      __syncthreads();
+      s = 0.0;
+      for (int w = 0; w < kS2sTypedThreads / 64; ++w) {
+        s += S.wsum[w];
+      }
+      lse = (double)mx + log(s);
+    }
+    if (Q.rowLse && tid == 0) {
+      Q.rowLse[r] = lse;
+    }
+    if constexpr (CACHED) {
+#pragma unroll
+      for (int j = 0; j < kS2sTypedRegs; ++j) { /* (slots beyond V hold 0 and stay 0) */
+        kr[j] = kr[j] != 0u ? s2sKey32((float)((double)f32FromKey(kr[j]) - lse)) : 0u;
+      }
+    }
+  }
+  /* the radix select over the 48-bit composite key << 16 | (0xFFFF - token), most significant digit first: four
+   * digits of the key, then (equal keys at the cut) two of the inverted token */
+  uint32_t preK = 0u, mskK = 0u, preI = 0u, mskI = 0u;
+  int need = m;
+  bool all = m >= V, allEq = false;
+  for (int shift = 40; shift >= 0 && !all && !allEq; shift -= 8) {
+    __syncthreads();
+    S.hist[tid] = 0u; /* (kS2sTypedThreads == kSlNB) */
+    __syncthreads();
+    s2sTypedEach<DT, LOGITS, CACHED, false>(row, V, lse, kr, [&](int i, uint32_t k) {
+      const uint32_t ix = 0xFFFFu - (uint32_t)i;
+      if (k != 0u && (k & mskK) == preK && (ix & mskI) == preI) {
+        const uint32_t dg = shift >= 16 ? (k >> (shift - 16)) & 255u : (ix >> shift) & 255u;
+        atomAdd32(&S.hist[255u - dg], 1u);
+      }
+    });
+    __syncthreads();
+    const SlScan sc = slScan(S.hist, need, false); /* (every wave scans the same counts) */
+    if (sc.total <= need) {
+      all = true;
+      break;
+    }
+    need -= sc.cum;
+    const uint32_t dg = (uint32_t)(255 - sc.bstar);
+    if (shift >= 16) {
+      preK |= dg << (shift - 16);
+      mskK |= 255u << (shift - 16);
+    } else {
+      preI |= dg << shift;
+      mskI |= 255u << shift;
+    }
+    allEq = sc.cnt == need;
+  }
+  /* the list: every candidate at or above the cut (the composite keys are distinct: min(mSel, candidates) of them) */
+  if (tid == 0) {
+    S.nList = 0u;
+    S.eosIn = 0;
+    S.eosA = __uint_as_float(0x7FC00000u);
+  }
+  __syncthreads();
+  s2sTypedEach<DT, LOGITS, CACHED, false>(row, V, lse, kr, [&](int i, uint32_t k) {
+    const uint32_t ix = 0xFFFFu - (uint32_t)i;
+    const bool sel = k != 0u && (all || (k & mskK) > preK || ((k & mskK) == preK && (ix & mskI) >= preI));
+    if (sel || (i == P.eos && k != 0u)) {
+      const float a = f32FromKey(k); /* (a zero comes back as +0: no score the step forms can tell the sign) */
+      if (sel) {
+        const uint32_t p = atomAdd32(&S.nList, 1u);
+        if (p < (uint32_t)kS2sTypedMaxList) {
+          S.listTok[p] = i;
+          S.listAm[p] = a;
+        }
+      }
+      if (i == P.eos) {
+        S.eosIn = sel ? 1 : 0;
+        S.eosA = a;
+      }
+    }
+  });
+  __syncthreads();
+  const int n = (int)(S.nList < (uint32_t)kS2sTypedMaxList ? S.nList : (uint32_t)kS2sTypedMaxList);
+  /* the shortcut kept fewer than the token beam: eos still is a candidate when it is among the row's Kt best */
+  bool eosAdd = false;
+  const float ae = S.eosA;
+  if (P.eosExtra && !S.eosIn && P.eos >= 0 && P.eos < V) {
+    const uint32_t ke = s2sKey32(ae);
+    if (ke != 0u) {
+      int above = 0;
+      s2sTypedEach<DT, LOGITS, CACHED, false>(row, V, lse, kr, [&](int i, uint32_t k) {
+        above += (k > ke || (k == ke && i < P.eos)) ? 1 : 0;
+      });
+      eosAdd = s2sTypedBlockSum(S, above) < P.Kt;
+    }
+  }
+  /* written in token order (the rank of each token among the listed), eos after them */
+  int32_t* tok = P.recTok + r * P.cap;
+  float* am = P.recAm + r * P.cap;
+  for (int e = tid; e < n; e += kS2sTypedThreads) {
+    const int32_t te = S.listTok[e];
+    int rank = 0;
+    for (int q = 0; q < n; ++q) {
+      rank += S.listTok[q] < te ? 1 : 0;
+    }
+    tok[rank] = te;
+    am[rank] = S.listAm[e];
+  }
+  if (tid == 0) {
+    if (eosAdd) {
+      tok[n] = P.eos;
+      am[n] = ae;
+    }
+    P.recN[r] = n + (eosAdd ? 1 : 0);
+  }
+}
+
+/* workgroup = row b*K + k of the step */
+template <int DT, bool LOGITS>
+FLTX_DEV void s2sTypedRows(const S2sTypedParams& Q, char* smem) {
+  const S2sParams& P = Q.s;
+  const int64_t r = (int64_t)blockIdx.x;
+  const int b = (int)(r / P.K), k = (int)(r % P.K);
+  const bool live = !P.done[b] && P.t < P.maxOut && k < P.nRowsInt[b] && (P.rowValid == nullptr || P.rowValid[r] != 0);
+  if (!live) {
+    if (threadIdx.x == 0) {
+      P.recN[r] = 0;
+      if (LOGITS && Q.rowLse) {
+        Q.rowLse[r] = __longlong_as_double(0x7FF8000000000000ll);
+      }
+    }
+    return;
+  }
+  S2sTypedLds& S = *(S2sTypedLds*)smem;
+  if (P.V <= kS2sTypedReadOnceV) {
+    s2sTypedRow<DT, LOGITS, true>(Q, S, r);
+  } else {
+    s2sTypedRow<DT, LOGITS, false>(Q, S, r);
+  }
+}
+
 /* ---- the step: one workgroup of kS2sStepThreads per utterance ---------------------------------------------------- */
 struct S2sStepLds {
   uint32_t hist[kSlNB];
