@@ -24,7 +24,11 @@ barrier and the max-over-ranks of the timed region.  `--gpus N` WITHOUT the
 launcher (WORLD_SIZE unset) starts the N ranks itself, so the line always
 reports the N it was asked for.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line: the contract fields and `config` (engine, geometry, fallbacks).  A plain run does
+only what that line needs: set-up, --warmup steps, the --steps timed steps, --dump-outputs, the line.  With --full
+(off by default) the run goes on, after the timed steps, to everything else the benchmark measures or checks, and
+the line also carries
+  value_kernels_only : the timed loop again with the looks at the batches' statuses dropped
   roofline     : dominant kernel (the decode kernel) vs the HBM roofline: its own
                  algorithmic bytes (n-gram queries and
                  returned hypotheses as the kernels counted them) / its HIP-event
@@ -39,6 +43,10 @@ Rank 0 prints ONE JSON line.  Besides the contract fields it carries
                  memory, DecodeResult-like views materialised
   streaming    : the same batch as B parallel streams fed in chunks of 50 frames
                  with prune() after every chunk
+  strong_scaling, sustained, drop_in, secondary : C5's 8192 utterances over the run's GPUs; >= 10 s of back-to-back
+                 steps; the reference's Python names; the C3 / C4 / C5-share / WP / token-LM lines
+and a sampled n-best that differs from the reference CPU's fails the run.  --mode group compares with the reference
+only under --full as well.
 """
 import argparse
 import json
@@ -69,6 +77,11 @@ WORKLOADS = {
     "C2T": dict(lex=False, batch=256, T=1000, K=50, Kt=29, lm=False, toklm=(3, 11, 0.8)),
 }
 
+# options that select among the legs of a --full run (--profile: the per-phase clock split, decoded once more per
+# sampled wave, with the decoder objects set up for it)
+FULL_ONLY = ("cpu_sample", "no_cpu", "no_extras", "no_secondary", "sustained_seconds", "profile", "profile_out",
+             "profile_waves")
+
 
 def parse():
     ap = argparse.ArgumentParser()
@@ -85,6 +98,10 @@ def parse():
     ap.add_argument("--pipeline", type=int, default=2, choices=[1, 2],
                     help="decoder objects (each on its own HIP stream) the steps alternate between: with 2 the "
                          "back-trace of one batch runs under the decode kernel of the next")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, every other leg: roofline, kernels-only "
+                    "loop, strong scaling, sustained, CPU baselines and n-best comparisons, end to end, streaming, "
+                    "drop-in, secondary workloads (--cpu-sample, --no-cpu, --no-extras, --no-secondary, "
+                    "--sustained-seconds and --profile* select among them, and need it)")
     ap.add_argument("--cpu-sample", type=int, default=160, help="utterances timed on the one-thread CPU baseline")
     ap.add_argument("--no-cpu", action="store_true", help="skip every CPU / host-side leg (profiling runs)")
     ap.add_argument("--no-extras", action="store_true", help="skip all-cores / steady / end-to-end / streaming / sustained / secondary")
@@ -109,7 +126,12 @@ def parse():
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="after the timed steps, write the n-best of the last timed step as DIR/<name>.npy (a fixed "
                          "sample of utterances, at most 64 MB; rank 0's shard): two builds compared output for output")
-    return ap.parse_args()
+    a = ap.parse_args()
+    given = [k for k in FULL_ONLY if getattr(a, k) != ap.get_default(k)]
+    if given and not a.full:
+        ap.error("%s: only with --full (selects among the legs a --full run adds)" %
+                 ", ".join("--" + k.replace("_", "-") for k in given))
+    return a
 
 
 def self_launch(a):
@@ -322,17 +344,53 @@ def main():
         raise SystemExit(fail)
 
 
+def headline(a, job, dec, decs, B, world, dt, redone, unread_redone):
+    """The line's contract fields and `config`, from the timed region (dt seconds over a.steps steps)."""
+    T, N, K, Kt = job.T, job.N, job.K, job.Kt
+    st = dec.stats()
+    return {
+        "metric": "decoded frames/sec (whole node), T=%d N=%d beam=%d; hyp bit-exact vs CPU" % (T, N, K),
+        "value": B * T * a.steps * world / dt, "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "%s: %s + %s CTC, batch=%d utterances/GPU, T=%d, N=%d, beam=%d, "
+                               "beamToken=%d, beamThreshold=25, logAdd=false, `%s` emissions" %
+                               (a.workload, "LexiconDecoder + 90k-word trie" if job.lex else "LexiconFreeDecoder",
+                                "synthetic 4-gram word LM (lmWeight 2, wordScore 2, silScore -1)" if job.haslm
+                                else ("synthetic token-level %d-gram LM (lmWeight %g)" % (job.toklm[0], job.toklm[2])
+                                      if job.toklm else "ZeroLM"), B, T, N, K, Kt, job.dist),
+                   "parallelism": "utterance-sharded x%d, no collective" % world,
+                   "threads_per_utterance": st["threads_per_utt"], "lds_bytes_per_workgroup": st["lds_bytes"],
+                   "engine": dec.get("engine"), "redone": redone, "unread_redone": unread_redone,
+                   "status_look": "inside the timed region: every decode_batch settles the batch its decoder object had in "
+                                  "flight (statuses read, flagged utterances decoded again) before it launches",
+                   "lane_groups": dec.get("lane_groups"),
+                   "why_not_lane": dec.get("why_not_lane"), "fallback_reasons": dec.get("fallback_reasons"),
+                   "pipeline": "%d decoder object(s), one HIP stream each, taking turns batch by batch%s" % (
+                       len(decs), " (the back-trace of a batch runs under the decode kernel of the next)"
+                       if len(decs) > 1 else "")},
+    }
+
+
+def fallback_fail(a, B, redone, unread_redone):
+    """None, or why a line that spent its time in fallbacks must not look green."""
+    if redone * 4 > B or unread_redone * 4 > B * (a.steps + a.warmup):
+        return "bench.py: %s: %d of %d utterances fell back to a general engine (%d over the timed batches)" % (
+            a.workload, redone, B, unread_redone)
+    return None
+
+
 def measure(a, torch, dist, rank, local, world, primary):
     """One workload through the timed loop -> (the JSON line's dict, None or why the line must not look green).
-    primary: the judged line with every leg; otherwise a `secondary` entry (kernel timing, roofline, a small CPU
-    sample for the n-best comparison)."""
+    primary: the judged line (with --full, every leg); otherwise a `secondary` entry of a --full run (kernel timing,
+    roofline, a small CPU sample for the n-best comparison)."""
     cfg = dict(WORKLOADS[a.workload])
     for key, val in (("T", a.frames), ("K", a.beam), ("Kt", a.beam_token)):
         if val:
             cfg[key] = val
     B = a.batch or cfg["batch"]
     job = Job(a, rank, local, B, cfg)
-    T, N, K, Kt = job.T, job.N, job.K, job.Kt
+    T, N, K = job.T, job.N, job.K
     if a.streaming_only:
         return {"workload": a.workload, "streaming": streaming(job, B, T, N)}, None  # (no metric / value: not a bench line)
     e_dev = torch.from_numpy(job.e_host).cuda()  # resident in HBM before timing
@@ -401,6 +459,14 @@ def measure(a, torch, dist, rank, local, world, primary):
     # look at the utterances' statuses -- and the second pass of whatever a fast path flagged -- is inside the clock
     # for every timed batch; `unread_redone` counts what those looks decoded again)
     unread_redone = sum(d.get("unread_redone") for d in decs)
+    if not a.full:  # a plain run: the line of the timed steps, nothing that takes a run of its own
+        redone = max(d.get("redone") for d in decs)
+        out = headline(a, job, dec, decs, B, world, dt, redone, unread_redone)
+        for d in decs:
+            d.close()
+        job.close()
+        del e_dev
+        return out, fallback_fail(a, B, redone, unread_redone)
     in_region_k, in_region_b = list(kern_ms), list(bt_ms)
     kernels_only = None
     if primary and len(decs) > 1 and not a.no_corun and not a.profile and not a.no_extras:
@@ -436,30 +502,8 @@ def measure(a, torch, dist, rank, local, world, primary):
     by = dec.bytes()
     engine = dec.get("engine")
     redone = max(d.get("redone") for d in decs)  # utterances of the last timed batches the engine handed to a more general one
-    value = B * T * a.steps * world / dt
-
-    out = {
-        "metric": "decoded frames/sec (whole node), T=%d N=%d beam=%d; hyp bit-exact vs CPU" % (T, N, K),
-        "value": value, "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "%s: %s + %s CTC, batch=%d utterances/GPU, T=%d, N=%d, beam=%d, "
-                               "beamToken=%d, beamThreshold=25, logAdd=false, `%s` emissions" %
-                               (a.workload, "LexiconDecoder + 90k-word trie" if job.lex else "LexiconFreeDecoder",
-                                "synthetic 4-gram word LM (lmWeight 2, wordScore 2, silScore -1)" if job.haslm
-                                else ("synthetic token-level %d-gram LM (lmWeight %g)" % (job.toklm[0], job.toklm[2])
-                                      if job.toklm else "ZeroLM"), B, T, N, K, Kt, job.dist),
-                   "parallelism": "utterance-sharded x%d, no collective" % world,
-                   "threads_per_utterance": st["threads_per_utt"], "lds_bytes_per_workgroup": st["lds_bytes"],
-                   "engine": engine, "redone": redone, "unread_redone": unread_redone,
-                   "status_look": "inside the timed region: every decode_batch settles the batch its decoder object had in "
-                                  "flight (statuses read, flagged utterances decoded again) before it launches",
-                   "lane_groups": dec.get("lane_groups"),
-                   "why_not_lane": dec.get("why_not_lane"), "fallback_reasons": dec.get("fallback_reasons"),
-                   "pipeline": "%d decoder object(s), one HIP stream each, taking turns batch by batch%s" % (
-                       len(decs), " (the back-trace of a batch runs under the decode kernel of the next)"
-                       if len(decs) > 1 else "")},
-    }
+    out = headline(a, job, dec, decs, B, world, dt, redone, unread_redone)
+    value = out["value"]
     if kernels_only is not None:
         out["value_kernels_only"] = kernels_only
     # ---- roofline (rank-local): each kernel's own algorithmic bytes over its own duration ----
@@ -576,9 +620,7 @@ def measure(a, torch, dist, rank, local, world, primary):
         out.get("streaming", {}).get("final_nbest_mismatches_vs_cpu_on_sample", 0)
     if mism:
         fail = "bench.py: %s: %d of the sampled utterances differ from the CPU reference" % (a.workload, mism)
-    if redone * 4 > B or unread_redone * 4 > B * (a.steps + a.warmup):
-        fail = "bench.py: %s: %d of %d utterances fell back to a general engine (%d over the timed batches)" % (
-            a.workload, redone, B, unread_redone)
+    fail = fallback_fail(a, B, redone, unread_redone) or fail
 
     # ---- secondary: the other BASELINE configurations under the same clock (default invocation, N = 1) ----
     if primary and rank == 0 and world == 1 and a.workload == "C2" and not a.no_secondary and not a.no_extras and not a.no_cpu and \
@@ -675,8 +717,8 @@ def group_mode(a):
                               "thread per device, contiguous shards, no collective)" % devices,
                       "shards": [[f, c] for _, f, c in parts],
                       "same_device_plumbing_check": len(set(devices)) < n}}
-    # parity spot check: first and last utterance of every shard against the reference CPU
-    if not a.no_cpu:
+    # parity spot check (--full): first and last utterance of every shard against the reference CPU
+    if a.full and not a.no_cpu:
         cpu = CpuSide(j0)
         mism = chk = 0
         for i, (_, first, count) in enumerate(parts):

@@ -6,7 +6,7 @@ OUT="$1"; shift
 BEAMS="${@:-64 65 100 128 160 200 256 300 400 500}"
 : > "$OUT"
 for K in $BEAMS; do
-  python "$R/bench.py" --workload C2 --beam $K --steps 3 --warmup 2 --no-extras --cpu-sample 4 >> "$OUT" 2>> "$OUT.err" || echo "{\"beam\": $K, \"failed\": true}" >> "$OUT"
+  python "$R/bench.py" --full --workload C2 --beam $K --steps 3 --warmup 2 --no-extras --cpu-sample 4 >> "$OUT" 2>> "$OUT.err" || echo "{\"beam\": $K, \"failed\": true}" >> "$OUT"
 done
 python - "$OUT" <<'PY'
 import json, sys

@@ -7,7 +7,7 @@ R="${GRAFT_REPO_ROOT:-$(pwd)}"; O="$R/gpurun_out/r06t"; rm -rf "$O"; mkdir -p "$
 run() { # name, bench flags
   n=$1; shift
   for c in FETCH_SIZE WRITE_SIZE; do
-    rocprofv3 --pmc $c --output-format csv -d "$O/${n}_$c" -- python "$R/bench.py" "$@" --steps 3 --warmup 1 --no-cpu --no-secondary --sustained-seconds 0 > "$O/${n}_$c.log" 2>&1
+    rocprofv3 --pmc $c --output-format csv -d "$O/${n}_$c" -- python "$R/bench.py" --full "$@" --steps 3 --warmup 1 --no-cpu --no-secondary --sustained-seconds 0 > "$O/${n}_$c.log" 2>&1
   done
   f=$(ls -t $O/${n}_FETCH_SIZE/*/*_counter_collection.csv | head -1); w=$(ls -t $O/${n}_WRITE_SIZE/*/*_counter_collection.csv | head -1)
   python "$R/tools/pmc_traffic.py" "$f" "$w" "$n" "$O/traffic_$n.json" > /dev/null
