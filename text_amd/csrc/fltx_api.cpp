@@ -146,14 +146,11 @@ __global__ void __launch_bounds__(kS2sStepThreads) fltx_s2s_step_kernel(S2sParam
   __shared__ __attribute__((aligned(16))) S2sStepLds fltx_s2s_lds;
   s2sStepUtterance(P, (char*)&fltx_s2s_lds);
 }
-__global__ void __launch_bounds__(64) fltx_s2s_begin_kernel(S2sParams P) {
-  const int b = (int)(blockIdx.x * 64 + threadIdx.x);
-  if (b < P.B) {
-    s2sBeginUtterance(P, b);
-  }
+__global__ void __launch_bounds__(kS2sBeginThreads) fltx_s2s_begin_kernel(S2sParams P) {
+  s2sBeginUtterance(P, nullptr);
 }
-__global__ void __launch_bounds__(256) fltx_s2s_end_kernel(S2sParams P) {
-  s2sEndUtterance(P, (int)blockIdx.x, (int)threadIdx.x, (int)blockDim.x);
+__global__ void __launch_bounds__(kS2sEndThreads) fltx_s2s_end_kernel(S2sParams P) {
+  s2sEndUtterance(P, nullptr);
 }
 /* the typed front end (fltx_s2s_step_typed): fp16 / bf16 rows, and logits of any of the three types */
 template <int DT, bool LOGITS>
@@ -161,23 +158,16 @@ __global__ void __launch_bounds__(kS2sTypedThreads) fltx_s2s_typed_kernel(S2sTyp
   __shared__ __attribute__((aligned(16))) S2sTypedLds fltx_s2s_typed_lds;
   s2sTypedRows<DT, LOGITS>(Q, (char*)&fltx_s2s_typed_lds);
 }
-template <int DT, bool LOGITS>
-static void s2sTypedLaunch(int nRows, hipStream_t st, const S2sTypedParams& T) {
-  hipLaunchKernelGGL((fltx_s2s_typed_kernel<DT, LOGITS>), dim3(nRows), dim3(kS2sTypedThreads), 0, st, T);
-}
 /* fltx_s2s_lex.h: the lexicon seq2seq step (its front end is fltx_s2s_tokbeam_kernel), start and back-trace */
 __global__ void __launch_bounds__(kS2sStepThreads) fltx_s2s_lex_step_kernel(S2lParams Q) {
   __shared__ __attribute__((aligned(16))) S2lStepLds fltx_s2l_lds;
   s2lStepUtterance(Q, (char*)&fltx_s2l_lds);
 }
-__global__ void __launch_bounds__(64) fltx_s2s_lex_begin_kernel(S2lParams Q) {
-  const int b = (int)(blockIdx.x * 64 + threadIdx.x);
-  if (b < Q.s.B) {
-    s2lBeginUtterance(Q, b);
-  }
+__global__ void __launch_bounds__(kS2sBeginThreads) fltx_s2s_lex_begin_kernel(S2lParams Q) {
+  s2lBeginUtterance(Q, nullptr);
 }
-__global__ void __launch_bounds__(256) fltx_s2s_lex_end_kernel(S2lParams Q) {
-  s2lEndUtterance(Q, (int)blockIdx.x, (int)threadIdx.x, (int)blockDim.x);
+__global__ void __launch_bounds__(kS2sEndThreads) fltx_s2s_lex_end_kernel(S2lParams Q) {
+  s2lEndUtterance(Q, nullptr);
 }
 __global__ void __launch_bounds__(1024) fltx_streamop_kernel(StreamOpParams Q) {
   __shared__ int32_t sh[kStreamOpLds / 4];
@@ -609,21 +599,22 @@ struct fltx_decoder {
   bool slotUsed[2] = {false, false};
 #endif
   bool timed = false;
-  /* seq2seq (kind FLTX_DECODER_S2S_LEXFREE, fltx_s2s_*: fltx_s2s.h) */
-  fltx_s2s_options s2sOpt{};
-  int s2sEos = 0, s2sMaxOut = 0, s2sT = 0, s2sCap = 0, s2sMSel = 0, s2sEosExtra = 0;
-  bool s2sBegun = false;
-  int32_t s2sCtx0[kS2sCtx] = {0};
-  DBuf s2sBeam, s2sBeamN, s2sHist, s2sRowsInt, s2sDone, s2sFinal, s2sRecTok, s2sRecAm, s2sRecN, s2sKey;
-  DBuf s2sScores, s2sValid; /* device copies of host inputs */
-  /* lexicon seq2seq (kind FLTX_DECODER_S2S_LEXICON, fltx_s2s_lex_decoder_create: fltx_s2s_lex.h) */
-  double s2lWordScore = 0.0;
-  bool s2lIsLmToken = false;
-  int s2lMaxLabels = 0, s2lS = 1, s2lMSize = 0, s2lSSize = 0, s2lSMax = 0, s2lMaxStates = 0;
-  int64_t s2lNodes = 0, s2lEdges = 0, s2lLabels = 0, s2lTrieBytes = 0;
-  DBuf s2lMax, s2lKidOff, s2lKidTok, s2lKidNode, s2lLabOff, s2lLab; /* the compact trie */
-  DBuf s2lBeam, s2lHist, s2lScore, s2lMk, s2lGrp, s2lList, s2lNext, s2lMTab, s2lSKey, s2lSVal, s2lSCount, s2lStatus,
-      s2lMerges;
+  /* seq2seq (kinds FLTX_DECODER_S2S_LEXFREE / _LEXICON, fltx_s2s_*: fltx_s2s.h, fltx_s2s_lex.h) */
+  struct {
+    fltx_s2s_options opt{};
+    int eos = 0, maxOut = 0, t = 0, cap = 0, mSel = 0, eosExtra = 0;
+    bool begun = false;
+    int32_t ctx0[kS2sCtx] = {0};
+    DBuf beam, beamN, hist, rowsInt, done, finalStep, recTok, recAm, recN, cKey; /* (beam, hist: of the kind's types) */
+    DBuf scores, valid; /* device copies of host inputs */
+    /* with a lexicon (fltx_s2s_lex_decoder_create) */
+    double wordScore = 0.0;
+    bool isLmToken = false;
+    int maxLabels = 0, slots = 1, mSize = 0, sSize = 0, sMax = 0, maxStates = 0;
+    int64_t nodes = 0, edges = 0, labels = 0, trieBytes = 0;
+    DBuf trieMax, kidOff, kidTok, kidNode, labOff, lab; /* the compact trie */
+    DBuf cScore, cMk, cGrp, cList, cNext, mTab, sKey, sVal, sCount, status, merges;
+  } s2s;
 };
 
 static bool isS2sKind(int kind) { return kind == FLTX_DECODER_S2S_LEXFREE || kind == FLTX_DECODER_S2S_LEXICON; }
@@ -4666,6 +4657,19 @@ static int s2sCheck(fltx_decoder* d, const char* what) {
   return FLTX_OK;
 }
 
+/* a seq2seq launch, written once for both builds: `kernel` over grid x block workgroups on the stream; the emulator runs
+ * `body`, the device function that kernel wraps, on host threads with `lds` bytes per workgroup */
+#ifdef FLTX_EMU
+#define S2S_LAUNCH(kernel, body, grid, block, lds, st, params) \
+  emuLaunch((grid), (block), (lds), [&](char* smem) { body((params), smem); })
+#else
+#define S2S_LAUNCH(kernel, body, grid, block, lds, st, params)              \
+  do {                                                                       \
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, (st), (params)); \
+    HIPCHK(hipGetLastError());                                               \
+  } while (0)
+#endif
+
 static S2sParams s2sParams(fltx_decoder* d) {
   S2sParams P;
   memset(&P, 0, sizeof(P));
@@ -4684,33 +4688,33 @@ static S2sParams s2sParams(fltx_decoder* d) {
     P.lmp.lmUnk = lm->unk;
   }
   P.B = d->B;
-  P.K = d->s2sOpt.beam_size;
-  P.Kt = d->s2sOpt.beam_size_token;
+  P.K = d->s2s.opt.beam_size;
+  P.Kt = d->s2s.opt.beam_size_token;
   P.V = d->N;
-  P.eos = d->s2sEos;
-  P.maxOut = d->s2sMaxOut;
-  P.t = std::min(d->s2sT, d->s2sMaxOut);
-  P.cap = d->s2sCap;
-  P.mSel = d->s2sMSel;
-  P.eosExtra = d->s2sEosExtra;
-  P.beamThreshold = d->s2sOpt.beam_threshold;
-  P.lmWeight = d->s2sOpt.lm_weight;
-  P.eosScore = d->s2sOpt.eos_score;
-  P.beam = d->s2sBeam.as<S2sHyp>();
-  P.beamN = d->s2sBeamN.as<int32_t>();
-  P.hist = d->s2sHist.as<int2>();
-  P.nRowsInt = d->s2sRowsInt.as<int32_t>();
-  P.done = d->s2sDone.as<int32_t>();
-  P.finalStep = d->s2sFinal.as<int32_t>();
-  P.recTok = d->s2sRecTok.as<int32_t>();
-  P.recAm = d->s2sRecAm.as<float>();
-  P.recN = d->s2sRecN.as<int32_t>();
-  P.cKey = d->s2sKey.as<unsigned long long>();
+  P.eos = d->s2s.eos;
+  P.maxOut = d->s2s.maxOut;
+  P.t = std::min(d->s2s.t, d->s2s.maxOut);
+  P.cap = d->s2s.cap;
+  P.mSel = d->s2s.mSel;
+  P.eosExtra = d->s2s.eosExtra;
+  P.beamThreshold = d->s2s.opt.beam_threshold;
+  P.lmWeight = d->s2s.opt.lm_weight;
+  P.eosScore = d->s2s.opt.eos_score;
+  P.beam = d->s2s.beam.as<S2sHyp>();
+  P.beamN = d->s2s.beamN.as<int32_t>();
+  P.hist = d->s2s.hist.as<int2>();
+  P.nRowsInt = d->s2s.rowsInt.as<int32_t>();
+  P.done = d->s2s.done.as<int32_t>();
+  P.finalStep = d->s2s.finalStep.as<int32_t>();
+  P.recTok = d->s2s.recTok.as<int32_t>();
+  P.recAm = d->s2s.recAm.as<float>();
+  P.recN = d->s2s.recN.as<int32_t>();
+  P.cKey = d->s2s.cKey.as<unsigned long long>();
   P.nC = (int64_t)P.K * P.cap + P.K;
   for (int j = 0; j < kS2sCtx; ++j) {
-    P.ctx0[j] = d->s2sCtx0[j];
+    P.ctx0[j] = d->s2s.ctx0[j];
   }
-  P.len = d->s2sMaxOut + 3;
+  P.len = d->s2s.maxOut + 3;
   return P;
 }
 
@@ -4754,15 +4758,15 @@ int fltx_s2s_decoder_create(fltx_ctx* ctx, const fltx_s2s_options* opt, const fl
   d->lm = lm;
   d->lmDev = lmDev;
   d->kind = FLTX_DECODER_S2S_LEXFREE;
-  d->s2sOpt = *opt;
+  d->s2s.opt = *opt;
   d->opt.beam_size = opt->beam_size;
   d->opt.beam_size_token = opt->beam_size_token;
   d->opt.beam_threshold = opt->beam_threshold;
   d->opt.lm_weight = opt->lm_weight;
   d->opt.log_add = opt->log_add;
   d->opt.criterion = FLTX_CRITERION_S2S;
-  d->s2sEos = eos;
-  d->s2sMaxOut = maxOut;
+  d->s2s.eos = eos;
+  d->s2s.maxOut = maxOut;
   if (lm->kind == 1) {
     int32_t c[kMaxNgramOrder] = {0};
     if ((rc = fltx_lm_start(const_cast<fltx_lm*>(lm), 0, c))) {
@@ -4770,7 +4774,7 @@ int fltx_s2s_decoder_create(fltx_ctx* ctx, const fltx_s2s_options* opt, const fl
       return rc;
     }
     for (int j = 0; j < kS2sCtx; ++j) {
-      d->s2sCtx0[j] = j < lm->order - 1 ? c[j] : 0;
+      d->s2s.ctx0[j] = j < lm->order - 1 ? c[j] : 0;
     }
   }
   *out = d;
@@ -4778,37 +4782,41 @@ int fltx_s2s_decoder_create(fltx_ctx* ctx, const fltx_s2s_options* opt, const fl
 }
 
 /* ---- lexicon seq2seq (fltx_s2s_lex.h) ---------------------------------------------------------------------------- */
-static S2lParams s2lParams(fltx_decoder* d) {
+/* the parameters of either kind: .s is the lexicon-free view, the rest stays 0 without a lexicon */
+static S2lParams s2sStepParams(fltx_decoder* d) {
   S2lParams Q;
   memset(&Q, 0, sizeof(Q));
   Q.s = s2sParams(d);
-  Q.s.nC = (int64_t)Q.s.K * Q.s.cap * d->s2lS + Q.s.K;
-  Q.trie.maxScore = d->s2lMax.as<float>();
-  Q.trie.kidOff = d->s2lKidOff.as<int32_t>();
-  Q.trie.kidTok = d->s2lKidTok.as<int32_t>();
-  Q.trie.kidNode = d->s2lKidNode.as<int32_t>();
-  Q.trie.labOff = d->s2lLabOff.as<int32_t>();
-  Q.trie.labels = d->s2lLab.as<int32_t>();
-  Q.isLmToken = d->s2lIsLmToken ? 1 : 0;
-  Q.S = d->s2lS;
-  Q.wordScore = d->s2lWordScore;
-  Q.logAdd = d->s2sOpt.log_add ? 1 : 0;
-  Q.beam = d->s2lBeam.as<S2lHyp>();
-  Q.hist = d->s2lHist.as<S2lRec>();
-  Q.cScore = d->s2lScore.as<double>();
-  Q.cMk = d->s2lMk.as<uint4>();
-  Q.cGrp = d->s2lGrp.as<int32_t>();
-  Q.cList = d->s2lList.as<int32_t>();
-  Q.cNext = d->s2lNext.as<int32_t>();
-  Q.mTab = d->s2lMTab.as<int32_t>();
-  Q.mSize = d->s2lMSize;
-  Q.sKey = d->s2lSKey.as<unsigned long long>();
-  Q.sVal = d->s2lSVal.as<int32_t>();
-  Q.sCount = d->s2lSCount.as<int32_t>();
-  Q.sSize = d->s2lSSize;
-  Q.sMax = d->s2lSMax;
-  Q.status = d->s2lStatus.as<int32_t>();
-  Q.merges = d->s2lMerges.as<int32_t>();
+  if (d->kind != FLTX_DECODER_S2S_LEXICON) {
+    return Q;
+  }
+  Q.s.nC = (int64_t)Q.s.K * Q.s.cap * d->s2s.slots + Q.s.K;
+  Q.trie.maxScore = d->s2s.trieMax.as<float>();
+  Q.trie.kidOff = d->s2s.kidOff.as<int32_t>();
+  Q.trie.kidTok = d->s2s.kidTok.as<int32_t>();
+  Q.trie.kidNode = d->s2s.kidNode.as<int32_t>();
+  Q.trie.labOff = d->s2s.labOff.as<int32_t>();
+  Q.trie.labels = d->s2s.lab.as<int32_t>();
+  Q.isLmToken = d->s2s.isLmToken ? 1 : 0;
+  Q.S = d->s2s.slots;
+  Q.wordScore = d->s2s.wordScore;
+  Q.logAdd = d->s2s.opt.log_add ? 1 : 0;
+  Q.beam = d->s2s.beam.as<S2lHyp>();
+  Q.hist = d->s2s.hist.as<S2lRec>();
+  Q.cScore = d->s2s.cScore.as<double>();
+  Q.cMk = d->s2s.cMk.as<uint4>();
+  Q.cGrp = d->s2s.cGrp.as<int32_t>();
+  Q.cList = d->s2s.cList.as<int32_t>();
+  Q.cNext = d->s2s.cNext.as<int32_t>();
+  Q.mTab = d->s2s.mTab.as<int32_t>();
+  Q.mSize = d->s2s.mSize;
+  Q.sKey = d->s2s.sKey.as<unsigned long long>();
+  Q.sVal = d->s2s.sVal.as<int32_t>();
+  Q.sCount = d->s2s.sCount.as<int32_t>();
+  Q.sSize = d->s2s.sSize;
+  Q.sMax = d->s2s.sMax;
+  Q.status = d->s2s.status.as<int32_t>();
+  Q.merges = d->s2s.merges.as<int32_t>();
   return Q;
 }
 
@@ -4866,25 +4874,25 @@ static int s2lUploadTrie(fltx_decoder* d, fltx_htrie* t) {
   }
   Stream st = d->ctx->stream;
   const size_t nE = kidTok.size(), nL = lab.size();
-  if (d->s2lMax.ensure(4 * (size_t)nn, st, false) || d->s2lKidOff.ensure(4 * ((size_t)nn + 1), st, false) ||
-      d->s2lKidTok.ensure(4 * std::max<size_t>(nE, 1), st, false) ||
-      d->s2lKidNode.ensure(4 * std::max<size_t>(nE, 1), st, false) ||
-      d->s2lLabOff.ensure(4 * ((size_t)nn + 1), st, false) || d->s2lLab.ensure(4 * std::max<size_t>(nL, 1), st, false)) {
+  if (d->s2s.trieMax.ensure(4 * (size_t)nn, st, false) || d->s2s.kidOff.ensure(4 * ((size_t)nn + 1), st, false) ||
+      d->s2s.kidTok.ensure(4 * std::max<size_t>(nE, 1), st, false) ||
+      d->s2s.kidNode.ensure(4 * std::max<size_t>(nE, 1), st, false) ||
+      d->s2s.labOff.ensure(4 * ((size_t)nn + 1), st, false) || d->s2s.lab.ensure(4 * std::max<size_t>(nL, 1), st, false)) {
     return fail(FLTX_ERR_OOM, "seq2seq lexicon: trie allocation failed (%lld nodes)", (long long)nn);
   }
-  if (devCopyH2D(d->s2lMax.p, mx.data(), 4 * (size_t)nn, st) ||
-      devCopyH2D(d->s2lKidOff.p, kidOff.data(), 4 * ((size_t)nn + 1), st) ||
-      (nE && devCopyH2D(d->s2lKidTok.p, kidTok.data(), 4 * nE, st)) ||
-      (nE && devCopyH2D(d->s2lKidNode.p, kidNode.data(), 4 * nE, st)) ||
-      devCopyH2D(d->s2lLabOff.p, labOff.data(), 4 * ((size_t)nn + 1), st) ||
-      (nL && devCopyH2D(d->s2lLab.p, lab.data(), 4 * nL, st)) || devSync(st)) {
+  if (devCopyH2D(d->s2s.trieMax.p, mx.data(), 4 * (size_t)nn, st) ||
+      devCopyH2D(d->s2s.kidOff.p, kidOff.data(), 4 * ((size_t)nn + 1), st) ||
+      (nE && devCopyH2D(d->s2s.kidTok.p, kidTok.data(), 4 * nE, st)) ||
+      (nE && devCopyH2D(d->s2s.kidNode.p, kidNode.data(), 4 * nE, st)) ||
+      devCopyH2D(d->s2s.labOff.p, labOff.data(), 4 * ((size_t)nn + 1), st) ||
+      (nL && devCopyH2D(d->s2s.lab.p, lab.data(), 4 * nL, st)) || devSync(st)) {
     return fail(FLTX_ERR_HIP, "seq2seq lexicon: trie upload failed");
   }
-  d->s2lNodes = nn;
-  d->s2lEdges = (int64_t)nE;
-  d->s2lLabels = (int64_t)nL;
-  d->s2lMaxLabels = maxLabels;
-  d->s2lTrieBytes = 4 * nn + 4 * 2 * (nn + 1) + 8 * (int64_t)nE + 4 * (int64_t)nL;
+  d->s2s.nodes = nn;
+  d->s2s.edges = (int64_t)nE;
+  d->s2s.labels = (int64_t)nL;
+  d->s2s.maxLabels = maxLabels;
+  d->s2s.trieBytes = 4 * nn + 4 * 2 * (nn + 1) + 8 * (int64_t)nE + 4 * (int64_t)nL;
   return FLTX_OK;
 }
 
@@ -4912,14 +4920,14 @@ int fltx_s2s_lex_decoder_create(fltx_ctx* ctx, const fltx_s2s_lex_options* opt, 
   }
   d->kind = FLTX_DECODER_S2S_LEXICON;
   d->opt.word_score = opt->word_score;
-  d->s2lWordScore = opt->word_score;
-  d->s2lIsLmToken = isLmToken != 0;
-  d->s2lMaxStates = kS2lDefaultStates;
+  d->s2s.wordScore = opt->word_score;
+  d->s2s.isLmToken = isLmToken != 0;
+  d->s2s.maxStates = kS2lDefaultStates;
   if ((rc = s2lUploadTrie(d, const_cast<fltx_htrie*>(trie)))) {
     delete d;
     return rc;
   }
-  d->s2lS = 1 + (d->s2lIsLmToken ? std::min(d->s2lMaxLabels, 1) : d->s2lMaxLabels);
+  d->s2s.slots = 1 + (d->s2s.isLmToken ? std::min(d->s2s.maxLabels, 1) : d->s2s.maxLabels);
   *out = d;
   return FLTX_OK;
 }
@@ -4932,7 +4940,7 @@ int fltx_s2s_lex_set_max_states(fltx_decoder* d, int32_t maxStates) {
   if (d->kind != FLTX_DECODER_S2S_LEXICON || maxStates < 1) {
     return fail(FLTX_ERR_INVALID, "fltx_s2s_lex_set_max_states: a lexicon seq2seq decoder and a count >= 1");
   }
-  d->s2lMaxStates = maxStates;
+  d->s2s.maxStates = maxStates;
   return FLTX_OK;
 }
 
@@ -4949,89 +4957,79 @@ int fltx_s2s_lex_info(fltx_decoder* d, int64_t* trieBytes, int64_t* nNodes, int6
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
   if (trieBytes) {
-    *trieBytes = d->s2lTrieBytes;
+    *trieBytes = d->s2s.trieBytes;
   }
   if (nNodes) {
-    *nNodes = d->s2lNodes;
+    *nNodes = d->s2s.nodes;
   }
   if (nEdges) {
-    *nEdges = d->s2lEdges;
+    *nEdges = d->s2s.edges;
   }
-  if (merges && d->s2sBegun) {
-    if (devCopyD2H(merges, d->s2lMerges.p, 4 * (size_t)d->B, d->ctx->stream) || devSync(d->ctx->stream)) {
+  if (merges && d->s2s.begun) {
+    if (devCopyD2H(merges, d->s2s.merges.p, 4 * (size_t)d->B, d->ctx->stream) || devSync(d->ctx->stream)) {
       return fail(FLTX_ERR_HIP, "fltx_s2s_lex_info: copy failed: %s", devErr());
     }
   }
   return FLTX_OK;
 }
 
-static int s2lBegin(fltx_decoder* d, int32_t B, int32_t V, int32_t* nextTok, int32_t* nextBeam, int32_t* nextSrc,
-                    int32_t* nRows) {
-  const int K = d->s2sOpt.beam_size, Kt = d->s2sOpt.beam_size_token;
+/* fltx_s2s_begin's parts that depend on the kind: the token beam the front end keeps (mSel / eosExtra / cap) and the
+ * candidates per step (*nC); with a lexicon also the sizes of its tables, and then the buffers only it has */
+static int s2sPlanLexFree(fltx_decoder* d, int32_t V, int64_t* nC) {
+  const int K = d->s2s.opt.beam_size, Kt = d->s2s.opt.beam_size_token;
+  const int ktEff = std::min(Kt, V);
+  /* without LM terms in the score a row contributes at most K survivors besides eos: its top min(Kt, K + 1) (one more
+   * than K: eos may be among them) and eos when it is in the top Kt are every candidate that can survive */
+  const bool lmTerms = d->lm->kind == 1 && d->s2s.opt.lm_weight != 0.0;
+  if (lmTerms && ktEff > kS2sMaxKtLm) {
+    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq: a token beam of %d (beam_size_token, V = %d) > %d with LM terms", ktEff, V,
+                kS2sMaxKtLm);
+  }
+  d->s2s.mSel = lmTerms ? ktEff : std::min(ktEff, K + 1);
+  d->s2s.eosExtra = d->s2s.mSel < ktEff ? 1 : 0;
+  d->s2s.cap = d->s2s.mSel + d->s2s.eosExtra;
+  *nC = (int64_t)K * d->s2s.cap + K;
+  return FLTX_OK;
+}
+
+static int s2sPlanLexicon(fltx_decoder* d, int32_t V, int64_t* nC) {
+  const int K = d->s2s.opt.beam_size, Kt = d->s2s.opt.beam_size_token;
   const int ktEff = std::min(Kt, V);
   if (ktEff > kS2lMaxKt) {
     return fail(FLTX_ERR_UNSUPPORTED, "seq2seq lexicon: a token beam of %d (beam_size_token, V = %d) > %d", ktEff, V,
                 kS2lMaxKt);
   }
-  d->s2sMSel = ktEff; /* the exact token beam: the trie and word scores make the score non-monotone in the model's */
-  d->s2sEosExtra = 0;
-  d->s2sCap = ktEff;
-  const int64_t nC = (int64_t)K * ktEff * d->s2lS + K;
-  if (nC >= (int64_t)1 << 30) {
-    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq lexicon: %lld candidates per step", (long long)nC);
+  d->s2s.mSel = ktEff; /* the exact token beam: the trie and word scores make the score non-monotone in the model's */
+  d->s2s.eosExtra = 0;
+  d->s2s.cap = ktEff;
+  *nC = (int64_t)K * ktEff * d->s2s.slots + K;
+  if (*nC >= (int64_t)1 << 30) {
+    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq lexicon: %lld candidates per step", (long long)*nC);
   }
-  d->s2lMSize = s2lPow2AtLeast(2 * nC);
-  d->s2lSMax = (int)std::min<int64_t>((int64_t)K * d->s2sMaxOut + 1, d->s2lMaxStates);
-  d->s2lSSize = s2lPow2AtLeast(2 * (int64_t)d->s2lSMax);
-  Stream st = d->ctx->stream;
-  const size_t BK = (size_t)B * K, BC = (size_t)B * (size_t)nC;
-  if (d->s2lBeam.ensure(2 * BK * sizeof(S2lHyp), st, false) || d->s2sBeamN.ensure(8 * (size_t)B, st, false) ||
-      d->s2lHist.ensure((size_t)(d->s2sMaxOut + 1) * BK * sizeof(S2lRec), st, false) ||
-      d->s2sRowsInt.ensure(4 * (size_t)B, st, false) || d->s2sDone.ensure(4 * (size_t)B, st, false) ||
-      d->s2sFinal.ensure(4 * (size_t)B, st, false) || d->s2sRecTok.ensure(4 * BK * ktEff, st, false) ||
-      d->s2sRecAm.ensure(4 * BK * ktEff, st, false) || d->s2sRecN.ensure(4 * BK, st, false) ||
-      d->s2sKey.ensure(8 * BC, st, false) || d->s2lScore.ensure(8 * BC, st, false) ||
-      d->s2lMk.ensure(16 * BC, st, false) || d->s2lGrp.ensure(4 * BC, st, false) ||
-      d->s2lList.ensure(4 * BC, st, false) || d->s2lNext.ensure(4 * BC, st, false) ||
-      d->s2lMTab.ensure(4 * (size_t)B * d->s2lMSize, st, false) ||
-      d->s2lSKey.ensure(8 * (size_t)B * d->s2lSSize, st, false) ||
-      d->s2lSVal.ensure(4 * (size_t)B * d->s2lSSize, st, false) || d->s2lSCount.ensure(4 * (size_t)B, st, false) ||
-      d->s2lStatus.ensure(4 * (size_t)B, st, false) || d->s2lMerges.ensure(4 * (size_t)B, st, false)) {
-    return fail(FLTX_ERR_OOM, "seq2seq lexicon workspace: device allocation failed (B=%d K=%d V=%d)", B, K, V);
-  }
-  if (devMemset(d->s2lSKey.p, 0xFF, 8 * (size_t)B * d->s2lSSize, st)) { /* the state tables: empty */
-    return fail(FLTX_ERR_HIP, "seq2seq lexicon: memset failed");
-  }
-  d->B = B;
-  d->N = V;
-  d->s2sT = 0;
-  d->s2sBegun = true;
-  d->haveResults = false;
-  d->ended = false;
-  d->backtraced = false;
-  d->resultsSynced = false;
-  d->stateCap = (uint32_t)d->s2lSMax;
-  S2lParams Q = s2lParams(d);
-  Q.s.outTok = nextTok;
-  Q.s.outBeam = nextBeam;
-  Q.s.outSrc = nextSrc;
-  Q.s.outN = nRows;
-#ifdef FLTX_EMU
-  const S2lParams* qp = &Q;
-  emuLaunch((B + 63) / 64, 64, 0, [qp](char*) {
-    const int b = (int)(blockIdx.x * 64 + threadIdx.x);
-    if (b < qp->s.B) {
-      s2lBeginUtterance(*qp, b);
-    }
-  });
-#else
-  hipLaunchKernelGGL(fltx_s2s_lex_begin_kernel, dim3((B + 63) / 64), dim3(64), 0, st, Q);
-  HIPCHK(hipGetLastError());
-#endif
+  d->s2s.mSize = s2lPow2AtLeast(2 * *nC);
+  d->s2s.sMax = (int)std::min<int64_t>((int64_t)K * d->s2s.maxOut + 1, d->s2s.maxStates);
+  d->s2s.sSize = s2lPow2AtLeast(2 * (int64_t)d->s2s.sMax);
   return FLTX_OK;
 }
 
-/* row lists out: a launch of `kernel` writes them; the emulator runs the same function on host threads */
+static int s2sAllocLexicon(fltx_decoder* d, int32_t B, int32_t V, int64_t nC) {
+  Stream st = d->ctx->stream;
+  const size_t BC = (size_t)B * (size_t)nC;
+  if (d->s2s.cScore.ensure(8 * BC, st, false) || d->s2s.cMk.ensure(16 * BC, st, false) ||
+      d->s2s.cGrp.ensure(4 * BC, st, false) || d->s2s.cList.ensure(4 * BC, st, false) ||
+      d->s2s.cNext.ensure(4 * BC, st, false) || d->s2s.mTab.ensure(4 * (size_t)B * d->s2s.mSize, st, false) ||
+      d->s2s.sKey.ensure(8 * (size_t)B * d->s2s.sSize, st, false) ||
+      d->s2s.sVal.ensure(4 * (size_t)B * d->s2s.sSize, st, false) || d->s2s.sCount.ensure(4 * (size_t)B, st, false) ||
+      d->s2s.status.ensure(4 * (size_t)B, st, false) || d->s2s.merges.ensure(4 * (size_t)B, st, false)) {
+    return fail(FLTX_ERR_OOM, "seq2seq lexicon workspace: device allocation failed (B=%d K=%d V=%d)", B,
+                d->s2s.opt.beam_size, V);
+  }
+  if (devMemset(d->s2s.sKey.p, 0xFF, 8 * (size_t)B * d->s2s.sSize, st)) { /* the state tables: empty */
+    return fail(FLTX_ERR_HIP, "seq2seq lexicon: memset failed");
+  }
+  return FLTX_OK;
+}
+
 int fltx_s2s_begin(fltx_decoder* d, int32_t B, int32_t V, int32_t* nextTok, int32_t* nextBeam, int32_t* nextSrc,
                    int32_t* nRows) {
   DeviceScope devScope(d ? d->ctx : nullptr);
@@ -5048,57 +5046,132 @@ int fltx_s2s_begin(fltx_decoder* d, int32_t B, int32_t V, int32_t* nextTok, int3
   if (V > kS2sMaxV) {
     return fail(FLTX_ERR_UNSUPPORTED, "seq2seq: row width V = %d > %d", V, kS2sMaxV);
   }
-  if (d->kind == FLTX_DECODER_S2S_LEXICON) {
-    return s2lBegin(d, B, V, nextTok, nextBeam, nextSrc, nRows);
+  const bool lex = d->kind == FLTX_DECODER_S2S_LEXICON;
+  int64_t nC = 0;
+  if ((rc = lex ? s2sPlanLexicon(d, V, &nC) : s2sPlanLexFree(d, V, &nC))) {
+    return rc;
   }
-  const int K = d->s2sOpt.beam_size, Kt = d->s2sOpt.beam_size_token;
-  const int ktEff = std::min(Kt, V);
-  /* without LM terms in the score a row contributes at most K survivors besides eos: its top min(Kt, K + 1) (one more
-   * than K: eos may be among them) and eos when it is in the top Kt are every candidate that can survive */
-  const bool lmTerms = d->lm->kind == 1 && d->s2sOpt.lm_weight != 0.0;
-  if (lmTerms && ktEff > kS2sMaxKtLm) {
-    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq: a token beam of %d (beam_size_token, V = %d) > %d with LM terms", ktEff, V,
-                kS2sMaxKtLm);
-  }
-  d->s2sMSel = lmTerms ? ktEff : std::min(ktEff, K + 1);
-  d->s2sEosExtra = d->s2sMSel < ktEff ? 1 : 0;
-  d->s2sCap = d->s2sMSel + d->s2sEosExtra;
   Stream st = d->ctx->stream;
-  const size_t BK = (size_t)B * K;
-  const size_t nC = (size_t)K * d->s2sCap + K;
-  if (d->s2sBeam.ensure(2 * BK * sizeof(S2sHyp), st, false) || d->s2sBeamN.ensure(8 * (size_t)B, st, false) ||
-      d->s2sHist.ensure((size_t)(d->s2sMaxOut + 1) * BK * sizeof(int2), st, false) ||
-      d->s2sRowsInt.ensure(4 * (size_t)B, st, false) || d->s2sDone.ensure(4 * (size_t)B, st, false) ||
-      d->s2sFinal.ensure(4 * (size_t)B, st, false) || d->s2sRecTok.ensure(4 * BK * d->s2sCap, st, false) ||
-      d->s2sRecAm.ensure(4 * BK * d->s2sCap, st, false) || d->s2sRecN.ensure(4 * BK, st, false) ||
-      d->s2sKey.ensure(8 * (size_t)B * nC, st, false)) {
-    return fail(FLTX_ERR_OOM, "seq2seq workspace: device allocation failed (B=%d K=%d V=%d)", B, K, V);
+  const size_t BK = (size_t)B * d->s2s.opt.beam_size;
+  const size_t hypBytes = lex ? sizeof(S2lHyp) : sizeof(S2sHyp), recBytes = lex ? sizeof(S2lRec) : sizeof(int2);
+  if (d->s2s.beam.ensure(2 * BK * hypBytes, st, false) || d->s2s.beamN.ensure(8 * (size_t)B, st, false) ||
+      d->s2s.hist.ensure((size_t)(d->s2s.maxOut + 1) * BK * recBytes, st, false) ||
+      d->s2s.rowsInt.ensure(4 * (size_t)B, st, false) || d->s2s.done.ensure(4 * (size_t)B, st, false) ||
+      d->s2s.finalStep.ensure(4 * (size_t)B, st, false) ||
+      d->s2s.recTok.ensure(4 * BK * d->s2s.cap, st, false) || d->s2s.recAm.ensure(4 * BK * d->s2s.cap, st, false) ||
+      d->s2s.recN.ensure(4 * BK, st, false) || d->s2s.cKey.ensure(8 * (size_t)B * (size_t)nC, st, false)) {
+    return fail(FLTX_ERR_OOM, "seq2seq workspace: device allocation failed (B=%d K=%d V=%d)", B, d->s2s.opt.beam_size,
+                V);
+  }
+  if (lex && (rc = s2sAllocLexicon(d, B, V, nC))) {
+    return rc;
   }
   d->B = B;
   d->N = V;
-  d->s2sT = 0;
-  d->s2sBegun = true;
+  d->s2s.t = 0;
+  d->s2s.begun = true;
   d->haveResults = false;
   d->ended = false;
   d->backtraced = false;
   d->resultsSynced = false;
-  S2sParams P = s2sParams(d);
+  if (lex) {
+    d->stateCap = (uint32_t)d->s2s.sMax;
+  }
+  S2lParams Q = s2sStepParams(d);
+  S2sParams& P = Q.s;
   P.outTok = nextTok;
   P.outBeam = nextBeam;
   P.outSrc = nextSrc;
   P.outN = nRows;
-#ifdef FLTX_EMU
-  const S2sParams* pp = &P;
-  emuLaunch((B + 63) / 64, 64, 0, [pp](char*) {
-    const int b = (int)(blockIdx.x * 64 + threadIdx.x);
-    if (b < pp->B) {
-      s2sBeginUtterance(*pp, b);
+  const int nGrid = (B + kS2sBeginThreads - 1) / kS2sBeginThreads;
+  if (lex) {
+    S2S_LAUNCH(fltx_s2s_lex_begin_kernel, s2lBeginUtterance, nGrid, kS2sBeginThreads, 0, st, Q);
+  } else {
+    S2S_LAUNCH(fltx_s2s_begin_kernel, s2sBeginUtterance, nGrid, kS2sBeginThreads, 0, st, P);
+  }
+  return FLTX_OK;
+}
+
+extern "C++" { /* (a template, inside this file's extern "C" block) */
+template <int DT, bool LOGITS>
+static int s2sTypedLaunch(int nRows, Stream st, const S2sTypedParams& T) {
+  S2S_LAUNCH((fltx_s2s_typed_kernel<DT, LOGITS>), (s2sTypedRows<DT, LOGITS>), nRows, kS2sTypedThreads,
+             sizeof(S2sTypedLds), st, T);
+  return FLTX_OK;
+}
+}
+
+/* one step of either kind (the entry points have checked the decoder, `what` names the one that was called): the front
+ * end the input asks for -- fltx_s2s_tokbeam_kernel for float log-probs, else the typed one (fltx_s2s.h: s2sTypedRows)
+ * -- then the kind's step kernel */
+static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_t dtype, bool logits, int32_t onDevice,
+                   int64_t rowStride, const uint8_t* rowValid, double* rowLse, int32_t* nextTok, int32_t* nextBeam,
+                   int32_t* nextSrc, int32_t* nRows) {
+  if (!d->s2s.begun) {
+    return fail(FLTX_ERR_STATE, "%s: fltx_s2s_begin first", what);
+  }
+  if (!nextTok || !nextBeam || !nextSrc || !nRows || (!scores && d->s2s.t < d->s2s.maxOut) || rowStride < d->N) {
+    return fail(FLTX_ERR_INVALID, "%s: bad argument (row_stride %lld, V = %d)", what, (long long)rowStride, d->N);
+  }
+  const bool typed = dtype != FLTX_DTYPE_F32 || logits;
+  if (typed && d->s2s.mSel > kS2sTypedMaxList) { /* (not reachable within the limits of fltx_s2s_begin) */
+    return fail(FLTX_ERR_UNSUPPORTED, "%s: a token beam of %d > %d", what, d->s2s.mSel, kS2sTypedMaxList);
+  }
+  Stream st = d->ctx->stream;
+  const size_t BK = (size_t)d->B * d->s2s.opt.beam_size;
+  const size_t elem = dtype == FLTX_DTYPE_F32 ? 4 : 2;
+  const bool last = d->s2s.t >= d->s2s.maxOut; /* nothing to score: the kernels only list no rows */
+  if (!onDevice && !last) {
+    const size_t nE = (BK - 1) * (size_t)rowStride + (size_t)d->N;
+    if (d->s2s.scores.ensure(elem * nE, st, false) || (rowValid && d->s2s.valid.ensure(BK, st, false))) {
+      return fail(FLTX_ERR_OOM, "seq2seq: staging allocation failed");
     }
-  });
-#else
-  hipLaunchKernelGGL(fltx_s2s_begin_kernel, dim3((B + 63) / 64), dim3(64), 0, st, P);
-  HIPCHK(hipGetLastError());
-#endif
+    if (devCopyH2D(d->s2s.scores.p, scores, elem * nE, st) ||
+        (rowValid && devCopyH2D(d->s2s.valid.p, rowValid, BK, st))) {
+      return fail(FLTX_ERR_HIP, "seq2seq: upload failed");
+    }
+    scores = d->s2s.scores.p;
+    rowValid = rowValid ? d->s2s.valid.as<uint8_t>() : nullptr;
+  }
+  if (last && logits && rowLse && devMemset(rowLse, 0xFF, 8 * BK, st)) { /* (all-ones: a NaN) */
+    return fail(FLTX_ERR_HIP, "%s: memset failed", what);
+  }
+  S2lParams Q = s2sStepParams(d);
+  S2sParams& P = Q.s;
+  P.scores = typed ? nullptr : (const float*)scores;
+  P.rowStride = rowStride;
+  P.rowValid = rowValid;
+  P.outTok = nextTok;
+  P.outBeam = nextBeam;
+  P.outSrc = nextSrc;
+  P.outN = nRows;
+  if (!last && !typed) {
+    S2S_LAUNCH(fltx_s2s_tokbeam_kernel, s2sTokBeamRows, (int)((BK + 3) / 4), 256, 4 * sizeof(S2sFrontLds), st, P);
+  } else if (!last) {
+    S2sTypedParams T;
+    T.s = P;
+    T.x = scores;
+    T.rowLse = logits ? rowLse : nullptr;
+    int rc;
+    switch (dtype * 2 + (logits ? 1 : 0)) {
+      case 1: rc = s2sTypedLaunch<kS2sDtF32, true>((int)BK, st, T); break;
+      case 2: rc = s2sTypedLaunch<kS2sDtF16, false>((int)BK, st, T); break;
+      case 3: rc = s2sTypedLaunch<kS2sDtF16, true>((int)BK, st, T); break;
+      case 4: rc = s2sTypedLaunch<kS2sDtBf16, false>((int)BK, st, T); break;
+      default: rc = s2sTypedLaunch<kS2sDtBf16, true>((int)BK, st, T); break;
+    }
+    if (rc) {
+      return rc;
+    }
+  }
+  if (d->kind == FLTX_DECODER_S2S_LEXICON) {
+    S2S_LAUNCH(fltx_s2s_lex_step_kernel, s2lStepUtterance, d->B, kS2sStepThreads, sizeof(S2lStepLds), st, Q);
+  } else {
+    S2S_LAUNCH(fltx_s2s_step_kernel, s2sStepUtterance, d->B, kS2sStepThreads, sizeof(S2sStepLds), st, P);
+  }
+  if (!last) {
+    ++d->s2s.t;
+  }
   return FLTX_OK;
 }
 
@@ -5112,73 +5185,11 @@ int fltx_s2s_step(fltx_decoder* d, const float* scores, int32_t onDevice, int64_
   if (rc) {
     return rc;
   }
-  if (!d->s2sBegun) {
-    return fail(FLTX_ERR_STATE, "fltx_s2s_step: fltx_s2s_begin first");
-  }
-  if (!nextTok || !nextBeam || !nextSrc || !nRows || (!scores && d->s2sT < d->s2sMaxOut) || rowStride < d->N) {
-    return fail(FLTX_ERR_INVALID, "fltx_s2s_step: bad argument (row_stride %lld, V = %d)", (long long)rowStride, d->N);
-  }
-  Stream st = d->ctx->stream;
-  const size_t BK = (size_t)d->B * d->s2sOpt.beam_size;
-  const bool last = d->s2sT >= d->s2sMaxOut; /* nothing to score: the kernels only list no rows */
-  if (!onDevice && !last) {
-    const size_t nF = (BK - 1) * (size_t)rowStride + (size_t)d->N;
-    if (d->s2sScores.ensure(4 * nF, st, false) || (rowValid && d->s2sValid.ensure(BK, st, false))) {
-      return fail(FLTX_ERR_OOM, "seq2seq: staging allocation failed");
-    }
-    if (devCopyH2D(d->s2sScores.p, scores, 4 * nF, st) || (rowValid && devCopyH2D(d->s2sValid.p, rowValid, BK, st))) {
-      return fail(FLTX_ERR_HIP, "seq2seq: upload failed");
-    }
-    scores = d->s2sScores.as<float>();
-    rowValid = rowValid ? d->s2sValid.as<uint8_t>() : nullptr;
-  }
-  const bool lex = d->kind == FLTX_DECODER_S2S_LEXICON;
-  S2lParams Q;
-  if (lex) {
-    Q = s2lParams(d);
-  } else {
-    memset(&Q, 0, sizeof(Q));
-    Q.s = s2sParams(d);
-  }
-  S2sParams& P = Q.s;
-  P.scores = scores;
-  P.rowStride = rowStride;
-  P.rowValid = rowValid;
-  P.outTok = nextTok;
-  P.outBeam = nextBeam;
-  P.outSrc = nextSrc;
-  P.outN = nRows;
-  const int nFront = (int)((BK + 3) / 4);
-#ifdef FLTX_EMU
-  const S2sParams* pp = &P;
-  const S2lParams* qp = &Q;
-  if (!last) {
-    emuLaunch(nFront, 256, 4 * sizeof(S2sFrontLds), [pp](char* smem) { s2sTokBeamRows(*pp, smem); });
-  }
-  if (lex) {
-    emuLaunch(d->B, kS2sStepThreads, sizeof(S2lStepLds), [qp](char* smem) { s2lStepUtterance(*qp, smem); });
-  } else {
-    emuLaunch(d->B, kS2sStepThreads, sizeof(S2sStepLds), [pp](char* smem) { s2sStepUtterance(*pp, smem); });
-  }
-#else
-  if (!last) {
-    hipLaunchKernelGGL(fltx_s2s_tokbeam_kernel, dim3(nFront), dim3(256), 0, st, P);
-    HIPCHK(hipGetLastError());
-  }
-  if (lex) {
-    hipLaunchKernelGGL(fltx_s2s_lex_step_kernel, dim3(d->B), dim3(kS2sStepThreads), 0, st, Q);
-  } else {
-    hipLaunchKernelGGL(fltx_s2s_step_kernel, dim3(d->B), dim3(kS2sStepThreads), 0, st, P);
-  }
-  HIPCHK(hipGetLastError());
-#endif
-  if (!last) {
-    ++d->s2sT;
-  }
-  return FLTX_OK;
+  return s2sStep(d, "fltx_s2s_step", scores, FLTX_DTYPE_F32, false, onDevice, rowStride, rowValid, nullptr, nextTok,
+                 nextBeam, nextSrc, nRows);
 }
 
-/* the typed front end (fltx_s2s.h: s2sTypedRows) in place of fltx_s2s_tokbeam_kernel, then the same step kernel */
+/* the model's rows as it produces them: fp16 / bf16 / f32, log-probs or raw logits */
 int fltx_s2s_step_typed(fltx_decoder* d, const void* scores, int32_t dtype, int32_t kind, int32_t onDevice,
                         int64_t rowStride, const uint8_t* rowValid, double* rowLse, int32_t* nextTok,
                         int32_t* nextBeam, int32_t* nextSrc, int32_t* nRows) {
@@ -5196,102 +5207,8 @@ int fltx_s2s_step_typed(fltx_decoder* d, const void* scores, int32_t dtype, int3
   if (kind != FLTX_S2S_LOG_PROBS && kind != FLTX_S2S_LOGITS) {
     return fail(FLTX_ERR_INVALID, "fltx_s2s_step_typed: kind %d", kind);
   }
-  if (!d->s2sBegun) {
-    return fail(FLTX_ERR_STATE, "fltx_s2s_step_typed: fltx_s2s_begin first");
-  }
-  if (rowStride < d->N) {
-    return fail(FLTX_ERR_INVALID, "fltx_s2s_step_typed: row_stride %lld < V = %d", (long long)rowStride, d->N);
-  }
-  const bool logits = kind == FLTX_S2S_LOGITS;
-  if (dtype == FLTX_DTYPE_F32 && !logits) { /* float log-probs: exactly fltx_s2s_step */
-    return fltx_s2s_step(d, (const float*)scores, onDevice, rowStride, rowValid, nextTok, nextBeam, nextSrc, nRows);
-  }
-  if (!nextTok || !nextBeam || !nextSrc || !nRows || (!scores && d->s2sT < d->s2sMaxOut)) {
-    return fail(FLTX_ERR_INVALID, "fltx_s2s_step_typed: bad argument");
-  }
-  if (d->s2sMSel > kS2sTypedMaxList) { /* (not reachable within the limits of fltx_s2s_begin) */
-    return fail(FLTX_ERR_UNSUPPORTED, "fltx_s2s_step_typed: a token beam of %d > %d", d->s2sMSel, kS2sTypedMaxList);
-  }
-  Stream st = d->ctx->stream;
-  const size_t BK = (size_t)d->B * d->s2sOpt.beam_size;
-  const size_t elem = dtype == FLTX_DTYPE_F32 ? 4 : 2;
-  const bool last = d->s2sT >= d->s2sMaxOut; /* nothing to score: the kernels only list no rows */
-  if (!onDevice && !last) {
-    const size_t nE = (BK - 1) * (size_t)rowStride + (size_t)d->N;
-    if (d->s2sScores.ensure(elem * nE, st, false) || (rowValid && d->s2sValid.ensure(BK, st, false))) {
-      return fail(FLTX_ERR_OOM, "seq2seq: staging allocation failed");
-    }
-    if (devCopyH2D(d->s2sScores.p, scores, elem * nE, st) ||
-        (rowValid && devCopyH2D(d->s2sValid.p, rowValid, BK, st))) {
-      return fail(FLTX_ERR_HIP, "seq2seq: upload failed");
-    }
-    scores = d->s2sScores.p;
-    rowValid = rowValid ? d->s2sValid.as<uint8_t>() : nullptr;
-  }
-  if (last && logits && rowLse && devMemset(rowLse, 0xFF, 8 * BK, st)) { /* (all-ones: a NaN) */
-    return fail(FLTX_ERR_HIP, "fltx_s2s_step_typed: memset failed");
-  }
-  const bool lex = d->kind == FLTX_DECODER_S2S_LEXICON;
-  S2lParams Q;
-  if (lex) {
-    Q = s2lParams(d);
-  } else {
-    memset(&Q, 0, sizeof(Q));
-    Q.s = s2sParams(d);
-  }
-  S2sParams& P = Q.s;
-  P.rowStride = rowStride;
-  P.rowValid = rowValid;
-  P.outTok = nextTok;
-  P.outBeam = nextBeam;
-  P.outSrc = nextSrc;
-  P.outN = nRows;
-  S2sTypedParams T;
-  T.s = P;
-  T.x = scores;
-  T.rowLse = logits ? rowLse : nullptr;
-#ifdef FLTX_EMU
-  const S2sParams* pp = &P;
-  const S2lParams* qp = &Q;
-  const S2sTypedParams* tp = &T;
-  if (!last) {
-    std::function<void(char*)> fn;
-    switch (dtype * 2 + (logits ? 1 : 0)) {
-      case 1: fn = [tp](char* smem) { s2sTypedRows<kS2sDtF32, true>(*tp, smem); }; break;
-      case 2: fn = [tp](char* smem) { s2sTypedRows<kS2sDtF16, false>(*tp, smem); }; break;
-      case 3: fn = [tp](char* smem) { s2sTypedRows<kS2sDtF16, true>(*tp, smem); }; break;
-      case 4: fn = [tp](char* smem) { s2sTypedRows<kS2sDtBf16, false>(*tp, smem); }; break;
-      default: fn = [tp](char* smem) { s2sTypedRows<kS2sDtBf16, true>(*tp, smem); }; break;
-    }
-    emuLaunch((int)BK, kS2sTypedThreads, sizeof(S2sTypedLds), fn);
-  }
-  if (lex) {
-    emuLaunch(d->B, kS2sStepThreads, sizeof(S2lStepLds), [qp](char* smem) { s2lStepUtterance(*qp, smem); });
-  } else {
-    emuLaunch(d->B, kS2sStepThreads, sizeof(S2sStepLds), [pp](char* smem) { s2sStepUtterance(*pp, smem); });
-  }
-#else
-  if (!last) {
-    switch (dtype * 2 + (logits ? 1 : 0)) {
-      case 1: s2sTypedLaunch<kS2sDtF32, true>((int)BK, st, T); break;
-      case 2: s2sTypedLaunch<kS2sDtF16, false>((int)BK, st, T); break;
-      case 3: s2sTypedLaunch<kS2sDtF16, true>((int)BK, st, T); break;
-      case 4: s2sTypedLaunch<kS2sDtBf16, false>((int)BK, st, T); break;
-      default: s2sTypedLaunch<kS2sDtBf16, true>((int)BK, st, T); break;
-    }
-    HIPCHK(hipGetLastError());
-  }
-  if (lex) {
-    hipLaunchKernelGGL(fltx_s2s_lex_step_kernel, dim3(d->B), dim3(kS2sStepThreads), 0, st, Q);
-  } else {
-    hipLaunchKernelGGL(fltx_s2s_step_kernel, dim3(d->B), dim3(kS2sStepThreads), 0, st, P);
-  }
-  HIPCHK(hipGetLastError());
-#endif
-  if (!last) {
-    ++d->s2sT;
-  }
-  return FLTX_OK;
+  return s2sStep(d, "fltx_s2s_step_typed", scores, dtype, kind == FLTX_S2S_LOGITS, onDevice, rowStride, rowValid,
+                 rowLse, nextTok, nextBeam, nextSrc, nRows);
 }
 
 int fltx_s2s_done(fltx_decoder* d, int32_t* done) {
@@ -5306,15 +5223,15 @@ int fltx_s2s_done(fltx_decoder* d, int32_t* done) {
   if (!done) {
     return fail(FLTX_ERR_INVALID, "fltx_s2s_done: null argument");
   }
-  if (!d->s2sBegun) {
+  if (!d->s2s.begun) {
     return fail(FLTX_ERR_STATE, "fltx_s2s_done: fltx_s2s_begin first");
   }
-  if (d->s2sT >= d->s2sMaxOut) {
+  if (d->s2s.t >= d->s2s.maxOut) {
     *done = 1;
     return FLTX_OK;
   }
   std::vector<int32_t> h((size_t)d->B);
-  if (devCopyD2H(h.data(), d->s2sDone.p, 4 * (size_t)d->B, d->ctx->stream) || devSync(d->ctx->stream)) {
+  if (devCopyD2H(h.data(), d->s2s.done.p, 4 * (size_t)d->B, d->ctx->stream) || devSync(d->ctx->stream)) {
     return fail(FLTX_ERR_HIP, "fltx_s2s_done: copy failed: %s", devErr());
   }
   *done = 1;
@@ -5333,11 +5250,11 @@ int fltx_s2s_end(fltx_decoder* d) {
   if (rc) {
     return rc;
   }
-  if (!d->s2sBegun) {
+  if (!d->s2s.begun) {
     return fail(FLTX_ERR_STATE, "fltx_s2s_end: fltx_s2s_begin first");
   }
   Stream st = d->ctx->stream;
-  const int B = d->B, K = d->s2sOpt.beam_size, len = d->s2sMaxOut + 3;
+  const int B = d->B, K = d->s2s.opt.beam_size, len = d->s2s.maxOut + 3;
   d->histOff.resize((size_t)B + 1);
   for (int b = 0; b <= B; ++b) {
     d->histOff[b] = (int64_t)b * K * len;
@@ -5356,14 +5273,8 @@ int fltx_s2s_end(fltx_decoder* d) {
   if (lex && d->words.ensure(4 * (size_t)d->histRecords, st, false)) {
     return fail(FLTX_ERR_OOM, "seq2seq results: device allocation failed");
   }
-  S2lParams Q;
-  if (lex) {
-    Q = s2lParams(d);
-    Q.words = d->words.as<int32_t>();
-  } else {
-    memset(&Q, 0, sizeof(Q));
-    Q.s = s2sParams(d);
-  }
+  S2lParams Q = s2sStepParams(d);
+  Q.words = lex ? d->words.as<int32_t>() : nullptr;
   S2sParams& P = Q.s;
   P.outScores = d->outScores.as<double>();
   P.tokens = d->tokens.as<int32_t>();
@@ -5371,22 +5282,11 @@ int fltx_s2s_end(fltx_decoder* d) {
   P.uttNBeam = d->uttNBeam.as<int32_t>();
   P.uttFrame = d->uttFrame.as<int32_t>();
   P.uttStatus = d->uttStatus.as<int32_t>();
-#ifdef FLTX_EMU
-  const S2sParams* pp = &P;
-  const S2lParams* qp = &Q;
   if (lex) {
-    emuLaunch(B, 64, 0, [qp](char*) { s2lEndUtterance(*qp, (int)blockIdx.x, (int)threadIdx.x, 64); });
+    S2S_LAUNCH(fltx_s2s_lex_end_kernel, s2lEndUtterance, B, kS2sEndThreads, 0, st, Q);
   } else {
-    emuLaunch(B, 64, 0, [pp](char*) { s2sEndUtterance(*pp, (int)blockIdx.x, (int)threadIdx.x, 64); });
+    S2S_LAUNCH(fltx_s2s_end_kernel, s2sEndUtterance, B, kS2sEndThreads, 0, st, P);
   }
-#else
-  if (lex) {
-    hipLaunchKernelGGL(fltx_s2s_lex_end_kernel, dim3(B), dim3(256), 0, st, Q);
-  } else {
-    hipLaunchKernelGGL(fltx_s2s_end_kernel, dim3(B), dim3(256), 0, st, P);
-  }
-  HIPCHK(hipGetLastError());
-#endif
   d->haveResults = true;
   d->ended = true;
   d->backtraced = true;

@@ -28,6 +28,8 @@ constexpr int kS2sMaxKtLm = 64;      /* min(beamSizeToken, V) with a scoring LM 
 constexpr int kS2sMaxLen = 4096;     /* maxOutputLength */
 constexpr int kS2sCtx = kMaxNgramOrder - 1;
 constexpr int kS2sStepThreads = 256; /* the step kernel: one thread per beam slot */
+constexpr int kS2sBeginThreads = 64; /* the begin kernel: one thread per utterance */
+constexpr int kS2sEndThreads = 256;  /* the end kernel: one workgroup per utterance, thread per hypothesis */
 
 struct S2sHyp { /* one hypothesis of a beam, 56 B */
   double score, am, lm;
@@ -70,17 +72,21 @@ struct S2sParams {
 };
 
 /* ---- LM ------------------------------------------------------------------------------------------------------- */
-/* LM::score (KenLM.cpp:63-75: child state per token) and LM::finish of the n-gram tables; ZeroLM: 0 */
-FLTX_DEV float s2sLm(const S2sParams& P, const int32_t* ctx, int tok, int32_t* ctxOut) {
+/* LM::score (KenLM.cpp:63-75: child state per token) over the LM's user ids, and LM::finish, of the n-gram tables;
+ * ZeroLM: 0.  The question is `usr`, or finish when usr == finishUsr: eos where the ids are the model's tokens,
+ * kS2sLmFinish where no id means it.  (The comparison stays in here, behind lmOn: handed in as a flag it cost the
+ * lexicon-free step kernel 1.3 us a launch.) */
+constexpr int kS2sLmFinish = -2;
+FLTX_DEV float s2sLm(const S2sParams& P, const int32_t* ctx, int usr, int finishUsr, int32_t* ctxOut) {
   if (!P.lmOn) {
     return 0.0f;
   }
   const DecodeParams& L = P.lmp;
   uint32_t word;
-  if (tok == P.eos) {
+  if (usr == finishUsr) {
     word = (uint32_t)L.lmEos;
   } else {
-    word = (tok >= 0 && tok < L.nUsr) ? (uint32_t)L.usrToLm[tok] : (uint32_t)L.lmUnk;
+    word = (usr >= 0 && usr < L.nUsr) ? (uint32_t)L.usrToLm[usr] : (uint32_t)L.lmUnk;
   }
   return ngScore(L, ctx, word, ctxOut);
 }
@@ -288,16 +294,18 @@ FLTX_DEV void s2sTypedEach(const void* row, int V, double lse, const uint32_t* k
   }
 }
 
-FLTX_DEV int s2sTypedBlockSum(S2sTypedLds& S, int v) {
+/* sum of v over the workgroup, in every thread (the typed front end's workgroup and the step's: four waves) */
+static_assert(kS2sTypedThreads == kS2sStepThreads, "s2sBlockSum: one wcnt slot per wave");
+FLTX_DEV int s2sBlockSum(int32_t (&wcnt)[kS2sStepThreads / 64], int v) {
   const int s = (int)waveReadLane32((uint32_t)waveInclusiveScan(v), 63);
   __syncthreads();
   if (laneId() == 0) {
-    S.wcnt[waveId()] = s;
+    wcnt[waveId()] = s;
   }
   __syncthreads();
   int all = 0;
-  for (int w = 0; w < kS2sTypedThreads / 64; ++w) {
-    all += S.wcnt[w];
+  for (int w = 0; w < kS2sStepThreads / 64; ++w) {
+    all += wcnt[w];
   }
   return all;
 }
@@ -436,7 +444,7 @@ FLTX_DEV void s2sTypedRow(const S2sTypedParams& Q, S2sTypedLds& S, int64_t r) {
       s2sTypedEach<DT, LOGITS, CACHED, false>(row, V, lse, kr, [&](int i, uint32_t k) {
         above += (k > ke || (k == ke && i < P.eos)) ? 1 : 0;
       });
-      eosAdd = s2sTypedBlockSum(S, above) < P.Kt;
+      eosAdd = s2sBlockSum(S.wcnt, above) < P.Kt;
     }
   }
   /* written in token order (the rank of each token among the listed), eos after them */
@@ -518,109 +526,72 @@ FLTX_DEV int s2sBlockRank(S2sStepLds& S, bool flag, int* total) {
   return base + wavePrefixCount(bl);
 }
 
-/* sum of v over the workgroup, in every thread */
-FLTX_DEV int s2sBlockSum(S2sStepLds& S, int v) {
-  const int s = (int)waveReadLane32((uint32_t)waveInclusiveScan(v), 63);
-  __syncthreads();
-  if (laneId() == 0) {
-    S.wcnt[waveId()] = s;
+/* ---- the step's skeleton: what the lexicon-free step below and the lexicon step (fltx_s2s_lex.h) share. -------------
+ * A decoder differs in its hypothesis / record types (template parameters) and in the values it hands in; every
+ * function here is called by all kS2sStepThreads threads of the workgroup under uniform control flow (barriers). */
+
+/* the order key of a score: NaN is never a candidate (0); +0.0: -0 and +0 compare equal, as the reference's doubles */
+FLTX_DEV unsigned long long s2sScoreKey(double s) { return s == s ? f64Key(s + 0.0) : 0ull; }
+
+/* a step that scores nothing (after the last one, a stopped utterance): no rows for the model */
+FLTX_DEV void s2sIdleStep(const S2sParams& P, int b) {
+  const int64_t rb = (int64_t)b * P.K;
+  for (int k = (int)threadIdx.x; k < P.K; k += kS2sStepThreads) {
+    P.outTok[rb + k] = -1;
+    P.outBeam[rb + k] = -1;
+    P.outSrc[rb + k] = -1;
   }
-  __syncthreads();
-  int all = 0;
-  for (int w = 0; w < kS2sStepThreads / 64; ++w) {
-    all += S.wcnt[w];
+  if (threadIdx.x == 0) {
+    P.outN[b] = 0;
   }
-  return all;
 }
 
-/* candidate j of the utterance: row k = j / cap, entry e = j % cap for j < nRows*cap; then the carried hypotheses */
-FLTX_DEV void s2sStepUtterance(const S2sParams& P, char* smem) {
-  S2sStepLds& S = *(S2sStepLds*)smem;
-  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
-  const int K = P.K;
-  const int64_t rb = (int64_t)b * K;
-  const int lane = laneId(), wave = waveId();
-  if (P.done[b] || P.t >= P.maxOut) { /* a step after the last one: nothing to score */
-    for (int k = tid; k < K; k += kS2sStepThreads) {
-      P.outTok[rb + k] = -1;
-      P.outBeam[rb + k] = -1;
-      P.outSrc[rb + k] = -1;
+/* rows <-> hypotheses: the live ones (not ended by eos) of the current beam, in beam order */
+template <typename Hyp>
+FLTX_DEV void s2sMapRows(S2sStepLds& S, const Hyp* prev, int nPrev, int eos) {
+  const int tid = (int)threadIdx.x;
+  const bool isLive = tid < nPrev && prev[tid].token != eos;
+  int tot;
+  const int q = s2sBlockRank(S, isLive, &tot);
+  if (tid < nPrev) {
+    S.rowOfHyp[tid] = isLive ? q : -1;
+    if (isLive) {
+      S.hypOfRow[q] = tid;
     }
-    if (tid == 0) {
-      P.outN[b] = 0;
-    }
-    return;
   }
-  const int par = P.t & 1;
-  const S2sHyp* prev = P.beam + (size_t)par * P.B * K + rb;
-  S2sHyp* next = P.beam + (size_t)(par ^ 1) * P.B * K + rb;
-  const int nPrev = P.beamN[par * P.B + b];
-  const int nRows = P.nRowsInt[b];
-  const int cap = P.cap;
-  /* 1. rows <-> hypotheses (the live ones in beam order: LexiconFreeSeq2SeqDecoder.cpp:44-55) */
-  {
-    const bool isLive = tid < nPrev && prev[tid].token != P.eos;
-    int tot;
-    const int q = s2sBlockRank(S, isLive, &tot);
-    if (tid < nPrev) {
-      S.rowOfHyp[tid] = isLive ? q : -1;
-      if (isLive) {
-        S.hypOfRow[q] = tid;
-      }
-    }
-    __syncthreads();
-  }
-  /* 2. the candidates' keys and the best of the step */
-  unsigned long long* cKey = P.cKey + (size_t)b * P.nC;
-  const int64_t nRowC = (int64_t)nRows * cap, n = nRowC + nPrev;
-  unsigned long long mx = 0ull;
-  for (int64_t j = tid; j < n; j += kS2sStepThreads) {
-    unsigned long long key = 0ull;
-    if (j < nRowC) {
-      const int k = (int)(j / cap), e = (int)(j % cap);
-      const int64_t r = rb + k;
-      if (e < P.recN[r]) {
-        const S2sHyp& h = prev[S.hypOfRow[k]];
-        const int tok = P.recTok[r * cap + e];
-        const float lmS = s2sLm(P, h.ctx, tok, nullptr);
-        const double s = s2sScore(P, h, tok, P.recAm[r * cap + e], lmS);
-        key = s == s ? f64Key(s + 0.0) : 0ull; /* (+0.0: -0 and +0 compare equal, as the reference's doubles do) */
-      }
-    } else {
-      const S2sHyp& h = prev[j - nRowC];
-      if (h.token == P.eos) { /* a finished hypothesis is carried unchanged (:68-82) */
-        key = h.score == h.score ? f64Key(h.score + 0.0) : 0ull;
-      }
-    }
-    cKey[j] = key;
-    mx = key > mx ? key : mx;
-  }
+  __syncthreads();
+}
+
+/* the largest of the threads' keys, in every thread */
+FLTX_DEV unsigned long long s2sBlockMaxKey(S2sStepLds& S, unsigned long long mx) {
   mx = waveMax64(mx);
-  if (lane == 0) {
-    S.wmax[wave] = mx;
+  if (laneId() == 0) {
+    S.wmax[waveId()] = mx;
   }
   __syncthreads();
   for (int w = 0; w < kS2sStepThreads / 64; ++w) {
     mx = S.wmax[w] > mx ? S.wmax[w] : mx;
   }
-  /* 3. threshold (candidatesAdd / candidatesStore: score >= best - beamThreshold, best over the whole step) */
+  return mx;
+}
+
+/* threshold (candidatesAdd / candidatesStore: score >= best - beamThreshold, best over the whole step) as a key:
+ * a candidate survives when its key is >= this one */
+FLTX_DEV unsigned long long s2sThresholdKey(unsigned long long bestKey, double beamThreshold) {
   unsigned long long thrKey = 1ull;
-  if (mx != 0ull) {
-    const double thr = f64FromKey(mx) - P.beamThreshold;
+  if (bestKey != 0ull) {
+    const double thr = f64FromKey(bestKey) - beamThreshold;
     thrKey = thr == thr ? f64Key(thr + 0.0) : ~0ull;
     thrKey = thrKey == 0ull ? 1ull : thrKey;
   }
-  int surv = 0;
-  for (int64_t j = tid; j < n; j += kS2sStepThreads) {
-    const unsigned long long key = cKey[j];
-    if (key != 0ull && key < thrKey) {
-      cKey[j] = 0ull;
-    } else if (key != 0ull) {
-      ++surv;
-    }
-  }
-  const int nSurv = s2sBlockSum(S, surv);
-  /* 4. the K best survivors: radix select over the 64-bit keys */
+  return thrKey;
+}
+
+/* the K best of the utterance's keys cKey[0..n) (0: none), nSurv of them not 0: a radix select over the 64-bit keys,
+ * then the selected sorted best first (returnSorted: Utils.h:204-216).  Leaves S.selIdx / S.selKey (the selected, in
+ * no order) and S.order (rank -> position in those); returns how many */
+FLTX_DEV int s2sSelectTopK(S2sStepLds& S, const unsigned long long* cKey, int64_t n, int K, int nSurv) {
+  const int tid = (int)threadIdx.x, lane = laneId(), wave = waveId();
   unsigned long long pre = 0ull, msk = 0ull;
   bool all = nSurv <= K, allEq = false;
   int need = K;
@@ -668,7 +639,6 @@ FLTX_DEV void s2sStepUtterance(const S2sParams& P, char* smem) {
       seen += tot;
     }
   }
-  /* 5. the selected, then sorted best first (returnSorted: Utils.h:204-216) */
   if (tid == 0) {
     S.nSel = 0;
   }
@@ -697,36 +667,15 @@ FLTX_DEV void s2sStepUtterance(const S2sParams& P, char* smem) {
     S.order[rank] = tid;
   }
   __syncthreads();
-  /* 6. the new beam, its history records and the next call's rows */
-  S2sHyp nh;
-  bool isLive = false;
-  int srcRow = -1;
-  if (tid < nSel) {
-    const int64_t j = S.selIdx[S.order[tid]];
-    if (j < nRowC) {
-      const int k = (int)(j / cap), e = (int)(j % cap);
-      const int64_t r = rb + k;
-      const int i = S.hypOfRow[k];
-      const S2sHyp& h = prev[i];
-      const int tok = P.recTok[r * cap + e];
-      const float a = P.recAm[r * cap + e];
-      nh = h;
-      const float lmS = s2sLm(P, h.ctx, tok, tok == P.eos ? nullptr : nh.ctx);
-      nh.score = s2sScore(P, h, tok, a, lmS);
-      nh.am = h.am + (double)a;
-      nh.lm = h.lm + (double)lmS;
-      nh.token = tok;
-      nh.parent = i;
-      isLive = tok != P.eos;
-      srcRow = (int)rb + k;
-    } else {
-      const int i = (int)(j - nRowC);
-      nh = prev[i];
-      nh.parent = i;
-    }
-    next[tid] = nh;
-    P.hist[(size_t)(P.t + 1) * P.B * K + rb + tid] = make_int2(nh.token, nh.parent);
-  }
+  return nSel;
+}
+
+/* the step's outcome: thread tid < nSel made hypothesis tid of the new beam, (token, parent), `isLive` when the model
+ * extends it, from row `srcRow` of this call.  Writes the next call's rows and the utterance's bookkeeping */
+FLTX_DEV void s2sPublishStep(const S2sParams& P, S2sStepLds& S, int b, int nSel, bool isLive, int token, int parent,
+                             int srcRow) {
+  const int tid = (int)threadIdx.x, K = P.K, par = P.t & 1;
+  const int64_t rb = (int64_t)b * K;
   int nLive;
   const int q = s2sBlockRank(S, isLive, &nLive);
   const bool fin = nSel == 0 || nLive == 0 || P.t + 1 >= P.maxOut;
@@ -734,8 +683,8 @@ FLTX_DEV void s2sStepUtterance(const S2sParams& P, char* smem) {
     nLive = 0;
   }
   if (isLive && !fin) {
-    P.outTok[rb + q] = nh.token;
-    P.outBeam[rb + q] = nh.parent;
+    P.outTok[rb + q] = token;
+    P.outBeam[rb + q] = parent;
     P.outSrc[rb + q] = srcRow;
   }
   for (int k = nLive + tid; k < K; k += kS2sStepThreads) {
@@ -751,15 +700,14 @@ FLTX_DEV void s2sStepUtterance(const S2sParams& P, char* smem) {
     }
     if (fin) {
       P.done[b] = 1;
-      P.finalStep[b] = nSel > 0 ? P.t + 1 : P.t; /* the last non-empty beam (:152-158) */
+      P.finalStep[b] = nSel > 0 ? P.t + 1 : P.t; /* the last non-empty beam (:152-158; lexicon: :204-207) */
     }
   }
 }
 
-/* decodeStep's start (:30-32): the root, and the first call's single row (token -1, beam index -1, no source row) */
-FLTX_DEV void s2sBeginUtterance(const S2sParams& P, int b) {
-  const int64_t rb = (int64_t)b * P.K;
-  S2sHyp h;
+/* decodeStep's start (:30-32): the root's fields that every hypothesis type has ... */
+template <typename Hyp>
+FLTX_DEV void s2sRootHyp(const S2sParams& P, Hyp& h) {
   h.score = 0.0;
   h.am = 0.0;
   h.lm = 0.0;
@@ -768,8 +716,11 @@ FLTX_DEV void s2sBeginUtterance(const S2sParams& P, int b) {
   for (int j = 0; j < kS2sCtx; ++j) {
     h.ctx[j] = P.ctx0[j];
   }
-  h.pad = 0;
-  P.beam[rb] = h;
+}
+
+/* ... and the utterance's state: a beam of one, the first call's single row (token -1, beam index -1, no source row) */
+FLTX_DEV void s2sBeginReset(const S2sParams& P, int b) {
+  const int64_t rb = (int64_t)b * P.K;
   P.beamN[b] = 1;
   const int live = P.maxOut > 0 ? 1 : 0;
   P.nRowsInt[b] = live;
@@ -783,39 +734,159 @@ FLTX_DEV void s2sBeginUtterance(const S2sParams& P, int b) {
   P.outN[b] = live;
 }
 
-/* getAllFinalHypothesis (:160-163, Utils.h:230-266): the final beam's paths, right-aligned in rows of `len` =
- * maxOutputLength + 3 tokens with -1 in front; thread per hypothesis */
-FLTX_DEV void s2sEndUtterance(const S2sParams& P, int b, int tid, int nThreads) {
+/* getAllFinalHypothesis (:160-163, Utils.h:230-266): the final beam's scores and paths, right-aligned in rows of
+ * `len` = maxOutputLength + 3 with -1 in front; workgroup per utterance, thread per hypothesis.  `beams` / `hist` are
+ * the decoder's own; `path` says where a record goes: none(at) writes -1 at element `at`, put(at, rec) the record,
+ * returning its parent.  put takes the record BY VALUE: by reference, its fields may alias the rows it stores to, and
+ * every field is loaded again after each store -- three dependent loads per step of the walk instead of one */
+template <typename Hyp, typename Rec, typename Path>
+FLTX_DEV void s2sBackTrace(const S2sParams& P, const Hyp* beams, const Rec* hist, const Path& path, int status) {
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
   const int K = P.K;
   const int64_t rb = (int64_t)b * K;
   const int fs = P.done[b] ? P.finalStep[b] : P.t;
   const int par = fs & 1;
   const int n = P.beamN[par * P.B + b];
-  const S2sHyp* beam = P.beam + (size_t)par * P.B * K + rb;
+  const Hyp* beam = beams + (size_t)par * P.B * K + rb;
   const int len = P.len;
-  for (int k = tid; k < n; k += nThreads) {
-    const S2sHyp& h = beam[k];
+  for (int k = tid; k < n; k += kS2sEndThreads) {
+    const Hyp& h = beam[k];
     double* sc = P.outScores + (rb + k) * 3;
     sc[0] = h.score;
     sc[1] = h.am;
     sc[2] = h.lm;
-    int32_t* out = P.tokens + (rb + k) * len;
+    const int64_t row = (rb + k) * len;
     for (int f = 0; f < len - fs; ++f) {
-      out[f] = -1;
+      path.none(row + f);
     }
     int p = k;
     for (int s = fs; s >= 1; --s) {
-      const int2 rec = P.hist[(size_t)s * P.B * K + rb + p];
-      out[len - 1 - (fs - s)] = rec.x;
-      p = rec.y;
+      const Rec rec = hist[(size_t)s * P.B * K + rb + p];
+      p = path.put(row + len - 1 - (fs - s), rec);
     }
   }
   if (tid == 0) {
     P.outNHyp[b] = n;
     P.uttNBeam[b] = n;
     P.uttFrame[b] = len - 1;
-    P.uttStatus[b] = 0;
+    P.uttStatus[b] = status;
   }
+}
+
+/* ---- the lexicon-free step ------------------------------------------------------------------------------------ */
+/* candidate j of the utterance: row k = j / cap, entry e = j % cap for j < nRows*cap; then the carried hypotheses */
+FLTX_DEV void s2sStepUtterance(const S2sParams& P, char* smem) {
+  S2sStepLds& S = *(S2sStepLds*)smem;
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+  const int K = P.K;
+  const int64_t rb = (int64_t)b * K;
+  if (P.done[b] || P.t >= P.maxOut) { /* a step after the last one: nothing to score */
+    s2sIdleStep(P, b);
+    return;
+  }
+  const int par = P.t & 1;
+  const S2sHyp* prev = P.beam + (size_t)par * P.B * K + rb;
+  S2sHyp* next = P.beam + (size_t)(par ^ 1) * P.B * K + rb;
+  const int nPrev = P.beamN[par * P.B + b];
+  const int nRows = P.nRowsInt[b];
+  const int cap = P.cap;
+  /* 1. rows <-> hypotheses (the live ones in beam order: LexiconFreeSeq2SeqDecoder.cpp:44-55) */
+  s2sMapRows(S, prev, nPrev, P.eos);
+  /* 2. the candidates' keys and the best of the step */
+  unsigned long long* cKey = P.cKey + (size_t)b * P.nC;
+  const int64_t nRowC = (int64_t)nRows * cap, n = nRowC + nPrev;
+  unsigned long long mx = 0ull;
+  for (int64_t j = tid; j < n; j += kS2sStepThreads) {
+    unsigned long long key = 0ull;
+    if (j < nRowC) {
+      const int k = (int)(j / cap), e = (int)(j % cap);
+      const int64_t r = rb + k;
+      if (e < P.recN[r]) {
+        const S2sHyp& h = prev[S.hypOfRow[k]];
+        const int tok = P.recTok[r * cap + e];
+        const float lmS = s2sLm(P, h.ctx, tok, P.eos, nullptr);
+        key = s2sScoreKey(s2sScore(P, h, tok, P.recAm[r * cap + e], lmS));
+      }
+    } else {
+      const S2sHyp& h = prev[j - nRowC];
+      if (h.token == P.eos) { /* a finished hypothesis is carried unchanged (:68-82) */
+        key = s2sScoreKey(h.score);
+      }
+    }
+    cKey[j] = key;
+    mx = key > mx ? key : mx;
+  }
+  /* 3. threshold */
+  const unsigned long long thrKey = s2sThresholdKey(s2sBlockMaxKey(S, mx), P.beamThreshold);
+  int surv = 0;
+  for (int64_t j = tid; j < n; j += kS2sStepThreads) {
+    const unsigned long long key = cKey[j];
+    if (key != 0ull && key < thrKey) {
+      cKey[j] = 0ull;
+    } else if (key != 0ull) {
+      ++surv;
+    }
+  }
+  /* 4. the K best survivors, sorted best first */
+  const int nSel = s2sSelectTopK(S, cKey, n, K, s2sBlockSum(S.wcnt, surv));
+  /* 5. the new beam, its history records and the next call's rows */
+  S2sHyp nh;
+  bool isLive = false;
+  int srcRow = -1, token = -1, parent = -1;
+  if (tid < nSel) {
+    const int64_t j = S.selIdx[S.order[tid]];
+    if (j < nRowC) {
+      const int k = (int)(j / cap), e = (int)(j % cap);
+      const int64_t r = rb + k;
+      const int i = S.hypOfRow[k];
+      const S2sHyp& h = prev[i];
+      const int tok = P.recTok[r * cap + e];
+      const float a = P.recAm[r * cap + e];
+      nh = h;
+      const float lmS = s2sLm(P, h.ctx, tok, P.eos, tok == P.eos ? nullptr : nh.ctx);
+      nh.score = s2sScore(P, h, tok, a, lmS);
+      nh.am = h.am + (double)a;
+      nh.lm = h.lm + (double)lmS;
+      nh.token = tok;
+      nh.parent = i;
+      isLive = tok != P.eos;
+      srcRow = (int)rb + k;
+    } else {
+      const int i = (int)(j - nRowC);
+      nh = prev[i];
+      nh.parent = i;
+    }
+    next[tid] = nh;
+    P.hist[(size_t)(P.t + 1) * P.B * K + rb + tid] = make_int2(nh.token, nh.parent);
+    token = nh.token;
+    parent = nh.parent;
+  }
+  s2sPublishStep(P, S, b, nSel, isLive, token, parent, srcRow);
+}
+
+FLTX_DEV void s2sBeginUtterance(const S2sParams& P, char*) {
+  const int b = (int)(blockIdx.x * kS2sBeginThreads + threadIdx.x);
+  if (b >= P.B) {
+    return;
+  }
+  S2sHyp h;
+  s2sRootHyp(P, h);
+  h.pad = 0;
+  P.beam[(int64_t)b * P.K] = h;
+  s2sBeginReset(P, b);
+}
+
+struct S2sPath { /* a path's records: the tokens row */
+  int32_t* tokens;
+  __device__ __forceinline__ void none(int64_t at) const { tokens[at] = -1; }
+  __device__ __forceinline__ int put(int64_t at, int2 rec) const {
+    tokens[at] = rec.x;
+    return rec.y;
+  }
+};
+
+FLTX_DEV void s2sEndUtterance(const S2sParams& P, char*) {
+  s2sBackTrace(P, P.beam, P.hist, S2sPath{P.tokens}, 0);
 }
 
 } // namespace fltx

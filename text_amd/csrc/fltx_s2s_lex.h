@@ -109,16 +109,6 @@ FLTX_DEV int s2lChild(const S2lTrie& T, int node, int tok) {
   return -1;
 }
 
-/* LM::score over the LM's user ids (words, or tokens when isLmToken); finish when usr < 0 */
-FLTX_DEV float s2lLm(const S2lParams& Q, const int32_t* ctx, int usr, bool finish, int32_t* ctxOut) {
-  if (!Q.s.lmOn) {
-    return 0.0f;
-  }
-  const DecodeParams& L = Q.s.lmp;
-  const uint32_t w = finish ? (uint32_t)L.lmEos : (usr >= 0 && usr < L.nUsr) ? (uint32_t)L.usrToLm[usr] : (uint32_t)L.lmUnk;
-  return ngScore(L, ctx, w, ctxOut);
-}
-
 struct S2lCand {
   double score;
   float am, lmS;
@@ -126,7 +116,7 @@ struct S2lCand {
   int32_t token, word, node, src;
   int32_t newEdge;   /* the state is child(prev.sid, newEdge) when isNew */
   bool isNew;
-  int32_t usr;       /* the LM question that made the state (-2: finish) */
+  int32_t usr;       /* the LM question that made the state (kS2sLmFinish: finish) */
 };
 
 /* candidate j of the utterance: record slot j < nRowC (row k, entry e, sub-slot s: 0 = stay / eos, 1.. = the labels),
@@ -170,13 +160,13 @@ FLTX_DEV bool s2lCand(const S2lParams& Q, const S2lHyp* prev, const int32_t* hyp
     if (s != 0 || h.node != 0) {
       return false;
     }
-    c.lmS = s2lLm(Q, h.ctx, -1, true, nullptr) - 0.0f; /* (lexMaxScore is 0 at the root) */
+    c.lmS = s2sLm(P, h.ctx, kS2sLmFinish, kS2sLmFinish, nullptr) - 0.0f; /* (lexMaxScore is 0 at the root) */
     c.score = (((h.score + (double)a) + P.eosScore) + P.lmWeight * (double)c.lmS);
     c.word = -1;
     c.node = 0;
     c.isNew = P.lmOn != 0;
     c.newEdge = -1;
-    c.usr = -2;
+    c.usr = kS2sLmFinish;
     return true;
   }
   const int child = s2lChild(Q.trie, h.node, tok); /* (2) a normal token: a child of the hypothesis' node */
@@ -186,7 +176,7 @@ FLTX_DEV bool s2lCand(const S2lParams& Q, const S2lHyp* prev, const int32_t* hyp
   const float lexMax = h.node == 0 ? 0.0f : Q.trie.maxScore[h.node];
   if (s == 0) { /* stay in the trie (:146-171) */
     if (Q.isLmToken) {
-      c.lmS = s2lLm(Q, h.ctx, tok, false, nullptr);
+      c.lmS = s2sLm(P, h.ctx, tok, kS2sLmFinish, nullptr);
       c.isNew = true;
       c.newEdge = tok;
       c.usr = tok;
@@ -206,11 +196,11 @@ FLTX_DEV bool s2lCand(const S2lParams& Q, const S2lHyp* prev, const int32_t* hyp
   }
   const int word = Q.trie.labels[l0 + s - 1];
   if (Q.isLmToken) {
-    c.lmS = s2lLm(Q, h.ctx, tok, false, nullptr);
+    c.lmS = s2sLm(P, h.ctx, tok, kS2sLmFinish, nullptr);
     c.newEdge = tok;
     c.usr = tok;
   } else {
-    c.lmS = s2lLm(Q, h.ctx, word, false, nullptr) - lexMax;
+    c.lmS = s2sLm(P, h.ctx, word, kS2sLmFinish, nullptr) - lexMax;
     c.newEdge = word;
     c.usr = word;
   }
@@ -244,16 +234,8 @@ FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) {
   const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
   const int K = P.K;
   const int64_t rb = (int64_t)b * K;
-  const int lane = laneId(), wave = waveId();
   if (P.done[b] || P.t >= P.maxOut) { /* a step after the last one: nothing to score */
-    for (int k = tid; k < K; k += kS2sStepThreads) {
-      P.outTok[rb + k] = -1;
-      P.outBeam[rb + k] = -1;
-      P.outSrc[rb + k] = -1;
-    }
-    if (tid == 0) {
-      P.outN[b] = 0;
-    }
+    s2sIdleStep(P, b);
     return;
   }
   const int par = P.t & 1;
@@ -262,21 +244,10 @@ FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) {
   const int nPrev = P.beamN[par * P.B + b];
   const int nRows = P.nRowsInt[b];
   /* 1. rows <-> hypotheses (the live ones in beam order: :42-52) */
-  {
-    const bool isLive = tid < nPrev && prev[tid].token != P.eos;
-    int tot;
-    const int q = s2sBlockRank(S, isLive, &tot);
-    if (tid < nPrev) {
-      S.rowOfHyp[tid] = isLive ? q : -1;
-      if (isLive) {
-        S.hypOfRow[q] = tid;
-      }
-    }
-    if (tid == 0) {
-      L.full = 0;
-    }
-    __syncthreads();
+  if (tid == 0) {
+    L.full = 0;
   }
+  s2sMapRows(S, prev, nPrev, P.eos);
   /* 2. the candidates: order keys, scores, merge keys; the best of the step */
   const size_t cb = (size_t)b * P.nC;
   unsigned long long* cKey = P.cKey + cb;
@@ -295,28 +266,15 @@ FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) {
     unsigned long long key = 0ull;
     S2lCand c;
     if (s2lCand(Q, prev, S.hypOfRow, rb, nRowC, j, c)) {
-      key = c.score == c.score ? f64Key(c.score + 0.0) : 0ull; /* (+0.0: -0 and +0 compare equal) */
+      key = s2sScoreKey(c.score);
       cScore[j] = c.score;
       cMk[j] = s2lMergeKey(c, prev[c.hyp]);
     }
     cKey[j] = key;
     mx = key > mx ? key : mx;
   }
-  mx = waveMax64(mx);
-  if (lane == 0) {
-    S.wmax[wave] = mx;
-  }
-  __syncthreads();
-  for (int w = 0; w < kS2sStepThreads / 64; ++w) {
-    mx = S.wmax[w] > mx ? S.wmax[w] : mx;
-  }
   /* 3. threshold (candidatesStore step 1: score >= best - beamThreshold) */
-  unsigned long long thrKey = 1ull;
-  if (mx != 0ull) {
-    const double thr = f64FromKey(mx) - P.beamThreshold;
-    thrKey = thr == thr ? f64Key(thr + 0.0) : ~0ull;
-    thrKey = thrKey == 0ull ? 1ull : thrKey;
-  }
+  const unsigned long long thrKey = s2sThresholdKey(s2sBlockMaxKey(S, mx), P.beamThreshold);
   /* 4. merge (step 2): the first survivor of a key to claim its slot heads the group, the others join its list */
   const uint32_t mMask = (uint32_t)Q.mSize - 1u;
   for (int64_t j = tid; j < n; j += kS2sStepThreads) {
@@ -384,7 +342,7 @@ FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) {
       cKey[m] = 0ull;
     }
     cScore[best] = acc;
-    cKey[best] = acc == acc ? f64Key(acc + 0.0) : 0ull;
+    cKey[best] = s2sScoreKey(acc);
   }
   __threadfence();
   int surv = 0;
@@ -392,87 +350,15 @@ FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) {
   for (int64_t j = tid; j < n; j += kS2sStepThreads) {
     surv += cKey[j] != 0ull ? 1 : 0;
   }
-  const int nSurv = s2sBlockSum(S, surv);
-  nMerged = s2sBlockSum(S, nMerged);
-  /* 5. the K best: radix select over the 64-bit keys (as fltx_s2s.h) */
-  unsigned long long pre = 0ull, msk = 0ull;
-  bool all = nSurv <= K, allEq = false;
-  int need = K;
-  int64_t eqCut = -1;
-  for (int shift = 56; shift >= 0 && !all && !allEq; shift -= 8) {
-    __syncthreads();
-    S.hist[tid] = 0u;
-    __syncthreads();
-    for (int64_t j = tid; j < n; j += kS2sStepThreads) {
-      const unsigned long long key = cKey[j];
-      if (key != 0ull && (key & msk) == pre) {
-        atomAdd32(&S.hist[255u - (uint32_t)((key >> shift) & 255ull)], 1u);
-      }
-    }
-    __syncthreads();
-    if (wave == 0) {
-      const SlScan sc = slScan(S.hist, need, false);
-      if (lane == 0) {
-        S.scanBstar = sc.bstar;
-        S.scanCum = sc.cum;
-        S.scanCnt = sc.cnt;
-      }
-    }
-    __syncthreads();
-    need -= S.scanCum;
-    pre |= (unsigned long long)(255 - S.scanBstar) << shift;
-    msk |= 255ull << shift;
-    allEq = S.scanCnt == need;
-  }
-  if (!all && !allEq) { /* equal keys at the cut: the lower candidate indices */
-    int seen = 0;
-    for (int64_t j0 = 0; j0 < n && eqCut < 0; j0 += kS2sStepThreads) {
-      const int64_t j = j0 + tid;
-      const bool eq = j < n && cKey[j] == pre;
-      int tot;
-      const int r = s2sBlockRank(S, eq, &tot);
-      if (eq && seen + r == need - 1) {
-        S.eqCut = j;
-      }
-      __syncthreads();
-      if (seen + tot >= need) {
-        eqCut = S.eqCut;
-      }
-      seen += tot;
-    }
-  }
-  if (tid == 0) {
-    S.nSel = 0;
-  }
-  __syncthreads();
-  for (int64_t j = tid; j < n; j += kS2sStepThreads) {
-    const unsigned long long key = cKey[j];
-    const bool sel = key != 0ull && (all || (key & msk) > pre || ((key & msk) == pre && (allEq || j <= eqCut)));
-    if (sel) {
-      const uint32_t p = atomAdd32((uint32_t*)&S.nSel, 1u);
-      if (p < (uint32_t)K) {
-        S.selIdx[p] = (uint32_t)j;
-        S.selKey[p] = key;
-      }
-    }
-  }
-  __syncthreads();
-  const int nSel = S.nSel < K ? S.nSel : K;
-  if (tid < nSel) {
-    const unsigned long long mk = S.selKey[tid];
-    const uint32_t mi = S.selIdx[tid];
-    int rank = 0;
-    for (int q = 0; q < nSel; ++q) {
-      const unsigned long long ok = S.selKey[q];
-      rank += (ok > mk || (ok == mk && S.selIdx[q] < mi)) ? 1 : 0;
-    }
-    S.order[rank] = tid;
-  }
-  __syncthreads();
+  const int nSurv = s2sBlockSum(S.wcnt, surv);
+  nMerged = s2sBlockSum(S.wcnt, nMerged);
+  /* 5. the K best, sorted best first */
+  const int nSel = s2sSelectTopK(S, cKey, n, K, nSurv);
   /* 6. the new beam; survivors that enter a new state look it up (or insert it) in the utterance's state table */
   S2lHyp nh;
   S2lCand c;
   bool isLive = false, claimed = false, hasNew = false;
+  int token = -1, parent = -1, srcRow = -1;
   uint32_t sslot = 0u;
   unsigned long long skey = 0ull;
   unsigned long long* sKey = Q.sKey + (size_t)b * Q.sSize;
@@ -494,7 +380,7 @@ FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) {
         nh.psid = h.sid;
         nh.edge = c.newEdge;
         if (P.lmOn) {
-          (void)s2lLm(Q, h.ctx, c.usr, c.usr == -2, nh.ctx);
+          (void)s2sLm(P, h.ctx, c.usr, kS2sLmFinish, nh.ctx);
         }
         skey = s2lPair(nh.psid, nh.edge);
         hasNew = true;
@@ -530,14 +416,9 @@ FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) {
   __threadfence();
   __syncthreads();
   if (L.full) { /* the state table is full: the utterance stops, its status says so (never a silent wrong merge) */
-    for (int k = tid; k < K; k += kS2sStepThreads) {
-      P.outTok[rb + k] = -1;
-      P.outBeam[rb + k] = -1;
-      P.outSrc[rb + k] = -1;
-    }
+    s2sIdleStep(P, b);
     if (tid == 0) {
       Q.status[b] |= ST_TABLE_FULL;
-      P.outN[b] = 0;
       P.nRowsInt[b] = 0;
       P.done[b] = 1;
       P.finalStep[b] = P.t;
@@ -557,109 +438,53 @@ FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) {
       rec.pad = 0;
       Q.hist[(size_t)(P.t + 1) * P.B * K + rb + tid] = rec;
     }
-  }
-  int nLive;
-  const int q = s2sBlockRank(S, isLive, &nLive);
-  const bool fin = nSel == 0 || nLive == 0 || P.t + 1 >= P.maxOut;
-  if (fin) {
-    nLive = 0;
-  }
-  if (isLive && !fin) {
-    P.outTok[rb + q] = nh.token;
-    P.outBeam[rb + q] = nh.parent;
-    P.outSrc[rb + q] = c.src;
-  }
-  for (int k = nLive + tid; k < K; k += kS2sStepThreads) {
-    P.outTok[rb + k] = -1;
-    P.outBeam[rb + k] = -1;
-    P.outSrc[rb + k] = -1;
+    token = nh.token;
+    parent = nh.parent;
+    srcRow = c.src;
   }
   if (tid == 0) {
-    P.outN[b] = nLive;
-    P.nRowsInt[b] = nLive;
     Q.merges[b] += nMerged;
-    if (nSel > 0) {
-      P.beamN[(par ^ 1) * P.B + b] = nSel;
-    }
-    if (fin) {
-      P.done[b] = 1;
-      P.finalStep[b] = nSel > 0 ? P.t + 1 : P.t; /* the last non-empty beam (:204-207) */
-    }
   }
+  s2sPublishStep(P, S, b, nSel, isLive, token, parent, srcRow);
 }
 
 /* decodeStep's start (:29-31): the root in LM::start's state (sid 0) at the trie's root */
-FLTX_DEV void s2lBeginUtterance(const S2lParams& Q, int b) {
+FLTX_DEV void s2lBeginUtterance(const S2lParams& Q, char*) {
   const S2sParams& P = Q.s;
-  const int64_t rb = (int64_t)b * P.K;
+  const int b = (int)(blockIdx.x * kS2sBeginThreads + threadIdx.x);
+  if (b >= P.B) {
+    return;
+  }
   S2lHyp h;
-  h.score = 0.0;
-  h.am = 0.0;
-  h.lm = 0.0;
-  h.token = -1;
+  s2sRootHyp(P, h);
   h.word = -1;
-  h.parent = -1;
   h.node = 0;
   h.sid = 0;
   h.psid = -1;
   h.edge = -1;
-  for (int j = 0; j < kS2sCtx; ++j) {
-    h.ctx[j] = P.ctx0[j];
-  }
-  Q.beam[rb] = h;
-  P.beamN[b] = 1;
+  Q.beam[(int64_t)b * P.K] = h;
   Q.sCount[b] = 1;
   Q.status[b] = 0;
   Q.merges[b] = 0;
-  const int live = P.maxOut > 0 ? 1 : 0;
-  P.nRowsInt[b] = live;
-  P.done[b] = live ? 0 : 1;
-  P.finalStep[b] = 0;
-  for (int k = 0; k < P.K; ++k) {
-    P.outTok[rb + k] = -1;
-    P.outBeam[rb + k] = -1;
-    P.outSrc[rb + k] = -1;
-  }
-  P.outN[b] = live;
+  s2sBeginReset(P, b);
 }
 
-/* getAllFinalHypothesis (:209-211, Utils.h:230-266): tokens and words of the final beam's paths, right-aligned in
- * rows of maxOutputLength + 3 with -1 in front */
-FLTX_DEV void s2lEndUtterance(const S2lParams& Q, int b, int tid, int nThreads) {
-  const S2sParams& P = Q.s;
-  const int K = P.K;
-  const int64_t rb = (int64_t)b * K;
-  const int fs = P.done[b] ? P.finalStep[b] : P.t;
-  const int par = fs & 1;
-  const int n = P.beamN[par * P.B + b];
-  const S2lHyp* beam = Q.beam + (size_t)par * P.B * K + rb;
-  const int len = P.len;
-  for (int k = tid; k < n; k += nThreads) {
-    const S2lHyp& h = beam[k];
-    double* sc = P.outScores + (rb + k) * 3;
-    sc[0] = h.score;
-    sc[1] = h.am;
-    sc[2] = h.lm;
-    int32_t* out = P.tokens + (rb + k) * len;
-    int32_t* wout = Q.words + (rb + k) * len;
-    for (int f = 0; f < len - fs; ++f) {
-      out[f] = -1;
-      wout[f] = -1;
-    }
-    int p = k;
-    for (int s = fs; s >= 1; --s) {
-      const S2lRec rec = Q.hist[(size_t)s * P.B * K + rb + p];
-      out[len - 1 - (fs - s)] = rec.token;
-      wout[len - 1 - (fs - s)] = rec.word;
-      p = rec.parent;
-    }
+struct S2lPath { /* a path's records: the tokens row and the words row */
+  int32_t *tokens, *words;
+  __device__ __forceinline__ void none(int64_t at) const {
+    tokens[at] = -1;
+    words[at] = -1;
   }
-  if (tid == 0) {
-    P.outNHyp[b] = n;
-    P.uttNBeam[b] = n;
-    P.uttFrame[b] = len - 1;
-    P.uttStatus[b] = Q.status[b];
+  __device__ __forceinline__ int put(int64_t at, S2lRec rec) const {
+    tokens[at] = rec.token;
+    words[at] = rec.word;
+    return rec.parent;
   }
+};
+
+/* getAllFinalHypothesis (:209-211, Utils.h:230-266): tokens and words of the final beam's paths */
+FLTX_DEV void s2lEndUtterance(const S2lParams& Q, char*) {
+  s2sBackTrace(Q.s, Q.beam, Q.hist, S2lPath{Q.s.tokens, Q.words}, Q.status[blockIdx.x]);
 }
 
 } // namespace fltx
