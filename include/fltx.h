@@ -473,7 +473,10 @@ FLTX_API int fltx_decoder_profile(fltx_decoder* dec, uint64_t* out);
  * "stream_defer" (0 = fltx_stream_step of a lexicon stream waits for its chunk; default: the chunk is launched and whether
  * a stream has to decode it again is looked at by the next call that needs the beam -- the next chunk's upload runs
  * under the kernel; a deferred fltx_stream_prune reports its errors there too), "lm_cache" (0 = the generic step asks
- * the n-gram tables for every word-end candidate instead of keeping the last (LM state, word) answers), "bt_lds_kb".  fltx_decoder_get also answers "engine", "redone", "stream_redone", "yshare", "sstream". */
+ * the n-gram tables for every word-end candidate instead of keeping the last (LM state, word) answers), "bt_lds_kb".  fltx_decoder_get also answers "engine", "redone", "stream_redone", "yshare", "sstream",
+ * "bt_record_bytes" (the last back-trace: 2 or 4 = it narrowed the lane engines' packed history records to that many
+ * bytes and kept the utterance's token tile in LDS; 0 = the chunked back-trace of plain 8-byte records),
+ * "bt_chunk_frames" / "bt_stretch_frames" (frames per LDS chunk of history records / of emission rows in it). */
 /* Round 5: "defer_check" (1 = fltx_decode_batch returns as soon as its kernels are queued.  By default the call waits
  * for the decode kernel when the batch ran on a fast path that may flag an utterance, decodes the flagged ones again
  * and only then queues the back-trace -- every read of a device buffer is then queued before the call returns.  With

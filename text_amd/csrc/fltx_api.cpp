@@ -106,6 +106,12 @@ __global__ void __launch_bounds__(512) fltx_backtrace_kernel(BacktraceParams P) 
   extern __shared__ __attribute__((aligned(16))) char fltx_bt_smem[];
   backtraceUtterance(P, fltx_bt_smem);
 }
+/* packed records narrowed into LDS, the token tile resident (backtraceNarrow): 8 + 8 and 16 + 16 bits */
+template <typename RT>
+__global__ void __launch_bounds__(512) fltx_backtrace_narrow_kernel(BacktraceParams P) {
+  extern __shared__ __attribute__((aligned(16))) char fltx_btn_smem[];
+  backtraceNarrow<RT>(P, fltx_btn_smem);
+}
 __global__ void __launch_bounds__(64) fltx_snapshot_kernel(SnapParams Q) {
   const int b = Q.map ? Q.map[blockIdx.x] : (int)blockIdx.x;
   snapUtterance(Q, b, (int)threadIdx.x, 64);
@@ -276,6 +282,59 @@ struct HBuf {
     cap = 0;
   }
   ~HBuf() { release(); }
+};
+
+/* PINNED staging of a small upload that must not stall its stream: the host writes it, an asynchronous copy reads it,
+ * and it is rewritten only when that copy has completed (an event of its own: queried, waited for only if it has not
+ * fired -- after a settled batch it always has) */
+struct Staging {
+  HBuf h;
+#ifndef FLTX_EMU
+  hipEvent_t done = nullptr;
+  bool inFlight = false;
+  ~Staging() {
+    if (done) {
+      (void)hipEventDestroy(done);
+    }
+  }
+#endif
+  void* acquire(size_t n) { /* null: failed */
+#ifndef FLTX_EMU
+    if (inFlight) {
+      if (hipEventQuery(done) != hipSuccess) {
+        (void)hipGetLastError(); /* ("not ready" is no error of the launch that follows) */
+        if (hipEventSynchronize(done) != hipSuccess) {
+          return nullptr;
+        }
+      }
+      inFlight = false;
+    }
+#endif
+    return h.ensure(n) ? nullptr : h.p;
+  }
+  int sent(Stream s) { /* the copy that reads the staging has been queued on s */
+#ifndef FLTX_EMU
+    if (!done && hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) {
+      return 1;
+    }
+    if (hipEventRecord(done, s) != hipSuccess) {
+      return 1;
+    }
+    inFlight = true;
+#else
+    (void)s;
+#endif
+    return 0;
+  }
+};
+
+/* a part of a device buffer */
+struct DView {
+  void* p = nullptr;
+  template <class T>
+  T* as() const {
+    return (T*)p;
+  }
 };
 
 /* growable device buffer */
@@ -504,6 +563,7 @@ struct fltx_decoder {
   const fltx_lm* xlmwordLm = nullptr;
   int ylane = 0, noYlane = 0, ylaneLm = 0, ylaneRounds = 0, ylaneTpw = 0; /* ylane: lane groups of fltx_ylane.h (0 = not used) */
   int btLdsKb = 0;
+  int btNarrow = 0, btChunk = 0, btStretch = 0; /* fltx_decoder_get "bt_record_bytes", "bt_chunk_frames", "bt_stretch_frames" */
   int streamTotalFrames = 0; /* frames a stream will decode in all (sizes its LM-state id tables), 0 = default */
   /* stream chunks of the lexicon-free decoder on the lane = LM state engine (fltx_slane.h, ST): list positions per
    * token wave (0 = not used) and threads; begin / end / prune / best stay the lane-per-slot engine's */
@@ -547,10 +607,19 @@ struct fltx_decoder {
   DBuf emis[2], emOff[2], stepT[2];
   int upSlot = 0;
   DBuf histOffD, histPT, histW, stateTab, stateCtx;
+  std::vector<int64_t> histOffSent; /* what histOffD holds ... */
+  const void* histOffSentTo = nullptr; /* ... in this allocation (uploadHistOff) */
+  Staging histOffStage, descStage[2]; /* pinned: histOff; the offsets and T of an upload slot */
+  const void* ldsRaisedFn[2] = {nullptr, nullptr}; /* decode / back-trace kernel whose LDS limit this decoder last raised ... */
+  size_t ldsRaisedTo[2] = {0, 0};                  /* ... and to what (raiseMaxLdsOnce) */
   DBuf tokRowsBuf; /* fltx_wlane.h: the token beams of all rows (fltx_tokbeam_kernel) */
   int wlMaxT = 0;  /* ... longest utterance of the call (the front-end kernel's grid) */
   DBuf gScore, gAm, gLm, gState, gSPar, gSEdge, gLex, gTokPb;
-  DBuf uttNBeam, uttFrame, uttTotal, uttStatus, outN, outScores, gws;
+  DBuf uttRes;   /* rows of uttRow int32: beam count, final frame, status per utterance -- one allocation, so that
+                    syncResults brings the three home in one copy (ensureUttRes) */
+  size_t uttRow = 0;
+  DView uttNBeam, uttFrame, uttStatus;
+  DBuf uttTotal, outN, outScores, gws;
   DBuf childTab, maskTab, uttNextId, gMask, gLexMax;
   /* streams: recycled LM-state ids (DecodeParams::idPar ...) */
   DBuf idPar, idEdge, idBorn, idKeep, idNew, idList, stateVal;
@@ -1613,6 +1682,13 @@ int fltx_decoder_get(fltx_decoder* d, const char* key, int64_t* value) {
     *value = d->tokLmCtx;
   } else if (!strcmp(key, "fallback_reasons")) {
     *value = d->fallbackReasons;
+  } else if (!strcmp(key, "bt_record_bytes")) { /* the last back-trace: 2 / 4 = packed records narrowed to that width with the
+                                                    token tile resident in LDS (backtraceNarrow), 0 = backtraceUtterance */
+    *value = d->btNarrow;
+  } else if (!strcmp(key, "bt_chunk_frames")) { /* ... frames per chunk of history records in LDS (0: none, walked through HBM) */
+    *value = d->btChunk;
+  } else if (!strcmp(key, "bt_stretch_frames")) { /* ... frames per stretch of emission rows in LDS while the scores are re-added */
+    *value = d->btStretch;
   } else if (!strcmp(key, "why_not_lane")) { /* FLTX_WHY_* (include/fltx.h): why the last call did not start on a lane engine */
     *value = d->whyFirst;
   } else if (!strcmp(key, "lane_groups")) { /* lane groups of the lane = LM state engine: 1 = fltx_slane.h, 2 / 4 / 8 = fltx_mlane.h;
@@ -1855,6 +1931,43 @@ void latchFirst(fltx_decoder* d) {
   d->xlaneFirst = d->xlane;
   d->ylaneFirst = d->ylane;
   d->laneGroupsFirst = d->slane ? std::max(1, d->mlaneNG) : d->ylane;
+}
+
+/* the per-utterance results a look reads (beam count, final frame, status): three rows of one allocation */
+int ensureUttRes(fltx_decoder* d, int B, Stream st) {
+  if ((size_t)B > d->uttRow || !d->uttRes.p) {
+    const size_t row = ((size_t)B + (size_t)B / 8 + 3) & ~(size_t)3;
+    bool grew = false;
+    if (d->uttRes.ensure(12 * row, st, true, &grew) || (!grew && devMemset(d->uttRes.p, 0, 12 * row, st))) {
+      return 1; /* (rows that move start zeroed, as a fresh allocation does) */
+    }
+    d->uttRow = row;
+    d->uttNBeam.p = d->uttRes.p;
+    d->uttFrame.p = d->uttRes.as<int32_t>() + row;
+    d->uttStatus.p = d->uttRes.as<int32_t>() + 2 * row;
+  }
+  return 0;
+}
+
+/* histOff is a function of (T[], K) alone: it travels only when it differs from what histOffD already holds, and then
+ * through pinned staging (no pageable copy on the launch stream) */
+int uploadHistOff(fltx_decoder* d, Stream st) {
+  if (d->histOffSentTo == d->histOffD.p && d->histOffSent == d->histOff) {
+    return 0;
+  }
+  const size_t n = sizeof(int64_t) * d->histOff.size();
+  void* h = d->histOffStage.acquire(n);
+  if (!h) {
+    return 1;
+  }
+  memcpy(h, d->histOff.data(), n);
+  d->histOffSentTo = nullptr;
+  if (devCopyH2D(d->histOffD.p, h, n, st) || d->histOffStage.sent(st)) {
+    return 1;
+  }
+  d->histOffSent = d->histOff;
+  d->histOffSentTo = d->histOffD.p;
+  return 0;
 }
 
 int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstCaseCap) {
@@ -2496,8 +2609,8 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
   rc |= d->gScore.ensure(8 * bk, st, false) | d->gAm.ensure(8 * bk, st, false) | d->gLm.ensure(8 * bk, st, false);
   rc |= d->gState.ensure(4 * bk, st, false) | d->gSPar.ensure(4 * bk, st, false) | d->gSEdge.ensure(4 * bk, st, false);
   rc |= d->gLex.ensure(4 * bk, st, false) | d->gTokPb.ensure(4 * bk, st, false) | d->gLexMax.ensure(4 * bk, st, false);
-  rc |= d->uttNBeam.ensure(4 * (size_t)B, st, true) | d->uttFrame.ensure(4 * (size_t)B, st, true);
-  rc |= d->uttTotal.ensure(4 * (size_t)B, st, true) | d->uttStatus.ensure(4 * (size_t)B, st, true);
+  rc |= ensureUttRes(d, B, st);
+  rc |= d->uttTotal.ensure(4 * (size_t)B, st, true);
   rc |= d->outN.ensure(4 * (size_t)B, st, true) | d->outScores.ensure(8 * bk * 3, st, false);
   for (int u = 0; u < 2; ++u) {
     rc |= d->emOff[u].ensure(sizeof(int64_t) * (size_t)B, st, false) | d->stepT[u].ensure(4 * (size_t)B, st, false);
@@ -2550,7 +2663,7 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
   if (rc) {
     return fail(FLTX_ERR_OOM, "device allocation failed (B=%d K=%d T<=%d)", B, K, maxT);
   }
-  if (devCopyH2D(d->histOffD.p, d->histOff.data(), sizeof(int64_t) * (B + 1), st)) {
+  if (uploadHistOff(d, st)) {
     return fail(FLTX_ERR_HIP, "upload failed");
   }
   return FLTX_OK;
@@ -2827,6 +2940,19 @@ int raiseMaxLds(int device, const void* fn, size_t bytes) {
   }
   return FLTX_OK;
 }
+/* ... and per decoder object nothing at all while it launches the same kernel within what it last asked for (which: 0 the
+ * decode kernel, 1 the back-trace) */
+int raiseMaxLdsOnce(fltx_decoder* d, int which, const void* fn, size_t bytes) {
+  if (d->ldsRaisedFn[which] == fn && bytes <= d->ldsRaisedTo[which]) {
+    return FLTX_OK;
+  }
+  int rc = raiseMaxLds(d->ctx->device, fn, bytes);
+  if (!rc) {
+    d->ldsRaisedFn[which] = fn;
+    d->ldsRaisedTo[which] = bytes;
+  }
+  return rc;
+}
 #endif
 
 int launchDecode(fltx_decoder* d, const DecodeParams& P) {
@@ -2866,7 +2992,7 @@ int launchDecode(fltx_decoder* d, const DecodeParams& P) {
   const bool defaultLimit = key.fam == kSlane || key.fam == kSstream || key.fam == kTstream ||
                             (key.fam == kGeneric && !d->wsInLds && d->lean);
   int rc;
-  if (!defaultLimit && (rc = raiseMaxLds(d->ctx->device, fn, lds))) {
+  if (!defaultLimit && (rc = raiseMaxLdsOnce(d, 0, fn, lds))) {
     return rc;
   }
   void* args[] = {(void*)&P};
@@ -2898,14 +3024,12 @@ int uploadStep(fltx_decoder* d, const float* emissions, int onDevice, const int6
                const int32_t* T, DecodeParams& P) {
   Stream st = d->ctx->stream;
   const int B = d->B, N = d->N;
-  std::vector<int64_t> offs(B, 0);
   int64_t maxEnd = 0;
   for (int b = 0; b < B; ++b) {
-    offs[b] = offsets ? offsets[b] : 0;
-    if (offs[b] < 0) {
+    if (offsets && offsets[b] < 0) {
       return fail(FLTX_ERR_INVALID, "offsets[%d] is negative", b);
     }
-    maxEnd = std::max<int64_t>(maxEnd, offs[b] + (int64_t)T[b] * N);
+    maxEnd = std::max<int64_t>(maxEnd, (offsets ? offsets[b] : 0) + (int64_t)T[b] * N);
   }
   if (maxEnd > 0 && !emissions) {
     return fail(FLTX_ERR_INVALID, "emissions is null");
@@ -2947,17 +3071,29 @@ int uploadStep(fltx_decoder* d, const float* emissions, int onDevice, const int6
     P.emissions = d->emis[slot].as<float>();
   }
   d->lastEmis = P.emissions;
-  if (devCopyH2D(d->emOff[slot].p, offs.data(), sizeof(int64_t) * B, cs) ||
-      devCopyH2D(d->stepT[slot].p, T, sizeof(int32_t) * B, cs)) {
+  /* the batch descriptors go through the slot's pinned staging: the copies are asynchronous for real, and nothing
+   * of this call has to outlive it */
+  int64_t* offs = (int64_t*)d->descStage[slot].acquire(12 * (size_t)B);
+  if (!offs) {
+    return fail(FLTX_ERR_HIP, "batch descriptor staging failed");
+  }
+  int32_t* stT = (int32_t*)(offs + B);
+  for (int b = 0; b < B; ++b) {
+    offs[b] = offsets ? offsets[b] : 0;
+    stT[b] = T[b];
+  }
+  if (devCopyH2D(d->emOff[slot].p, offs, sizeof(int64_t) * B, cs) ||
+      devCopyH2D(d->stepT[slot].p, stT, sizeof(int32_t) * B, cs) || d->descStage[slot].sent(cs)) {
     return fail(FLTX_ERR_HIP, "batch descriptor upload failed");
   }
   d->upSlot = slot;
   P.emOff = d->emOff[slot].as<int64_t>();
   P.stepT = d->stepT[slot].as<int32_t>();
 #ifndef FLTX_EMU
-  /* the H2D copies above read pageable host memory that only lives for this call (offs); when the copy stream is
-   * drained they have been consumed -- and are in place for the launch that follows on the other stream */
-  if (devSync(cs)) {
+  /* A stream chunk's copies run on the copy stream: when it is drained they are in place for the launch that follows
+   * on the other stream.  An offline batch uploads on its launch stream, which orders them before the kernel: it waits
+   * only where the caller's own (pageable) emissions have to be consumed before the call returns. */
+  if ((!d->offlineCall || (!onDevice && maxEnd > 0)) && devSync(cs)) {
     return fail(FLTX_ERR_HIP, "stream synchronize failed");
   }
 #endif
@@ -2992,29 +3128,18 @@ int syncResults(fltx_decoder* d) {
   d->hN.resize(B);
   d->hFrame.resize(B);
   d->hStatus.resize(B);
-#ifdef FLTX_EMU
-  if (devCopyD2H(d->hN.data(), d->uttNBeam.p, 4 * (size_t)B, st) ||
-      devCopyD2H(d->hFrame.data(), d->uttFrame.p, 4 * (size_t)B, st) ||
-      devCopyD2H(d->hStatus.data(), d->uttStatus.p, 4 * (size_t)B, st)) {
-    return fail(FLTX_ERR_HIP, "result copy failed: %s", devErr());
-  }
-#else
-  /* three small arrays, one wait: pinned staging, the copies queued back to back (a stream chunk pays this
-   * after every step and every prune) */
-  if (d->hSync.ensure(12 * (size_t)B)) {
+  /* the three rows share an allocation (ensureUttRes): one copy into pinned staging, one wait */
+  const size_t row = d->uttRow;
+  if (d->hSync.ensure(4 * (2 * row + (size_t)B))) {
     return fail(FLTX_ERR_OOM, "pinned staging allocation failed");
   }
-  int32_t* h = (int32_t*)d->hSync.p;
-  if (hipMemcpyAsync(h, d->uttNBeam.p, 4 * (size_t)B, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(h + B, d->uttFrame.p, 4 * (size_t)B, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(h + 2 * B, d->uttStatus.p, 4 * (size_t)B, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
+  const int32_t* h = (const int32_t*)d->hSync.p;
+  if (devCopyD2H(d->hSync.p, d->uttRes.p, 4 * (2 * row + (size_t)B), st)) {
     return fail(FLTX_ERR_HIP, "result copy failed: %s", devErr());
   }
   memcpy(d->hN.data(), h, 4 * (size_t)B);
-  memcpy(d->hFrame.data(), h + B, 4 * (size_t)B);
-  memcpy(d->hStatus.data(), h + 2 * B, 4 * (size_t)B);
-#endif
+  memcpy(d->hFrame.data(), h + row, 4 * (size_t)B);
+  memcpy(d->hStatus.data(), h + 2 * row, 4 * (size_t)B);
   d->resultsSynced = true;
   return FLTX_OK;
 }
@@ -3091,13 +3216,58 @@ int launchBacktrace(fltx_decoder* d) {
                                     : 4 * ((size_t)F * d->N + (Q.transitions ? (size_t)d->N * d->N : 0) + (size_t)Q.K * F) + 16;
     btLds = std::max(btLds, amLds);
   }
+  /* Packed records in one residency (backtraceNarrow): the batch's longest token tile at the narrow width, and behind
+   * it, within the same budget, double-buffered chunks of narrowed records (walk) and then of emission rows (score).
+   * 8 + 8 bits when slots and tokens both fit a byte beside the all-ones "none", 16 + 16 otherwise.  A budget that
+   * holds no tile with chunks of 8 frames keeps backtraceUtterance (long utterances, big beams). */
+  int narrow = 0; /* bytes of a narrowed record: 2, 4, or 0 = backtraceUtterance */
+  if (d->batchPacked && F > 0 && Q.K <= btThreads) {
+    const bool byteRec = d->packedBits <= 8 && Q.packedTokMask == 0xFF && d->N <= 255;
+    const bool wordRec = d->packedBits <= 16 && d->N <= 65535;
+    const size_t rec = byteRec ? 2 : 4, tokB = rec / 2;
+    size_t row = 0;
+    for (int b = 0; b < d->B; ++b) {
+      row = std::max<size_t>(row, (size_t)((d->histOff[b + 1] - d->histOff[b]) / Q.K));
+    }
+    const bool lexRec = d->kind == FLTX_DECODER_LEXICON;
+    const size_t tile = ((size_t)Q.K * row * tokB + 15) & ~(size_t)15;
+    const size_t room = btBudget > tile + 16 ? btBudget - tile - 16 : 0;
+    const size_t perWalk = (size_t)Q.K * (2 * rec + (lexRec ? 2 * 4 + 4 : 0));
+    const size_t trBytes = (Q.transitions && !Q.amGather) ? 4 * (size_t)d->N * d->N : 0;
+    const size_t perEm = 2 * 4 * (size_t)d->N;
+    const size_t npF = std::min<size_t>(room / perWalk, std::max<size_t>(row, 8));
+    const size_t npFe = Q.amGather ? (size_t)1 << 20 : (room > trBytes ? std::min<size_t>((room - trBytes) / perEm, std::max<size_t>(row, 8)) : 0);
+    if ((byteRec || wordRec) && row > 0 && row < (1u << 24) && npF >= 8 && npFe >= 8) {
+      narrow = (int)rec;
+      Q.npRow = (int32_t)row;
+      Q.npF = (int32_t)npF;
+      Q.npFe = (int32_t)npFe;
+      Q.npScratch = (int32_t)tile;
+      btLds = std::max(btLds, tile + std::max(npF * perWalk, Q.amGather ? (size_t)0 : trBytes + npFe * perEm) + 16);
+    }
+  }
+  d->btNarrow = narrow;
+  d->btChunk = narrow ? Q.npF : F;
+  d->btStretch = narrow ? (Q.amGather ? 0 : Q.npFe) : (d->batchPacked && !Q.amGather ? F : 0);
 #ifdef FLTX_EMU
   const BacktraceParams* qq = &Q;
-  emuLaunch(d->B, btThreads, btLds, [qq](char* smem) { backtraceUtterance(*qq, smem); });
+  if (narrow == 2) {
+    emuLaunch(d->B, btThreads, btLds, [qq](char* smem) { backtraceNarrow<uint16_t>(*qq, smem); });
+  } else if (narrow == 4) {
+    emuLaunch(d->B, btThreads, btLds, [qq](char* smem) { backtraceNarrow<uint32_t>(*qq, smem); });
+  } else {
+    emuLaunch(d->B, btThreads, btLds, [qq](char* smem) { backtraceUtterance(*qq, smem); });
+  }
 #else
-  HIPCHK(hipFuncSetAttribute((const void*)fltx_backtrace_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)btLds));
-  hipLaunchKernelGGL(fltx_backtrace_kernel, dim3(d->B), dim3(btThreads), btLds, st, Q);
+  const void* btFn = narrow == 2   ? (const void*)fltx_backtrace_narrow_kernel<uint16_t>
+                     : narrow == 4 ? (const void*)fltx_backtrace_narrow_kernel<uint32_t>
+                                   : (const void*)fltx_backtrace_kernel;
+  int rcLds = raiseMaxLdsOnce(d, 1, btFn, btLds);
+  if (rcLds) {
+    return rcLds;
+  }
+  void* btArgs[] = {(void*)&Q};
+  HIPCHK(hipLaunchKernel(btFn, dim3(d->B), dim3(btThreads), btArgs, btLds, st));
   HIPCHK(hipGetLastError());
   if (d->ev[2]) {
     HIPCHK(hipEventRecord(d->ev[2], st));
@@ -5261,12 +5431,11 @@ int fltx_s2s_end(fltx_decoder* d) {
   }
   d->histRecords = (int64_t)B * K * len;
   if (d->outScores.ensure(24 * (size_t)B * K, st, false) || d->tokens.ensure(4 * (size_t)d->histRecords, st, false) ||
-      d->outN.ensure(4 * (size_t)B, st, false) || d->uttNBeam.ensure(4 * (size_t)B, st, false) ||
-      d->uttFrame.ensure(4 * (size_t)B, st, false) || d->uttStatus.ensure(4 * (size_t)B, st, false) ||
+      d->outN.ensure(4 * (size_t)B, st, false) || ensureUttRes(d, B, st) ||
       d->histOffD.ensure(8 * ((size_t)B + 1), st, false)) {
     return fail(FLTX_ERR_OOM, "seq2seq results: device allocation failed");
   }
-  if (devCopyH2D(d->histOffD.p, d->histOff.data(), 8 * ((size_t)B + 1), st)) {
+  if (uploadHistOff(d, st)) {
     return fail(FLTX_ERR_HIP, "seq2seq results: upload failed");
   }
   const bool lex = d->kind == FLTX_DECODER_S2S_LEXICON;

@@ -3646,6 +3646,11 @@ struct BacktraceParams {
   const int2* tokLm;     /* DecodeParams::tokLm, or null */
   int32_t tokLmStride;
   int32_t blank;         /* CTC: the blank token; ASG: -1 */
+  /* backtraceNarrow (packed records, the token tile resident in LDS): 0 = not in use */
+  int32_t npRow;         /* elements per tile row: no utterance of the batch has more history rows */
+  int32_t npF;           /* frames per narrowed record chunk */
+  int32_t npFe;          /* frames per stretch of emission rows */
+  int32_t npScratch;     /* byte offset of the chunks behind the tile */
 };
 
 /* A parent-pointer walk is a chain of T dependent loads; straight from HBM that
@@ -3918,6 +3923,283 @@ FLTX_DEV void backtraceUtterance(const BacktraceParams& P, char* smem) {
     }
   }
 }
+/* The back-trace of PACKED records in one residency (all lane engines).  A packed record is {parent slot, token}
+ * in a few bits each, so it is narrowed on the way into LDS -- RT = uint16_t: 8 + 8 bits (fltx_slane.h,
+ * fltx_xlane.h, fltx_ylane.h), uint32_t: 16 + 16 (fltx_mlane.h's 10-bit and fltx_ylane.h's 13-bit slots,
+ * fltx_wlane.h's tokens); all ones = no parent / a pruned row -- and the utterance's whole token tile
+ * [hypothesis][frame] stays in LDS at the narrow width next to the chunks:
+ *   walk   newest frame first, npF frames per chunk, double buffered: the walker waves follow the parent slots of
+ *          chunk c and drop the tokens into the tile while the other waves narrow chunk c + 1 into the other buffer;
+ *   store  the tile leaves as row-contiguous int32 stores, widened;
+ *   score  oldest frame first out of the SAME tile (the token rows are never read back from HBM), in the order and
+ *          arithmetic of backtraceUtterance; the emission rows of stretch c + 1 (npFe frames) arrive through the
+ *          idle waves while stretch c is added, so no stretch begins with an exposed round trip.
+ * The host picks the variant and checks that tile + chunks fit the budget (launchBacktrace); an utterance with plain
+ * records (decoded again on the generic engine), or longer than the tile's rows, takes backtraceUtterance. */
+template <typename RT>
+struct BtNarrow;
+template <>
+struct BtNarrow<uint16_t> {
+  typedef uint8_t Tok;
+};
+template <>
+struct BtNarrow<uint32_t> {
+  typedef uint16_t Tok;
+};
+
+template <typename RT>
+FLTX_DEV void backtraceNarrow(const BacktraceParams& P, char* smem) {
+  typedef typename BtNarrow<RT>::Tok TT;
+  constexpr int HB = (int)sizeof(RT) * 4;    /* bits of each half */
+  constexpr uint32_t NONE = (1u << HB) - 1u; /* no parent; a pruned row's token */
+  const int b = (int)blockIdx.x;
+  const int ff = P.uttFrame[b];
+  const int len = ff + 1;
+  const int L = P.npRow;
+  if (!(P.uttStatus[b] & ST_PACKED) || len > L) {
+    backtraceUtterance(P, smem);
+    return;
+  }
+  const int W = (int)blockDim.x, tid = (int)threadIdx.x;
+  int nh = P.uttNBeam[b];
+  if (P.nbest > 0 && nh > P.nbest) {
+    nh = P.nbest;
+  }
+  const int K = P.K;
+  const bool lex = P.kind == 1;
+  const int pmask = (1 << P.packed) - 1;
+  const int64_t hb = P.histOff[b], ob = P.tokOff[b];
+  const int F = P.npF;
+  TT* tile = (TT*)smem;                                  /* [K][L] */
+  char* scr = smem + P.npScratch;
+  RT* cR0 = (RT*)scr;                                    /* [2][F][K] */
+  int32_t* cW0 = (int32_t*)(cR0 + (size_t)2 * F * K);    /* [2][F][K] (lexicon decoder) */
+  int32_t* oW = cW0 + (lex ? (size_t)2 * F * K : 0);     /* [nh][F]   (lexicon decoder) */
+  auto tokOf = [&](int k, int j) {
+    const uint32_t t = tile[(size_t)k * L + j];
+    return t == NONE ? -1 : (int)t;
+  };
+  int slot[4]; /* hypotheses tid, tid + W, ... (nh <= 4 W is checked by the host) */
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    slot[q] = tid + q * W;
+  }
+  const int wThreads = nh >= W ? W : ((nh + 63) >> 6) << 6; /* whole waves that walk */
+  const int mThreads = W - wThreads;                         /* threads free to copy meanwhile */
+  auto copyChunk = [&](int hi, int buf, int t0, int step) {
+    const int lo = hi - F + 1 > 0 ? hi - F + 1 : 0;
+    const int n = (hi - lo + 1) * K;
+    const int64_t src = hb + (int64_t)lo * K;
+    RT* cR = cR0 + (size_t)buf * F * K;
+    int32_t* cW = cW0 + (size_t)buf * F * K;
+    for (int base = t0; base < n; base += 8 * step) { /* eight loads in flight per thread before the first LDS store */
+      int2 v[8];
+      int32_t wv[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = base + u * step;
+        if (i < n) {
+          v[u] = P.histPT[src + i];
+          wv[u] = lex ? P.histW[src + i] : -1;
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = base + u * step;
+        if (i < n) {
+          const uint32_t par = (v[u].x & pmask) == pmask ? NONE : (uint32_t)(v[u].x & pmask);
+          const uint32_t tk = v[u].y < 0 ? NONE : (uint32_t)(v[u].y & P.packedTokMask);
+          cR[i] = (RT)(par | (tk << HB));
+          if (lex) {
+            cW[i] = wv[u];
+          }
+        }
+      }
+    }
+  };
+  copyChunk(ff, 0, tid, W);
+  __syncthreads();
+  int c = 0;
+  for (int hi = ff; hi >= 0; hi -= F, ++c) {
+    const int lo = hi - F + 1 > 0 ? hi - F + 1 : 0;
+    const int nf = hi - lo + 1;
+    const RT* cR = cR0 + (size_t)(c & 1) * F * K;
+    const int32_t* cW = cW0 + (size_t)(c & 1) * F * K;
+    const bool more = lo > 0;
+    if (tid < wThreads) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int k = tid + q * W;
+        if (k < nh) {
+          int s = slot[q];
+          TT* row = tile + (size_t)k * L + lo;
+          for (int j = nf - 1; j >= 0; --j) {
+            uint32_t tokv = NONE;
+            int wv = -1;
+            if (s >= 0) {
+              const uint32_t r = cR[j * K + s];
+              tokv = r >> HB;
+              wv = lex ? cW[j * K + s] : -1;
+              const uint32_t par = r & NONE;
+              s = par == NONE ? -1 : (int)par;
+            }
+            row[j] = (TT)tokv;
+            if (P.words) {
+              oW[k * F + j] = wv;
+            }
+          }
+          slot[q] = s;
+        }
+      }
+    } else if (more) {
+      copyChunk(lo - 1, (c + 1) & 1, tid - wThreads, mThreads);
+    }
+    if (more && mThreads == 0) { /* every thread walks: copy afterwards */
+      copyChunk(lo - 1, (c + 1) & 1, tid, W);
+    }
+    __syncthreads();
+    if (P.words) { /* (uniform) the word tile of the chunk: a wave per row, contiguous stores */
+      for (int k = tid >> 6; k < nh; k += W >> 6) {
+        for (int j = tid & 63; j < nf; j += 64) {
+          P.words[ob + (int64_t)k * len + lo + j] = oW[k * F + j];
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int k = tid >> 6; k < nh; k += W >> 6) { /* the token rows, widened: a wave per row */
+    for (int j = tid & 63; j < len; j += 64) {
+      P.tokens[ob + (int64_t)k * len + j] = tokOf(k, j);
+    }
+  }
+  if (!P.amOut) {
+    return;
+  }
+  /* emitting-model (and token-LM) scores, oldest frame first, the tokens from the tile */
+  const int N = P.N;
+  const int Fe = P.npFe;
+  float* trT = (float*)scr;                                                                     /* [N][N] (ASG) */
+  float* eT0 = trT + ((P.transitions && !P.amGather) ? (size_t)N * N : 0);                      /* [2][Fe][N] */
+  const float* em = P.emissions + P.emOff[b];
+  const float* const trG = P.amGather ? P.transitions : trT;
+  const int Tb = ff - 1; /* frames decoded: history rows 1 .. Tb */
+  const int aThreads = nh >= W ? W : ((nh + 63) >> 6) << 6; /* whole waves that add (one hypothesis per thread) */
+  const int fThreads = W - aThreads;
+  auto fetch = [&](int lo, int buf, int t0, int step) { /* emission rows lo - 1 .. of a stretch: contiguous */
+    const int hi = lo + Fe - 1 < Tb ? lo + Fe - 1 : Tb;
+    const int nEm = P.amGather ? 0 : (hi - lo + 1) * N;
+    float* eT = eT0 + (size_t)buf * Fe * N;
+    for (int base = t0; base < nEm; base += 8 * step) {
+      float v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = base + u * step;
+        v[u] = i < nEm ? em[(size_t)(lo - 1) * N + i] : 0.0f;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = base + u * step;
+        if (i < nEm) {
+          eT[i] = v[u];
+        }
+      }
+    }
+  };
+  if (P.transitions && !P.amGather) {
+    for (int i = tid; i < N * N; i += W) {
+      trT[i] = P.transitions[i];
+    }
+  }
+  if (Tb >= 1) {
+    fetch(1, 0, tid, W);
+  }
+  __syncthreads();
+  double am = 0.0;
+  int prevTok = (tid < nh && len > 0) ? tokOf(tid, 0) : 0;
+  double lmAcc = 0.0; /* token LM: the path's LM score ... */
+  int lmCtx = 0;      /* ... and context row (row 0 = lm.start) */
+  int lmPrev = prevTok;
+  c = 0;
+  for (int lo = 1; lo <= Tb; lo += Fe, ++c) {
+    const int hi = lo + Fe - 1 < Tb ? lo + Fe - 1 : Tb;
+    const int nf = hi - lo + 1;
+    const bool more = hi < Tb;
+    const float* eT = eT0 + (size_t)(c & 1) * Fe * N;
+    if (tid < aThreads) {
+      if (tid < nh) {
+        /* the chain is the additions: tokens and emissions of eight steps are read ahead of them */
+        constexpr int U = 8;
+        auto walk = [&](auto withTrans) {
+          constexpr bool TR = decltype(withTrans)::value;
+          for (int j0 = 0; j0 < nf; j0 += U) {
+            int tk[U];
+            float ev[U], tr[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+              tk[u] = tokOf(tid, lo + (j0 + u < nf ? j0 + u : nf - 1));
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+              const int jj = j0 + u < nf ? j0 + u : nf - 1;
+              ev[u] = P.amGather ? em[(size_t)(lo - 1 + jj) * N + (tk[u] >= 0 ? tk[u] : 0)] : eT[jj * N + (tk[u] >= 0 ? tk[u] : 0)];
+              tr[u] = 0.0f;
+            }
+            if (TR) {
+#pragma unroll
+              for (int u = 0; u < U; ++u) {
+                const int pv = u == 0 ? prevTok : tk[u - 1];
+                tr[u] = (tk[u] >= 0 && pv >= 0 && lo - 1 + j0 + u > 0) ? trG[(size_t)tk[u] * N + pv] : 0.0f;
+              }
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+              if (j0 + u < nf && tk[u] >= 0) {
+                double x = (double)ev[u];
+                if (TR && lo - 1 + j0 + u > 0) {
+                  x += (double)tr[u];
+                }
+                am += x;
+                prevTok = tk[u];
+              }
+            }
+          }
+        };
+        if (P.transitions) {
+          walk(SlParity<1>());
+        } else {
+          walk(SlParity<0>());
+        }
+        if (P.tokLm) { /* a chain of dependent gathers, one per new-token step */
+          for (int j = 0; j < nf; ++j) {
+            const int tk = tokOf(tid, lo + j);
+            if (tk >= 0) {
+              if (tk != lmPrev && tk != P.blank) {
+                const int2 e = P.tokLm[(size_t)lmCtx * (size_t)P.tokLmStride + (size_t)tk];
+                lmAcc = lmAcc + (double)__uint_as_float((uint32_t)e.x);
+                lmCtx = e.y;
+              }
+              lmPrev = tk;
+            }
+          }
+        }
+      }
+    } else if (more) {
+      fetch(hi + 1, (c + 1) & 1, tid - aThreads, fThreads);
+    }
+    if (more && fThreads == 0) {
+      fetch(hi + 1, (c + 1) & 1, tid, W);
+    }
+    __syncthreads();
+  }
+  if (tid < nh) {
+    P.amOut[((size_t)b * K + tid) * 3 + 1] = am;
+    if (P.tokLm) {
+      lmAcc = lmAcc + (double)__uint_as_float((uint32_t)P.tokLm[(size_t)lmCtx * (size_t)P.tokLmStride + (size_t)P.N].x);
+      P.amOut[((size_t)b * K + tid) * 3 + 2] = lmAcc;
+    }
+  }
+}
+
 /* ------------------------------------------------------------------------ */
 /* streaming helpers on the device-resident history:                         */
 /*   op 0: getBestHypothesis(lookBack)  (LexiconFreeDecoder.cpp:188-194,       */
