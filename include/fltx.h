@@ -299,6 +299,37 @@ enum { FLTX_S2S_LOG_PROBS = 0, FLTX_S2S_LOGITS = 1 };
 FLTX_API int fltx_s2s_step_typed(fltx_decoder* dec, const void* scores, int32_t dtype, int32_t kind,
                                  int32_t on_device, int64_t row_stride, const uint8_t* row_valid, double* row_lse,
                                  int32_t* next_token, int32_t* next_beam_idx, int32_t* next_src_row, int32_t* n_rows);
+/* Shallow fusion with an LM that scores a whole vocabulary per state (a neural token LM: ConvLM, a transformer LM).
+ * An LM whose answers arrive per step as rows next to the model's rows: row b*K+k holds LM::score(state of that
+ * hypothesis, v) for every LM index v (ConvLM.cpp:120-141's shape).  lm_width: entries per LM row (0: the decoder's V).
+ * usr_to_lm (may be NULL: identity, n_usr ignored): the LM index of the model's token u (ConvLM.cpp:40-49); every
+ * entry must lie in [0, lm_width) when lm_width > 0, else FLTX_ERR_INVALID.  finish_index: the LM index LM::finish reads
+ * (ConvLM.cpp:140-141: the LM's </s>); -1: usr_to_lm[eos] of the decoder.  The LM's per-hypothesis state is the
+ * caller's, carried by index_select(next_src_row) as the model's is; every hypothesis has its own prefix and so its own
+ * state: no merges.  Only fltx_s2s_decoder_create takes such an LM (the other decoders, fltx_group_create and the
+ * fltx_lm_* state functions return FLTX_ERR_UNSUPPORTED).  At fltx_s2s_begin: FLTX_ERR_INVALID when a map has fewer than
+ * V entries, or when a token's LM index or (eos < V) the finish index lies outside the LM's rows. */
+FLTX_API int fltx_lm_rows_create(int32_t lm_width, const int32_t* usr_to_lm, int32_t n_usr, int32_t finish_index,
+                                 fltx_lm** out);
+/* fltx_s2s_step_typed on a decoder made with a rows LM (LexiconFreeSeq2SeqDecoder.cpp:103-143): the token beam of a
+ * row is taken from the model's scores alone; for each kept token n the LM score is a float -- in log-probs mode the LM
+ * row's entry at usr_to_lm[n] (at finish_index when n == eos), widened exactly; in logits mode (float)((double)x -
+ * lse_lm), lse_lm as fltx_s2s_step_typed defines lse, which lm_row_lse (may be NULL; B*K doubles on the device)
+ * receives -- and the candidate's score, emittingModelScore and lmScore are built with the reference's double
+ * operations (lmScore accumulates when lm_weight == 0 too).  A candidate whose score is NaN (a NaN LM entry,
+ * 0 * -inf) is never a candidate; a -inf LM entry behaves as a -inf model entry.  LM rows of padding rows and of rows
+ * with row_valid 0 are never read.  The model's and the LM's rows have independent dtype, kind and stride
+ * (lm_row_stride >= lm_width, in elements); both are device pointers, or both host pointers staged in their own types.
+ * With lm_weight != 0 the exact token beam is kept (min(beam_size_token, V) <= 64); with lm_weight == 0 the shortcut of
+ * ZeroLM stays (the row's best min(beam_size_token, beam_size + 1) tokens and eos) and the LM entries of those are
+ * gathered for lmScore -- a NaN candidate among them is dropped, not replaced by a token beyond the shortcut.
+ * fltx_s2s_step / fltx_s2s_step_typed on such a decoder, and this call on any other, return FLTX_ERR_STATE;
+ * FLTX_ERR_INVALID on a bad dtype or kind, a stride below the width, or NULL rows before the last step. */
+FLTX_API int fltx_s2s_step_lm_rows(fltx_decoder* dec,
+    const void* scores, int32_t dtype, int32_t kind, int64_t row_stride,
+    const void* lm_scores, int32_t lm_dtype, int32_t lm_kind, int64_t lm_row_stride,
+    int32_t on_device, const uint8_t* row_valid, double* row_lse, double* lm_row_lse,
+    int32_t* next_token, int32_t* next_beam_idx, int32_t* next_src_row, int32_t* n_rows);
 /* *done = 1 when every utterance is done (no live hypothesis, or max_output_length steps); synchronises. */
 FLTX_API int fltx_s2s_done(fltx_decoder* dec, int32_t* done);
 /* The back-trace (:152-163): every utterance's final beam -- the last non-empty one, which may hold unfinished

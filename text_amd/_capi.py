@@ -91,6 +91,7 @@ class Lib:
         "fltx_group_decode_batch", "fltx_group_result_count", "fltx_group_result_fetch", "fltx_group_synchronize",
         "fltx_s2s_decoder_create", "fltx_s2s_begin", "fltx_s2s_step", "fltx_s2s_step_typed", "fltx_s2s_done",
         "fltx_s2s_end", "fltx_s2s_lex_decoder_create", "fltx_s2s_lex_set_max_states", "fltx_s2s_lex_info",
+        "fltx_lm_rows_create", "fltx_s2s_step_lm_rows",
     ]
 
     def __init__(self, path=None):
@@ -164,6 +165,8 @@ class Lib:
             "fltx_s2s_begin": [vp, i32, i32, vp, vp, vp, vp],
             "fltx_s2s_step": [vp, vp, i32, i64, vp, vp, vp, vp, vp],
             "fltx_s2s_step_typed": [vp, vp, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp],
+            "fltx_lm_rows_create": [i32, vp, i32, i32, pvp],
+            "fltx_s2s_step_lm_rows": [vp, vp, i32, i32, i64, vp, i32, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp],
             "fltx_s2s_done": [vp, vp],
             "fltx_s2s_end": [vp],
             "fltx_s2s_lex_decoder_create": [vp, C.POINTER(S2sLexOptions), vp, vp, i32, i32, i32, pvp],
@@ -309,6 +312,23 @@ class NgramLM(ZeroLM):
                                                      _ptr(bo), _ptr(um), len(um), bos, eos, unk,
                                                      C.byref(h)))
         self.h = h
+        _live["lm"].add(self)
+
+
+class RowsLM(ZeroLM):
+    """fltx_lm_rows_create: an LM whose answers arrive per step as rows next to the model's rows (a neural token LM in
+    shallow fusion; Seq2SeqBatchDecoder.step(..., lm_scores=)).  lm_width: entries per LM row (0: the decoder's V);
+    usr_to_lm: the LM index of each model token (None: identity); finish_index: the LM index LM::finish reads (-1:
+    usr_to_lm[eos])."""
+
+    def __init__(self, lm_width=0, usr_to_lm=None, finish_index=-1, lib=None):
+        self.ctx, self.L = None, lib or default_lib()
+        um = None if usr_to_lm is None else np.ascontiguousarray(usr_to_lm, dtype=np.int32)
+        h = C.c_void_p()
+        self.L.check(self.L.lib.fltx_lm_rows_create(int(lm_width), None if um is None else _ptr(um),
+                                                    0 if um is None else len(um), int(finish_index), C.byref(h)))
+        self.h = h
+        self.lm_width, self.usr_to_lm, self.finish_index = int(lm_width), um, int(finish_index)
         _live["lm"].add(self)
 
 
@@ -844,18 +864,8 @@ class Seq2SeqBatchDecoder(BatchDecoder):
         self._chk(self.L.lib.fltx_s2s_begin(self.h, self.B, self.V, *[self._addr(o) for o in out]))
         return tuple(out)
 
-    def step(self, scores, row_valid=None, *, kind="log_probs", lse_out=None, dtype=None):
-        """scores: [B*K, >= V] rows b*K + k: a torch tensor of float32, float16 or bfloat16 on the device or the host
-        (any row stride, unit column stride), or a numpy float32 / float16 array -- or uint16 holding bfloat16 bits
-        with dtype="bf16".  kind: "log_probs" (the model's scores) or "logits" (the step takes each row's
-        log-softmax itself, fltx_s2s_step_typed).  lse_out: None or a device float64 tensor of B*K that receives each
-        live row's log-sum-exp in logits mode (NaN for the other rows).  row_valid: None or B*K bytes / bools (0: the
-        model dropped the row).  float32 log-probs go through fltx_s2s_step exactly as before."""
-        if kind not in S2S_KINDS:
-            raise ValueError("kind: one of %s" % sorted(S2S_KINDS))
-        out = self._rows()
-        ptrs = [self._addr(o) for o in out]
-        BK = self.B * int(self.options.beam_size)
+    def _rows_in(self, scores, dtype, BK, what="scores"):
+        """-> (the array kept alive, fltx_dtype, row stride, address, on_device, the rows live on the host)"""
         if isinstance(scores, np.ndarray):
             if dtype is not None:
                 if dtype not in ("bf16", "bfloat16") or scores.dtype != np.uint16:
@@ -866,36 +876,68 @@ class Seq2SeqBatchDecoder(BatchDecoder):
             else:
                 dt = DTYPE_F32
             sc = np.ascontiguousarray(scores, dtype=_NP_DTYPES[dt]).reshape(BK, -1)
-            stride, ptr = sc.shape[1], sc.ctypes.data
-            on_dev = 1 if self._emu else 0
+            return sc, dt, sc.shape[1], sc.ctypes.data, 1 if self._emu else 0, True
+        import torch
+        sc = scores.reshape(-1, scores.shape[-1])
+        dts = {torch.float32: DTYPE_F32, torch.float16: DTYPE_F16, torch.bfloat16: DTYPE_BF16}
+        assert sc.dtype in dts and sc.stride(-1) == 1, \
+            "%s: float32 / float16 / bfloat16 rows of unit column stride" % what
+        cpu = sc.device.type == "cpu"
+        return sc, dts[sc.dtype], sc.stride(0), sc.data_ptr(), 0 if cpu else 1, cpu
+
+    def _lse_ptr(self, lse_out, BK):
+        if lse_out is None:
+            return None
+        n_lse = lse_out.size if isinstance(lse_out, np.ndarray) else lse_out.numel()
+        assert n_lse >= BK and str(lse_out.dtype).endswith("float64"), "lse_out: B*K float64 on the device"
+        return self._addr(lse_out)
+
+    def step(self, scores, row_valid=None, *, kind="log_probs", lse_out=None, dtype=None, lm_scores=None,
+             lm_kind="log_probs", lm_lse_out=None, lm_dtype=None):
+        """scores: [B*K, >= V] rows b*K + k: a torch tensor of float32, float16 or bfloat16 on the device or the host
+        (any row stride, unit column stride), or a numpy float32 / float16 array -- or uint16 holding bfloat16 bits
+        with dtype="bf16".  kind: "log_probs" (the model's scores) or "logits" (the step takes each row's
+        log-softmax itself, fltx_s2s_step_typed).  lse_out: None or a device float64 tensor of B*K that receives each
+        live row's log-sum-exp in logits mode (NaN for the other rows).  row_valid: None or B*K bytes / bools (0: the
+        model dropped the row).  float32 log-probs go through fltx_s2s_step exactly as before.
+        lm_scores / lm_kind / lm_lse_out / lm_dtype: the rows of a RowsLM ([B*K, >= lm_width], the same forms as
+        `scores` and on the same side -- both on the device or both on the host), required when the decoder was made
+        with one and refused otherwise (fltx_s2s_step_lm_rows)."""
+        if kind not in S2S_KINDS or lm_kind not in S2S_KINDS:
+            raise ValueError("kind: one of %s" % sorted(S2S_KINDS))
+        has_rows_lm = isinstance(self._keep[0], RowsLM)
+        if (lm_scores is not None) != has_rows_lm:
+            raise FltxError(ERR_STATE, "Seq2SeqBatchDecoder.step: lm_scores go with a decoder made with a RowsLM, and "
+                            "such a decoder takes them at every step")
+        out = self._rows()
+        ptrs = [self._addr(o) for o in out]
+        BK = self.B * int(self.options.beam_size)
+        sc, dt, stride, ptr, on_dev, host = self._rows_in(scores, dtype, BK)
+        if isinstance(scores, np.ndarray):
             rv = None if row_valid is None else np.ascontiguousarray(row_valid, dtype=np.uint8)
+            rvp = None if rv is None else rv.ctypes.data
+        elif host:
+            rv = None if row_valid is None else np.ascontiguousarray(
+                row_valid.cpu().numpy() if hasattr(row_valid, "cpu") else row_valid, dtype=np.uint8)
             rvp = None if rv is None else rv.ctypes.data
         else:
             import torch
-            sc = scores.reshape(-1, scores.shape[-1])
-            dts = {torch.float32: DTYPE_F32, torch.float16: DTYPE_F16, torch.bfloat16: DTYPE_BF16}
-            assert sc.dtype in dts and sc.stride(-1) == 1, \
-                "scores: float32 / float16 / bfloat16 rows of unit column stride"
-            dt = dts[sc.dtype]
-            stride, ptr, on_dev = sc.stride(0), sc.data_ptr(), 0 if sc.device.type == "cpu" else 1
-            if sc.device.type == "cpu":
-                rv = None if row_valid is None else np.ascontiguousarray(
-                    row_valid.cpu().numpy() if hasattr(row_valid, "cpu") else row_valid, dtype=np.uint8)
-                rvp = None if rv is None else rv.ctypes.data
-            else:
-                rv = None if row_valid is None else row_valid.reshape(-1).to(torch.uint8).contiguous()
-                rvp = None if rv is None else rv.data_ptr()
-        if dt == DTYPE_F32 and kind == "log_probs":
+            rv = None if row_valid is None else row_valid.reshape(-1).to(torch.uint8).contiguous()
+            rvp = None if rv is None else rv.data_ptr()
+        lsc = None
+        if lm_scores is not None:
+            lsc, ldt, lstride, lptr, l_on_dev, _ = self._rows_in(lm_scores, lm_dtype, BK, "lm_scores")
+            assert l_on_dev == on_dev, "scores and lm_scores: both on the device or both on the host"
+            self._chk(self.L.lib.fltx_s2s_step_lm_rows(self.h, ptr, dt, S2S_KINDS[kind], stride, lptr, ldt,
+                                                        S2S_KINDS[lm_kind], lstride, on_dev, rvp,
+                                                        self._lse_ptr(lse_out, BK), self._lse_ptr(lm_lse_out, BK),
+                                                        *ptrs))
+        elif dt == DTYPE_F32 and kind == "log_probs":
             self._chk(self.L.lib.fltx_s2s_step(self.h, ptr, on_dev, stride, rvp, *ptrs))
         else:
-            lp = None
-            if lse_out is not None:
-                n_lse = lse_out.size if isinstance(lse_out, np.ndarray) else lse_out.numel()
-                assert n_lse >= BK and str(lse_out.dtype).endswith("float64"), "lse_out: B*K float64 on the device"
-                lp = self._addr(lse_out)
-            self._chk(self.L.lib.fltx_s2s_step_typed(self.h, ptr, dt, S2S_KINDS[kind], on_dev, stride, rvp, lp,
-                                                      *ptrs))
-        self._inputs = (sc, rv)  # (kept until the next step: the kernels read them asynchronously)
+            self._chk(self.L.lib.fltx_s2s_step_typed(self.h, ptr, dt, S2S_KINDS[kind], on_dev, stride, rvp,
+                                                      self._lse_ptr(lse_out, BK), *ptrs))
+        self._inputs = (sc, rv, lsc)  # (kept until the next step: the kernels read them asynchronously)
         return tuple(out)
 
     def done(self):

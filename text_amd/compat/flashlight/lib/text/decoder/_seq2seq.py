@@ -58,15 +58,30 @@ def _context():
     return _ctx[0]
 
 
-def _decode(dec, K, update_func, max_output_length, emissions, T, N, raw_beam_idx):
+def _pad_rows(K, vectors):
+    W = max(len(r) for r in vectors)
+    rows = np.full((K, W), np.nan, dtype=np.float32)
+    for k, r in enumerate(vectors):
+        rows[k, :len(r)] = np.asarray(r, dtype=np.float32)
+    return rows
+
+
+def _decode(dec, K, update_func, max_output_length, emissions, T, N, raw_beam_idx, rows_lm=False):
     """decodeStep over a batched decoder at B = 1: one update_func call and one device step per step.  raw_beam_idx:
     update_func sees the parents' beam indices (LexiconFreeSeq2SeqDecoder.cpp:49), else -1 for every row (the
-    lexicon decoder's candidates never record prevHypIdx: LexiconSeq2SeqDecoder.cpp:49)."""
+    lexicon decoder's candidates never record prevHypIdx: LexiconSeq2SeqDecoder.cpp:49).  rows_lm: update_func returns
+    a third element, the LM's row vectors aligned with the scores (text_amd._capi.RowsLM)."""
     raw_y, raw_beam, prev_states = [-1], [-1], [None]
     t = 0
     begun = False
     while t < max_output_length:
-        scores, out_states = update_func(emissions, N, T, raw_y, raw_beam, prev_states, t)
+        ret = update_func(emissions, N, T, raw_y, raw_beam, prev_states, t)
+        if rows_lm:
+            if len(ret) != 3:
+                raise ValueError("update_func: with a RowsLM it returns (scores, states, lm_scores)")
+            scores, out_states, lm_rows = ret
+        else:
+            scores, out_states = ret
         V = max(len(r) for r in scores)
         if not begun:
             dec.begin(1, V)
@@ -76,7 +91,7 @@ def _decode(dec, K, update_func, max_output_length, emissions, T, N, raw_beam_id
         for k, (r, s) in enumerate(zip(scores, out_states)):
             rows[k, :len(r)] = np.asarray(r, dtype=np.float32)
             valid[k] = s is not None
-        out = dec.step(rows, valid)
+        out = dec.step(rows, valid, lm_scores=_pad_rows(K, lm_rows)) if rows_lm else dec.step(rows, valid)
         dec.ctx.synchronize()  # (the rows decide the next model call: one host wait per step)
         tok, beam, src, n = (x.cpu().numpy() if hasattr(x, "cpu") else x for x in out)
         t += 1
@@ -100,7 +115,13 @@ def _decode(dec, K, update_func, max_output_length, emissions, T, N, raw_beam_id
 
 class LexiconFreeSeq2SeqDecoder:
     """LexiconFreeSeq2SeqDecoder(options, lm, eos_idx, update_func, max_output_length): ZeroLM, or an LM object of
-    text_amd._capi (ZeroLM / NgramLM / ArpaLM); a user-defined LM is refused (FLTX_ERR_UNSUPPORTED)."""
+    text_amd._capi (ZeroLM / NgramLM / ArpaLM / RowsLM); any other user-defined LM is refused
+    (FLTX_ERR_UNSUPPORTED).
+
+    With a text_amd._capi.RowsLM (a neural token LM in shallow fusion) update_func returns three elements,
+    (scores, states, lm_scores): lm_scores is a list of row vectors aligned with scores, row k holding the LM's
+    log-probabilities of every LM index after the hypothesis of row k (the LM's own state travels inside the model's
+    state object).  The decoder keeps emittingModelScore and lmScore apart, as the reference does."""
 
     def __init__(self, options, lm, eos_idx, update_func, max_output_length):
         self.options, self.eos = options, int(eos_idx)
@@ -120,7 +141,7 @@ class LexiconFreeSeq2SeqDecoder:
 
     def decode_step(self, emissions, T, N):
         self._hyps = _decode(self._dec, self.options.beam_size, self.update_func, self.max_output_length, emissions, T,
-                             N, raw_beam_idx=True)
+                             N, raw_beam_idx=True, rows_lm=isinstance(self._lm, _capi.RowsLM))
 
     def prune(self, look_back=0):
         return None

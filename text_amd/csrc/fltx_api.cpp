@@ -164,6 +164,16 @@ __global__ void __launch_bounds__(kS2sTypedThreads) fltx_s2s_typed_kernel(S2sTyp
   __shared__ __attribute__((aligned(16))) S2sTypedLds fltx_s2s_typed_lds;
   s2sTypedRows<DT, LOGITS>(Q, (char*)&fltx_s2s_typed_lds);
 }
+/* a rows LM (fltx_s2s_step_lm_rows): the LM scores of the records' tokens, then the step that reads them */
+template <int DT, bool LOGITS>
+__global__ void __launch_bounds__(kS2sLmThreads) fltx_s2s_lm_rows_kernel(S2sLmRowsParams Q) {
+  __shared__ __attribute__((aligned(16))) S2sLmRowsLds fltx_s2s_lm_rows_lds;
+  s2sLmRows<DT, LOGITS>(Q, (char*)&fltx_s2s_lm_rows_lds);
+}
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_s2s_step_lm_rows_kernel(S2sLmRowsParams Q) {
+  __shared__ __attribute__((aligned(16))) S2sStepLds fltx_s2s_lm_step_lds;
+  s2sStepUtteranceLmRows(Q, (char*)&fltx_s2s_lm_step_lds);
+}
 /* fltx_s2s_lex.h: the lexicon seq2seq step (its front end is fltx_s2s_tokbeam_kernel), start and back-trace */
 __global__ void __launch_bounds__(kS2sStepThreads) fltx_s2s_lex_step_kernel(S2lParams Q) {
   __shared__ __attribute__((aligned(16))) S2lStepLds fltx_s2l_lds;
@@ -437,8 +447,12 @@ struct DeviceScope {
 
 struct fltx_lm {
   fltx_ctx* ctx = nullptr;
-  int kind = 0; /* 0 zero, 1 ngram, 2 host callbacks (fltx_lm_host_create) */
+  int kind = 0; /* 0 zero, 1 ngram, 2 host callbacks (fltx_lm_host_create), 3 rows (fltx_lm_rows_create) */
   fltx_host_lm host{};
+  /* rows LM: entries per LM row (0: the decoder's V), the LM index finish reads (-1: usr_to_lm[eos]), and whether hUsr
+   * holds a map (else identity) */
+  int32_t rowsWidth = 0, rowsFinish = -1;
+  bool rowsMap = false;
   int order = 0;
   int32_t bos = 0, eos = 0, unk = 0, nUsr = 0;
   uint32_t mask = 0;
@@ -676,6 +690,8 @@ struct fltx_decoder {
     int32_t ctx0[kS2sCtx] = {0};
     DBuf beam, beamN, hist, rowsInt, done, finalStep, recTok, recAm, recN, cKey; /* (beam, hist: of the kind's types) */
     DBuf scores, valid; /* device copies of host inputs */
+    DBuf recLm, lmScores; /* a rows LM: the records' LM scores; the device copy of host LM rows */
+    int lmWidth = 0, lmFinish = 0; /* a rows LM: as fltx_s2s_begin resolved them for V */
     /* with a lexicon (fltx_s2s_lex_decoder_create) */
     double wordScore = 0.0;
     bool isLmToken = false;
@@ -699,7 +715,7 @@ __attribute__((visibility("hidden"))) int fltx_set_error_(int code, const char* 
   g_err = msg ? msg : "";
   return code;
 }
-/* internal (fltx_group.cpp): 0 ZeroLM, 1 n-gram tables, 2 host callbacks */
+/* internal (fltx_group.cpp): 0 ZeroLM, 1 n-gram tables, 2 host callbacks, 3 rows */
 __attribute__((visibility("hidden"))) int fltx_lm_kind_(const fltx_lm* lm) { return lm ? lm->kind : -1; }
 const char* fltx_version(void) {
 #ifdef FLTX_EMU
@@ -815,6 +831,41 @@ int fltx_lm_host_create(const fltx_host_lm* cb, fltx_lm** out) {
   auto* lm = new fltx_lm();
   lm->kind = 2;
   lm->host = *cb;
+  {
+    std::lock_guard<std::mutex> lock(g_lmRegMu);
+    g_lmReg.insert(lm);
+  }
+  *out = lm;
+  return FLTX_OK;
+}
+
+/* an LM whose answers arrive per step as rows (fltx_s2s_step_lm_rows): only the map is kept */
+int fltx_lm_rows_create(int32_t lmWidth, const int32_t* usrToLm, int32_t nUsr, int32_t finishIndex, fltx_lm** out) {
+  if (!out || lmWidth < 0 || finishIndex < -1 || (usrToLm && nUsr < 0)) {
+    return fail(FLTX_ERR_INVALID, "fltx_lm_rows_create: bad argument");
+  }
+  if (lmWidth > kS2sMaxV) {
+    return fail(FLTX_ERR_UNSUPPORTED, "fltx_lm_rows_create: lm_width %d > %d", lmWidth, kS2sMaxV);
+  }
+  if (lmWidth > 0 && finishIndex >= lmWidth) {
+    return fail(FLTX_ERR_INVALID, "fltx_lm_rows_create: finish_index %d outside [0, %d)", finishIndex, lmWidth);
+  }
+  if (usrToLm && lmWidth > 0) {
+    for (int32_t u = 0; u < nUsr; ++u) {
+      if (usrToLm[u] < 0 || usrToLm[u] >= lmWidth) {
+        return fail(FLTX_ERR_INVALID, "fltx_lm_rows_create: usr_to_lm[%d] = %d outside [0, %d)", u, usrToLm[u], lmWidth);
+      }
+    }
+  }
+  auto* lm = new fltx_lm();
+  lm->kind = 3;
+  lm->rowsWidth = lmWidth;
+  lm->rowsFinish = finishIndex;
+  lm->rowsMap = usrToLm != nullptr;
+  if (usrToLm) {
+    lm->hUsr.assign(usrToLm, usrToLm + nUsr);
+    lm->nUsr = nUsr;
+  }
   {
     std::lock_guard<std::mutex> lock(g_lmRegMu);
     g_lmReg.insert(lm);
@@ -946,6 +997,9 @@ int fltx_lm_score_sequence(fltx_lm* lm, const int32_t* usrWords, int32_t n, int3
   if (lm->kind == 2) {
     return fail(FLTX_ERR_UNSUPPORTED, "a host LM keeps its own states (call the LM object)");
   }
+  if (lm->kind == 3) {
+    return fail(FLTX_ERR_UNSUPPORTED, "a rows LM has no states here: its answers arrive with fltx_s2s_step_lm_rows");
+  }
   float tot = 0;
   if (lm->kind == 0) {
     for (int i = 0; i < n; ++i) {
@@ -1068,6 +1122,9 @@ int fltx_lm_state_size(fltx_lm* lm, int32_t* n) {
   if (lm->kind == 2) {
     return fail(FLTX_ERR_UNSUPPORTED, "a host LM keeps its own states (call the LM object)");
   }
+  if (lm->kind == 3) {
+    return fail(FLTX_ERR_UNSUPPORTED, "a rows LM has no states here: its answers arrive with fltx_s2s_step_lm_rows");
+  }
   *n = lm->kind == 0 ? 0 : std::max(1, lm->order - 1);
   return FLTX_OK;
 }
@@ -1078,6 +1135,9 @@ int fltx_lm_start(fltx_lm* lm, int32_t startWithNothing, int32_t* ctxOut) {
   }
   if (lm->kind == 2) {
     return fail(FLTX_ERR_UNSUPPORTED, "a host LM keeps its own states (call the LM object)");
+  }
+  if (lm->kind == 3) {
+    return fail(FLTX_ERR_UNSUPPORTED, "a rows LM has no states here: its answers arrive with fltx_s2s_step_lm_rows");
   }
   if (lm->kind == 0) {
     return FLTX_OK;
@@ -1151,6 +1211,9 @@ int fltx_lm_step(fltx_lm* lm, const int32_t* ctxIn, int32_t usrIdx, int32_t* ctx
   }
   if (lm->kind == 2) {
     return fail(FLTX_ERR_UNSUPPORTED, "a host LM keeps its own states (call the LM object)");
+  }
+  if (lm->kind == 3) {
+    return fail(FLTX_ERR_UNSUPPORTED, "a rows LM has no states here: its answers arrive with fltx_s2s_step_lm_rows");
   }
   if (lm->kind == 0) {
     *score = 0.0f;
@@ -1360,8 +1423,8 @@ int fltx_trie_destroy(fltx_trie* t) {
 /* upload the flat n-gram tables to the context's device (once) */
 static int lmEnsureUploaded(fltx_lm* lm, fltx_ctx* ctx, fltx_lm::Dev** out) {
   *out = nullptr;
-  if (lm->kind != 1) {
-    return FLTX_OK; /* (ZeroLM: nothing to compute; host LM: answered on the host) */
+  if (lm->kind != 1 && !(lm->kind == 3 && lm->rowsMap)) {
+    return FLTX_OK; /* (ZeroLM: nothing to compute; host LM: answered on the host; rows LM without a map: identity) */
   }
   std::lock_guard<std::mutex> lock(lm->devMu);
   auto it = lm->dev.find(ctx->uid);
@@ -1371,6 +1434,19 @@ static int lmEnsureUploaded(fltx_lm* lm, fltx_ctx* ctx, fltx_lm::Dev** out) {
   }
   std::unique_ptr<fltx_lm::Dev> dv(new fltx_lm::Dev());
   Stream st = ctx->stream;
+  if (lm->kind == 3) { /* a rows LM: the map alone */
+    const size_t nb = sizeof(int32_t) * std::max<size_t>(1, lm->hUsr.size());
+    if (dv->usrToLm.ensure(nb, st, false)) {
+      return fail(FLTX_ERR_OOM, "rows LM: device allocation failed");
+    }
+    if ((!lm->hUsr.empty() && devCopyH2D(dv->usrToLm.p, lm->hUsr.data(), sizeof(int32_t) * lm->hUsr.size(), st)) ||
+        devSync(st)) {
+      return fail(FLTX_ERR_HIP, "rows LM: upload failed");
+    }
+    *out = dv.get();
+    lm->dev[ctx->uid] = std::move(dv);
+    return FLTX_OK;
+  }
   const size_t cap = lm->hTab.size(), nn = lm->hBackoff.size();
   if (dv->tab.ensure(sizeof(NgramSlot) * cap, st, false) || dv->backoff.ensure(sizeof(float) * nn, st, false) ||
       dv->usrToLm.ensure(sizeof(int32_t) * std::max<size_t>(1, lm->hUsr.size()), st, false)) {
@@ -1548,6 +1624,9 @@ int fltx_decoder_create(fltx_ctx* ctx, int32_t kind, const fltx_options* opt, co
   }
   if (kind != FLTX_DECODER_LEXFREE && kind != FLTX_DECODER_LEXICON) {
     return fail(FLTX_ERR_INVALID, "unknown decoder kind %d", kind);
+  }
+  if (lm->kind == 3) {
+    return fail(FLTX_ERR_UNSUPPORTED, "a rows LM (fltx_lm_rows_create) serves the lexicon-free seq2seq decoder only");
   }
   if (kind == FLTX_DECODER_LEXICON && !trie) {
     return fail(FLTX_ERR_INVALID, "lexicon decoder needs a trie");
@@ -5071,6 +5150,10 @@ int fltx_s2s_lex_decoder_create(fltx_ctx* ctx, const fltx_s2s_lex_options* opt, 
   if (!ctx || !opt || !trie || !lm || !out) {
     return fail(FLTX_ERR_INVALID, "fltx_s2s_lex_decoder_create: null argument");
   }
+  if (lm->kind == 3) {
+    /* (a token-level LM here shares states between segmentations: it needs this step's merge keys) */
+    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq lexicon: a rows LM (fltx_lm_rows_create) is not supported");
+  }
   fltx_s2s_options o{};
   o.beam_size = opt->beam_size;
   o.beam_size_token = opt->beam_size_token;
@@ -5150,7 +5233,7 @@ static int s2sPlanLexFree(fltx_decoder* d, int32_t V, int64_t* nC) {
   const int ktEff = std::min(Kt, V);
   /* without LM terms in the score a row contributes at most K survivors besides eos: its top min(Kt, K + 1) (one more
    * than K: eos may be among them) and eos when it is in the top Kt are every candidate that can survive */
-  const bool lmTerms = d->lm->kind == 1 && d->s2s.opt.lm_weight != 0.0;
+  const bool lmTerms = (d->lm->kind == 1 || d->lm->kind == 3) && d->s2s.opt.lm_weight != 0.0;
   if (lmTerms && ktEff > kS2sMaxKtLm) {
     return fail(FLTX_ERR_UNSUPPORTED, "seq2seq: a token beam of %d (beam_size_token, V = %d) > %d with LM terms", ktEff, V,
                 kS2sMaxKtLm);
@@ -5159,6 +5242,33 @@ static int s2sPlanLexFree(fltx_decoder* d, int32_t V, int64_t* nC) {
   d->s2s.eosExtra = d->s2s.mSel < ktEff ? 1 : 0;
   d->s2s.cap = d->s2s.mSel + d->s2s.eosExtra;
   *nC = (int64_t)K * d->s2s.cap + K;
+  if (d->lm->kind == 3) { /* a rows LM: every index the gather can form lies inside the LM's rows */
+    const fltx_lm* lm = d->lm;
+    const int eos = d->s2s.eos;
+    const int width = lm->rowsWidth > 0 ? lm->rowsWidth : V;
+    if (lm->rowsMap && V > lm->nUsr) {
+      return fail(FLTX_ERR_INVALID, "seq2seq rows LM: V = %d > the %d entries of usr_to_lm", V, lm->nUsr);
+    }
+    int finish = lm->rowsFinish;
+    if (finish < 0 && eos < V) {
+      finish = lm->rowsMap ? lm->hUsr[(size_t)eos] : eos;
+    }
+    if (eos < V && (finish < 0 || finish >= width)) {
+      return fail(FLTX_ERR_INVALID, "seq2seq rows LM: finish index %d outside the LM's rows of %d", finish, width);
+    }
+    if (lm->rowsMap) {
+      for (int u = 0; u < V; ++u) {
+        if (lm->hUsr[(size_t)u] < 0 || lm->hUsr[(size_t)u] >= width) {
+          return fail(FLTX_ERR_INVALID, "seq2seq rows LM: usr_to_lm[%d] = %d outside the LM's rows of %d (lm_width 0: V)",
+                      u, lm->hUsr[(size_t)u], width);
+        }
+      }
+    } else if (width < V) {
+      return fail(FLTX_ERR_INVALID, "seq2seq rows LM: lm_width %d < V = %d without a map", width, V);
+    }
+    d->s2s.lmWidth = width;
+    d->s2s.lmFinish = eos < V ? finish : 0; /* (eos >= V is never proposed: finish is never read) */
+  }
   return FLTX_OK;
 }
 
@@ -5229,7 +5339,8 @@ int fltx_s2s_begin(fltx_decoder* d, int32_t B, int32_t V, int32_t* nextTok, int3
       d->s2s.rowsInt.ensure(4 * (size_t)B, st, false) || d->s2s.done.ensure(4 * (size_t)B, st, false) ||
       d->s2s.finalStep.ensure(4 * (size_t)B, st, false) ||
       d->s2s.recTok.ensure(4 * BK * d->s2s.cap, st, false) || d->s2s.recAm.ensure(4 * BK * d->s2s.cap, st, false) ||
-      d->s2s.recN.ensure(4 * BK, st, false) || d->s2s.cKey.ensure(8 * (size_t)B * (size_t)nC, st, false)) {
+      d->s2s.recN.ensure(4 * BK, st, false) || d->s2s.cKey.ensure(8 * (size_t)B * (size_t)nC, st, false) ||
+      (d->lm->kind == 3 && d->s2s.recLm.ensure(4 * BK * d->s2s.cap, st, false))) {
     return fail(FLTX_ERR_OOM, "seq2seq workspace: device allocation failed (B=%d K=%d V=%d)", B, d->s2s.opt.beam_size,
                 V);
   }
@@ -5262,23 +5373,47 @@ int fltx_s2s_begin(fltx_decoder* d, int32_t B, int32_t V, int32_t* nextTok, int3
   return FLTX_OK;
 }
 
-extern "C++" { /* (a template, inside this file's extern "C" block) */
+extern "C++" { /* (templates, inside this file's extern "C" block) */
 template <int DT, bool LOGITS>
 static int s2sTypedLaunch(int nRows, Stream st, const S2sTypedParams& T) {
   S2S_LAUNCH((fltx_s2s_typed_kernel<DT, LOGITS>), (s2sTypedRows<DT, LOGITS>), nRows, kS2sTypedThreads,
              sizeof(S2sTypedLds), st, T);
   return FLTX_OK;
 }
+/* log-probs: a wave per row, four rows per workgroup; logits: a workgroup per row */
+template <int DT, bool LOGITS>
+static int s2sLmRowsLaunch(int nRows, Stream st, const S2sLmRowsParams& Q) {
+  S2S_LAUNCH((fltx_s2s_lm_rows_kernel<DT, LOGITS>), (s2sLmRows<DT, LOGITS>), LOGITS ? nRows : (nRows + 3) / 4,
+             kS2sLmThreads, sizeof(S2sLmRowsLds), st, Q);
+  return FLTX_OK;
 }
+}
+
+/* the LM's rows of fltx_s2s_step_lm_rows */
+struct S2sLmIn {
+  const void* scores;
+  int32_t dtype;
+  bool logits;
+  int64_t rowStride;
+  double* rowLse;
+};
 
 /* one step of either kind (the entry points have checked the decoder, `what` names the one that was called): the front
  * end the input asks for -- fltx_s2s_tokbeam_kernel for float log-probs, else the typed one (fltx_s2s.h: s2sTypedRows)
  * -- then the kind's step kernel */
 static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_t dtype, bool logits, int32_t onDevice,
                    int64_t rowStride, const uint8_t* rowValid, double* rowLse, int32_t* nextTok, int32_t* nextBeam,
-                   int32_t* nextSrc, int32_t* nRows) {
+                   int32_t* nextSrc, int32_t* nRows, const S2sLmIn* lmIn = nullptr) {
+  if ((d->lm->kind == 3) != (lmIn != nullptr)) {
+    return fail(FLTX_ERR_STATE, lmIn ? "%s: the decoder has no rows LM (fltx_lm_rows_create)"
+                                     : "%s: a decoder with a rows LM steps with fltx_s2s_step_lm_rows", what);
+  }
   if (!d->s2s.begun) {
     return fail(FLTX_ERR_STATE, "%s: fltx_s2s_begin first", what);
+  }
+  if (lmIn && ((!lmIn->scores && d->s2s.t < d->s2s.maxOut) || lmIn->rowStride < d->s2s.lmWidth)) {
+    return fail(FLTX_ERR_INVALID, "%s: bad argument (lm_row_stride %lld, lm_width = %d)", what,
+                (long long)lmIn->rowStride, d->s2s.lmWidth);
   }
   if (!nextTok || !nextBeam || !nextSrc || !nRows || (!scores && d->s2s.t < d->s2s.maxOut) || rowStride < d->N) {
     return fail(FLTX_ERR_INVALID, "%s: bad argument (row_stride %lld, V = %d)", what, (long long)rowStride, d->N);
@@ -5303,7 +5438,22 @@ static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_
     scores = d->s2s.scores.p;
     rowValid = rowValid ? d->s2s.valid.as<uint8_t>() : nullptr;
   }
+  const void* lmScores = lmIn ? lmIn->scores : nullptr;
+  if (lmIn && !onDevice && !last) { /* the LM's rows, staged in their own type */
+    const size_t lmElem = lmIn->dtype == FLTX_DTYPE_F32 ? 4 : 2;
+    const size_t nE = (BK - 1) * (size_t)lmIn->rowStride + (size_t)d->s2s.lmWidth;
+    if (d->s2s.lmScores.ensure(lmElem * nE, st, false)) {
+      return fail(FLTX_ERR_OOM, "seq2seq: staging allocation failed");
+    }
+    if (devCopyH2D(d->s2s.lmScores.p, lmScores, lmElem * nE, st)) {
+      return fail(FLTX_ERR_HIP, "seq2seq: upload failed");
+    }
+    lmScores = d->s2s.lmScores.p;
+  }
   if (last && logits && rowLse && devMemset(rowLse, 0xFF, 8 * BK, st)) { /* (all-ones: a NaN) */
+    return fail(FLTX_ERR_HIP, "%s: memset failed", what);
+  }
+  if (last && lmIn && lmIn->logits && lmIn->rowLse && devMemset(lmIn->rowLse, 0xFF, 8 * BK, st)) {
     return fail(FLTX_ERR_HIP, "%s: memset failed", what);
   }
   S2lParams Q = s2sStepParams(d);
@@ -5336,6 +5486,31 @@ static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_
   }
   if (d->kind == FLTX_DECODER_S2S_LEXICON) {
     S2S_LAUNCH(fltx_s2s_lex_step_kernel, s2lStepUtterance, d->B, kS2sStepThreads, sizeof(S2lStepLds), st, Q);
+  } else if (lmIn) {
+    S2sLmRowsParams R;
+    R.s = P;
+    R.x = lmScores;
+    R.rowStride = lmIn->rowStride;
+    R.width = d->s2s.lmWidth;
+    R.finishIdx = d->s2s.lmFinish;
+    R.usrToLm = d->lm->rowsMap ? d->lmDev->usrToLm.as<int32_t>() : nullptr;
+    R.recLm = d->s2s.recLm.as<float>();
+    R.rowLse = lmIn->logits ? lmIn->rowLse : nullptr;
+    if (!last) {
+      int rc;
+      switch (lmIn->dtype * 2 + (lmIn->logits ? 1 : 0)) {
+        case 0: rc = s2sLmRowsLaunch<kS2sDtF32, false>((int)BK, st, R); break;
+        case 1: rc = s2sLmRowsLaunch<kS2sDtF32, true>((int)BK, st, R); break;
+        case 2: rc = s2sLmRowsLaunch<kS2sDtF16, false>((int)BK, st, R); break;
+        case 3: rc = s2sLmRowsLaunch<kS2sDtF16, true>((int)BK, st, R); break;
+        case 4: rc = s2sLmRowsLaunch<kS2sDtBf16, false>((int)BK, st, R); break;
+        default: rc = s2sLmRowsLaunch<kS2sDtBf16, true>((int)BK, st, R); break;
+      }
+      if (rc) {
+        return rc;
+      }
+    }
+    S2S_LAUNCH(fltx_s2s_step_lm_rows_kernel, s2sStepUtteranceLmRows, d->B, kS2sStepThreads, sizeof(S2sStepLds), st, R);
   } else {
     S2S_LAUNCH(fltx_s2s_step_kernel, s2sStepUtterance, d->B, kS2sStepThreads, sizeof(S2sStepLds), st, P);
   }
@@ -5379,6 +5554,35 @@ int fltx_s2s_step_typed(fltx_decoder* d, const void* scores, int32_t dtype, int3
   }
   return s2sStep(d, "fltx_s2s_step_typed", scores, dtype, kind == FLTX_S2S_LOGITS, onDevice, rowStride, rowValid,
                  rowLse, nextTok, nextBeam, nextSrc, nRows);
+}
+
+/* fltx_s2s_step_typed with the rows of a rows LM (fltx_lm_rows_create) next to the model's */
+int fltx_s2s_step_lm_rows(fltx_decoder* d, const void* scores, int32_t dtype, int32_t kind, int64_t rowStride,
+                          const void* lmScores, int32_t lmDtype, int32_t lmKind, int64_t lmRowStride, int32_t onDevice,
+                          const uint8_t* rowValid, double* rowLse, double* lmRowLse, int32_t* nextTok,
+                          int32_t* nextBeam, int32_t* nextSrc, int32_t* nRows) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = s2sCheck(d, "fltx_s2s_step_lm_rows");
+  if (rc) {
+    return rc;
+  }
+  if (d->kind != FLTX_DECODER_S2S_LEXFREE || d->lm->kind != 3) {
+    return fail(FLTX_ERR_STATE, "fltx_s2s_step_lm_rows: the decoder has no rows LM (fltx_lm_rows_create)");
+  }
+  if ((dtype != FLTX_DTYPE_F32 && dtype != FLTX_DTYPE_F16 && dtype != FLTX_DTYPE_BF16) ||
+      (lmDtype != FLTX_DTYPE_F32 && lmDtype != FLTX_DTYPE_F16 && lmDtype != FLTX_DTYPE_BF16)) {
+    return fail(FLTX_ERR_INVALID, "fltx_s2s_step_lm_rows: dtype %d, lm_dtype %d", dtype, lmDtype);
+  }
+  if ((kind != FLTX_S2S_LOG_PROBS && kind != FLTX_S2S_LOGITS) ||
+      (lmKind != FLTX_S2S_LOG_PROBS && lmKind != FLTX_S2S_LOGITS)) {
+    return fail(FLTX_ERR_INVALID, "fltx_s2s_step_lm_rows: kind %d, lm_kind %d", kind, lmKind);
+  }
+  const S2sLmIn lmIn{lmScores, lmDtype, lmKind == FLTX_S2S_LOGITS, lmRowStride, lmRowLse};
+  return s2sStep(d, "fltx_s2s_step_lm_rows", scores, dtype, kind == FLTX_S2S_LOGITS, onDevice, rowStride, rowValid,
+                 rowLse, nextTok, nextBeam, nextSrc, nRows, &lmIn);
 }
 
 int fltx_s2s_done(fltx_decoder* d, int32_t* done) {

@@ -774,8 +774,12 @@ FLTX_DEV void s2sBackTrace(const S2sParams& P, const Hyp* beams, const Rec* hist
 }
 
 /* ---- the lexicon-free step ------------------------------------------------------------------------------------ */
+/* Where a candidate's LM score comes from is a template parameter, not a flag (see s2sLm): REC false: ZeroLM / the
+ * n-gram tables (s2sLm); REC true: a rows LM, recLm[r * cap + e] as fltx_s2s_lm_rows_kernel gathered it -- no n-gram
+ * context, ctx stays ctx0.  The step is instantiated once per source. */
 /* candidate j of the utterance: row k = j / cap, entry e = j % cap for j < nRows*cap; then the carried hypotheses */
-FLTX_DEV void s2sStepUtterance(const S2sParams& P, char* smem) {
+template <bool REC>
+FLTX_DEV void s2sStepUtteranceOn(const S2sParams& P, char* smem, const float* recLm) {
   S2sStepLds& S = *(S2sStepLds*)smem;
   const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
   const int K = P.K;
@@ -804,7 +808,12 @@ FLTX_DEV void s2sStepUtterance(const S2sParams& P, char* smem) {
       if (e < P.recN[r]) {
         const S2sHyp& h = prev[S.hypOfRow[k]];
         const int tok = P.recTok[r * cap + e];
-        const float lmS = s2sLm(P, h.ctx, tok, P.eos, nullptr);
+        float lmS;
+        if constexpr (REC) {
+          lmS = recLm[r * cap + e];
+        } else {
+          lmS = s2sLm(P, h.ctx, tok, P.eos, nullptr);
+        }
         key = s2sScoreKey(s2sScore(P, h, tok, P.recAm[r * cap + e], lmS));
       }
     } else {
@@ -843,7 +852,12 @@ FLTX_DEV void s2sStepUtterance(const S2sParams& P, char* smem) {
       const int tok = P.recTok[r * cap + e];
       const float a = P.recAm[r * cap + e];
       nh = h;
-      const float lmS = s2sLm(P, h.ctx, tok, P.eos, tok == P.eos ? nullptr : nh.ctx);
+      float lmS;
+      if constexpr (REC) {
+        lmS = recLm[r * cap + e];
+      } else {
+        lmS = s2sLm(P, h.ctx, tok, P.eos, tok == P.eos ? nullptr : nh.ctx);
+      }
       nh.score = s2sScore(P, h, tok, a, lmS);
       nh.am = h.am + (double)a;
       nh.lm = h.lm + (double)lmS;
@@ -863,6 +877,8 @@ FLTX_DEV void s2sStepUtterance(const S2sParams& P, char* smem) {
   }
   s2sPublishStep(P, S, b, nSel, isLive, token, parent, srcRow);
 }
+
+FLTX_DEV void s2sStepUtterance(const S2sParams& P, char* smem) { s2sStepUtteranceOn<false>(P, smem, nullptr); }
 
 FLTX_DEV void s2sBeginUtterance(const S2sParams& P, char*) {
   const int b = (int)(blockIdx.x * kS2sBeginThreads + threadIdx.x);
@@ -887,6 +903,209 @@ struct S2sPath { /* a path's records: the tokens row */
 
 FLTX_DEV void s2sEndUtterance(const S2sParams& P, char*) {
   s2sBackTrace(P, P.beam, P.hist, S2sPath{P.tokens}, 0);
+}
+
+/* ---- a rows LM (fltx_lm_rows_create): the LM's answers arrive as rows next to the model's ------------------------------
+ * Shallow fusion with an LM that scores a whole vocabulary per state (ConvLM.cpp:120-141's shape): like the emitting
+ * model it runs between two steps and leaves row b*K + k = LM::score(state of that hypothesis, v) for every LM index v;
+ * its state is carried by index_select(next_src_row) as the model's is.  Every hypothesis has its own prefix, hence its
+ * own LM state, so -- as for KenLM above -- candidatesStore's merge cannot fire: no state table, no merges.
+ *
+ * fltx_s2s_lm_rows_kernel runs after the front end (either of the two, unchanged) and before the step: for every entry
+ * of a live row's record it writes the LM score of that token into recLm, a float: the LM row's element at
+ * usrToLm[token] (at finishIdx for eos: LM::finish), widened exactly; with logits, (float)((double)x - lse) with lse
+ * the LM row's log-sum-exp as the typed front end defines it.  The step then is s2sStepUtteranceOn<S2sLmRecords>.
+ *   log-probs: a pure gather -- one wave per row, four rows per workgroup, <= cap elements of the row are read;
+ *   logits:    one workgroup per row: the row is read once with 16-byte loads (element-wise up to the first 16-byte
+ *              boundary and after the last) and kept in registers between the max and the sum pass when it has at most
+ *              kS2sLmVecs * 256 vectors; wider rows are read once per pass.  The sum is the typed front end's: f32 exp
+ *              summed in double per thread in a fixed order, the same butterfly per wave, the waves in order. */
+constexpr int kS2sLmThreads = 256;
+constexpr int kS2sLmVecs = 16; /* 16-byte vectors per thread kept in registers: 32 768 2-byte / 16 384 4-byte elements */
+
+struct S2sLmRowsParams {
+  S2sParams s;            /* (s.scores is not read) */
+  const void* x;          /* the LM's rows: element (r, i) at x + (r * rowStride + i) elements */
+  int64_t rowStride;
+  int32_t width;          /* entries per LM row */
+  int32_t finishIdx;      /* the LM index LM::finish reads */
+  const int32_t* usrToLm; /* [>= V] or null: identity */
+  float* recLm;           /* [B*K][cap] */
+  double* rowLse;         /* [B*K] or null: logits mode writes lse (live rows) or NaN */
+};
+
+struct S2sLmRowsLds {
+  double wsum[kS2sLmThreads / 64];
+  uint32_t wmax[kS2sLmThreads / 64];
+};
+
+FLTX_DEV bool s2sRowLive(const S2sParams& P, int64_t r) {
+  const int b = (int)(r / P.K), k = (int)(r % P.K);
+  return !P.done[b] && P.t < P.maxOut && k < P.nRowsInt[b] && (P.rowValid == nullptr || P.rowValid[r] != 0);
+}
+
+/* the LM scores of row r's record: entry e by thread `tid` of `nThreads` */
+template <int DT, bool LOGITS>
+FLTX_DEV void s2sLmGather(const S2sLmRowsParams& Q, int64_t r, const void* row, double lse, int tid, int nThreads) {
+  const S2sParams& P = Q.s;
+  const int n = P.recN[r];
+  for (int e = tid; e < n; e += nThreads) {
+    const int tok = P.recTok[r * P.cap + e];
+    const int idx = tok == P.eos ? Q.finishIdx : (Q.usrToLm ? Q.usrToLm[tok] : tok);
+    float v = __uint_as_float(0x7FC00000u); /* (an index outside the row -- fltx_s2s_begin refuses those -- is no candidate) */
+    if (idx >= 0 && idx < Q.width) {
+      v = s2sTypedScore<DT, LOGITS>(row, idx, lse);
+    }
+    Q.recLm[r * P.cap + e] = v;
+  }
+}
+
+/* log-probs: workgroup = four waves, wave = row b*K + k of the step */
+template <int DT>
+FLTX_DEV void s2sLmRowsGather(const S2sLmRowsParams& Q, char*) {
+  const S2sParams& P = Q.s;
+  const int wave = waveUniform(waveId());
+  const int64_t r = (int64_t)blockIdx.x * ((int)blockDim.x >> 6) + wave;
+  if (r >= (int64_t)P.B * P.K || !s2sRowLive(P, r)) {
+    return; /* (the record of a row that is not live is empty: the step reads no recLm of it) */
+  }
+  const void* row = (const char*)Q.x + r * Q.rowStride * (DT == kS2sDtF32 ? 4 : 2);
+  s2sLmGather<DT, false>(Q, r, row, 0.0, laneId(), 64);
+}
+
+/* f(raw key) for the j-th element of a 16-byte vector */
+template <int DT>
+FLTX_DEV uint32_t s2sVecKey(const uint4& v, int j) {
+  if constexpr (DT == kS2sDtF32) {
+    const uint32_t w = j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w;
+    return s2sRawKey(__uint_as_float(w));
+  } else {
+    const uint32_t w = (j >> 1) == 0 ? v.x : (j >> 1) == 1 ? v.y : (j >> 1) == 2 ? v.z : v.w;
+    const uint32_t h = (j & 1) ? w >> 16 : w & 0xFFFFu;
+    return s2sRawKey(DT == kS2sDtF16 ? s2sWidenF16(h) : __uint_as_float(h << 16));
+  }
+}
+
+/* f(raw key) for every element of the row this thread holds, in a fixed order: the head and tail elements (one per
+ * thread at most), then its vectors -- from the registers (CACHED) or from memory */
+template <int DT, bool CACHED, typename F>
+FLTX_DEV void s2sLmEach(const void* row, int nEdge, int edgeAt, const uint4* body, int nVec, const uint4* vr, F&& f) {
+  constexpr int kPer = DT == kS2sDtF32 ? 4 : 8;
+  const int tid = (int)threadIdx.x;
+  if (tid < nEdge) {
+    f(s2sRawKey(s2sElem<DT>(row, edgeAt)));
+  }
+  if constexpr (CACHED) {
+#pragma unroll
+    for (int q = 0; q < kS2sLmVecs; ++q) {
+      if (q * kS2sLmThreads < nVec && tid + q * kS2sLmThreads < nVec) {
+#pragma unroll
+        for (int j = 0; j < kPer; ++j) {
+          f(s2sVecKey<DT>(vr[q], j));
+        }
+      }
+    }
+  } else {
+    for (int i = tid; i < nVec; i += kS2sLmThreads) {
+      const uint4 v = body[i];
+#pragma unroll
+      for (int j = 0; j < kPer; ++j) {
+        f(s2sVecKey<DT>(v, j));
+      }
+    }
+  }
+}
+
+template <int DT, bool CACHED>
+FLTX_DEV double s2sLmRowLse(const S2sLmRowsParams& Q, S2sLmRowsLds& S, const void* row) {
+  constexpr int kElem = DT == kS2sDtF32 ? 4 : 2, kPer = 16 / kElem;
+  const int tid = (int)threadIdx.x, lane = laneId(), wave = waveId();
+  const int W = Q.width;
+  /* head: the elements before the first 16-byte boundary; body: whole vectors; tail: the rest */
+  int nHead = (int)(((16u - (uint32_t)((uintptr_t)row & 15u)) & 15u) / kElem);
+  nHead = nHead < W ? nHead : W;
+  const int nVec = (W - nHead) / kPer, nTail = W - nHead - nVec * kPer;
+  const uint4* body = (const uint4*)((const char*)row + (size_t)nHead * kElem);
+  const int nEdge = nHead + nTail; /* < 2 * kPer <= kS2sLmThreads */
+  const int edgeAt = tid < nHead ? tid : nHead + nVec * kPer + (tid - nHead);
+  uint4 vr[CACHED ? kS2sLmVecs : 1];
+  if constexpr (CACHED) {
+#pragma unroll
+    for (int q = 0; q < kS2sLmVecs; ++q) {
+      if (q * kS2sLmThreads < nVec && tid + q * kS2sLmThreads < nVec) {
+        vr[q] = body[tid + q * kS2sLmThreads];
+      }
+    }
+  }
+  uint32_t mk = 0u;
+  s2sLmEach<DT, CACHED>(row, nEdge, edgeAt, body, nVec, vr, [&](uint32_t k) { mk = k > mk ? k : mk; });
+  mk = waveMax32(mk);
+  if (lane == 0) {
+    S.wmax[wave] = mk;
+  }
+  __syncthreads();
+  for (int w = 0; w < kS2sLmThreads / 64; ++w) {
+    mk = S.wmax[w] > mk ? S.wmax[w] : mk;
+  }
+  const float mx = mk != 0u ? f32FromKey(mk) : -__builtin_huge_valf();
+  double lse = (double)mx;
+  if (mx - mx == 0.0f) { /* finite */
+    double s = 0.0;
+    s2sLmEach<DT, CACHED>(row, nEdge, edgeAt, body, nVec, vr, [&](uint32_t k) {
+      if (k != 0u) {
+        s += (double)expf(f32FromKey(k) - mx);
+      }
+    });
+    for (int d = 32; d >= 1; d >>= 1) { /* (the typed front end's butterfly: the same sum in every lane, run to run) */
+      s += __longlong_as_double((long long)waveShflXor64((unsigned long long)__double_as_longlong(s), d));
+    }
+    if (lane == 0) {
+      S.wsum[wave] = s;
+    }
+    __syncthreads();
+    s = 0.0;
+    for (int w = 0; w < kS2sLmThreads / 64; ++w) {
+      s += S.wsum[w];
+    }
+    lse = (double)mx + log(s);
+  }
+  return lse;
+}
+
+/* logits: workgroup = row b*K + k of the step */
+template <int DT>
+FLTX_DEV void s2sLmRowsLogits(const S2sLmRowsParams& Q, char* smem) {
+  const S2sParams& P = Q.s;
+  const int64_t r = (int64_t)blockIdx.x;
+  if (!s2sRowLive(P, r)) {
+    if (threadIdx.x == 0 && Q.rowLse) {
+      Q.rowLse[r] = __longlong_as_double(0x7FF8000000000000ll);
+    }
+    return;
+  }
+  S2sLmRowsLds& S = *(S2sLmRowsLds*)smem;
+  const void* row = (const char*)Q.x + r * Q.rowStride * (DT == kS2sDtF32 ? 4 : 2);
+  constexpr int kPer = DT == kS2sDtF32 ? 4 : 8;
+  const double lse = Q.width <= kS2sLmVecs * kS2sLmThreads * kPer ? s2sLmRowLse<DT, true>(Q, S, row)
+                                                                   : s2sLmRowLse<DT, false>(Q, S, row);
+  if (Q.rowLse && threadIdx.x == 0) {
+    Q.rowLse[r] = lse;
+  }
+  s2sLmGather<DT, true>(Q, r, row, lse, (int)threadIdx.x, kS2sLmThreads);
+}
+
+template <int DT, bool LOGITS>
+FLTX_DEV void s2sLmRows(const S2sLmRowsParams& Q, char* smem) {
+  if constexpr (LOGITS) {
+    s2sLmRowsLogits<DT>(Q, smem);
+  } else {
+    s2sLmRowsGather<DT>(Q, smem);
+  }
+}
+
+/* the step with the LM term from the records */
+FLTX_DEV void s2sStepUtteranceLmRows(const S2sLmRowsParams& Q, char* smem) {
+  s2sStepUtteranceOn<true>(Q.s, smem, Q.recLm);
 }
 
 } // namespace fltx
