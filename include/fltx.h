@@ -305,13 +305,22 @@ FLTX_API int fltx_s2s_step_typed(fltx_decoder* dec, const void* scores, int32_t 
  * usr_to_lm (may be NULL: identity, n_usr ignored): the LM index of the model's token u (ConvLM.cpp:40-49); every
  * entry must lie in [0, lm_width) when lm_width > 0, else FLTX_ERR_INVALID.  finish_index: the LM index LM::finish reads
  * (ConvLM.cpp:140-141: the LM's </s>); -1: usr_to_lm[eos] of the decoder.  The LM's per-hypothesis state is the
- * caller's, carried by index_select(next_src_row) as the model's is; every hypothesis has its own prefix and so its own
- * state: no merges.  Only fltx_s2s_decoder_create takes such an LM (the other decoders, fltx_group_create and the
- * fltx_lm_* state functions return FLTX_ERR_UNSUPPORTED).  At fltx_s2s_begin: FLTX_ERR_INVALID when a map has fewer than
- * V entries, or when a token's LM index or (eos < V) the finish index lies outside the LM's rows. */
+ * caller's, carried by index_select(next_src_row) as the model's is.
+ * Two decoders take such an LM: fltx_s2s_decoder_create (every hypothesis has its own prefix and so its own state: no
+ * merges) and fltx_s2s_lex_decoder_create with is_lm_token != 0 (a word-piece LM under a lexicon: hypotheses that
+ * segment one token string differently share a state and merge, see there).  The other decoders, a lexicon seq2seq
+ * decoder with is_lm_token == 0 (its rows would be as wide as the word vocabulary), fltx_group_create and the fltx_lm_*
+ * state functions return FLTX_ERR_UNSUPPORTED.
+ * The caller's obligation: the LM must be a pure function of the token prefix -- the same row for the same tokens since
+ * the start, whatever words they were cut into (LMState::child semantics, lm/LM.h:24-34; what a neural token LM fed
+ * its own prefix is).  Under the lexicon decoder the state a merged hypothesis carries on is the one
+ * index_select(next_src_row) picks, the best member's; that equals any member's only under this condition.
+ * At fltx_s2s_begin: FLTX_ERR_INVALID when a map has fewer than V entries, or when a token's LM index or (eos < V) the
+ * finish index lies outside the LM's rows. */
 FLTX_API int fltx_lm_rows_create(int32_t lm_width, const int32_t* usr_to_lm, int32_t n_usr, int32_t finish_index,
                                  fltx_lm** out);
-/* fltx_s2s_step_typed on a decoder made with a rows LM (LexiconFreeSeq2SeqDecoder.cpp:103-143): the token beam of a
+/* fltx_s2s_step_typed on a decoder of either seq2seq kind made with a rows LM (LexiconFreeSeq2SeqDecoder.cpp:103-143,
+ * LexiconSeq2SeqDecoder.cpp:94-198 with isLmToken): the token beam of a
  * row is taken from the model's scores alone; for each kept token n the LM score is a float -- in log-probs mode the LM
  * row's entry at usr_to_lm[n] (at finish_index when n == eos), widened exactly; in logits mode (float)((double)x -
  * lse_lm), lse_lm as fltx_s2s_step_typed defines lse, which lm_row_lse (may be NULL; B*K doubles on the device)
@@ -320,10 +329,19 @@ FLTX_API int fltx_lm_rows_create(int32_t lm_width, const int32_t* usr_to_lm, int
  * 0 * -inf) is never a candidate; a -inf LM entry behaves as a -inf model entry.  LM rows of padding rows and of rows
  * with row_valid 0 are never read.  The model's and the LM's rows have independent dtype, kind and stride
  * (lm_row_stride >= lm_width, in elements); both are device pointers, or both host pointers staged in their own types.
- * With lm_weight != 0 the exact token beam is kept (min(beam_size_token, V) <= 64); with lm_weight == 0 the shortcut of
- * ZeroLM stays (the row's best min(beam_size_token, beam_size + 1) tokens and eos) and the LM entries of those are
- * gathered for lmScore -- a NaN candidate among them is dropped, not replaced by a token beyond the shortcut.
- * fltx_s2s_step / fltx_s2s_step_typed on such a decoder, and this call on any other, return FLTX_ERR_STATE;
+ * Lexicon-free decoder: with lm_weight != 0 the exact token beam is kept (min(beam_size_token, V) <= 64); with
+ * lm_weight == 0 the shortcut of ZeroLM stays (the row's best min(beam_size_token, beam_size + 1) tokens and eos) and
+ * the LM entries of those are gathered for lmScore -- a NaN candidate among them is dropped, not replaced by a token
+ * beyond the shortcut.
+ * Lexicon decoder (is_lm_token != 0): always the exact token beam, min(beam_size_token, V) <= 256, taken before the trie
+ * filter; no shortcut at lm_weight == 0.  A kept token n of a hypothesis makes up to three kinds of candidate, which
+ * share the one LM entry of (row, n): eos at the trie root -- the entry at finish_index, new LM state child(state, -1),
+ * score ((h.score + am) + eos_score) + lm_weight * lm; the move to n's child in the trie -- the entry at usr_to_lm[n],
+ * new state child(state, n), score (h.score + am) + lm_weight * lm (no smearing term); and, when that child carries
+ * labels, the end of its first label's word -- the same entry and state, score ((h.score + am) + word_score) +
+ * lm_weight * lm, back at the root.  Candidates in one state, trie node and token merge (max or logAdd); the merged
+ * hypothesis keeps the best member's fields, next_src_row among them.
+ * fltx_s2s_step / fltx_s2s_step_typed on a decoder with a rows LM, and this call on any other, return FLTX_ERR_STATE;
  * FLTX_ERR_INVALID on a bad dtype or kind, a stride below the width, or NULL rows before the last step. */
 FLTX_API int fltx_s2s_step_lm_rows(fltx_decoder* dec,
     const void* scores, int32_t dtype, int32_t kind, int64_t row_stride,
@@ -358,8 +376,10 @@ typedef struct fltx_s2s_lex_options {
  * elsewhere).  Candidates in one LM state, trie node and token merge exactly as candidatesStore does (Utils.h:146-225:
  * max, or logAdd when log_add != 0).
  * Limits (FLTX_ERR_UNSUPPORTED beyond them; there is no CPU fallback): beam_size <= 256, V <= 65 536,
- * max_output_length <= 4 096, min(beam_size_token, V) <= 256 (fltx_s2s_begin), ZeroLM or n-gram LMs only (a host LM
- * is refused).  Each utterance names its LM states in a table of min(beam_size * max_output_length + 1, max_states)
+ * max_output_length <= 4 096, min(beam_size_token, V) <= 256 (fltx_s2s_begin, with any LM).  `lm`: ZeroLM, n-gram
+ * tables, or -- with is_lm_token != 0 only -- a rows LM (fltx_lm_rows_create: a neural token LM; the decoder then steps
+ * with fltx_s2s_step_lm_rows, which describes the candidates; the LM must be a pure function of the token prefix).  A
+ * host LM, and a rows LM with is_lm_token == 0 (word-level rows), are refused.  Each utterance names its LM states in a table of min(beam_size * max_output_length + 1, max_states)
  * entries (max_states: 65 536, or fltx_s2s_lex_set_max_states); an utterance that needs more stops, and
  * fltx_result_count reports FLTX_ERR_UNSUPPORTED ("LM-state table full") for it. */
 FLTX_API int fltx_s2s_lex_decoder_create(fltx_ctx* ctx, const fltx_s2s_lex_options* opt, const fltx_htrie* trie,

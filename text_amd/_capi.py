@@ -317,9 +317,9 @@ class NgramLM(ZeroLM):
 
 class RowsLM(ZeroLM):
     """fltx_lm_rows_create: an LM whose answers arrive per step as rows next to the model's rows (a neural token LM in
-    shallow fusion; Seq2SeqBatchDecoder.step(..., lm_scores=)).  lm_width: entries per LM row (0: the decoder's V);
-    usr_to_lm: the LM index of each model token (None: identity); finish_index: the LM index LM::finish reads (-1:
-    usr_to_lm[eos])."""
+    shallow fusion; Seq2SeqBatchDecoder.step(..., lm_scores=), and LexiconSeq2SeqBatchDecoder's with is_lm_token=True).
+    lm_width: entries per LM row (0: the decoder's V); usr_to_lm: the LM index of each model token (None: identity);
+    finish_index: the LM index LM::finish reads (-1: usr_to_lm[eos])."""
 
     def __init__(self, lm_width=0, usr_to_lm=None, finish_index=-1, lib=None):
         self.ctx, self.L = None, lib or default_lib()
@@ -845,6 +845,11 @@ class Seq2SeqBatchDecoder(BatchDecoder):
         self._emu = "emulation" in self.L.version()
         _live["dec"].add(self)
 
+    @property
+    def has_rows_lm(self):
+        """the decoder (either seq2seq kind) was made with a RowsLM: step() takes lm_scores"""
+        return isinstance(self._keep[0], RowsLM)
+
     def _rows(self):
         B, K = self.B, int(self.options.beam_size)
         if self._emu:  # (the emulator's "device" memory is host memory)
@@ -905,10 +910,9 @@ class Seq2SeqBatchDecoder(BatchDecoder):
         with one and refused otherwise (fltx_s2s_step_lm_rows)."""
         if kind not in S2S_KINDS or lm_kind not in S2S_KINDS:
             raise ValueError("kind: one of %s" % sorted(S2S_KINDS))
-        has_rows_lm = isinstance(self._keep[0], RowsLM)
-        if (lm_scores is not None) != has_rows_lm:
-            raise FltxError(ERR_STATE, "Seq2SeqBatchDecoder.step: lm_scores go with a decoder made with a RowsLM, and "
-                            "such a decoder takes them at every step")
+        if (lm_scores is not None) != self.has_rows_lm:
+            raise FltxError(ERR_STATE, "%s.step: lm_scores go with a decoder made with a RowsLM, and such a decoder "
+                            "takes them at every step" % type(self).__name__)
         out = self._rows()
         ptrs = [self._addr(o) for o in out]
         BK = self.B * int(self.options.beam_size)
@@ -972,8 +976,13 @@ class Seq2SeqBatchDecoder(BatchDecoder):
 class LexiconSeq2SeqBatchDecoder(Seq2SeqBatchDecoder):
     """fltx_s2s_lex_*: LexiconSeq2SeqDecoder for B utterances at once, with Seq2SeqBatchDecoder's begin / step / done /
     end / decode loop and row contract.  `trie` is a HostTrie (already smeared) or anything with an fltx_htrie handle
-    `.h`; `lm` a ZeroLM / n-gram LM of this module (words are its user ids, tokens when is_lm_token).  The results
-    carry words."""
+    `.h`; `lm` a ZeroLM / n-gram LM of this module (words are its user ids, tokens when is_lm_token), or -- with
+    is_lm_token=True only -- a RowsLM: a neural token LM whose rows go to step(..., lm_scores=) next to the model's,
+    exactly as on Seq2SeqBatchDecoder (a word-level RowsLM is refused).  A row's token move, its word end and eos read
+    the row's one LM entry (usr_to_lm[token]; finish_index for eos); there is no shortcut at lm_weight == 0; the token
+    beam min(beam_size_token, V) is at most 256.  The LM must be a pure function of the token prefix: hypotheses that
+    spell one token string differently share an LM state and merge, and the merged survivor's next_src_row is the best
+    member's -- index_select the LM's state by it as the model's.  The results carry words."""
 
     def __init__(self, ctx, options, trie, lm, eos, max_output_length, is_lm_token=False):
         self.ctx, self.L = ctx, ctx.L

@@ -203,7 +203,12 @@ class LexiconSeq2SeqDecoder:
     (options, lm, trie, eos_idx, update_func, max_output_length, is_token_lm) -- the second parameter is named `lm`
     and takes the Trie, the third is named `trie` and takes the LM, as there.  The trie is the compat package's Trie
     (or a text_amd._capi.HostTrie), already smeared; the LM ZeroLM / KenLM (or a text_amd._capi LM object).
-    update_func sees -1 for every beam index, as the reference's does."""
+    update_func sees -1 for every beam index, as the reference's does.
+
+    With a text_amd._capi.RowsLM and is_token_lm=True (a neural word-piece LM in shallow fusion) update_func returns
+    three elements, (scores, states, lm_scores), as LexiconFreeSeq2SeqDecoder's does: row k of lm_scores holds the LM's
+    log-probabilities of every LM index after the hypothesis of row k.  The LM must be a pure function of the token
+    prefix (hypotheses that spell one token string differently merge; the best member's state object survives)."""
 
     def __init__(self, options, lm, trie, eos_idx, update_func, max_output_length, is_token_lm):
         self.options, self.eos = options, int(eos_idx)
@@ -219,7 +224,7 @@ class LexiconSeq2SeqDecoder:
 
     def decode_step(self, emissions, T, N):
         self._hyps = _decode(self._dec, self.options.beam_size, self.update_func, self.max_output_length, emissions, T,
-                             N, raw_beam_idx=False)
+                             N, raw_beam_idx=False, rows_lm=isinstance(self._lm, _capi.RowsLM))
 
     def prune(self, look_back=0):
         return None

@@ -179,6 +179,11 @@ __global__ void __launch_bounds__(kS2sStepThreads) fltx_s2s_lex_step_kernel(S2lP
   __shared__ __attribute__((aligned(16))) S2lStepLds fltx_s2l_lds;
   s2lStepUtterance(Q, (char*)&fltx_s2l_lds);
 }
+/* ... with a rows LM: after fltx_s2s_lm_rows_kernel, the LM term read from the records */
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_s2s_lex_step_lm_rows_kernel(S2lLmRowsParams R) {
+  __shared__ __attribute__((aligned(16))) S2lStepLds fltx_s2l_lm_lds;
+  s2lStepUtteranceLmRows(R, (char*)&fltx_s2l_lm_lds);
+}
 __global__ void __launch_bounds__(kS2sBeginThreads) fltx_s2s_lex_begin_kernel(S2lParams Q) {
   s2lBeginUtterance(Q, nullptr);
 }
@@ -1626,7 +1631,7 @@ int fltx_decoder_create(fltx_ctx* ctx, int32_t kind, const fltx_options* opt, co
     return fail(FLTX_ERR_INVALID, "unknown decoder kind %d", kind);
   }
   if (lm->kind == 3) {
-    return fail(FLTX_ERR_UNSUPPORTED, "a rows LM (fltx_lm_rows_create) serves the lexicon-free seq2seq decoder only");
+    return fail(FLTX_ERR_UNSUPPORTED, "a rows LM (fltx_lm_rows_create) serves the seq2seq decoders only");
   }
   if (kind == FLTX_DECODER_LEXICON && !trie) {
     return fail(FLTX_ERR_INVALID, "lexicon decoder needs a trie");
@@ -5150,9 +5155,10 @@ int fltx_s2s_lex_decoder_create(fltx_ctx* ctx, const fltx_s2s_lex_options* opt, 
   if (!ctx || !opt || !trie || !lm || !out) {
     return fail(FLTX_ERR_INVALID, "fltx_s2s_lex_decoder_create: null argument");
   }
-  if (lm->kind == 3) {
-    /* (a token-level LM here shares states between segmentations: it needs this step's merge keys) */
-    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq lexicon: a rows LM (fltx_lm_rows_create) is not supported");
+  if (lm->kind == 3 && !isLmToken) {
+    /* (its rows would be as wide as the word vocabulary: DESIGN section 7) */
+    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq lexicon: a word-level rows LM (fltx_lm_rows_create with is_lm_token == 0) "
+                                      "is not supported");
   }
   fltx_s2s_options o{};
   o.beam_size = opt->beam_size;
@@ -5228,6 +5234,36 @@ int fltx_s2s_lex_info(fltx_decoder* d, int64_t* trieBytes, int64_t* nNodes, int6
 
 /* fltx_s2s_begin's parts that depend on the kind: the token beam the front end keeps (mSel / eosExtra / cap) and the
  * candidates per step (*nC); with a lexicon also the sizes of its tables, and then the buffers only it has */
+/* a rows LM: every index the gather can form lies inside the LM's rows (either decoder kind) */
+static int s2sPlanRowsLm(fltx_decoder* d, int32_t V) {
+  const fltx_lm* lm = d->lm;
+  const int eos = d->s2s.eos;
+  const int width = lm->rowsWidth > 0 ? lm->rowsWidth : V;
+  if (lm->rowsMap && V > lm->nUsr) {
+    return fail(FLTX_ERR_INVALID, "seq2seq rows LM: V = %d > the %d entries of usr_to_lm", V, lm->nUsr);
+  }
+  int finish = lm->rowsFinish;
+  if (finish < 0 && eos < V) {
+    finish = lm->rowsMap ? lm->hUsr[(size_t)eos] : eos;
+  }
+  if (eos < V && (finish < 0 || finish >= width)) {
+    return fail(FLTX_ERR_INVALID, "seq2seq rows LM: finish index %d outside the LM's rows of %d", finish, width);
+  }
+  if (lm->rowsMap) {
+    for (int u = 0; u < V; ++u) {
+      if (lm->hUsr[(size_t)u] < 0 || lm->hUsr[(size_t)u] >= width) {
+        return fail(FLTX_ERR_INVALID, "seq2seq rows LM: usr_to_lm[%d] = %d outside the LM's rows of %d (lm_width 0: V)",
+                    u, lm->hUsr[(size_t)u], width);
+      }
+    }
+  } else if (width < V) {
+    return fail(FLTX_ERR_INVALID, "seq2seq rows LM: lm_width %d < V = %d without a map", width, V);
+  }
+  d->s2s.lmWidth = width;
+  d->s2s.lmFinish = eos < V ? finish : 0; /* (eos >= V is never proposed: finish is never read) */
+  return FLTX_OK;
+}
+
 static int s2sPlanLexFree(fltx_decoder* d, int32_t V, int64_t* nC) {
   const int K = d->s2s.opt.beam_size, Kt = d->s2s.opt.beam_size_token;
   const int ktEff = std::min(Kt, V);
@@ -5242,32 +5278,8 @@ static int s2sPlanLexFree(fltx_decoder* d, int32_t V, int64_t* nC) {
   d->s2s.eosExtra = d->s2s.mSel < ktEff ? 1 : 0;
   d->s2s.cap = d->s2s.mSel + d->s2s.eosExtra;
   *nC = (int64_t)K * d->s2s.cap + K;
-  if (d->lm->kind == 3) { /* a rows LM: every index the gather can form lies inside the LM's rows */
-    const fltx_lm* lm = d->lm;
-    const int eos = d->s2s.eos;
-    const int width = lm->rowsWidth > 0 ? lm->rowsWidth : V;
-    if (lm->rowsMap && V > lm->nUsr) {
-      return fail(FLTX_ERR_INVALID, "seq2seq rows LM: V = %d > the %d entries of usr_to_lm", V, lm->nUsr);
-    }
-    int finish = lm->rowsFinish;
-    if (finish < 0 && eos < V) {
-      finish = lm->rowsMap ? lm->hUsr[(size_t)eos] : eos;
-    }
-    if (eos < V && (finish < 0 || finish >= width)) {
-      return fail(FLTX_ERR_INVALID, "seq2seq rows LM: finish index %d outside the LM's rows of %d", finish, width);
-    }
-    if (lm->rowsMap) {
-      for (int u = 0; u < V; ++u) {
-        if (lm->hUsr[(size_t)u] < 0 || lm->hUsr[(size_t)u] >= width) {
-          return fail(FLTX_ERR_INVALID, "seq2seq rows LM: usr_to_lm[%d] = %d outside the LM's rows of %d (lm_width 0: V)",
-                      u, lm->hUsr[(size_t)u], width);
-        }
-      }
-    } else if (width < V) {
-      return fail(FLTX_ERR_INVALID, "seq2seq rows LM: lm_width %d < V = %d without a map", width, V);
-    }
-    d->s2s.lmWidth = width;
-    d->s2s.lmFinish = eos < V ? finish : 0; /* (eos >= V is never proposed: finish is never read) */
+  if (d->lm->kind == 3) {
+    return s2sPlanRowsLm(d, V);
   }
   return FLTX_OK;
 }
@@ -5289,6 +5301,9 @@ static int s2sPlanLexicon(fltx_decoder* d, int32_t V, int64_t* nC) {
   d->s2s.mSize = s2lPow2AtLeast(2 * *nC);
   d->s2s.sMax = (int)std::min<int64_t>((int64_t)K * d->s2s.maxOut + 1, d->s2s.maxStates);
   d->s2s.sSize = s2lPow2AtLeast(2 * (int64_t)d->s2s.sMax);
+  if (d->lm->kind == 3) { /* (the token beam's limit stays kS2lMaxKt: kS2sMaxKtLm is the lexicon-free step's) */
+    return s2sPlanRowsLm(d, V);
+  }
   return FLTX_OK;
 }
 
@@ -5400,7 +5415,7 @@ struct S2sLmIn {
 
 /* one step of either kind (the entry points have checked the decoder, `what` names the one that was called): the front
  * end the input asks for -- fltx_s2s_tokbeam_kernel for float log-probs, else the typed one (fltx_s2s.h: s2sTypedRows)
- * -- then the kind's step kernel */
+ * -- then, with a rows LM, the gather of the records' LM scores, then the kind's step kernel */
 static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_t dtype, bool logits, int32_t onDevice,
                    int64_t rowStride, const uint8_t* rowValid, double* rowLse, int32_t* nextTok, int32_t* nextBeam,
                    int32_t* nextSrc, int32_t* nRows, const S2sLmIn* lmIn = nullptr) {
@@ -5484,7 +5499,7 @@ static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_
       return rc;
     }
   }
-  if (d->kind == FLTX_DECODER_S2S_LEXICON) {
+  if (d->kind == FLTX_DECODER_S2S_LEXICON && !lmIn) {
     S2S_LAUNCH(fltx_s2s_lex_step_kernel, s2lStepUtterance, d->B, kS2sStepThreads, sizeof(S2lStepLds), st, Q);
   } else if (lmIn) {
     S2sLmRowsParams R;
@@ -5510,7 +5525,15 @@ static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_
         return rc;
       }
     }
-    S2S_LAUNCH(fltx_s2s_step_lm_rows_kernel, s2sStepUtteranceLmRows, d->B, kS2sStepThreads, sizeof(S2sStepLds), st, R);
+    if (d->kind == FLTX_DECODER_S2S_LEXICON) {
+      S2lLmRowsParams RL;
+      RL.q = Q;
+      RL.recLm = R.recLm;
+      S2S_LAUNCH(fltx_s2s_lex_step_lm_rows_kernel, s2lStepUtteranceLmRows, d->B, kS2sStepThreads, sizeof(S2lStepLds), st,
+                 RL);
+    } else {
+      S2S_LAUNCH(fltx_s2s_step_lm_rows_kernel, s2sStepUtteranceLmRows, d->B, kS2sStepThreads, sizeof(S2sStepLds), st, R);
+    }
   } else {
     S2S_LAUNCH(fltx_s2s_step_kernel, s2sStepUtterance, d->B, kS2sStepThreads, sizeof(S2sStepLds), st, P);
   }
@@ -5569,7 +5592,7 @@ int fltx_s2s_step_lm_rows(fltx_decoder* d, const void* scores, int32_t dtype, in
   if (rc) {
     return rc;
   }
-  if (d->kind != FLTX_DECODER_S2S_LEXFREE || d->lm->kind != 3) {
+  if (d->lm->kind != 3) {
     return fail(FLTX_ERR_STATE, "fltx_s2s_step_lm_rows: the decoder has no rows LM (fltx_lm_rows_create)");
   }
   if ((dtype != FLTX_DTYPE_F32 && dtype != FLTX_DTYPE_F16 && dtype != FLTX_DTYPE_BF16) ||

@@ -22,6 +22,15 @@
  * order (max, or logAdd's max + log1p(exp(min - max)) from the best), the best member's fields survive.  The <= K
  * survivors that enter a new state get a canonical id from the utterance's lookup-or-insert table in HBM, which lives
  * across steps (a state can be born again at a later step); a full table stops the utterance with ST_TABLE_FULL.
+ *
+ * LM rows.  With a rows LM (fltx_lm_rows_create, a token LM: isLmToken) the step is three kernels: the front end,
+ * fltx_s2s_lm_rows_kernel (fltx_s2s.h, unchanged: one float per record entry into recLm -- usrToLm[token], the finish
+ * index for eos) and fltx_s2s_lex_step_lm_rows_kernel, this step with its LM term read from recLm.  Where the LM term
+ * comes from is a template parameter (REC) as in s2sStepUtteranceOn, so fltx_s2s_lex_step_kernel compiles to what it
+ * was.  Under REC the token move, the word end (the first label) and eos of a record entry share its one LM entry and
+ * all enter a new state: child(h.sid, token), or child(h.sid, -1) for eos (finish is its own child, as KenLM's) --
+ * LexiconSeq2SeqDecoder.cpp:115-198 with isLmToken.  The LM's state is the token prefix, so two segmentations of one
+ * token string carry the same (parent sid, edge) and merge by the keys above.  No n-gram walk: ctx stays ctx0.
  */
 #pragma once
 
@@ -120,9 +129,10 @@ struct S2lCand {
 };
 
 /* candidate j of the utterance: record slot j < nRowC (row k, entry e, sub-slot s: 0 = stay / eos, 1.. = the labels),
- * then the carried hypotheses; false: no candidate */
-FLTX_DEV bool s2lCand(const S2lParams& Q, const S2lHyp* prev, const int32_t* hypOfRow, int64_t rb, int64_t nRowC,
-                      int64_t j, S2lCand& c) {
+ * then the carried hypotheses; false: no candidate.  REC: the LM term of all three kinds is recLm[r * cap + e] */
+template <bool REC>
+FLTX_DEV bool s2lCand(const S2lParams& Q, const float* recLm, const S2lHyp* prev, const int32_t* hypOfRow, int64_t rb,
+                      int64_t nRowC, int64_t j, S2lCand& c) {
   const S2sParams& P = Q.s;
   if (j >= nRowC) {
     const int i = (int)(j - nRowC);
@@ -160,11 +170,16 @@ FLTX_DEV bool s2lCand(const S2lParams& Q, const S2lHyp* prev, const int32_t* hyp
     if (s != 0 || h.node != 0) {
       return false;
     }
-    c.lmS = s2sLm(P, h.ctx, kS2sLmFinish, kS2sLmFinish, nullptr) - 0.0f; /* (lexMaxScore is 0 at the root) */
+    if constexpr (REC) { /* LM::finish: the entry at the finish index, a child of its own */
+      c.lmS = recLm[r * cap + e];
+      c.isNew = true;
+    } else {
+      c.lmS = s2sLm(P, h.ctx, kS2sLmFinish, kS2sLmFinish, nullptr) - 0.0f; /* (lexMaxScore is 0 at the root) */
+      c.isNew = P.lmOn != 0;
+    }
     c.score = (((h.score + (double)a) + P.eosScore) + P.lmWeight * (double)c.lmS);
     c.word = -1;
     c.node = 0;
-    c.isNew = P.lmOn != 0;
     c.newEdge = -1;
     c.usr = kS2sLmFinish;
     return true;
@@ -172,6 +187,21 @@ FLTX_DEV bool s2lCand(const S2lParams& Q, const S2lHyp* prev, const int32_t* hyp
   const int child = s2lChild(Q.trie, h.node, tok); /* (2) a normal token: a child of the hypothesis' node */
   if (child < 0) {
     return false;
+  }
+  if constexpr (REC) { /* a token LM: the move and the word end (the first label) share the entry and the new state */
+    const int l0 = Q.trie.labOff[child];
+    if (s > 1 || (s == 1 && Q.trie.labOff[child + 1] == l0)) {
+      return false;
+    }
+    c.lmS = recLm[r * cap + e];
+    c.isNew = true;
+    c.newEdge = tok;
+    c.usr = tok;
+    c.word = s == 0 ? -1 : Q.trie.labels[l0];
+    c.node = s == 0 ? child : 0;
+    c.score = s == 0 ? (h.score + (double)a) + P.lmWeight * (double)c.lmS
+                     : ((h.score + (double)a) + Q.wordScore) + P.lmWeight * (double)c.lmS;
+    return true;
   }
   const float lexMax = h.node == 0 ? 0.0f : Q.trie.maxScore[h.node];
   if (s == 0) { /* stay in the trie (:146-171) */
@@ -227,7 +257,8 @@ struct S2lStepLds {
   int32_t full;
 };
 
-FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) {
+template <bool REC>
+FLTX_DEV void s2lStepUtteranceOn(const S2lParams& Q, char* smem, const float* recLm) {
   const S2sParams& P = Q.s;
   S2lStepLds& L = *(S2lStepLds*)smem;
   S2sStepLds& S = L.s;
@@ -265,7 +296,7 @@ FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) {
   for (int64_t j = tid; j < n; j += kS2sStepThreads) {
     unsigned long long key = 0ull;
     S2lCand c;
-    if (s2lCand(Q, prev, S.hypOfRow, rb, nRowC, j, c)) {
+    if (s2lCand<REC>(Q, recLm, prev, S.hypOfRow, rb, nRowC, j, c)) {
       key = s2sScoreKey(c.score);
       cScore[j] = c.score;
       cMk[j] = s2lMergeKey(c, prev[c.hyp]);
@@ -365,7 +396,7 @@ FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) {
   int32_t* sVal = Q.sVal + (size_t)b * Q.sSize;
   if (tid < nSel) {
     const int64_t j = S.selIdx[S.order[tid]];
-    s2lCand(Q, prev, S.hypOfRow, rb, nRowC, j, c);
+    s2lCand<REC>(Q, recLm, prev, S.hypOfRow, rb, nRowC, j, c);
     const S2lHyp& h = prev[c.hyp];
     nh = h;
     nh.parent = c.hyp;
@@ -379,8 +410,10 @@ FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) {
       if (c.isNew) {
         nh.psid = h.sid;
         nh.edge = c.newEdge;
-        if (P.lmOn) {
-          (void)s2sLm(P, h.ctx, c.usr, kS2sLmFinish, nh.ctx);
+        if constexpr (!REC) {
+          if (P.lmOn) {
+            (void)s2sLm(P, h.ctx, c.usr, kS2sLmFinish, nh.ctx);
+          }
         }
         skey = s2lPair(nh.psid, nh.edge);
         hasNew = true;
@@ -446,6 +479,18 @@ FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) {
     Q.merges[b] += nMerged;
   }
   s2sPublishStep(P, S, b, nSel, isLive, token, parent, srcRow);
+}
+
+FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) { s2lStepUtteranceOn<false>(Q, smem, nullptr); }
+
+/* the step with the LM term from the records (a rows LM) */
+struct S2lLmRowsParams {
+  S2lParams q;
+  const float* recLm; /* [B*K][cap], as fltx_s2s_lm_rows_kernel gathered it */
+};
+
+FLTX_DEV void s2lStepUtteranceLmRows(const S2lLmRowsParams& R, char* smem) {
+  s2lStepUtteranceOn<true>(R.q, smem, R.recLm);
 }
 
 /* decodeStep's start (:29-31): the root in LM::start's state (sid 0) at the trie's root */
