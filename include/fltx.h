@@ -309,8 +309,8 @@ FLTX_API int fltx_s2s_step_typed(fltx_decoder* dec, const void* scores, int32_t 
  * Two decoders take such an LM: fltx_s2s_decoder_create (every hypothesis has its own prefix and so its own state: no
  * merges) and fltx_s2s_lex_decoder_create with is_lm_token != 0 (a word-piece LM under a lexicon: hypotheses that
  * segment one token string differently share a state and merge, see there).  The other decoders, a lexicon seq2seq
- * decoder with is_lm_token == 0 (its rows would be as wide as the word vocabulary), fltx_group_create and the fltx_lm_*
- * state functions return FLTX_ERR_UNSUPPORTED.
+ * decoder with is_lm_token == 0 (word-level rows come in by fltx_lm_word_rows_create below), fltx_group_create and the
+ * fltx_lm_* state functions return FLTX_ERR_UNSUPPORTED.
  * The caller's obligation: the LM must be a pure function of the token prefix -- the same row for the same tokens since
  * the start, whatever words they were cut into (LMState::child semantics, lm/LM.h:24-34; what a neural token LM fed
  * its own prefix is).  Under the lexicon decoder the state a merged hypothesis carries on is the one
@@ -348,6 +348,54 @@ FLTX_API int fltx_s2s_step_lm_rows(fltx_decoder* dec,
     const void* lm_scores, int32_t lm_dtype, int32_t lm_kind, int64_t lm_row_stride,
     int32_t on_device, const uint8_t* row_valid, double* row_lse, double* lm_row_lse,
     int32_t* next_token, int32_t* next_beam_idx, int32_t* next_src_row, int32_t* n_rows);
+/* A word-level rows LM: a neural LM over the lexicon's WORDS (a word-level ConvLM / transformer LM) in shallow fusion
+ * under fltx_s2s_lex_decoder_create with is_lm_token == 0 -- spellings constrained by the trie, whole words scored by the
+ * LM, the smeared trie standing in for the LM inside a word.  lm_width (required, 0 < lm_width <= 4 194 304 = 2^22;
+ * FLTX_ERR_UNSUPPORTED beyond): entries per LM row; every row offset is formed in 64 bits.  word_to_lm (may be NULL:
+ * identity, n_words ignored): the LM index of the lexicon's word id w (a trie label).  finish_index (required, >= 0:
+ * eos is a token and has no word id): the LM index LM::finish reads.  Only fltx_s2s_lex_decoder_create with
+ * is_lm_token == 0 takes such an LM; that decoder with is_lm_token != 0, fltx_s2s_decoder_create, fltx_decoder_create,
+ * fltx_group_create and the fltx_lm_* state functions return FLTX_ERR_UNSUPPORTED ("rows LM").  The trie is known at
+ * fltx_s2s_lex_decoder_create, which returns FLTX_ERR_INVALID when a label w of the trie has no entry in a given map
+ * (w >= n_words) or an LM index outside [0, lm_width), or when finish_index lies outside [0, lm_width).
+ * The caller's obligation (the token-level one above, for words): the LM must be a pure function of the WORD prefix --
+ * the same row for the same words since the start, however they were spelled.  Hypotheses in one LM state, trie node
+ * and token merge; the state that lives on is the one index_select(next_src_row) picks, the best member's, which equals
+ * any member's only under this condition. */
+FLTX_API int fltx_lm_word_rows_create(int32_t lm_width, const int32_t* word_to_lm, int32_t n_words, int32_t finish_index,
+                                      fltx_lm** out);
+/* The step of a decoder made with a word-level rows LM (LexiconSeq2SeqDecoder.cpp:91-198 with isLmToken == false).  The
+ * model's rows are fltx_s2s_step_lm_rows' in every respect: dtypes, kinds, strides in elements, host staging, row_valid,
+ * row_lse, the no-op step after the last one, asynchrony.
+ * The LM's state changes only where a word ends, so most hypotheses carry the state they had a step ago and many share
+ * one: lm_scores holds n_lm_rows rows of lm_width entries (lm_row_stride >= lm_width), and lm_row_of (B*K int32; a device
+ * pointer when on_device, else a host pointer, staged) names the LM row of each decoder row -- one LM row can serve
+ * many.  lm_row_of == NULL: identity, n_lm_rows is ignored and taken as B*K.  An entry outside [0, n_lm_rows) on a live
+ * row makes that row's LM entries NaN: it keeps its moves inside words and has no word-end and no eos candidate;
+ * nothing is read through it.  lm_row_lse (may be NULL; B*K doubles on the device, indexed by DECODER row) receives in
+ * logits mode the lse of the LM row each live decoder row names, NaN for the other rows.  A shared LM row has its lse
+ * computed once per decoder row that names it -- the same bits every time; the work is duplicated, not deduplicated.
+ * The token beam is the exact min(beam_size_token, V) <= 256 largest model scores, before the trie filter.  A kept
+ * token n of hypothesis h makes three kinds of candidate: eos at the trie root -- lm = the entry at finish_index (minus
+ * lexMaxScore, 0 at the root), new LM state child(state, -1), score ((h.score + am) + eos_score) + lm_weight * lm; the
+ * move to n's child -- no LM entry is read, lm = maxScore[child] - lexMaxScore in float (smearing), the state unchanged;
+ * and one word end per label w of that child -- lm = (float)entry(word_to_lm[w]) - lexMaxScore (a float subtraction),
+ * new state child(state, w), score ((h.score + am) + word_score) + lm_weight * lm, back at the root.  am and lm
+ * accumulate separately, also at lm_weight == 0; a NaN score is never a candidate; a -inf entry behaves as a -inf model
+ * entry.  Log-probs rows cost about rows * min(beam_size_token, V) * (1 + labels) element reads, whatever lm_width.
+ * next_word (required; B*K int32 on the device): for every listed row the word its hypothesis ended in this step, -1
+ * when it ended none, -1 on padding rows (fltx_s2s_begin lists the root, which ended none: nothing to write there).
+ * With next_src_row it is all the caller's LM needs: next_word[r] < 0 -- the state, and its LM row, are those of
+ * next_src_row[r]; else the caller advances that state by the word and makes a new row.
+ * fltx_s2s_step / _typed / _lm_rows on such a decoder, and this call on any other, return FLTX_ERR_STATE;
+ * FLTX_ERR_INVALID on a bad dtype or kind, a stride below the width, NULL next_word, n_lm_rows < 1 with lm_row_of, or
+ * NULL rows before the last step. */
+FLTX_API int fltx_s2s_step_word_lm_rows(fltx_decoder* dec,
+    const void* scores, int32_t dtype, int32_t kind, int64_t row_stride,
+    const void* lm_scores, int32_t lm_dtype, int32_t lm_kind, int64_t lm_row_stride,
+    const int32_t* lm_row_of, int32_t n_lm_rows,
+    int32_t on_device, const uint8_t* row_valid, double* row_lse, double* lm_row_lse,
+    int32_t* next_token, int32_t* next_beam_idx, int32_t* next_src_row, int32_t* next_word, int32_t* n_rows);
 /* *done = 1 when every utterance is done (no live hypothesis, or max_output_length steps); synchronises. */
 FLTX_API int fltx_s2s_done(fltx_decoder* dec, int32_t* done);
 /* The back-trace (:152-163): every utterance's final beam -- the last non-empty one, which may hold unfinished
@@ -377,10 +425,12 @@ typedef struct fltx_s2s_lex_options {
  * max, or logAdd when log_add != 0).
  * Limits (FLTX_ERR_UNSUPPORTED beyond them; there is no CPU fallback): beam_size <= 256, V <= 65 536,
  * max_output_length <= 4 096, min(beam_size_token, V) <= 256 (fltx_s2s_begin, with any LM).  `lm`: ZeroLM, n-gram
- * tables, or -- with is_lm_token != 0 only -- a rows LM (fltx_lm_rows_create: a neural token LM; the decoder then steps
- * with fltx_s2s_step_lm_rows, which describes the candidates; the LM must be a pure function of the token prefix).  A
- * host LM, and a rows LM with is_lm_token == 0 (word-level rows), are refused.  Each utterance names its LM states in a table of min(beam_size * max_output_length + 1, max_states)
- * entries (max_states: 65 536, or fltx_s2s_lex_set_max_states); an utterance that needs more stops, and
+ * tables, with is_lm_token != 0 a rows LM (fltx_lm_rows_create: a neural token LM; the decoder then steps with
+ * fltx_s2s_step_lm_rows, which describes the candidates; the LM must be a pure function of the token prefix), or with
+ * is_lm_token == 0 a word-level rows LM (fltx_lm_word_rows_create: a neural word LM; the decoder steps with
+ * fltx_s2s_step_word_lm_rows; a pure function of the word prefix).  A host LM, a fltx_lm_rows_create LM with
+ * is_lm_token == 0 and a fltx_lm_word_rows_create LM with is_lm_token != 0 are refused.  Each utterance names its LM
+ * states in a table of min(beam_size * max_output_length + 1, max_states) entries (max_states: 65 536, or fltx_s2s_lex_set_max_states); an utterance that needs more stops, and
  * fltx_result_count reports FLTX_ERR_UNSUPPORTED ("LM-state table full") for it. */
 FLTX_API int fltx_s2s_lex_decoder_create(fltx_ctx* ctx, const fltx_s2s_lex_options* opt, const fltx_htrie* trie,
                                          const fltx_lm* lm, int32_t eos, int32_t max_output_length,

@@ -92,6 +92,7 @@ class Lib:
         "fltx_s2s_decoder_create", "fltx_s2s_begin", "fltx_s2s_step", "fltx_s2s_step_typed", "fltx_s2s_done",
         "fltx_s2s_end", "fltx_s2s_lex_decoder_create", "fltx_s2s_lex_set_max_states", "fltx_s2s_lex_info",
         "fltx_lm_rows_create", "fltx_s2s_step_lm_rows",
+        "fltx_lm_word_rows_create", "fltx_s2s_step_word_lm_rows",
     ]
 
     def __init__(self, path=None):
@@ -167,6 +168,9 @@ class Lib:
             "fltx_s2s_step_typed": [vp, vp, i32, i32, i32, i64, vp, vp, vp, vp, vp, vp],
             "fltx_lm_rows_create": [i32, vp, i32, i32, pvp],
             "fltx_s2s_step_lm_rows": [vp, vp, i32, i32, i64, vp, i32, i32, i64, i32, vp, vp, vp, vp, vp, vp, vp],
+            "fltx_lm_word_rows_create": [i32, vp, i32, i32, pvp],
+            "fltx_s2s_step_word_lm_rows": [vp, vp, i32, i32, i64, vp, i32, i32, i64, vp, i32, i32, vp, vp, vp, vp, vp, vp,
+                                           vp, vp],
             "fltx_s2s_done": [vp, vp],
             "fltx_s2s_end": [vp],
             "fltx_s2s_lex_decoder_create": [vp, C.POINTER(S2sLexOptions), vp, vp, i32, i32, i32, pvp],
@@ -329,6 +333,24 @@ class RowsLM(ZeroLM):
                                                     0 if um is None else len(um), int(finish_index), C.byref(h)))
         self.h = h
         self.lm_width, self.usr_to_lm, self.finish_index = int(lm_width), um, int(finish_index)
+        _live["lm"].add(self)
+
+
+class WordRowsLM(RowsLM):
+    """fltx_lm_word_rows_create: a neural LM over the lexicon's WORDS whose answers arrive per step as rows
+    (LexiconSeq2SeqBatchDecoder with is_lm_token=False; step(..., lm_scores=, lm_row_of=)).  lm_width: entries per LM
+    row (required, at most 2**22); word_to_lm: the LM index of each lexicon word id (None: identity); finish_index: the
+    LM index LM::finish reads (required: eos is a token and has no word id).  No other decoder takes it."""
+
+    def __init__(self, lm_width, word_to_lm=None, finish_index=0, lib=None):
+        self.ctx, self.L = None, lib or default_lib()
+        wm = None if word_to_lm is None else np.ascontiguousarray(word_to_lm, dtype=np.int32)
+        h = C.c_void_p()
+        self.L.check(self.L.lib.fltx_lm_word_rows_create(int(lm_width), None if wm is None else _ptr(wm),
+                                                         0 if wm is None else len(wm), int(finish_index), C.byref(h)))
+        self.h = h
+        self.lm_width, self.word_to_lm, self.finish_index = int(lm_width), wm, int(finish_index)
+        self.usr_to_lm = wm
         _live["lm"].add(self)
 
 
@@ -1002,6 +1024,82 @@ class LexiconSeq2SeqBatchDecoder(Seq2SeqBatchDecoder):
 
     def set_max_states(self, n):
         self.L.check(self.L.lib.fltx_s2s_lex_set_max_states(self.h, int(n)))
+
+    @property
+    def has_word_rows_lm(self):
+        """the decoder was made with a WordRowsLM: step() takes lm_scores / lm_row_of and returns next_word too"""
+        return isinstance(self._keep[0], WordRowsLM)
+
+    def step(self, scores, row_valid=None, *, lm_row_of=None, **kw):
+        """Seq2SeqBatchDecoder.step.  With a WordRowsLM (is_lm_token=False): lm_scores is [n_lm_rows, >= lm_width], one
+        row per LM STATE, and lm_row_of (None: identity, lm_scores then has B*K rows) B*K int32 -- a device tensor, or
+        numpy on the host side -- naming the LM row of each decoder row; an entry outside [0, n_lm_rows) takes the
+        row's word ends and eos away.  Returns (token, beam_idx, src_row, n_rows, next_word): next_word [B, K] int32
+        is the word each listed row's hypothesis ended in this step, -1 for none and on padding rows.  The caller's
+        recipe: the LM state of next row r is that of row src_row[r] when next_word[r] < 0 (reuse its LM row), else
+        that state advanced by next_word[r] (run the LM for it alone).  The LM must be a pure function of the word
+        prefix.  lm_lse_out is indexed by decoder row (fltx_s2s_step_word_lm_rows)."""
+        if not self.has_word_rows_lm:
+            if lm_row_of is not None:
+                raise FltxError(ERR_STATE, "%s.step: lm_row_of goes with a decoder made with a WordRowsLM"
+                                % type(self).__name__)
+            return super().step(scores, row_valid, **kw)
+        kind, lm_kind = kw.pop("kind", "log_probs"), kw.pop("lm_kind", "log_probs")
+        lse_out, lm_lse_out = kw.pop("lse_out", None), kw.pop("lm_lse_out", None)
+        dtype, lm_dtype, lm_scores = kw.pop("dtype", None), kw.pop("lm_dtype", None), kw.pop("lm_scores", None)
+        if kw:
+            raise TypeError("step: unexpected arguments %s" % sorted(kw))
+        if kind not in S2S_KINDS or lm_kind not in S2S_KINDS:
+            raise ValueError("kind: one of %s" % sorted(S2S_KINDS))
+        if lm_scores is None:
+            raise FltxError(ERR_STATE, "%s.step: a decoder made with a WordRowsLM takes lm_scores at every step"
+                            % type(self).__name__)
+        out = self._rows()
+        out.append(out[0].copy() if self._emu else out[0].clone())  # next_word
+        BK = self.B * int(self.options.beam_size)
+        sc, dt, stride, ptr, on_dev, host = self._rows_in(scores, dtype, BK)
+        if row_valid is None:
+            rv = None
+        elif host:
+            rv = np.ascontiguousarray(row_valid.cpu().numpy() if hasattr(row_valid, "cpu") else row_valid, dtype=np.uint8)
+        else:
+            import torch
+            rv = row_valid.reshape(-1).to(torch.uint8).contiguous()
+        # the LM's rows: any number of them (one per LM state), the same forms and side as `scores`
+        if isinstance(lm_scores, np.ndarray):
+            if lm_dtype is not None:
+                if lm_dtype not in ("bf16", "bfloat16") or lm_scores.dtype != np.uint16:
+                    raise TypeError("lm_dtype=%r: numpy rows of bfloat16 bits are uint16 with lm_dtype='bf16'" % (lm_dtype,))
+                ldt = DTYPE_BF16
+            else:
+                ldt = DTYPE_F16 if lm_scores.dtype == np.float16 else DTYPE_F32
+            l_on_dev = 1 if self._emu else 0
+            lsc = np.ascontiguousarray(lm_scores, dtype=_NP_DTYPES[ldt]).reshape(-1, lm_scores.shape[-1])
+            lstride, lptr = lsc.shape[1], lsc.ctypes.data
+        else:
+            lsc, ldt, lstride, lptr, l_on_dev, _ = self._rows_in(lm_scores, lm_dtype, BK, "lm_scores")
+        assert l_on_dev == on_dev, "scores and lm_scores: both on the device or both on the host"
+        n_lm = int(lsc.shape[0])
+        ro = None
+        if lm_row_of is not None:
+            if isinstance(lm_row_of, np.ndarray) or host:
+                ro = np.ascontiguousarray(lm_row_of.cpu().numpy() if hasattr(lm_row_of, "cpu") else lm_row_of,
+                                          dtype=np.int32).reshape(-1)
+                n_ro = ro.size
+            else:
+                import torch
+                ro = lm_row_of.reshape(-1).to(torch.int32).contiguous()
+                n_ro = ro.numel()
+            assert n_ro == BK, "lm_row_of: B*K entries"
+        else:
+            assert n_lm >= BK, "lm_scores: B*K rows without lm_row_of"
+        self._chk(self.L.lib.fltx_s2s_step_word_lm_rows(
+            self.h, ptr, dt, S2S_KINDS[kind], stride, lptr, ldt, S2S_KINDS[lm_kind], lstride,
+            None if ro is None else self._addr(ro), n_lm, on_dev, None if rv is None else self._addr(rv),
+            self._lse_ptr(lse_out, BK), self._lse_ptr(lm_lse_out, BK), self._addr(out[0]), self._addr(out[1]),
+            self._addr(out[2]), self._addr(out[4]), self._addr(out[3])))
+        self._inputs = (sc, rv, lsc, ro)  # (kept until the next step: the kernels read them asynchronously)
+        return tuple(out)
 
     def info(self):
         """-> dict(trie_bytes, nodes, edges, merges: per utterance since begin, or None before it)."""

@@ -72,6 +72,7 @@ def _decode(dec, K, update_func, max_output_length, emissions, T, N, raw_beam_id
     lexicon decoder's candidates never record prevHypIdx: LexiconSeq2SeqDecoder.cpp:49).  rows_lm: update_func returns
     a third element, the LM's row vectors aligned with the scores (text_amd._capi.RowsLM)."""
     raw_y, raw_beam, prev_states = [-1], [-1], [None]
+    dec.raw_words = [-1]  # (a WordRowsLM: the word each row of the coming update_func call ended, see below)
     t = 0
     begun = False
     while t < max_output_length:
@@ -92,6 +93,8 @@ def _decode(dec, K, update_func, max_output_length, emissions, T, N, raw_beam_id
             rows[k, :len(r)] = np.asarray(r, dtype=np.float32)
             valid[k] = s is not None
         out = dec.step(rows, valid, lm_scores=_pad_rows(K, lm_rows)) if rows_lm else dec.step(rows, valid)
+        next_word = out[4] if len(out) == 5 else None  # (a decoder made with a text_amd._capi.WordRowsLM lists it)
+        out = out[:4]
         dec.ctx.synchronize()  # (the rows decide the next model call: one host wait per step)
         tok, beam, src, n = (x.cpu().numpy() if hasattr(x, "cpu") else x for x in out)
         t += 1
@@ -99,6 +102,8 @@ def _decode(dec, K, update_func, max_output_length, emissions, T, N, raw_beam_id
         if n == 0:
             break
         raw_y = tok[0, :n].tolist()
+        if next_word is not None:
+            dec.raw_words = (next_word.cpu().numpy() if hasattr(next_word, "cpu") else next_word)[0, :n].tolist()
         raw_beam = beam[0, :n].tolist() if raw_beam_idx else [-1] * n
         prev_states = [out_states[int(s)] for s in src[0, :n]]
     if not begun:  # maxOutputLength 0: the root alone
@@ -209,6 +214,17 @@ class LexiconSeq2SeqDecoder:
     three elements, (scores, states, lm_scores), as LexiconFreeSeq2SeqDecoder's does: row k of lm_scores holds the LM's
     log-probabilities of every LM index after the hypothesis of row k.  The LM must be a pure function of the token
     prefix (hypotheses that spell one token string differently merge; the best member's state object survives)."""
+
+    @property
+    def raw_words(self):
+        """With a text_amd._capi.WordRowsLM and is_token_lm=False (a neural word LM in shallow fusion) update_func returns
+        the three elements of the token case; row k of lm_scores holds the LM's log-probabilities of every LM index
+        after the WORDS of the hypothesis of row k (one row per hypothesis: the decoder reads them with an identity
+        lm_row_of).  The reference's update_func signature does not say where a word ended, so the decoder does: during
+        a call, raw_words[k] is the word the hypothesis of row k ended at its last token, -1 for none -- the LM state of
+        row k is that of prev_states[k], advanced by raw_words[k] when it is >= 0.  The LM must be a pure function of
+        the word prefix.  None with any other LM."""
+        return getattr(self._dec, "raw_words", None) if self._dec.has_word_rows_lm else None
 
     def __init__(self, options, lm, trie, eos_idx, update_func, max_output_length, is_token_lm):
         self.options, self.eos = options, int(eos_idx)

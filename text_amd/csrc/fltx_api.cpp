@@ -184,6 +184,16 @@ __global__ void __launch_bounds__(kS2sStepThreads) fltx_s2s_lex_step_lm_rows_ker
   __shared__ __attribute__((aligned(16))) S2lStepLds fltx_s2l_lm_lds;
   s2lStepUtteranceLmRows(R, (char*)&fltx_s2l_lm_lds);
 }
+/* ... with a word rows LM (fltx_s2s_step_word_lm_rows): the records' word-level LM entries, then the step on them */
+template <int DT, bool LOGITS>
+__global__ void __launch_bounds__(kS2sLmThreads) fltx_s2s_lex_word_lm_rows_kernel(S2lWordLmParams W) {
+  __shared__ __attribute__((aligned(16))) S2sLmRowsLds fltx_s2l_word_lm_lds;
+  s2lWordLmRows<DT, LOGITS>(W, (char*)&fltx_s2l_word_lm_lds);
+}
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_s2s_lex_step_word_lm_rows_kernel(S2lWordLmStepParams R) {
+  __shared__ __attribute__((aligned(16))) S2lStepLds fltx_s2l_word_lm_step_lds;
+  s2lStepUtteranceWordLmRows(R, (char*)&fltx_s2l_word_lm_step_lds);
+}
 __global__ void __launch_bounds__(kS2sBeginThreads) fltx_s2s_lex_begin_kernel(S2lParams Q) {
   s2lBeginUtterance(Q, nullptr);
 }
@@ -452,7 +462,8 @@ struct DeviceScope {
 
 struct fltx_lm {
   fltx_ctx* ctx = nullptr;
-  int kind = 0; /* 0 zero, 1 ngram, 2 host callbacks (fltx_lm_host_create), 3 rows (fltx_lm_rows_create) */
+  int kind = 0; /* 0 zero, 1 ngram, 2 host callbacks (fltx_lm_host_create), 3 rows (fltx_lm_rows_create), 4 word-level
+                 * rows (fltx_lm_word_rows_create: hUsr maps word ids, rowsFinish is given) */
   fltx_host_lm host{};
   /* rows LM: entries per LM row (0: the decoder's V), the LM index finish reads (-1: usr_to_lm[eos]), and whether hUsr
    * holds a map (else identity) */
@@ -697,6 +708,7 @@ struct fltx_decoder {
     DBuf scores, valid; /* device copies of host inputs */
     DBuf recLm, lmScores; /* a rows LM: the records' LM scores; the device copy of host LM rows */
     int lmWidth = 0, lmFinish = 0; /* a rows LM: as fltx_s2s_begin resolved them for V */
+    DBuf rowNode, lmRowOf; /* a word rows LM: the trie node of each row's hypothesis; the device copy of a host lm_row_of */
     /* with a lexicon (fltx_s2s_lex_decoder_create) */
     double wordScore = 0.0;
     bool isLmToken = false;
@@ -879,6 +891,33 @@ int fltx_lm_rows_create(int32_t lmWidth, const int32_t* usrToLm, int32_t nUsr, i
   return FLTX_OK;
 }
 
+/* a word-level rows LM (fltx_s2s_step_word_lm_rows): the word map and the finish index; the trie's labels are checked
+ * against them where the trie is known, at fltx_s2s_lex_decoder_create */
+int fltx_lm_word_rows_create(int32_t lmWidth, const int32_t* wordToLm, int32_t nWords, int32_t finishIndex,
+                             fltx_lm** out) {
+  if (!out || lmWidth <= 0 || finishIndex < 0 || (wordToLm && nWords < 0)) {
+    return fail(FLTX_ERR_INVALID, "fltx_lm_word_rows_create: bad argument (lm_width > 0 and finish_index >= 0 are required)");
+  }
+  if (lmWidth > kS2lMaxLmWidth) {
+    return fail(FLTX_ERR_UNSUPPORTED, "fltx_lm_word_rows_create: lm_width %d > %d", lmWidth, kS2lMaxLmWidth);
+  }
+  auto* lm = new fltx_lm();
+  lm->kind = 4;
+  lm->rowsWidth = lmWidth;
+  lm->rowsFinish = finishIndex;
+  lm->rowsMap = wordToLm != nullptr;
+  if (wordToLm) {
+    lm->hUsr.assign(wordToLm, wordToLm + nWords);
+    lm->nUsr = nWords;
+  }
+  {
+    std::lock_guard<std::mutex> lock(g_lmRegMu);
+    g_lmReg.insert(lm);
+  }
+  *out = lm;
+  return FLTX_OK;
+}
+
 int fltx_lm_ngram_create(fltx_ctx* ctx, int32_t order, int64_t nNgrams, const int32_t* ngOrder,
                          const int32_t* ngWords, const float* prob, const float* backoff,
                          const int32_t* usrToLm, int32_t nUsr, int32_t bos, int32_t eos,
@@ -1002,7 +1041,7 @@ int fltx_lm_score_sequence(fltx_lm* lm, const int32_t* usrWords, int32_t n, int3
   if (lm->kind == 2) {
     return fail(FLTX_ERR_UNSUPPORTED, "a host LM keeps its own states (call the LM object)");
   }
-  if (lm->kind == 3) {
+  if (lm->kind == 3 || lm->kind == 4) {
     return fail(FLTX_ERR_UNSUPPORTED, "a rows LM has no states here: its answers arrive with fltx_s2s_step_lm_rows");
   }
   float tot = 0;
@@ -1127,7 +1166,7 @@ int fltx_lm_state_size(fltx_lm* lm, int32_t* n) {
   if (lm->kind == 2) {
     return fail(FLTX_ERR_UNSUPPORTED, "a host LM keeps its own states (call the LM object)");
   }
-  if (lm->kind == 3) {
+  if (lm->kind == 3 || lm->kind == 4) {
     return fail(FLTX_ERR_UNSUPPORTED, "a rows LM has no states here: its answers arrive with fltx_s2s_step_lm_rows");
   }
   *n = lm->kind == 0 ? 0 : std::max(1, lm->order - 1);
@@ -1141,7 +1180,7 @@ int fltx_lm_start(fltx_lm* lm, int32_t startWithNothing, int32_t* ctxOut) {
   if (lm->kind == 2) {
     return fail(FLTX_ERR_UNSUPPORTED, "a host LM keeps its own states (call the LM object)");
   }
-  if (lm->kind == 3) {
+  if (lm->kind == 3 || lm->kind == 4) {
     return fail(FLTX_ERR_UNSUPPORTED, "a rows LM has no states here: its answers arrive with fltx_s2s_step_lm_rows");
   }
   if (lm->kind == 0) {
@@ -1217,7 +1256,7 @@ int fltx_lm_step(fltx_lm* lm, const int32_t* ctxIn, int32_t usrIdx, int32_t* ctx
   if (lm->kind == 2) {
     return fail(FLTX_ERR_UNSUPPORTED, "a host LM keeps its own states (call the LM object)");
   }
-  if (lm->kind == 3) {
+  if (lm->kind == 3 || lm->kind == 4) {
     return fail(FLTX_ERR_UNSUPPORTED, "a rows LM has no states here: its answers arrive with fltx_s2s_step_lm_rows");
   }
   if (lm->kind == 0) {
@@ -1428,7 +1467,7 @@ int fltx_trie_destroy(fltx_trie* t) {
 /* upload the flat n-gram tables to the context's device (once) */
 static int lmEnsureUploaded(fltx_lm* lm, fltx_ctx* ctx, fltx_lm::Dev** out) {
   *out = nullptr;
-  if (lm->kind != 1 && !(lm->kind == 3 && lm->rowsMap)) {
+  if (lm->kind != 1 && !((lm->kind == 3 || lm->kind == 4) && lm->rowsMap)) {
     return FLTX_OK; /* (ZeroLM: nothing to compute; host LM: answered on the host; rows LM without a map: identity) */
   }
   std::lock_guard<std::mutex> lock(lm->devMu);
@@ -1439,7 +1478,7 @@ static int lmEnsureUploaded(fltx_lm* lm, fltx_ctx* ctx, fltx_lm::Dev** out) {
   }
   std::unique_ptr<fltx_lm::Dev> dv(new fltx_lm::Dev());
   Stream st = ctx->stream;
-  if (lm->kind == 3) { /* a rows LM: the map alone */
+  if (lm->kind == 3 || lm->kind == 4) { /* a rows LM: the map alone */
     const size_t nb = sizeof(int32_t) * std::max<size_t>(1, lm->hUsr.size());
     if (dv->usrToLm.ensure(nb, st, false)) {
       return fail(FLTX_ERR_OOM, "rows LM: device allocation failed");
@@ -1630,8 +1669,9 @@ int fltx_decoder_create(fltx_ctx* ctx, int32_t kind, const fltx_options* opt, co
   if (kind != FLTX_DECODER_LEXFREE && kind != FLTX_DECODER_LEXICON) {
     return fail(FLTX_ERR_INVALID, "unknown decoder kind %d", kind);
   }
-  if (lm->kind == 3) {
-    return fail(FLTX_ERR_UNSUPPORTED, "a rows LM (fltx_lm_rows_create) serves the seq2seq decoders only");
+  if (lm->kind == 3 || lm->kind == 4) {
+    return fail(FLTX_ERR_UNSUPPORTED, "a rows LM (fltx_lm_rows_create, fltx_lm_word_rows_create) serves the seq2seq "
+                                      "decoders only");
   }
   if (kind == FLTX_DECODER_LEXICON && !trie) {
     return fail(FLTX_ERR_INVALID, "lexicon decoder needs a trie");
@@ -4972,10 +5012,15 @@ static S2sParams s2sParams(fltx_decoder* d) {
   return P;
 }
 
-int fltx_s2s_decoder_create(fltx_ctx* ctx, const fltx_s2s_options* opt, const fltx_lm* lm, int32_t eos,
-                            int32_t maxOut, fltx_decoder** out) {
+/* (fltx_s2s_lex_decoder_create makes its decoder here too: wordRows = it was given a word-level rows LM) */
+static int s2sDecoderCreate(fltx_ctx* ctx, const fltx_s2s_options* opt, const fltx_lm* lm, int32_t eos, int32_t maxOut,
+                            bool wordRows, fltx_decoder** out) {
   if (!ctx || !opt || !lm || !out) {
     return fail(FLTX_ERR_INVALID, "fltx_s2s_decoder_create: null argument");
+  }
+  if (lm->kind == 4 && !wordRows) {
+    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq: a word-level rows LM (fltx_lm_word_rows_create) serves the lexicon "
+                                      "seq2seq decoder with is_lm_token == 0 only");
   }
   if (opt->beam_size < 1 || opt->beam_size_token < 1) {
     return fail(FLTX_ERR_INVALID, "beam_size and beam_size_token must be >= 1");
@@ -5035,8 +5080,21 @@ int fltx_s2s_decoder_create(fltx_ctx* ctx, const fltx_s2s_options* opt, const fl
   return FLTX_OK;
 }
 
+int fltx_s2s_decoder_create(fltx_ctx* ctx, const fltx_s2s_options* opt, const fltx_lm* lm, int32_t eos,
+                            int32_t maxOut, fltx_decoder** out) {
+  return s2sDecoderCreate(ctx, opt, lm, eos, maxOut, false, out);
+}
+
 /* ---- lexicon seq2seq (fltx_s2s_lex.h) ---------------------------------------------------------------------------- */
 /* the parameters of either kind: .s is the lexicon-free view, the rest stays 0 without a lexicon */
+/* a rows LM of either level: the finish index lies inside the LM's rows */
+static int s2sRowsLmFinishCheck(int finish, int width) {
+  if (finish < 0 || finish >= width) {
+    return fail(FLTX_ERR_INVALID, "seq2seq rows LM: finish index %d outside the LM's rows of %d", finish, width);
+  }
+  return FLTX_OK;
+}
+
 static S2lParams s2sStepParams(fltx_decoder* d) {
   S2lParams Q;
   memset(&Q, 0, sizeof(Q));
@@ -5083,7 +5141,7 @@ static int s2lPow2AtLeast(int64_t n) {
 }
 
 /* the compact trie: per node maxScore, children sorted by token (CSR) and labels; bytes ~ nodes + edges + labels */
-static int s2lUploadTrie(fltx_decoder* d, fltx_htrie* t) {
+static int s2lUploadTrie(fltx_decoder* d, fltx_htrie* t, std::vector<int32_t>* labelsOut = nullptr) {
   int64_t nn = 0;
   int rc = fltx_htrie_num_nodes(t, &nn);
   if (rc) {
@@ -5147,6 +5205,9 @@ static int s2lUploadTrie(fltx_decoder* d, fltx_htrie* t) {
   d->s2s.labels = (int64_t)nL;
   d->s2s.maxLabels = maxLabels;
   d->s2s.trieBytes = 4 * nn + 4 * 2 * (nn + 1) + 8 * (int64_t)nE + 4 * (int64_t)nL;
+  if (labelsOut) {
+    labelsOut->swap(lab);
+  }
   return FLTX_OK;
 }
 
@@ -5156,9 +5217,13 @@ int fltx_s2s_lex_decoder_create(fltx_ctx* ctx, const fltx_s2s_lex_options* opt, 
     return fail(FLTX_ERR_INVALID, "fltx_s2s_lex_decoder_create: null argument");
   }
   if (lm->kind == 3 && !isLmToken) {
-    /* (its rows would be as wide as the word vocabulary: DESIGN section 7) */
+    /* (its rows are read one per decoder row through the token map: word-level rows come in by their own LM object) */
     return fail(FLTX_ERR_UNSUPPORTED, "seq2seq lexicon: a word-level rows LM (fltx_lm_rows_create with is_lm_token == 0) "
-                                      "is not supported");
+                                      "is not supported; make it with fltx_lm_word_rows_create");
+  }
+  if (lm->kind == 4 && isLmToken) {
+    return fail(FLTX_ERR_UNSUPPORTED, "seq2seq lexicon: a word-level rows LM (fltx_lm_word_rows_create) goes with "
+                                      "is_lm_token == 0");
   }
   fltx_s2s_options o{};
   o.beam_size = opt->beam_size;
@@ -5168,7 +5233,7 @@ int fltx_s2s_lex_decoder_create(fltx_ctx* ctx, const fltx_s2s_lex_options* opt, 
   o.eos_score = opt->eos_score;
   o.log_add = opt->log_add;
   fltx_decoder* d = nullptr;
-  int rc = fltx_s2s_decoder_create(ctx, &o, lm, eos, maxOut, &d);
+  int rc = s2sDecoderCreate(ctx, &o, lm, eos, maxOut, lm->kind == 4, &d);
   if (rc) {
     return rc;
   }
@@ -5182,9 +5247,31 @@ int fltx_s2s_lex_decoder_create(fltx_ctx* ctx, const fltx_s2s_lex_options* opt, 
   d->s2s.wordScore = opt->word_score;
   d->s2s.isLmToken = isLmToken != 0;
   d->s2s.maxStates = kS2lDefaultStates;
-  if ((rc = s2lUploadTrie(d, const_cast<fltx_htrie*>(trie)))) {
+  std::vector<int32_t> labels;
+  if ((rc = s2lUploadTrie(d, const_cast<fltx_htrie*>(trie), &labels))) {
     delete d;
     return rc;
+  }
+  if (lm->kind == 4) { /* every index the word gather can form lies inside the LM's rows */
+    const int width = lm->rowsWidth;
+    rc = s2sRowsLmFinishCheck(lm->rowsFinish, width);
+    for (size_t i = 0; i < labels.size() && !rc; ++i) {
+      const int32_t w = labels[i];
+      if (w < 0 || (lm->rowsMap && w >= lm->nUsr)) {
+        rc = fail(FLTX_ERR_INVALID, "seq2seq word rows LM: the trie's label %d outside the %d entries of word_to_lm", w,
+                  lm->nUsr);
+      } else {
+        const int32_t idx = lm->rowsMap ? lm->hUsr[(size_t)w] : w;
+        if (idx < 0 || idx >= width) {
+          rc = fail(FLTX_ERR_INVALID, "seq2seq word rows LM: word %d has LM index %d outside the LM's rows of %d", w, idx,
+                    width);
+        }
+      }
+    }
+    if (rc) {
+      delete d;
+      return rc;
+    }
   }
   d->s2s.slots = 1 + (d->s2s.isLmToken ? std::min(d->s2s.maxLabels, 1) : d->s2s.maxLabels);
   *out = d;
@@ -5246,8 +5333,8 @@ static int s2sPlanRowsLm(fltx_decoder* d, int32_t V) {
   if (finish < 0 && eos < V) {
     finish = lm->rowsMap ? lm->hUsr[(size_t)eos] : eos;
   }
-  if (eos < V && (finish < 0 || finish >= width)) {
-    return fail(FLTX_ERR_INVALID, "seq2seq rows LM: finish index %d outside the LM's rows of %d", finish, width);
+  if (eos < V && s2sRowsLmFinishCheck(finish, width)) {
+    return FLTX_ERR_INVALID;
   }
   if (lm->rowsMap) {
     for (int u = 0; u < V; ++u) {
@@ -5304,6 +5391,10 @@ static int s2sPlanLexicon(fltx_decoder* d, int32_t V, int64_t* nC) {
   if (d->lm->kind == 3) { /* (the token beam's limit stays kS2lMaxKt: kS2sMaxKtLm is the lexicon-free step's) */
     return s2sPlanRowsLm(d, V);
   }
+  if (d->lm->kind == 4) { /* (word ids, not tokens: checked against the trie's labels at create; nothing depends on V) */
+    d->s2s.lmWidth = d->lm->rowsWidth;
+    d->s2s.lmFinish = d->lm->rowsFinish;
+  }
   return FLTX_OK;
 }
 
@@ -5355,12 +5446,17 @@ int fltx_s2s_begin(fltx_decoder* d, int32_t B, int32_t V, int32_t* nextTok, int3
       d->s2s.finalStep.ensure(4 * (size_t)B, st, false) ||
       d->s2s.recTok.ensure(4 * BK * d->s2s.cap, st, false) || d->s2s.recAm.ensure(4 * BK * d->s2s.cap, st, false) ||
       d->s2s.recN.ensure(4 * BK, st, false) || d->s2s.cKey.ensure(8 * (size_t)B * (size_t)nC, st, false) ||
-      (d->lm->kind == 3 && d->s2s.recLm.ensure(4 * BK * d->s2s.cap, st, false))) {
+      (d->lm->kind == 3 && d->s2s.recLm.ensure(4 * BK * d->s2s.cap, st, false)) ||
+      (d->lm->kind == 4 && (d->s2s.recLm.ensure(4 * BK * d->s2s.cap * d->s2s.slots, st, false) ||
+                            d->s2s.rowNode.ensure(4 * BK, st, false)))) {
     return fail(FLTX_ERR_OOM, "seq2seq workspace: device allocation failed (B=%d K=%d V=%d)", B, d->s2s.opt.beam_size,
                 V);
   }
   if (lex && (rc = s2sAllocLexicon(d, B, V, nC))) {
     return rc;
+  }
+  if (d->lm->kind == 4 && devMemset(d->s2s.rowNode.p, 0, 4 * BK, st)) { /* the first call's row: the root */
+    return fail(FLTX_ERR_HIP, "seq2seq lexicon: memset failed");
   }
   d->B = B;
   d->N = V;
@@ -5402,6 +5498,12 @@ static int s2sLmRowsLaunch(int nRows, Stream st, const S2sLmRowsParams& Q) {
              kS2sLmThreads, sizeof(S2sLmRowsLds), st, Q);
   return FLTX_OK;
 }
+template <int DT, bool LOGITS>
+static int s2lWordLmRowsLaunch(int nRows, Stream st, const S2lWordLmParams& W) {
+  S2S_LAUNCH((fltx_s2s_lex_word_lm_rows_kernel<DT, LOGITS>), (s2lWordLmRows<DT, LOGITS>),
+             LOGITS ? nRows : (nRows + 3) / 4, kS2sLmThreads, sizeof(S2sLmRowsLds), st, W);
+  return FLTX_OK;
+}
 }
 
 /* the LM's rows of fltx_s2s_step_lm_rows */
@@ -5411,6 +5513,11 @@ struct S2sLmIn {
   bool logits;
   int64_t rowStride;
   double* rowLse;
+  /* fltx_s2s_step_word_lm_rows: word-level rows, read through lmRowOf (null: identity, nLmRows = B*K) */
+  bool wordRows = false;
+  const int32_t* lmRowOf = nullptr;
+  int32_t nLmRows = 0;
+  int32_t* nextWord = nullptr;
 };
 
 /* one step of either kind (the entry points have checked the decoder, `what` names the one that was called): the front
@@ -5419,7 +5526,13 @@ struct S2sLmIn {
 static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_t dtype, bool logits, int32_t onDevice,
                    int64_t rowStride, const uint8_t* rowValid, double* rowLse, int32_t* nextTok, int32_t* nextBeam,
                    int32_t* nextSrc, int32_t* nRows, const S2sLmIn* lmIn = nullptr) {
-  if ((d->lm->kind == 3) != (lmIn != nullptr)) {
+  const bool wordRows = lmIn && lmIn->wordRows;
+  if ((d->lm->kind == 4) != wordRows) {
+    return fail(FLTX_ERR_STATE, wordRows ? "%s: the decoder has no word-level rows LM (fltx_lm_word_rows_create)"
+                                         : "%s: a decoder with a word-level rows LM steps with fltx_s2s_step_word_lm_rows",
+                what);
+  }
+  if (!wordRows && (d->lm->kind == 3) != (lmIn != nullptr)) {
     return fail(FLTX_ERR_STATE, lmIn ? "%s: the decoder has no rows LM (fltx_lm_rows_create)"
                                      : "%s: a decoder with a rows LM steps with fltx_s2s_step_lm_rows", what);
   }
@@ -5441,6 +5554,11 @@ static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_
   const size_t BK = (size_t)d->B * d->s2s.opt.beam_size;
   const size_t elem = dtype == FLTX_DTYPE_F32 ? 4 : 2;
   const bool last = d->s2s.t >= d->s2s.maxOut; /* nothing to score: the kernels only list no rows */
+  const size_t nLmRows = wordRows && lmIn->lmRowOf ? (size_t)std::max(lmIn->nLmRows, 0) : BK;
+  if (wordRows && (!lmIn->nextWord || (lmIn->lmRowOf && lmIn->nLmRows < 1 && !last))) {
+    return fail(FLTX_ERR_INVALID, "%s: bad argument (next_word is required; n_lm_rows %d with lm_row_of)", what,
+                lmIn->nLmRows);
+  }
   if (!onDevice && !last) {
     const size_t nE = (BK - 1) * (size_t)rowStride + (size_t)d->N;
     if (d->s2s.scores.ensure(elem * nE, st, false) || (rowValid && d->s2s.valid.ensure(BK, st, false))) {
@@ -5456,7 +5574,7 @@ static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_
   const void* lmScores = lmIn ? lmIn->scores : nullptr;
   if (lmIn && !onDevice && !last) { /* the LM's rows, staged in their own type */
     const size_t lmElem = lmIn->dtype == FLTX_DTYPE_F32 ? 4 : 2;
-    const size_t nE = (BK - 1) * (size_t)lmIn->rowStride + (size_t)d->s2s.lmWidth;
+    const size_t nE = (nLmRows - 1) * (size_t)lmIn->rowStride + (size_t)d->s2s.lmWidth;
     if (d->s2s.lmScores.ensure(lmElem * nE, st, false)) {
       return fail(FLTX_ERR_OOM, "seq2seq: staging allocation failed");
     }
@@ -5464,6 +5582,16 @@ static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_
       return fail(FLTX_ERR_HIP, "seq2seq: upload failed");
     }
     lmScores = d->s2s.lmScores.p;
+  }
+  const int32_t* lmRowOf = wordRows ? lmIn->lmRowOf : nullptr;
+  if (lmRowOf && !onDevice && !last) {
+    if (d->s2s.lmRowOf.ensure(4 * BK, st, false)) {
+      return fail(FLTX_ERR_OOM, "seq2seq: staging allocation failed");
+    }
+    if (devCopyH2D(d->s2s.lmRowOf.p, lmRowOf, 4 * BK, st)) {
+      return fail(FLTX_ERR_HIP, "seq2seq: upload failed");
+    }
+    lmRowOf = d->s2s.lmRowOf.as<int32_t>();
   }
   if (last && logits && rowLse && devMemset(rowLse, 0xFF, 8 * BK, st)) { /* (all-ones: a NaN) */
     return fail(FLTX_ERR_HIP, "%s: memset failed", what);
@@ -5499,7 +5627,44 @@ static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_
       return rc;
     }
   }
-  if (d->kind == FLTX_DECODER_S2S_LEXICON && !lmIn) {
+  if (wordRows) {
+    S2lWordLmParams W;
+    memset(&W, 0, sizeof(W));
+    W.r.s = P;
+    W.r.x = lmScores;
+    W.r.rowStride = lmIn->rowStride;
+    W.r.width = d->s2s.lmWidth;
+    W.r.finishIdx = d->s2s.lmFinish;
+    W.r.usrToLm = d->lm->rowsMap ? d->lmDev->usrToLm.as<int32_t>() : nullptr;
+    W.r.recLm = d->s2s.recLm.as<float>();
+    W.r.rowLse = lmIn->logits ? lmIn->rowLse : nullptr;
+    W.trie = Q.trie;
+    W.rowNode = d->s2s.rowNode.as<int32_t>();
+    W.lmRowOf = lmRowOf;
+    W.nLmRows = (int32_t)nLmRows;
+    W.S = Q.S;
+    if (!last) {
+      int rc;
+      switch (lmIn->dtype * 2 + (lmIn->logits ? 1 : 0)) {
+        case 0: rc = s2lWordLmRowsLaunch<kS2sDtF32, false>((int)BK, st, W); break;
+        case 1: rc = s2lWordLmRowsLaunch<kS2sDtF32, true>((int)BK, st, W); break;
+        case 2: rc = s2lWordLmRowsLaunch<kS2sDtF16, false>((int)BK, st, W); break;
+        case 3: rc = s2lWordLmRowsLaunch<kS2sDtF16, true>((int)BK, st, W); break;
+        case 4: rc = s2lWordLmRowsLaunch<kS2sDtBf16, false>((int)BK, st, W); break;
+        default: rc = s2lWordLmRowsLaunch<kS2sDtBf16, true>((int)BK, st, W); break;
+      }
+      if (rc) {
+        return rc;
+      }
+    }
+    S2lWordLmStepParams RW;
+    RW.q = Q;
+    RW.recLm = W.r.recLm;
+    RW.outWord = lmIn->nextWord;
+    RW.rowNode = d->s2s.rowNode.as<int32_t>();
+    S2S_LAUNCH(fltx_s2s_lex_step_word_lm_rows_kernel, s2lStepUtteranceWordLmRows, d->B, kS2sStepThreads,
+               sizeof(S2lStepLds), st, RW);
+  } else if (d->kind == FLTX_DECODER_S2S_LEXICON && !lmIn) {
     S2S_LAUNCH(fltx_s2s_lex_step_kernel, s2lStepUtterance, d->B, kS2sStepThreads, sizeof(S2lStepLds), st, Q);
   } else if (lmIn) {
     S2sLmRowsParams R;
@@ -5605,6 +5770,41 @@ int fltx_s2s_step_lm_rows(fltx_decoder* d, const void* scores, int32_t dtype, in
   }
   const S2sLmIn lmIn{lmScores, lmDtype, lmKind == FLTX_S2S_LOGITS, lmRowStride, lmRowLse};
   return s2sStep(d, "fltx_s2s_step_lm_rows", scores, dtype, kind == FLTX_S2S_LOGITS, onDevice, rowStride, rowValid,
+                 rowLse, nextTok, nextBeam, nextSrc, nRows, &lmIn);
+}
+
+/* fltx_s2s_step_lm_rows for a word-level rows LM (fltx_lm_word_rows_create): the LM's rows through lm_row_of */
+int fltx_s2s_step_word_lm_rows(fltx_decoder* d, const void* scores, int32_t dtype, int32_t kind, int64_t rowStride,
+                               const void* lmScores, int32_t lmDtype, int32_t lmKind, int64_t lmRowStride,
+                               const int32_t* lmRowOf, int32_t nLmRows, int32_t onDevice, const uint8_t* rowValid,
+                               double* rowLse, double* lmRowLse, int32_t* nextTok, int32_t* nextBeam, int32_t* nextSrc,
+                               int32_t* nextWord, int32_t* nRows) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = s2sCheck(d, "fltx_s2s_step_word_lm_rows");
+  if (rc) {
+    return rc;
+  }
+  if (d->lm->kind != 4) {
+    return fail(FLTX_ERR_STATE, "fltx_s2s_step_word_lm_rows: the decoder has no word-level rows LM "
+                                "(fltx_lm_word_rows_create)");
+  }
+  if ((dtype != FLTX_DTYPE_F32 && dtype != FLTX_DTYPE_F16 && dtype != FLTX_DTYPE_BF16) ||
+      (lmDtype != FLTX_DTYPE_F32 && lmDtype != FLTX_DTYPE_F16 && lmDtype != FLTX_DTYPE_BF16)) {
+    return fail(FLTX_ERR_INVALID, "fltx_s2s_step_word_lm_rows: dtype %d, lm_dtype %d", dtype, lmDtype);
+  }
+  if ((kind != FLTX_S2S_LOG_PROBS && kind != FLTX_S2S_LOGITS) ||
+      (lmKind != FLTX_S2S_LOG_PROBS && lmKind != FLTX_S2S_LOGITS)) {
+    return fail(FLTX_ERR_INVALID, "fltx_s2s_step_word_lm_rows: kind %d, lm_kind %d", kind, lmKind);
+  }
+  S2sLmIn lmIn{lmScores, lmDtype, lmKind == FLTX_S2S_LOGITS, lmRowStride, lmRowLse};
+  lmIn.wordRows = true;
+  lmIn.lmRowOf = lmRowOf;
+  lmIn.nLmRows = nLmRows;
+  lmIn.nextWord = nextWord;
+  return s2sStep(d, "fltx_s2s_step_word_lm_rows", scores, dtype, kind == FLTX_S2S_LOGITS, onDevice, rowStride, rowValid,
                  rowLse, nextTok, nextBeam, nextSrc, nRows, &lmIn);
 }
 

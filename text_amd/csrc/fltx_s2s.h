@@ -672,8 +672,16 @@ FLTX_DEV int s2sSelectTopK(S2sStepLds& S, const unsigned long long* cKey, int64_
 
 /* the step's outcome: thread tid < nSel made hypothesis tid of the new beam, (token, parent), `isLive` when the model
  * extends it, from row `srcRow` of this call.  Writes the next call's rows and the utterance's bookkeeping */
-FLTX_DEV void s2sPublishStep(const S2sParams& P, S2sStepLds& S, int b, int nSel, bool isLive, int token, int parent,
-                             int srcRow) {
+struct S2sNoRowExtra { /* nothing more per listed row */
+  __device__ __forceinline__ void put(int64_t) const {}
+  __device__ __forceinline__ void none(int64_t) const {}
+};
+
+/* ... `extra` says what else a row of the next call's list gets: put(r) for the listed row r of this thread's
+ * hypothesis, none(r) for a padding row (the lexicon step with word-level LM rows: next_word and the row's trie node) */
+template <typename Extra>
+FLTX_DEV void s2sPublishStepWith(const S2sParams& P, S2sStepLds& S, int b, int nSel, bool isLive, int token, int parent,
+                                 int srcRow, const Extra& extra) {
   const int tid = (int)threadIdx.x, K = P.K, par = P.t & 1;
   const int64_t rb = (int64_t)b * K;
   int nLive;
@@ -686,11 +694,13 @@ FLTX_DEV void s2sPublishStep(const S2sParams& P, S2sStepLds& S, int b, int nSel,
     P.outTok[rb + q] = token;
     P.outBeam[rb + q] = parent;
     P.outSrc[rb + q] = srcRow;
+    extra.put(rb + q);
   }
   for (int k = nLive + tid; k < K; k += kS2sStepThreads) {
     P.outTok[rb + k] = -1;
     P.outBeam[rb + k] = -1;
     P.outSrc[rb + k] = -1;
+    extra.none(rb + k);
   }
   if (tid == 0) {
     P.outN[b] = nLive;
@@ -703,6 +713,11 @@ FLTX_DEV void s2sPublishStep(const S2sParams& P, S2sStepLds& S, int b, int nSel,
       P.finalStep[b] = nSel > 0 ? P.t + 1 : P.t; /* the last non-empty beam (:152-158; lexicon: :204-207) */
     }
   }
+}
+
+FLTX_DEV void s2sPublishStep(const S2sParams& P, S2sStepLds& S, int b, int nSel, bool isLive, int token, int parent,
+                             int srcRow) {
+  s2sPublishStepWith(P, S, b, nSel, isLive, token, parent, srcRow, S2sNoRowExtra{});
 }
 
 /* decodeStep's start (:30-32): the root's fields that every hypothesis type has ... */

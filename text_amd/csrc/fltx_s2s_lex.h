@@ -31,6 +31,17 @@
  * all enter a new state: child(h.sid, token), or child(h.sid, -1) for eos (finish is its own child, as KenLM's) --
  * LexiconSeq2SeqDecoder.cpp:115-198 with isLmToken.  The LM's state is the token prefix, so two segmentations of one
  * token string carry the same (parent sid, edge) and merge by the keys above.  No n-gram walk: ctx stays ctx0.
+ *
+ * Word-level LM rows.  With a word rows LM (fltx_lm_word_rows_create: an LM over the lexicon's words, !isLmToken) the
+ * step is the front end, fltx_s2s_lex_word_lm_rows_kernel and fltx_s2s_lex_step_word_lm_rows_kernel.  An LM row is as
+ * wide as the word vocabulary, its state changes only where a word ends, and many hypotheses share one: the rows are
+ * read through lmRowOf (decoder row -> LM row), and the gather reads only what the step can use -- per record entry
+ * S = 1 + max labels floats recLm[row][e][s]: slot 0 the finish entry (eos at the root), slot s >= 1 the entry of label
+ * s - 1 of the token's child, NaN where there is none.  The trie node of a row's hypothesis comes from rowNode, which
+ * this step's instantiation leaves for the next call's rows (the root's 0 by fltx_s2s_begin).  The step (kS2lLmWordRows)
+ * takes eos from slot 0 and a word end from slot s minus lexMaxScore (a float subtraction, :174-198); the move inside a
+ * word reads no LM entry (smearing, the same state); states and merge keys are the tables path's -- child(h.sid, word),
+ * child(h.sid, -1).  It also writes next_word: the word each listed row's hypothesis ended in this step, -1 for none.
  */
 #pragma once
 
@@ -128,9 +139,14 @@ struct S2lCand {
   int32_t usr;       /* the LM question that made the state (kS2sLmFinish: finish) */
 };
 
+/* where a candidate's LM term comes from: a template parameter of the step, never a runtime flag */
+enum { kS2lLmTables = 0,    /* ZeroLM / the n-gram tables (s2sLm) */
+       kS2lLmTokenRows = 1, /* a token rows LM: recLm[r * cap + e] for all three kinds of candidate */
+       kS2lLmWordRows = 2 };/* a word rows LM: recLm[(r * cap + e) * S + s] for eos (s = 0) and a word end (s >= 1) */
+
 /* candidate j of the utterance: record slot j < nRowC (row k, entry e, sub-slot s: 0 = stay / eos, 1.. = the labels),
- * then the carried hypotheses; false: no candidate.  REC: the LM term of all three kinds is recLm[r * cap + e] */
-template <bool REC>
+ * then the carried hypotheses; false: no candidate */
+template <int SRC>
 FLTX_DEV bool s2lCand(const S2lParams& Q, const float* recLm, const S2lHyp* prev, const int32_t* hypOfRow, int64_t rb,
                       int64_t nRowC, int64_t j, S2lCand& c) {
   const S2sParams& P = Q.s;
@@ -170,8 +186,11 @@ FLTX_DEV bool s2lCand(const S2lParams& Q, const float* recLm, const S2lHyp* prev
     if (s != 0 || h.node != 0) {
       return false;
     }
-    if constexpr (REC) { /* LM::finish: the entry at the finish index, a child of its own */
+    if constexpr (SRC == kS2lLmTokenRows) { /* LM::finish: the entry at the finish index, a child of its own */
       c.lmS = recLm[r * cap + e];
+      c.isNew = true;
+    } else if constexpr (SRC == kS2lLmWordRows) {
+      c.lmS = recLm[(r * cap + e) * S] - 0.0f; /* (lexMaxScore is 0 at the root) */
       c.isNew = true;
     } else {
       c.lmS = s2sLm(P, h.ctx, kS2sLmFinish, kS2sLmFinish, nullptr) - 0.0f; /* (lexMaxScore is 0 at the root) */
@@ -188,7 +207,7 @@ FLTX_DEV bool s2lCand(const S2lParams& Q, const float* recLm, const S2lHyp* prev
   if (child < 0) {
     return false;
   }
-  if constexpr (REC) { /* a token LM: the move and the word end (the first label) share the entry and the new state */
+  if constexpr (SRC == kS2lLmTokenRows) { /* a token LM: the move and the word end (the first label) share the entry and the new state */
     const int l0 = Q.trie.labOff[child];
     if (s > 1 || (s == 1 && Q.trie.labOff[child + 1] == l0)) {
       return false;
@@ -204,6 +223,29 @@ FLTX_DEV bool s2lCand(const S2lParams& Q, const float* recLm, const S2lHyp* prev
     return true;
   }
   const float lexMax = h.node == 0 ? 0.0f : Q.trie.maxScore[h.node];
+  if constexpr (SRC == kS2lLmWordRows) { /* a word LM: the move reads the trie alone, a word end its label's entry */
+    if (s == 0) {
+      c.lmS = Q.trie.maxScore[child] - lexMax; /* smearing (float) */
+      c.isNew = false;
+      c.score = (h.score + (double)a) + P.lmWeight * (double)c.lmS;
+      c.word = -1;
+      c.node = child;
+      return true;
+    }
+    const int l0 = Q.trie.labOff[child];
+    if (s - 1 >= Q.trie.labOff[child + 1] - l0) {
+      return false;
+    }
+    const int word = Q.trie.labels[l0 + s - 1];
+    c.lmS = recLm[(r * cap + e) * S + s] - lexMax;
+    c.newEdge = word;
+    c.usr = word;
+    c.isNew = true;
+    c.score = ((h.score + (double)a) + Q.wordScore) + P.lmWeight * (double)c.lmS;
+    c.word = word;
+    c.node = 0;
+    return true;
+  }
   if (s == 0) { /* stay in the trie (:146-171) */
     if (Q.isLmToken) {
       c.lmS = s2sLm(P, h.ctx, tok, kS2sLmFinish, nullptr);
@@ -257,8 +299,27 @@ struct S2lStepLds {
   int32_t full;
 };
 
-template <bool REC>
-FLTX_DEV void s2lStepUtteranceOn(const S2lParams& Q, char* smem, const float* recLm) {
+/* what the word-rows step leaves per row of the next call: next_word and the row's trie node (the gather's) */
+struct S2lRowExtra {
+  int32_t *outWord, *rowNode;
+  int32_t word, node;
+  __device__ __forceinline__ void put(int64_t r) const {
+    outWord[r] = word;
+    rowNode[r] = node;
+  }
+  __device__ __forceinline__ void none(int64_t r) const { outWord[r] = -1; }
+};
+
+FLTX_DEV void s2lNoWords(const S2sParams& P, int b, int32_t* outWord) {
+  for (int k = (int)threadIdx.x; k < P.K; k += kS2sStepThreads) {
+    outWord[(int64_t)b * P.K + k] = -1;
+  }
+}
+
+/* outWord / rowNode: kS2lLmWordRows only */
+template <int SRC>
+FLTX_DEV void s2lStepUtteranceOn(const S2lParams& Q, char* smem, const float* recLm, int32_t* outWord = nullptr,
+                                 int32_t* rowNode = nullptr) {
   const S2sParams& P = Q.s;
   S2lStepLds& L = *(S2lStepLds*)smem;
   S2sStepLds& S = L.s;
@@ -267,6 +328,9 @@ FLTX_DEV void s2lStepUtteranceOn(const S2lParams& Q, char* smem, const float* re
   const int64_t rb = (int64_t)b * K;
   if (P.done[b] || P.t >= P.maxOut) { /* a step after the last one: nothing to score */
     s2sIdleStep(P, b);
+    if constexpr (SRC == kS2lLmWordRows) {
+      s2lNoWords(P, b, outWord);
+    }
     return;
   }
   const int par = P.t & 1;
@@ -296,7 +360,7 @@ FLTX_DEV void s2lStepUtteranceOn(const S2lParams& Q, char* smem, const float* re
   for (int64_t j = tid; j < n; j += kS2sStepThreads) {
     unsigned long long key = 0ull;
     S2lCand c;
-    if (s2lCand<REC>(Q, recLm, prev, S.hypOfRow, rb, nRowC, j, c)) {
+    if (s2lCand<SRC>(Q, recLm, prev, S.hypOfRow, rb, nRowC, j, c)) {
       key = s2sScoreKey(c.score);
       cScore[j] = c.score;
       cMk[j] = s2lMergeKey(c, prev[c.hyp]);
@@ -396,7 +460,7 @@ FLTX_DEV void s2lStepUtteranceOn(const S2lParams& Q, char* smem, const float* re
   int32_t* sVal = Q.sVal + (size_t)b * Q.sSize;
   if (tid < nSel) {
     const int64_t j = S.selIdx[S.order[tid]];
-    s2lCand<REC>(Q, recLm, prev, S.hypOfRow, rb, nRowC, j, c);
+    s2lCand<SRC>(Q, recLm, prev, S.hypOfRow, rb, nRowC, j, c);
     const S2lHyp& h = prev[c.hyp];
     nh = h;
     nh.parent = c.hyp;
@@ -410,7 +474,7 @@ FLTX_DEV void s2lStepUtteranceOn(const S2lParams& Q, char* smem, const float* re
       if (c.isNew) {
         nh.psid = h.sid;
         nh.edge = c.newEdge;
-        if constexpr (!REC) {
+        if constexpr (SRC == kS2lLmTables) {
           if (P.lmOn) {
             (void)s2sLm(P, h.ctx, c.usr, kS2sLmFinish, nh.ctx);
           }
@@ -450,6 +514,9 @@ FLTX_DEV void s2lStepUtteranceOn(const S2lParams& Q, char* smem, const float* re
   __syncthreads();
   if (L.full) { /* the state table is full: the utterance stops, its status says so (never a silent wrong merge) */
     s2sIdleStep(P, b);
+    if constexpr (SRC == kS2lLmWordRows) {
+      s2lNoWords(P, b, outWord);
+    }
     if (tid == 0) {
       Q.status[b] |= ST_TABLE_FULL;
       P.nRowsInt[b] = 0;
@@ -478,10 +545,16 @@ FLTX_DEV void s2lStepUtteranceOn(const S2lParams& Q, char* smem, const float* re
   if (tid == 0) {
     Q.merges[b] += nMerged;
   }
-  s2sPublishStep(P, S, b, nSel, isLive, token, parent, srcRow);
+  if constexpr (SRC == kS2lLmWordRows) {
+    s2sPublishStepWith(P, S, b, nSel, isLive, token, parent, srcRow, S2lRowExtra{outWord, rowNode, nh.word, nh.node});
+  } else {
+    s2sPublishStep(P, S, b, nSel, isLive, token, parent, srcRow);
+  }
 }
 
-FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) { s2lStepUtteranceOn<false>(Q, smem, nullptr); }
+FLTX_DEV void s2lStepUtterance(const S2lParams& Q, char* smem) {
+  s2lStepUtteranceOn<kS2lLmTables>(Q, smem, nullptr);
+}
 
 /* the step with the LM term from the records (a rows LM) */
 struct S2lLmRowsParams {
@@ -490,7 +563,122 @@ struct S2lLmRowsParams {
 };
 
 FLTX_DEV void s2lStepUtteranceLmRows(const S2lLmRowsParams& R, char* smem) {
-  s2lStepUtteranceOn<true>(R.q, smem, R.recLm);
+  s2lStepUtteranceOn<kS2lLmTokenRows>(R.q, smem, R.recLm);
+}
+
+/* ---- word-level LM rows (fltx_lm_word_rows_create) ------------------------------------------------------------------
+ * the gather: for every entry of a live row's record the S floats the step can read (see the head of this file).
+ *   log-probs: one wave per row, four rows per workgroup, lanes over the record's entries: <= cap * S elements of the
+ *              LM row are read, whatever its width;
+ *   logits:    one workgroup per decoder row: s2sLmRowLse (fltx_s2s.h: the same max / sum passes, summation order and
+ *              widening; rows wider than the register cache re-read per pass) over the LM row lmRowOf names, then the
+ *              same gather.  A shared LM row has its lse computed once per decoder row that names it -- the same bits
+ *              every time; the duplicated reads are the price of one launch without a row-level dependency.
+ * Every index is formed in 64 bits from a row number and a stride; an element index is an int below the width (at most
+ * kS2lMaxLmWidth).  A decoder row whose lmRowOf entry lies outside [0, nLmRows) reads nothing: its slots are NaN. */
+constexpr int kS2lMaxLmWidth = 1 << 22;
+
+struct S2lWordLmParams {
+  S2sLmRowsParams r;      /* r.s: the step's lexicon-free view; r.x / rowStride / width / finishIdx / rowLse: the LM's
+                           * rows; r.usrToLm: word id -> LM index (null: identity); r.recLm: [B*K][cap][S] */
+  S2lTrie trie;
+  const int32_t* rowNode; /* [B*K]: the trie node of each row's hypothesis */
+  const int32_t* lmRowOf; /* [B*K] or null (identity): the LM row of each decoder row */
+  int32_t nLmRows;
+  int32_t S;
+};
+
+/* the LM row of decoder row r; null: none */
+template <int DT>
+FLTX_DEV const void* s2lWordLmRow(const S2lWordLmParams& W, int64_t r) {
+  const int64_t lr = W.lmRowOf ? (int64_t)W.lmRowOf[r] : r;
+  if (lr < 0 || lr >= (int64_t)W.nLmRows) {
+    return nullptr;
+  }
+  return (const char*)W.r.x + lr * W.r.rowStride * (DT == kS2sDtF32 ? 4 : 2);
+}
+
+template <int DT, bool LOGITS>
+FLTX_DEV void s2lWordLmGather(const S2lWordLmParams& W, int64_t r, const void* row, double lse, int tid, int nThreads) {
+  const S2sLmRowsParams& Q = W.r;
+  const S2sParams& P = Q.s;
+  const int n = P.recN[r], S = W.S;
+  const int node = W.rowNode[r];
+  for (int e = tid; e < n; e += nThreads) {
+    const int tok = P.recTok[r * P.cap + e];
+    float* out = Q.recLm + (r * P.cap + e) * S;
+    int l0 = 0, nl = 0;
+    bool fin = false;
+    if (tok == P.eos) {
+      fin = node == 0;
+    } else {
+      const int child = s2lChild(W.trie, node, tok);
+      if (child >= 0) {
+        l0 = W.trie.labOff[child];
+        nl = W.trie.labOff[child + 1] - l0;
+      }
+    }
+    for (int s = 0; s < S; ++s) {
+      int idx = -1;
+      if (s == 0) {
+        idx = fin ? Q.finishIdx : -1;
+      } else if (s - 1 < nl) {
+        const int word = W.trie.labels[l0 + s - 1];
+        idx = Q.usrToLm ? Q.usrToLm[word] : word;
+      }
+      float v = __uint_as_float(0x7FC00000u);
+      if (row != nullptr && idx >= 0 && idx < Q.width) {
+        v = s2sTypedScore<DT, LOGITS>(row, idx, lse);
+      }
+      out[s] = v;
+    }
+  }
+}
+
+template <int DT, bool LOGITS>
+FLTX_DEV void s2lWordLmRows(const S2lWordLmParams& W, char* smem) {
+  const S2sLmRowsParams& Q = W.r;
+  const S2sParams& P = Q.s;
+  if constexpr (!LOGITS) { /* workgroup = four waves, wave = row b*K + k of the step */
+    const int wave = waveUniform(waveId());
+    const int64_t r = (int64_t)blockIdx.x * ((int)blockDim.x >> 6) + wave;
+    if (r >= (int64_t)P.B * P.K || !s2sRowLive(P, r)) {
+      return; /* (the record of a row that is not live is empty: the step reads no recLm of it) */
+    }
+    s2lWordLmGather<DT, false>(W, r, s2lWordLmRow<DT>(W, r), 0.0, laneId(), 64);
+  } else { /* workgroup = row b*K + k of the step */
+    const int64_t r = (int64_t)blockIdx.x;
+    const void* row = s2sRowLive(P, r) ? s2lWordLmRow<DT>(W, r) : nullptr;
+    if (row == nullptr) {
+      if (threadIdx.x == 0 && Q.rowLse) {
+        Q.rowLse[r] = __longlong_as_double(0x7FF8000000000000ll);
+      }
+      if (s2sRowLive(P, r)) {
+        s2lWordLmGather<DT, true>(W, r, nullptr, 0.0, (int)threadIdx.x, kS2sLmThreads);
+      }
+      return;
+    }
+    S2sLmRowsLds& S = *(S2sLmRowsLds*)smem;
+    constexpr int kPer = DT == kS2sDtF32 ? 4 : 8;
+    const double lse = Q.width <= kS2sLmVecs * kS2sLmThreads * kPer ? s2sLmRowLse<DT, true>(Q, S, row)
+                                                                     : s2sLmRowLse<DT, false>(Q, S, row);
+    if (Q.rowLse && threadIdx.x == 0) {
+      Q.rowLse[r] = lse;
+    }
+    s2lWordLmGather<DT, true>(W, r, row, lse, (int)threadIdx.x, kS2sLmThreads);
+  }
+}
+
+/* the step with the LM term from the word-level records; it also lists next_word and leaves rowNode */
+struct S2lWordLmStepParams {
+  S2lParams q;
+  const float* recLm; /* [B*K][cap][S], as fltx_s2s_lex_word_lm_rows_kernel gathered it */
+  int32_t* outWord;   /* [B*K]: the caller's next_word */
+  int32_t* rowNode;   /* [B*K] */
+};
+
+FLTX_DEV void s2lStepUtteranceWordLmRows(const S2lWordLmStepParams& R, char* smem) {
+  s2lStepUtteranceOn<kS2lLmWordRows>(R.q, smem, R.recLm, R.outWord, R.rowNode);
 }
 
 /* decodeStep's start (:29-31): the root in LM::start's state (sid 0) at the trie's root */
