@@ -45,7 +45,8 @@ enum {
 enum { FLTX_CRITERION_ASG = 0, FLTX_CRITERION_CTC = 1, FLTX_CRITERION_S2S = 2 };
 /* SmearingMode, decoder/Trie.h:21-25. */
 enum { FLTX_SMEAR_NONE = 0, FLTX_SMEAR_MAX = 1, FLTX_SMEAR_LOGADD = 2 };
-enum { FLTX_DECODER_LEXFREE = 0, FLTX_DECODER_LEXICON = 1, FLTX_DECODER_S2S_LEXFREE = 2, FLTX_DECODER_S2S_LEXICON = 3 };
+enum { FLTX_DECODER_LEXFREE = 0, FLTX_DECODER_LEXICON = 1, FLTX_DECODER_S2S_LEXFREE = 2, FLTX_DECODER_S2S_LEXICON = 3,
+       FLTX_DECODER_CTC_ROWS = 4 };
 
 /* LexiconDecoderOptions (decoder/LexiconDecoder.h:21-31); the lexicon-free
  * decoder (decoder/LexiconFreeDecoder.h:20-28) ignores word_score/unk_score. */
@@ -306,9 +307,11 @@ FLTX_API int fltx_s2s_step_typed(fltx_decoder* dec, const void* scores, int32_t 
  * entry must lie in [0, lm_width) when lm_width > 0, else FLTX_ERR_INVALID.  finish_index: the LM index LM::finish reads
  * (ConvLM.cpp:140-141: the LM's </s>); -1: usr_to_lm[eos] of the decoder.  The LM's per-hypothesis state is the
  * caller's, carried by index_select(next_src_row) as the model's is.
- * Two decoders take such an LM: fltx_s2s_decoder_create (every hypothesis has its own prefix and so its own state: no
- * merges) and fltx_s2s_lex_decoder_create with is_lm_token != 0 (a word-piece LM under a lexicon: hypotheses that
- * segment one token string differently share a state and merge, see there).  The other decoders, a lexicon seq2seq
+ * Three decoders take such an LM: fltx_s2s_decoder_create (every hypothesis has its own prefix and so its own state: no
+ * merges), fltx_s2s_lex_decoder_create with is_lm_token != 0 (a word-piece LM under a lexicon: hypotheses that
+ * segment one token string differently share a state and merge, see there) and fltx_ctc_rows_decoder_create (CTC
+ * emissions, one LM row per LM state; finish_index must be given there).  The other decoders (fltx_decoder_create among
+ * them), a lexicon seq2seq
  * decoder with is_lm_token == 0 (word-level rows come in by fltx_lm_word_rows_create below), fltx_group_create and the
  * fltx_lm_* state functions return FLTX_ERR_UNSUPPORTED.
  * The caller's obligation: the LM must be a pure function of the token prefix -- the same row for the same tokens since
@@ -441,6 +444,74 @@ FLTX_API int fltx_s2s_lex_set_max_states(fltx_decoder* dec, int32_t max_states);
  * candidates of each utterance folded into another since fltx_s2s_begin (synchronises). */
 FLTX_API int fltx_s2s_lex_info(fltx_decoder* dec, int64_t* trie_bytes, int64_t* n_nodes, int64_t* n_edges,
                                int32_t* merges);
+
+/* ---- lexicon-free CTC with a rows LM: LexiconFreeDecoder as a batched device step per frame ----------------------- */
+/* LexiconFreeDecoder(opt, lm, sil, blank, {}) (decoder/LexiconFreeDecoder.h:102-112, .cpp:20-158) for B utterances at once
+ * with a neural token LM in shallow fusion: `lm` is a rows LM (fltx_lm_rows_create: lm_width, usr_to_lm, and a
+ * finish_index >= 0 -- CTC has no eos token whose entry LM::finish could default to).  The LM stays the caller's: between
+ * two frame steps it runs on the device and hands in one row of lm_width scores per LM STATE.  A decoder kind of its own
+ * (FLTX_DECODER_CTC_ROWS): fltx_decoder_create keeps refusing rows LMs; fltx_decode_batch, fltx_stream_* and fltx_s2s_* on
+ * this decoder, and fltx_ctc_rows_* on any other, return FLTX_ERR_STATE; fltx_group_create refuses the kind.  Any other
+ * LM (a word-level rows LM included) and the ASG criterion: FLTX_ERR_UNSUPPORTED.  word_score and unk_score are ignored.
+ * The caller's obligation is fltx_lm_rows_create's: the LM is a pure function of the token prefix -- here the token
+ * string CTC collapses a path to.
+ * Limits (FLTX_ERR_UNSUPPORTED beyond them; there is no CPU fallback): beam_size <= 256, N <= 65 536,
+ * min(beam_size_token, N) <= 256.  Each utterance names its LM states in a table of min(beam_size * max T + 2,
+ * max_states) entries (max_states: 65 536, or fltx_decoder_set(dec, "max_states", n) before fltx_ctc_rows_begin); an
+ * utterance that needs more stops, and fltx_result_count reports FLTX_ERR_UNSUPPORTED ("LM-state table full") for it. */
+FLTX_API int fltx_ctc_rows_decoder_create(fltx_ctx* ctx, const fltx_options* opt, const fltx_lm* lm, int32_t sil,
+                                          int32_t blank, fltx_decoder** out);
+/* decodeBegin (:20-28) for B utterances.  Emissions as for fltx_decode_batch: float32, utterance b reads T[b]*N floats
+ * (frame-major) at emissions + offsets[b] (offsets NULL: one after the other); offsets and T are host arrays.  A host
+ * buffer (on_device == 0) is copied before the call returns.  A DEVICE buffer is read by this call alone -- the token
+ * beams of all frames are taken here, on the context's stream -- but must stay valid and unchanged until
+ * fltx_ctc_rows_end has been queued: a later begin may read it again.  FLTX_ERR_INVALID when the LM's map has fewer than
+ * N entries, a token's LM index or the finish index lies outside the LM's rows, or finish_index < 0.
+ * Row lists are caller-owned DEVICE buffers of B*K int32 (K = beam_size), n_rows of B: row b*K + k is hypothesis k of
+ * utterance b's current beam (every hypothesis is live in CTC); entries k >= n_rows[b] are padding (-1).  For each row:
+ *   next_src_row  the parent's row in the call that produced it (-1 for the root);
+ *   next_token    the token that advanced the LM state in this frame, -1 when the state is the parent's (a blank, or a
+ *                 repeat without a blank in between); the root lists sil;
+ *   next_state    the hypothesis' canonical LM-state id within its utterance (the root's: 0), stable for the whole decode:
+ *                 two rows with the same id are in the same LM state, and the same id at a later frame is that state again
+ *                 -- a caller keeps one LM row per id and runs the LM only for ids it has not seen (the new state is the
+ *                 state of row next_src_row advanced by next_token).
+ * This call lists one row per utterance: the root. */
+FLTX_API int fltx_ctc_rows_begin(fltx_decoder* dec, const float* emissions, int32_t on_device, const int64_t* offsets,
+                                 const int32_t* T, int32_t B, int32_t N, int32_t* next_token, int32_t* next_src_row,
+                                 int32_t* next_state, int32_t* n_rows);
+/* One frame of every utterance that has frames left (:41-123).  lm_scores: n_lm_rows rows of lm_width entries of
+ * lm_dtype, row i at lm_scores + i * lm_row_stride ELEMENTS (lm_row_stride >= lm_width); lm_row_of (B*K int32, may be
+ * NULL: identity, n_lm_rows taken as B*K) names the LM row of each decoder row -- one LM row can serve many.  An entry
+ * outside [0, n_lm_rows) on a live row makes that row's LM entries NaN: it keeps its blank and repeat candidates and has
+ * no new-token candidate; nothing is read through it.  Both are device pointers (on_device != 0) or host pointers, staged
+ * in their own types.  lm_kind FLTX_S2S_LOG_PROBS: the entry widened exactly; FLTX_S2S_LOGITS: (float)((double)x - lse),
+ * lse as fltx_s2s_step_typed defines it; lm_row_lse (may be NULL; B*K doubles on the device, indexed by DECODER row)
+ * receives the lse of the LM row each live row names, NaN for the other rows.
+ * Per frame and utterance: the token beam is the frame's min(beam_size_token, N) largest emissions (ties to the lower
+ * token).  For hypothesis h and kept token n: score = h.score + e[n] (+ sil_score when n == sil); when n != blank and
+ * (n != h.token or h.prevBlank) -- a new token -- lm = the entry at usr_to_lm[n] of h's LM row, score += lm_weight * lm
+ * (a mul and an add), the state becomes child(state, n); a blank keeps the state and sets prevBlank; a repeat keeps the
+ * state.  emittingModelScore and lmScore accumulate separately, also at lm_weight == 0.  Candidates below best -
+ * beam_threshold go; candidates equal in (state, token, prevBlank) merge (max, or logAdd when log_add != 0; the best
+ * member's fields survive, next_src_row among them); the beam_size best survive, sorted best first.  A NaN score is never
+ * a candidate; a -inf LM entry behaves as a -inf emission.
+ * An utterance with no frames left keeps its beam and lists it again unchanged (next_src_row the slot itself, next_token
+ * -1, the same ids); a step after every utterance's last frame changes nothing (lm_scores may be NULL then).
+ * Asynchronous on the context's stream.  FLTX_ERR_INVALID on a bad lm_dtype or lm_kind, lm_row_stride < lm_width, NULL
+ * outputs, n_lm_rows < 1 with lm_row_of, or NULL lm_scores while frames are left. */
+FLTX_API int fltx_ctc_rows_step(fltx_decoder* dec, const void* lm_scores, int32_t lm_dtype, int32_t lm_kind,
+                                int64_t lm_row_stride, const int32_t* lm_row_of, int32_t n_lm_rows, int32_t on_device,
+                                double* lm_row_lse, int32_t* next_token, int32_t* next_src_row, int32_t* next_state,
+                                int32_t* n_rows);
+/* decodeEnd (:127-158) and the back-trace.  The LM rows are given as to fltx_ctc_rows_step, for the rows the last step
+ * listed; each hypothesis reads the entry at finish_index of its row: score += lm_weight * lm, the state child(state, -1),
+ * the token sil.  Hypotheses in one state merge, the n-best is sorted best first, and fltx_result_* read it in the layout
+ * fltx_decode_batch produces: T[b] + 2 tokens per hypothesis (the root's sil, the frames' tokens, decodeEnd's sil), words
+ * all -1.  (Ended before an utterance's last frame, its results hold the frames decoded so far.) */
+FLTX_API int fltx_ctc_rows_end(fltx_decoder* dec, const void* lm_scores, int32_t lm_dtype, int32_t lm_kind,
+                               int64_t lm_row_stride, const int32_t* lm_row_of, int32_t n_lm_rows, int32_t on_device,
+                               double* lm_row_lse);
 
 /* ---- results (getAllFinalHypothesis / getBestHypothesis) ------------------ */
 /* Number of hypotheses of utterance b and the length (finalFrame + 1) of each

@@ -14,7 +14,7 @@ DEFAULT_LIB = os.path.join(_HERE, "lib", "libfltx.so")
 
 FLTX_OK, ERR_INVALID, ERR_HIP, ERR_OOM, ERR_UNSUPPORTED, ERR_RANGE, ERR_STATE = range(7)
 CRITERION = {"asg": 0, "ctc": 1, "s2s": 2}
-LEXFREE, LEXICON, S2S_LEXFREE, S2S_LEXICON = 0, 1, 2, 3
+LEXFREE, LEXICON, S2S_LEXFREE, S2S_LEXICON, CTC_ROWS = 0, 1, 2, 3, 4
 # fltx_decoder_get "why_not_lane" (include/fltx.h FLTX_WHY_*)
 (FLTX_WHY_TOKENS, FLTX_WHY_BEAM, FLTX_WHY_STREAM, FLTX_WHY_LM, FLTX_WHY_LOGADD, FLTX_WHY_ASG, FLTX_WHY_UNK,
  FLTX_WHY_TRIE_SHAPE, FLTX_WHY_WORD_END, FLTX_WHY_OPTIONS, FLTX_WHY_LENGTH, FLTX_WHY_SWITCHED_OFF,
@@ -93,6 +93,7 @@ class Lib:
         "fltx_s2s_end", "fltx_s2s_lex_decoder_create", "fltx_s2s_lex_set_max_states", "fltx_s2s_lex_info",
         "fltx_lm_rows_create", "fltx_s2s_step_lm_rows",
         "fltx_lm_word_rows_create", "fltx_s2s_step_word_lm_rows",
+        "fltx_ctc_rows_decoder_create", "fltx_ctc_rows_begin", "fltx_ctc_rows_step", "fltx_ctc_rows_end",
     ]
 
     def __init__(self, path=None):
@@ -176,6 +177,10 @@ class Lib:
             "fltx_s2s_lex_decoder_create": [vp, C.POINTER(S2sLexOptions), vp, vp, i32, i32, i32, pvp],
             "fltx_s2s_lex_set_max_states": [vp, i32],
             "fltx_s2s_lex_info": [vp, vp, vp, vp, vp],
+            "fltx_ctc_rows_decoder_create": [vp, C.POINTER(Options), vp, i32, i32, pvp],
+            "fltx_ctc_rows_begin": [vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp],
+            "fltx_ctc_rows_step": [vp, vp, i32, i32, i64, vp, i32, i32, vp, vp, vp, vp, vp],
+            "fltx_ctc_rows_end": [vp, vp, i32, i32, i64, vp, i32, i32, vp],
         }
         for name, args in sig.items():
             fn = getattr(L, name)
@@ -1108,6 +1113,167 @@ class LexiconSeq2SeqBatchDecoder(Seq2SeqBatchDecoder):
         self.L.check(self.L.lib.fltx_s2s_lex_info(self.h, C.addressof(tb), C.addressof(nn), C.addressof(ne),
                                                   _ptr(m) if self.B else None))
         return dict(trie_bytes=tb.value, nodes=nn.value, edges=ne.value, merges=m.tolist() if self.B else None)
+
+
+class CtcRowsBatchDecoder(BatchDecoder):
+    """fltx_ctc_rows_*: LexiconFreeDecoder (CTC) for B utterances at once with a neural token LM in shallow fusion, one
+    device step per frame.  `rows_lm` is a RowsLM with a finish_index >= 0; `options` are make_options(...)'s with the
+    CTC criterion (word_score / unk_score ignored).
+
+    begin(emissions, T, N) and step(lm_scores) return the next call's rows (token, src_row, state) as [B, K] int32 and
+    n_rows as [B] int32 -- torch tensors on the context's device (numpy arrays on the emulator library).  Row k of
+    utterance b is hypothesis k of its current beam; `state` is the hypothesis' LM-state id within the utterance, stable
+    for the whole decode; `token` is the token that advanced the state in this frame (-1: the state is that of row
+    src_row); rows k >= n_rows[b] are padding (-1).  lm_scores is [n_lm_rows, >= lm_width], ONE ROW PER LM STATE, and
+    lm_row_of (B*K int32; None: identity) names the LM row of each decoder row.  end(lm_scores) reads each row's finish
+    entry; then the results* methods read the n-best (T[b] + 2 tokens, as decode_batch gives them).  decode() drives it
+    all from a callable."""
+
+    _rows = Seq2SeqBatchDecoder._rows
+    _addr = staticmethod(Seq2SeqBatchDecoder._addr)
+    _lse_ptr = Seq2SeqBatchDecoder._lse_ptr
+
+    def __init__(self, ctx, options, rows_lm, sil, blank):
+        self.ctx, self.L = ctx, ctx.L
+        self.kind, self.options = CTC_ROWS, options
+        self._keep = (rows_lm, None)
+        self.sil, self.blank = int(sil), int(blank)
+        h = C.c_void_p()
+        self.L.check(self.L.lib.fltx_ctc_rows_decoder_create(ctx.h, C.byref(options), rows_lm.h, int(sil), int(blank),
+                                                             C.byref(h)))
+        self.h = h
+        self.B = 0
+        self.N = None
+        self._emu = "emulation" in self.L.version()
+        _live["dec"].add(self)
+
+    def set_max_states(self, n):
+        """LM states per utterance from the next begin() on (default 65 536)"""
+        self.set("max_states", n)
+
+    def begin(self, emissions, T, N, offsets=None, device_ptr=None):
+        """emissions: a host float32 array (flat layout, copied by the call), or None when device_ptr (int) addresses
+        emissions in HBM -- those must stay valid until end().  -> (token, src_row, state, n_rows): the roots."""
+        T = np.ascontiguousarray(T, dtype=np.int32)
+        self.B, self.N, self._T = len(T), int(N), T
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        out = self._rows()
+        ptrs = [self._addr(o) for o in out]
+        if device_ptr is not None:
+            self._chk(self.L.lib.fltx_ctc_rows_begin(self.h, device_ptr, 1, _ptr(off), _ptr(T), self.B, self.N, *ptrs))
+        else:
+            e = np.ascontiguousarray(emissions, dtype=np.float32)
+            self._chk(self.L.lib.fltx_ctc_rows_begin(self.h, _ptr(e), 0, _ptr(off), _ptr(T), self.B, self.N, *ptrs))
+        return tuple(out)
+
+    def _lm_in(self, lm_scores, lm_row_of, lm_kind, lm_lse_out, lm_dtype):
+        """-> the C arguments of the LM rows (and what must stay alive while the kernels read them)"""
+        if lm_kind not in S2S_KINDS:
+            raise ValueError("lm_kind: one of %s" % sorted(S2S_KINDS))
+        BK = self.B * int(self.options.beam_size)
+        if lm_scores is None:  # (a step after the last frame reads no LM rows)
+            return (None, DTYPE_F32, S2S_KINDS[lm_kind], 1 << 40, None, 0, 1, self._lse_ptr(lm_lse_out, BK)), ()
+        if isinstance(lm_scores, np.ndarray):
+            if lm_dtype is not None:
+                if lm_dtype not in ("bf16", "bfloat16") or lm_scores.dtype != np.uint16:
+                    raise TypeError("lm_dtype=%r: numpy rows of bfloat16 bits are uint16 with lm_dtype='bf16'" % (lm_dtype,))
+                ldt = DTYPE_BF16
+            else:
+                ldt = DTYPE_F16 if lm_scores.dtype == np.float16 else DTYPE_F32
+            lsc = np.ascontiguousarray(lm_scores, dtype=_NP_DTYPES[ldt]).reshape(-1, lm_scores.shape[-1])
+            lstride, lptr, on_dev, host = lsc.shape[1], lsc.ctypes.data, 1 if self._emu else 0, True
+        else:
+            lsc, ldt, lstride, lptr, on_dev, host = Seq2SeqBatchDecoder._rows_in(self, lm_scores, lm_dtype, BK, "lm_scores")
+        n_lm = int(lsc.shape[0])
+        ro = None
+        if lm_row_of is not None:
+            if isinstance(lm_row_of, np.ndarray) or host:
+                ro = np.ascontiguousarray(lm_row_of.cpu().numpy() if hasattr(lm_row_of, "cpu") else lm_row_of,
+                                          dtype=np.int32).reshape(-1)
+                n_ro = ro.size
+            else:
+                import torch
+                ro = lm_row_of.reshape(-1).to(torch.int32).contiguous()
+                n_ro = ro.numel()
+            assert n_ro == BK, "lm_row_of: B*K entries"
+        else:
+            assert n_lm >= BK, "lm_scores: B*K rows without lm_row_of"
+        return (lptr, ldt, S2S_KINDS[lm_kind], lstride, None if ro is None else self._addr(ro), n_lm, on_dev,
+                self._lse_ptr(lm_lse_out, BK)), (lsc, ro)
+
+    def step(self, lm_scores, *, lm_row_of=None, lm_kind="log_probs", lm_lse_out=None, lm_dtype=None):
+        """One frame of every utterance that has frames left (fltx_ctc_rows_step).  lm_scores: a torch tensor of
+        float32 / float16 / bfloat16 on the device or the host, or a numpy float32 / float16 array (uint16 holding
+        bfloat16 bits with lm_dtype="bf16"); lm_row_of on the same side.  lm_kind "logits": the step takes each LM
+        row's log-softmax itself; lm_lse_out (device float64, B*K) then receives each live row's log-sum-exp."""
+        out = self._rows()
+        args, keep = self._lm_in(lm_scores, lm_row_of, lm_kind, lm_lse_out, lm_dtype)
+        self._chk(self.L.lib.fltx_ctc_rows_step(self.h, *args, *[self._addr(o) for o in out]))
+        self._inputs = keep  # (kept until the next call: the kernels read them asynchronously)
+        return tuple(out)
+
+    def end(self, lm_scores, *, lm_row_of=None, lm_kind="log_probs", lm_lse_out=None, lm_dtype=None):
+        """decodeEnd and the back-trace: the LM rows of the rows the last step listed, as step() takes them."""
+        args, keep = self._lm_in(lm_scores, lm_row_of, lm_kind, lm_lse_out, lm_dtype)
+        self._chk(self.L.lib.fltx_ctc_rows_end(self.h, *args))
+        self._inputs = keep
+
+    def decode(self, emissions, T, N, lm_rows, *, offsets=None, device_ptr=None, lm_kind="log_probs"):
+        """The whole batch from a callable: lm_rows(state_keys) -> rows, where state_keys is a list of (b, prefix) --
+        utterance and the tuple of tokens the state stands for -- one per LM state the search has just entered, and
+        rows is [len(state_keys), >= lm_width] (a torch tensor on the context's device; numpy on the emulator library),
+        row i the LM's scores after state_keys[i].  One row is kept per state id and shared through lm_row_of, so the
+        LM runs once per state, however many hypotheses and frames are in it.  Returns results_batch().  (The rows are
+        read on the host once per frame to name the new states.)"""
+        tok, src, state, n = self.begin(emissions, T, N, offsets=offsets, device_ptr=device_ptr)
+        B, K = self.B, int(self.options.beam_size)
+        max_t = int(self._T.max()) if B else 0
+        row_of, prefix = {}, {}
+        store, n_store, prev_state = None, 0, None
+
+        def host(a):
+            return a if isinstance(a, np.ndarray) else a.cpu().numpy()
+        for t in range(max_t + 1):
+            if not self._emu:
+                self.ctx.synchronize()
+            tok_h, src_h, st_h, n_h = host(tok), host(src), host(state), host(n)
+            keys = []
+            ro = np.full(B * K, -1, np.int32)
+            for b in range(B):
+                for k in range(int(n_h[b])):
+                    key = (b, int(st_h[b, k]))
+                    if key not in row_of:
+                        s = int(src_h[b, k])
+                        prefix[key] = () if s < 0 else prefix[(b, int(prev_state.reshape(-1)[s]))] + (int(tok_h[b, k]),)
+                        row_of[key] = n_store + len(keys)
+                        keys.append((b, prefix[key]))
+                    ro[b * K + k] = row_of[key]
+            if keys:
+                rows = lm_rows(keys)
+                need = n_store + len(keys)
+                if store is None or need > store.shape[0]:
+                    cap = max(need, 2 * (0 if store is None else store.shape[0]), B * K)
+                    if isinstance(rows, np.ndarray):
+                        grown = np.empty((cap, rows.shape[1]), rows.dtype)
+                    else:
+                        grown = rows.new_empty((cap, rows.shape[1]))
+                    if store is not None:
+                        grown[:n_store] = store[:n_store]
+                    store = grown
+                store[n_store:need] = rows
+                n_store = need
+            prev_state = st_h.copy()
+            ro_in = ro if isinstance(store, np.ndarray) else _to_device_i32(ro, store.device)
+            if t < max_t:
+                tok, src, state, n = self.step(store[:n_store], lm_row_of=ro_in, lm_kind=lm_kind)
+            else:
+                self.end(store[:n_store], lm_row_of=ro_in, lm_kind=lm_kind)
+        return self.results_batch()
+
+
+def _to_device_i32(a, device):
+    import torch
+    return torch.from_numpy(a).to(device)
 
 
 class DecoderGroup:

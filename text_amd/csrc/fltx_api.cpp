@@ -31,6 +31,7 @@
 #include "fltx_engines.h"
 #include "fltx_s2s.h"
 #include "fltx_s2s_lex.h"
+#include "fltx_ctc_rows.h"
 
 using namespace fltx;
 
@@ -199,6 +200,28 @@ __global__ void __launch_bounds__(kS2sBeginThreads) fltx_s2s_lex_begin_kernel(S2
 }
 __global__ void __launch_bounds__(kS2sEndThreads) fltx_s2s_lex_end_kernel(S2lParams Q) {
   s2lEndUtterance(Q, nullptr);
+}
+/* fltx_ctc_rows.h: lexicon-free CTC with a rows LM -- the frames' token beams (once), the LM entries of a frame's kept
+ * tokens, the frame step and its finish variant (decodeEnd + back-trace), the start */
+__global__ void __launch_bounds__(256) fltx_ctc_rows_tokbeam_kernel(CrParams Q) {
+  __shared__ __attribute__((aligned(16))) S2sFrontLds fltx_cr_front[4];
+  crTokBeamRows(Q, (char*)fltx_cr_front);
+}
+template <int DT, bool LOGITS>
+__global__ void __launch_bounds__(kS2sLmThreads) fltx_ctc_rows_lm_kernel(CrLmParams W) {
+  __shared__ __attribute__((aligned(16))) S2sLmRowsLds fltx_cr_lm_lds;
+  crLmRows<DT, LOGITS>(W, (char*)&fltx_cr_lm_lds);
+}
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_step_kernel(CrParams Q) {
+  __shared__ __attribute__((aligned(16))) S2lStepLds fltx_cr_step_lds;
+  crStepUtterance<false>(Q, (char*)&fltx_cr_step_lds);
+}
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_end_kernel(CrParams Q) {
+  __shared__ __attribute__((aligned(16))) S2lStepLds fltx_cr_end_lds;
+  crStepUtterance<true>(Q, (char*)&fltx_cr_end_lds);
+}
+__global__ void __launch_bounds__(kS2sBeginThreads) fltx_ctc_rows_begin_kernel(CrParams Q) {
+  crBeginUtterance(Q, nullptr);
 }
 __global__ void __launch_bounds__(1024) fltx_streamop_kernel(StreamOpParams Q) {
   __shared__ int32_t sh[kStreamOpLds / 4];
@@ -716,10 +739,23 @@ struct fltx_decoder {
     int64_t nodes = 0, edges = 0, labels = 0, trieBytes = 0;
     DBuf trieMax, kidOff, kidTok, kidNode, labOff, lab; /* the compact trie */
     DBuf cScore, cMk, cGrp, cList, cNext, mTab, sKey, sVal, sCount, status, merges;
+    /* lexicon-free CTC with a rows LM (kind FLTX_DECODER_CTC_ROWS, fltx_ctc_rows.h; it shares the buffers above): the
+     * longest utterance, frames in all, {frameOff[B + 1], emOff[B]} int64 then T[B] int32 on the device and their host
+     * copy, the device copy of host emissions */
+    int crMaxT = 0;
+    int64_t crFrames = 0;
+    DBuf crMeta, crEmis;
+    std::vector<int64_t> crMetaHost;
+    const float* crEmisDev = nullptr;
   } s2s;
 };
 
 static bool isS2sKind(int kind) { return kind == FLTX_DECODER_S2S_LEXFREE || kind == FLTX_DECODER_S2S_LEXICON; }
+/* decoders that are stepped by their own entry points (fltx_s2s_*, fltx_ctc_rows_*): no batch call, no streams */
+static const char* stepKindCalls(int kind) {
+  return isS2sKind(kind) ? "a seq2seq decoder steps with fltx_s2s_step"
+                         : kind == FLTX_DECODER_CTC_ROWS ? "a CTC rows decoder steps with fltx_ctc_rows_step" : nullptr;
+}
 /* decoders whose results carry words */
 static bool kindHasWords(int kind) { return kind == FLTX_DECODER_LEXICON || kind == FLTX_DECODER_S2S_LEXICON; }
 
@@ -1666,12 +1702,15 @@ int fltx_decoder_create(fltx_ctx* ctx, int32_t kind, const fltx_options* opt, co
   if (!ctx || !opt || !lm || !out) {
     return fail(FLTX_ERR_INVALID, "fltx_decoder_create: null argument");
   }
+  if (kind == FLTX_DECODER_CTC_ROWS) { /* (fltx_group_create comes through here too) */
+    return fail(FLTX_ERR_UNSUPPORTED, "a CTC rows decoder is made with fltx_ctc_rows_decoder_create (no groups)");
+  }
   if (kind != FLTX_DECODER_LEXFREE && kind != FLTX_DECODER_LEXICON) {
     return fail(FLTX_ERR_INVALID, "unknown decoder kind %d", kind);
   }
   if (lm->kind == 3 || lm->kind == 4) {
     return fail(FLTX_ERR_UNSUPPORTED, "a rows LM (fltx_lm_rows_create, fltx_lm_word_rows_create) serves the seq2seq "
-                                      "decoders only");
+                                      "decoders and fltx_ctc_rows_decoder_create only");
   }
   if (kind == FLTX_DECODER_LEXICON && !trie) {
     return fail(FLTX_ERR_INVALID, "lexicon decoder needs a trie");
@@ -1854,6 +1893,13 @@ int fltx_decoder_set(fltx_decoder* d, const char* key, int64_t value) {
   }
   if (!strcmp(key, "defer_check")) {
     d->deferCheck = value == 2 ? 2 : (value ? 1 : 0);
+    return FLTX_OK;
+  }
+  if (!strcmp(key, "max_states")) { /* a CTC rows decoder: LM states per utterance from the next fltx_ctc_rows_begin on */
+    if (d->kind != FLTX_DECODER_CTC_ROWS || value < 1 || value > 0x7FFFFFFF) {
+      return fail(FLTX_ERR_INVALID, "max_states: a CTC rows decoder (fltx_ctc_rows_decoder_create) and a count >= 1");
+    }
+    d->s2s.maxStates = (int)value;
     return FLTX_OK;
   }
   if (!strcmp(key, "compact_always")) {
@@ -3892,8 +3938,8 @@ int fltx_decode_batch(fltx_decoder* d, const float* emissions, int32_t onDevice,
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
-  if (d && isS2sKind(d->kind)) {
-    return fail(FLTX_ERR_STATE, "fltx_decode_batch: a seq2seq decoder steps with fltx_s2s_step");
+  if (d && stepKindCalls(d->kind)) {
+    return fail(FLTX_ERR_STATE, "fltx_decode_batch: %s", stepKindCalls(d->kind));
   }
   if (!d || !T || B <= 0 || N <= 0) {
     return fail(FLTX_ERR_INVALID, "fltx_decode_batch: bad argument");
@@ -4123,8 +4169,8 @@ int fltx_stream_begin(fltx_decoder* d, int32_t B, int32_t N, int32_t maxFrames) 
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
-  if (d && isS2sKind(d->kind)) {
-    return fail(FLTX_ERR_STATE, "fltx_stream_begin: a seq2seq decoder steps with fltx_s2s_step");
+  if (d && stepKindCalls(d->kind)) {
+    return fail(FLTX_ERR_STATE, "fltx_stream_begin: %s", stepKindCalls(d->kind));
   }
   if (!d || B <= 0 || N <= 0 || maxFrames < 0) {
     return fail(FLTX_ERR_INVALID, "fltx_stream_begin: bad argument");
@@ -4212,8 +4258,8 @@ int fltx_stream_step(fltx_decoder* d, const float* emissions, int32_t onDevice, 
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
-  if (d && isS2sKind(d->kind)) {
-    return fail(FLTX_ERR_STATE, "fltx_stream_step: a seq2seq decoder steps with fltx_s2s_step");
+  if (d && stepKindCalls(d->kind)) {
+    return fail(FLTX_ERR_STATE, "fltx_stream_step: %s", stepKindCalls(d->kind));
   }
   if (!d || !T) {
     return fail(FLTX_ERR_INVALID, "fltx_stream_step: bad argument");
@@ -4316,8 +4362,8 @@ int fltx_stream_end(fltx_decoder* d) {
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
-  if (d && isS2sKind(d->kind)) {
-    return fail(FLTX_ERR_STATE, "fltx_stream_end: a seq2seq decoder steps with fltx_s2s_step");
+  if (d && stepKindCalls(d->kind)) {
+    return fail(FLTX_ERR_STATE, "fltx_stream_end: %s", stepKindCalls(d->kind));
   }
   if (!d) {
     return fail(FLTX_ERR_INVALID, "null decoder");
@@ -4358,8 +4404,8 @@ int fltx_stream_prune(fltx_decoder* d, int32_t lookBack) {
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
-  if (d && isS2sKind(d->kind)) {
-    return fail(FLTX_ERR_STATE, "fltx_stream_prune: a seq2seq decoder steps with fltx_s2s_step");
+  if (d && stepKindCalls(d->kind)) {
+    return fail(FLTX_ERR_STATE, "fltx_stream_prune: %s", stepKindCalls(d->kind));
   }
   if (!d || lookBack < 0) {
     return fail(FLTX_ERR_INVALID, "fltx_stream_prune: bad argument");
@@ -4713,7 +4759,7 @@ int fltx_result_best(fltx_decoder* d, int32_t b, int32_t lookBack, double* score
   if (!d->haveResults) {
     return fail(FLTX_ERR_STATE, "no decode has been run");
   }
-  if (isS2sKind(d->kind)) { /* getBestHypothesis ignores lookBack: the final beam's first (:165-169) */
+  if (stepKindCalls(d->kind)) { /* getBestHypothesis ignores lookBack: the final beam's first (:165-169) */
     int32_t n = 0, len = 0;
     int rc = fltx_result_count(d, b, &n, &len);
     if (rc) {
@@ -5883,6 +5929,395 @@ int fltx_s2s_end(fltx_decoder* d) {
   } else {
     S2S_LAUNCH(fltx_s2s_end_kernel, s2sEndUtterance, B, kS2sEndThreads, 0, st, P);
   }
+  d->haveResults = true;
+  d->ended = true;
+  d->backtraced = true;
+  d->streaming = false;
+  d->resultsSynced = false;
+  d->hostFetched = false;
+  d->compactFetched = false;
+  d->scoresFetched = false;
+  d->offlinePending = false;
+  return FLTX_OK;
+}
+
+/* ---- lexicon-free CTC with a rows LM (fltx_ctc_rows.h) ------------------------------------------------------------- */
+static int crCheck(fltx_decoder* d, const char* what) {
+  if (!d) {
+    return fail(FLTX_ERR_INVALID, "%s: null decoder", what);
+  }
+  if (d->kind != FLTX_DECODER_CTC_ROWS) {
+    return fail(FLTX_ERR_STATE, "%s: not a CTC rows decoder (fltx_ctc_rows_decoder_create)", what);
+  }
+  return FLTX_OK;
+}
+
+static CrParams crParams(fltx_decoder* d) {
+  CrParams Q;
+  memset(&Q, 0, sizeof(Q));
+  S2sParams& P = Q.s;
+  const int B = d->B;
+  P.B = B;
+  P.K = d->opt.beam_size;
+  P.Kt = d->opt.beam_size_token;
+  P.V = d->N;
+  P.eos = -1;
+  P.maxOut = std::numeric_limits<int32_t>::max();
+  P.t = d->s2s.t;
+  P.cap = d->s2s.cap;
+  P.mSel = d->s2s.cap;
+  P.beamThreshold = d->opt.beam_threshold;
+  P.lmWeight = d->opt.lm_weight;
+  P.beamN = d->s2s.beamN.as<int32_t>();
+  P.nRowsInt = d->s2s.rowsInt.as<int32_t>();
+  P.done = d->s2s.done.as<int32_t>();
+  P.finalStep = d->s2s.finalStep.as<int32_t>();
+  P.recTok = d->s2s.recTok.as<int32_t>();
+  P.recAm = d->s2s.recAm.as<float>();
+  P.recN = d->s2s.recN.as<int32_t>();
+  P.cKey = d->s2s.cKey.as<unsigned long long>();
+  P.nC = (int64_t)P.K * P.cap;
+  P.outBeam = d->s2s.rowNode.as<int32_t>(); /* (the publisher's beam index: src_row - b*K here, nobody's output) */
+  Q.sil = d->sil;
+  Q.blank = d->blank;
+  Q.logAdd = d->opt.log_add ? 1 : 0;
+  Q.silScore = d->opt.sil_score;
+  Q.frameOff = d->s2s.crMeta.as<int64_t>();
+  Q.emOff = Q.frameOff + (B + 1);
+  Q.T = (const int32_t*)(Q.emOff + B);
+  Q.emissions = d->s2s.crEmisDev;
+  Q.beam = d->s2s.beam.as<CrHyp>();
+  Q.hist = d->s2s.hist.as<int2>();
+  Q.cScore = d->s2s.cScore.as<double>();
+  Q.cMk = d->s2s.cMk.as<uint4>();
+  Q.cGrp = d->s2s.cGrp.as<int32_t>();
+  Q.cList = d->s2s.cList.as<int32_t>();
+  Q.cNext = d->s2s.cNext.as<int32_t>();
+  Q.mTab = d->s2s.mTab.as<int32_t>();
+  Q.mSize = d->s2s.mSize;
+  Q.sKey = d->s2s.sKey.as<unsigned long long>();
+  Q.sVal = d->s2s.sVal.as<int32_t>();
+  Q.sCount = d->s2s.sCount.as<int32_t>();
+  Q.sSize = d->s2s.sSize;
+  Q.sMax = d->s2s.sMax;
+  Q.status = d->s2s.status.as<int32_t>();
+  Q.merges = d->s2s.merges.as<int32_t>();
+  Q.recLm = d->s2s.recLm.as<float>();
+  return Q;
+}
+
+int fltx_ctc_rows_decoder_create(fltx_ctx* ctx, const fltx_options* opt, const fltx_lm* lm, int32_t sil, int32_t blank,
+                                 fltx_decoder** out) {
+  if (!ctx || !opt || !lm || !out) {
+    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_decoder_create: null argument");
+  }
+  if (lm->kind != 3) {
+    return fail(FLTX_ERR_UNSUPPORTED, "fltx_ctc_rows_decoder_create: a token-level rows LM (fltx_lm_rows_create) only; "
+                                      "other LMs decode with fltx_decoder_create");
+  }
+  if (opt->criterion != FLTX_CRITERION_CTC) {
+    return fail(FLTX_ERR_UNSUPPORTED, "fltx_ctc_rows_decoder_create: criterion %d not supported (CTC only)",
+                opt->criterion);
+  }
+  if (opt->beam_size < 1 || opt->beam_size_token < 1 || sil < 0 || blank < 0) {
+    return fail(FLTX_ERR_INVALID, "beam_size and beam_size_token must be >= 1, sil and blank >= 0");
+  }
+  if (opt->beam_size > kS2sMaxBeam) {
+    return fail(FLTX_ERR_UNSUPPORTED, "CTC rows: beam_size %d > %d", opt->beam_size, kS2sMaxBeam);
+  }
+  DeviceScope devScope(ctx);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  fltx_lm::Dev* lmDev = nullptr;
+  int rc = lmEnsureUploaded(const_cast<fltx_lm*>(lm), ctx, &lmDev);
+  if (rc) {
+    return rc;
+  }
+  auto* d = new fltx_decoder();
+  d->ctx = ctx;
+  d->lm = lm;
+  d->lmDev = lmDev;
+  d->kind = FLTX_DECODER_CTC_ROWS;
+  d->opt = *opt;
+  d->sil = sil;
+  d->blank = blank;
+  d->s2s.maxStates = kS2lDefaultStates;
+  *out = d;
+  return FLTX_OK;
+}
+
+int fltx_ctc_rows_begin(fltx_decoder* d, const float* emissions, int32_t onDevice, const int64_t* offsets,
+                        const int32_t* T, int32_t B, int32_t N, int32_t* nextTok, int32_t* nextSrc, int32_t* nextState,
+                        int32_t* nRows) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = crCheck(d, "fltx_ctc_rows_begin");
+  if (rc) {
+    return rc;
+  }
+  if (B < 1 || N < 1 || !T || !nextTok || !nextSrc || !nextState || !nRows) {
+    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_begin: bad argument");
+  }
+  if (N > kS2sMaxV) {
+    return fail(FLTX_ERR_UNSUPPORTED, "CTC rows: N = %d > %d", N, kS2sMaxV);
+  }
+  const int K = d->opt.beam_size, cap = std::min(d->opt.beam_size_token, N);
+  if (cap > kS2lMaxKt) {
+    return fail(FLTX_ERR_UNSUPPORTED, "CTC rows: a token beam of %d (beam_size_token, N = %d) > %d", cap, N, kS2lMaxKt);
+  }
+  if (d->sil >= N || d->blank >= N) {
+    return fail(FLTX_ERR_RANGE, "sil index %d or blank index %d outside [0, %d)", d->sil, d->blank, N);
+  }
+  /* the LM's map and finish index against rows of this width (s2sPlanRowsLm's checks with N for V; CTC has no eos token
+   * whose entry finish could fall back to) */
+  d->s2s.eos = N;
+  if ((rc = s2sPlanRowsLm(d, N)) || (rc = s2sRowsLmFinishCheck(d->lm->rowsFinish, d->s2s.lmWidth))) {
+    return rc;
+  }
+  d->s2s.lmFinish = d->lm->rowsFinish;
+  std::vector<int64_t>& meta = d->s2s.crMetaHost; /* frameOff[B + 1], emOff[B], then T[B] as int32 */
+  meta.assign((size_t)2 * B + 1 + ((size_t)B + 1) / 2, 0);
+  int32_t* hT = (int32_t*)(meta.data() + 2 * (size_t)B + 1);
+  d->histOff.resize((size_t)B + 1);
+  int64_t frames = 0, off = 0;
+  int maxT = 0;
+  bool packed = true; /* the utterances' emissions follow each other */
+  for (int b = 0; b < B; ++b) {
+    if (T[b] < 0) {
+      return fail(FLTX_ERR_INVALID, "T[%d] = %d is negative", b, T[b]);
+    }
+    meta[(size_t)b] = frames;
+    packed = packed && (!offsets || offsets[b] == frames * N);
+    meta[(size_t)B + 1 + b] = onDevice && offsets ? offsets[b] : frames * N;
+    hT[b] = T[b];
+    d->histOff[(size_t)b] = off;
+    off += (int64_t)(T[b] + 2) * K;
+    frames += T[b];
+    maxT = std::max(maxT, T[b]);
+  }
+  meta[(size_t)B] = frames;
+  d->histOff[(size_t)B] = off;
+  d->histRecords = off;
+  if (frames > 0 && !emissions) {
+    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_begin: null emissions");
+  }
+  const int64_t nC = (int64_t)K * cap;
+  d->s2s.cap = cap;
+  d->s2s.mSize = s2lPow2AtLeast(2 * nC);
+  d->s2s.sMax = (int)std::min<int64_t>((int64_t)K * maxT + 2, d->s2s.maxStates);
+  d->s2s.sSize = s2lPow2AtLeast(2 * (int64_t)d->s2s.sMax);
+  Stream st = d->ctx->stream;
+  const size_t BK = (size_t)B * K, BC = (size_t)B * (size_t)nC, nF = (size_t)std::max<int64_t>(frames, 1);
+  if (d->s2s.beam.ensure(2 * BK * sizeof(CrHyp), st, false) || d->s2s.beamN.ensure(8 * (size_t)B, st, false) ||
+      d->s2s.hist.ensure((size_t)(maxT + 2) * BK * sizeof(int2), st, false) ||
+      d->s2s.rowsInt.ensure(4 * (size_t)B, st, false) || d->s2s.done.ensure(4 * (size_t)B, st, false) ||
+      d->s2s.finalStep.ensure(4 * (size_t)B, st, false) || d->s2s.recTok.ensure(4 * nF * cap, st, false) ||
+      d->s2s.recAm.ensure(4 * nF * cap, st, false) || d->s2s.recN.ensure(4 * nF, st, false) ||
+      d->s2s.cKey.ensure(8 * BC, st, false) || d->s2s.recLm.ensure(4 * BK * cap, st, false) ||
+      d->s2s.rowNode.ensure(4 * BK, st, false) || d->s2s.cScore.ensure(8 * BC, st, false) ||
+      d->s2s.cMk.ensure(16 * BC, st, false) || d->s2s.cGrp.ensure(4 * BC, st, false) ||
+      d->s2s.cList.ensure(4 * BC, st, false) || d->s2s.cNext.ensure(4 * BC, st, false) ||
+      d->s2s.mTab.ensure(4 * (size_t)B * d->s2s.mSize, st, false) ||
+      d->s2s.sKey.ensure(8 * (size_t)B * d->s2s.sSize, st, false) ||
+      d->s2s.sVal.ensure(4 * (size_t)B * d->s2s.sSize, st, false) || d->s2s.sCount.ensure(4 * (size_t)B, st, false) ||
+      d->s2s.status.ensure(4 * (size_t)B, st, false) || d->s2s.merges.ensure(4 * (size_t)B, st, false) ||
+      d->s2s.crMeta.ensure(8 * meta.size(), st, false) ||
+      (!onDevice && d->s2s.crEmis.ensure(4 * nF * N, st, false))) {
+    return fail(FLTX_ERR_OOM, "CTC rows workspace: device allocation failed (B=%d K=%d N=%d, %lld frames)", B, K, N,
+                (long long)frames);
+  }
+  if (devMemset(d->s2s.sKey.p, 0xFF, 8 * (size_t)B * d->s2s.sSize, st) || /* the state tables: empty */
+      devCopyH2D(d->s2s.crMeta.p, meta.data(), 8 * meta.size(), st)) {
+    return fail(FLTX_ERR_HIP, "CTC rows: upload failed");
+  }
+  d->s2s.crEmisDev = emissions;
+  if (!onDevice && frames > 0) { /* host emissions: copied here, utterance after utterance */
+    float* dst = d->s2s.crEmis.as<float>();
+    int bad = 0;
+    if (packed) {
+      bad = devCopyH2D(dst, emissions + (offsets ? offsets[0] : 0), 4 * (size_t)frames * N, st);
+    } else {
+      for (int b = 0; b < B && !bad; ++b) {
+        if (T[b] > 0) {
+          bad = devCopyH2D(dst + meta[(size_t)b] * N, emissions + offsets[b], 4 * (size_t)T[b] * N, st);
+        }
+      }
+    }
+    if (bad || devSync(st)) { /* (the caller's buffer is only borrowed for the call) */
+      return fail(FLTX_ERR_HIP, "CTC rows: emission upload failed");
+    }
+    d->s2s.crEmisDev = dst;
+  }
+  d->B = B;
+  d->N = N;
+  d->s2s.t = 0;
+  d->s2s.crMaxT = maxT;
+  d->s2s.crFrames = frames;
+  d->s2s.begun = true;
+  d->haveResults = false;
+  d->ended = false;
+  d->backtraced = false;
+  d->resultsSynced = false;
+  d->stateCap = (uint32_t)d->s2s.sMax;
+  CrParams Q = crParams(d);
+  Q.s.outTok = nextTok;
+  Q.s.outSrc = nextSrc;
+  Q.s.outN = nRows;
+  Q.outState = nextState;
+  if (frames > 0) {
+    S2S_LAUNCH(fltx_ctc_rows_tokbeam_kernel, crTokBeamRows, (int)((frames + 3) / 4), 256, 4 * sizeof(S2sFrontLds), st, Q);
+  }
+  S2S_LAUNCH(fltx_ctc_rows_begin_kernel, crBeginUtterance, (B + kS2sBeginThreads - 1) / kS2sBeginThreads,
+             kS2sBeginThreads, 0, st, Q);
+  return FLTX_OK;
+}
+
+extern "C++" {
+template <int DT, bool LOGITS>
+static int crLmRowsLaunch(int nRows, Stream st, const CrLmParams& W) {
+  S2S_LAUNCH((fltx_ctc_rows_lm_kernel<DT, LOGITS>), (crLmRows<DT, LOGITS>), LOGITS ? nRows : (nRows + 3) / 4,
+             kS2sLmThreads, sizeof(S2sLmRowsLds), st, W);
+  return FLTX_OK;
+}
+}
+
+/* the LM rows of a step or of the end (fin): checked, staged when they are the host's, and gathered into recLm */
+static int crLmRowsIn(fltx_decoder* d, const char* what, bool fin, bool idle, const void* lmScores, int32_t lmDtype,
+                      int32_t lmKind, int64_t lmRowStride, const int32_t* lmRowOf, int32_t nLmRows, int32_t onDevice,
+                      double* lmRowLse, const CrParams& Q) {
+  if (lmDtype != FLTX_DTYPE_F32 && lmDtype != FLTX_DTYPE_F16 && lmDtype != FLTX_DTYPE_BF16) {
+    return fail(FLTX_ERR_INVALID, "%s: lm_dtype %d", what, lmDtype);
+  }
+  if (lmKind != FLTX_S2S_LOG_PROBS && lmKind != FLTX_S2S_LOGITS) {
+    return fail(FLTX_ERR_INVALID, "%s: lm_kind %d", what, lmKind);
+  }
+  if ((!lmScores && !idle) || lmRowStride < d->s2s.lmWidth || (lmRowOf && nLmRows < 1 && !idle)) {
+    return fail(FLTX_ERR_INVALID, "%s: bad argument (lm_row_stride %lld, lm_width = %d, n_lm_rows %d)", what,
+                (long long)lmRowStride, d->s2s.lmWidth, nLmRows);
+  }
+  Stream st = d->ctx->stream;
+  const size_t BK = (size_t)d->B * d->opt.beam_size;
+  const bool logits = lmKind == FLTX_S2S_LOGITS;
+  if (idle) { /* nothing to score */
+    if (logits && lmRowLse && devMemset(lmRowLse, 0xFF, 8 * BK, st)) { /* (all-ones: a NaN) */
+      return fail(FLTX_ERR_HIP, "%s: memset failed", what);
+    }
+    return FLTX_OK;
+  }
+  const size_t nLm = lmRowOf ? (size_t)nLmRows : BK;
+  if (!onDevice) {
+    const size_t lmElem = lmDtype == FLTX_DTYPE_F32 ? 4 : 2;
+    const size_t nE = (nLm - 1) * (size_t)lmRowStride + (size_t)d->s2s.lmWidth;
+    if (d->s2s.lmScores.ensure(lmElem * nE, st, false) || (lmRowOf && d->s2s.lmRowOf.ensure(4 * BK, st, false))) {
+      return fail(FLTX_ERR_OOM, "%s: staging allocation failed", what);
+    }
+    if (devCopyH2D(d->s2s.lmScores.p, lmScores, lmElem * nE, st) ||
+        (lmRowOf && devCopyH2D(d->s2s.lmRowOf.p, lmRowOf, 4 * BK, st))) {
+      return fail(FLTX_ERR_HIP, "%s: upload failed", what);
+    }
+    lmScores = d->s2s.lmScores.p;
+    lmRowOf = lmRowOf ? d->s2s.lmRowOf.as<int32_t>() : nullptr;
+  }
+  CrLmParams W;
+  memset(&W, 0, sizeof(W));
+  W.r.s = Q.s;
+  W.r.x = lmScores;
+  W.r.rowStride = lmRowStride;
+  W.r.width = d->s2s.lmWidth;
+  W.r.finishIdx = d->s2s.lmFinish;
+  W.r.usrToLm = d->lm->rowsMap ? d->lmDev->usrToLm.as<int32_t>() : nullptr;
+  W.r.recLm = d->s2s.recLm.as<float>();
+  W.r.rowLse = logits ? lmRowLse : nullptr;
+  W.T = Q.T;
+  W.frameOff = Q.frameOff;
+  W.lmRowOf = lmRowOf;
+  W.nLmRows = (int32_t)nLm;
+  W.fin = fin ? 1 : 0;
+  switch (lmDtype * 2 + (logits ? 1 : 0)) {
+    case 0: return crLmRowsLaunch<kS2sDtF32, false>((int)BK, st, W);
+    case 1: return crLmRowsLaunch<kS2sDtF32, true>((int)BK, st, W);
+    case 2: return crLmRowsLaunch<kS2sDtF16, false>((int)BK, st, W);
+    case 3: return crLmRowsLaunch<kS2sDtF16, true>((int)BK, st, W);
+    case 4: return crLmRowsLaunch<kS2sDtBf16, false>((int)BK, st, W);
+    default: return crLmRowsLaunch<kS2sDtBf16, true>((int)BK, st, W);
+  }
+}
+
+int fltx_ctc_rows_step(fltx_decoder* d, const void* lmScores, int32_t lmDtype, int32_t lmKind, int64_t lmRowStride,
+                       const int32_t* lmRowOf, int32_t nLmRows, int32_t onDevice, double* lmRowLse, int32_t* nextTok,
+                       int32_t* nextSrc, int32_t* nextState, int32_t* nRows) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = crCheck(d, "fltx_ctc_rows_step");
+  if (rc) {
+    return rc;
+  }
+  if (!d->s2s.begun) {
+    return fail(FLTX_ERR_STATE, "fltx_ctc_rows_step: fltx_ctc_rows_begin first");
+  }
+  if (!nextTok || !nextSrc || !nextState || !nRows) {
+    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_step: null output");
+  }
+  const bool last = d->s2s.t >= d->s2s.crMaxT; /* every utterance's frames are used up: the beams are listed again */
+  CrParams Q = crParams(d);
+  Q.s.outTok = nextTok;
+  Q.s.outSrc = nextSrc;
+  Q.s.outN = nRows;
+  Q.outState = nextState;
+  if ((rc = crLmRowsIn(d, "fltx_ctc_rows_step", false, last, lmScores, lmDtype, lmKind, lmRowStride, lmRowOf, nLmRows,
+                       onDevice, lmRowLse, Q))) {
+    return rc;
+  }
+  S2S_LAUNCH(fltx_ctc_rows_step_kernel, crStepUtterance<false>, d->B, kS2sStepThreads, sizeof(S2lStepLds),
+             d->ctx->stream, Q);
+  if (!last) {
+    ++d->s2s.t;
+  }
+  return FLTX_OK;
+}
+
+int fltx_ctc_rows_end(fltx_decoder* d, const void* lmScores, int32_t lmDtype, int32_t lmKind, int64_t lmRowStride,
+                      const int32_t* lmRowOf, int32_t nLmRows, int32_t onDevice, double* lmRowLse) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = crCheck(d, "fltx_ctc_rows_end");
+  if (rc) {
+    return rc;
+  }
+  if (!d->s2s.begun) {
+    return fail(FLTX_ERR_STATE, "fltx_ctc_rows_end: fltx_ctc_rows_begin first");
+  }
+  Stream st = d->ctx->stream;
+  const int B = d->B, K = d->opt.beam_size;
+  if (d->outScores.ensure(24 * (size_t)B * K, st, false) ||
+      d->tokens.ensure(4 * (size_t)std::max<int64_t>(d->histRecords, 1), st, false) ||
+      d->outN.ensure(4 * (size_t)B, st, false) || ensureUttRes(d, B, st) ||
+      d->histOffD.ensure(8 * ((size_t)B + 1), st, false)) {
+    return fail(FLTX_ERR_OOM, "CTC rows results: device allocation failed");
+  }
+  if (uploadHistOff(d, st)) {
+    return fail(FLTX_ERR_HIP, "CTC rows results: upload failed");
+  }
+  CrParams Q = crParams(d);
+  if ((rc = crLmRowsIn(d, "fltx_ctc_rows_end", true, false, lmScores, lmDtype, lmKind, lmRowStride, lmRowOf, nLmRows,
+                       onDevice, lmRowLse, Q))) {
+    return rc;
+  }
+  Q.histOff = d->histOffD.as<int64_t>();
+  Q.s.outScores = d->outScores.as<double>();
+  Q.s.tokens = d->tokens.as<int32_t>();
+  Q.s.outNHyp = d->outN.as<int32_t>();
+  Q.s.uttNBeam = d->uttNBeam.as<int32_t>();
+  Q.s.uttFrame = d->uttFrame.as<int32_t>();
+  Q.s.uttStatus = d->uttStatus.as<int32_t>();
+  S2S_LAUNCH(fltx_ctc_rows_end_kernel, crStepUtterance<true>, B, kS2sStepThreads, sizeof(S2lStepLds), st, Q);
   d->haveResults = true;
   d->ended = true;
   d->backtraced = true;

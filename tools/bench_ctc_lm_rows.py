@@ -1,0 +1,141 @@
+"""Lexicon-free CTC with a rows LM (fltx_ctc_rows_*): device time per frame step, next to the host-LM path.
+
+One JSON line per token set: B = 256 utterances of T = 200 frames, beam K = 50, lmWeight 0.7, random float32 log-softmax
+emissions in HBM.  Letters: N = 29, every token kept (Kt = 29); word pieces: N = 10 000, Kt = 50.  The LM is a synthetic
+device LM, a table lookup: `--ctx` rows of lm_width = N + 1 entries (the last one the finish entry), and the row of a
+hypothesis is a hash of its utterance and its next_state id -- one row per LM state, named through lm_row_of, which a
+few torch operations on the timed stream compute from the step's own output (they are part of the caller's recipe).
+Two legs on the same table: (a) bf16 log-probs, (b) bf16 logits (the step takes each named row's log-softmax itself).
+Times are device events on the decoder's stream around begin + T steps + end, after a warm-up, divided by T; `begin_ms`
+(the emissions' token beams, once per batch) is timed on its own as well.
+(c) the baseline: the same kind of LM served through the existing host-LM path (fltx_lm_host_create + fltx_decode_batch),
+a Python object whose states are memoised children and whose scores are rows of the same table on the host.  That path
+asks Python one question per distinct (state, token), so it runs at --host-B utterances (default 4) of the same
+emissions; its figure is wall time per frame of that smaller batch.
+The per-kernel split comes from a separate run under `rocprofv3 --kernel-trace --stats` (the program after `--`; --only
+keeps that run to one leg).
+
+    python tools/bench_ctc_lm_rows.py [--T 200] [--warmup 1] [--only a,b,c] [--sets letters,word_piece]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from text_amd import _capi  # noqa: E402
+from bench_lex_s2s import timed  # noqa: E402
+
+
+class TableLM:
+    """The host twin for the host-LM path: a state is a memoised child per token; its row is a hash of its id."""
+
+    class State:
+        __slots__ = ("kids", "row")
+
+        def __init__(self, row):
+            self.kids, self.row = {}, row
+
+    def __init__(self, table, n_ctx):
+        self.table, self.n_ctx, self.made = table, n_ctx, 0
+
+    def start(self, _nothing):
+        return self.State(0)
+
+    def _child(self, st, idx):
+        k = st.kids.get(idx)
+        if k is None:
+            self.made += 1
+            k = st.kids[idx] = self.State((self.made * 2654435761) % self.n_ctx)
+        return k
+
+    def score(self, st, idx):
+        return self._child(st, idx), float(self.table[st.row, idx])
+
+    def finish(self, st):
+        return self._child(st, -1), float(self.table[st.row, -1])
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=256)
+    ap.add_argument("--K", type=int, default=50)
+    ap.add_argument("--T", type=int, default=200)
+    ap.add_argument("--ctx", type=int, default=4096)
+    ap.add_argument("--host-B", type=int, default=4)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--only", default="a,b,c")
+    ap.add_argument("--sets", default="letters,word_piece")
+    a = ap.parse_args()
+    only = set(a.only.split(","))
+    torch.manual_seed(0)
+    stream = torch.cuda.Stream()  # (the default stream's handle is NULL: a context given NULL makes its own stream)
+    torch.cuda.set_stream(stream)
+    ctx = _capi.Context(stream=stream.cuda_stream)
+    B, K, T = a.B, a.K, a.T
+    for name, N, Kt in (("letters", 29, 29), ("word_piece", 10000, 50)):
+        if name not in a.sets.split(","):
+            continue
+        W = N + 1
+        em = torch.randn(B * T, N, device="cuda").log_softmax(-1).contiguous()
+        logits = (torch.randn(a.ctx, W, device="cuda") * 3).to(torch.bfloat16)
+        log_probs = torch.log_softmax(logits.float(), -1).to(torch.bfloat16)
+        Ts = np.full(B, T, np.int32)
+        utt = (torch.arange(B, device="cuda", dtype=torch.int64) * 97)[:, None]
+        lm = _capi.RowsLM(W, None, N)
+        opts = _capi.make_options(K, Kt, 25.0, 0.7)
+        ms, extra = {}, {}
+        for leg, rows, kind in (("a_bf16_log_probs", log_probs, "log_probs"), ("b_bf16_logits", logits, "logits")):
+            if leg[0] not in only:
+                continue
+            dec = _capi.CtcRowsBatchDecoder(ctx, opts, lm, 0, 1)
+
+            def row_of(state):  # one LM row per (utterance, state id); padding rows (-1) stay out of range
+                r = (state.to(torch.int64) * 2654435761 + utt) % a.ctx
+                return torch.where(state >= 0, r, torch.full_like(r, -1)).to(torch.int32)
+
+            def loop():
+                tok, src, state, n = dec.begin(None, Ts, N, device_ptr=em.data_ptr())
+                for _ in range(T):
+                    tok, src, state, n = dec.step(rows, lm_row_of=row_of(state), lm_kind=kind)
+                dec.end(rows, lm_row_of=row_of(state), lm_kind=kind)
+            for _ in range(a.warmup):
+                loop()
+            ms[leg] = timed(loop, stream) / T
+            begin_ms = timed(lambda: dec.begin(None, Ts, N, device_ptr=em.data_ptr()), stream)
+            loop()
+            hyps = dec.results(0)
+            extra[leg] = {"begin_ms": begin_ms, "hyps_utt0": len(hyps), "best_utt0": hyps[0].score}
+            dec.close()
+        if "c" in only:
+            hb = a.host_B
+            host = _capi.HostLM(TableLM(log_probs[:, :].float().cpu().numpy(), a.ctx))
+            ref = _capi.BatchDecoder(ctx, _capi.LEXFREE, opts, host, 0, 1)
+            e_host = em[:hb * T].cpu().numpy()
+            ref.decode_batch(e_host, Ts[:hb], N)  # warm-up
+            ref.count(0)
+            t0 = time.perf_counter()
+            ref.decode_batch(e_host, Ts[:hb], N)
+            ref.count(0)
+            ms["c_host_lm_path"] = (time.perf_counter() - t0) * 1e3 / T
+            extra["c_host_lm_path"] = {"B": hb, "lm_calls": host.calls, "hyps_utt0": ref.count(0)[0]}
+            ref.close()
+            host.close()
+        print(json.dumps({"config": {"name": name, "B": B, "K": K, "Kt": Kt, "N": N, "T": T, "lm_width": W,
+                                     "lm_table_rows": a.ctx, "lm_weight": 0.7},
+                          "ms_per_frame_step": ms, "search": extra,
+                          "bytes": {"emissions_f32": B * T * N * 4, "lm_bf16_table": a.ctx * W * 2}}), flush=True)
+        lm.close()
+        del em, logits, log_probs
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
