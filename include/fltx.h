@@ -46,7 +46,7 @@ enum { FLTX_CRITERION_ASG = 0, FLTX_CRITERION_CTC = 1, FLTX_CRITERION_S2S = 2 };
 /* SmearingMode, decoder/Trie.h:21-25. */
 enum { FLTX_SMEAR_NONE = 0, FLTX_SMEAR_MAX = 1, FLTX_SMEAR_LOGADD = 2 };
 enum { FLTX_DECODER_LEXFREE = 0, FLTX_DECODER_LEXICON = 1, FLTX_DECODER_S2S_LEXFREE = 2, FLTX_DECODER_S2S_LEXICON = 3,
-       FLTX_DECODER_CTC_ROWS = 4 };
+       FLTX_DECODER_CTC_ROWS = 4, FLTX_DECODER_LEX_CTC_ROWS = 5 };
 
 /* LexiconDecoderOptions (decoder/LexiconDecoder.h:21-31); the lexicon-free
  * decoder (decoder/LexiconFreeDecoder.h:20-28) ignores word_score/unk_score. */
@@ -307,10 +307,11 @@ FLTX_API int fltx_s2s_step_typed(fltx_decoder* dec, const void* scores, int32_t 
  * entry must lie in [0, lm_width) when lm_width > 0, else FLTX_ERR_INVALID.  finish_index: the LM index LM::finish reads
  * (ConvLM.cpp:140-141: the LM's </s>); -1: usr_to_lm[eos] of the decoder.  The LM's per-hypothesis state is the
  * caller's, carried by index_select(next_src_row) as the model's is.
- * Three decoders take such an LM: fltx_s2s_decoder_create (every hypothesis has its own prefix and so its own state: no
+ * Four decoders take such an LM: fltx_s2s_decoder_create (every hypothesis has its own prefix and so its own state: no
  * merges), fltx_s2s_lex_decoder_create with is_lm_token != 0 (a word-piece LM under a lexicon: hypotheses that
- * segment one token string differently share a state and merge, see there) and fltx_ctc_rows_decoder_create (CTC
- * emissions, one LM row per LM state; finish_index must be given there).  The other decoders (fltx_decoder_create among
+ * segment one token string differently share a state and merge, see there), fltx_ctc_rows_decoder_create (CTC
+ * emissions, one LM row per LM state; finish_index must be given there) and fltx_ctc_rows_lex_decoder_create with
+ * is_lm_token != 0 (CTC emissions under a lexicon; finish_index likewise).  The other decoders (fltx_decoder_create among
  * them), a lexicon seq2seq
  * decoder with is_lm_token == 0 (word-level rows come in by fltx_lm_word_rows_create below), fltx_group_create and the
  * fltx_lm_* state functions return FLTX_ERR_UNSUPPORTED.
@@ -356,8 +357,10 @@ FLTX_API int fltx_s2s_step_lm_rows(fltx_decoder* dec,
  * LM, the smeared trie standing in for the LM inside a word.  lm_width (required, 0 < lm_width <= 4 194 304 = 2^22;
  * FLTX_ERR_UNSUPPORTED beyond): entries per LM row; every row offset is formed in 64 bits.  word_to_lm (may be NULL:
  * identity, n_words ignored): the LM index of the lexicon's word id w (a trie label).  finish_index (required, >= 0:
- * eos is a token and has no word id): the LM index LM::finish reads.  Only fltx_s2s_lex_decoder_create with
- * is_lm_token == 0 takes such an LM; that decoder with is_lm_token != 0, fltx_s2s_decoder_create, fltx_decoder_create,
+ * eos is a token and has no word id): the LM index LM::finish reads.  Only fltx_s2s_lex_decoder_create and
+ * fltx_ctc_rows_lex_decoder_create (CTC emissions, the same checks at its create; there unk needs a map entry too when
+ * unk_score > -inf), both with is_lm_token == 0, take such an LM; those decoders with is_lm_token != 0,
+ * fltx_s2s_decoder_create, fltx_ctc_rows_decoder_create, fltx_decoder_create,
  * fltx_group_create and the fltx_lm_* state functions return FLTX_ERR_UNSUPPORTED ("rows LM").  The trie is known at
  * fltx_s2s_lex_decoder_create, which returns FLTX_ERR_INVALID when a label w of the trie has no entry in a given map
  * (w >= n_words) or an LM index outside [0, lm_width), or when finish_index lies outside [0, lm_width).
@@ -512,6 +515,47 @@ FLTX_API int fltx_ctc_rows_step(fltx_decoder* dec, const void* lm_scores, int32_
 FLTX_API int fltx_ctc_rows_end(fltx_decoder* dec, const void* lm_scores, int32_t lm_dtype, int32_t lm_kind,
                                int64_t lm_row_stride, const int32_t* lm_row_of, int32_t n_lm_rows, int32_t on_device,
                                double* lm_row_lse);
+
+/* ---- lexicon CTC with a rows LM: LexiconDecoder as a batched device step per frame -------------------------------- */
+/* LexiconDecoder(opt, lexicon, lm, sil, blank, unk, {}, isLmToken) (decoder/LexiconDecoder.h:117-133, .cpp:21-274) for B
+ * utterances at once with a neural LM in shallow fusion: CTC emissions, spellings constrained by `trie` (a host trie,
+ * already smeared; copied into the compact device layout of fltx_s2s_lex_decoder_create, so it may be destroyed
+ * afterwards), and `lm` a word-level rows LM (fltx_lm_word_rows_create) when is_lm_token == 0 or a token-level one
+ * (fltx_lm_rows_create) when is_lm_token != 0; the crossed pairs and every other LM: FLTX_ERR_UNSUPPORTED, as the ASG
+ * criterion.  finish_index >= 0 is required for both (FLTX_ERR_INVALID).  unk_score > -inf needs unk >= 0, the unknown
+ * word's id (FLTX_ERR_INVALID otherwise, either LM).  Word LM: FLTX_ERR_INVALID when a label of the
+ * trie, or unk when opt->unk_score > -inf, has no entry in word_to_lm or an LM index outside [0, lm_width), or when
+ * finish_index lies outside; token LM: the map is checked against N at fltx_ctc_rows_begin.  A decoder kind of its own
+ * (FLTX_DECODER_LEX_CTC_ROWS), refused where FLTX_DECODER_CTC_ROWS is: fltx_decoder_create, fltx_group_create
+ * (FLTX_ERR_UNSUPPORTED), fltx_decode_batch, fltx_stream_*, fltx_s2s_* (FLTX_ERR_STATE).  Limits and the state table
+ * (fltx_decoder_set(dec, "max_states", n)) are fltx_ctc_rows_decoder_create's; lm_width <= 2^22 for the word LM.
+ *
+ * The decoder is stepped with fltx_ctc_rows_begin / step / end; next_state, next_src_row, n_rows, lm_row_of, n_lm_rows,
+ * lm_row_lse, typed rows, host staging and the idle steps keep their contract.  next_token is the LM EDGE that made the
+ * row's state from the state of row next_src_row: the word id that ended in this frame (word LM, unk included), the token
+ * (token LM), -1 where the state is the parent's, -1 for the root at begin.  A DEVICE emissions buffer is read by every
+ * step (below): it must stay valid and unchanged until fltx_ctc_rows_end has been queued.
+ * Per frame, hypothesis h (trie node, last token, prevBlank) and kept token n with a child c of h's node:
+ * s = h.score + e[n] (+ sil_score when n == sil), lexMax = 0 at the root, else maxScore[node];
+ *   move      when (h.prevBlank or n != h.token) and c has children: word LM lm = maxScore[c] - lexMax (float; no row is
+ *             read; the state stays), token LM lm = the entry at usr_to_lm[n] of h's row (state child(state, n));
+ *             score = s + lm_weight * lm; node c;
+ *   word end  per label w of c (not when h is at the root and n == h.token): word LM lm = entry(word_to_lm[w]) - lexMax
+ *             (float), state child(state, w); token LM the move's entry and state; score = (s + lm_weight * lm) +
+ *             word_score; the root, word w;
+ *   unknown   when c has no labels and unk_score > -inf: as the word end with unk for w and unk_score.
+ * Two more candidates read their emission from the frame itself, not from the token beam: the same node (when not
+ * h.prevBlank, or at the root; token sil at the root, else h.token; + sil_score for sil) and blank (prevBlank = 1); state,
+ * node and lmScore stay.  Then the threshold, the merge of candidates equal in (LM state, trie node, token, prevBlank)
+ * (max / logAdd, the best member's fields survive) and the beam_size best.  NaN and -inf behave as in fltx_ctc_rows_step;
+ * an out-of-range lm_row_of entry makes the row's LM entries NaN: it keeps the same-node and blank candidates and, under
+ * the word LM, its moves.
+ * fltx_ctc_rows_end: if any hypothesis sits at the root only those finish, else all; lm = the entry at finish_index,
+ * score = h.score + lm_weight * lm, the state child(state, -1), the token sil.  fltx_result_* return tokens and WORDS in
+ * the layout of the lexicon fltx_decode_batch: T[b] + 2 entries per hypothesis, the word where it ended, -1 elsewhere. */
+FLTX_API int fltx_ctc_rows_lex_decoder_create(fltx_ctx* ctx, const fltx_options* opt, const fltx_htrie* trie,
+                                              const fltx_lm* lm, int32_t sil, int32_t blank, int32_t unk,
+                                              int32_t is_lm_token, fltx_decoder** out);
 
 /* ---- results (getAllFinalHypothesis / getBestHypothesis) ------------------ */
 /* Number of hypotheses of utterance b and the length (finalFrame + 1) of each

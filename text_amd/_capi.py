@@ -14,7 +14,7 @@ DEFAULT_LIB = os.path.join(_HERE, "lib", "libfltx.so")
 
 FLTX_OK, ERR_INVALID, ERR_HIP, ERR_OOM, ERR_UNSUPPORTED, ERR_RANGE, ERR_STATE = range(7)
 CRITERION = {"asg": 0, "ctc": 1, "s2s": 2}
-LEXFREE, LEXICON, S2S_LEXFREE, S2S_LEXICON, CTC_ROWS = 0, 1, 2, 3, 4
+LEXFREE, LEXICON, S2S_LEXFREE, S2S_LEXICON, CTC_ROWS, LEX_CTC_ROWS = 0, 1, 2, 3, 4, 5
 # fltx_decoder_get "why_not_lane" (include/fltx.h FLTX_WHY_*)
 (FLTX_WHY_TOKENS, FLTX_WHY_BEAM, FLTX_WHY_STREAM, FLTX_WHY_LM, FLTX_WHY_LOGADD, FLTX_WHY_ASG, FLTX_WHY_UNK,
  FLTX_WHY_TRIE_SHAPE, FLTX_WHY_WORD_END, FLTX_WHY_OPTIONS, FLTX_WHY_LENGTH, FLTX_WHY_SWITCHED_OFF,
@@ -93,7 +93,7 @@ class Lib:
         "fltx_s2s_end", "fltx_s2s_lex_decoder_create", "fltx_s2s_lex_set_max_states", "fltx_s2s_lex_info",
         "fltx_lm_rows_create", "fltx_s2s_step_lm_rows",
         "fltx_lm_word_rows_create", "fltx_s2s_step_word_lm_rows",
-        "fltx_ctc_rows_decoder_create", "fltx_ctc_rows_begin", "fltx_ctc_rows_step", "fltx_ctc_rows_end",
+        "fltx_ctc_rows_decoder_create", "fltx_ctc_rows_lex_decoder_create", "fltx_ctc_rows_begin", "fltx_ctc_rows_step", "fltx_ctc_rows_end",
     ]
 
     def __init__(self, path=None):
@@ -178,6 +178,7 @@ class Lib:
             "fltx_s2s_lex_set_max_states": [vp, i32],
             "fltx_s2s_lex_info": [vp, vp, vp, vp, vp],
             "fltx_ctc_rows_decoder_create": [vp, C.POINTER(Options), vp, i32, i32, pvp],
+            "fltx_ctc_rows_lex_decoder_create": [vp, C.POINTER(Options), vp, vp, i32, i32, i32, i32, pvp],
             "fltx_ctc_rows_begin": [vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp],
             "fltx_ctc_rows_step": [vp, vp, i32, i32, i64, vp, i32, i32, vp, vp, vp, vp, vp],
             "fltx_ctc_rows_end": [vp, vp, i32, i32, i64, vp, i32, i32, vp],
@@ -1134,18 +1135,29 @@ class CtcRowsBatchDecoder(BatchDecoder):
     _lse_ptr = Seq2SeqBatchDecoder._lse_ptr
 
     def __init__(self, ctx, options, rows_lm, sil, blank):
-        self.ctx, self.L = ctx, ctx.L
-        self.kind, self.options = CTC_ROWS, options
-        self._keep = (rows_lm, None)
-        self.sil, self.blank = int(sil), int(blank)
+        self._init(ctx, CTC_ROWS, options, rows_lm, None, sil, blank)
         h = C.c_void_p()
         self.L.check(self.L.lib.fltx_ctc_rows_decoder_create(ctx.h, C.byref(options), rows_lm.h, int(sil), int(blank),
                                                              C.byref(h)))
+        self._made(h)
+
+    def _init(self, ctx, kind, options, lm, trie, sil, blank):
+        self.ctx, self.L = ctx, ctx.L
+        self.kind, self.options = kind, options
+        self._keep = (lm, trie)
+        self.sil, self.blank = int(sil), int(blank)
+
+    def _made(self, h):
         self.h = h
         self.B = 0
         self.N = None
         self._emu = "emulation" in self.L.version()
         _live["dec"].add(self)
+
+    @staticmethod
+    def _state_key(b, prefix, parent_id, edge, state_id):
+        """what decode() hands lm_rows for a state it has not seen"""
+        return (b, prefix)
 
     def set_max_states(self, n):
         """LM states per utterance from the next begin() on (default 65 536)"""
@@ -1244,9 +1256,10 @@ class CtcRowsBatchDecoder(BatchDecoder):
                     key = (b, int(st_h[b, k]))
                     if key not in row_of:
                         s = int(src_h[b, k])
-                        prefix[key] = () if s < 0 else prefix[(b, int(prev_state.reshape(-1)[s]))] + (int(tok_h[b, k]),)
+                        par = -1 if s < 0 else int(prev_state.reshape(-1)[s])
+                        prefix[key] = () if s < 0 else prefix[(b, par)] + (int(tok_h[b, k]),)
                         row_of[key] = n_store + len(keys)
-                        keys.append((b, prefix[key]))
+                        keys.append(self._state_key(b, prefix[key], par, int(tok_h[b, k]) if s >= 0 else -1, key[1]))
                     ro[b * K + k] = row_of[key]
             if keys:
                 rows = lm_rows(keys)
@@ -1269,6 +1282,34 @@ class CtcRowsBatchDecoder(BatchDecoder):
             else:
                 self.end(store[:n_store], lm_row_of=ro_in, lm_kind=lm_kind)
         return self.results_batch()
+
+
+class LexiconCtcRowsBatchDecoder(CtcRowsBatchDecoder):
+    """fltx_ctc_rows_lex_decoder_create: LexiconDecoder (CTC) for B utterances at once with a neural LM in shallow
+    fusion, stepped by CtcRowsBatchDecoder's begin / step / end / set_max_states and row contract.  `host_trie` is a
+    HostTrie (already smeared); `lm` a WordRowsLM (is_lm_token=False: an LM over the lexicon's words) or a RowsLM
+    (is_lm_token=True: an LM over the tokens), either with a finish_index >= 0; `options` are make_options(...)'s with
+    the CTC criterion, word_score and unk_score included (unk_score > -inf needs `unk`).  The `token` a row lists is the
+    LM EDGE that made its state from the state of row src_row: the word that ended in this frame (word LM), the token
+    (token LM), -1 where the state is the parent's (and for the root).  The results carry words.
+
+    decode(emissions, T, N, lm_rows, ...): lm_rows(state_keys) gets one (b, prefix, parent_id, edge, state_id) per LM
+    state the search has just entered -- prefix the tuple of edges (words or tokens) since the start, parent_id the
+    next_state id of the state it was made from (-1: LM::start) and edge what advanced it -- so an LM that caches its
+    hidden state per id advances parent_id's by edge; it is asked once per state id."""
+
+    def __init__(self, ctx, options, host_trie, lm, sil, blank, unk=-1, is_lm_token=False):
+        self._init(ctx, LEX_CTC_ROWS, options, lm, host_trie, sil, blank)
+        self.unk, self.is_lm_token = int(unk), bool(is_lm_token)
+        h = C.c_void_p()
+        self.L.check(self.L.lib.fltx_ctc_rows_lex_decoder_create(ctx.h, C.byref(options), host_trie.h, lm.h, int(sil),
+                                                                 int(blank), int(unk), int(bool(is_lm_token)),
+                                                                 C.byref(h)))
+        self._made(h)
+
+    @staticmethod
+    def _state_key(b, prefix, parent_id, edge, state_id):
+        return (b, prefix, parent_id, edge, state_id)
 
 
 def _to_device_i32(a, device):

@@ -32,6 +32,7 @@
 #include "fltx_s2s.h"
 #include "fltx_s2s_lex.h"
 #include "fltx_ctc_rows.h"
+#include "fltx_ctc_rows_lex.h"
 
 using namespace fltx;
 
@@ -222,6 +223,26 @@ __global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_end_kernel(CrPa
 }
 __global__ void __launch_bounds__(kS2sBeginThreads) fltx_ctc_rows_begin_kernel(CrParams Q) {
   crBeginUtterance(Q, nullptr);
+}
+/* fltx_ctc_rows_lex.h: lexicon CTC with a rows LM -- the word-level gather, the frame step and its finish variant per LM
+ * level (SRC), the start; the token beams and the token-level gather are the kernels above */
+template <int DT, bool LOGITS>
+__global__ void __launch_bounds__(kS2sLmThreads) fltx_ctc_rows_lex_word_lm_kernel(CrlWordLmParams W) {
+  __shared__ __attribute__((aligned(16))) S2sLmRowsLds fltx_crl_lm_lds;
+  crlWordLmRows<DT, LOGITS>(W, (char*)&fltx_crl_lm_lds);
+}
+template <int SRC>
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_lex_step_kernel(CrlParams R) {
+  __shared__ __attribute__((aligned(16))) CrlStepLds fltx_crl_step_lds;
+  crlStepUtterance<SRC, false>(R, (char*)&fltx_crl_step_lds);
+}
+template <int SRC>
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_lex_end_kernel(CrlParams R) {
+  __shared__ __attribute__((aligned(16))) CrlStepLds fltx_crl_end_lds;
+  crlStepUtterance<SRC, true>(R, (char*)&fltx_crl_end_lds);
+}
+__global__ void __launch_bounds__(kS2sBeginThreads) fltx_ctc_rows_lex_begin_kernel(CrlParams R) {
+  crlBeginUtterance(R, nullptr);
 }
 __global__ void __launch_bounds__(1024) fltx_streamop_kernel(StreamOpParams Q) {
   __shared__ int32_t sh[kStreamOpLds / 4];
@@ -747,17 +768,23 @@ struct fltx_decoder {
     DBuf crMeta, crEmis;
     std::vector<int64_t> crMetaHost;
     const float* crEmisDev = nullptr;
+    /* lexicon CTC with a rows LM (kind FLTX_DECODER_LEX_CTC_ROWS, fltx_ctc_rows_lex.h; the compact trie, slots = S,
+     * isLmToken and rowNode above are its too): the publisher's beam index, which is nobody's output */
+    DBuf crOutBeam;
   } s2s;
 };
 
 static bool isS2sKind(int kind) { return kind == FLTX_DECODER_S2S_LEXFREE || kind == FLTX_DECODER_S2S_LEXICON; }
+static bool isCrKind(int kind) { return kind == FLTX_DECODER_CTC_ROWS || kind == FLTX_DECODER_LEX_CTC_ROWS; }
 /* decoders that are stepped by their own entry points (fltx_s2s_*, fltx_ctc_rows_*): no batch call, no streams */
 static const char* stepKindCalls(int kind) {
   return isS2sKind(kind) ? "a seq2seq decoder steps with fltx_s2s_step"
-                         : kind == FLTX_DECODER_CTC_ROWS ? "a CTC rows decoder steps with fltx_ctc_rows_step" : nullptr;
+                         : isCrKind(kind) ? "a CTC rows decoder steps with fltx_ctc_rows_step" : nullptr;
 }
 /* decoders whose results carry words */
-static bool kindHasWords(int kind) { return kind == FLTX_DECODER_LEXICON || kind == FLTX_DECODER_S2S_LEXICON; }
+static bool kindHasWords(int kind) {
+  return kind == FLTX_DECODER_LEXICON || kind == FLTX_DECODER_S2S_LEXICON || kind == FLTX_DECODER_LEX_CTC_ROWS;
+}
 
 /* ------------------------------------------------------------------------ */
 extern "C" {
@@ -1705,12 +1732,15 @@ int fltx_decoder_create(fltx_ctx* ctx, int32_t kind, const fltx_options* opt, co
   if (kind == FLTX_DECODER_CTC_ROWS) { /* (fltx_group_create comes through here too) */
     return fail(FLTX_ERR_UNSUPPORTED, "a CTC rows decoder is made with fltx_ctc_rows_decoder_create (no groups)");
   }
+  if (kind == FLTX_DECODER_LEX_CTC_ROWS) {
+    return fail(FLTX_ERR_UNSUPPORTED, "a lexicon CTC rows decoder is made with fltx_ctc_rows_lex_decoder_create (no groups)");
+  }
   if (kind != FLTX_DECODER_LEXFREE && kind != FLTX_DECODER_LEXICON) {
     return fail(FLTX_ERR_INVALID, "unknown decoder kind %d", kind);
   }
   if (lm->kind == 3 || lm->kind == 4) {
     return fail(FLTX_ERR_UNSUPPORTED, "a rows LM (fltx_lm_rows_create, fltx_lm_word_rows_create) serves the seq2seq "
-                                      "decoders and fltx_ctc_rows_decoder_create only");
+                                      "decoders, fltx_ctc_rows_decoder_create and fltx_ctc_rows_lex_decoder_create only");
   }
   if (kind == FLTX_DECODER_LEXICON && !trie) {
     return fail(FLTX_ERR_INVALID, "lexicon decoder needs a trie");
@@ -1896,8 +1926,9 @@ int fltx_decoder_set(fltx_decoder* d, const char* key, int64_t value) {
     return FLTX_OK;
   }
   if (!strcmp(key, "max_states")) { /* a CTC rows decoder: LM states per utterance from the next fltx_ctc_rows_begin on */
-    if (d->kind != FLTX_DECODER_CTC_ROWS || value < 1 || value > 0x7FFFFFFF) {
-      return fail(FLTX_ERR_INVALID, "max_states: a CTC rows decoder (fltx_ctc_rows_decoder_create) and a count >= 1");
+    if (!isCrKind(d->kind) || value < 1 || value > 0x7FFFFFFF) {
+      return fail(FLTX_ERR_INVALID, "max_states: a CTC rows decoder (fltx_ctc_rows_decoder_create, "
+                                    "fltx_ctc_rows_lex_decoder_create) and a count >= 1");
     }
     d->s2s.maxStates = (int)value;
     return FLTX_OK;
@@ -5946,8 +5977,9 @@ static int crCheck(fltx_decoder* d, const char* what) {
   if (!d) {
     return fail(FLTX_ERR_INVALID, "%s: null decoder", what);
   }
-  if (d->kind != FLTX_DECODER_CTC_ROWS) {
-    return fail(FLTX_ERR_STATE, "%s: not a CTC rows decoder (fltx_ctc_rows_decoder_create)", what);
+  if (!isCrKind(d->kind)) {
+    return fail(FLTX_ERR_STATE, "%s: not a CTC rows decoder (fltx_ctc_rows_decoder_create, "
+                                "fltx_ctc_rows_lex_decoder_create)", what);
   }
   return FLTX_OK;
 }
@@ -5978,6 +6010,10 @@ static CrParams crParams(fltx_decoder* d) {
   P.cKey = d->s2s.cKey.as<unsigned long long>();
   P.nC = (int64_t)P.K * P.cap;
   P.outBeam = d->s2s.rowNode.as<int32_t>(); /* (the publisher's beam index: src_row - b*K here, nobody's output) */
+  if (d->kind == FLTX_DECODER_LEX_CTC_ROWS) { /* (rowNode is the word gather's there) */
+    P.nC = (int64_t)P.K * ((int64_t)P.cap * (1 + d->s2s.slots) + 2);
+    P.outBeam = d->s2s.crOutBeam.as<int32_t>();
+  }
   Q.sil = d->sil;
   Q.blank = d->blank;
   Q.logAdd = d->opt.log_add ? 1 : 0;
@@ -6004,6 +6040,104 @@ static CrParams crParams(fltx_decoder* d) {
   Q.merges = d->s2s.merges.as<int32_t>();
   Q.recLm = d->s2s.recLm.as<float>();
   return Q;
+}
+
+/* the lexicon kind's parameters around those (fltx_ctc_rows_lex.h) */
+static CrlParams crlParams(fltx_decoder* d, const CrParams& Q) {
+  CrlParams R;
+  memset(&R, 0, sizeof(R));
+  R.c = Q;
+  R.trie.maxScore = d->s2s.trieMax.as<float>();
+  R.trie.kidOff = d->s2s.kidOff.as<int32_t>();
+  R.trie.kidTok = d->s2s.kidTok.as<int32_t>();
+  R.trie.kidNode = d->s2s.kidNode.as<int32_t>();
+  R.trie.labOff = d->s2s.labOff.as<int32_t>();
+  R.trie.labels = d->s2s.lab.as<int32_t>();
+  R.S = d->s2s.slots;
+  R.unk = d->opt.unk_score > -std::numeric_limits<double>::infinity() ? d->unk : -1;
+  R.lmStride = d->s2s.isLmToken ? d->s2s.cap : d->s2s.cap * d->s2s.slots;
+  R.wordScore = d->opt.word_score;
+  R.unkScore = d->opt.unk_score;
+  R.beam = d->s2s.beam.as<CrlHyp>();
+  R.hist = d->s2s.hist.as<S2lRec>();
+  R.rowNode = d->s2s.rowNode.as<int32_t>();
+  R.words = d->words.as<int32_t>();
+  return R;
+}
+
+int fltx_ctc_rows_lex_decoder_create(fltx_ctx* ctx, const fltx_options* opt, const fltx_htrie* trie, const fltx_lm* lm,
+                                     int32_t sil, int32_t blank, int32_t unk, int32_t isLmToken, fltx_decoder** out) {
+  if (!ctx || !opt || !trie || !lm || !out) {
+    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_lex_decoder_create: null argument");
+  }
+  if (lm->kind != (isLmToken ? 3 : 4)) {
+    return fail(FLTX_ERR_UNSUPPORTED, "fltx_ctc_rows_lex_decoder_create: a word-level rows LM (fltx_lm_word_rows_create) "
+                                      "with is_lm_token == 0, a token-level one (fltx_lm_rows_create) with is_lm_token "
+                                      "!= 0; other LMs decode with fltx_decoder_create");
+  }
+  if (opt->criterion != FLTX_CRITERION_CTC) {
+    return fail(FLTX_ERR_UNSUPPORTED, "fltx_ctc_rows_lex_decoder_create: criterion %d not supported (CTC only)",
+                opt->criterion);
+  }
+  if (opt->beam_size < 1 || opt->beam_size_token < 1 || sil < 0 || blank < 0) {
+    return fail(FLTX_ERR_INVALID, "beam_size and beam_size_token must be >= 1, sil and blank >= 0");
+  }
+  if (opt->beam_size > kS2sMaxBeam) {
+    return fail(FLTX_ERR_UNSUPPORTED, "lexicon CTC rows: beam_size %d > %d", opt->beam_size, kS2sMaxBeam);
+  }
+  if (lm->rowsFinish < 0) { /* (CTC has no eos token whose entry finish could fall back to) */
+    return fail(FLTX_ERR_INVALID, "lexicon CTC rows: the LM needs a finish_index >= 0");
+  }
+  if (opt->unk_score > -std::numeric_limits<double>::infinity() && unk < 0) { /* (the unknown word's id is listed and stored) */
+    return fail(FLTX_ERR_INVALID, "lexicon CTC rows: unk_score > -inf needs an unk word id >= 0 (unk = %d)", unk);
+  }
+  DeviceScope devScope(ctx);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  fltx_lm::Dev* lmDev = nullptr;
+  int rc = lmEnsureUploaded(const_cast<fltx_lm*>(lm), ctx, &lmDev);
+  if (rc) {
+    return rc;
+  }
+  std::unique_ptr<fltx_decoder> d(new fltx_decoder());
+  d->ctx = ctx;
+  d->lm = lm;
+  d->lmDev = lmDev;
+  d->kind = FLTX_DECODER_LEX_CTC_ROWS;
+  d->opt = *opt;
+  d->sil = sil;
+  d->blank = blank;
+  d->unk = unk;
+  d->isLmToken = isLmToken ? 1 : 0;
+  d->s2s.isLmToken = isLmToken != 0;
+  d->s2s.maxStates = kS2lDefaultStates;
+  std::vector<int32_t> labels;
+  if ((rc = s2lUploadTrie(d.get(), const_cast<fltx_htrie*>(trie), &labels))) {
+    return rc;
+  }
+  if (lm->kind == 4) { /* every index the word gather can form lies inside the LM's rows */
+    const int width = lm->rowsWidth;
+    if (lm->rowsFinish >= width) {
+      return fail(FLTX_ERR_INVALID, "lexicon CTC rows: finish index %d outside the LM's rows of %d", lm->rowsFinish, width);
+    }
+    if (opt->unk_score > -std::numeric_limits<double>::infinity()) {
+      labels.push_back(unk);
+    }
+    for (int32_t w : labels) {
+      if (w < 0 || (lm->rowsMap && w >= lm->nUsr)) {
+        return fail(FLTX_ERR_INVALID, "lexicon CTC rows: word %d (a label of the trie, or unk) outside the %d entries of "
+                                      "word_to_lm", w, lm->nUsr);
+      }
+      const int32_t idx = lm->rowsMap ? lm->hUsr[(size_t)w] : w;
+      if (idx < 0 || idx >= width) {
+        return fail(FLTX_ERR_INVALID, "lexicon CTC rows: word %d has LM index %d outside the LM's rows of %d", w, idx, width);
+      }
+    }
+  }
+  d->s2s.slots = std::max(1, d->s2s.maxLabels);
+  *out = d.release();
+  return FLTX_OK;
 }
 
 int fltx_ctc_rows_decoder_create(fltx_ctx* ctx, const fltx_options* opt, const fltx_lm* lm, int32_t sil, int32_t blank,
@@ -6074,7 +6208,10 @@ int fltx_ctc_rows_begin(fltx_decoder* d, const float* emissions, int32_t onDevic
   /* the LM's map and finish index against rows of this width (s2sPlanRowsLm's checks with N for V; CTC has no eos token
    * whose entry finish could fall back to) */
   d->s2s.eos = N;
-  if ((rc = s2sPlanRowsLm(d, N)) || (rc = s2sRowsLmFinishCheck(d->lm->rowsFinish, d->s2s.lmWidth))) {
+  const bool lex = d->kind == FLTX_DECODER_LEX_CTC_ROWS;
+  if (lex && d->lm->kind == 4) { /* (word ids, not tokens: checked against the trie's labels at create) */
+    d->s2s.lmWidth = d->lm->rowsWidth;
+  } else if ((rc = s2sPlanRowsLm(d, N)) || (rc = s2sRowsLmFinishCheck(d->lm->rowsFinish, d->s2s.lmWidth))) {
     return rc;
   }
   d->s2s.lmFinish = d->lm->rowsFinish;
@@ -6104,19 +6241,26 @@ int fltx_ctc_rows_begin(fltx_decoder* d, const float* emissions, int32_t onDevic
   if (frames > 0 && !emissions) {
     return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_begin: null emissions");
   }
-  const int64_t nC = (int64_t)K * cap;
+  const int64_t nC = lex ? (int64_t)K * ((int64_t)cap * (1 + d->s2s.slots) + 2) : (int64_t)K * cap;
+  if (nC > (int64_t)1 << 29) { /* (the merge table holds the next power of two >= 2 nC slots, an int32 count) */
+    return fail(FLTX_ERR_UNSUPPORTED, "%s: %lld candidates per frame", lex ? "lexicon CTC rows" : "CTC rows",
+                (long long)nC);
+  }
+  const size_t hypBytes = lex ? sizeof(CrlHyp) : sizeof(CrHyp), recBytes = lex ? sizeof(S2lRec) : sizeof(int2);
+  const size_t lmPerRow = (size_t)cap * (lex && !d->s2s.isLmToken ? d->s2s.slots : 1);
   d->s2s.cap = cap;
   d->s2s.mSize = s2lPow2AtLeast(2 * nC);
   d->s2s.sMax = (int)std::min<int64_t>((int64_t)K * maxT + 2, d->s2s.maxStates);
   d->s2s.sSize = s2lPow2AtLeast(2 * (int64_t)d->s2s.sMax);
   Stream st = d->ctx->stream;
   const size_t BK = (size_t)B * K, BC = (size_t)B * (size_t)nC, nF = (size_t)std::max<int64_t>(frames, 1);
-  if (d->s2s.beam.ensure(2 * BK * sizeof(CrHyp), st, false) || d->s2s.beamN.ensure(8 * (size_t)B, st, false) ||
-      d->s2s.hist.ensure((size_t)(maxT + 2) * BK * sizeof(int2), st, false) ||
+  if (d->s2s.beam.ensure(2 * BK * hypBytes, st, false) || d->s2s.beamN.ensure(8 * (size_t)B, st, false) ||
+      d->s2s.hist.ensure((size_t)(maxT + 2) * BK * recBytes, st, false) ||
+      (lex && d->s2s.crOutBeam.ensure(4 * BK, st, false)) ||
       d->s2s.rowsInt.ensure(4 * (size_t)B, st, false) || d->s2s.done.ensure(4 * (size_t)B, st, false) ||
       d->s2s.finalStep.ensure(4 * (size_t)B, st, false) || d->s2s.recTok.ensure(4 * nF * cap, st, false) ||
       d->s2s.recAm.ensure(4 * nF * cap, st, false) || d->s2s.recN.ensure(4 * nF, st, false) ||
-      d->s2s.cKey.ensure(8 * BC, st, false) || d->s2s.recLm.ensure(4 * BK * cap, st, false) ||
+      d->s2s.cKey.ensure(8 * BC, st, false) || d->s2s.recLm.ensure(4 * BK * lmPerRow, st, false) ||
       d->s2s.rowNode.ensure(4 * BK, st, false) || d->s2s.cScore.ensure(8 * BC, st, false) ||
       d->s2s.cMk.ensure(16 * BC, st, false) || d->s2s.cGrp.ensure(4 * BC, st, false) ||
       d->s2s.cList.ensure(4 * BC, st, false) || d->s2s.cNext.ensure(4 * BC, st, false) ||
@@ -6170,6 +6314,12 @@ int fltx_ctc_rows_begin(fltx_decoder* d, const float* emissions, int32_t onDevic
   if (frames > 0) {
     S2S_LAUNCH(fltx_ctc_rows_tokbeam_kernel, crTokBeamRows, (int)((frames + 3) / 4), 256, 4 * sizeof(S2sFrontLds), st, Q);
   }
+  if (lex) {
+    const CrlParams R = crlParams(d, Q);
+    S2S_LAUNCH(fltx_ctc_rows_lex_begin_kernel, crlBeginUtterance, (B + kS2sBeginThreads - 1) / kS2sBeginThreads,
+               kS2sBeginThreads, 0, st, R);
+    return FLTX_OK;
+  }
   S2S_LAUNCH(fltx_ctc_rows_begin_kernel, crBeginUtterance, (B + kS2sBeginThreads - 1) / kS2sBeginThreads,
              kS2sBeginThreads, 0, st, Q);
   return FLTX_OK;
@@ -6180,6 +6330,15 @@ template <int DT, bool LOGITS>
 static int crLmRowsLaunch(int nRows, Stream st, const CrLmParams& W) {
   S2S_LAUNCH((fltx_ctc_rows_lm_kernel<DT, LOGITS>), (crLmRows<DT, LOGITS>), LOGITS ? nRows : (nRows + 3) / 4,
              kS2sLmThreads, sizeof(S2sLmRowsLds), st, W);
+  return FLTX_OK;
+}
+}
+
+extern "C++" {
+template <int DT, bool LOGITS>
+static int crlWordLmRowsLaunch(int nRows, Stream st, const CrlWordLmParams& W) {
+  S2S_LAUNCH((fltx_ctc_rows_lex_word_lm_kernel<DT, LOGITS>), (crlWordLmRows<DT, LOGITS>),
+             LOGITS ? nRows : (nRows + 3) / 4, kS2sLmThreads, sizeof(S2sLmRowsLds), st, W);
   return FLTX_OK;
 }
 }
@@ -6236,6 +6395,24 @@ static int crLmRowsIn(fltx_decoder* d, const char* what, bool fin, bool idle, co
   W.lmRowOf = lmRowOf;
   W.nLmRows = (int32_t)nLm;
   W.fin = fin ? 1 : 0;
+  if (d->kind == FLTX_DECODER_LEX_CTC_ROWS && !d->s2s.isLmToken) { /* a word LM: the entries of the labels (fltx_ctc_rows_lex.h) */
+    const CrlParams R = crlParams(d, Q);
+    CrlWordLmParams X;
+    memset(&X, 0, sizeof(X));
+    X.w = W;
+    X.trie = R.trie;
+    X.rowNode = R.rowNode;
+    X.S = R.S;
+    X.unk = R.unk;
+    switch (lmDtype * 2 + (logits ? 1 : 0)) {
+      case 0: return crlWordLmRowsLaunch<kS2sDtF32, false>((int)BK, st, X);
+      case 1: return crlWordLmRowsLaunch<kS2sDtF32, true>((int)BK, st, X);
+      case 2: return crlWordLmRowsLaunch<kS2sDtF16, false>((int)BK, st, X);
+      case 3: return crlWordLmRowsLaunch<kS2sDtF16, true>((int)BK, st, X);
+      case 4: return crlWordLmRowsLaunch<kS2sDtBf16, false>((int)BK, st, X);
+      default: return crlWordLmRowsLaunch<kS2sDtBf16, true>((int)BK, st, X);
+    }
+  }
   switch (lmDtype * 2 + (logits ? 1 : 0)) {
     case 0: return crLmRowsLaunch<kS2sDtF32, false>((int)BK, st, W);
     case 1: return crLmRowsLaunch<kS2sDtF32, true>((int)BK, st, W);
@@ -6273,8 +6450,19 @@ int fltx_ctc_rows_step(fltx_decoder* d, const void* lmScores, int32_t lmDtype, i
                        onDevice, lmRowLse, Q))) {
     return rc;
   }
-  S2S_LAUNCH(fltx_ctc_rows_step_kernel, crStepUtterance<false>, d->B, kS2sStepThreads, sizeof(S2lStepLds),
-             d->ctx->stream, Q);
+  if (d->kind == FLTX_DECODER_LEX_CTC_ROWS) {
+    const CrlParams R = crlParams(d, Q);
+    if (d->s2s.isLmToken) {
+      S2S_LAUNCH(fltx_ctc_rows_lex_step_kernel<kCrlLmTokenRows>, (crlStepUtterance<kCrlLmTokenRows, false>), d->B,
+                 kS2sStepThreads, sizeof(CrlStepLds), d->ctx->stream, R);
+    } else {
+      S2S_LAUNCH(fltx_ctc_rows_lex_step_kernel<kCrlLmWordRows>, (crlStepUtterance<kCrlLmWordRows, false>), d->B,
+                 kS2sStepThreads, sizeof(CrlStepLds), d->ctx->stream, R);
+    }
+  } else {
+    S2S_LAUNCH(fltx_ctc_rows_step_kernel, crStepUtterance<false>, d->B, kS2sStepThreads, sizeof(S2lStepLds),
+               d->ctx->stream, Q);
+  }
   if (!last) {
     ++d->s2s.t;
   }
@@ -6299,7 +6487,9 @@ int fltx_ctc_rows_end(fltx_decoder* d, const void* lmScores, int32_t lmDtype, in
   if (d->outScores.ensure(24 * (size_t)B * K, st, false) ||
       d->tokens.ensure(4 * (size_t)std::max<int64_t>(d->histRecords, 1), st, false) ||
       d->outN.ensure(4 * (size_t)B, st, false) || ensureUttRes(d, B, st) ||
-      d->histOffD.ensure(8 * ((size_t)B + 1), st, false)) {
+      d->histOffD.ensure(8 * ((size_t)B + 1), st, false) ||
+      (d->kind == FLTX_DECODER_LEX_CTC_ROWS &&
+       d->words.ensure(4 * (size_t)std::max<int64_t>(d->histRecords, 1), st, false))) {
     return fail(FLTX_ERR_OOM, "CTC rows results: device allocation failed");
   }
   if (uploadHistOff(d, st)) {
@@ -6317,7 +6507,18 @@ int fltx_ctc_rows_end(fltx_decoder* d, const void* lmScores, int32_t lmDtype, in
   Q.s.uttNBeam = d->uttNBeam.as<int32_t>();
   Q.s.uttFrame = d->uttFrame.as<int32_t>();
   Q.s.uttStatus = d->uttStatus.as<int32_t>();
-  S2S_LAUNCH(fltx_ctc_rows_end_kernel, crStepUtterance<true>, B, kS2sStepThreads, sizeof(S2lStepLds), st, Q);
+  if (d->kind == FLTX_DECODER_LEX_CTC_ROWS) {
+    const CrlParams R = crlParams(d, Q);
+    if (d->s2s.isLmToken) {
+      S2S_LAUNCH(fltx_ctc_rows_lex_end_kernel<kCrlLmTokenRows>, (crlStepUtterance<kCrlLmTokenRows, true>), B,
+                 kS2sStepThreads, sizeof(CrlStepLds), st, R);
+    } else {
+      S2S_LAUNCH(fltx_ctc_rows_lex_end_kernel<kCrlLmWordRows>, (crlStepUtterance<kCrlLmWordRows, true>), B,
+                 kS2sStepThreads, sizeof(CrlStepLds), st, R);
+    }
+  } else {
+    S2S_LAUNCH(fltx_ctc_rows_end_kernel, crStepUtterance<true>, B, kS2sStepThreads, sizeof(S2lStepLds), st, Q);
+  }
   d->haveResults = true;
   d->ended = true;
   d->backtraced = true;
