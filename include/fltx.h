@@ -557,6 +557,50 @@ FLTX_API int fltx_ctc_rows_lex_decoder_create(fltx_ctx* ctx, const fltx_options*
                                               const fltx_lm* lm, int32_t sil, int32_t blank, int32_t unk,
                                               int32_t is_lm_token, fltx_decoder** out);
 
+/* ---- streams on the two CTC rows kinds: decodeStep on chunks, getBestHypothesis, prune ------------------------------ */
+/* The online half of the Decoder interface (decoder/Decoder.h:40-69) for a decoder of fltx_ctc_rows_decoder_create or
+ * fltx_ctc_rows_lex_decoder_create; on any other kind these calls return FLTX_ERR_STATE, and fltx_stream_* keeps
+ * returning FLTX_ERR_STATE on these kinds.  All of it runs on the device, asynchronously on the context's stream: every
+ * stream counts its own frames there, its history is a ring of max_frames (+ 100, lexicon kind) + 2 rows, and a prune
+ * copies nothing.
+ *
+ * fltx_ctc_rows_stream_begin: decodeBegin for B parallel streams.  No emissions; N, the token beam, sil / blank and the
+ * LM's map and finish index are checked as by fltx_ctc_rows_begin, and the root is listed per stream as there.
+ * max_frames >= 1 bounds the frames a stream holds between prunes; the lexicon kind gets kLookBackLimit = 100
+ * (Utils.h:28) frames on top, which its prune may keep beyond look_back.  The LM-state table of a stream holds max_states
+ * entries (fltx_decoder_set(dec, "max_states", n) before this call; 65 536): ids stay stable for the whole stream and are
+ * not recycled, and a stream that needs more stops with the "LM-state table full" status while the others go on. */
+FLTX_API int fltx_ctc_rows_stream_begin(fltx_decoder* dec, int32_t B, int32_t N, int32_t max_frames, int32_t* next_token,
+                                        int32_t* next_src_row, int32_t* next_state, int32_t* n_rows);
+/* The next chunk: T[b] >= 0 frames of stream b (0 is allowed; chunks of unequal lengths are the normal case), laid out
+ * as fltx_ctc_rows_begin's emissions.  The token beams of the chunk's frames are taken here.  A host buffer is copied
+ * before the call returns; a DEVICE buffer must stay valid and unchanged until the next append, end or begin on this
+ * decoder has been queued (the lexicon step reads the blank and same-node emissions from it).  Then fltx_ctc_rows_step,
+ * max_b T[b] times, consumes the chunk: each call decodes one frame of every stream that still has frames of it, and a
+ * stream without lists its beam again unchanged, exactly as an exhausted utterance of a batch does.
+ * FLTX_ERR_RANGE when a stream's buffered frames plus the new ones exceed its bound (the host counts an upper bound --
+ * look_back, + 100 for the lexicon kind, after a prune -- and asks the device only when that would not fit);
+ * FLTX_ERR_STATE while frames of the previous chunk are unstepped, outside a stream, and on a decoder begun with
+ * fltx_ctc_rows_begin; FLTX_ERR_INVALID on a negative T[b]. */
+FLTX_API int fltx_ctc_rows_stream_append(fltx_decoder* dec, const float* emissions, int32_t on_device,
+                                         const int64_t* offsets, const int32_t* T);
+/* prune(lookBack) of every stream (LexiconFreeDecoder.cpp:205-227, LexiconDecoder.cpp:304-325), no host
+ * synchronisation.  findBestAncestor (Utils.h:268-310): from the first best of the current beam (strict >) look_back
+ * frames up, for the lexicon kind further while the hypothesis is not complete (its parent ended no word), look_back + 100
+ * steps at most; that updated look-back is what stays buffered.  Nothing happens with too few frames.  pruneAndNormalize
+ * (Utils.h:312-342): the largest score of the CURRENT beam is subtracted from the current beam's scores only; the
+ * emitting-model and LM scores stay, and older frames keep the scores they had -- fltx_result_best(look_back > 0) after a
+ * prune shows them, as the reference does.  FLTX_ERR_INVALID on look_back < 0. */
+FLTX_API int fltx_ctc_rows_stream_prune(fltx_decoder* dec, int32_t look_back);
+/* nDecodedFramesInBuffer of stream b (synchronises). */
+FLTX_API int fltx_ctc_rows_stream_frames_in_buffer(fltx_decoder* dec, int32_t b, int32_t* n);
+/* Inside such a stream fltx_result_best(dec, b, look_back, ...) is getBestHypothesis(lookBack): the ancestor's score,
+ * emitting-model score and LM score, its tokens (and words, lexicon kind), length = frames in buffer - look_back'; an
+ * empty result (LexiconDecoder.cpp:286 included) has length 0.  One launch answers all B streams, and the answer is kept
+ * until the next step, append or prune.  fltx_ctc_rows_end finishes the stream: frames in buffer + 1 entries per
+ * hypothesis -- the buffer's first frame first (the root's sil only if nothing was pruned), decodeEnd's sil last -- read
+ * with fltx_result_* as a batch's. */
+
 /* ---- results (getAllFinalHypothesis / getBestHypothesis) ------------------ */
 /* Number of hypotheses of utterance b and the length (finalFrame + 1) of each
  * tokens/words vector (decoder/Utils.h:236-247). */

@@ -94,6 +94,8 @@ class Lib:
         "fltx_lm_rows_create", "fltx_s2s_step_lm_rows",
         "fltx_lm_word_rows_create", "fltx_s2s_step_word_lm_rows",
         "fltx_ctc_rows_decoder_create", "fltx_ctc_rows_lex_decoder_create", "fltx_ctc_rows_begin", "fltx_ctc_rows_step", "fltx_ctc_rows_end",
+        "fltx_ctc_rows_stream_begin", "fltx_ctc_rows_stream_append", "fltx_ctc_rows_stream_prune",
+        "fltx_ctc_rows_stream_frames_in_buffer",
     ]
 
     def __init__(self, path=None):
@@ -182,6 +184,10 @@ class Lib:
             "fltx_ctc_rows_begin": [vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp],
             "fltx_ctc_rows_step": [vp, vp, i32, i32, i64, vp, i32, i32, vp, vp, vp, vp, vp],
             "fltx_ctc_rows_end": [vp, vp, i32, i32, i64, vp, i32, i32, vp],
+            "fltx_ctc_rows_stream_begin": [vp, i32, i32, i32, vp, vp, vp, vp],
+            "fltx_ctc_rows_stream_append": [vp, vp, i32, vp, vp],
+            "fltx_ctc_rows_stream_prune": [vp, i32],
+            "fltx_ctc_rows_stream_frames_in_buffer": [vp, i32, vp],
         }
         for name, args in sig.items():
             fn = getattr(L, name)
@@ -1128,7 +1134,9 @@ class CtcRowsBatchDecoder(BatchDecoder):
     src_row); rows k >= n_rows[b] are padding (-1).  lm_scores is [n_lm_rows, >= lm_width], ONE ROW PER LM STATE, and
     lm_row_of (B*K int32; None: identity) names the LM row of each decoder row.  end(lm_scores) reads each row's finish
     entry; then the results* methods read the n-best (T[b] + 2 tokens, as decode_batch gives them).  decode() drives it
-    all from a callable."""
+    all from a callable.  Streams: stream_begin(B, N, max_frames), then append(chunk, T) and as many step() calls as it
+    returns, prune(look_back), best(b, look_back) -- getBestHypothesis(lookBack), an empty result has no tokens --
+    frames_in_buffer(b), and end(); decode_stream() drives those."""
 
     _rows = Seq2SeqBatchDecoder._rows
     _addr = staticmethod(Seq2SeqBatchDecoder._addr)
@@ -1177,6 +1185,43 @@ class CtcRowsBatchDecoder(BatchDecoder):
             e = np.ascontiguousarray(emissions, dtype=np.float32)
             self._chk(self.L.lib.fltx_ctc_rows_begin(self.h, _ptr(e), 0, _ptr(off), _ptr(T), self.B, self.N, *ptrs))
         return tuple(out)
+
+    # ---- streams: chunks as they arrive, partial results, a bounded buffer (fltx_ctc_rows_stream_*) ----
+    def stream_begin(self, B, N, max_frames):
+        """decodeBegin for B parallel streams that hold up to max_frames frames each between prunes (the lexicon kind:
+        100 more, which its prune may keep).  Every stream gets a table of max_states LM-state ids, cleared here: call
+        set_max_states(n) first (the default of 65 536 is 1.5 MB per stream).  -> (token, src_row, state, n_rows): the roots.  Then append() a chunk,
+        step() as often as append() says, prune() / best() as wanted, ..., end()."""
+        self.B, self.N, self._T = int(B), int(N), np.zeros(int(B), np.int32)
+        out = self._rows()
+        self._chk(self.L.lib.fltx_ctc_rows_stream_begin(self.h, self.B, self.N, int(max_frames),
+                                                        *[self._addr(o) for o in out]))
+        return tuple(out)
+
+    def append(self, emissions, T, offsets=None, device_ptr=None):
+        """The next chunk: T[b] >= 0 frames of stream b; emissions a host float32 array (flat layout, copied by the
+        call), or None when device_ptr (int) addresses the chunk in HBM -- that must stay valid until the next append()
+        or end().  -> the number of step() calls that consume the chunk (max T)."""
+        T = np.ascontiguousarray(T, dtype=np.int32)
+        assert len(T) == self.B, "T: one entry per stream"
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        if device_ptr is not None:
+            self._chk(self.L.lib.fltx_ctc_rows_stream_append(self.h, device_ptr, 1, _ptr(off), _ptr(T)))
+        else:
+            e = None if emissions is None else np.ascontiguousarray(emissions, dtype=np.float32)
+            self._chk(self.L.lib.fltx_ctc_rows_stream_append(self.h, _ptr(e), 0, _ptr(off), _ptr(T)))
+        self._T = T
+        return int(T.max()) if len(T) else 0
+
+    def prune(self, look_back=0):
+        """prune(lookBack) of every stream, on the device"""
+        self._chk(self.L.lib.fltx_ctc_rows_stream_prune(self.h, int(look_back)))
+
+    def frames_in_buffer(self, b):
+        """nDecodedFramesInBuffer of stream b (synchronises)"""
+        n = C.c_int32(0)
+        self._chk(self.L.lib.fltx_ctc_rows_stream_frames_in_buffer(self.h, int(b), C.addressof(n)))
+        return n.value
 
     def _lm_in(self, lm_scores, lm_row_of, lm_kind, lm_lse_out, lm_dtype):
         """-> the C arguments of the LM rows (and what must stay alive while the kernels read them)"""
@@ -1238,50 +1283,84 @@ class CtcRowsBatchDecoder(BatchDecoder):
         LM runs once per state, however many hypotheses and frames are in it.  Returns results_batch().  (The rows are
         read on the host once per frame to name the new states.)"""
         tok, src, state, n = self.begin(emissions, T, N, offsets=offsets, device_ptr=device_ptr)
-        B, K = self.B, int(self.options.beam_size)
-        max_t = int(self._T.max()) if B else 0
-        row_of, prefix = {}, {}
-        store, n_store, prev_state = None, 0, None
-
-        def host(a):
-            return a if isinstance(a, np.ndarray) else a.cpu().numpy()
-        for t in range(max_t + 1):
-            if not self._emu:
-                self.ctx.synchronize()
-            tok_h, src_h, st_h, n_h = host(tok), host(src), host(state), host(n)
-            keys = []
-            ro = np.full(B * K, -1, np.int32)
-            for b in range(B):
-                for k in range(int(n_h[b])):
-                    key = (b, int(st_h[b, k]))
-                    if key not in row_of:
-                        s = int(src_h[b, k])
-                        par = -1 if s < 0 else int(prev_state.reshape(-1)[s])
-                        prefix[key] = () if s < 0 else prefix[(b, par)] + (int(tok_h[b, k]),)
-                        row_of[key] = n_store + len(keys)
-                        keys.append(self._state_key(b, prefix[key], par, int(tok_h[b, k]) if s >= 0 else -1, key[1]))
-                    ro[b * K + k] = row_of[key]
-            if keys:
-                rows = lm_rows(keys)
-                need = n_store + len(keys)
-                if store is None or need > store.shape[0]:
-                    cap = max(need, 2 * (0 if store is None else store.shape[0]), B * K)
-                    if isinstance(rows, np.ndarray):
-                        grown = np.empty((cap, rows.shape[1]), rows.dtype)
-                    else:
-                        grown = rows.new_empty((cap, rows.shape[1]))
-                    if store is not None:
-                        grown[:n_store] = store[:n_store]
-                    store = grown
-                store[n_store:need] = rows
-                n_store = need
-            prev_state = st_h.copy()
-            ro_in = ro if isinstance(store, np.ndarray) else _to_device_i32(ro, store.device)
-            if t < max_t:
-                tok, src, state, n = self.step(store[:n_store], lm_row_of=ro_in, lm_kind=lm_kind)
-            else:
-                self.end(store[:n_store], lm_row_of=ro_in, lm_kind=lm_kind)
+        lister = _RowLister(self, self.B, int(self.options.beam_size), lm_rows)
+        for _ in range(int(self._T.max()) if self.B else 0):
+            rows, ro = lister.rows(tok, src, state, n)
+            tok, src, state, n = self.step(rows, lm_row_of=ro, lm_kind=lm_kind)
+        rows, ro = lister.rows(tok, src, state, n)
+        self.end(rows, lm_row_of=ro, lm_kind=lm_kind)
         return self.results_batch()
+
+    def decode_stream(self, chunks, lm_rows, look_back=None, *, N=None, max_frames=None, lm_kind="log_probs"):
+        """B streams from an iterable of chunks, each (emissions, T): a host float32 array in flat layout and the B
+        frame counts (0 allowed).  lm_rows is decode()'s callable.  A generator: after every chunk it yields the list
+        of best(b) per stream -- after prune(look_back) when look_back is given -- and, when the chunks are used up,
+        ends the streams and yields results_batch().  N: the token-set size (default: that of the last begin);
+        max_frames: the frames a stream holds between prunes (default: 4096)."""
+        N = self.N if N is None else int(N)
+        chunks = iter(chunks)
+        first = next(chunks, None)
+        B = self.B if first is None else len(first[1])
+        tok, src, state, n = self.stream_begin(B, N, 4096 if max_frames is None else max_frames)
+        K = int(self.options.beam_size)
+        lister = _RowLister(self, B, K, lm_rows)
+        args = lister.rows(tok, src, state, n)
+        chunk = first
+        while chunk is not None:
+            for _ in range(self.append(chunk[0], chunk[1])):
+                tok, src, state, n = self.step(args[0], lm_row_of=args[1], lm_kind=lm_kind)
+                args = lister.rows(tok, src, state, n)
+            if look_back is not None:
+                self.prune(look_back)
+            yield [self.best(b) for b in range(B)]
+            chunk = next(chunks, None)
+        self.end(args[0], lm_row_of=args[1], lm_kind=lm_kind)
+        yield self.results_batch()
+
+
+class _RowLister:
+    """The bookkeeping of decode() and decode_stream(): one LM row per state id, the LM asked once per id."""
+
+    def __init__(self, dec, B, K, lm_rows):
+        self.dec, self.B, self.K, self.lm_rows = dec, B, K, lm_rows
+        self.row_of, self.prefix = {}, {}
+        self.store, self.n_store, self.prev_state = None, 0, None
+
+    def rows(self, tok, src, state, n):
+        """the row lists of a call -> (lm_scores, lm_row_of) for the next"""
+        dec, B, K = self.dec, self.B, self.K
+        if not dec._emu:
+            dec.ctx.synchronize()
+        tok_h, src_h, st_h, n_h = [a if isinstance(a, np.ndarray) else a.cpu().numpy() for a in (tok, src, state, n)]
+        keys = []
+        ro = np.full(B * K, -1, np.int32)
+        for b in range(B):
+            for k in range(int(n_h[b])):
+                key = (b, int(st_h[b, k]))
+                if key not in self.row_of:
+                    s = int(src_h[b, k])
+                    par = -1 if s < 0 else int(self.prev_state.reshape(-1)[s])
+                    self.prefix[key] = () if s < 0 else self.prefix[(b, par)] + (int(tok_h[b, k]),)
+                    self.row_of[key] = self.n_store + len(keys)
+                    keys.append(dec._state_key(b, self.prefix[key], par, int(tok_h[b, k]) if s >= 0 else -1, key[1]))
+                ro[b * K + k] = self.row_of[key]
+        if keys:
+            rows = self.lm_rows(keys)
+            need = self.n_store + len(keys)
+            if self.store is None or need > self.store.shape[0]:
+                cap = max(need, 2 * (0 if self.store is None else self.store.shape[0]), B * K)
+                if isinstance(rows, np.ndarray):
+                    grown = np.empty((cap, rows.shape[1]), rows.dtype)
+                else:
+                    grown = rows.new_empty((cap, rows.shape[1]))
+                if self.store is not None:
+                    grown[:self.n_store] = self.store[:self.n_store]
+                self.store = grown
+            self.store[self.n_store:need] = rows
+            self.n_store = need
+        self.prev_state = st_h.copy()
+        ro_in = ro if isinstance(self.store, np.ndarray) else _to_device_i32(ro, self.store.device)
+        return self.store[:self.n_store], ro_in
 
 
 class LexiconCtcRowsBatchDecoder(CtcRowsBatchDecoder):

@@ -33,6 +33,7 @@
 #include "fltx_s2s_lex.h"
 #include "fltx_ctc_rows.h"
 #include "fltx_ctc_rows_lex.h"
+#include "fltx_ctc_rows_stream.h"
 
 using namespace fltx;
 
@@ -243,6 +244,42 @@ __global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_lex_end_kernel(
 }
 __global__ void __launch_bounds__(kS2sBeginThreads) fltx_ctc_rows_lex_begin_kernel(CrlParams R) {
   crlBeginUtterance(R, nullptr);
+}
+/* fltx_ctc_rows_stream.h: streams on the two CTC rows kinds -- the start, the frame step and its finish variant on the
+ * streams' own counts and history ring; getBestHypothesis and prune */
+__global__ void __launch_bounds__(kS2sBeginThreads) fltx_ctc_rows_stream_begin_kernel(CrStreamParams Z) {
+  crsBeginStream(Z, nullptr);
+}
+__global__ void __launch_bounds__(kS2sBeginThreads) fltx_ctc_rows_lex_stream_begin_kernel(CrlStreamParams Z) {
+  crlsBeginStream(Z, nullptr);
+}
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_stream_step_kernel(CrStreamParams Z) {
+  __shared__ __attribute__((aligned(16))) S2lStepLds fltx_crs_step_lds;
+  crsStepStream<false>(Z, (char*)&fltx_crs_step_lds);
+}
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_stream_end_kernel(CrStreamParams Z) {
+  __shared__ __attribute__((aligned(16))) S2lStepLds fltx_crs_end_lds;
+  crsStepStream<true>(Z, (char*)&fltx_crs_end_lds);
+}
+template <int SRC>
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_lex_stream_step_kernel(CrlStreamParams Z) {
+  __shared__ __attribute__((aligned(16))) CrlStepLds fltx_crls_step_lds;
+  crlsStepStream<SRC, false>(Z, (char*)&fltx_crls_step_lds);
+}
+template <int SRC>
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_lex_stream_end_kernel(CrlStreamParams Z) {
+  __shared__ __attribute__((aligned(16))) CrlStepLds fltx_crls_end_lds;
+  crlsStepStream<SRC, true>(Z, (char*)&fltx_crls_end_lds);
+}
+template <bool LEX>
+__global__ void __launch_bounds__(kCrsOpThreads) fltx_ctc_rows_stream_best_kernel(CrsOpParams W) {
+  __shared__ __attribute__((aligned(16))) CrsOpLds fltx_crs_best_lds;
+  crsBest<LEX>(W, (char*)&fltx_crs_best_lds);
+}
+template <bool LEX>
+__global__ void __launch_bounds__(kCrsOpThreads) fltx_ctc_rows_stream_prune_kernel(CrsOpParams W) {
+  __shared__ __attribute__((aligned(16))) CrsOpLds fltx_crs_prune_lds;
+  crsPrune<LEX>(W, (char*)&fltx_crs_prune_lds);
 }
 __global__ void __launch_bounds__(1024) fltx_streamop_kernel(StreamOpParams Q) {
   __shared__ int32_t sh[kStreamOpLds / 4];
@@ -771,6 +808,15 @@ struct fltx_decoder {
     /* lexicon CTC with a rows LM (kind FLTX_DECODER_LEX_CTC_ROWS, fltx_ctc_rows_lex.h; the compact trie, slots = S,
      * isLmToken and rowNode above are its too): the publisher's beam index, which is nobody's output */
     DBuf crOutBeam;
+    /* streams on the two CTC rows kinds (fltx_ctc_rows_stream_begin, fltx_ctc_rows_stream.h): the frames a stream may
+     * hold, the rows of the rings, {nDec[B], base[B]} and the score ring on the device, the host's upper bound of the
+     * frames each stream holds, and the look-back the best* buffers answer (-1: none) */
+    bool crStream = false;
+    int crCap = 0, crRing = 0, crBestLb = -1;
+    std::vector<int32_t> crBestLen;  /* [2][B] of the last best launch: lengths, statuses */
+    std::vector<double> crBestScores; /* [B][3] */
+    DBuf crCnt, crSHist;
+    std::vector<int32_t> crBuf;
   } s2s;
 };
 
@@ -4778,6 +4824,9 @@ int fltx_result_fetch_batch_compact(fltx_decoder* d, const int32_t** nHyp, const
   return FLTX_OK;
 }
 
+static int crsResultBest(fltx_decoder* d, int32_t b, int32_t lookBack, double* scores, int32_t* tokens, int32_t* words,
+                  int32_t capacity, int32_t* length);
+
 int fltx_result_best(fltx_decoder* d, int32_t b, int32_t lookBack, double* scores, int32_t* tokens,
                      int32_t* words, int32_t capacity, int32_t* length) {
   DeviceScope devScope(d ? d->ctx : nullptr);
@@ -4786,6 +4835,9 @@ int fltx_result_best(fltx_decoder* d, int32_t b, int32_t lookBack, double* score
   }
   if (!d || b < 0 || b >= d->B || lookBack < 0 || !length) {
     return fail(FLTX_ERR_INVALID, "fltx_result_best: bad argument");
+  }
+  if (isCrKind(d->kind) && d->s2s.begun && d->s2s.crStream) { /* inside a stream: getBestHypothesis(lookBack) */
+    return crsResultBest(d, b, lookBack, scores, tokens, words, capacity, length);
   }
   if (!d->haveResults) {
     return fail(FLTX_ERR_STATE, "no decode has been run");
@@ -6181,19 +6233,36 @@ int fltx_ctc_rows_decoder_create(fltx_ctx* ctx, const fltx_options* opt, const f
   return FLTX_OK;
 }
 
-int fltx_ctc_rows_begin(fltx_decoder* d, const float* emissions, int32_t onDevice, const int64_t* offsets,
-                        const int32_t* T, int32_t B, int32_t N, int32_t* nextTok, int32_t* nextSrc, int32_t* nextState,
-                        int32_t* nRows) {
+static CrsParams crsParams(fltx_decoder* d) {
+  CrsParams X;
+  X.nDec = d->s2s.crCnt.as<int32_t>();
+  X.base = X.nDec + d->B;
+  X.ring = d->s2s.crRing;
+  X.sHist = d->s2s.crSHist.as<double>();
+  return X;
+}
+
+/* decodeBegin of a batch (maxFrames < 0: fltx_ctc_rows_begin) or of B streams that hold up to maxFrames frames each
+ * (fltx_ctc_rows_stream_begin; T: null) */
+static int crBegin(fltx_decoder* d, const char* what, const float* emissions, int32_t onDevice, const int64_t* offsets,
+                   const int32_t* T, int32_t B, int32_t N, int32_t maxFrames, int32_t* nextTok, int32_t* nextSrc,
+                   int32_t* nextState, int32_t* nRows) {
   DeviceScope devScope(d ? d->ctx : nullptr);
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
-  int rc = crCheck(d, "fltx_ctc_rows_begin");
+  int rc = crCheck(d, what);
   if (rc) {
     return rc;
   }
-  if (B < 1 || N < 1 || !T || !nextTok || !nextSrc || !nextState || !nRows) {
-    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_begin: bad argument");
+  const bool stream = maxFrames >= 0;
+  if (B < 1 || N < 1 || (!T && !stream) || (stream && maxFrames < 1) || !nextTok || !nextSrc || !nextState || !nRows) {
+    return fail(FLTX_ERR_INVALID, "%s: bad argument", what);
+  }
+  std::vector<int32_t> noFrames;
+  if (stream) { /* no frames yet: a chunk brings them (fltx_ctc_rows_stream_append) */
+    noFrames.assign((size_t)B, 0);
+    T = noFrames.data();
   }
   if (N > kS2sMaxV) {
     return fail(FLTX_ERR_UNSUPPORTED, "CTC rows: N = %d > %d", N, kS2sMaxV);
@@ -6209,6 +6278,9 @@ int fltx_ctc_rows_begin(fltx_decoder* d, const float* emissions, int32_t onDevic
    * whose entry finish could fall back to) */
   d->s2s.eos = N;
   const bool lex = d->kind == FLTX_DECODER_LEX_CTC_ROWS;
+  /* a stream's rings: the frames it may hold -- for the lexicon kind kLookBackLimit ON TOP of max_frames, as
+   * fltx_stream_begin explains -- the root's row and the row the next step writes */
+  const int sCap = stream ? maxFrames + (lex ? kLookBackLimit : 0) : 0, ring = sCap + 2;
   if (lex && d->lm->kind == 4) { /* (word ids, not tokens: checked against the trie's labels at create) */
     d->s2s.lmWidth = d->lm->rowsWidth;
   } else if ((rc = s2sPlanRowsLm(d, N)) || (rc = s2sRowsLmFinishCheck(d->lm->rowsFinish, d->s2s.lmWidth))) {
@@ -6231,7 +6303,7 @@ int fltx_ctc_rows_begin(fltx_decoder* d, const float* emissions, int32_t onDevic
     meta[(size_t)B + 1 + b] = onDevice && offsets ? offsets[b] : frames * N;
     hT[b] = T[b];
     d->histOff[(size_t)b] = off;
-    off += (int64_t)(T[b] + 2) * K;
+    off += (int64_t)(stream ? ring : T[b] + 2) * K; /* (a stream's results: frames in buffer + 1 <= ring entries) */
     frames += T[b];
     maxT = std::max(maxT, T[b]);
   }
@@ -6239,7 +6311,7 @@ int fltx_ctc_rows_begin(fltx_decoder* d, const float* emissions, int32_t onDevic
   d->histOff[(size_t)B] = off;
   d->histRecords = off;
   if (frames > 0 && !emissions) {
-    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_begin: null emissions");
+    return fail(FLTX_ERR_INVALID, "%s: null emissions", what);
   }
   const int64_t nC = lex ? (int64_t)K * ((int64_t)cap * (1 + d->s2s.slots) + 2) : (int64_t)K * cap;
   if (nC > (int64_t)1 << 29) { /* (the merge table holds the next power of two >= 2 nC slots, an int32 count) */
@@ -6250,12 +6322,13 @@ int fltx_ctc_rows_begin(fltx_decoder* d, const float* emissions, int32_t onDevic
   const size_t lmPerRow = (size_t)cap * (lex && !d->s2s.isLmToken ? d->s2s.slots : 1);
   d->s2s.cap = cap;
   d->s2s.mSize = s2lPow2AtLeast(2 * nC);
-  d->s2s.sMax = (int)std::min<int64_t>((int64_t)K * maxT + 2, d->s2s.maxStates);
+  d->s2s.sMax = stream ? d->s2s.maxStates : (int)std::min<int64_t>((int64_t)K * maxT + 2, d->s2s.maxStates);
   d->s2s.sSize = s2lPow2AtLeast(2 * (int64_t)d->s2s.sMax);
   Stream st = d->ctx->stream;
   const size_t BK = (size_t)B * K, BC = (size_t)B * (size_t)nC, nF = (size_t)std::max<int64_t>(frames, 1);
   if (d->s2s.beam.ensure(2 * BK * hypBytes, st, false) || d->s2s.beamN.ensure(8 * (size_t)B, st, false) ||
-      d->s2s.hist.ensure((size_t)(maxT + 2) * BK * recBytes, st, false) ||
+      d->s2s.hist.ensure((size_t)(stream ? ring : maxT + 2) * BK * recBytes, st, false) ||
+      (stream && (d->s2s.crCnt.ensure(8 * (size_t)B, st, false) || d->s2s.crSHist.ensure((size_t)ring * BK * 24, st, false))) ||
       (lex && d->s2s.crOutBeam.ensure(4 * BK, st, false)) ||
       d->s2s.rowsInt.ensure(4 * (size_t)B, st, false) || d->s2s.done.ensure(4 * (size_t)B, st, false) ||
       d->s2s.finalStep.ensure(4 * (size_t)B, st, false) || d->s2s.recTok.ensure(4 * nF * cap, st, false) ||
@@ -6301,6 +6374,11 @@ int fltx_ctc_rows_begin(fltx_decoder* d, const float* emissions, int32_t onDevic
   d->s2s.crMaxT = maxT;
   d->s2s.crFrames = frames;
   d->s2s.begun = true;
+  d->s2s.crStream = stream;
+  d->s2s.crCap = sCap;
+  d->s2s.crRing = ring;
+  d->s2s.crBestLb = -1;
+  d->s2s.crBuf.assign(stream ? (size_t)B : 0, 0);
   d->haveResults = false;
   d->ended = false;
   d->backtraced = false;
@@ -6311,6 +6389,17 @@ int fltx_ctc_rows_begin(fltx_decoder* d, const float* emissions, int32_t onDevic
   Q.s.outSrc = nextSrc;
   Q.s.outN = nRows;
   Q.outState = nextState;
+  if (stream) {
+    const int grid = (B + kS2sBeginThreads - 1) / kS2sBeginThreads;
+    if (lex) {
+      const CrlStreamParams Z = {crlParams(d, Q), crsParams(d)};
+      S2S_LAUNCH(fltx_ctc_rows_lex_stream_begin_kernel, crlsBeginStream, grid, kS2sBeginThreads, 0, st, Z);
+    } else {
+      const CrStreamParams Z = {Q, crsParams(d)};
+      S2S_LAUNCH(fltx_ctc_rows_stream_begin_kernel, crsBeginStream, grid, kS2sBeginThreads, 0, st, Z);
+    }
+    return FLTX_OK;
+  }
   if (frames > 0) {
     S2S_LAUNCH(fltx_ctc_rows_tokbeam_kernel, crTokBeamRows, (int)((frames + 3) / 4), 256, 4 * sizeof(S2sFrontLds), st, Q);
   }
@@ -6323,6 +6412,23 @@ int fltx_ctc_rows_begin(fltx_decoder* d, const float* emissions, int32_t onDevic
   S2S_LAUNCH(fltx_ctc_rows_begin_kernel, crBeginUtterance, (B + kS2sBeginThreads - 1) / kS2sBeginThreads,
              kS2sBeginThreads, 0, st, Q);
   return FLTX_OK;
+}
+
+int fltx_ctc_rows_begin(fltx_decoder* d, const float* emissions, int32_t onDevice, const int64_t* offsets,
+                        const int32_t* T, int32_t B, int32_t N, int32_t* nextTok, int32_t* nextSrc, int32_t* nextState,
+                        int32_t* nRows) {
+  return crBegin(d, "fltx_ctc_rows_begin", emissions, onDevice, offsets, T, B, N, -1, nextTok, nextSrc, nextState, nRows);
+}
+
+int fltx_ctc_rows_stream_begin(fltx_decoder* d, int32_t B, int32_t N, int32_t maxFrames, int32_t* nextTok,
+                               int32_t* nextSrc, int32_t* nextState, int32_t* nRows) {
+  if (maxFrames < 1) {
+    DeviceScope devScope(d ? d->ctx : nullptr);
+    int rc = crCheck(d, "fltx_ctc_rows_stream_begin");
+    return rc ? rc : fail(FLTX_ERR_INVALID, "fltx_ctc_rows_stream_begin: max_frames = %d (>= 1)", maxFrames);
+  }
+  return crBegin(d, "fltx_ctc_rows_stream_begin", nullptr, 1, nullptr, nullptr, B, N, maxFrames, nextTok, nextSrc,
+                 nextState, nRows);
 }
 
 extern "C++" {
@@ -6450,7 +6556,23 @@ int fltx_ctc_rows_step(fltx_decoder* d, const void* lmScores, int32_t lmDtype, i
                        onDevice, lmRowLse, Q))) {
     return rc;
   }
-  if (d->kind == FLTX_DECODER_LEX_CTC_ROWS) {
+  d->s2s.crBestLb = -1;
+  if (d->s2s.crStream) { /* the same step on the streams' own counts (fltx_ctc_rows_stream.h) */
+    if (d->kind == FLTX_DECODER_LEX_CTC_ROWS) {
+      const CrlStreamParams Z = {crlParams(d, Q), crsParams(d)};
+      if (d->s2s.isLmToken) {
+        S2S_LAUNCH(fltx_ctc_rows_lex_stream_step_kernel<kCrlLmTokenRows>, (crlsStepStream<kCrlLmTokenRows, false>), d->B,
+                   kS2sStepThreads, sizeof(CrlStepLds), d->ctx->stream, Z);
+      } else {
+        S2S_LAUNCH(fltx_ctc_rows_lex_stream_step_kernel<kCrlLmWordRows>, (crlsStepStream<kCrlLmWordRows, false>), d->B,
+                   kS2sStepThreads, sizeof(CrlStepLds), d->ctx->stream, Z);
+      }
+    } else {
+      const CrStreamParams Z = {Q, crsParams(d)};
+      S2S_LAUNCH(fltx_ctc_rows_stream_step_kernel, crsStepStream<false>, d->B, kS2sStepThreads, sizeof(S2lStepLds),
+                 d->ctx->stream, Z);
+    }
+  } else if (d->kind == FLTX_DECODER_LEX_CTC_ROWS) {
     const CrlParams R = crlParams(d, Q);
     if (d->s2s.isLmToken) {
       S2S_LAUNCH(fltx_ctc_rows_lex_step_kernel<kCrlLmTokenRows>, (crlStepUtterance<kCrlLmTokenRows, false>), d->B,
@@ -6507,7 +6629,24 @@ int fltx_ctc_rows_end(fltx_decoder* d, const void* lmScores, int32_t lmDtype, in
   Q.s.uttNBeam = d->uttNBeam.as<int32_t>();
   Q.s.uttFrame = d->uttFrame.as<int32_t>();
   Q.s.uttStatus = d->uttStatus.as<int32_t>();
-  if (d->kind == FLTX_DECODER_LEX_CTC_ROWS) {
+  if (d->s2s.crStream) { /* (frames in buffer + 1 entries per hypothesis: what is left of the stream, and decodeEnd's sil) */
+    if (d->kind == FLTX_DECODER_LEX_CTC_ROWS) {
+      const CrlStreamParams Z = {crlParams(d, Q), crsParams(d)};
+      if (d->s2s.isLmToken) {
+        S2S_LAUNCH(fltx_ctc_rows_lex_stream_end_kernel<kCrlLmTokenRows>, (crlsStepStream<kCrlLmTokenRows, true>), B,
+                   kS2sStepThreads, sizeof(CrlStepLds), st, Z);
+      } else {
+        S2S_LAUNCH(fltx_ctc_rows_lex_stream_end_kernel<kCrlLmWordRows>, (crlsStepStream<kCrlLmWordRows, true>), B,
+                   kS2sStepThreads, sizeof(CrlStepLds), st, Z);
+      }
+    } else {
+      const CrStreamParams Z = {Q, crsParams(d)};
+      S2S_LAUNCH(fltx_ctc_rows_stream_end_kernel, crsStepStream<true>, B, kS2sStepThreads, sizeof(S2lStepLds), st, Z);
+    }
+    d->s2s.crStream = false; /* the stream is over: its results are read as a batch's */
+    d->s2s.begun = false;
+    d->s2s.crBestLb = -1;
+  } else if (d->kind == FLTX_DECODER_LEX_CTC_ROWS) {
     const CrlParams R = crlParams(d, Q);
     if (d->s2s.isLmToken) {
       S2S_LAUNCH(fltx_ctc_rows_lex_end_kernel<kCrlLmTokenRows>, (crlStepUtterance<kCrlLmTokenRows, true>), B,
@@ -6528,6 +6667,262 @@ int fltx_ctc_rows_end(fltx_decoder* d, const void* lmScores, int32_t lmDtype, in
   d->compactFetched = false;
   d->scoresFetched = false;
   d->offlinePending = false;
+  return FLTX_OK;
+}
+
+/* ---- streams on the CTC rows kinds (fltx_ctc_rows_stream.h) ----------------------------------------------------------- */
+static int crsCheck(fltx_decoder* d, const char* what) {
+  int rc = crCheck(d, what);
+  if (rc) {
+    return rc;
+  }
+  if (!d->s2s.begun || !d->s2s.crStream) {
+    return fail(FLTX_ERR_STATE, "%s: no open stream (fltx_ctc_rows_stream_begin first)", what);
+  }
+  return FLTX_OK;
+}
+
+/* {nDec[B], base[B]} as the device has them: the frames each stream really holds */
+static int crsReadCounts(fltx_decoder* d, std::vector<int32_t>& cnt) {
+  cnt.resize(2 * (size_t)d->B);
+  if (devCopyD2H(cnt.data(), d->s2s.crCnt.p, 4 * cnt.size(), d->ctx->stream) || devSync(d->ctx->stream)) {
+    return fail(FLTX_ERR_HIP, "CTC rows stream: copy failed");
+  }
+  return FLTX_OK;
+}
+
+int fltx_ctc_rows_stream_append(fltx_decoder* d, const float* emissions, int32_t onDevice, const int64_t* offsets,
+                                const int32_t* T) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = crsCheck(d, "fltx_ctc_rows_stream_append");
+  if (rc) {
+    return rc;
+  }
+  if (!T) {
+    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_stream_append: bad argument");
+  }
+  const int B = d->B, N = d->N, cap = d->s2s.cap;
+  for (int b = 0; b < B; ++b) {
+    if (T[b] < 0) {
+      return fail(FLTX_ERR_INVALID, "T[%d] = %d is negative", b, T[b]);
+    }
+  }
+  if (d->s2s.t < d->s2s.crMaxT) {
+    return fail(FLTX_ERR_STATE, "fltx_ctc_rows_stream_append: %d frames of the previous chunk are unstepped "
+                                "(fltx_ctc_rows_step)", d->s2s.crMaxT - d->s2s.t);
+  }
+  std::vector<int32_t>& buf = d->s2s.crBuf;
+  for (int pass = 0; pass < 2; ++pass) {
+    int bad = -1;
+    for (int b = 0; b < B && bad < 0; ++b) {
+      if (buf[(size_t)b] + T[b] > d->s2s.crCap) {
+        bad = b;
+      }
+    }
+    if (bad < 0) {
+      break;
+    }
+    if (pass == 0) { /* the host's count is an upper bound (a prune of the lexicon kind, a stream that stopped) */
+      std::vector<int32_t> cnt;
+      if ((rc = crsReadCounts(d, cnt))) {
+        return rc;
+      }
+      for (int b = 0; b < B; ++b) {
+        buf[(size_t)b] = cnt[(size_t)b] - cnt[(size_t)B + b];
+      }
+      continue;
+    }
+    const bool lex = d->kind == FLTX_DECODER_LEX_CTC_ROWS;
+    return fail(FLTX_ERR_RANGE, "stream %d: %d buffered + %d new frames exceed max_frames %d%s", bad, buf[(size_t)bad],
+                T[bad], d->s2s.crCap - (lex ? kLookBackLimit : 0),
+                lex ? " + 100 (a lexicon stream's prune keeps the frames back to the last complete word, up to lookBack + "
+                      "100, Utils.h:28,293-308)"
+                    : "");
+  }
+  std::vector<int64_t>& meta = d->s2s.crMetaHost; /* frameOff[B + 1], emOff[B], then T[B] as int32: the CHUNK's */
+  meta.assign((size_t)2 * B + 1 + ((size_t)B + 1) / 2, 0);
+  int32_t* hT = (int32_t*)(meta.data() + 2 * (size_t)B + 1);
+  int64_t frames = 0;
+  int maxT = 0;
+  bool packed = true;
+  for (int b = 0; b < B; ++b) {
+    meta[(size_t)b] = frames;
+    packed = packed && (!offsets || offsets[b] == frames * N);
+    meta[(size_t)B + 1 + b] = onDevice && offsets ? offsets[b] : frames * N;
+    hT[b] = T[b];
+    frames += T[b];
+    maxT = std::max(maxT, T[b]);
+  }
+  meta[(size_t)B] = frames;
+  if (frames > 0 && !emissions) {
+    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_stream_append: null emissions");
+  }
+  Stream st = d->ctx->stream;
+  const size_t nF = (size_t)std::max<int64_t>(frames, 1);
+  if (d->s2s.recTok.ensure(4 * nF * cap, st, false) || d->s2s.recAm.ensure(4 * nF * cap, st, false) ||
+      d->s2s.recN.ensure(4 * nF, st, false) || (!onDevice && d->s2s.crEmis.ensure(4 * nF * N, st, false))) {
+    return fail(FLTX_ERR_OOM, "CTC rows stream: device allocation failed (%lld frames)", (long long)frames);
+  }
+  if (devCopyH2D(d->s2s.crMeta.p, meta.data(), 8 * meta.size(), st)) {
+    return fail(FLTX_ERR_HIP, "CTC rows stream: upload failed");
+  }
+  d->s2s.crEmisDev = emissions;
+  if (!onDevice && frames > 0) { /* a host chunk: copied here, stream after stream */
+    float* dst = d->s2s.crEmis.as<float>();
+    int bad = 0;
+    if (packed) {
+      bad = devCopyH2D(dst, emissions + (offsets ? offsets[0] : 0), 4 * (size_t)frames * N, st);
+    } else {
+      for (int b = 0; b < B && !bad; ++b) {
+        if (T[b] > 0) {
+          bad = devCopyH2D(dst + meta[(size_t)b] * N, emissions + offsets[b], 4 * (size_t)T[b] * N, st);
+        }
+      }
+    }
+    if (bad || devSync(st)) { /* (the caller's buffer is only borrowed for the call) */
+      return fail(FLTX_ERR_HIP, "CTC rows stream: emission upload failed");
+    }
+    d->s2s.crEmisDev = dst;
+  }
+  d->s2s.t = 0;
+  d->s2s.crMaxT = maxT;
+  d->s2s.crFrames = frames;
+  d->s2s.crBestLb = -1;
+  for (int b = 0; b < B; ++b) {
+    buf[(size_t)b] += T[b];
+  }
+  if (frames > 0) {
+    CrParams Q = crParams(d);
+    S2S_LAUNCH(fltx_ctc_rows_tokbeam_kernel, crTokBeamRows, (int)((frames + 3) / 4), 256, 4 * sizeof(S2sFrontLds), st, Q);
+  }
+  return FLTX_OK;
+}
+
+static CrsOpParams crsOpParams(fltx_decoder* d, int lookBack) {
+  CrsOpParams W;
+  memset(&W, 0, sizeof(W));
+  W.B = d->B;
+  W.K = d->opt.beam_size;
+  W.lookBack = lookBack;
+  W.maxLen = d->s2s.crRing;
+  W.beamN = d->s2s.beamN.as<int32_t>();
+  W.status = d->s2s.status.as<int32_t>();
+  W.x = crsParams(d);
+  W.beam = d->s2s.beam.p;
+  W.hist = d->s2s.hist.p;
+  W.bestLen = d->bestLen.as<int32_t>();
+  W.bestScores = d->bestScores.as<double>();
+  W.bestTok = d->bestTok.as<int32_t>();
+  W.bestWrd = d->bestWrd.as<int32_t>();
+  return W;
+}
+
+int fltx_ctc_rows_stream_prune(fltx_decoder* d, int32_t lookBack) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = crsCheck(d, "fltx_ctc_rows_stream_prune");
+  if (rc) {
+    return rc;
+  }
+  if (lookBack < 0) {
+    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_stream_prune: look_back = %d", lookBack);
+  }
+  const CrsOpParams W = crsOpParams(d, lookBack);
+  if (d->kind == FLTX_DECODER_LEX_CTC_ROWS) {
+    S2S_LAUNCH(fltx_ctc_rows_stream_prune_kernel<true>, crsPrune<true>, d->B, kCrsOpThreads, sizeof(CrsOpLds),
+               d->ctx->stream, W);
+  } else {
+    S2S_LAUNCH(fltx_ctc_rows_stream_prune_kernel<false>, crsPrune<false>, d->B, kCrsOpThreads, sizeof(CrsOpLds),
+               d->ctx->stream, W);
+  }
+  d->s2s.crBestLb = -1;
+  /* what stays buffered, without asking the device: look_back frames (every lexicon-free hypothesis is complete), up to
+   * kLookBackLimit more for the lexicon kind; a prune that does nothing leaves no more than that either */
+  const int keep = lookBack + (d->kind == FLTX_DECODER_LEX_CTC_ROWS ? kLookBackLimit : 0);
+  /* (a prune between append and the chunk's last step sees only the frames stepped so far: the chunk's unstepped frames
+   * -- T[b] of the chunk's meta less the steps taken -- arrive afterwards and stay on top of the bound) */
+  const int32_t* chunkT = (const int32_t*)(d->s2s.crMetaHost.data() + 2 * (size_t)d->B + 1);
+  for (int b = 0; b < d->B; ++b) {
+    const int pending = std::max(0, chunkT[b] - d->s2s.t);
+    const int stepped = d->s2s.crBuf[(size_t)b] - pending;
+    d->s2s.crBuf[(size_t)b] = (stepped - lookBack >= 1 ? std::min(stepped, keep) : stepped) + pending;
+  }
+  return FLTX_OK;
+}
+
+int fltx_ctc_rows_stream_frames_in_buffer(fltx_decoder* d, int32_t b, int32_t* n) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = crsCheck(d, "fltx_ctc_rows_stream_frames_in_buffer");
+  if (rc) {
+    return rc;
+  }
+  if (!n || b < 0 || b >= d->B) {
+    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_stream_frames_in_buffer: bad argument");
+  }
+  std::vector<int32_t> cnt;
+  if ((rc = crsReadCounts(d, cnt))) {
+    return rc;
+  }
+  *n = cnt[(size_t)b] - cnt[(size_t)d->B + b] + 1; /* nDecodedFramesInBuffer: the buffer's first frame counts */
+  return FLTX_OK;
+}
+
+/* fltx_result_best inside a stream of a CTC rows decoder: getBestHypothesis(lookBack) of all B streams in one launch,
+ * kept until the next step, append or prune */
+static int crsResultBest(fltx_decoder* d, int32_t b, int32_t lookBack, double* scores, int32_t* tokens, int32_t* words,
+                  int32_t capacity, int32_t* length) {
+  Stream st = d->ctx->stream;
+  const int B = d->B, maxLen = d->s2s.crRing;
+  const bool lex = d->kind == FLTX_DECODER_LEX_CTC_ROWS;
+  if (d->s2s.crBestLb != lookBack) {
+    if (d->bestLen.ensure(8 * (size_t)B, st, false) || d->bestScores.ensure(24 * (size_t)B, st, false) ||
+        d->bestTok.ensure(4 * (size_t)B * maxLen, st, false) || d->bestWrd.ensure(4 * (size_t)B * maxLen, st, false)) {
+      return fail(FLTX_ERR_OOM, "best-hypothesis buffers: allocation failed");
+    }
+    const CrsOpParams W = crsOpParams(d, lookBack);
+    if (lex) {
+      S2S_LAUNCH(fltx_ctc_rows_stream_best_kernel<true>, crsBest<true>, B, 64, sizeof(CrsOpLds), st, W);
+    } else {
+      S2S_LAUNCH(fltx_ctc_rows_stream_best_kernel<false>, crsBest<false>, B, 64, sizeof(CrsOpLds), st, W);
+    }
+    /* the lengths, statuses and scores of all B streams cross once per launch; a call then copies its tokens alone */
+    d->s2s.crBestLen.resize(2 * (size_t)B);
+    d->s2s.crBestScores.resize(3 * (size_t)B);
+    if (devCopyD2H(d->s2s.crBestLen.data(), d->bestLen.p, 8 * (size_t)B, st) ||
+        devCopyD2H(d->s2s.crBestScores.data(), d->bestScores.p, 24 * (size_t)B, st)) {
+      return fail(FLTX_ERR_HIP, "copy failed");
+    }
+    d->s2s.crBestLb = lookBack;
+  }
+  const int32_t len = d->s2s.crBestLen[(size_t)b], status = d->s2s.crBestLen[(size_t)B + b];
+  if (status & ST_TABLE_FULL) {
+    return fail(FLTX_ERR_UNSUPPORTED, "utterance %d: LM-state table full (cap=%u)", b, d->stateCap);
+  }
+  *length = len;
+  if (len == 0) {
+    return FLTX_OK; /* an empty DecodeResult */
+  }
+  if (len > capacity) {
+    return fail(FLTX_ERR_RANGE, "fltx_result_best: capacity %d < length %d", capacity, len);
+  }
+  if (scores) {
+    memcpy(scores, d->s2s.crBestScores.data() + 3 * (size_t)b, 24);
+  }
+  if ((tokens && devCopyD2H(tokens, d->bestTok.as<int32_t>() + (size_t)b * maxLen, 4 * (size_t)len, st)) ||
+      (words && lex && devCopyD2H(words, d->bestWrd.as<int32_t>() + (size_t)b * maxLen, 4 * (size_t)len, st))) {
+    return fail(FLTX_ERR_HIP, "copy failed");
+  }
+  if (words && !lex) {
+    std::fill(words, words + len, -1); /* LexiconFreeDecoder.h:80-82 */
+  }
   return FLTX_OK;
 }
 

@@ -74,6 +74,47 @@ FLTX_DEV int crParity(const CrParams& Q, int b) {
   return (Q.s.t < tb ? Q.s.t : tb) & 1;
 }
 
+/* what a stream (fltx_ctc_rows_stream_begin, fltx_ctc_rows_stream.h) adds: there s.t, T, frameOff and emOff are those of
+ * the current CHUNK, every stream counts its own frames, and the history is a ring.  beamN holds a stream's count in
+ * both of its slots, so the gathers -- which take the slot from the chunk's t -- run as they are. */
+struct CrsParams {
+  int32_t* nDec;  /* [B] frames decoded since begin: the beam's parity, the history row (nDec % ring) */
+  int32_t* base;  /* [B] frames pruned off: the buffer holds frames base .. nDec */
+  int32_t ring;   /* rows of the two rings */
+  double* sHist;  /* [ring][B*K][3]: (score, am, lm) of the hypotheses after s frames */
+};
+
+/* the frames stream b has decoded, and its beam's parity */
+template <bool STREAM>
+FLTX_DEV int crStepParity(const CrParams& Q, const CrsParams* X, int b, int& nd) {
+  if constexpr (STREAM) {
+    nd = X->nDec[b];
+    return nd & 1;
+  } else {
+    nd = 0;
+    return crParity(Q, b);
+  }
+}
+
+/* a stream's step is over: the count in both slots of beamN, the scores into their ring, one frame more */
+template <typename Hyp>
+FLTX_DEV void crsStepDone(const CrParams& Q, const CrsParams& X, int b, int nd, int nSel, const Hyp& nh) {
+  const S2sParams& P = Q.s;
+  const int tid = (int)threadIdx.x;
+  if (tid < nSel) {
+    double* sc = X.sHist + ((size_t)((nd + 1) % X.ring) * P.B * P.K + (size_t)b * P.K + tid) * 3;
+    sc[0] = nh.score;
+    sc[1] = nh.am;
+    sc[2] = nh.lm;
+  }
+  if (tid == 0) { /* (nSel == 0 -- every candidate NaN: the frame counts and its beam is empty, as in the reference; the
+                   * publisher has stopped the stream, best answers with an empty result) */
+    P.beamN[b] = nSel;
+    P.beamN[P.B + b] = nSel;
+    X.nDec[b] = nd + 1;
+  }
+}
+
 /* ---- front end: the token beam of every frame, once ------------------------------------------------------------------ */
 /* workgroup = four waves, wave = frame record fr of the batch */
 FLTX_DEV void crTokBeamRows(const CrParams& Q, char* smem) {
@@ -347,8 +388,8 @@ FLTX_DEV void crIdleStep(const CrParams& Q, int b) {
   }
 }
 
-template <bool FIN>
-FLTX_DEV void crStepUtterance(const CrParams& Q, char* smem) {
+template <bool FIN, bool STREAM = false>
+FLTX_DEV void crStepUtterance(const CrParams& Q, char* smem, const CrsParams* X = nullptr) {
   const S2sParams& P = Q.s;
   S2lStepLds& L = *(S2lStepLds*)smem;
   S2sStepLds& S = L.s;
@@ -356,7 +397,8 @@ FLTX_DEV void crStepUtterance(const CrParams& Q, char* smem) {
   const int K = P.K;
   const int64_t rb = (int64_t)b * K;
   const int tb = Q.T[b];
-  const int par = crParity(Q, b);
+  int nd;
+  const int par = crStepParity<STREAM>(Q, X, b, nd);
   const CrHyp* prev = Q.beam + (size_t)par * P.B * K + rb;
   const int nPrev = P.done[b] ? 0 : P.beamN[par * P.B + b];
   if constexpr (!FIN) {
@@ -442,7 +484,12 @@ FLTX_DEV void crStepUtterance(const CrParams& Q, char* smem) {
   }
   if constexpr (FIN) {
     /* 5. the n-best: scores, and the paths walked back through the history (getAllHypothesis, Utils.h:230-266) */
-    const int fb = P.t < tb ? P.t : tb; /* frames decoded (all of them, unless the caller ends early) */
+    int fb = P.t < tb ? P.t : tb; /* frames decoded (all of them, unless the caller ends early) */
+    int first = 0;
+    if constexpr (STREAM) { /* the frames in the buffer, walked by count: its first row has parents of a pruned frame */
+      first = X->base[b];
+      fb = nd - first;
+    }
     const int len = fb + 2;
     if (tid < nSel) {
       double* sc = P.outScores + (rb + tid) * 3;
@@ -453,7 +500,7 @@ FLTX_DEV void crStepUtterance(const CrParams& Q, char* smem) {
       out[len - 1] = Q.sil;
       int p = c.hyp;
       for (int s = fb; s >= 0; --s) {
-        const int2 rec = Q.hist[(size_t)s * P.B * K + rb + p];
+        const int2 rec = Q.hist[(size_t)(STREAM ? (first + s) % X->ring : s) * P.B * K + rb + p];
         out[s] = rec.x;
         p = rec.y;
       }
@@ -516,7 +563,7 @@ FLTX_DEV void crStepUtterance(const CrParams& Q, char* smem) {
         nh.sid = (int32_t)loadCoherent32((const uint32_t*)&sVal[sslot]);
       }
       next[tid] = nh;
-      Q.hist[(size_t)(P.t + 1) * P.B * K + rb + tid] = make_int2(nh.token, nh.parent);
+      Q.hist[(size_t)(STREAM ? (nd + 1) % X->ring : P.t + 1) * P.B * K + rb + tid] = make_int2(nh.token, nh.parent);
     }
     if (tid == 0) {
       Q.merges[b] += nMerged;
@@ -524,6 +571,9 @@ FLTX_DEV void crStepUtterance(const CrParams& Q, char* smem) {
     const bool in = tid < nSel;
     s2sPublishStepWith(P, S, b, nSel, in, in && c.isNew ? c.token : -1, in ? nh.parent : -1,
                        in ? (int)rb + nh.parent : -1, CrRowState{Q.outState, nh.sid});
+    if constexpr (STREAM) {
+      crsStepDone(Q, *X, b, nd, nSel, nh);
+    }
   }
 }
 

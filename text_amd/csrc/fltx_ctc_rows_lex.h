@@ -308,8 +308,8 @@ struct CrlRowState {
   __device__ __forceinline__ void none(int64_t r) const { outState[r] = -1; }
 };
 
-template <int SRC, bool FIN>
-FLTX_DEV void crlStepUtterance(const CrlParams& R, char* smem) {
+template <int SRC, bool FIN, bool STREAM = false>
+FLTX_DEV void crlStepUtterance(const CrlParams& R, char* smem, const CrsParams* Z = nullptr) {
   const CrParams& Q = R.c;
   const S2sParams& P = Q.s;
   CrlStepLds& X = *(CrlStepLds*)smem;
@@ -319,7 +319,8 @@ FLTX_DEV void crlStepUtterance(const CrlParams& R, char* smem) {
   const int K = P.K;
   const int64_t rb = (int64_t)b * K;
   const int tb = Q.T[b];
-  const int par = crParity(Q, b);
+  int nd;
+  const int par = crStepParity<STREAM>(Q, Z, b, nd);
   const CrlHyp* prev = R.beam + (size_t)par * P.B * K + rb;
   const int nPrev = P.done[b] ? 0 : P.beamN[par * P.B + b];
   if constexpr (!FIN) {
@@ -420,7 +421,12 @@ FLTX_DEV void crlStepUtterance(const CrlParams& R, char* smem) {
   }
   if constexpr (FIN) {
     /* 5. the n-best: scores, and the paths walked back through the history (getAllHypothesis, Utils.h:230-266) */
-    const int fb = P.t < tb ? P.t : tb; /* frames decoded (all of them, unless the caller ends early) */
+    int fb = P.t < tb ? P.t : tb; /* frames decoded (all of them, unless the caller ends early) */
+    int first = 0;
+    if constexpr (STREAM) { /* the frames in the buffer, walked by count */
+      first = Z->base[b];
+      fb = nd - first;
+    }
     const int len = fb + 2;
     if (tid < nSel) {
       double* sc = P.outScores + (rb + tid) * 3;
@@ -434,7 +440,7 @@ FLTX_DEV void crlStepUtterance(const CrlParams& R, char* smem) {
       outW[len - 1] = -1;
       int p = c.hyp;
       for (int s = fb; s >= 0; --s) {
-        const S2lRec rec = R.hist[(size_t)s * P.B * K + rb + p];
+        const S2lRec rec = R.hist[(size_t)(STREAM ? (first + s) % Z->ring : s) * P.B * K + rb + p];
         out[s] = rec.token;
         outW[s] = rec.word;
         p = rec.parent;
@@ -503,7 +509,7 @@ FLTX_DEV void crlStepUtterance(const CrlParams& R, char* smem) {
       rec.word = nh.word;
       rec.parent = nh.parent;
       rec.pad = 0;
-      R.hist[(size_t)(P.t + 1) * P.B * K + rb + tid] = rec;
+      R.hist[(size_t)(STREAM ? (nd + 1) % Z->ring : P.t + 1) * P.B * K + rb + tid] = rec;
     }
     if (tid == 0) {
       Q.merges[b] += nMerged;
@@ -511,6 +517,9 @@ FLTX_DEV void crlStepUtterance(const CrlParams& R, char* smem) {
     const bool in = tid < nSel;
     s2sPublishStepWith(P, S, b, nSel, in, in && c.isNew ? c.edge : -1, in ? nh.parent : -1,
                        in ? (int)rb + nh.parent : -1, CrlRowState{Q.outState, R.rowNode, nh.sid, nh.node});
+    if constexpr (STREAM) {
+      crsStepDone(Q, *Z, b, nd, nSel, nh);
+    }
   }
 }
 

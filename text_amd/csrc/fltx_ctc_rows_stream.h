@@ -1,0 +1,238 @@
+/*
+ * fltx_ctc_rows_stream.h -- streams on the two CTC rows decoders (fltx_ctc_rows.h, fltx_ctc_rows_lex.h): decodeStep on
+ * chunks as they arrive, getBestHypothesis(lookBack) and prune(lookBack) (LexiconFreeDecoder.cpp:188-227,
+ * LexiconDecoder.cpp:285-325, Utils.h:268-342).  Included after fltx_ctc_rows_lex.h.
+ *
+ * Counts.  A chunk is what the offline path calls a batch: s.t, T, frameOff and emOff of CrParams are the chunk's, so the
+ * token beams (crTokBeamRows) and the two gathers (crLmRows, crlWordLmRows) run unchanged.  What outlives a chunk is per
+ * stream and on the device (CrsParams): nDec, the frames decoded since begin, and base, the frames pruned off.  The
+ * buffer holds frames base .. nDec: nDecodedFramesInBuffer is nDec - base + 1.  The beam after nDec frames is the one
+ * of parity nDec & 1; beamN carries its size in both slots.
+ *
+ * Rings.  The history row of frame s is s % ring, ring = max_frames (+ kLookBackLimit for the lexicon kind) + 2 rows of
+ * [B*K] records; a second ring of the same shape holds (score, am, lm), which getBestHypothesis(lookBack > 0) returns of
+ * the ancestor.  Walks stop by count: the first row of the buffer still names parents, of a frame that is gone.  So
+ * prune moves base, subtracts the current beam's largest score from the current beam's scores (beam and score ring;
+ * am and lm stay, and so do the scores of older frames: Utils.h:331-341) and copies nothing.
+ *
+ * Kernels: the begin, step and end variants of the two kinds (the offline bodies with STREAM set), and
+ *   fltx_ctc_rows_stream_best_kernel<LEX>   one workgroup per stream: the first best of the beam by strict > is slot 0
+ *   fltx_ctc_rows_stream_prune_kernel<LEX>  (the beams are sorted best first); thread 0 alone walks lookBack
+ *                                           records up -- a chain of dependent loads, nothing to spread -- and, for
+ *                                           the lexicon kind, on to a complete hypothesis (its parent ended a word, or
+ *                                           it has none), lookBack + kLookBackLimit steps at most.  best writes the
+ *                                           ancestor's scores and its path; prune the new base and the normalised scores.
+ */
+#pragma once
+
+namespace fltx {
+
+constexpr int kCrsOpThreads = 256;  /* >= kS2sMaxBeam: prune normalises with a thread per hypothesis */
+
+struct CrStreamParams {
+  CrParams c;
+  CrsParams x;
+};
+
+struct CrlStreamParams {
+  CrlParams r;
+  CrsParams x;
+};
+
+/* ---- begin, step, end: the offline bodies on a stream's counts -------------------------------------------------------- */
+FLTX_DEV void crsBeginCounts(const CrParams& Q, const CrsParams& X) {
+  const S2sParams& P = Q.s;
+  const int b = (int)(blockIdx.x * kS2sBeginThreads + threadIdx.x);
+  if (b >= P.B) {
+    return;
+  }
+  X.nDec[b] = 0;
+  X.base[b] = 0;
+  P.beamN[P.B + b] = 1;
+  double* sc = X.sHist + (size_t)b * P.K * 3; /* the root's scores */
+  sc[0] = 0.0;
+  sc[1] = 0.0;
+  sc[2] = 0.0;
+}
+
+FLTX_DEV void crsBeginStream(const CrStreamParams& Z, char* smem) {
+  crBeginUtterance(Z.c, smem);
+  crsBeginCounts(Z.c, Z.x);
+}
+
+FLTX_DEV void crlsBeginStream(const CrlStreamParams& Z, char* smem) {
+  crlBeginUtterance(Z.r, smem);
+  crsBeginCounts(Z.r.c, Z.x);
+}
+
+template <bool FIN>
+FLTX_DEV void crsStepStream(const CrStreamParams& Z, char* smem) {
+  crStepUtterance<FIN, true>(Z.c, smem, &Z.x);
+}
+
+template <int SRC, bool FIN>
+FLTX_DEV void crlsStepStream(const CrlStreamParams& Z, char* smem) {
+  crlStepUtterance<SRC, FIN, true>(Z.r, smem, &Z.x);
+}
+
+/* ---- getBestHypothesis and prune ------------------------------------------------------------------------------------------ */
+struct CrsOpParams {
+  int32_t B, K, lookBack, maxLen;
+  const int32_t* beamN; /* [2][B], both slots the stream's */
+  const int32_t* status; /* [B] ST_* */
+  CrsParams x;
+  void* beam;           /* [2][B*K] CrHyp / CrlHyp */
+  const void* hist;     /* [ring][B*K] int2 / S2lRec */
+  /* best */
+  int32_t* bestLen;     /* [2][B]: the length (0: an empty result), the stream's status */
+  double* bestScores;   /* [B][3] */
+  int32_t *bestTok, *bestWrd; /* [B][maxLen] */
+};
+
+struct CrsOpLds {
+  int32_t anc, steps; /* the ancestor's slot in its beam (-1: none) and how far back it is */
+  double largest;
+};
+
+template <bool LEX>
+struct CrsKind {
+  using Hyp = CrHyp;
+  using Rec = int2;
+  static __device__ __forceinline__ int token(const Rec& r) { return r.x; }
+  static __device__ __forceinline__ int word(const Rec&) { return -1; }
+  static __device__ __forceinline__ int parent(const Rec& r) { return r.y; }
+};
+template <>
+struct CrsKind<true> {
+  using Hyp = CrlHyp;
+  using Rec = S2lRec;
+  static __device__ __forceinline__ int token(const Rec& r) { return r.token; }
+  static __device__ __forceinline__ int word(const Rec& r) { return r.word; }
+  static __device__ __forceinline__ int parent(const Rec& r) { return r.parent; }
+};
+
+/* findBestAncestor (Utils.h:268-310) on stream b, whose buffer holds F + 1 frames.  Every thread gets the same answer:
+ * S.anc the ancestor's slot in the beam of buffer frame F - S.steps (-1: the walk left the buffer, or the beam is empty),
+ * S.steps the updated lookBack, S.largest the beam's largest score. */
+template <bool LEX>
+FLTX_DEV void crsFindBestAncestor(const CrsOpParams& W, CrsOpLds& S, int b, int nd, int first, int n) {
+  using Kd = CrsKind<LEX>;
+  const int tid = (int)threadIdx.x;
+  const int64_t BK = (int64_t)W.B * W.K, rb = (int64_t)b * W.K;
+  const typename Kd::Hyp* beam = (const typename Kd::Hyp*)W.beam + (size_t)(nd & 1) * BK + rb;
+  const typename Kd::Rec* hist = (const typename Kd::Rec*)W.hist;
+  if (tid == 0) {
+    const int F = nd - first;
+    /* The first best by strict > (the largest score, the lower slot among equals) is slot 0: the step leaves every beam
+     * sorted best first (s2sSelectTopK), and a prune takes one value off all of its scores.  No reduction over the beam. */
+    int p = n > 0 ? 0 : -1;
+    int f = F, steps = 0;
+    S.largest = n > 0 ? beam[0].score : 0.0;
+    while (p >= 0 && steps < W.lookBack) { /* (the parent of the buffer's first frame is null) */
+      ++steps;
+      p = f > 0 ? Kd::parent(hist[(size_t)((first + f) % W.x.ring) * BK + rb + p]) : -1;
+      --f;
+    }
+    if constexpr (LEX) { /* (one record per step: the parent's record says whether it ended a word, and names its own parent) */
+      const int maxLookBack = W.lookBack + kLookBackLimit;
+      typename Kd::Rec rec = {};
+      if (p >= 0 && f > 0) {
+        rec = hist[(size_t)((first + f) % W.x.ring) * BK + rb + p];
+      }
+      while (p >= 0 && f > 0) { /* isComplete (LexiconDecoder.h:97-99): no parent (f == 0) ... */
+        const int pp = Kd::parent(rec);
+        rec = hist[(size_t)((first + f - 1) % W.x.ring) * BK + rb + pp];
+        if (Kd::word(rec) >= 0) { /* ... or the parent ended a word */
+          break;
+        }
+        ++steps;
+        p = pp;
+        --f;
+        if (steps == maxLookBack) {
+          break;
+        }
+      }
+    }
+    S.anc = p;
+    S.steps = steps;
+  }
+  __syncthreads();
+}
+
+/* getBestHypothesis(lookBack) of every stream: workgroup = stream */
+template <bool LEX>
+FLTX_DEV void crsBest(const CrsOpParams& W, char* smem) {
+  using Kd = CrsKind<LEX>;
+  CrsOpLds& S = *(CrsOpLds*)smem;
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+  const int64_t BK = (int64_t)W.B * W.K, rb = (int64_t)b * W.K;
+  const int nd = W.x.nDec[b], first = W.x.base[b];
+  const int F = nd - first;
+  const int n = W.beamN[b];
+  if (tid == 0) {
+    W.bestLen[W.B + b] = W.status[b];
+  }
+  if (LEX && F - W.lookBack < 1) { /* LexiconDecoder.cpp:286 */
+    if (tid == 0) {
+      W.bestLen[b] = 0;
+    }
+    return;
+  }
+  crsFindBestAncestor<LEX>(W, S, b, nd, first, n);
+  if (tid != 0) {
+    return;
+  }
+  int p = S.anc;
+  if (p < 0) {
+    W.bestLen[b] = 0;
+    return;
+  }
+  const int f0 = F - S.steps; /* the ancestor's frame in the buffer: getHypothesis(node, f0) (Utils.h:229-250) */
+  const typename Kd::Rec* hist = (const typename Kd::Rec*)W.hist;
+  const double* sc = W.x.sHist + ((size_t)((first + f0) % W.x.ring) * BK + rb + p) * 3;
+  W.bestScores[3 * b] = sc[0];
+  W.bestScores[3 * b + 1] = sc[1];
+  W.bestScores[3 * b + 2] = sc[2];
+  W.bestLen[b] = f0 + 1;
+  int32_t* tok = W.bestTok + (size_t)b * W.maxLen;
+  int32_t* wrd = W.bestWrd + (size_t)b * W.maxLen;
+  for (int f = f0; f >= 0; --f) {
+    const typename Kd::Rec rec = hist[(size_t)((first + f) % W.x.ring) * BK + rb + p];
+    tok[f] = Kd::token(rec);
+    wrd[f] = Kd::word(rec);
+    p = Kd::parent(rec);
+  }
+}
+
+/* prune(lookBack) of every stream: workgroup = stream */
+template <bool LEX>
+FLTX_DEV void crsPrune(const CrsOpParams& W, char* smem) {
+  using Kd = CrsKind<LEX>;
+  CrsOpLds& S = *(CrsOpLds*)smem;
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+  const int64_t BK = (int64_t)W.B * W.K, rb = (int64_t)b * W.K;
+  const int nd = W.x.nDec[b], first = W.x.base[b];
+  const int F = nd - first;
+  const int n = W.beamN[b];
+  if (F - W.lookBack < 1) {
+    return; /* not enough decoded frames */
+  }
+  crsFindBestAncestor<LEX>(W, S, b, nd, first, n);
+  const int startFrame = F - S.steps;
+  if (S.anc < 0 || startFrame < 1) {
+    return;
+  }
+  /* pruneAndNormalize (Utils.h:312-342): the buffer begins at startFrame; the current beam's scores, less their largest */
+  if (tid < n) {
+    typename Kd::Hyp* beam = (typename Kd::Hyp*)W.beam + (size_t)(nd & 1) * BK + rb;
+    double s = beam[tid].score;
+    s -= S.largest;
+    beam[tid].score = s;
+    W.x.sHist[((size_t)(nd % W.x.ring) * BK + rb + tid) * 3] = s;
+  }
+  if (tid == 0) {
+    W.x.base[b] = first + startFrame;
+  }
+}
+
+} // namespace fltx
