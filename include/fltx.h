@@ -461,7 +461,9 @@ FLTX_API int fltx_s2s_lex_info(fltx_decoder* dec, int64_t* trie_bytes, int64_t* 
  * Limits (FLTX_ERR_UNSUPPORTED beyond them; there is no CPU fallback): beam_size <= 256, N <= 65 536,
  * min(beam_size_token, N) <= 256.  Each utterance names its LM states in a table of min(beam_size * max T + 2,
  * max_states) entries (max_states: 65 536, or fltx_decoder_set(dec, "max_states", n) before fltx_ctc_rows_begin); an
- * utterance that needs more stops, and fltx_result_count reports FLTX_ERR_UNSUPPORTED ("LM-state table full") for it. */
+ * utterance that needs more stops, and fltx_result_count reports FLTX_ERR_UNSUPPORTED ("LM-state table full") for it.
+ * (A stream -- fltx_ctc_rows_stream_begin -- holds max_states ids and gets dead ones back through
+ * fltx_ctc_rows_stream_collect.) */
 FLTX_API int fltx_ctc_rows_decoder_create(fltx_ctx* ctx, const fltx_options* opt, const fltx_lm* lm, int32_t sil,
                                           int32_t blank, fltx_decoder** out);
 /* decodeBegin (:20-28) for B utterances.  Emissions as for fltx_decode_batch: float32, utterance b reads T[b]*N floats
@@ -475,7 +477,8 @@ FLTX_API int fltx_ctc_rows_decoder_create(fltx_ctx* ctx, const fltx_options* opt
  *   next_src_row  the parent's row in the call that produced it (-1 for the root);
  *   next_token    the token that advanced the LM state in this frame, -1 when the state is the parent's (a blank, or a
  *                 repeat without a blank in between); the root lists sil;
- *   next_state    the hypothesis' canonical LM-state id within its utterance (the root's: 0), stable for the whole decode:
+ *   next_state    the hypothesis' canonical LM-state id within its utterance (the root's: 0), stable for the whole decode
+ *                 (in a stream: until fltx_ctc_rows_stream_collect lists it as released):
  *                 two rows with the same id are in the same LM state, and the same id at a later frame is that state again
  *                 -- a caller keeps one LM row per id and runs the LM only for ids it has not seen (the new state is the
  *                 state of row next_src_row advanced by next_token).
@@ -568,8 +571,10 @@ FLTX_API int fltx_ctc_rows_lex_decoder_create(fltx_ctx* ctx, const fltx_options*
  * LM's map and finish index are checked as by fltx_ctc_rows_begin, and the root is listed per stream as there.
  * max_frames >= 1 bounds the frames a stream holds between prunes; the lexicon kind gets kLookBackLimit = 100
  * (Utils.h:28) frames on top, which its prune may keep beyond look_back.  The LM-state table of a stream holds max_states
- * entries (fltx_decoder_set(dec, "max_states", n) before this call; 65 536): ids stay stable for the whole stream and are
- * not recycled, and a stream that needs more stops with the "LM-state table full" status while the others go on. */
+ * entries (fltx_decoder_set(dec, "max_states", n) before this call; 65 536): an id keeps its meaning until
+ * fltx_ctc_rows_stream_collect lists it, and a stream that needs more ids than are free stops with the "LM-state table
+ * full" status while the others go on.  A stream that never collects hands every id out once.  A begin starts the ids
+ * over: nothing is free, the root is id 0. */
 FLTX_API int fltx_ctc_rows_stream_begin(fltx_decoder* dec, int32_t B, int32_t N, int32_t max_frames, int32_t* next_token,
                                         int32_t* next_src_row, int32_t* next_state, int32_t* n_rows);
 /* The next chunk: T[b] >= 0 frames of stream b (0 is allowed; chunks of unequal lengths are the normal case), laid out
@@ -592,6 +597,22 @@ FLTX_API int fltx_ctc_rows_stream_append(fltx_decoder* dec, const float* emissio
  * emitting-model and LM scores stay, and older frames keep the scores they had -- fltx_result_best(look_back > 0) after a
  * prune shows them, as the reference does.  FLTX_ERR_INVALID on look_back < 0. */
 FLTX_API int fltx_ctc_rows_stream_prune(fltx_decoder* dec, int32_t look_back);
+/* Give back the LM-state ids of every stream that no later step can meet again, so that a stream of any length runs in
+ * a table of max_states ids and the caller keeps a bounded number of LM rows.  With R the next_state ids of the stream's
+ * current beam plus, transitively, every id whose (parent id, edge) table entry has its parent in R, an allocated id is
+ * kept while it is in R or is the parent id a hypothesis of the current beam was made from (merge keys still compare
+ * that number); every other allocated id is dead.  Per stream the lowest release_cap dead ids are released -- the rest
+ * at a later call -- and listed ascending in released[b * release_cap ..], -1 behind them; n_released[b] is their count
+ * and n_live[b] (may be NULL) the ids still allocated after the call.  All three are DEVICE buffers.  A released id may
+ * be handed out again by a later step for a DIFFERENT state: the caller drops the LM row it kept for it, and an id a
+ * later row list shows that the caller does not hold is a new state -- that of row next_src_row advanced by next_token,
+ * as always.  Ids not listed keep their meaning, and every later step decides what it would have decided without the
+ * call.  A stream that has stopped (a full table, an empty beam) is left alone: n_released[b] = 0, its status stays.
+ * May be called wherever fltx_ctc_rows_stream_prune may, also between an append and its steps; asynchronous on the
+ * context's stream, nothing is copied to the host.  FLTX_ERR_STATE outside a stream, on a decoder begun with
+ * fltx_ctc_rows_begin and on any other kind; FLTX_ERR_INVALID on release_cap < 1 or NULL released / n_released. */
+FLTX_API int fltx_ctc_rows_stream_collect(fltx_decoder* dec, int32_t release_cap, int32_t* released,
+                                          int32_t* n_released, int32_t* n_live);
 /* nDecodedFramesInBuffer of stream b (synchronises). */
 FLTX_API int fltx_ctc_rows_stream_frames_in_buffer(fltx_decoder* dec, int32_t b, int32_t* n);
 /* Inside such a stream fltx_result_best(dec, b, look_back, ...) is getBestHypothesis(lookBack): the ancestor's score,

@@ -95,7 +95,7 @@ class Lib:
         "fltx_lm_word_rows_create", "fltx_s2s_step_word_lm_rows",
         "fltx_ctc_rows_decoder_create", "fltx_ctc_rows_lex_decoder_create", "fltx_ctc_rows_begin", "fltx_ctc_rows_step", "fltx_ctc_rows_end",
         "fltx_ctc_rows_stream_begin", "fltx_ctc_rows_stream_append", "fltx_ctc_rows_stream_prune",
-        "fltx_ctc_rows_stream_frames_in_buffer",
+        "fltx_ctc_rows_stream_frames_in_buffer", "fltx_ctc_rows_stream_collect",
     ]
 
     def __init__(self, path=None):
@@ -188,6 +188,7 @@ class Lib:
             "fltx_ctc_rows_stream_append": [vp, vp, i32, vp, vp],
             "fltx_ctc_rows_stream_prune": [vp, i32],
             "fltx_ctc_rows_stream_frames_in_buffer": [vp, i32, vp],
+            "fltx_ctc_rows_stream_collect": [vp, i32, vp, vp, vp],
         }
         for name, args in sig.items():
             fn = getattr(L, name)
@@ -1136,7 +1137,8 @@ class CtcRowsBatchDecoder(BatchDecoder):
     entry; then the results* methods read the n-best (T[b] + 2 tokens, as decode_batch gives them).  decode() drives it
     all from a callable.  Streams: stream_begin(B, N, max_frames), then append(chunk, T) and as many step() calls as it
     returns, prune(look_back), best(b, look_back) -- getBestHypothesis(lookBack), an empty result has no tokens --
-    frames_in_buffer(b), and end(); decode_stream() drives those."""
+    frames_in_buffer(b), and end(); decode_stream() drives those.  A stream's state ids stay stable until collect()
+    lists them as released: a released id may come back for another state."""
 
     _rows = Seq2SeqBatchDecoder._rows
     _addr = staticmethod(Seq2SeqBatchDecoder._addr)
@@ -1160,6 +1162,8 @@ class CtcRowsBatchDecoder(BatchDecoder):
         self.B = 0
         self.N = None
         self._emu = "emulation" in self.L.version()
+        self._max_states = 65536    # what the next begin / stream_begin gives every utterance
+        self._stream_states = 65536  # what the open stream got: collect()'s default cap
         _live["dec"].add(self)
 
     @staticmethod
@@ -1170,6 +1174,11 @@ class CtcRowsBatchDecoder(BatchDecoder):
     def set_max_states(self, n):
         """LM states per utterance from the next begin() on (default 65 536)"""
         self.set("max_states", n)
+
+    def set(self, key, value):
+        BatchDecoder.set(self, key, value)
+        if key == "max_states":  # (takes effect at the next begin: an open stream keeps its table)
+            self._max_states = int(value)
 
     def begin(self, emissions, T, N, offsets=None, device_ptr=None):
         """emissions: a host float32 array (flat layout, copied by the call), or None when device_ptr (int) addresses
@@ -1196,6 +1205,7 @@ class CtcRowsBatchDecoder(BatchDecoder):
         out = self._rows()
         self._chk(self.L.lib.fltx_ctc_rows_stream_begin(self.h, self.B, self.N, int(max_frames),
                                                         *[self._addr(o) for o in out]))
+        self._stream_states = self._max_states
         return tuple(out)
 
     def append(self, emissions, T, offsets=None, device_ptr=None):
@@ -1216,6 +1226,26 @@ class CtcRowsBatchDecoder(BatchDecoder):
     def prune(self, look_back=0):
         """prune(lookBack) of every stream, on the device"""
         self._chk(self.L.lib.fltx_ctc_rows_stream_prune(self.h, int(look_back)))
+
+    def collect(self, release_cap=None):
+        """Give back the state ids of every stream that no later step can meet again (fltx_ctc_rows_stream_collect):
+        the ids that are neither in the current beam, nor below one of its states in the table, nor the parent id of
+        one of its hypotheses.  -> (released [B, cap], n_released [B], n_live [B]) int32 -- torch tensors on the
+        context's device, numpy arrays on the emulator library; nothing is copied to the host.  released[b] lists the
+        stream's released ids ascending, -1 behind them, at most release_cap (default: the stream's max_states) per call; n_live
+        the ids still allocated.  A released id may be handed out again for another state: drop the LM row kept for
+        it.  A stopped stream releases nothing."""
+        cap = self._stream_states if release_cap is None else int(release_cap)
+        B = self.B
+        if self._emu:
+            out = [np.empty((B, max(cap, 0)), np.int32), np.empty(B, np.int32), np.empty(B, np.int32)]
+        else:
+            import torch
+            dev = torch.device("cuda", torch.cuda.current_device())
+            out = [torch.empty((B, max(cap, 0)), dtype=torch.int32, device=dev),
+                   torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev)]
+        self._chk(self.L.lib.fltx_ctc_rows_stream_collect(self.h, cap, *[self._addr(o) for o in out]))
+        return tuple(out)
 
     def frames_in_buffer(self, b):
         """nDecodedFramesInBuffer of stream b (synchronises)"""
@@ -1291,12 +1321,18 @@ class CtcRowsBatchDecoder(BatchDecoder):
         self.end(rows, lm_row_of=ro, lm_kind=lm_kind)
         return self.results_batch()
 
-    def decode_stream(self, chunks, lm_rows, look_back=None, *, N=None, max_frames=None, lm_kind="log_probs"):
+    def decode_stream(self, chunks, lm_rows, look_back=None, *, N=None, max_frames=None, lm_kind="log_probs",
+                      collect_every=None, on_release=None):
         """B streams from an iterable of chunks, each (emissions, T): a host float32 array in flat layout and the B
         frame counts (0 allowed).  lm_rows is decode()'s callable.  A generator: after every chunk it yields the list
         of best(b) per stream -- after prune(look_back) when look_back is given -- and, when the chunks are used up,
         ends the streams and yields results_batch().  N: the token-set size (default: that of the last begin);
-        max_frames: the frames a stream holds between prunes (default: 4096)."""
+        max_frames: the frames a stream holds between prunes (default: 4096).
+        collect_every=n: after every n-th chunk (after the prune) collect() gives the dead state ids back, the LM rows
+        kept for them are dropped and their places reused, and on_release(b, ids) -- ids a list, ascending -- tells an
+        LM that caches per state_id to drop its states; a stream then runs in max_states ids and a bounded row store
+        however long it is.  (The `prefix` handed to lm_rows still grows with the stream.)  None: no collect, ids are
+        handed out once, as without the argument."""
         N = self.N if N is None else int(N)
         chunks = iter(chunks)
         first = next(chunks, None)
@@ -1306,12 +1342,28 @@ class CtcRowsBatchDecoder(BatchDecoder):
         lister = _RowLister(self, B, K, lm_rows)
         args = lister.rows(tok, src, state, n)
         chunk = first
+        n_chunks = 0
         while chunk is not None:
             for _ in range(self.append(chunk[0], chunk[1])):
                 tok, src, state, n = self.step(args[0], lm_row_of=args[1], lm_kind=lm_kind)
                 args = lister.rows(tok, src, state, n)
             if look_back is not None:
                 self.prune(look_back)
+            n_chunks += 1
+            if collect_every is not None and n_chunks % int(collect_every) == 0:
+                # (a modest cap: the list is cleared on the device whatever it holds; what does not fit goes at the next
+                # collect.  The counts come to the host first, then only the part of the list that is filled.)
+                rel, n_rel, _ = self.collect(min(self._stream_states, 1024))
+                if not self._emu:
+                    self.ctx.synchronize()
+                    n_rel = n_rel.cpu().numpy()
+                    rel = rel[:, :max(int(n_rel.max()), 1)].cpu().numpy()
+                for b in range(B):
+                    if n_rel[b]:
+                        ids = [int(i) for i in rel[b, :int(n_rel[b])]]
+                        lister.release(b, ids)
+                        if on_release is not None:
+                            on_release(b, ids)
             yield [self.best(b) for b in range(B)]
             chunk = next(chunks, None)
         self.end(args[0], lm_row_of=args[1], lm_kind=lm_kind)
@@ -1319,12 +1371,22 @@ class CtcRowsBatchDecoder(BatchDecoder):
 
 
 class _RowLister:
-    """The bookkeeping of decode() and decode_stream(): one LM row per state id, the LM asked once per id."""
+    """The bookkeeping of decode() and decode_stream(): one LM row per state id, the LM asked once per id (once per
+    time the id is handed out, when release() gives ids back).  `prefix` -- what lm_rows is handed -- is the tuple of
+    edges since the start of the stream and grows with it; the rows kept do not."""
 
     def __init__(self, dec, B, K, lm_rows):
         self.dec, self.B, self.K, self.lm_rows = dec, B, K, lm_rows
         self.row_of, self.prefix = {}, {}
         self.store, self.n_store, self.prev_state = None, 0, None
+        self.free = []  # rows of the store whose state ids were released
+
+    def release(self, b, ids):
+        """stream b's state ids `ids` were released (collect()): forget them, their rows of the store are free"""
+        for i in ids:
+            key = (b, int(i))
+            self.free.append(self.row_of.pop(key))
+            del self.prefix[key]
 
     def rows(self, tok, src, state, n):
         """the row lists of a call -> (lm_scores, lm_row_of) for the next"""
@@ -1332,7 +1394,7 @@ class _RowLister:
         if not dec._emu:
             dec.ctx.synchronize()
         tok_h, src_h, st_h, n_h = [a if isinstance(a, np.ndarray) else a.cpu().numpy() for a in (tok, src, state, n)]
-        keys = []
+        keys, slots = [], []
         ro = np.full(B * K, -1, np.int32)
         for b in range(B):
             for k in range(int(n_h[b])):
@@ -1341,12 +1403,17 @@ class _RowLister:
                     s = int(src_h[b, k])
                     par = -1 if s < 0 else int(self.prev_state.reshape(-1)[s])
                     self.prefix[key] = () if s < 0 else self.prefix[(b, par)] + (int(tok_h[b, k]),)
-                    self.row_of[key] = self.n_store + len(keys)
+                    if self.free:
+                        slots.append(self.free.pop())
+                    else:
+                        slots.append(self.n_store)
+                        self.n_store += 1
+                    self.row_of[key] = slots[-1]
                     keys.append(dec._state_key(b, self.prefix[key], par, int(tok_h[b, k]) if s >= 0 else -1, key[1]))
                 ro[b * K + k] = self.row_of[key]
         if keys:
             rows = self.lm_rows(keys)
-            need = self.n_store + len(keys)
+            need = self.n_store
             if self.store is None or need > self.store.shape[0]:
                 cap = max(need, 2 * (0 if self.store is None else self.store.shape[0]), B * K)
                 if isinstance(rows, np.ndarray):
@@ -1354,10 +1421,14 @@ class _RowLister:
                 else:
                     grown = rows.new_empty((cap, rows.shape[1]))
                 if self.store is not None:
-                    grown[:self.n_store] = self.store[:self.n_store]
+                    grown[:self.store.shape[0]] = self.store
                 self.store = grown
-            self.store[self.n_store:need] = rows
-            self.n_store = need
+            if slots == list(range(slots[0], slots[0] + len(slots))):
+                self.store[slots[0]:slots[0] + len(slots)] = rows
+            elif isinstance(self.store, np.ndarray):
+                self.store[np.asarray(slots)] = rows
+            else:
+                self.store[_to_device_i32(np.asarray(slots, np.int64), self.store.device)] = rows
         self.prev_state = st_h.copy()
         ro_in = ro if isinstance(self.store, np.ndarray) else _to_device_i32(ro, self.store.device)
         return self.store[:self.n_store], ro_in

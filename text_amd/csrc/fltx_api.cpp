@@ -281,6 +281,11 @@ __global__ void __launch_bounds__(kCrsOpThreads) fltx_ctc_rows_stream_prune_kern
   __shared__ __attribute__((aligned(16))) CrsOpLds fltx_crs_prune_lds;
   crsPrune<LEX>(W, (char*)&fltx_crs_prune_lds);
 }
+template <bool LEX>
+__global__ void __launch_bounds__(kCrsOpThreads) fltx_ctc_rows_stream_collect_kernel(CrsCollectParams W) {
+  __shared__ __attribute__((aligned(16))) CrsCollectLds fltx_crs_collect_lds;
+  crsCollect<LEX>(W, (char*)&fltx_crs_collect_lds);
+}
 __global__ void __launch_bounds__(1024) fltx_streamop_kernel(StreamOpParams Q) {
   __shared__ int32_t sh[kStreamOpLds / 4];
   streamOpUtterance(Q, sh);
@@ -816,6 +821,9 @@ struct fltx_decoder {
     std::vector<int32_t> crBestLen;  /* [2][B] of the last best launch: lengths, statuses */
     std::vector<double> crBestScores; /* [B][3] */
     DBuf crCnt, crSHist;
+    /* what fltx_ctc_rows_stream_collect recycles LM-state ids with: {sPar, sEdge, sFree}[B][sMax] then sFreeN[B], and
+     * the mark bitsets [B][2][(sMax + 31) / 32] of tables too large for the kernel's LDS */
+    DBuf crIds, crMarks;
     std::vector<int32_t> crBuf;
   } s2s;
 };
@@ -6239,6 +6247,11 @@ static CrsParams crsParams(fltx_decoder* d) {
   X.base = X.nDec + d->B;
   X.ring = d->s2s.crRing;
   X.sHist = d->s2s.crSHist.as<double>();
+  const size_t ids = (size_t)d->B * d->s2s.sMax;
+  X.sPar = d->s2s.crIds.as<int32_t>();
+  X.sEdge = X.sPar + ids;
+  X.sFree = X.sEdge + ids;
+  X.sFreeN = X.sFree + ids;
   return X;
 }
 
@@ -6328,7 +6341,10 @@ static int crBegin(fltx_decoder* d, const char* what, const float* emissions, in
   const size_t BK = (size_t)B * K, BC = (size_t)B * (size_t)nC, nF = (size_t)std::max<int64_t>(frames, 1);
   if (d->s2s.beam.ensure(2 * BK * hypBytes, st, false) || d->s2s.beamN.ensure(8 * (size_t)B, st, false) ||
       d->s2s.hist.ensure((size_t)(stream ? ring : maxT + 2) * BK * recBytes, st, false) ||
-      (stream && (d->s2s.crCnt.ensure(8 * (size_t)B, st, false) || d->s2s.crSHist.ensure((size_t)ring * BK * 24, st, false))) ||
+      (stream && (d->s2s.crCnt.ensure(8 * (size_t)B, st, false) || d->s2s.crSHist.ensure((size_t)ring * BK * 24, st, false) ||
+                  d->s2s.crIds.ensure(4 * (size_t)B * (3 * (size_t)d->s2s.sMax + 1), st, false) ||
+                  (d->s2s.sMax > kCrsLdsIds &&
+                   d->s2s.crMarks.ensure(8 * (size_t)B * (((size_t)d->s2s.sMax + 31) / 32), st, false)))) ||
       (lex && d->s2s.crOutBeam.ensure(4 * BK, st, false)) ||
       d->s2s.rowsInt.ensure(4 * (size_t)B, st, false) || d->s2s.done.ensure(4 * (size_t)B, st, false) ||
       d->s2s.finalStep.ensure(4 * (size_t)B, st, false) || d->s2s.recTok.ensure(4 * nF * cap, st, false) ||
@@ -6851,6 +6867,48 @@ int fltx_ctc_rows_stream_prune(fltx_decoder* d, int32_t lookBack) {
     const int pending = std::max(0, chunkT[b] - d->s2s.t);
     const int stepped = d->s2s.crBuf[(size_t)b] - pending;
     d->s2s.crBuf[(size_t)b] = (stepped - lookBack >= 1 ? std::min(stepped, keep) : stepped) + pending;
+  }
+  return FLTX_OK;
+}
+
+int fltx_ctc_rows_stream_collect(fltx_decoder* d, int32_t releaseCap, int32_t* released, int32_t* nReleased,
+                                 int32_t* nLive) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = crsCheck(d, "fltx_ctc_rows_stream_collect");
+  if (rc) {
+    return rc;
+  }
+  if (releaseCap < 1 || !released || !nReleased) {
+    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_stream_collect: release_cap = %d (>= 1), null released or n_released",
+                releaseCap);
+  }
+  CrsCollectParams W;
+  memset(&W, 0, sizeof(W));
+  W.B = d->B;
+  W.K = d->opt.beam_size;
+  W.sMax = d->s2s.sMax;
+  W.sSize = d->s2s.sSize;
+  W.releaseCap = releaseCap;
+  W.beamN = d->s2s.beamN.as<int32_t>();
+  W.done = d->s2s.done.as<int32_t>();
+  W.x = crsParams(d);
+  W.beam = d->s2s.beam.p;
+  W.sKey = d->s2s.sKey.as<unsigned long long>();
+  W.sVal = d->s2s.sVal.as<int32_t>();
+  W.sCount = d->s2s.sCount.as<int32_t>();
+  W.marks = d->s2s.sMax > kCrsLdsIds ? d->s2s.crMarks.as<uint32_t>() : nullptr;
+  W.released = released;
+  W.nReleased = nReleased;
+  W.nLive = nLive;
+  if (d->kind == FLTX_DECODER_LEX_CTC_ROWS) {
+    S2S_LAUNCH(fltx_ctc_rows_stream_collect_kernel<true>, crsCollect<true>, d->B, kCrsOpThreads, sizeof(CrsCollectLds),
+               d->ctx->stream, W);
+  } else {
+    S2S_LAUNCH(fltx_ctc_rows_stream_collect_kernel<false>, crsCollect<false>, d->B, kCrsOpThreads, sizeof(CrsCollectLds),
+               d->ctx->stream, W);
   }
   return FLTX_OK;
 }

@@ -82,7 +82,36 @@ struct CrsParams {
   int32_t* base;  /* [B] frames pruned off: the buffer holds frames base .. nDec */
   int32_t ring;   /* rows of the two rings */
   double* sHist;  /* [ring][B*K][3]: (score, am, lm) of the hypotheses after s frames */
+  /* what fltx_ctc_rows_stream_collect recycles ids with (fltx_ctc_rows_stream.h) */
+  int32_t* sPar;   /* [B][sMax] the parent id of state id's table entry; -1: allocated without an entry; -2: free */
+  int32_t* sEdge;  /* [B][sMax] the entry's edge */
+  int32_t* sFree;  /* [B][sMax] the stack of free ids below the high-water mark sCount */
+  int32_t* sFreeN; /* [B] ids on the stack */
 };
+
+/* a stream's step hands out an id for the state child(psid, edge): one off the free stack (fltx_ctc_rows_stream_collect
+ * put it there) while there is one, else the next unused one; >= Q.sMax: the table is full.  The threads of a step pop
+ * concurrently, so the count may pass below zero: crsClaimDone puts it right behind the step's barrier. */
+FLTX_DEV int32_t crsClaimId(const CrParams& Q, const CrsParams& X, int b, int32_t psid, int32_t edge) {
+  int32_t v;
+  const int32_t f = (int32_t)atomAdd32((uint32_t*)&X.sFreeN[b], 0xFFFFFFFFu);
+  if (f > 0) {
+    v = (int32_t)loadCoherent32((const uint32_t*)&X.sFree[(size_t)b * Q.sMax + f - 1]);
+  } else {
+    v = (int32_t)atomAdd32((uint32_t*)&Q.sCount[b], 1u);
+  }
+  if (v < Q.sMax) {
+    X.sPar[(size_t)b * Q.sMax + v] = psid;
+    X.sEdge[(size_t)b * Q.sMax + v] = edge;
+  }
+  return v;
+}
+
+FLTX_DEV void crsClaimDone(const CrsParams& X, int b) {
+  if (threadIdx.x == 0 && (int32_t)loadCoherent32((const uint32_t*)&X.sFreeN[b]) < 0) {
+    X.sFreeN[b] = 0;
+  }
+}
 
 /* the frames stream b has decoded, and its beam's parity */
 template <bool STREAM>
@@ -539,7 +568,12 @@ FLTX_DEV void crStepUtterance(const CrParams& Q, char* smem, const CrsParams* X 
     }
     __syncthreads();
     if (claimed) {
-      const int32_t v = (int32_t)atomAdd32((uint32_t*)&Q.sCount[b], 1u);
+      int32_t v;
+      if constexpr (STREAM) { /* (ids come back: fltx_ctc_rows_stream_collect) */
+        v = crsClaimId(Q, *X, b, nh.psid, nh.edge);
+      } else {
+        v = (int32_t)atomAdd32((uint32_t*)&Q.sCount[b], 1u);
+      }
       if (v >= Q.sMax) {
         L.full = 1;
       }
@@ -547,6 +581,9 @@ FLTX_DEV void crStepUtterance(const CrParams& Q, char* smem, const CrsParams* X 
     }
     __threadfence();
     __syncthreads();
+    if constexpr (STREAM) {
+      crsClaimDone(*X, b);
+    }
     if (L.full) { /* the state table is full: the utterance stops, its status says so (never a silent wrong merge) */
       crIdleStep(Q, b);
       if (tid == 0) {

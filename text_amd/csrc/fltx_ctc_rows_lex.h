@@ -480,7 +480,12 @@ FLTX_DEV void crlStepUtterance(const CrlParams& R, char* smem, const CrsParams* 
     }
     __syncthreads();
     if (claimed) {
-      const int32_t v = (int32_t)atomAdd32((uint32_t*)&Q.sCount[b], 1u);
+      int32_t v;
+      if constexpr (STREAM) { /* (ids come back: fltx_ctc_rows_stream_collect) */
+        v = crsClaimId(Q, *Z, b, nh.psid, nh.edge);
+      } else {
+        v = (int32_t)atomAdd32((uint32_t*)&Q.sCount[b], 1u);
+      }
       if (v >= Q.sMax) {
         L.full = 1;
       }
@@ -488,6 +493,9 @@ FLTX_DEV void crlStepUtterance(const CrlParams& R, char* smem, const CrsParams* 
     }
     __threadfence();
     __syncthreads();
+    if constexpr (STREAM) {
+      crsClaimDone(*Z, b);
+    }
     if (L.full) { /* the state table is full: the utterance stops, its status says so (never a silent wrong merge) */
       crIdleStep(Q, b);
       if (tid == 0) {

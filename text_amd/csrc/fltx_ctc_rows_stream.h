@@ -48,6 +48,9 @@ FLTX_DEV void crsBeginCounts(const CrParams& Q, const CrsParams& X) {
   }
   X.nDec[b] = 0;
   X.base[b] = 0;
+  X.sFreeN[b] = 0; /* no id is free; id 0, LM::start, is allocated and has no table entry */
+  X.sPar[(size_t)b * Q.sMax] = -1;
+  X.sEdge[(size_t)b * Q.sMax] = -1;
   P.beamN[P.B + b] = 1;
   double* sc = X.sHist + (size_t)b * P.K * 3; /* the root's scores */
   sc[0] = 0.0;
@@ -232,6 +235,177 @@ FLTX_DEV void crsPrune(const CrsOpParams& W, char* smem) {
   }
   if (tid == 0) {
     W.x.base[b] = first + startFrame;
+  }
+}
+
+/* ---- collect: the LM-state ids nothing can meet again go back to the stream ------------------------------------------- */
+constexpr int kCrsLdsIds = 65536; /* ids whose two mark bitsets fit the kernel's LDS (2 x 8 KB); more: the HBM scratch */
+
+struct CrsCollectParams {
+  int32_t B, K, sMax, sSize, releaseCap;
+  const int32_t* beamN;  /* [2][B], both slots the stream's */
+  const int32_t* done;   /* [B] the stream has stopped */
+  CrsParams x;
+  const void* beam;      /* [2][B*K] CrHyp / CrlHyp */
+  unsigned long long* sKey;
+  int32_t* sVal;
+  const int32_t* sCount;
+  uint32_t* marks;       /* [B][2][(sMax + 31) / 32] when sMax > kCrsLdsIds, else null */
+  int32_t *released, *nReleased, *nLive;
+};
+
+struct CrsCollectLds {
+  uint32_t bits[2][kCrsLdsIds / 32];
+  int32_t wsum[kCrsOpThreads / 64];
+  int32_t changed;
+};
+
+FLTX_DEV bool crsMarked(const uint32_t* bits, int id) {
+  return (loadCoherent32(&bits[id >> 5]) >> (id & 31)) & 1u;
+}
+FLTX_DEV void crsMark(uint32_t* bits, int id) { (void)atomOr32(&bits[id >> 5], 1u << (id & 31)); }
+
+/* One workgroup per stream.  With R the ids a later step can still look up or enter -- the sids of the current beam and,
+ * transitively, every id whose table entry hangs below one of R -- and the psids of the current beam, which merge keys
+ * still compare as numbers, every other allocated id is dead: the lowest releaseCap of them go on the free stack and
+ * into released[] (ascending, -1 behind them), the table entries whose id or parent went are dropped, and a pinned id
+ * that loses its entry keeps its number. */
+template <bool LEX>
+FLTX_DEV void crsCollect(const CrsCollectParams& W, char* smem) {
+  using Hyp = typename CrsKind<LEX>::Hyp;
+  CrsCollectLds& S = *(CrsCollectLds*)smem;
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+  const size_t sb = (size_t)b * W.sMax;
+  int32_t* sPar = W.x.sPar + sb;
+  int32_t* sEdge = W.x.sEdge + sb;
+  int32_t* out = W.released + (size_t)b * W.releaseCap;
+  for (int i = tid; i < W.releaseCap; i += kCrsOpThreads) {
+    out[i] = -1;
+  }
+  const int cnt = W.sCount[b];
+  const int hw = cnt < W.sMax ? cnt : W.sMax; /* ids below the high-water mark */
+  const int nFree = W.x.sFreeN[b];
+  if (W.done[b]) { /* a stopped stream is left alone */
+    if (tid == 0) {
+      W.nReleased[b] = 0;
+      if (W.nLive) {
+        W.nLive[b] = hw - nFree;
+      }
+    }
+    return;
+  }
+  const int words = (W.sMax + 31) >> 5;
+  uint32_t* inR = W.marks ? W.marks + (size_t)b * 2 * words : S.bits[0];
+  uint32_t* pin = W.marks ? inR + words : S.bits[1];
+  /* 1. mark: the beam's states and their parents' numbers, then R down the table tree until a pass adds nothing */
+  for (int i = tid; i < ((hw + 31) >> 5); i += kCrsOpThreads) {
+    inR[i] = 0u;
+    pin[i] = 0u;
+  }
+  __threadfence();
+  __syncthreads();
+  const int nd = W.x.nDec[b];
+  const int n = W.beamN[b];
+  const Hyp* beam = (const Hyp*)W.beam + (size_t)(nd & 1) * W.B * W.K + (size_t)b * W.K;
+  for (int k = tid; k < n; k += kCrsOpThreads) {
+    const int sid = beam[k].sid, psid = beam[k].psid;
+    if (sid >= 0 && sid < hw) {
+      crsMark(inR, sid);
+    }
+    if (psid >= 0 && psid < hw) {
+      crsMark(pin, psid);
+    }
+  }
+  for (;;) {
+    __threadfence();
+    __syncthreads();
+    if (tid == 0) {
+      S.changed = 0;
+    }
+    __syncthreads();
+    bool any = false;
+    for (int id = tid; id < hw; id += kCrsOpThreads) {
+      const int p = sPar[id];
+      if (p >= 0 && !crsMarked(inR, id) && crsMarked(inR, p)) {
+        crsMark(inR, id);
+        any = true;
+      }
+    }
+    if (any) {
+      S.changed = 1;
+    }
+    __threadfence();
+    __syncthreads();
+    if (!S.changed) {
+      break;
+    }
+  }
+  /* 2. select: the dead ids in ascending order -- thread tid owns ids [tid * per, (tid + 1) * per) */
+  const int per = (hw + kCrsOpThreads - 1) / kCrsOpThreads;
+  const int lo = tid * per < hw ? tid * per : hw, hi = lo + per < hw ? lo + per : hw;
+  int mine = 0;
+  for (int id = lo; id < hi; ++id) {
+    mine += sPar[id] != -2 && !crsMarked(inR, id) && !crsMarked(pin, id) ? 1 : 0;
+  }
+  const int incl = waveInclusiveScan(mine);
+  if (laneId() == 63) {
+    S.wsum[waveId()] = incl;
+  }
+  __syncthreads();
+  int rank = incl - mine, dead = 0;
+  for (int w = 0; w < kCrsOpThreads / 64; ++w) {
+    rank += w < waveId() ? S.wsum[w] : 0;
+    dead += S.wsum[w];
+  }
+  const int nRel = dead < W.releaseCap ? dead : W.releaseCap;
+  /* 3. free: on the stack and into the caller's list */
+  int32_t* stack = W.x.sFree + sb + nFree;
+  for (int id = lo; id < hi && rank < nRel; ++id) {
+    if (sPar[id] != -2 && !crsMarked(inR, id) && !crsMarked(pin, id)) {
+      out[rank] = id;
+      stack[rank] = id;
+      sPar[id] = -2;
+      ++rank;
+    }
+  }
+  if (tid == 0) {
+    W.x.sFreeN[b] = nFree + nRel;
+    W.nReleased[b] = nRel;
+    if (W.nLive) {
+      W.nLive[b] = hw - nFree - nRel;
+    }
+  }
+  if (nRel == 0) {
+    return;
+  }
+  /* 4. rebuild: linear probing has no single-slot delete, so the table is cleared and the entries that stay -- neither
+   * the id nor its parent went -- are inserted again */
+  unsigned long long* sKey = W.sKey + (size_t)b * W.sSize;
+  int32_t* sVal = W.sVal + (size_t)b * W.sSize;
+  for (int i = tid; i < W.sSize; i += kCrsOpThreads) {
+    sKey[i] = ~0ull;
+  }
+  __threadfence();
+  __syncthreads();
+  const uint32_t sMask = (uint32_t)W.sSize - 1u;
+  for (int id = tid; id < hw; id += kCrsOpThreads) {
+    const int p = sPar[id];
+    if (p < 0) {
+      continue;
+    }
+    if ((int32_t)loadCoherent32((const uint32_t*)&sPar[p]) == -2) { /* (a parent's own entry may go meanwhile: -1, not -2) */
+      sPar[id] = -1;
+      continue;
+    }
+    const unsigned long long skey = s2lPair(p, sEdge[id]);
+    uint32_t slot = (uint32_t)s2lMix(skey) & sMask;
+    for (int probes = 0; probes < W.sSize; ++probes) { /* (sSize >= 2 sMax: a free slot always exists) */
+      if (atomCas64(&sKey[slot], ~0ull, skey) == ~0ull) {
+        sVal[slot] = id;
+        break;
+      }
+      slot = (slot + 1u) & sMask;
+    }
   }
 }
 

@@ -15,11 +15,17 @@ host, so a stream waits for the device once per chunk; `stream_no_best_ms_per_fr
 scores, then a copy of the tokens per stream).  A stream's LM-state table holds max_states ids, whatever the chunks
 bring, and stream_begin clears it: `stream_begin_ms` is its device time at --max-states (default K * T + 2, what the
 offline path would size) and `stream_begin_default_ms` at the default of 65 536 ids per stream.
-The medians of the append, prune and best kernels per call come from a separate run under
+`--collect-every n[,m..]` (off by default): the stream loop again with collect(--release-cap) after every n-th chunk,
+after the prune -- `stream_collect_ms_per_frame[n]`, `collect_added_ms_per_call[n]` = (that median - the plain stream's)
+* T / calls, and of the last of those runs the ids released in all and the most ids live in any stream after a
+collect.  (The LM rows here are a hash of the state id, so a recycled id reads the row it read before: the timing does
+not depend on it.)
+The medians of the append, prune, best and collect kernels per call come from a separate run under
 `rocprofv3 --kernel-trace --stats` (the program after `--`; --only stream keeps that run to the stream).
 
     python tools/bench_ctc_lm_rows_stream.py [--T 200] [--chunk 20] [--look-back 10] [--sets letters,word_piece]
                                              [--kinds lexfree,lexicon] [--only stream,offline] [--repeat 3]
+                                             [--collect-every 1,5] [--release-cap 1024]
 """
 import argparse
 import json
@@ -52,6 +58,8 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--max-states", type=int, default=0)
     ap.add_argument("--only", default="stream,offline")
+    ap.add_argument("--collect-every", default="")
+    ap.add_argument("--release-cap", type=int, default=1024)
     ap.add_argument("--sets", default="letters,word_piece")
     ap.add_argument("--kinds", default="lexfree,lexicon")
     a = ap.parse_args()
@@ -104,13 +112,18 @@ def main():
                     tok, src, state, n = dec.step(log_probs, lm_row_of=row_of(state))
                 dec.end(log_probs, lm_row_of=row_of(state))
 
-            def streamed(with_best=True):
+            def streamed(with_best=True, collect_every=0):
                 tok, src, state, n = dec.stream_begin(B, N, LB + CH + 2)
+                seen["released"], seen["live"] = [], []
                 for c in range(T // CH):
                     off = (np.arange(B, dtype=np.int64) * T + c * CH) * N
                     for _ in range(dec.append(None, chunk_T, offsets=off, device_ptr=em.data_ptr())):
                         tok, src, state, n = dec.step(log_probs, lm_row_of=row_of(state))
                     dec.prune(LB)
+                    if collect_every and (c + 1) % collect_every == 0:
+                        _, n_rel, n_live = dec.collect(a.release_cap)
+                        seen["released"].append(n_rel)
+                        seen["live"].append(n_live)
                     if with_best:
                         seen["best_len"] = len(dec.best(0, 0).tokens)
                     if with_best == "all" and c == 0:
@@ -141,12 +154,28 @@ def main():
                 out["best_all_streams_ms"] = seen.get("best_all_ms")
                 out["stream_begin_ms"] = timed(lambda: dec.stream_begin(B, N, LB + CH + 2), stream)
                 out["stream_begin_default_ms"] = begin_default
+                for ce in [int(x) for x in a.collect_every.split(",") if x]:
+                    streamed(True, ce)
+                    runs = [timed(lambda: streamed(True, ce), stream) / T for _ in range(a.repeat)]
+                    med = statistics.median(runs)
+                    out.setdefault("stream_collect_ms_per_frame", {})[ce] = {"median": med, "min": min(runs),
+                                                                             "max": max(runs)}
+                    calls = (T // CH) // ce
+                    out.setdefault("collect_added_ms_per_call", {})[ce] = \
+                        (med - out["stream_ms_per_frame"]["median"]) * T / max(calls, 1)
+                    stream.synchronize()
+                    out.setdefault("collect_released_total", {})[ce] = int(sum(int(r.sum()) for r in seen["released"]))
+                    out.setdefault("collect_max_live", {})[ce] = int(max(int(v.max()) for v in seen["live"]))
+                    out.setdefault("collect_max_released_one_stream", {})[ce] = \
+                        int(max(int(r.max()) for r in seen["released"]))
             if "offline" in only and "stream" in only:
                 out["ratio"] = out["stream_ms_per_frame"]["median"] / out["offline_ms_per_frame"]["median"]
                 out["ratio_no_best"] = out["stream_no_best_ms_per_frame"]["median"] / out["offline_ms_per_frame"]["median"]
             dec.close()
             print(json.dumps({"config": {"name": name, "kind": kind, "B": B, "K": K, "Kt": Kt, "N": N, "T": T,
-                                         "chunk": CH, "look_back": LB, "lm_width": W, "lm_table_rows": a.ctx}, **out}),
+                                         "chunk": CH, "look_back": LB, "lm_width": W, "lm_table_rows": a.ctx,
+                                         "max_states": a.max_states or K * T + 2, "release_cap": a.release_cap},
+                              **out}),
                   flush=True)
             lm.close()
             if trie is not None:
