@@ -654,6 +654,50 @@ FLTX_API int fltx_result_fetch_batch(fltx_decoder* dec, const int32_t** n_hyp, c
 FLTX_API int fltx_result_fetch_batch_compact(fltx_decoder* dec, const int32_t** n_hyp, const int32_t** length,
                                              const double** scores, const uint8_t** tokens_u8,
                                              const int32_t** words, const int64_t** offsets);
+/* ---- collapsed transcripts ------------------------------------------------ */
+/* What a caller wants of a CTC / ASG n-best is rarely its frame rows (T[b] + 2 tokens per hypothesis, a word row that is
+ * -1 except where a word ended) but the transcript: the tokens after CTC collapse, the frame at which each starts, the
+ * words and their frames.  These two calls collapse frame rows on the device (text_amd/csrc/fltx_transcript.h), so
+ * that only the transcript -- ten to a hundred times smaller -- crosses PCIe, or nothing at all.
+ *
+ * The rule, for one row tok[0 .. len) with an optional wrd[0 .. len) and a blank id (blank < 0: nothing is a blank):
+ *   position i is kept iff tok[i] >= 0, tok[i] != blank and (i == 0 or tok[i] != tok[i - 1]) -- the RAW previous
+ *   entry: a blank or a -1 between two equal tokens makes the second one a new token;
+ *   a kept position yields (tokens, timesteps) = (tok[i], i);
+ *   every position with wrd[i] >= 0 yields (words, word_timesteps, word_tok_end) = (wrd[i], i, kept positions <= i),
+ *   so tokens[word_tok_end[j - 1] .. word_tok_end[j]) of the row is the spelling that ended word j, with its leading
+ *   separators.
+ * (The host-side groupby / drop-blank / first-index rule.  In a decoder's rows entry 0 is the root's sil: the emission
+ * frame of a token is timestep - 1.)
+ *
+ * Row r's tokens / timesteps are at [tok_off[r], tok_off[r + 1]), its words / word_timesteps / word_tok_end at
+ * [word_off[r], word_off[r + 1]).  on_device == 0: the arrays are copied into pinned host buffers, one transfer per
+ * array.  on_device != 0: the pointers address HBM (in the order of the context's stream) and only the two totals
+ * cross PCIe.  The buffers belong to the context (fltx_collapse_rows) or the decoder (fltx_result_transcripts), grow
+ * as needed and stay valid until the next such call on it, or the next decode. */
+typedef struct fltx_transcripts {
+  int64_t n_rows;
+  const int64_t* row_first;      /* [B + 1] rows of utterance b: row_first[b] .. row_first[b+1]  (decoder call; NULL for fltx_collapse_rows) */
+  const double*  scores;         /* [B*K*3] as fltx_result_fetch_batch  (decoder call; NULL otherwise) */
+  const int64_t* tok_off;        /* [n_rows + 1] */
+  const int32_t* tokens;         /* [tok_off[n_rows]] */
+  const int32_t* timesteps;
+  const int64_t* word_off;       /* [n_rows + 1]; all 0 without a word row */
+  const int32_t* words, *word_timesteps, *word_tok_end;
+  int64_t n_tokens, n_words;     /* = tok_off[n_rows], word_off[n_rows]: the two totals, on the host either way */
+} fltx_transcripts;
+/* Any frame rows in HBM: row r = row_len[r] entries at element offset row_off[r] of tokens (and of words, which may be
+ * NULL); all four are device pointers.  n_rows == 0 or all lengths 0 give empty arrays; a negative row_len is
+ * FLTX_ERR_INVALID. */
+FLTX_API int fltx_collapse_rows(fltx_ctx* ctx, const int32_t* tokens, const int32_t* words, const int64_t* row_off,
+                                const int32_t* row_len, int64_t n_rows, int32_t blank, int32_t on_device,
+                                fltx_transcripts* out);
+/* The n-best of the last finished decode (fltx_decode_batch, or fltx_ctc_rows_end -- of a stream too): the first
+ * min(n_hyp[b], max_hyp) hypotheses of every utterance, best first, with the decoder's own blank (under the ASG
+ * criterion nothing is a blank); n_hyp / length and the errors of an utterance's status as fltx_result_fetch_batch_compact,
+ * token sets of any size.  FLTX_ERR_STATE without a finished decode and on the seq2seq kinds (their results are token
+ * strings already), FLTX_ERR_INVALID on max_hyp < 1.  The other fetch calls return what they return without it. */
+FLTX_API int fltx_result_transcripts(fltx_decoder* dec, int32_t max_hyp, int32_t on_device, fltx_transcripts* out);
 /* getBestHypothesis(lookBack) of stream b (LexiconFreeDecoder.cpp:188-194,
  * decoder/Utils.h:268-310): *length = 0 for an empty result. */
 FLTX_API int fltx_result_best(fltx_decoder* dec, int32_t b, int32_t look_back,

@@ -64,6 +64,48 @@ class S2sLexOptions(C.Structure):
     ]
 
 
+class Transcripts(C.Structure):
+    """fltx_transcripts (include/fltx.h)"""
+    _fields_ = [
+        ("n_rows", C.c_int64),
+        ("row_first", C.c_void_p),
+        ("scores", C.c_void_p),
+        ("tok_off", C.c_void_p),
+        ("tokens", C.c_void_p),
+        ("timesteps", C.c_void_p),
+        ("word_off", C.c_void_p),
+        ("words", C.c_void_p),
+        ("word_timesteps", C.c_void_p),
+        ("word_tok_end", C.c_void_p),
+        ("n_tokens", C.c_int64),
+        ("n_words", C.c_int64),
+    ]
+
+
+def _view(ptr, ctype, n):
+    """n elements at a host address as a NumPy array (no copy)"""
+    if n == 0 or not ptr:
+        return np.zeros(0, dtype=np.dtype(ctype))
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,))
+
+
+def _transcript_views(t, device):
+    """The arrays of a filled fltx_transcripts.  Host: NumPy views of the library's pinned buffers (valid until the next
+    call on the same owner).  device: the integer addresses, and the sizes n_tokens / n_words."""
+    n = int(t.n_rows)
+    if device:
+        return {"n_rows": n, "n_tokens": int(t.n_tokens), "n_words": int(t.n_words), "tok_off": t.tok_off, "tokens": t.tokens, "timesteps": t.timesteps,
+                "word_off": t.word_off, "words": t.words, "word_timesteps": t.word_timesteps,
+                "word_tok_end": t.word_tok_end}
+    tok_off = _view(t.tok_off, C.c_int64, n + 1)
+    word_off = _view(t.word_off, C.c_int64, n + 1)
+    nt, nw = int(t.n_tokens), int(t.n_words)
+    return {"n_rows": n, "n_tokens": nt, "n_words": nw, "tok_off": tok_off, "tokens": _view(t.tokens, C.c_int32, nt),
+            "timesteps": _view(t.timesteps, C.c_int32, nt), "word_off": word_off,
+            "words": _view(t.words, C.c_int32, nw), "word_timesteps": _view(t.word_timesteps, C.c_int32, nw),
+            "word_tok_end": _view(t.word_tok_end, C.c_int32, nw)}
+
+
 class FltxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("fltx error %d: %s" % (code, msg))
@@ -96,6 +138,7 @@ class Lib:
         "fltx_ctc_rows_decoder_create", "fltx_ctc_rows_lex_decoder_create", "fltx_ctc_rows_begin", "fltx_ctc_rows_step", "fltx_ctc_rows_end",
         "fltx_ctc_rows_stream_begin", "fltx_ctc_rows_stream_append", "fltx_ctc_rows_stream_prune",
         "fltx_ctc_rows_stream_frames_in_buffer", "fltx_ctc_rows_stream_collect",
+        "fltx_collapse_rows", "fltx_result_transcripts",
     ]
 
     def __init__(self, path=None):
@@ -189,6 +232,8 @@ class Lib:
             "fltx_ctc_rows_stream_prune": [vp, i32],
             "fltx_ctc_rows_stream_frames_in_buffer": [vp, i32, vp],
             "fltx_ctc_rows_stream_collect": [vp, i32, vp, vp, vp],
+            "fltx_collapse_rows": [vp, vp, vp, vp, vp, i64, i32, i32, C.POINTER(Transcripts)],
+            "fltx_result_transcripts": [vp, i32, i32, C.POINTER(Transcripts)],
         }
         for name, args in sig.items():
             fn = getattr(L, name)
@@ -252,6 +297,41 @@ class Context:
     @property
     def stream(self):
         return self.L.lib.fltx_ctx_stream(self.h)
+
+    def collapse_rows(self, tokens, words, row_off, row_len, blank, device=False, n_rows=None):
+        """fltx_collapse_rows: the collapsed transcripts of frame rows in HBM.  tokens (int32) / words (int32; None: no
+        word row) / row_off (int64) / row_len (int32) are each a device address (int) or a NumPy array, which is uploaded
+        first (a convenience for tests and small uses; it needs torch unless the library is the emulator, whose device
+        memory is host memory).  n_rows: the row count -- needed when row_len is an address, else len(row_len).
+        -> a dict of NumPy views of the context's pinned buffers (n_rows, n_tokens, n_words, tok_off, tokens, timesteps,
+        word_off, words, word_timesteps, word_tok_end), valid until the next call; with device=True the array keys hold
+        device addresses, n_tokens / n_words the sizes."""
+        if n_rows is None:
+            if not isinstance(row_len, np.ndarray):
+                raise TypeError("collapse_rows: n_rows is needed when row_len is a device address")
+            n_rows = len(row_len)
+        keep = []
+
+        def addr(a, dtype):
+            if a is None or isinstance(a, int):
+                return a
+            a = np.ascontiguousarray(a, dtype=dtype)
+            if "emulation" not in self.L.version() and a.size:
+                import torch
+                a = torch.from_numpy(a).to(torch.device("cuda", torch.cuda.current_device()))
+            keep.append(a)
+            return a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
+        ptrs = (addr(tokens, np.int32), addr(words, np.int32), addr(row_off, np.int64), addr(row_len, np.int32))
+        uploaded = any(not isinstance(k, np.ndarray) for k in keep)
+        if uploaded:  # (the uploads are done before the context's stream reads them)
+            import torch
+            torch.cuda.current_stream().synchronize()
+        t = Transcripts()
+        self.L.check(self.L.lib.fltx_collapse_rows(self.h, *ptrs, int(n_rows), int(blank), 1 if device else 0,
+                                                   C.byref(t)))
+        if device and uploaded:  # (the write kernel may still be reading the uploads, which go when this returns)
+            self.synchronize()
+        return _transcript_views(t, device)
 
     def close(self):
         if self.h:
@@ -578,6 +658,18 @@ _U8_TO_I32 = np.arange(256, dtype=np.int32)
 _U8_TO_I32[255] = -1  # (fltx_result_fetch_batch_compact: 0xFF = -1)
 
 
+class Transcript:
+    """One hypothesis after CTC collapse (BatchDecoder.transcripts_batch): tokens and the row index at which each starts
+    (the emission frame is timestep - 1), the words with the index at which each ended, and word_tok_end[j] = the tokens
+    up to and including word j's end -- tokens[word_tok_end[j - 1]:word_tok_end[j]] spells word j."""
+    __slots__ = ("score", "am", "lm", "tokens", "timesteps", "words", "word_timesteps", "word_tok_end")
+
+    def __init__(self, score, am, lm, tokens, timesteps, words, word_timesteps, word_tok_end):
+        self.score, self.am, self.lm = score, am, lm
+        self.tokens, self.timesteps = tokens, timesteps
+        self.words, self.word_timesteps, self.word_tok_end = words, word_timesteps, word_tok_end
+
+
 class _CompactHyp(Hyp):
     """A hypothesis of results_batch(): its token row stays the byte row the device packed until somebody reads it
     (an n-best of 50 x 1 002 frames is read in full by few callers; widening 12.8 M bytes per batch up front cost more
@@ -794,6 +886,39 @@ class BatchDecoder:
                 wb = None
             s3 = sc[b, :n].tolist()
             out.append([make(s3[i][0], s3[i][1], s3[i][2], tb[i], wb[i] if wb is not None else row) for i in range(n)])
+        return out
+
+    def transcripts(self, max_hyp=None, device=False):
+        """fltx_result_transcripts: the n-best of the last finished decode after CTC collapse, made on the device -- the
+        first min(n_hyp[b], max_hyp) hypotheses of every utterance, best first.  -> a dict: row_first [B + 1] (the rows
+        of utterance b are row_first[b] .. row_first[b + 1]), scores [B, K, 3], and per row r tokens / timesteps at
+        tok_off[r]:tok_off[r + 1], words / word_timesteps / word_tok_end at word_off[r]:word_off[r + 1] -- NumPy
+        views of the decoder's pinned buffers, valid until the next call or decode.  device=True: the arrays stay in
+        HBM; their keys hold integer addresses and n_tokens / n_words the sizes (row_first stays a host array)."""
+        K = int(self.options.beam_size)
+        t = Transcripts()
+        self._chk(self.L.lib.fltx_result_transcripts(self.h, K if max_hyp is None else int(max_hyp),
+                                                     1 if device else 0, C.byref(t)))
+        r = _transcript_views(t, device)
+        r["row_first"] = _view(t.row_first, C.c_int64, self.B + 1)
+        if device:
+            r["scores"] = t.scores
+        else:
+            r["scores"] = _view(t.scores, C.c_double, self.B * K * 3).reshape(self.B, K, 3)
+        return r
+
+    def transcripts_batch(self, max_hyp=None):
+        """[[Transcript]] for every utterance: the arrays of transcripts() copied once, sliced per hypothesis"""
+        r = self.transcripts(max_hyp)
+        first, to, wo = r["row_first"].tolist(), r["tok_off"].tolist(), r["word_off"].tolist()
+        tok, ts = r["tokens"].copy(), r["timesteps"].copy()
+        wrd, wts, wte = r["words"].copy(), r["word_timesteps"].copy(), r["word_tok_end"].copy()
+        out = []
+        for b in range(self.B):
+            s3 = r["scores"][b].tolist()
+            out.append([Transcript(s3[i][0], s3[i][1], s3[i][2], tok[to[q]:to[q + 1]], ts[to[q]:to[q + 1]],
+                                   wrd[wo[q]:wo[q + 1]], wts[wo[q]:wo[q + 1]], wte[wo[q]:wo[q + 1]])
+                        for i, q in enumerate(range(first[b], first[b + 1]))])
         return out
 
     def best(self, b, look_back=0, capacity=1 << 16):

@@ -34,6 +34,7 @@
 #include "fltx_ctc_rows.h"
 #include "fltx_ctc_rows_lex.h"
 #include "fltx_ctc_rows_stream.h"
+#include "fltx_transcript.h"
 
 using namespace fltx;
 
@@ -146,6 +147,13 @@ __global__ void __launch_bounds__(256) fltx_pack_results_kernel(PackParams Q) {
     }
   }
 }
+/* fltx_transcript.h: collapsed transcripts of frame rows -- count per row, offsets, write */
+__global__ void __launch_bounds__(kTrThreads) fltx_transcript_count_kernel(TrParams Q) { trCountRows(Q, nullptr); }
+__global__ void __launch_bounds__(kTrScanThreads) fltx_transcript_scan_kernel(TrParams Q) {
+  __shared__ __attribute__((aligned(16))) TrScanLds fltx_tr_scan_lds;
+  trScanRows(Q, (char*)&fltx_tr_scan_lds);
+}
+__global__ void __launch_bounds__(kTrThreads) fltx_transcript_write_kernel(TrParams Q) { trWriteRows(Q, nullptr); }
 /* fltx_s2s.h: the seq2seq step (front end, step), its start and its back-trace */
 __global__ void __launch_bounds__(256) fltx_s2s_tokbeam_kernel(S2sParams P) {
   __shared__ __attribute__((aligned(16))) S2sFrontLds fltx_s2s_front[4];
@@ -491,6 +499,28 @@ struct DBuf {
   }
 };
 
+/* fltx_collapse_rows / fltx_result_transcripts: one set of growing buffers per owner (context / decoder) */
+struct TrBufs {
+  DBuf meta;  /* totals[2] i64, tokOff[n + 1] i64, wordOff[n + 1] i64, nTok[n] i32, nWord[n] i32 */
+  DBuf desc;  /* rowOff[n] i64, rowLen[n] i32 (the decoder call's rows) */
+  DBuf tokens, timesteps, words, wordT, wordEnd;
+  HBuf hTotals, hDesc, hOff, hTokens, hTimesteps, hWords, hWordT, hWordEnd;
+  std::vector<int64_t> rowFirst;
+  /* "time_transcripts": HIP events around the three kernels (and around fltx_pack_results_kernel) */
+  int timed = 0;
+  float ms[4] = {0.0f, 0.0f, 0.0f, 0.0f}; /* count, scan, write; pack */
+#ifndef FLTX_EMU
+  hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  ~TrBufs() {
+    for (hipEvent_t e : ev) {
+      if (e) {
+        (void)hipEventDestroy(e);
+      }
+    }
+  }
+#endif
+};
+
 uint32_t nextPow2(uint64_t v) {
   uint64_t p = 1;
   while (p < v) {
@@ -510,6 +540,7 @@ struct fltx_ctx {
   int numCUs = 256; /* MI355X; read from the device at creation */
   Stream stream = nullptr;
   bool ownStream = false;
+  TrBufs tr; /* fltx_collapse_rows */
 };
 
 /* every entry point that allocates, copies or launches selects its context's device first:
@@ -758,6 +789,7 @@ struct fltx_decoder {
   DBuf tokens, words, prof, histS, bestLen, bestScores, bestTok, bestWrd;
   HBuf hTokens, hWords, hScores; /* fltx_result_fetch_batch */
   HBuf hTok8, hWordsC, hPackMeta;  /* fltx_result_fetch_batch_compact */
+  TrBufs tr;                       /* fltx_result_transcripts */
   HBuf hSync;                      /* syncResults */
   HBuf hStat;                      /* DecodeParams::statusHost */
   DBuf dTok8, dWordsC, dPackMeta;
@@ -1876,6 +1908,16 @@ int fltx_decoder_destroy(fltx_decoder* d) {
 }
 
 static int settlePendingLook(fltx_decoder* d); /* (defined after syncResults) */
+/* the fltx_decoder_get keys of TrBufs::ms -> its slot, -1: none of them */
+static int trTimedSlot(const char* key) {
+  static const char* const kKeys[4] = {"transcript_count_ns", "transcript_scan_ns", "transcript_write_ns", "pack_ns"};
+  for (int i = 0; i < 4; ++i) {
+    if (!strcmp(key, kKeys[i])) {
+      return i;
+    }
+  }
+  return -1;
+}
 int fltx_decoder_get(fltx_decoder* d, const char* key, int64_t* value) {
   if (!d || !key || !value) {
     return fail(FLTX_ERR_INVALID, "fltx_decoder_get: null argument");
@@ -1963,6 +2005,10 @@ int fltx_decoder_get(fltx_decoder* d, const char* key, int64_t* value) {
     *value = d->CAP2;
   } else if (!strcmp(key, "items")) {
     *value = d->itemCap;
+  } else if (trTimedSlot(key) >= 0) {
+    /* "time_transcripts": device time of the last fltx_result_transcripts' three kernels / of the last
+     * fltx_pack_results_kernel (HIP events around each; 0 when not timed or not launched) */
+    *value = (int64_t)((double)d->tr.ms[trTimedSlot(key)] * 1e6 + 0.5);
   } else if (!strcmp(key, "ws_bytes")) { /* d->wsBytes: the workspace bytes of one utterance that prepare() sized */
     *value = (int64_t)d->wsBytes;
   } else {
@@ -1985,6 +2031,10 @@ int fltx_decoder_set(fltx_decoder* d, const char* key, int64_t value) {
                                     "fltx_ctc_rows_lex_decoder_create) and a count >= 1");
     }
     d->s2s.maxStates = (int)value;
+    return FLTX_OK;
+  }
+  if (!strcmp(key, "time_transcripts")) { /* measurement: see fltx_decoder_get "transcript_count_ns" */
+    d->tr.timed = value ? 1 : 0;
     return FLTX_OK;
   }
   if (!strcmp(key, "compact_always")) {
@@ -4722,6 +4772,9 @@ int fltx_result_fetch_batch(fltx_decoder* d, const int32_t** nHyp, const int32_t
   return FLTX_OK;
 }
 
+static int trMark(TrBufs& T, int i, Stream st);
+static void trElapsed(TrBufs& T, int from, int to, int slot);
+
 int fltx_result_fetch_batch_compact(fltx_decoder* d, const int32_t** nHyp, const int32_t** length,
                                     const double** scores, const uint8_t** tokensU8, const int32_t** words,
                                     const int64_t** offsets) {
@@ -4800,8 +4853,14 @@ int fltx_result_fetch_batch_compact(fltx_decoder* d, const int32_t** nHyp, const
     Q.count = (const int32_t*)(d->dPackMeta.as<int64_t>() + B);
     Q.tok8 = d->dTok8.as<uint8_t>();
     Q.wordsOut = lex ? d->dWordsC.as<int32_t>() : nullptr;
+    if (trMark(d->tr, 0, st)) {
+      return fail(FLTX_ERR_HIP, "compact results: event failed");
+    }
     hipLaunchKernelGGL(fltx_pack_results_kernel, dim3(B), dim3(256), 0, st, Q);
     HIPCHK(hipGetLastError());
+    if (trMark(d->tr, 1, st)) {
+      return fail(FLTX_ERR_HIP, "compact results: event failed");
+    }
 #endif
     if ((!d->scoresFetched && devCopyD2H(d->hScores.p, d->outScores.p, 8 * 3 * (size_t)B * K, st)) ||
         (total > 0 && devCopyD2H(d->hTok8.p, d->dTok8.p, (size_t)total, st)) ||
@@ -4810,6 +4869,9 @@ int fltx_result_fetch_batch_compact(fltx_decoder* d, const int32_t** nHyp, const
     }
     d->scoresFetched = true;
     d->compactFetched = true;
+    if (d->tr.timed) {
+      trElapsed(d->tr, 0, 1, 3);
+    }
   }
   if (nHyp) {
     *nHyp = d->hNHyp.data();
@@ -6980,6 +7042,241 @@ static int crsResultBest(fltx_decoder* d, int32_t b, int32_t lookBack, double* s
   }
   if (words && !lex) {
     std::fill(words, words + len, -1); /* LexiconFreeDecoder.h:80-82 */
+  }
+  return FLTX_OK;
+}
+
+/* ---- collapsed transcripts (fltx_transcript.h) -------------------------------------------------------------------------- */
+static int trMark(TrBufs& T, int i, Stream st) {
+#ifndef FLTX_EMU
+  if (T.timed) {
+    if (!T.ev[i] && hipEventCreate(&T.ev[i]) != hipSuccess) {
+      return 1;
+    }
+    return hipEventRecord(T.ev[i], st) != hipSuccess;
+  }
+#else
+  (void)T, (void)i, (void)st;
+#endif
+  return 0;
+}
+/* ms[slot] = the time between two marks, once `to` has fired */
+static void trElapsed(TrBufs& T, int from, int to, int slot) {
+  T.ms[slot] = 0.0f;
+#ifndef FLTX_EMU
+  if (T.timed && T.ev[from] && T.ev[to] && hipEventSynchronize(T.ev[to]) == hipSuccess) {
+    (void)hipEventElapsedTime(&T.ms[slot], T.ev[from], T.ev[to]);
+  }
+#else
+  (void)from, (void)to;
+#endif
+}
+/* a copy home that waits for nothing: trRun waits once, behind the last */
+static int trCopyHome(void* h, const void* dv, size_t n, Stream st) {
+#ifndef FLTX_EMU
+  return hipMemcpyAsync(h, dv, n, hipMemcpyDeviceToHost, st) == hipSuccess ? 0 : 1;
+#else
+  (void)st;
+  memcpy(h, dv, n);
+  return 0;
+#endif
+}
+
+/* count, scan, (the host reads the two totals and sizes the output,) write; then the arrays home unless on_device.
+ * tok / wrd / rowOff / rowLen: device pointers.  Fills everything of *out but row_first and scores. */
+static int trRun(TrBufs& T, Stream st, const int32_t* tok, const int32_t* wrd, const int64_t* rowOff, const int32_t* rowLen,
+                 int64_t n, int32_t blank, int32_t onDevice, const char* what, fltx_transcripts* out) {
+  const size_t n1 = (size_t)n + 1;
+  const int64_t blocks = (n + kTrRowsPerBlock - 1) / kTrRowsPerBlock;
+  if (blocks > 0x7FFFFFFF) {
+    return fail(FLTX_ERR_RANGE, "%s: %lld rows exceed a launch", what, (long long)n);
+  }
+  if (T.meta.ensure(16 + 16 * n1 + 8 * (size_t)n, st, false) || T.hTotals.ensure(16)) {
+    return fail(FLTX_ERR_OOM, "%s: allocation failed", what);
+  }
+  TrParams Q;
+  memset(&Q, 0, sizeof(Q));
+  Q.tok = tok;
+  Q.wrd = wrd;
+  Q.rowOff = rowOff;
+  Q.rowLen = rowLen;
+  Q.nRows = n;
+  Q.blank = blank;
+  Q.totals = T.meta.as<int64_t>();
+  Q.tokOff = Q.totals + 2;
+  Q.wordOff = Q.tokOff + n1;
+  Q.nTok = (int32_t*)(Q.wordOff + n1);
+  Q.nWord = Q.nTok + n;
+  for (float& m : T.ms) {
+    m = 0.0f;
+  }
+  if (n > 0) {
+    if (trMark(T, 0, st)) {
+      return fail(FLTX_ERR_HIP, "%s: event failed", what);
+    }
+    S2S_LAUNCH(fltx_transcript_count_kernel, trCountRows, (int)blocks, kTrThreads, 0, st, Q);
+  }
+  if (trMark(T, 1, st)) {
+    return fail(FLTX_ERR_HIP, "%s: event failed", what);
+  }
+  S2S_LAUNCH(fltx_transcript_scan_kernel, trScanRows, 1, kTrScanThreads, sizeof(TrScanLds), st, Q);
+  if (trMark(T, 2, st)) {
+    return fail(FLTX_ERR_HIP, "%s: event failed", what);
+  }
+  /* the one look in between: 16 bytes, one wait */
+  const int64_t* tot = (const int64_t*)T.hTotals.p;
+  if (devCopyD2H(T.hTotals.p, Q.totals, 16, st)) {
+    return fail(FLTX_ERR_HIP, "%s: copy failed: %s", what, devErr());
+  }
+  if (tot[0] < 0) {
+    return fail(FLTX_ERR_INVALID, "%s: a row length is negative", what);
+  }
+  const size_t nt = (size_t)tot[0], nw = (size_t)tot[1];
+  const size_t bt = 4 * std::max<size_t>(nt, 1), bw = 4 * std::max<size_t>(nw, 1);
+  if (T.tokens.ensure(bt, st, false) || T.timesteps.ensure(bt, st, false) || T.words.ensure(bw, st, false) ||
+      T.wordT.ensure(bw, st, false) || T.wordEnd.ensure(bw, st, false)) {
+    return fail(FLTX_ERR_OOM, "%s: allocation failed", what);
+  }
+  Q.tokens = T.tokens.as<int32_t>();
+  Q.timesteps = T.timesteps.as<int32_t>();
+  Q.words = T.words.as<int32_t>();
+  Q.wordT = T.wordT.as<int32_t>();
+  Q.wordEnd = T.wordEnd.as<int32_t>();
+  const bool wrote = n > 0 && nt + nw > 0;
+  if (wrote) {
+    if (trMark(T, 3, st)) {
+      return fail(FLTX_ERR_HIP, "%s: event failed", what);
+    }
+    S2S_LAUNCH(fltx_transcript_write_kernel, trWriteRows, (int)blocks, kTrThreads, 0, st, Q);
+    if (trMark(T, 4, st)) {
+      return fail(FLTX_ERR_HIP, "%s: event failed", what);
+    }
+  }
+  out->n_rows = n;
+  out->n_tokens = (int64_t)nt;
+  out->n_words = (int64_t)nw;
+  if (onDevice) {
+    out->tok_off = Q.tokOff;
+    out->word_off = Q.wordOff;
+    out->tokens = Q.tokens;
+    out->timesteps = Q.timesteps;
+    out->words = Q.words;
+    out->word_timesteps = Q.wordT;
+    out->word_tok_end = Q.wordEnd;
+  } else {
+    if (T.hOff.ensure(16 * n1) || T.hTokens.ensure(bt) || T.hTimesteps.ensure(bt) || T.hWords.ensure(bw) ||
+        T.hWordT.ensure(bw) || T.hWordEnd.ensure(bw)) {
+      return fail(FLTX_ERR_OOM, "%s: pinned buffers: allocation failed", what);
+    }
+    if (trCopyHome(T.hOff.p, Q.tokOff, 16 * n1, st) || /* (tokOff and wordOff lie back to back) */
+        (nt && (trCopyHome(T.hTokens.p, Q.tokens, 4 * nt, st) || trCopyHome(T.hTimesteps.p, Q.timesteps, 4 * nt, st))) ||
+        (nw && (trCopyHome(T.hWords.p, Q.words, 4 * nw, st) || trCopyHome(T.hWordT.p, Q.wordT, 4 * nw, st) ||
+                trCopyHome(T.hWordEnd.p, Q.wordEnd, 4 * nw, st))) ||
+        devSync(st)) {
+      return fail(FLTX_ERR_HIP, "%s: copy failed: %s", what, devErr());
+    }
+    out->tok_off = (const int64_t*)T.hOff.p;
+    out->word_off = out->tok_off + n1;
+    out->tokens = (const int32_t*)T.hTokens.p;
+    out->timesteps = (const int32_t*)T.hTimesteps.p;
+    out->words = (const int32_t*)T.hWords.p;
+    out->word_timesteps = (const int32_t*)T.hWordT.p;
+    out->word_tok_end = (const int32_t*)T.hWordEnd.p;
+  }
+  if (T.timed) {
+    if (n > 0) {
+      trElapsed(T, 0, 1, 0);
+    }
+    trElapsed(T, 1, 2, 1);
+    if (wrote) {
+      trElapsed(T, 3, 4, 2);
+    }
+  }
+  return FLTX_OK;
+}
+
+int fltx_collapse_rows(fltx_ctx* ctx, const int32_t* tokens, const int32_t* words, const int64_t* rowOff,
+                       const int32_t* rowLen, int64_t nRows, int32_t blank, int32_t onDevice, fltx_transcripts* out) {
+  DeviceScope devScope(ctx);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  if (!ctx || !out || nRows < 0 || (nRows > 0 && (!tokens || !rowOff || !rowLen))) {
+    return fail(FLTX_ERR_INVALID, "fltx_collapse_rows: null ctx, out, tokens, row_off or row_len, or n_rows < 0");
+  }
+  memset(out, 0, sizeof(*out));
+  return trRun(ctx->tr, ctx->stream, tokens, words, rowOff, rowLen, nRows, blank, onDevice, "fltx_collapse_rows", out);
+}
+
+int fltx_result_transcripts(fltx_decoder* d, int32_t maxHyp, int32_t onDevice, fltx_transcripts* out) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  if (!d || !out || maxHyp < 1) {
+    return fail(FLTX_ERR_INVALID, "fltx_result_transcripts: null decoder or out, or max_hyp < 1");
+  }
+  if (isS2sKind(d->kind)) {
+    return fail(FLTX_ERR_STATE, "fltx_result_transcripts: a seq2seq decoder's results are token strings already");
+  }
+  if (!d->haveResults || !d->ended) {
+    return fail(FLTX_ERR_STATE, "fltx_result_transcripts: no finished decode");
+  }
+  int rc = syncResults(d);
+  if (rc) {
+    return rc;
+  }
+  const int B = d->B, K = d->opt.beam_size;
+  for (int b = 0; b < B; ++b) {
+    if ((rc = checkStatus(d, b))) {
+      return rc;
+    }
+  }
+  if (!d->backtraced && (rc = launchBacktrace(d))) {
+    return rc;
+  }
+  Stream st = d->ctx->stream;
+  TrBufs& T = d->tr;
+  const bool lex = kindHasWords(d->kind);
+  /* the rows: the first min(n_hyp[b], max_hyp) hypotheses of every utterance (counts as fltx_result_fetch_batch_compact) */
+  T.rowFirst.resize((size_t)B + 1);
+  int64_t n = 0;
+  for (int b = 0; b < B; ++b) {
+    T.rowFirst[b] = n;
+    n += std::min((lex && d->hFrame[b] < 1) ? 0 : d->hN[b], maxHyp); /* LexiconDecoder.cpp:276-280 */
+  }
+  T.rowFirst[B] = n;
+  const size_t nd = (size_t)std::max<int64_t>(n, 1);
+  if (T.hDesc.ensure(12 * nd) || T.desc.ensure(12 * nd, st, false) || (!onDevice && d->hScores.ensure(8 * 3 * (size_t)B * K))) {
+    return fail(FLTX_ERR_OOM, "fltx_result_transcripts: allocation failed");
+  }
+  int64_t* hOff = (int64_t*)T.hDesc.p;
+  int32_t* hLen = (int32_t*)(hOff + n);
+  for (int b = 0; b < B; ++b) {
+    const int32_t len = d->hFrame[b] + 1;
+    for (int64_t r = T.rowFirst[b]; r < T.rowFirst[b + 1]; ++r) {
+      hOff[r] = d->histOff[b] + (r - T.rowFirst[b]) * len;
+      hLen[r] = len;
+    }
+  }
+  if (n > 0 && devCopyH2D(T.desc.p, T.hDesc.p, 12 * (size_t)n, st)) { /* (pinned; the look at the totals waits behind it) */
+    return fail(FLTX_ERR_HIP, "fltx_result_transcripts: upload failed");
+  }
+  memset(out, 0, sizeof(*out));
+  const int32_t blank = d->opt.criterion == FLTX_CRITERION_CTC ? d->blank : -1;
+  if ((rc = trRun(T, st, d->tokens.as<int32_t>(), lex ? d->words.as<int32_t>() : nullptr, T.desc.as<int64_t>(),
+                  (const int32_t*)(T.desc.as<int64_t>() + n), n, blank, onDevice, "fltx_result_transcripts", out))) {
+    return rc;
+  }
+  out->row_first = T.rowFirst.data();
+  if (onDevice) {
+    out->scores = d->outScores.as<double>();
+  } else {
+    if (!d->scoresFetched && devCopyD2H(d->hScores.p, d->outScores.p, 8 * 3 * (size_t)B * K, st)) {
+      return fail(FLTX_ERR_HIP, "result copy failed: %s", devErr());
+    }
+    d->scoresFetched = true;
+    out->scores = (const double*)d->hScores.p;
   }
   return FLTX_OK;
 }
