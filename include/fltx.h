@@ -613,6 +613,46 @@ FLTX_API int fltx_ctc_rows_stream_prune(fltx_decoder* dec, int32_t look_back);
  * fltx_ctc_rows_begin and on any other kind; FLTX_ERR_INVALID on release_cap < 1 or NULL released / n_released. */
 FLTX_API int fltx_ctc_rows_stream_collect(fltx_decoder* dec, int32_t release_cap, int32_t* released,
                                           int32_t* n_released, int32_t* n_live);
+/* ---- the LM rows of a CTC rows decode, planned on the device ---------------------------------------------------------
+ * What connects the row lists to the caller's LM: which states of a list are new, the row of the LM-row store each
+ * gets, the row of its parent and the edge that advanced it, and the next step's lm_row_of.  Per decoder the planner
+ * keeps the LM row of every state id (-1: none yet, -2: dropped), a stack of free rows, a high-water mark and the
+ * lm_row_of of the call before.  Everything runs on the context's stream; nothing is copied to the host.  A decoder that
+ * never calls fltx_ctc_rows_plan_begin steps exactly as before.
+ *
+ * fltx_ctc_rows_plan_begin: after fltx_ctc_rows_begin or fltx_ctc_rows_stream_begin and before the first plan; sizes and
+ * clears the tables for that decode's B and state ids, for a store of row_capacity rows.  FLTX_ERR_INVALID on
+ * row_capacity < 1; FLTX_ERR_STATE outside a begun decode and on any other decoder kind.  The next begin ends planning
+ * until the next fltx_ctc_rows_plan_begin. */
+FLTX_API int fltx_ctc_rows_plan_begin(fltx_decoder* dec, int32_t row_capacity);
+/* Plan the list the last begin / step wrote (the four device lists, unchanged).  The outputs are caller-owned DEVICE
+ * buffers of B*K int32, counts of 4.  The result is that of this loop -- a function of the call sequence alone:
+ *   for b ascending, k < n_rows[b] ascending, s = next_state[b*K + k]:
+ *     s outside the decode's ids: lm_row_of = -1 (nothing is read through it);
+ *     s has no row yet -- a NEW state, listed once, at its lowest k (two rows of a list can carry the same new state):
+ *       r = the top of the free stack, else high_water++ while high_water < row_capacity, else the state is DROPPED;
+ *       a new state with a row is entry i = n_new++ of the lists:  new_row[i] = r,  new_parent_row[i] = the lm_row_of
+ *       the PREVIOUS plan gave row next_src_row (-1 for a root),  new_edge[i] = next_token (-1 for a root),
+ *       new_dec_row[i] = b*K + k;
+ *     lm_row_of[b*K + k] = the state's row, -1 for a dropped state.
+ *   rows k >= n_rows[b] and list entries >= n_new: -1.
+ *   counts = {n_new, high_water, rows on the free stack, states dropped since fltx_ctc_rows_plan_begin}.
+ * The caller runs its LM for the n_new listed states, writes row new_row[i] of its store and passes lm_row_of and
+ * n_lm_rows = row_capacity to the next fltx_ctc_rows_step / _end.  A dropped state stays dropped until its id is
+ * released: its rows read -1, so by the step's contract their LM entries are NaN, it keeps its blank / repeat / same-node
+ * candidates and makes no child state -- a parent always has a row.
+ * FLTX_ERR_INVALID on a NULL pointer.  FLTX_ERR_STATE without fltx_ctc_rows_plan_begin; when a step was queued whose list
+ * was never planned (the parent rows would be wrong); when this list has been planned already; and when a
+ * fltx_ctc_rows_stream_collect was queued without a fltx_ctc_rows_plan_release after it. */
+FLTX_API int fltx_ctc_rows_plan(fltx_decoder* dec, const int32_t* next_token, const int32_t* next_src_row,
+                                const int32_t* next_state, const int32_t* n_rows, int32_t* lm_row_of, int32_t* new_row,
+                                int32_t* new_parent_row, int32_t* new_edge, int32_t* new_dec_row, int32_t* counts);
+/* Tell the planner what a fltx_ctc_rows_stream_collect released: its DEVICE outputs released / n_released and its
+ * release_cap, unchanged, once per collect.  For each stream b ascending, each listed id in listed order: the id's row,
+ * if it has one, goes on the free stack; the id is unplanned again (a dropped id too).  FLTX_ERR_STATE outside a stream
+ * or without fltx_ctc_rows_plan_begin; FLTX_ERR_INVALID on NULL or release_cap < 1. */
+FLTX_API int fltx_ctc_rows_plan_release(fltx_decoder* dec, const int32_t* released, const int32_t* n_released,
+                                        int32_t release_cap);
 /* nDecodedFramesInBuffer of stream b (synchronises). */
 FLTX_API int fltx_ctc_rows_stream_frames_in_buffer(fltx_decoder* dec, int32_t b, int32_t* n);
 /* Inside such a stream fltx_result_best(dec, b, look_back, ...) is getBestHypothesis(lookBack): the ancestor's score,

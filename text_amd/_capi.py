@@ -138,6 +138,7 @@ class Lib:
         "fltx_ctc_rows_decoder_create", "fltx_ctc_rows_lex_decoder_create", "fltx_ctc_rows_begin", "fltx_ctc_rows_step", "fltx_ctc_rows_end",
         "fltx_ctc_rows_stream_begin", "fltx_ctc_rows_stream_append", "fltx_ctc_rows_stream_prune",
         "fltx_ctc_rows_stream_frames_in_buffer", "fltx_ctc_rows_stream_collect",
+        "fltx_ctc_rows_plan_begin", "fltx_ctc_rows_plan", "fltx_ctc_rows_plan_release",
         "fltx_collapse_rows", "fltx_result_transcripts",
     ]
 
@@ -232,6 +233,9 @@ class Lib:
             "fltx_ctc_rows_stream_prune": [vp, i32],
             "fltx_ctc_rows_stream_frames_in_buffer": [vp, i32, vp],
             "fltx_ctc_rows_stream_collect": [vp, i32, vp, vp, vp],
+            "fltx_ctc_rows_plan_begin": [vp, i32],
+            "fltx_ctc_rows_plan": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+            "fltx_ctc_rows_plan_release": [vp, vp, vp, i32],
             "fltx_collapse_rows": [vp, vp, vp, vp, vp, i64, i32, i32, C.POINTER(Transcripts)],
             "fltx_result_transcripts": [vp, i32, i32, C.POINTER(Transcripts)],
         }
@@ -1263,7 +1267,9 @@ class CtcRowsBatchDecoder(BatchDecoder):
     all from a callable.  Streams: stream_begin(B, N, max_frames), then append(chunk, T) and as many step() calls as it
     returns, prune(look_back), best(b, look_back) -- getBestHypothesis(lookBack), an empty result has no tokens --
     frames_in_buffer(b), and end(); decode_stream() drives those.  A stream's state ids stay stable until collect()
-    lists them as released: a released id may come back for another state."""
+    lists them as released: a released id may come back for another state.  plan_begin(row_capacity), plan(lists) and
+    plan_release(released, n_released) keep the LM rows of the state ids on the device (fltx_ctc_rows_plan_*);
+    decode_device() and decode_stream_device() are decode() and decode_stream() on those."""
 
     _rows = Seq2SeqBatchDecoder._rows
     _addr = staticmethod(Seq2SeqBatchDecoder._addr)
@@ -1377,6 +1383,96 @@ class CtcRowsBatchDecoder(BatchDecoder):
         n = C.c_int32(0)
         self._chk(self.L.lib.fltx_ctc_rows_stream_frames_in_buffer(self.h, int(b), C.addressof(n)))
         return n.value
+
+    # ---- the LM rows planned on the device (fltx_ctc_rows_plan_*) ----
+    def plan_begin(self, row_capacity):
+        """After begin() / stream_begin(): plan this decode's LM rows on the device, for a store of row_capacity rows."""
+        self._chk(self.L.lib.fltx_ctc_rows_plan_begin(self.h, int(row_capacity)))
+
+    def plan(self, tok, src, state, n):
+        """The lists of the last begin() / step() -> a CtcRowsPlan: lm_row_of for the next step() / end(), and the
+        states that are new in this list -- new_row (their rows of the store), new_parent_row (-1: a root), new_edge,
+        new_dec_row -- the first counts[0] entries of each; counts = (n_new, high_water, n_free, n_dropped).  All [B*K]
+        int32 ([4] for counts): torch tensors on the context's device, numpy arrays on the emulator library; nothing
+        is copied to the host."""
+        BK = self.B * int(self.options.beam_size)
+        if self._emu:
+            out = [np.empty(BK, np.int32) for _ in range(5)] + [np.empty(4, np.int32)]
+        else:
+            import torch
+            dev = torch.device("cuda", torch.cuda.current_device())
+            out = [torch.empty(BK, dtype=torch.int32, device=dev) for _ in range(5)] + \
+                [torch.empty(4, dtype=torch.int32, device=dev)]
+        self._chk(self.L.lib.fltx_ctc_rows_plan(self.h, *[self._addr(a) for a in (tok, src, state, n)],
+                                                *[self._addr(o) for o in out]))
+        return CtcRowsPlan(*out)
+
+    def plan_release(self, released, n_released):
+        """collect()'s `released` and `n_released`, unchanged, once per collect() and before the next plan(): the rows
+        of the released ids are free again."""
+        self._chk(self.L.lib.fltx_ctc_rows_plan_release(self.h, self._addr(released), self._addr(n_released),
+                                                        int(released.shape[1])))
+
+    def _planned(self, lists, lm_store, lm_new):
+        """plan the lists and have lm_new fill the new rows -> (the plan, its counts on the host: 16 bytes)"""
+        p = self.plan(*lists)
+        counts = p.counts if self._emu else p.counts.cpu()  # (waits for the stream: the one read per frame)
+        n_new = int(counts[0])
+        if n_new:
+            lm_new(p, n_new)
+        return p, counts
+
+    @staticmethod
+    def _store_full(counts):
+        if int(counts[3]) > 0:
+            raise RuntimeError("LM row store full: %d states got no row (row_capacity = lm_store.shape[0] is too "
+                               "small; a stream can collect_every)" % int(counts[3]))
+
+    def decode_device(self, emissions, T, N, lm_store, lm_new, *, offsets=None, device_ptr=None, lm_kind="log_probs"):
+        """decode() without the host in the loop: lm_store is the caller's [row_capacity, >= lm_width] array of LM rows
+        (a torch tensor on the context's device; numpy on the emulator library) and lm_new(p, n_new) writes its rows
+        p.new_row[:n_new] -- row i the LM's scores after the state of row p.new_parent_row[i] (-1: the start) advanced
+        by p.new_edge[i]; p.new_dec_row[i] // K is the utterance.  Per frame the host reads the plan's four counts and
+        nothing else.  RuntimeError "LM row store full" if a state got no row.  Returns results_batch()."""
+        lists = self.begin(emissions, T, N, offsets=offsets, device_ptr=device_ptr)
+        self.plan_begin(lm_store.shape[0])
+        for _ in range(int(self._T.max()) if self.B else 0):
+            p, _c = self._planned(lists, lm_store, lm_new)
+            lists = self.step(lm_store, lm_row_of=p.lm_row_of, lm_kind=lm_kind)
+        p, counts = self._planned(lists, lm_store, lm_new)
+        self.end(lm_store, lm_row_of=p.lm_row_of, lm_kind=lm_kind)
+        self._store_full(counts)
+        return self.results_batch()
+
+    def decode_stream_device(self, chunks, lm_store, lm_new, look_back=None, *, N=None, max_frames=None,
+                             collect_every=None, lm_kind="log_probs"):
+        """decode_stream() on decode_device()'s terms: chunks, look_back, N, max_frames and collect_every as there,
+        lm_store and lm_new as in decode_device.  A collect's released ids go straight to plan_release() on the
+        device: their rows of lm_store are handed out again.  Yields what decode_stream() yields."""
+        N = self.N if N is None else int(N)
+        chunks = iter(chunks)
+        first = next(chunks, None)
+        B = self.B if first is None else len(first[1])
+        lists = self.stream_begin(B, N, 4096 if max_frames is None else max_frames)
+        self.plan_begin(lm_store.shape[0])
+        p, counts = self._planned(lists, lm_store, lm_new)
+        chunk = first
+        n_chunks = 0
+        while chunk is not None:
+            for _ in range(self.append(chunk[0], chunk[1])):
+                lists = self.step(lm_store, lm_row_of=p.lm_row_of, lm_kind=lm_kind)
+                p, counts = self._planned(lists, lm_store, lm_new)
+            if look_back is not None:
+                self.prune(look_back)
+            n_chunks += 1
+            if collect_every is not None and n_chunks % int(collect_every) == 0:
+                rel, n_rel, _ = self.collect(min(self._stream_states, 1024))
+                self.plan_release(rel, n_rel)
+            yield [self.best(b) for b in range(B)]
+            chunk = next(chunks, None)
+        self.end(lm_store, lm_row_of=p.lm_row_of, lm_kind=lm_kind)
+        self._store_full(counts)
+        yield self.results_batch()
 
     def _lm_in(self, lm_scores, lm_row_of, lm_kind, lm_lse_out, lm_dtype):
         """-> the C arguments of the LM rows (and what must stay alive while the kernels read them)"""
@@ -1493,6 +1589,15 @@ class CtcRowsBatchDecoder(BatchDecoder):
             chunk = next(chunks, None)
         self.end(args[0], lm_row_of=args[1], lm_kind=lm_kind)
         yield self.results_batch()
+
+
+class CtcRowsPlan:
+    """What CtcRowsBatchDecoder.plan() returns (fltx_ctc_rows_plan's outputs)"""
+    __slots__ = ("lm_row_of", "new_row", "new_parent_row", "new_edge", "new_dec_row", "counts")
+
+    def __init__(self, lm_row_of, new_row, new_parent_row, new_edge, new_dec_row, counts):
+        self.lm_row_of, self.new_row, self.new_parent_row = lm_row_of, new_row, new_parent_row
+        self.new_edge, self.new_dec_row, self.counts = new_edge, new_dec_row, counts
 
 
 class _RowLister:

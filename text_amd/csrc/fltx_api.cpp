@@ -35,6 +35,7 @@
 #include "fltx_ctc_rows_lex.h"
 #include "fltx_ctc_rows_stream.h"
 #include "fltx_transcript.h"
+#include "fltx_ctc_rows_plan.h"
 
 using namespace fltx;
 
@@ -154,6 +155,24 @@ __global__ void __launch_bounds__(kTrScanThreads) fltx_transcript_scan_kernel(Tr
   trScanRows(Q, (char*)&fltx_tr_scan_lds);
 }
 __global__ void __launch_bounds__(kTrThreads) fltx_transcript_write_kernel(TrParams Q) { trWriteRows(Q, nullptr); }
+/* fltx_ctc_rows_plan.h: the LM rows of a CTC rows step's list -- new states marked and counted, rows assigned and the
+ * lists written; the same pair for a release */
+__global__ void __launch_bounds__(kCpThreads) fltx_ctc_rows_plan_mark_kernel(CpParams P) {
+  __shared__ CpLds lds;
+  cpMark(P, (char*)&lds);
+}
+__global__ void __launch_bounds__(kCpThreads) fltx_ctc_rows_plan_assign_kernel(CpParams P) {
+  __shared__ CpLds lds;
+  cpAssign(P, (char*)&lds);
+}
+__global__ void __launch_bounds__(kCpThreads) fltx_ctc_rows_plan_release_count_kernel(CpParams P) {
+  __shared__ CpLds lds;
+  cpReleaseCount(P, (char*)&lds);
+}
+__global__ void __launch_bounds__(kCpThreads) fltx_ctc_rows_plan_release_kernel(CpParams P) {
+  __shared__ CpLds lds;
+  cpRelease(P, (char*)&lds);
+}
 /* fltx_s2s.h: the seq2seq step (front end, step), its start and its back-trace */
 __global__ void __launch_bounds__(256) fltx_s2s_tokbeam_kernel(S2sParams P) {
   __shared__ __attribute__((aligned(16))) S2sFrontLds fltx_s2s_front[4];
@@ -857,6 +876,12 @@ struct fltx_decoder {
      * the mark bitsets [B][2][(sMax + 31) / 32] of tables too large for the kernel's LDS */
     DBuf crIds, crMarks;
     std::vector<int32_t> crBuf;
+    /* fltx_ctc_rows_plan_begin (fltx_ctc_rows_plan.h): rowOf, the free stack, meta and prev (two halves each, the one
+     * to read next in plMetaPar / plPrevPar), the counts and ranks between the two launches; and what the host knows of
+     * the call sequence -- the last list is unplanned, a list was never planned, collects without their release */
+    bool plOn = false, plFresh = false, plSkipped = false;
+    int plRowCap = 0, plMetaPar = 0, plPrevPar = 0, plCollects = 0;
+    DBuf plRowOf, plFree, plMeta, plPrev, plCnt, plRank;
   } s2s;
 };
 
@@ -6457,6 +6482,7 @@ static int crBegin(fltx_decoder* d, const char* what, const float* emissions, in
   d->s2s.crRing = ring;
   d->s2s.crBestLb = -1;
   d->s2s.crBuf.assign(stream ? (size_t)B : 0, 0);
+  d->s2s.plOn = false; /* (planning ends with the decode it was begun for: fltx_ctc_rows_plan_begin) */
   d->haveResults = false;
   d->ended = false;
   d->backtraced = false;
@@ -6666,6 +6692,8 @@ int fltx_ctc_rows_step(fltx_decoder* d, const void* lmScores, int32_t lmDtype, i
   if (!last) {
     ++d->s2s.t;
   }
+  d->s2s.plSkipped = d->s2s.plSkipped || d->s2s.plFresh; /* (the list before this one was never planned) */
+  d->s2s.plFresh = true;
   return FLTX_OK;
 }
 
@@ -6972,6 +7000,7 @@ int fltx_ctc_rows_stream_collect(fltx_decoder* d, int32_t releaseCap, int32_t* r
     S2S_LAUNCH(fltx_ctc_rows_stream_collect_kernel<false>, crsCollect<false>, d->B, kCrsOpThreads, sizeof(CrsCollectLds),
                d->ctx->stream, W);
   }
+  ++d->s2s.plCollects; /* (a planner must hear of it: fltx_ctc_rows_plan_release) */
   return FLTX_OK;
 }
 
@@ -7043,6 +7072,137 @@ static int crsResultBest(fltx_decoder* d, int32_t b, int32_t lookBack, double* s
   if (words && !lex) {
     std::fill(words, words + len, -1); /* LexiconFreeDecoder.h:80-82 */
   }
+  return FLTX_OK;
+}
+
+/* ---- the LM rows of the CTC rows decoders, planned on the device (fltx_ctc_rows_plan.h) ------------------------------- */
+static CpParams cpParams(fltx_decoder* d) {
+  CpParams P;
+  memset(&P, 0, sizeof(P));
+  P.B = d->B;
+  P.K = d->opt.beam_size;
+  P.sMax = d->s2s.sMax;
+  P.rowCap = d->s2s.plRowCap;
+  P.metaPar = d->s2s.plMetaPar;
+  P.prevPar = d->s2s.plPrevPar;
+  P.rowOf = d->s2s.plRowOf.as<int32_t>();
+  P.freeRows = d->s2s.plFree.as<int32_t>();
+  P.meta = d->s2s.plMeta.as<int32_t>();
+  P.prev = d->s2s.plPrev.as<int32_t>();
+  P.cnt = d->s2s.plCnt.as<int32_t>();
+  P.rank = d->s2s.plRank.as<int32_t>();
+  return P;
+}
+
+int fltx_ctc_rows_plan_begin(fltx_decoder* d, int32_t rowCapacity) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = crCheck(d, "fltx_ctc_rows_plan_begin");
+  if (rc) {
+    return rc;
+  }
+  if (!d->s2s.begun || d->ended) {
+    return fail(FLTX_ERR_STATE, "fltx_ctc_rows_plan_begin: fltx_ctc_rows_begin or fltx_ctc_rows_stream_begin first");
+  }
+  if (rowCapacity < 1) {
+    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_plan_begin: row_capacity = %d (>= 1)", rowCapacity);
+  }
+  Stream st = d->ctx->stream;
+  const size_t B = (size_t)d->B, BK = B * (size_t)d->opt.beam_size, nIds = B * (size_t)d->s2s.sMax;
+  if (d->s2s.plRowOf.ensure(4 * nIds, st, false) || d->s2s.plFree.ensure(4 * (size_t)rowCapacity, st, false) ||
+      d->s2s.plMeta.ensure(32, st, false) || d->s2s.plPrev.ensure(8 * BK, st, false) ||
+      d->s2s.plCnt.ensure(4 * B, st, false) || d->s2s.plRank.ensure(4 * BK, st, false)) {
+    return fail(FLTX_ERR_OOM, "fltx_ctc_rows_plan_begin: device allocation failed (B=%d, %d states, %d rows)", d->B,
+                d->s2s.sMax, rowCapacity);
+  }
+  if (devMemset(d->s2s.plRowOf.p, 0xFF, 4 * nIds, st) || devMemset(d->s2s.plPrev.p, 0xFF, 8 * BK, st) ||
+      devMemset(d->s2s.plMeta.p, 0, 32, st)) {
+    return fail(FLTX_ERR_HIP, "fltx_ctc_rows_plan_begin: clearing the tables failed");
+  }
+  d->s2s.plOn = true;
+  d->s2s.plFresh = true; /* the begin's list (or the last step's) */
+  d->s2s.plSkipped = false;
+  d->s2s.plRowCap = rowCapacity;
+  d->s2s.plMetaPar = 0;
+  d->s2s.plPrevPar = 0;
+  d->s2s.plCollects = 0;
+  return FLTX_OK;
+}
+
+int fltx_ctc_rows_plan(fltx_decoder* d, const int32_t* nextTok, const int32_t* nextSrc, const int32_t* nextState,
+                       const int32_t* nRows, int32_t* lmRowOf, int32_t* newRow, int32_t* newParentRow, int32_t* newEdge,
+                       int32_t* newDecRow, int32_t* counts) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = crCheck(d, "fltx_ctc_rows_plan");
+  if (rc) {
+    return rc;
+  }
+  if (!d->s2s.plOn) {
+    return fail(FLTX_ERR_STATE, "fltx_ctc_rows_plan: fltx_ctc_rows_plan_begin first (after the decode's begin)");
+  }
+  if (!nextTok || !nextSrc || !nextState || !nRows || !lmRowOf || !newRow || !newParentRow || !newEdge || !newDecRow ||
+      !counts) {
+    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_plan: null argument");
+  }
+  if (d->s2s.plSkipped) {
+    return fail(FLTX_ERR_STATE, "fltx_ctc_rows_plan: a step was queued whose list was never planned (the parent rows "
+                                "of this list are unknown)");
+  }
+  if (!d->s2s.plFresh) {
+    return fail(FLTX_ERR_STATE, "fltx_ctc_rows_plan: this list has been planned already");
+  }
+  if (d->s2s.plCollects > 0) {
+    return fail(FLTX_ERR_STATE, "fltx_ctc_rows_plan: fltx_ctc_rows_plan_release first (%d fltx_ctc_rows_stream_collect "
+                                "since the last plan)", d->s2s.plCollects);
+  }
+  CpParams P = cpParams(d);
+  P.tok = nextTok;
+  P.src = nextSrc;
+  P.state = nextState;
+  P.nRows = nRows;
+  P.lmRowOf = lmRowOf;
+  P.newRow = newRow;
+  P.newParent = newParentRow;
+  P.newEdge = newEdge;
+  P.newDecRow = newDecRow;
+  P.counts = counts;
+  S2S_LAUNCH(fltx_ctc_rows_plan_mark_kernel, cpMark, d->B, kCpThreads, sizeof(CpLds), d->ctx->stream, P);
+  S2S_LAUNCH(fltx_ctc_rows_plan_assign_kernel, cpAssign, d->B, kCpThreads, sizeof(CpLds), d->ctx->stream, P);
+  d->s2s.plMetaPar ^= 1;
+  d->s2s.plPrevPar ^= 1;
+  d->s2s.plFresh = false;
+  return FLTX_OK;
+}
+
+int fltx_ctc_rows_plan_release(fltx_decoder* d, const int32_t* released, const int32_t* nReleased, int32_t releaseCap) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = crsCheck(d, "fltx_ctc_rows_plan_release");
+  if (rc) {
+    return rc;
+  }
+  if (!d->s2s.plOn) {
+    return fail(FLTX_ERR_STATE, "fltx_ctc_rows_plan_release: fltx_ctc_rows_plan_begin first");
+  }
+  if (!released || !nReleased || releaseCap < 1) {
+    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_plan_release: release_cap = %d (>= 1), null released or n_released",
+                releaseCap);
+  }
+  CpParams P = cpParams(d);
+  P.released = released;
+  P.nReleased = nReleased;
+  P.releaseCap = releaseCap;
+  S2S_LAUNCH(fltx_ctc_rows_plan_release_count_kernel, cpReleaseCount, d->B, kCpThreads, sizeof(CpLds), d->ctx->stream, P);
+  S2S_LAUNCH(fltx_ctc_rows_plan_release_kernel, cpRelease, d->B, kCpThreads, sizeof(CpLds), d->ctx->stream, P);
+  d->s2s.plMetaPar ^= 1;
+  d->s2s.plCollects = std::max(0, d->s2s.plCollects - 1);
   return FLTX_OK;
 }
 

@@ -12,10 +12,17 @@ Times are device events on the decoder's stream around begin + T steps + end, af
 a Python object whose states are memoised children and whose scores are rows of the same table on the host.  That path
 asks Python one question per distinct (state, token), so it runs at --host-B utterances (default 4) of the same
 emissions; its figure is wall time per frame of that smaller batch.
+(p) --plan: the same table behind the device planner (fltx_ctc_rows_plan): every list is planned, the rows new_row of a
+bf16 store are filled from the table (the row the hash names for the new state's utterance and id) and the step reads
+the store through the planner's lm_row_of -- fixed-shape torch operations, nothing read on the host.  The store of a
+batch decode holds every state the decode can enter, B * (K * T + 2) rows; where that is more than --plan-store-gb the
+leg runs as B streams instead -- chunks of --plan-chunk frames, a collect and plan_release after each, max_states 1024
+per stream -- and says so ("mode").  --plan-read-counts: the leg reads the plan's counts every frame (16 bytes, a
+synchronisation) and fills the n_new listed rows only, as a caller with wide LM rows would.
 The per-kernel split comes from a separate run under `rocprofv3 --kernel-trace --stats` (the program after `--`; --only
 keeps that run to one leg).
 
-    python tools/bench_ctc_lm_rows.py [--T 200] [--warmup 1] [--only a,b,c] [--sets letters,word_piece]
+    python tools/bench_ctc_lm_rows.py [--T 200] [--warmup 1] [--only a,b,c] [--sets letters,word_piece] [--plan]
 """
 import argparse
 import json
@@ -73,8 +80,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--only", default="a,b,c")
     ap.add_argument("--sets", default="letters,word_piece")
+    ap.add_argument("--plan", action="store_true", help="add leg p: the device planner in the place of the hash recipe")
+    ap.add_argument("--plan-store-gb", type=float, default=8.0)
+    ap.add_argument("--plan-chunk", type=int, default=10)
+    ap.add_argument("--plan-read-counts", action="store_true",
+                    help="leg p reads the plan's counts (16 bytes, a synchronisation per frame) and fills n_new rows only")
     a = ap.parse_args()
-    only = set(a.only.split(","))
+    only = set(a.only.split(",")) | ({"p"} if a.plan else set())
     torch.manual_seed(0)
     stream = torch.cuda.Stream()  # (the default stream's handle is NULL: a context given NULL makes its own stream)
     torch.cuda.set_stream(stream)
@@ -114,6 +126,58 @@ def main():
             hyps = dec.results(0)
             extra[leg] = {"begin_ms": begin_ms, "hyps_utt0": len(hyps), "best_utt0": hyps[0].score}
             dec.close()
+        if "p" in only:
+            leg = "p_plan_bf16_log_probs"
+            dec = _capi.CtcRowsBatchDecoder(ctx, opts, lm, 0, 1)
+            batch = B * (K * T + 2) * W * 2 <= a.plan_store_gb * 2 ** 30
+            max_states = 1024
+            cap = B * (K * T + 2) if batch else B * max_states
+            store = torch.zeros(cap + 1, W, device="cuda", dtype=torch.bfloat16)  # (the last row takes the padding)
+            utt_of_row = (torch.arange(B * K, device="cuda", dtype=torch.int64) // K) * 97
+            last = {}
+
+            def planned(lists):
+                p = dec.plan(*lists)
+                n_new = int(p.counts[0]) if a.plan_read_counts else B * K
+                dr = p.new_dec_row[:n_new].to(torch.int64).clamp_min(0)
+                table_row = (lists[2].reshape(-1)[dr].to(torch.int64) * 2654435761 + utt_of_row[dr]) % a.ctx
+                nr = p.new_row[:n_new].to(torch.int64)
+                store[torch.where(nr >= 0, nr, torch.full_like(nr, cap))] = log_probs[table_row]
+                last["counts"] = p.counts
+                return p.lm_row_of
+
+            def plan_loop():
+                if batch:
+                    lists = dec.begin(None, Ts, N, device_ptr=em.data_ptr())
+                    dec.plan_begin(cap)
+                    for _ in range(T):
+                        lists = dec.step(store[:cap], lm_row_of=planned(lists))
+                    dec.end(store[:cap], lm_row_of=planned(lists))
+                    return
+                dec.set_max_states(max_states)
+                lists = dec.stream_begin(B, N, a.plan_chunk)
+                dec.plan_begin(cap)
+                ro = planned(lists)
+                for t0 in range(0, T, a.plan_chunk):  # (utterance-major emissions: a chunk is named by its offsets)
+                    n = min(a.plan_chunk, T - t0)
+                    off = (np.arange(B, dtype=np.int64) * T + t0) * N
+                    for _ in range(dec.append(None, np.full(B, n, np.int32), offsets=off, device_ptr=em.data_ptr())):
+                        ro = planned(dec.step(store[:cap], lm_row_of=ro))
+                    dec.prune(0)
+                    rel, n_rel, _ = dec.collect(max_states)
+                    dec.plan_release(rel, n_rel)
+                dec.end(store[:cap], lm_row_of=ro)
+            for _ in range(a.warmup):
+                plan_loop()
+            ms[leg] = timed(plan_loop, stream) / T
+            plan_loop()
+            hyps = dec.results(0)
+            counts = last["counts"].cpu().tolist()
+            extra[leg] = {"mode": "batch" if batch else "streams", "fill": "n_new rows" if a.plan_read_counts else "B*K rows",
+                          "row_capacity": cap, "high_water": counts[1],
+                          "n_dropped": counts[3], "hyps_utt0": len(hyps), "best_utt0": hyps[0].score}
+            dec.close()
+            del store
         if "c" in only:
             hb = a.host_B
             host = _capi.HostLM(TableLM(log_probs[:, :].float().cpu().numpy(), a.ctx))
