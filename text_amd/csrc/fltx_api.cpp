@@ -111,11 +111,12 @@ __global__ void __launch_bounds__(512) fltx_backtrace_kernel(BacktraceParams P) 
   extern __shared__ __attribute__((aligned(16))) char fltx_bt_smem[];
   backtraceUtterance(P, fltx_bt_smem);
 }
-/* packed records narrowed into LDS, the token tile resident (backtraceNarrow): 8 + 8 and 16 + 16 bits */
-template <typename RT>
-__global__ void __launch_bounds__(512) fltx_backtrace_narrow_kernel(BacktraceParams P) {
+/* packed records narrowed into LDS, the token tile resident (backtraceNarrow): 8 + 8 and 16 + 16 bits; PW = every wave
+ * walks a stretch of each chunk from every slot and the paths are composed (K <= 64), else one walk per hypothesis */
+template <typename RT, bool PW>
+__global__ void __launch_bounds__(512, 4) fltx_backtrace_narrow_kernel(BacktraceParams P) {
   extern __shared__ __attribute__((aligned(16))) char fltx_btn_smem[];
-  backtraceNarrow<RT>(P, fltx_btn_smem);
+  backtraceNarrow<RT, PW>(P, fltx_btn_smem);
 }
 __global__ void __launch_bounds__(64) fltx_snapshot_kernel(SnapParams Q) {
   const int b = Q.map ? Q.map[blockIdx.x] : (int)blockIdx.x;
@@ -730,6 +731,11 @@ struct fltx_decoder {
   int ylane = 0, noYlane = 0, ylaneLm = 0, ylaneRounds = 0, ylaneTpw = 0; /* ylane: lane groups of fltx_ylane.h (0 = not used) */
   int btLdsKb = 0;
   int btNarrow = 0, btChunk = 0, btStretch = 0; /* fltx_decoder_get "bt_record_bytes", "bt_chunk_frames", "bt_stretch_frames" */
+  int btThreads = 0;    /* "bt_threads": threads of a back-trace workgroup (0: 512; the emulator: one wave; never fewer than the beam's slots) */
+  int btWalkAsked = -1; /* "bt_walk_waves" (set): 0 / 1 = the serial walk, else the parallel walk where it applies */
+  int btWalkWaves = 0;  /* "bt_walk_waves" (get): waves that walked the chunks of the last back-trace (1 = the serial walk) */
+  bool btProfile = false; /* "bt_profile": shader-clock marks of the narrow back-trace (btProf, kBtProfMarks per utterance) */
+  DBuf btProf;
   int streamTotalFrames = 0; /* frames a stream will decode in all (sizes its LM-state id tables), 0 = default */
   /* stream chunks of the lexicon-free decoder on the lane = LM state engine (fltx_slane.h, ST): list positions per
    * token wave (0 = not used) and threads; begin / end / prune / best stay the lane-per-slot engine's */
@@ -1943,6 +1949,51 @@ static int trTimedSlot(const char* key) {
   }
   return -1;
 }
+/* fltx_decoder_get "bt_prof_<what>" after a batch decoded with "bt_profile" = 1: shader clocks of the last narrow
+ * back-trace summed over the utterances that took it -- copy0 (the first chunk into LDS), walk (the marking wave's own
+ * share of the walk loop: walking, composing, copying), wait (its barrier waits in that loop), store (the widened token
+ * rows), fetch0 (the first emission stretch), score (the score loop), total; utts = utterances counted */
+static int btProfileGet(fltx_decoder* d, const char* what, int64_t* value) {
+  if (!d->btProfile || !d->btProf.p || !d->backtraced) {
+    return fail(FLTX_ERR_STATE, "no back-trace profile: fltx_decoder_set(dec, \"bt_profile\", 1) before the batch");
+  }
+  DeviceScope devScope(d->ctx);
+  std::vector<unsigned long long> h((size_t)kBtProfMarks * d->B);
+  if (devCopyD2H(h.data(), d->btProf.p, 8 * h.size(), d->ctx->stream)) {
+    return fail(FLTX_ERR_HIP, "profile copy failed");
+  }
+  int64_t sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int b = 0; b < d->B; ++b) {
+    const unsigned long long* m = h.data() + (size_t)b * kBtProfMarks;
+    if (!m[1]) {
+      continue; /* (not a narrow back-trace: no marks) */
+    }
+    sum[0] += (int64_t)(m[1] - m[0]);
+    unsigned long long prev = m[1];
+    for (int c = 0; c < (int)m[6]; ++c) {
+      sum[1] += (int64_t)(m[8 + 2 * c] - prev);
+      sum[2] += (int64_t)(m[9 + 2 * c] - m[8 + 2 * c]);
+      prev = m[9 + 2 * c];
+    }
+    sum[1] += (int64_t)(m[2] - prev); /* (the word rows of the last chunk; chunks beyond the marked ones) */
+    sum[3] += (int64_t)(m[3] - m[2]);
+    if (m[5]) {
+      sum[4] += (int64_t)(m[4] - m[3]);
+      sum[5] += (int64_t)(m[5] - m[4]);
+    }
+    sum[6] += (int64_t)((m[5] ? m[5] : m[3]) - m[0]);
+    sum[7] += 1;
+  }
+  static const char* const kNames[8] = {"copy0", "walk", "wait", "store", "fetch0", "score", "total", "utts"};
+  for (int i = 0; i < 8; ++i) {
+    if (!strcmp(what, kNames[i])) {
+      *value = sum[i];
+      return FLTX_OK;
+    }
+  }
+  return fail(FLTX_ERR_INVALID, "fltx_decoder_get: unknown key bt_prof_%s", what);
+}
+
 int fltx_decoder_get(fltx_decoder* d, const char* key, int64_t* value) {
   if (!d || !key || !value) {
     return fail(FLTX_ERR_INVALID, "fltx_decoder_get: null argument");
@@ -2003,6 +2054,13 @@ int fltx_decoder_get(fltx_decoder* d, const char* key, int64_t* value) {
     *value = d->btChunk;
   } else if (!strcmp(key, "bt_stretch_frames")) { /* ... frames per stretch of emission rows in LDS while the scores are re-added */
     *value = d->btStretch;
+  } else if (!strcmp(key, "bt_walk_waves")) { /* ... waves that walked its chunks: 1 = one walk per hypothesis, more = every wave walked
+                                                  a stretch of each chunk from every slot and the paths were composed */
+    *value = d->btWalkWaves;
+  } else if (!strcmp(key, "bt_threads")) {
+    *value = d->btThreads;
+  } else if (!strncmp(key, "bt_prof_", 8)) { /* "bt_profile": shader clocks of the last narrow back-trace, summed over the utterances */
+    return btProfileGet(d, key + 8, value);
   } else if (!strcmp(key, "why_not_lane")) { /* FLTX_WHY_* (include/fltx.h): why the last call did not start on a lane engine */
     *value = d->whyFirst;
   } else if (!strcmp(key, "lane_groups")) { /* lane groups of the lane = LM state engine: 1 = fltx_slane.h, 2 / 4 / 8 = fltx_mlane.h;
@@ -2142,6 +2200,21 @@ int fltx_decoder_set(fltx_decoder* d, const char* key, int64_t value) {
   }
   if (!strcmp(key, "stream_defer")) { /* 0: fltx_stream_step waits for its chunk and decodes it again there if it must */
     d->deferRedo = value ? 1 : 0;
+    return FLTX_OK;
+  }
+  if (!strcmp(key, "bt_threads")) { /* threads of a back-trace workgroup: 64 .. 512 in whole waves, 0 = the default */
+    if (value != 0 && (value < 64 || value > 512 || value % 64 != 0)) {
+      return fail(FLTX_ERR_INVALID, "bt_threads must be 0 or a multiple of 64 up to 512");
+    }
+    d->btThreads = (int)value;
+    return FLTX_OK;
+  }
+  if (!strcmp(key, "bt_walk_waves")) { /* 0 / 1: the narrow back-trace keeps one walk per hypothesis (A/B runs, tests) */
+    d->btWalkAsked = (value == 0 || value == 1) ? 1 : -1;
+    return FLTX_OK;
+  }
+  if (!strcmp(key, "bt_profile")) { /* phase marks of the narrow back-trace: fltx_decoder_get "bt_prof_*" */
+    d->btProfile = value != 0;
     return FLTX_OK;
   }
   if (!strcmp(key, "bt_lds_kb")) { /* LDS the back-trace kernel stages history chunks in (0: 144 KB) */
@@ -3498,10 +3571,13 @@ int launchBacktrace(fltx_decoder* d) {
   Q.nbest = 0;
   /* frames per LDS chunk: two record buffers in ({parent, token} 8 B, word 4 B) + token and word tiles out */
 #ifdef FLTX_EMU
-  const int btThreads = std::min(512, std::max(64, (d->opt.beam_size + 63) / 64 * 64)); /* (the emitting-model pass is one thread per hypothesis) */
+  const int btAsked = d->btThreads ? d->btThreads : 64;
 #else
-  const int btThreads = 512;
+  const int btAsked = d->btThreads ? d->btThreads : 512;
 #endif
+  /* (the score passes are one thread per hypothesis: a workgroup never has fewer threads than the beam has slots,
+   * whatever "bt_threads" asks for) */
+  const int btThreads = std::min(512, std::max(btAsked, (d->opt.beam_size + 63) / 64 * 64));
   const size_t perFrame = (size_t)Q.K * (2 * (8 + (d->kind == FLTX_DECODER_LEXICON ? 4 : 0)) + 8);
   /* 140 KB: leaves a CU room for a 16 KB decode workgroup of the next batch beside a back-trace workgroup */
   size_t btBudget = 0;
@@ -3551,6 +3627,7 @@ int launchBacktrace(fltx_decoder* d) {
    * 8 + 8 bits when slots and tokens both fit a byte beside the all-ones "none", 16 + 16 otherwise.  A budget that
    * holds no tile with chunks of 8 frames keeps backtraceUtterance (long utterances, big beams). */
   int narrow = 0; /* bytes of a narrowed record: 2, 4, or 0 = backtraceUtterance */
+  int walkWaves = 1; /* waves that walk a chunk: 1 = one walk per hypothesis */
   if (d->batchPacked && F > 0 && Q.K <= btThreads) {
     const bool byteRec = d->packedBits <= 8 && Q.packedTokMask == 0xFF && d->N <= 255;
     const bool wordRec = d->packedBits <= 16 && d->N <= 65535;
@@ -3567,7 +3644,35 @@ int launchBacktrace(fltx_decoder* d) {
     const size_t perEm = 2 * 4 * (size_t)d->N;
     const size_t npF = std::min<size_t>(room / perWalk, std::max<size_t>(row, 8));
     const size_t npFe = Q.amGather ? (size_t)1 << 20 : (room > trBytes ? std::min<size_t>((room - trBytes) / perEm, std::max<size_t>(row, 8)) : 0);
-    if ((byteRec || wordRec) && row > 0 && row < (1u << 24) && npF >= 8 && npFe >= 8) {
+    /* The parallel walk (K <= 64: a lane per slot; two waves or more): ONE chunk buffer, the waves' exit maps beside
+     * it, and between the tile and all that the entry map [chunk][wave][K], which the score pass still reads.  The
+     * chunk keeps the length the double-buffered walk has (short chunks cost the parallel walk a barrier, not a
+     * serial stretch), so the buffer it no longer doubles pays for the maps; where they do not fit, and for beams
+     * beyond 64 -- their walk is already spread over K / 64 waves, and they are not where the time is -- the walk
+     * stays serial. */
+    const size_t nW = (size_t)btThreads / 64;
+    if ((byteRec || wordRec) && Q.K <= 64 && nW >= 2 && d->btWalkAsked != 1 && row > 0 && row < (1u << 24) && npF >= 8) {
+      /* (the records of a chunk, rounded up to 16 bytes so that the int32 words behind them stay aligned) */
+      const size_t pwChunk = (((size_t)Q.K * npF * rec + 15) & ~(size_t)15) + (lexRec ? (size_t)Q.K * npF * (4 + 4) : 0);
+      const size_t exitB = (nW * Q.K + 15) & ~(size_t)15;
+      const size_t ent = ((size_t)Q.K * nW * ((row + npF - 1) / npF) + 15) & ~(size_t)15;
+      const size_t roomE = room > ent ? room - ent : 0;
+      /* (a stretch holds its tokens by hypothesis as well, double buffered like its emission rows) */
+      const size_t perEmPw = (Q.amGather ? 0 : perEm) + 2 * (size_t)Q.K * tokB;
+      const size_t pwFe = roomE > trBytes ? std::min<size_t>((roomE - trBytes) / perEmPw, std::max<size_t>(row, 8)) : 0;
+      if (ent + exitB + pwChunk <= room && pwFe >= 8) {
+        narrow = (int)rec;
+        walkWaves = (int)nW;
+        Q.npRow = (int32_t)row;
+        Q.npF = (int32_t)npF;
+        Q.npFe = (int32_t)pwFe;
+        Q.npWaves = (int32_t)nW;
+        Q.npEntry = (int32_t)tile;
+        Q.npScratch = (int32_t)(tile + ent);
+        btLds = std::max(btLds, tile + ent + std::max(exitB + pwChunk, trBytes + pwFe * perEmPw) + 16);
+      }
+    }
+    if (!narrow && (byteRec || wordRec) && row > 0 && row < (1u << 24) && npF >= 8 && npFe >= 8) {
       narrow = (int)rec;
       Q.npRow = (int32_t)row;
       Q.npF = (int32_t)npF;
@@ -3576,21 +3681,35 @@ int launchBacktrace(fltx_decoder* d) {
       btLds = std::max(btLds, tile + std::max(npF * perWalk, Q.amGather ? (size_t)0 : trBytes + npFe * perEm) + 16);
     }
   }
+  if (narrow && d->btProfile) {
+    if (d->btProf.ensure(8 * (size_t)kBtProfMarks * d->B, st, true)) {
+      return fail(FLTX_ERR_OOM, "back-trace profile allocation failed");
+    }
+    devMemset(d->btProf.p, 0, 8 * (size_t)kBtProfMarks * d->B, st);
+    Q.btProf = d->btProf.as<unsigned long long>();
+  }
+  d->btWalkWaves = walkWaves;
   d->btNarrow = narrow;
   d->btChunk = narrow ? Q.npF : F;
   d->btStretch = narrow ? (Q.amGather ? 0 : Q.npFe) : (d->batchPacked && !Q.amGather ? F : 0);
 #ifdef FLTX_EMU
   const BacktraceParams* qq = &Q;
-  if (narrow == 2) {
-    emuLaunch(d->B, btThreads, btLds, [qq](char* smem) { backtraceNarrow<uint16_t>(*qq, smem); });
+  if (narrow == 2 && walkWaves > 1) {
+    emuLaunch(d->B, btThreads, btLds, [qq](char* smem) { backtraceNarrow<uint16_t, true>(*qq, smem); });
+  } else if (narrow == 4 && walkWaves > 1) {
+    emuLaunch(d->B, btThreads, btLds, [qq](char* smem) { backtraceNarrow<uint32_t, true>(*qq, smem); });
+  } else if (narrow == 2) {
+    emuLaunch(d->B, btThreads, btLds, [qq](char* smem) { backtraceNarrow<uint16_t, false>(*qq, smem); });
   } else if (narrow == 4) {
-    emuLaunch(d->B, btThreads, btLds, [qq](char* smem) { backtraceNarrow<uint32_t>(*qq, smem); });
+    emuLaunch(d->B, btThreads, btLds, [qq](char* smem) { backtraceNarrow<uint32_t, false>(*qq, smem); });
   } else {
     emuLaunch(d->B, btThreads, btLds, [qq](char* smem) { backtraceUtterance(*qq, smem); });
   }
 #else
-  const void* btFn = narrow == 2   ? (const void*)fltx_backtrace_narrow_kernel<uint16_t>
-                     : narrow == 4 ? (const void*)fltx_backtrace_narrow_kernel<uint32_t>
+  const void* btFn = narrow == 2   ? (walkWaves > 1 ? (const void*)fltx_backtrace_narrow_kernel<uint16_t, true>
+                                                   : (const void*)fltx_backtrace_narrow_kernel<uint16_t, false>)
+                     : narrow == 4 ? (walkWaves > 1 ? (const void*)fltx_backtrace_narrow_kernel<uint32_t, true>
+                                                   : (const void*)fltx_backtrace_narrow_kernel<uint32_t, false>)
                                    : (const void*)fltx_backtrace_kernel;
   int rcLds = raiseMaxLdsOnce(d, 1, btFn, btLds);
   if (rcLds) {

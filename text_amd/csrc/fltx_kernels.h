@@ -3650,8 +3650,24 @@ struct BacktraceParams {
   int32_t npRow;         /* elements per tile row: no utterance of the batch has more history rows */
   int32_t npF;           /* frames per narrowed record chunk */
   int32_t npFe;          /* frames per stretch of emission rows */
-  int32_t npScratch;     /* byte offset of the chunks behind the tile */
+  int32_t npScratch;     /* byte offset of the chunks behind the tile (and the entry map) */
+  /* the parallel walk (backtraceNarrow<RT, true>, K <= 64): every wave walks its own npF / npWaves frames of a chunk */
+  int32_t npWaves;       /* waves of the workgroup, each with ceil(npF / npWaves) frames of a chunk; the serial walk ignores it */
+  int32_t npEntry;       /* byte offset of the entry map [sub-stretch][K] behind the tile */
+  unsigned long long* btProf; /* "bt_profile": kBtProfMarks shader-clock marks per utterance, or null */
 };
+
+/* marks of "bt_profile" (thread 0 of an utterance's workgroup, raw shader clocks, reduced by the host): */
+constexpr int kBtProfChunks = 28; /* chunks with marks of their own (the rest of a longer walk falls between two marks) */
+constexpr int kBtProfMarks = 8 + 2 * kBtProfChunks;
+/* [0] begin  [1] first chunk in LDS  [2] walk done  [3] token rows stored  [4] first emission stretch in LDS
+ * [5] scores added  [6] chunks marked  [8 + 2c] chunk c walked (composed) by this wave  [9 + 2c] ... and by every wave */
+#define FLTX_BT_MARK(i)                                                            \
+  do {                                                                             \
+    if (P.btProf && tid == 0) {                                                    \
+      P.btProf[(size_t)b * kBtProfMarks + (i)] = devClock();                       \
+    }                                                                              \
+  } while (0)
 
 /* A parent-pointer walk is a chain of T dependent loads; straight from HBM that
  * is T x ~1 us per hypothesis and the token rows come out as strided 4-byte
@@ -3934,6 +3950,17 @@ FLTX_DEV void backtraceUtterance(const BacktraceParams& P, char* smem) {
  *   score  oldest frame first out of the SAME tile (the token rows are never read back from HBM), in the order and
  *          arithmetic of backtraceUtterance; the emission rows of stretch c + 1 (npFe frames) arrive through the
  *          idle waves while stretch c is added, so no stretch begins with an exposed round trip.
+ * PW (the parallel walk, K <= 64, two waves or more): the walk above is one wave following len dependent LDS reads
+ * while the others copy.  Instead every wave both copies and walks: chunk c (npF frames, ONE buffer) is cut
+ * into nW sub-stretches of S = ceil(npF / nW) frames (the last ones shorter, or empty), wave w walks its own from EVERY slot at once -- lane s starts at slot s of the
+ * sub-stretch's newest frame, drops its tokens into tile row s (the tile is then addressed by entry slot of the
+ * sub-stretch, not by hypothesis) and leaves the slot it arrives at in exitOf[w][s] -- and hypothesis k is composed
+ * through the maps, newest sub-stretch first: entry[sub][k] = cur; cur = exitOf[w][cur], one dependent read per
+ * sub-stretch instead of one per frame.  The next chunk's records are loaded into registers before the walk and
+ * narrowed into the buffer after it.  Whatever reads "token (word) of hypothesis k at frame j" goes through
+ * entry[sub-stretch of j][k]: a gather on the way out, since hypotheses share entry slots.  A lane that starts from a slot
+ * with no live record walks whatever the workspace holds there (an earlier batch's records): its parent is clamped to
+ * K, so it stays inside the chunk and its own tile row, and no hypothesis composes onto it.
  * The host picks the variant and checks that tile + chunks fit the budget (launchBacktrace); an utterance with plain
  * records (decoded again on the generic engine), or longer than the tile's rows, takes backtraceUtterance. */
 template <typename RT>
@@ -3947,11 +3974,12 @@ struct BtNarrow<uint32_t> {
   typedef uint16_t Tok;
 };
 
-template <typename RT>
+template <typename RT, bool PW>
 FLTX_DEV void backtraceNarrow(const BacktraceParams& P, char* smem) {
   typedef typename BtNarrow<RT>::Tok TT;
   constexpr int HB = (int)sizeof(RT) * 4;    /* bits of each half */
   constexpr uint32_t NONE = (1u << HB) - 1u; /* no parent; a pruned row's token */
+  constexpr uint32_t NOROW = 0xFFu;          /* entry / exit maps (PW): no record */
   const int b = (int)blockIdx.x;
   const int ff = P.uttFrame[b];
   const int len = ff + 1;
@@ -3961,6 +3989,7 @@ FLTX_DEV void backtraceNarrow(const BacktraceParams& P, char* smem) {
     return;
   }
   const int W = (int)blockDim.x, tid = (int)threadIdx.x;
+  FLTX_BT_MARK(0);
   int nh = P.uttNBeam[b];
   if (P.nbest > 0 && nh > P.nbest) {
     nh = P.nbest;
@@ -3972,110 +4001,309 @@ FLTX_DEV void backtraceNarrow(const BacktraceParams& P, char* smem) {
   const int F = P.npF;
   TT* tile = (TT*)smem;                                  /* [K][L] */
   char* scr = smem + P.npScratch;
-  RT* cR0 = (RT*)scr;                                    /* [2][F][K] */
-  int32_t* cW0 = (int32_t*)(cR0 + (size_t)2 * F * K);    /* [2][F][K] (lexicon decoder) */
-  int32_t* oW = cW0 + (lex ? (size_t)2 * F * K : 0);     /* [nh][F]   (lexicon decoder) */
-  auto tokOf = [&](int k, int j) {
-    const uint32_t t = tile[(size_t)k * L + j];
+  const int nW = W >> 6, wv = tid >> 6, ln = tid & 63;
+  /* PW: frame j lies d = ff - j rows below the newest one, in chunk c = d / F, at o = d - c F from the chunk's top, in
+   * wave w = o / S's sub-stretch; S = ceil(F / nW), so the last waves of a chunk may have fewer frames, or none */
+  const uint8_t* entry = (const uint8_t*)smem + P.npEntry; /* [chunk][wave][K] */
+  const int S = PW ? (F + nW - 1) / nW : 1;
+  const float invS = 1.0f / (float)S, invF = 1.0f / (float)F;
+  auto divBy = [](int d, int m, float inv) { /* d / m, exact: rows < 2^24 (launchBacktrace) */
+    int q = (int)((float)d * inv);
+    q -= q * m > d ? 1 : 0;
+    q += (q + 1) * m <= d ? 1 : 0;
+    return q;
+  };
+  auto subOf = [&](int j) { /* c nW + w of frame j */
+    const int d = ff - j;
+    const int cc = divBy(d, F, invF);
+    return cc * nW + divBy(d - cc * F, S, invS);
+  };
+  auto rowOf = [&](int k, int j) -> uint32_t {
+    return PW ? (uint32_t)entry[(size_t)subOf(j) * K + k] : (uint32_t)k;
+  };
+  auto tokAt = [&](uint32_t row, int j) { /* the token at frame j of tile row `row` (PW: NOROW = pruned below the cut) */
+    if (PW && row == NOROW) {
+      return -1;
+    }
+    const uint32_t t = tile[(size_t)row * L + j];
     return t == NONE ? -1 : (int)t;
   };
-  int slot[4]; /* hypotheses tid, tid + W, ... (nh <= 4 W is checked by the host) */
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    slot[q] = tid + q * W;
-  }
-  const int wThreads = nh >= W ? W : ((nh + 63) >> 6) << 6; /* whole waves that walk */
-  const int mThreads = W - wThreads;                         /* threads free to copy meanwhile */
-  auto copyChunk = [&](int hi, int buf, int t0, int step) {
-    const int lo = hi - F + 1 > 0 ? hi - F + 1 : 0;
-    const int n = (hi - lo + 1) * K;
-    const int64_t src = hb + (int64_t)lo * K;
-    RT* cR = cR0 + (size_t)buf * F * K;
-    int32_t* cW = cW0 + (size_t)buf * F * K;
-    for (int base = t0; base < n; base += 8 * step) { /* eight loads in flight per thread before the first LDS store */
-      int2 v[8];
-      int32_t wv[8];
+  auto narrowed = [&](const int2& v) {
+    const uint32_t par = (v.x & pmask) == pmask ? NONE : (uint32_t)(v.x & pmask);
+    const uint32_t tk = v.y < 0 ? NONE : (uint32_t)(v.y & P.packedTokMask);
+    return (RT)(par | (tk << HB));
+  };
+  int c = 0;
+  if (PW) {
+    uint8_t* entryW = (uint8_t*)smem + P.npEntry;
+    uint8_t* exitOf = (uint8_t*)scr;                                  /* [nW][K] */
+    RT* cR = (RT*)(scr + (((size_t)nW * K + 15) & ~(size_t)15));       /* [F][K] */
+    /* (the words behind the records on a 16-byte boundary: F K two-byte records end on an odd half-word as often as not) */
+    int32_t* cW = (int32_t*)((char*)cR + (((size_t)F * K * sizeof(RT) + 15) & ~(size_t)15)); /* [F][K] (lexicon decoder) */
+    int32_t* oW = cW + (lex ? (size_t)F * K : 0);                     /* [K][F] (lexicon decoder): by slot, as the tile */
+    int2 v[8];
+    /* chunk [lo, hi]: its first 8 W records into registers (eight loads in flight per thread) ... */
+    auto chunkLoad = [&](int hi) {
+      const int lo = hi - F + 1 > 0 ? hi - F + 1 : 0;
+      const int n = (hi - lo + 1) * K;
+      const int64_t src = hb + (int64_t)lo * K;
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
-        const int i = base + u * step;
+        const int i = tid + u * W;
         if (i < n) {
           v[u] = P.histPT[src + i];
-          wv[u] = lex ? P.histW[src + i] : -1;
         }
       }
+    };
+    /* ... and from there, narrowed, into the buffer; what a chunk has beyond 8 W records follows in the same way, and
+     * so do the word records of the lexicon engines (registers: the kernel stays within 128) */
+    auto chunkStore = [&](int hi) {
+      const int lo = hi - F + 1 > 0 ? hi - F + 1 : 0;
+      const int n = (hi - lo + 1) * K;
+      const int64_t src = hb + (int64_t)lo * K;
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
-        const int i = base + u * step;
+        const int i = tid + u * W;
         if (i < n) {
-          const uint32_t par = (v[u].x & pmask) == pmask ? NONE : (uint32_t)(v[u].x & pmask);
-          const uint32_t tk = v[u].y < 0 ? NONE : (uint32_t)(v[u].y & P.packedTokMask);
-          cR[i] = (RT)(par | (tk << HB));
-          if (lex) {
-            cW[i] = wv[u];
-          }
+          cR[i] = narrowed(v[u]);
         }
       }
-    }
-  };
-  copyChunk(ff, 0, tid, W);
-  __syncthreads();
-  int c = 0;
-  for (int hi = ff; hi >= 0; hi -= F, ++c) {
-    const int lo = hi - F + 1 > 0 ? hi - F + 1 : 0;
-    const int nf = hi - lo + 1;
-    const RT* cR = cR0 + (size_t)(c & 1) * F * K;
-    const int32_t* cW = cW0 + (size_t)(c & 1) * F * K;
-    const bool more = lo > 0;
-    if (tid < wThreads) {
+      for (int base = 8 * W + tid; base < n; base += 8 * W) {
 #pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int k = tid + q * W;
-        if (k < nh) {
-          int s = slot[q];
-          TT* row = tile + (size_t)k * L + lo;
-          for (int j = nf - 1; j >= 0; --j) {
-            uint32_t tokv = NONE;
-            int wv = -1;
-            if (s >= 0) {
-              const uint32_t r = cR[j * K + s];
-              tokv = r >> HB;
-              wv = lex ? cW[j * K + s] : -1;
-              const uint32_t par = r & NONE;
-              s = par == NONE ? -1 : (int)par;
-            }
-            row[j] = (TT)tokv;
-            if (P.words) {
-              oW[k * F + j] = wv;
-            }
+        for (int u = 0; u < 8; ++u) {
+          const int i = base + u * W;
+          if (i < n) {
+            v[u] = P.histPT[src + i];
           }
-          slot[q] = s;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int i = base + u * W;
+          if (i < n) {
+            cR[i] = narrowed(v[u]);
+          }
         }
       }
-    } else if (more) {
-      copyChunk(lo - 1, (c + 1) & 1, tid - wThreads, mThreads);
-    }
-    if (more && mThreads == 0) { /* every thread walks: copy afterwards */
-      copyChunk(lo - 1, (c + 1) & 1, tid, W);
-    }
-    __syncthreads();
-    if (P.words) { /* (uniform) the word tile of the chunk: a wave per row, contiguous stores */
-      for (int k = tid >> 6; k < nh; k += W >> 6) {
-        for (int j = tid & 63; j < nf; j += 64) {
-          P.words[ob + (int64_t)k * len + lo + j] = oW[k * F + j];
+      if (lex) {
+        for (int base = tid; base < n; base += 8 * W) {
+          int32_t w8[8];
+#pragma unroll
+          for (int u = 0; u < 8; ++u) {
+            const int i = base + u * W;
+            if (i < n) {
+              w8[u] = P.histW[src + i];
+            }
+          }
+#pragma unroll
+          for (int u = 0; u < 8; ++u) {
+            const int i = base + u * W;
+            if (i < n) {
+              cW[i] = w8[u];
+            }
+          }
         }
+      }
+    };
+    chunkLoad(ff);
+    chunkStore(ff);
+    __syncthreads();
+    FLTX_BT_MARK(1);
+    int slotK = tid; /* hypothesis tid (< nh <= K <= 64: the first wave) */
+    for (int hi = ff; hi >= 0; hi -= F, ++c) {
+      const int lo = hi - F + 1 > 0 ? hi - F + 1 : 0;
+      const int nf = hi - lo + 1;
+      const bool more = lo > 0;
+      if (more) {
+        chunkLoad(lo - 1);
+      }
+      const int jTop = hi - wv * S; /* this wave's sub-stretch: frames jTop down to jBot (none below the chunk) */
+      if (ln < K && jTop >= lo) {
+        const int jBot = jTop - S + 1 > lo ? jTop - S + 1 : lo;
+        int cur = ln;
+        TT* row = tile + (size_t)ln * L;
+        for (int j = jTop; j >= jBot; --j) {
+          uint32_t tokv = NONE;
+          int wd = -1;
+          if (cur >= 0) {
+            const uint32_t r = cR[(j - lo) * K + cur];
+            tokv = r >> HB;
+            wd = lex ? cW[(j - lo) * K + cur] : -1;
+            const uint32_t par = r & NONE;
+            cur = par < (uint32_t)K ? (int)par : -1; /* (a stale record's parent stays inside the chunk's rows) */
+          }
+          row[j] = (TT)tokv;
+          if (P.words) {
+            oW[ln * F + (j - lo)] = wd;
+          }
+        }
+        exitOf[wv * K + ln] = (uint8_t)(cur < 0 ? NOROW : (uint32_t)cur);
+      }
+      if (c < kBtProfChunks) {
+        FLTX_BT_MARK(8 + 2 * c);
       }
       __syncthreads();
+      if (c < kBtProfChunks) {
+        FLTX_BT_MARK(9 + 2 * c);
+      }
+      if (tid < nh) { /* compose: one dependent read per sub-stretch */
+        int cur = slotK;
+        for (int w = 0; w < nW && hi - w * S >= lo; ++w) {
+          entryW[((size_t)c * nW + w) * K + tid] = (uint8_t)(cur < 0 ? NOROW : (uint32_t)cur);
+          if (cur >= 0) {
+            const uint32_t e = exitOf[w * K + cur];
+            cur = e == NOROW ? -1 : (int)e;
+          }
+        }
+        slotK = cur;
+      }
+      if (more) {
+        chunkStore(lo - 1); /* (every wave has walked: the buffer is free) */
+      }
+      __syncthreads();
+      if (P.words) { /* (uniform) the word rows of the chunk: a wave per hypothesis, contiguous stores, gathered by entry slot */
+        for (int k = wv; k < nh; k += nW) {
+          for (int jj = ln; jj < nf; jj += 64) {
+            const uint32_t r = rowOf(k, lo + jj);
+            P.words[ob + (int64_t)k * len + lo + jj] = r == NOROW ? -1 : oW[r * F + jj];
+          }
+        }
+        __syncthreads(); /* (the rows are read: the next walk, or the score pass, writes there) */
+      }
+    }
+  } else {
+    RT* cR0 = (RT*)scr;                                    /* [2][F][K] */
+    int32_t* cW0 = (int32_t*)(cR0 + (size_t)2 * F * K);    /* [2][F][K] (lexicon decoder) */
+    int32_t* oW = cW0 + (lex ? (size_t)2 * F * K : 0);     /* [nh][F]   (lexicon decoder) */
+    int slot[4]; /* hypotheses tid, tid + W, ... (nh <= 4 W is checked by the host) */
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      slot[q] = tid + q * W;
+    }
+    const int wThreads = nh >= W ? W : ((nh + 63) >> 6) << 6; /* whole waves that walk */
+    const int mThreads = W - wThreads;                         /* threads free to copy meanwhile */
+    auto copyChunk = [&](int hi, int buf, int t0, int step) {
+      const int lo = hi - F + 1 > 0 ? hi - F + 1 : 0;
+      const int n = (hi - lo + 1) * K;
+      const int64_t src = hb + (int64_t)lo * K;
+      RT* cR = cR0 + (size_t)buf * F * K;
+      int32_t* cW = cW0 + (size_t)buf * F * K;
+      for (int base = t0; base < n; base += 8 * step) { /* eight loads in flight per thread before the first LDS store */
+        int2 v[8];
+        int32_t wv8[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int i = base + u * step;
+          if (i < n) {
+            v[u] = P.histPT[src + i];
+            wv8[u] = lex ? P.histW[src + i] : -1;
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int i = base + u * step;
+          if (i < n) {
+            cR[i] = narrowed(v[u]);
+            if (lex) {
+              cW[i] = wv8[u];
+            }
+          }
+        }
+      }
+    };
+    copyChunk(ff, 0, tid, W);
+    __syncthreads();
+    FLTX_BT_MARK(1);
+    for (int hi = ff; hi >= 0; hi -= F, ++c) {
+      const int lo = hi - F + 1 > 0 ? hi - F + 1 : 0;
+      const int nf = hi - lo + 1;
+      const RT* cR = cR0 + (size_t)(c & 1) * F * K;
+      const int32_t* cW = cW0 + (size_t)(c & 1) * F * K;
+      const bool more = lo > 0;
+      if (tid < wThreads) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int k = tid + q * W;
+          if (k < nh) {
+            int s = slot[q];
+            TT* row = tile + (size_t)k * L + lo;
+            for (int j = nf - 1; j >= 0; --j) {
+              uint32_t tokv = NONE;
+              int wd = -1;
+              if (s >= 0) {
+                const uint32_t r = cR[j * K + s];
+                tokv = r >> HB;
+                wd = lex ? cW[j * K + s] : -1;
+                const uint32_t par = r & NONE;
+                s = par == NONE ? -1 : (int)par;
+              }
+              row[j] = (TT)tokv;
+              if (P.words) {
+                oW[k * F + j] = wd;
+              }
+            }
+            slot[q] = s;
+          }
+        }
+      } else if (more) {
+        copyChunk(lo - 1, (c + 1) & 1, tid - wThreads, mThreads);
+      }
+      if (more && mThreads == 0) { /* every thread walks: copy afterwards */
+        copyChunk(lo - 1, (c + 1) & 1, tid, W);
+      }
+      if (c < kBtProfChunks) {
+        FLTX_BT_MARK(8 + 2 * c);
+      }
+      __syncthreads();
+      if (c < kBtProfChunks) {
+        FLTX_BT_MARK(9 + 2 * c);
+      }
+      if (P.words) { /* (uniform) the word tile of the chunk: a wave per row, contiguous stores */
+        for (int k = wv; k < nh; k += nW) {
+          for (int j = ln; j < nf; j += 64) {
+            P.words[ob + (int64_t)k * len + lo + j] = oW[k * F + j];
+          }
+        }
+        __syncthreads();
+      }
     }
   }
-  for (int k = tid >> 6; k < nh; k += W >> 6) { /* the token rows, widened: a wave per row */
-    for (int j = tid & 63; j < len; j += 64) {
-      P.tokens[ob + (int64_t)k * len + j] = tokOf(k, j);
+  FLTX_BT_MARK(2);
+  if (P.btProf && tid == 0) {
+    P.btProf[(size_t)b * kBtProfMarks + 6] = (unsigned long long)(c < kBtProfChunks ? c : kBtProfChunks);
+  }
+  for (int j0 = 0; j0 < len; j0 += 64) { /* the token rows, widened: a wave per row (a lane keeps its frame: one look for its sub-stretch) */
+    const int j = j0 + ln;
+    if (j < len) {
+      const int sub = PW ? subOf(j) : 0;
+      for (int k0 = wv; k0 < nh; k0 += 8 * nW) { /* (eight rows' reads in flight: entry, then tile) */
+        uint32_t r[8];
+        int t[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int k = k0 + u * nW < nh ? k0 + u * nW : k0;
+          r[u] = PW ? (uint32_t)entry[(size_t)sub * K + k] : (uint32_t)k;
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          t[u] = tokAt(r[u], j);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const int k = k0 + u * nW;
+          if (k < nh) {
+            P.tokens[ob + (int64_t)k * len + j] = t[u];
+          }
+        }
+      }
     }
   }
+  FLTX_BT_MARK(3);
   if (!P.amOut) {
     return;
   }
-  /* emitting-model (and token-LM) scores, oldest frame first, the tokens from the tile */
+  /* emitting-model (and token-LM) scores, oldest frame first, the tokens from the tile (PW: gathered through the entry
+   * map, a stretch at a time and by the waves that fetch the emission rows, into rows by hypothesis: the adding wave is
+   * bound by the instructions it issues, so it is spared the indirection) */
   const int N = P.N;
   const int Fe = P.npFe;
   float* trT = (float*)scr;                                                                     /* [N][N] (ASG) */
@@ -4085,10 +4313,21 @@ FLTX_DEV void backtraceNarrow(const BacktraceParams& P, char* smem) {
   const int Tb = ff - 1; /* frames decoded: history rows 1 .. Tb */
   const int aThreads = nh >= W ? W : ((nh + 63) >> 6) << 6; /* whole waves that add (one hypothesis per thread) */
   const int fThreads = W - aThreads;
+  TT* hT0 = (TT*)(eT0 + (P.amGather ? 0 : (size_t)2 * Fe * N));                                 /* [2][K][Fe] (PW) */
   auto fetch = [&](int lo, int buf, int t0, int step) { /* emission rows lo - 1 .. of a stretch: contiguous */
     const int hi = lo + Fe - 1 < Tb ? lo + Fe - 1 : Tb;
     const int nEm = P.amGather ? 0 : (hi - lo + 1) * N;
     float* eT = eT0 + (size_t)buf * Fe * N;
+    if (PW) { /* the tokens of the stretch by hypothesis: a lane per frame, the waves take the hypotheses in turn */
+      TT* hT = hT0 + (size_t)buf * K * Fe;
+      for (int jj = t0 & 63; jj <= hi - lo; jj += 64) {
+        const int sub = subOf(lo + jj);
+        for (int k = t0 >> 6; k < nh; k += step >> 6) {
+          const uint32_t r = entry[(size_t)sub * K + k];
+          hT[k * Fe + jj] = r == NOROW ? (TT)NONE : tile[(size_t)r * L + lo + jj];
+        }
+      }
+    }
     for (int base = t0; base < nEm; base += 8 * step) {
       float v[8];
 #pragma unroll
@@ -4114,8 +4353,9 @@ FLTX_DEV void backtraceNarrow(const BacktraceParams& P, char* smem) {
     fetch(1, 0, tid, W);
   }
   __syncthreads();
+  FLTX_BT_MARK(4);
   double am = 0.0;
-  int prevTok = (tid < nh && len > 0) ? tokOf(tid, 0) : 0;
+  int prevTok = (tid < nh && len > 0) ? tokAt(rowOf(tid, 0), 0) : 0;
   double lmAcc = 0.0; /* token LM: the path's LM score ... */
   int lmCtx = 0;      /* ... and context row (row 0 = lm.start) */
   int lmPrev = prevTok;
@@ -4125,6 +4365,11 @@ FLTX_DEV void backtraceNarrow(const BacktraceParams& P, char* smem) {
     const int nf = hi - lo + 1;
     const bool more = hi < Tb;
     const float* eT = eT0 + (size_t)(c & 1) * Fe * N;
+    const TT* tokRow = PW ? hT0 + (size_t)(c & 1) * K * Fe + (size_t)tid * Fe : tile + (size_t)tid * L + lo;
+    auto tokOf = [&](int jj) { /* the token of hypothesis tid at frame lo + jj */
+      const uint32_t t = tokRow[jj];
+      return t == NONE ? -1 : (int)t;
+    };
     if (tid < aThreads) {
       if (tid < nh) {
         /* the chain is the additions: tokens and emissions of eight steps are read ahead of them */
@@ -4136,7 +4381,7 @@ FLTX_DEV void backtraceNarrow(const BacktraceParams& P, char* smem) {
             float ev[U], tr[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
-              tk[u] = tokOf(tid, lo + (j0 + u < nf ? j0 + u : nf - 1));
+              tk[u] = tokOf(j0 + u < nf ? j0 + u : nf - 1);
             }
 #pragma unroll
             for (int u = 0; u < U; ++u) {
@@ -4171,7 +4416,7 @@ FLTX_DEV void backtraceNarrow(const BacktraceParams& P, char* smem) {
         }
         if (P.tokLm) { /* a chain of dependent gathers, one per new-token step */
           for (int j = 0; j < nf; ++j) {
-            const int tk = tokOf(tid, lo + j);
+            const int tk = tokOf(j);
             if (tk >= 0) {
               if (tk != lmPrev && tk != P.blank) {
                 const int2 e = P.tokLm[(size_t)lmCtx * (size_t)P.tokLmStride + (size_t)tk];
@@ -4191,6 +4436,7 @@ FLTX_DEV void backtraceNarrow(const BacktraceParams& P, char* smem) {
     }
     __syncthreads();
   }
+  FLTX_BT_MARK(5);
   if (tid < nh) {
     P.amOut[((size_t)b * K + tid) * 3 + 1] = am;
     if (P.tokLm) {
