@@ -841,7 +841,8 @@ FLTX_API int fltx_decoder_profile(fltx_decoder* dec, uint64_t* out);
  * the n-gram tables for every word-end candidate instead of keeping the last (LM state, word) answers), "bt_lds_kb".  fltx_decoder_get also answers "engine", "redone", "stream_redone", "yshare", "sstream",
  * "bt_record_bytes" (the last back-trace: 2 or 4 = it narrowed the lane engines' packed history records to that many
  * bytes and kept the utterance's token tile in LDS; 0 = the chunked back-trace of plain 8-byte records),
- * "bt_chunk_frames" / "bt_stretch_frames" (frames per LDS chunk of history records / of emission rows in it),
+ * "bt_chunk_frames" / "bt_stretch_frames" (frames per LDS chunk of history records / per stretch of the addends
+ * staged by hypothesis while the emitting-model scores are re-added),
  * "bt_walk_waves" (waves that walked that back-trace's chunks: 1 = one walk per hypothesis; more = every wave walked
  * its own stretch of each chunk from every slot and the hypotheses were composed through the waves' maps -- narrowed
  * records at beams up to 64).  fltx_decoder_set: "bt_walk_waves" 0 / 1 keeps the walk per hypothesis (A/B runs, tests;
@@ -850,7 +851,9 @@ FLTX_API int fltx_decoder_profile(fltx_decoder* dec, uint64_t* out);
  * beam rounded up to whole waves, whatever is asked: the score passes are one thread per hypothesis), "bt_profile"
  * (1 = thread 0 of each workgroup of the narrow back-trace stores shader clocks at its phase borders; afterwards
  * fltx_decoder_get "bt_prof_copy0" / "bt_prof_walk" / "bt_prof_wait" / "bt_prof_store" / "bt_prof_fetch0" /
- * "bt_prof_score" / "bt_prof_total" give the clocks summed over the "bt_prof_utts" utterances of the last batch). */
+ * "bt_prof_score" / "bt_prof_total" give the clocks summed over the "bt_prof_utts" utterances of the last batch;
+ * "bt_prof_add" + "bt_prof_addwait" = "bt_prof_score": the first adding wave's own time in the score loop, and its
+ * waits at the stretch barriers for the waves that stage the addends). */
 /* Round 5: "defer_check" (1 = fltx_decode_batch returns as soon as its kernels are queued.  By default the call waits
  * for the decode kernel when the batch ran on a fast path that may flag an utterance, decodes the flagged ones again
  * and only then queues the back-trace -- every read of a device buffer is then queued before the call returns.  With

@@ -839,7 +839,9 @@ struct fltx_decoder {
   hipStream_t copyStream = nullptr;
   hipEvent_t evSlotFree[2] = {nullptr, nullptr}; /* recorded on the launch stream once everything that reads a slot is queued */
   bool slotUsed[2] = {false, false};
+  hipEvent_t lookEv = nullptr; /* "defer_check": fires when the pending batch's status rows have reached hSync */
 #endif
+  bool lookQueued = false; /* the copy of the pending batch's status rows is queued behind its back-trace (queueLook) */
   bool timed = false;
   /* seq2seq (kinds FLTX_DECODER_S2S_LEXFREE / _LEXICON, fltx_s2s_*: fltx_s2s.h, fltx_s2s_lex.h) */
   struct {
@@ -1926,6 +1928,9 @@ int fltx_decoder_destroy(fltx_decoder* d) {
         (void)hipEventDestroy(d->ev[i]);
       }
     }
+    if (d->lookEv) {
+      (void)hipEventDestroy(d->lookEv);
+    }
     if (d->copyStream) {
       (void)hipStreamSynchronize(d->copyStream);
       (void)hipEventDestroy(d->evSlotFree[0]);
@@ -1952,7 +1957,8 @@ static int trTimedSlot(const char* key) {
 /* fltx_decoder_get "bt_prof_<what>" after a batch decoded with "bt_profile" = 1: shader clocks of the last narrow
  * back-trace summed over the utterances that took it -- copy0 (the first chunk into LDS), walk (the marking wave's own
  * share of the walk loop: walking, composing, copying), wait (its barrier waits in that loop), store (the widened token
- * rows), fetch0 (the first emission stretch), score (the score loop), total; utts = utterances counted */
+ * rows), fetch0 (the first stretch of addends staged), score (the score loop), of which add is the first adding wave's own
+ * time and addwait its waits at the stretch barriers (for the staging waves), total; utts = utterances counted */
 static int btProfileGet(fltx_decoder* d, const char* what, int64_t* value) {
   if (!d->btProfile || !d->btProf.p || !d->backtraced) {
     return fail(FLTX_ERR_STATE, "no back-trace profile: fltx_decoder_set(dec, \"bt_profile\", 1) before the batch");
@@ -1962,7 +1968,7 @@ static int btProfileGet(fltx_decoder* d, const char* what, int64_t* value) {
   if (devCopyD2H(h.data(), d->btProf.p, 8 * h.size(), d->ctx->stream)) {
     return fail(FLTX_ERR_HIP, "profile copy failed");
   }
-  int64_t sum[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int64_t sum[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   for (int b = 0; b < d->B; ++b) {
     const unsigned long long* m = h.data() + (size_t)b * kBtProfMarks;
     if (!m[1]) {
@@ -1980,12 +1986,14 @@ static int btProfileGet(fltx_decoder* d, const char* what, int64_t* value) {
     if (m[5]) {
       sum[4] += (int64_t)(m[4] - m[3]);
       sum[5] += (int64_t)(m[5] - m[4]);
+      sum[8] += (int64_t)(m[5] - m[4]) - (int64_t)m[7];
+      sum[9] += (int64_t)m[7];
     }
     sum[6] += (int64_t)((m[5] ? m[5] : m[3]) - m[0]);
     sum[7] += 1;
   }
-  static const char* const kNames[8] = {"copy0", "walk", "wait", "store", "fetch0", "score", "total", "utts"};
-  for (int i = 0; i < 8; ++i) {
+  static const char* const kNames[10] = {"copy0", "walk", "wait", "store", "fetch0", "score", "total", "utts", "add", "addwait"};
+  for (int i = 0; i < 10; ++i) {
     if (!strcmp(what, kNames[i])) {
       *value = sum[i];
       return FLTX_OK;
@@ -2052,7 +2060,7 @@ int fltx_decoder_get(fltx_decoder* d, const char* key, int64_t* value) {
     *value = d->btNarrow;
   } else if (!strcmp(key, "bt_chunk_frames")) { /* ... frames per chunk of history records in LDS (0: none, walked through HBM) */
     *value = d->btChunk;
-  } else if (!strcmp(key, "bt_stretch_frames")) { /* ... frames per stretch of emission rows in LDS while the scores are re-added */
+  } else if (!strcmp(key, "bt_stretch_frames")) { /* ... frames per stretch of staged addends in LDS while the scores are re-added */
     *value = d->btStretch;
   } else if (!strcmp(key, "bt_walk_waves")) { /* ... waves that walked its chunks: 1 = one walk per hypothesis, more = every wave walked
                                                   a stretch of each chunk from every slot and the paths were composed */
@@ -3537,7 +3545,14 @@ int syncResults(fltx_decoder* d) {
     return fail(FLTX_ERR_OOM, "pinned staging allocation failed");
   }
   const int32_t* h = (const int32_t*)d->hSync.p;
-  if (devCopyD2H(d->hSync.p, d->uttRes.p, 4 * (2 * row + (size_t)B), st)) {
+  if (d->lookQueued) { /* the rows were copied right behind the back-trace (queueLook): wait for them, no copy, no stream drained */
+    d->lookQueued = false;
+#ifndef FLTX_EMU
+    if (hipEventSynchronize(d->lookEv) != hipSuccess) {
+      return fail(FLTX_ERR_HIP, "result copy failed: %s", devErr());
+    }
+#endif
+  } else if (devCopyD2H(d->hSync.p, d->uttRes.p, 4 * (2 * row + (size_t)B), st)) {
     return fail(FLTX_ERR_HIP, "result copy failed: %s", devErr());
   }
   memcpy(d->hN.data(), h, 4 * (size_t)B);
@@ -3640,10 +3655,21 @@ int launchBacktrace(fltx_decoder* d) {
     const size_t tile = ((size_t)Q.K * row * tokB + 15) & ~(size_t)15;
     const size_t room = btBudget > tile + 16 ? btBudget - tile - 16 : 0;
     const size_t perWalk = (size_t)Q.K * (2 * rec + (lexRec ? 2 * 4 + 4 : 0));
-    const size_t trBytes = (Q.transitions && !Q.amGather) ? 4 * (size_t)d->N * d->N : 0;
-    const size_t perEm = 2 * 4 * (size_t)d->N;
+    const size_t trBytes = (Q.transitions && !Q.amGather) ? btTransBytes(d->N) : 0;
     const size_t npF = std::min<size_t>(room / perWalk, std::max<size_t>(row, 8));
-    const size_t npFe = Q.amGather ? (size_t)1 << 20 : (room > trBytes ? std::min<size_t>((room - trBytes) / perEm, std::max<size_t>(row, 8)) : 0);
+    /* the score pass: two buffers of addends by hypothesis (floats; f64 sums with transitions), padded rows
+     * (btAddStride), and for the parallel walk under a token LM the stretch's tokens by hypothesis -> the longest
+     * stretch that `avail` bytes hold */
+    const bool withTrans = Q.transitions != nullptr;
+    auto stretchFor = [&](size_t avail, bool tokRows) {
+      const size_t perFe = (size_t)2 * Q.K * (withTrans ? 8 : 4) + (tokRows ? (size_t)2 * Q.K * tokB : 0);
+      size_t fe = std::min<size_t>(avail / perFe, std::max<size_t>(row, 8));
+      while (fe > 0 && btScoreBytes(Q.K, (int)fe, withTrans, tokRows, (int)tokB) > avail) {
+        --fe;
+      }
+      return fe;
+    };
+    const size_t npFe = room > trBytes ? stretchFor(room - trBytes, false) : 0;
     /* The parallel walk (K <= 64: a lane per slot; two waves or more): ONE chunk buffer, the waves' exit maps beside
      * it, and between the tile and all that the entry map [chunk][wave][K], which the score pass still reads.  The
      * chunk keeps the length the double-buffered walk has (short chunks cost the parallel walk a barrier, not a
@@ -3657,9 +3683,8 @@ int launchBacktrace(fltx_decoder* d) {
       const size_t exitB = (nW * Q.K + 15) & ~(size_t)15;
       const size_t ent = ((size_t)Q.K * nW * ((row + npF - 1) / npF) + 15) & ~(size_t)15;
       const size_t roomE = room > ent ? room - ent : 0;
-      /* (a stretch holds its tokens by hypothesis as well, double buffered like its emission rows) */
-      const size_t perEmPw = (Q.amGather ? 0 : perEm) + 2 * (size_t)Q.K * tokB;
-      const size_t pwFe = roomE > trBytes ? std::min<size_t>((roomE - trBytes) / perEmPw, std::max<size_t>(row, 8)) : 0;
+      const bool tokRows = Q.tokLm != nullptr;
+      const size_t pwFe = roomE > trBytes ? stretchFor(roomE - trBytes, tokRows) : 0;
       if (ent + exitB + pwChunk <= room && pwFe >= 8) {
         narrow = (int)rec;
         walkWaves = (int)nW;
@@ -3669,7 +3694,7 @@ int launchBacktrace(fltx_decoder* d) {
         Q.npWaves = (int32_t)nW;
         Q.npEntry = (int32_t)tile;
         Q.npScratch = (int32_t)(tile + ent);
-        btLds = std::max(btLds, tile + ent + std::max(exitB + pwChunk, trBytes + pwFe * perEmPw) + 16);
+        btLds = std::max(btLds, tile + ent + std::max(exitB + pwChunk, trBytes + btScoreBytes(Q.K, (int)pwFe, withTrans, tokRows, (int)tokB)) + 16);
       }
     }
     if (!narrow && (byteRec || wordRec) && row > 0 && row < (1u << 24) && npF >= 8 && npFe >= 8) {
@@ -3678,7 +3703,7 @@ int launchBacktrace(fltx_decoder* d) {
       Q.npF = (int32_t)npF;
       Q.npFe = (int32_t)npFe;
       Q.npScratch = (int32_t)tile;
-      btLds = std::max(btLds, tile + std::max(npF * perWalk, Q.amGather ? (size_t)0 : trBytes + npFe * perEm) + 16);
+      btLds = std::max(btLds, tile + std::max(npF * perWalk, trBytes + btScoreBytes(Q.K, (int)npFe, withTrans, false, (int)tokB)) + 16);
     }
   }
   if (narrow && d->btProfile) {
@@ -3691,7 +3716,7 @@ int launchBacktrace(fltx_decoder* d) {
   d->btWalkWaves = walkWaves;
   d->btNarrow = narrow;
   d->btChunk = narrow ? Q.npF : F;
-  d->btStretch = narrow ? (Q.amGather ? 0 : Q.npFe) : (d->batchPacked && !Q.amGather ? F : 0);
+  d->btStretch = narrow ? Q.npFe : (d->batchPacked && !Q.amGather ? F : 0);
 #ifdef FLTX_EMU
   const BacktraceParams* qq = &Q;
   if (narrow == 2 && walkWaves > 1) {
@@ -4229,6 +4254,7 @@ int fltx_decode_batch(fltx_decoder* d, const float* emissions, int32_t onDevice,
      * only wants kernels queued back to back asks for defer_check = 2 and gets the drops counted */
     if (d->deferCheck == 2) {
       d->offlinePending = false;
+      d->lookQueued = false;
       ++d->looksDropped;
     } else {
       int rc = syncResults(d);
@@ -4266,6 +4292,26 @@ int fltx_decode_batch(fltx_decoder* d, const float* emissions, int32_t onDevice,
  * first asked for (syncResults), on the emissions where the first pass left them in HBM. */
 } /* extern "C" */
 static int settlePendingLook(fltx_decoder* d) { return syncResults(d); }
+/* "defer_check" left the batch pending: the copy of its status rows (what syncResults brings home) and an event are
+ * queued on the launch stream right behind the back-trace, so that the settle finds them in the pinned rows and waits
+ * for that event only.  The rows are the decoder object's own and nothing else writes them before the settle. */
+static int queueLook(fltx_decoder* d) {
+#ifndef FLTX_EMU
+  const size_t bytes = 4 * (2 * d->uttRow + (size_t)d->B);
+  if (d->hSync.ensure(bytes)) {
+    return fail(FLTX_ERR_OOM, "pinned staging allocation failed");
+  }
+  if (!d->lookEv) {
+    HIPCHK(hipEventCreateWithFlags(&d->lookEv, hipEventDisableTiming));
+  }
+  HIPCHK(hipMemcpyAsync(d->hSync.p, d->uttRes.p, bytes, hipMemcpyDeviceToHost, d->ctx->stream));
+  HIPCHK(hipEventRecord(d->lookEv, d->ctx->stream));
+  d->lookQueued = true;
+#else
+  (void)d; /* (the emulator's kernels have run when the launch returns: the settle copies as before) */
+#endif
+  return FLTX_OK;
+}
 static int offlineAttempts(fltx_decoder* d, const float* emissions, int32_t onDevice, int firstAttempt) {
   const int32_t* T = d->offT.data();
   const int64_t* offsets = d->offOffsets.empty() ? nullptr : d->offOffsets.data();
@@ -4435,6 +4481,10 @@ static int offlineAttempts(fltx_decoder* d, const float* emissions, int32_t onDe
   if (rc) {
     return rc;
   }
+  d->lookQueued = false;
+  if (d->offlinePending && (rc = queueLook(d))) {
+    return rc;
+  }
   d->T.assign(T, T + B);
   d->statsDone = false;
   d->haveResults = true;
@@ -4466,6 +4516,7 @@ int fltx_stream_begin(fltx_decoder* d, int32_t B, int32_t N, int32_t maxFrames) 
   std::vector<int32_t> Tm(B, maxFrames);
   d->offlineCall = false;
   d->offlinePending = false; /* (an offline batch whose results were never read) */
+  d->lookQueued = false;
   d->batchPacked = false;
   d->keepScores = 1; /* streams serve getBestHypothesis(lookBack) of ancestors */
   /* The lexicon decoder's candidate lists are sized for what a frame usually produces (LDS) when a chunk
@@ -6235,6 +6286,7 @@ int fltx_s2s_end(fltx_decoder* d) {
   d->compactFetched = false;
   d->scoresFetched = false;
   d->offlinePending = false;
+  d->lookQueued = false;
   return FLTX_OK;
 }
 
@@ -6892,6 +6944,7 @@ int fltx_ctc_rows_end(fltx_decoder* d, const void* lmScores, int32_t lmDtype, in
   d->compactFetched = false;
   d->scoresFetched = false;
   d->offlinePending = false;
+  d->lookQueued = false;
   return FLTX_OK;
 }
 

@@ -3649,7 +3649,7 @@ struct BacktraceParams {
   /* backtraceNarrow (packed records, the token tile resident in LDS): 0 = not in use */
   int32_t npRow;         /* elements per tile row: no utterance of the batch has more history rows */
   int32_t npF;           /* frames per narrowed record chunk */
-  int32_t npFe;          /* frames per stretch of emission rows */
+  int32_t npFe;          /* frames per stretch of addends in the score pass */
   int32_t npScratch;     /* byte offset of the chunks behind the tile (and the entry map) */
   /* the parallel walk (backtraceNarrow<RT, true>, K <= 64): every wave walks its own npF / npWaves frames of a chunk */
   int32_t npWaves;       /* waves of the workgroup, each with ceil(npF / npWaves) frames of a chunk; the serial walk ignores it */
@@ -3661,7 +3661,7 @@ struct BacktraceParams {
 constexpr int kBtProfChunks = 28; /* chunks with marks of their own (the rest of a longer walk falls between two marks) */
 constexpr int kBtProfMarks = 8 + 2 * kBtProfChunks;
 /* [0] begin  [1] first chunk in LDS  [2] walk done  [3] token rows stored  [4] first emission stretch in LDS
- * [5] scores added  [6] chunks marked  [8 + 2c] chunk c walked (composed) by this wave  [9 + 2c] ... and by every wave */
+ * [5] scores added  [6] chunks marked  [7] clocks (not a mark) this wave waited at the score pass's stretch barriers  [8 + 2c] chunk c walked (composed) by this wave  [9 + 2c] ... and by every wave */
 #define FLTX_BT_MARK(i)                                                            \
   do {                                                                             \
     if (P.btProf && tid == 0) {                                                    \
@@ -3948,8 +3948,9 @@ FLTX_DEV void backtraceUtterance(const BacktraceParams& P, char* smem) {
  *          chunk c and drop the tokens into the tile while the other waves narrow chunk c + 1 into the other buffer;
  *   store  the tile leaves as row-contiguous int32 stores, widened;
  *   score  oldest frame first out of the SAME tile (the token rows are never read back from HBM), in the order and
- *          arithmetic of backtraceUtterance; the emission rows of stretch c + 1 (npFe frames) arrive through the
- *          idle waves while stretch c is added, so no stretch begins with an exposed round trip.
+ *          arithmetic of backtraceUtterance; the waves that do not add stage the ADDENDS of stretch c + 1 (npFe
+ *          frames: emission[frame][token], with transitions their f64 sum) by hypothesis in LDS while stretch c is
+ *          added, so an adding wave only reads, converts and adds (see the score pass below).
  * PW (the parallel walk, K <= 64, two waves or more): the walk above is one wave following len dependent LDS reads
  * while the others copy.  Instead every wave both copies and walks: chunk c (npF frames, ONE buffer) is cut
  * into nW sub-stretches of S = ceil(npF / nW) frames (the last ones shorter, or empty), wave w walks its own from EVERY slot at once -- lane s starts at slot s of the
@@ -3973,6 +3974,34 @@ template <>
 struct BtNarrow<uint32_t> {
   typedef uint16_t Tok;
 };
+
+/* the addends of the score pass in LDS: floats, with transitions (the sum of two floats is formed in f64) doubles */
+template <bool TR>
+struct BtAddend;
+template <>
+struct BtAddend<false> {
+  typedef float T;
+  struct alignas(16) Quad {
+    float v[4];
+  };
+};
+template <>
+struct BtAddend<true> {
+  typedef double T;
+  struct alignas(16) Quad {
+    double v[2];
+  };
+};
+/* elements of a hypothesis' row for stretches of Fe frames, `per` of them to a 16-byte read: whole reads, and an odd
+ * number of them, so that the reads of a wave's lanes (a row each) and the staging waves' writes spread over the banks */
+constexpr int btAddStride(int Fe, int per) {
+  return ((((Fe + per - 1) / per) & 1) ? (Fe + per - 1) / per : (Fe + per - 1) / per + 1) * per;
+}
+constexpr size_t btTransBytes(int N) { return ((size_t)4 * N * N + 15) & ~(size_t)15; }
+/* LDS of the score pass of backtraceNarrow per stretch length (launchBacktrace sizes npFe with it) */
+constexpr size_t btScoreBytes(int K, int Fe, bool withTrans, bool tokRows, int tokBytes) {
+  return (size_t)2 * K * btAddStride(Fe, withTrans ? 2 : 4) * (withTrans ? 8 : 4) + (tokRows ? (size_t)2 * K * Fe * tokBytes : 0);
+}
 
 template <typename RT, bool PW>
 FLTX_DEV void backtraceNarrow(const BacktraceParams& P, char* smem) {
@@ -4301,148 +4330,296 @@ FLTX_DEV void backtraceNarrow(const BacktraceParams& P, char* smem) {
   if (!P.amOut) {
     return;
   }
-  /* emitting-model (and token-LM) scores, oldest frame first, the tokens from the tile (PW: gathered through the entry
-   * map, a stretch at a time and by the waves that fetch the emission rows, into rows by hypothesis: the adding wave is
-   * bound by the instructions it issues, so it is spared the indirection) */
+  /* emitting-model (and token-LM) scores, oldest frame first.  What has to be serial is one f64 addition per frame and
+   * hypothesis, in the order and arithmetic of backtraceUtterance; everything around it is taken off the adding waves
+   * (one hypothesis per thread).  The other waves STAGE, a stretch of npFe frames ahead, the addend of every hypothesis
+   * and frame into LDS rows by hypothesis, [2][K][stride]: emission[frame][token of the hypothesis there] -- the token
+   * through the entry map and the tile (PW) or from the tile row, the emission gathered straight from HBM (a
+   * stretch's rows are one contiguous block; the gathers of stretch c + 2 are issued into registers before stretch
+   * c + 1 is written, so they have a whole stretch to arrive) -- as a float, or with transitions (ASG) as the f64 sum
+   * (double)emission + (double)transition, which is not always exact and is therefore formed before it joins the
+   * chain, as backtraceUtterance forms it.  A frame that adds nothing (no token, a pruned row) and the tail of a row
+   * are staged as -0.0: am + (-0.0) == am for every am (either zero, infinities and NaN included), so an adding wave
+   * reads its row 16 bytes at a time, a read ahead of the chain, converts and adds: no test, no select, no clamp.
+   * The token LM's chain of dependent gathers is independent of am: where the workgroup has the waves, it runs on
+   * waves of its own beside the adding ones (PW: on the stretch's tokens by hypothesis, staged like the addends).
+   * A workgroup with no wave to spare (one wave; a beam that fills them all) adds, then stages, with every thread;
+   * the barriers are the same for every thread in each case. */
+  if (nh <= 0) {
+    return;
+  }
   const int N = P.N;
   const int Fe = P.npFe;
-  float* trT = (float*)scr;                                                                     /* [N][N] (ASG) */
-  float* eT0 = trT + ((P.transitions && !P.amGather) ? (size_t)N * N : 0);                      /* [2][Fe][N] */
   const float* em = P.emissions + P.emOff[b];
-  const float* const trG = P.amGather ? P.transitions : trT;
   const int Tb = ff - 1; /* frames decoded: history rows 1 .. Tb */
-  const int aThreads = nh >= W ? W : ((nh + 63) >> 6) << 6; /* whole waves that add (one hypothesis per thread) */
-  const int fThreads = W - aThreads;
-  TT* hT0 = (TT*)(eT0 + (P.amGather ? 0 : (size_t)2 * Fe * N));                                 /* [2][K][Fe] (PW) */
-  auto fetch = [&](int lo, int buf, int t0, int step) { /* emission rows lo - 1 .. of a stretch: contiguous */
-    const int hi = lo + Fe - 1 < Tb ? lo + Fe - 1 : Tb;
-    const int nEm = P.amGather ? 0 : (hi - lo + 1) * N;
-    float* eT = eT0 + (size_t)buf * Fe * N;
-    if (PW) { /* the tokens of the stretch by hypothesis: a lane per frame, the waves take the hypotheses in turn */
-      TT* hT = hT0 + (size_t)buf * K * Fe;
-      for (int jj = t0 & 63; jj <= hi - lo; jj += 64) {
-        const int sub = subOf(lo + jj);
-        for (int k = t0 >> 6; k < nh; k += step >> 6) {
-          const uint32_t r = entry[(size_t)sub * K + k];
-          hT[k * Fe + jj] = r == NOROW ? (TT)NONE : tile[(size_t)r * L + lo + jj];
-        }
-      }
-    }
-    for (int base = t0; base < nEm; base += 8 * step) {
-      float v[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int i = base + u * step;
-        v[u] = i < nEm ? em[(size_t)(lo - 1) * N + i] : 0.0f;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int i = base + u * step;
-        if (i < nEm) {
-          eT[i] = v[u];
-        }
-      }
-    }
-  };
-  if (P.transitions && !P.amGather) {
+  const bool trLds = P.transitions && !P.amGather;
+  float* trT = (float*)scr;                                       /* [N][N] (ASG) */
+  char* addB = scr + (trLds ? btTransBytes(N) : 0);
+  const float* const trG = P.amGather ? P.transitions : trT;
+  if (trLds) {
     for (int i = tid; i < N * N; i += W) {
       trT[i] = P.transitions[i];
     }
+    __syncthreads(); /* (uniform: the first stretch is staged from them) */
   }
-  if (Tb >= 1) {
-    fetch(1, 0, tid, W);
-  }
-  __syncthreads();
-  FLTX_BT_MARK(4);
+  const int aThreads = nh >= W ? W : ((nh + 63) >> 6) << 6;       /* whole waves that add (one hypothesis per thread) */
+  const bool lmWaves = P.tokLm && W - aThreads >= 2 * aThreads;   /* ... as many again for the LM chains, and as many or more that stage */
+  const int sBase = aThreads + (lmWaves ? aThreads : 0);
+  const int fThreads = W - sBase;                                 /* threads that stage while those add */
+  const int kL = lmWaves ? tid - aThreads : tid;                  /* the hypothesis whose LM chain this thread runs */
+  const bool lmMine = P.tokLm && kL >= 0 && kL < nh;
+  auto tokKJ = [&](int k, int j) { return tokAt(rowOf(k, j), j); };
   double am = 0.0;
-  int prevTok = (tid < nh && len > 0) ? tokAt(rowOf(tid, 0), 0) : 0;
   double lmAcc = 0.0; /* token LM: the path's LM score ... */
   int lmCtx = 0;      /* ... and context row (row 0 = lm.start) */
-  int lmPrev = prevTok;
-  c = 0;
-  for (int lo = 1; lo <= Tb; lo += Fe, ++c) {
-    const int hi = lo + Fe - 1 < Tb ? lo + Fe - 1 : Tb;
-    const int nf = hi - lo + 1;
-    const bool more = hi < Tb;
-    const float* eT = eT0 + (size_t)(c & 1) * Fe * N;
-    const TT* tokRow = PW ? hT0 + (size_t)(c & 1) * K * Fe + (size_t)tid * Fe : tile + (size_t)tid * L + lo;
-    auto tokOf = [&](int jj) { /* the token of hypothesis tid at frame lo + jj */
-      const uint32_t t = tokRow[jj];
-      return t == NONE ? -1 : (int)t;
+  int lmPrev = (lmMine && len > 0) ? tokKJ(kL, 0) : 0;
+  unsigned long long waitAcc = 0; /* "bt_profile": thread 0's waits at the stretch barriers */
+  auto scorePass = [&](auto withTrans) {
+    constexpr bool TR = decltype(withTrans)::value;
+    typedef typename BtAddend<TR>::T AT;
+    typedef typename BtAddend<TR>::Quad Quad;
+    constexpr int PER = 16 / (int)sizeof(AT); /* addends to a 16-byte read */
+    constexpr int PF = 3;                     /* gathers a staging thread holds in registers across a barrier (C2: 448 threads stage 50 rows of 20) */
+    const int stride = btAddStride(Fe, PER);
+    AT* add0 = (AT*)addB;                                             /* [2][K][stride] */
+    TT* hT0 = (TT*)(addB + (size_t)2 * K * stride * sizeof(AT));       /* [2][K][Fe] (PW with a token LM) */
+    const bool stager = fThreads > 0 && tid >= sBase;
+    /* Who stages what: a thread keeps ONE frame column jj of every stretch (several, cols apart, where a stretch has more
+     * frames than there are threads) and takes the hypotheses kq, kq + G, ... -- fixed for the whole pass, so the
+     * divisions happen once here, the sub-stretch of the frame is looked up once per stretch and thread, and an
+     * element costs its reads and little else: these waves are bound by the instructions they issue.  Consecutive
+     * threads write consecutive addends. */
+    struct Lay {
+      int cols, G, jj, kq;
     };
-    if (tid < aThreads) {
-      if (tid < nh) {
-        /* the chain is the additions: tokens and emissions of eight steps are read ahead of them */
-        constexpr int U = 8;
-        auto walk = [&](auto withTrans) {
-          constexpr bool TR = decltype(withTrans)::value;
-          for (int j0 = 0; j0 < nf; j0 += U) {
-            int tk[U];
-            float ev[U], tr[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-              tk[u] = tokOf(j0 + u < nf ? j0 + u : nf - 1);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-              const int jj = j0 + u < nf ? j0 + u : nf - 1;
-              ev[u] = P.amGather ? em[(size_t)(lo - 1 + jj) * N + (tk[u] >= 0 ? tk[u] : 0)] : eT[jj * N + (tk[u] >= 0 ? tk[u] : 0)];
-              tr[u] = 0.0f;
-            }
-            if (TR) {
-#pragma unroll
-              for (int u = 0; u < U; ++u) {
-                const int pv = u == 0 ? prevTok : tk[u - 1];
-                tr[u] = (tk[u] >= 0 && pv >= 0 && lo - 1 + j0 + u > 0) ? trG[(size_t)tk[u] * N + pv] : 0.0f;
-              }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-              if (j0 + u < nf && tk[u] >= 0) {
-                double x = (double)ev[u];
-                if (TR && lo - 1 + j0 + u > 0) {
-                  x += (double)tr[u];
-                }
-                am += x;
-                prevTok = tk[u];
-              }
-            }
+    auto layFor = [&](int t, int nT) {
+      Lay y;
+      y.cols = stride < nT ? stride : nT;
+      y.G = nT / y.cols;
+      y.jj = t % y.cols;
+      y.kq = t / y.cols < y.G ? t / y.cols : (1 << 24); /* (the threads beyond G whole groups stage nothing) */
+      return y;
+    };
+    const Lay layAll = layFor(tid, W);
+    const Lay laySt = stager ? layFor(tid - sBase, fThreads) : layAll;
+    const bool ahead = stager && stride <= fThreads; /* (one column per thread: its first PF gathers are issued a stretch ahead) */
+    auto tokVia = [&](const uint8_t* entRow, int k, int j) { /* the token of hypothesis k at frame j, entRow = the entry map's row of j's sub-stretch (PW) */
+      const uint32_t row = PW ? (uint32_t)entRow[k] : (uint32_t)k;
+      const bool none = PW && row == NOROW;
+      const uint32_t t = tile[(size_t)(none ? 0u : row) * L + j];
+      return (none || t == NONE) ? -1 : (int)t;
+    };
+    /* what frame j (column jj of its stretch) adds for hypothesis k -> whether it adds at all.  The loads are
+     * unconditional (clamped), so that several stay in flight.  The transition comes from the token one frame
+     * before -- none if that frame has none --, and for the stretch's first frame from the last frame before it that
+     * has a token, as the loop this replaces took them; the first decoded frame has none. */
+    auto gather = [&](const uint8_t* e0, const uint8_t* e1, int k, int j, int jj, float& ev, float& tr) -> bool {
+      const int tk = tokVia(e0, k, j);
+      ev = em[(size_t)(j - 1) * N + (tk >= 0 ? tk : 0)];
+      tr = 0.0f;
+      if (TR) {
+        int pv = tokVia(e1, k, j - 1);
+        if (jj == 0) {
+          for (int p = j - 2; pv < 0 && p >= 0; --p) {
+            pv = tokKJ(k, p);
           }
-        };
-        if (P.transitions) {
-          walk(SlParity<1>());
-        } else {
-          walk(SlParity<0>());
         }
-        if (P.tokLm) { /* a chain of dependent gathers, one per new-token step */
-          for (int j = 0; j < nf; ++j) {
-            const int tk = tokOf(j);
-            if (tk >= 0) {
-              if (tk != lmPrev && tk != P.blank) {
-                const int2 e = P.tokLm[(size_t)lmCtx * (size_t)P.tokLmStride + (size_t)tk];
-                lmAcc = lmAcc + (double)__uint_as_float((uint32_t)e.x);
-                lmCtx = e.y;
-              }
-              lmPrev = tk;
+        const float t = trG[(size_t)(tk >= 0 ? tk : 0) * N + (pv >= 0 ? pv : 0)];
+        tr = (tk >= 0 && pv >= 0) ? t : 0.0f;
+      }
+      return tk >= 0;
+    };
+    auto addend = [&](bool on, float ev, float tr, int j) -> AT {
+      if constexpr (TR) {
+        double x = (double)ev;
+        if (j > 1) {
+          x += (double)tr;
+        }
+        return on ? x : -0.0;
+      } else {
+        return on ? ev : -0.0f;
+      }
+    };
+    /* a thread's columns of the stretch from lo, hypotheses kq + skip G on: gathered and written, PF at a time; the
+     * columns between the stretch's frames and the end of its last 16-byte read are -0.0 */
+    auto direct = [&](int lo, int buf, const Lay& y, int skip) {
+      const int hi = lo + Fe - 1 < Tb ? lo + Fe - 1 : Tb;
+      const int nf = hi - lo + 1;
+      AT* A = add0 + (size_t)buf * K * stride;
+      if (y.kq + skip * y.G >= nh) {
+        return;
+      }
+      for (int jj = y.jj; jj < ((nf + PER - 1) & ~(PER - 1)); jj += y.cols) {
+        const bool inF = jj < nf;
+        const int j = lo + (inF ? jj : 0);
+        const uint8_t* e0 = entry + (PW ? (size_t)subOf(j) * K : 0);
+        const uint8_t* e1 = entry + ((PW && TR) ? (size_t)subOf(j - 1) * K : 0);
+        for (int k0 = y.kq + skip * y.G; k0 < nh; k0 += PF * y.G) {
+          float ev[PF], tr[PF];
+          bool on[PF];
+#pragma unroll
+          for (int u = 0; u < PF; ++u) {
+            const int k = k0 + u * y.G;
+            on[u] = gather(e0, e1, k < nh ? k : 0, j, jj, ev[u], tr[u]) && inF;
+          }
+#pragma unroll
+          for (int u = 0; u < PF; ++u) {
+            const int k = k0 + u * y.G;
+            if (k < nh) {
+              A[k * stride + jj] = addend(on[u], ev[u], tr[u], j);
             }
           }
         }
       }
-    } else if (more) {
-      fetch(hi + 1, (c + 1) & 1, tid - aThreads, fThreads);
-    }
-    if (more && fThreads == 0) {
-      fetch(hi + 1, (c + 1) & 1, tid, W);
+    };
+    /* the first PF hypotheses of a staging thread's column (`ahead`): gathered into registers a whole round before they
+     * are written -- two sets: while stretch c is added, the gathers of stretch c + 2 are issued into one, THEN stretch
+     * c + 1 is written from the other, whose gathers were issued a round ago and have arrived */
+    struct Held {
+      float ev[PF], tr[PF];
+      uint32_t on;
+    };
+    Held hA = {{0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f}, 0u}, hB = hA;
+    auto issue = [&](int lo, const Lay& y, Held& h) {
+      const int hi = lo + Fe - 1 < Tb ? lo + Fe - 1 : Tb;
+      const int nf = hi - lo + 1;
+      h.on = 0;
+      /* (every thread issues all PF loads, clamped where it has nothing to stage: with a load under a condition the
+       * compiler cannot count the loads in flight and drains them all -- the ones just issued too -- before `put`) */
+      const bool inF = y.jj < nf;
+      const int j = lo + (inF ? y.jj : 0);
+      const uint8_t* e0 = entry + (PW ? (size_t)subOf(j) * K : 0);
+      const uint8_t* e1 = entry + ((PW && TR) ? (size_t)subOf(j - 1) * K : 0);
+#pragma unroll
+      for (int u = 0; u < PF; ++u) {
+        const int k = y.kq + u * y.G;
+        h.on |= ((gather(e0, e1, k < nh ? k : 0, j, inF ? y.jj : 1, h.ev[u], h.tr[u]) && inF) ? 1u : 0u) << u;
+      }
+    };
+    auto put = [&](int lo, int buf, const Lay& y, const Held& h) {
+      const int hi = lo + Fe - 1 < Tb ? lo + Fe - 1 : Tb;
+      const int nf = hi - lo + 1;
+      AT* A = add0 + (size_t)buf * K * stride;
+      if (y.jj < ((nf + PER - 1) & ~(PER - 1))) {
+#pragma unroll
+        for (int u = 0; u < PF; ++u) {
+          const int k = y.kq + u * y.G;
+          if (k < nh) {
+            A[k * stride + y.jj] = addend((h.on >> u) & 1u, h.ev[u], h.tr[u], lo + y.jj);
+          }
+        }
+      }
+    };
+    /* PW with a token LM: the tokens of the stretch by hypothesis (a lane per frame, the waves take the hypotheses in turn) */
+    auto stageTok = [&](int lo, int buf, int t0, int step) {
+      if (PW && P.tokLm) {
+        const int hi = lo + Fe - 1 < Tb ? lo + Fe - 1 : Tb;
+        TT* hT = hT0 + (size_t)buf * K * Fe;
+        for (int jj = t0 & 63; jj <= hi - lo; jj += 64) {
+          const int sub = subOf(lo + jj);
+          for (int k = t0 >> 6; k < nh; k += step >> 6) {
+            const uint32_t r = entry[(size_t)sub * K + k];
+            hT[k * Fe + jj] = r == NOROW ? (TT)NONE : tile[(size_t)r * L + lo + jj];
+          }
+        }
+      }
+    };
+    if (Tb >= 1) {
+      direct(1, 0, layAll, 0);
+      stageTok(1, 0, tid, W);
+      if (ahead) {
+        issue(1 + Fe <= Tb ? 1 + Fe : 1, laySt, hA);
+      }
     }
     __syncthreads();
+    FLTX_BT_MARK(4);
+    /* stretch c, from frame lo: added (and its LM steps taken) while stretch c + 1 is staged; `cur` holds the gathers of stretch c + 1 */
+    auto round = [&](int lo, int c, Held& cur, Held& nxt) {
+      const int hi = lo + Fe - 1 < Tb ? lo + Fe - 1 : Tb;
+      const int nf = hi - lo + 1;
+      const bool more = hi < Tb;
+      if (tid < aThreads && tid < nh) {
+        const Quad* R = (const Quad*)(add0 + (size_t)(c & 1) * K * stride + (size_t)tid * stride);
+        const int nq = (nf + PER - 1) / PER;
+        Quad q0 = R[0], q1 = R[nq > 1 ? 1 : 0];
+        for (int q = 0; q < nq; q += 2) { /* (q and nq are uniform: the clamps are scalar) */
+          const Quad n0 = R[q + 2 < nq ? q + 2 : nq - 1], n1 = R[q + 3 < nq ? q + 3 : nq - 1];
+#pragma unroll
+          for (int u = 0; u < PER; ++u) {
+            am += (double)q0.v[u];
+          }
+          if (q + 1 < nq) {
+#pragma unroll
+            for (int u = 0; u < PER; ++u) {
+              am += (double)q1.v[u];
+            }
+          }
+          q0 = n0;
+          q1 = n1;
+        }
+      }
+      if (lmMine && (tid < aThreads || lmWaves)) { /* a chain of dependent gathers, one per new-token step */
+        const TT* tokRow = PW ? hT0 + (size_t)(c & 1) * K * Fe + (size_t)kL * Fe : tile + (size_t)kL * L + lo;
+        for (int j = 0; j < nf; ++j) {
+          const uint32_t t = tokRow[j];
+          if (t != NONE) {
+            const int tk = (int)t;
+            if (tk != lmPrev && tk != P.blank) {
+              const int2 e = P.tokLm[(size_t)lmCtx * (size_t)P.tokLmStride + (size_t)tk];
+              lmAcc = lmAcc + (double)__uint_as_float((uint32_t)e.x);
+              lmCtx = e.y;
+            }
+            lmPrev = tk;
+          }
+        }
+      }
+      if (more) {
+        const int nb = (c + 1) & 1;
+        if (stager) {
+          /* (what a thread has beyond its PF held gathers comes first: the compiler drains every load in flight
+           * ahead of that loop, and the gathers issued below must stay in flight across the barrier) */
+          direct(hi + 1, nb, laySt, ahead ? PF : 0);
+          stageTok(hi + 1, nb, tid - sBase, fThreads);
+          if (ahead) { /* (past the last stretch the gathers are issued all the same, and never written) */
+            issue(hi + 1 + Fe <= Tb ? hi + 1 + Fe : hi + 1, laySt, nxt);
+            put(hi + 1, nb, laySt, cur);
+          }
+        } else if (fThreads == 0) { /* every thread has added: every thread stages */
+          direct(hi + 1, nb, layAll, 0);
+          stageTok(hi + 1, nb, tid, W);
+        }
+      }
+      unsigned long long tw = 0;
+      if (P.btProf && tid == 0) {
+        tw = devClock();
+      }
+      ldsBarrier(); /* (LDS only: the gathers issued above stay in flight) */
+      if (P.btProf && tid == 0) {
+        waitAcc += devClock() - tw;
+      }
+    };
+    for (int lo = 1, c = 0; lo <= Tb; lo += 2 * Fe, c += 2) { /* (two rounds a turn: the register sets change places by name) */
+      round(lo, c, hA, hB);
+      if (lo + Fe <= Tb) {
+        round(lo + Fe, c + 1, hB, hA);
+      }
+    }
+  };
+  if (P.transitions) {
+    scorePass(SlParity<1>());
+  } else {
+    scorePass(SlParity<0>());
   }
   FLTX_BT_MARK(5);
+  if (P.btProf && tid == 0) {
+    P.btProf[(size_t)b * kBtProfMarks + 7] = waitAcc;
+  }
   if (tid < nh) {
     P.amOut[((size_t)b * K + tid) * 3 + 1] = am;
-    if (P.tokLm) {
-      lmAcc = lmAcc + (double)__uint_as_float((uint32_t)P.tokLm[(size_t)lmCtx * (size_t)P.tokLmStride + (size_t)P.N].x);
-      P.amOut[((size_t)b * K + tid) * 3 + 2] = lmAcc;
-    }
+  }
+  if (lmMine && (tid < aThreads || lmWaves)) {
+    lmAcc = lmAcc + (double)__uint_as_float((uint32_t)P.tokLm[(size_t)lmCtx * (size_t)P.tokLmStride + (size_t)P.N].x);
+    P.amOut[((size_t)b * K + kL) * 3 + 2] = lmAcc;
   }
 }
 

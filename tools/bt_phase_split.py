@@ -13,7 +13,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 
-KEYS = ("copy0", "walk", "wait", "store", "fetch0", "score", "total", "utts")
+KEYS = ("copy0", "walk", "wait", "store", "fetch0", "score", "total", "utts", "add", "addwait")
+SHOWN = ("copy0", "walk", "wait", "store", "fetch0", "score", "add", "addwait")  # (add + addwait = score: the first
+# adding wave's own time in the score loop, and its waits for the staging waves at the stretch barriers)
 
 
 def split(d):
@@ -56,10 +58,11 @@ def main():
             fence()
             n = max(acc["utts"], 1)
             tot = max(acc["total"], 1)
-            print("walk_waves %d record_bytes %d chunk_frames %d %-11s clocks/utterance %8.0f  " %
-                  (decs[0].get("bt_walk_waves"), decs[0].get("bt_record_bytes"), decs[0].get("bt_chunk_frames"), mode,
+            print("walk_waves %d record_bytes %d chunk_frames %d stretch_frames %d %-11s clocks/utterance %8.0f  " %
+                  (decs[0].get("bt_walk_waves"), decs[0].get("bt_record_bytes"), decs[0].get("bt_chunk_frames"),
+                   decs[0].get("bt_stretch_frames"), mode,
                    acc["total"] / n) +
-                  "  ".join("%s %5.1f%%" % (k, 100.0 * acc[k] / tot) for k in KEYS[:6]), flush=True)
+                  "  ".join("%s %5.1f%%" % (k, 100.0 * acc[k] / tot) for k in SHOWN), flush=True)
         for d in decs:
             d.close()
     job.close()
