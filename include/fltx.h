@@ -743,6 +743,40 @@ FLTX_API int fltx_result_transcripts(fltx_decoder* dec, int32_t max_hyp, int32_t
 FLTX_API int fltx_result_best(fltx_decoder* dec, int32_t b, int32_t look_back,
                               double* scores, int32_t* tokens, int32_t* words,
                               int32_t capacity, int32_t* length);
+/* ---- partial transcripts of all streams ----------------------------------- */
+/* What a streaming recogniser shows after every chunk, for all B streams in one call: row b of `t` is the frame row
+ * fltx_result_best(dec, b, look_back, ...) returns (findBestAncestor, with the lexicon kinds' walk on to a complete
+ * hypothesis and their empty result while frames in buffer - 1 - look_back < 1), collapsed on the device by the rule
+ * above fltx_transcripts with the decoder's own blank (under the ASG criterion nothing is a blank).  Buffer entry 0 is
+ * the root's sil, or the hypothesis the last prune kept: like any other entry it is listed if it is not a blank, so a
+ * client that concatenates across prunes counts absolute entry first_frame[b] + i once.
+ *
+ * stable_frames[b]: with anc(h, j) the ancestor at buffer frame j of a hypothesis h of the current beam, 1 + the largest j
+ * at which anc(h, j) is one and the same hypothesis for every h -- every later hypothesis descends from the current
+ * beam, so entries [0, stable_frames) of the row can no longer change; 0 if there is no such j (after a prune buffer
+ * frame 0 can hold several parentless hypotheses) and for an empty beam, frames in buffer for a beam of one; independent
+ * of look_back.  stable_tokens / stable_words count the row's tokens / words at timesteps below
+ * min(stable_frames, length).
+ *
+ * Valid inside a stream: after fltx_stream_begin on the lexicon-free and lexicon decoders, after
+ * fltx_ctc_rows_stream_begin on the two CTC rows decoders where fltx_result_best is valid; FLTX_ERR_STATE elsewhere
+ * (offline decodes, the seq2seq kinds, a rows decoder begun with fltx_ctc_rows_begin), FLTX_ERR_INVALID on look_back < 0
+ * or a NULL out.  A stream that has stopped is no error of the call: its row is empty, length[b] = 0 and status[b] says
+ * why.  One launch for all streams, then the transcript's scan and write; the number of launches and copies does not
+ * depend on B.  on_device == 0: every array lands in the decoder's pinned buffers.  on_device != 0: the pointers address
+ * HBM in the order of the context's stream and only the two totals cross PCIe.  The buffers stay valid until the next
+ * call on the decoder that steps, appends, prunes or asks again. */
+typedef struct fltx_stream_partials_out {
+  fltx_transcripts t;            /* n_rows = B, row b = stream b; t.scores = [B*3] score / emitting-model / LM score of the
+                                    ancestor (as fltx_result_best); t.row_first = NULL */
+  const int32_t* length;         /* [B] frames of the result = what fltx_result_best would return in *length; 0: empty */
+  const int32_t* stable_frames;  /* [B] leading buffer entries that every hypothesis of the current beam shares */
+  const int32_t* stable_tokens;  /* [B] tokens of row b that lie inside them (timestep < stable_frames[b]) */
+  const int32_t* stable_words;   /* [B] likewise for words (word_timesteps) */
+  const int64_t* first_frame;    /* [B] frames pruned away so far: buffer entry i is absolute entry first_frame[b] + i */
+  const int32_t* status;         /* [B] 0, or the FLTX_ERR_* that fltx_result_best(dec, b, ...) would return for this stream */
+} fltx_stream_partials_out;
+FLTX_API int fltx_stream_partials(fltx_decoder* dec, int32_t look_back, int32_t on_device, fltx_stream_partials_out* out);
 /* Device-resident results of the last batch (no host copy): pointers into HBM
  * valid until the next decode call.  n_hyp: int32[B]; scores: double[B*K*3];
  * tokens/words: int32 at tok_off[b] + i*(T[b]+2) + f. */

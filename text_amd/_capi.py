@@ -82,6 +82,19 @@ class Transcripts(C.Structure):
     ]
 
 
+class StreamPartialsOut(C.Structure):
+    """fltx_stream_partials_out (include/fltx.h)"""
+    _fields_ = [
+        ("t", Transcripts),
+        ("length", C.c_void_p),
+        ("stable_frames", C.c_void_p),
+        ("stable_tokens", C.c_void_p),
+        ("stable_words", C.c_void_p),
+        ("first_frame", C.c_void_p),
+        ("status", C.c_void_p),
+    ]
+
+
 def _view(ptr, ctype, n):
     """n elements at a host address as a NumPy array (no copy)"""
     if n == 0 or not ptr:
@@ -139,7 +152,7 @@ class Lib:
         "fltx_ctc_rows_stream_begin", "fltx_ctc_rows_stream_append", "fltx_ctc_rows_stream_prune",
         "fltx_ctc_rows_stream_frames_in_buffer", "fltx_ctc_rows_stream_collect",
         "fltx_ctc_rows_plan_begin", "fltx_ctc_rows_plan", "fltx_ctc_rows_plan_release",
-        "fltx_collapse_rows", "fltx_result_transcripts",
+        "fltx_collapse_rows", "fltx_result_transcripts", "fltx_stream_partials",
     ]
 
     def __init__(self, path=None):
@@ -238,6 +251,7 @@ class Lib:
             "fltx_ctc_rows_plan_release": [vp, vp, vp, i32],
             "fltx_collapse_rows": [vp, vp, vp, vp, vp, i64, i32, i32, C.POINTER(Transcripts)],
             "fltx_result_transcripts": [vp, i32, i32, C.POINTER(Transcripts)],
+            "fltx_stream_partials": [vp, i32, i32, C.POINTER(StreamPartialsOut)],
         }
         for name, args in sig.items():
             fn = getattr(L, name)
@@ -674,6 +688,14 @@ class Transcript:
         self.words, self.word_timesteps, self.word_tok_end = words, word_timesteps, word_tok_end
 
 
+class Partial(Transcript):
+    """One stream's partial result (BatchDecoder.stream_partials_batch): the Transcript of getBestHypothesis(look_back),
+    and what of it can no longer change -- the first stable_frames buffer entries, which hold the first stable_tokens
+    tokens and stable_words words; buffer entry i is absolute entry first_frame + i of the stream.  status: 0, or the
+    error code fltx_result_best would report for the stream (its transcript is empty then)."""
+    __slots__ = ("length", "stable_frames", "stable_tokens", "stable_words", "first_frame", "status")
+
+
 class _CompactHyp(Hyp):
     """A hypothesis of results_batch(): its token row stays the byte row the device packed until somebody reads it
     (an n-best of 50 x 1 002 frames is read in full by few callers; widening 12.8 M bytes per batch up front cost more
@@ -923,6 +945,45 @@ class BatchDecoder:
             out.append([Transcript(s3[i][0], s3[i][1], s3[i][2], tok[to[q]:to[q + 1]], ts[to[q]:to[q + 1]],
                                    wrd[wo[q]:wo[q + 1]], wts[wo[q]:wo[q + 1]], wte[wo[q]:wo[q + 1]])
                         for i, q in enumerate(range(first[b], first[b + 1]))])
+        return out
+
+    def stream_partials(self, look_back=0, device=False):
+        """fltx_stream_partials: inside a stream, the partial transcript of every stream in one call -- row b is
+        getBestHypothesis(look_back) of stream b after CTC collapse, made on the device -- and how much of it is final.
+        -> a dict: the keys of transcripts() without row_first (n_rows = B), scores [B, 3], and per stream length
+        (frames of the result), stable_frames / stable_tokens / stable_words (the leading buffer entries every
+        hypothesis of the current beam shares, and the row's tokens / words inside them), first_frame (int64: frames
+        pruned away so far) and status.  NumPy views of the decoder's pinned buffers, valid until the next call that
+        steps, appends, prunes or asks again.  device=True: integer addresses of the arrays in HBM."""
+        o = StreamPartialsOut()
+        self._chk(self.L.lib.fltx_stream_partials(self.h, int(look_back), 1 if device else 0, C.byref(o)))
+        r = _transcript_views(o.t, device)
+        B = self.B
+        if device:
+            r.update(scores=o.t.scores, length=o.length, stable_frames=o.stable_frames, stable_tokens=o.stable_tokens,
+                     stable_words=o.stable_words, first_frame=o.first_frame, status=o.status)
+            return r
+        r["scores"] = _view(o.t.scores, C.c_double, 3 * B).reshape(B, 3)
+        for k in ("length", "stable_frames", "stable_tokens", "stable_words", "status"):
+            r[k] = _view(getattr(o, k), C.c_int32, B)
+        r["first_frame"] = _view(o.first_frame, C.c_int64, B)
+        return r
+
+    def stream_partials_batch(self, look_back=0):
+        """[Partial] per stream: the arrays of stream_partials() copied once, sliced per stream"""
+        r = self.stream_partials(look_back)
+        to, wo = r["tok_off"].tolist(), r["word_off"].tolist()
+        tok, ts = r["tokens"].copy(), r["timesteps"].copy()
+        wrd, wts, wte = r["words"].copy(), r["word_timesteps"].copy(), r["word_tok_end"].copy()
+        sc = r["scores"].tolist()
+        num = {k: r[k].tolist() for k in Partial.__slots__}
+        out = []
+        for b in range(self.B):
+            p = Partial(sc[b][0], sc[b][1], sc[b][2], tok[to[b]:to[b + 1]], ts[to[b]:to[b + 1]], wrd[wo[b]:wo[b + 1]],
+                        wts[wo[b]:wo[b + 1]], wte[wo[b]:wo[b + 1]])
+            for k, v in num.items():
+                setattr(p, k, v[b])
+            out.append(p)
         return out
 
     def best(self, b, look_back=0, capacity=1 << 16):

@@ -17,6 +17,7 @@
 #include <cstring>
 #include <thread>
 #include <limits>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -35,6 +36,7 @@
 #include "fltx_ctc_rows_lex.h"
 #include "fltx_ctc_rows_stream.h"
 #include "fltx_transcript.h"
+#include "fltx_stream_partials.h"
 #include "fltx_ctc_rows_plan.h"
 
 using namespace fltx;
@@ -314,6 +316,13 @@ __global__ void __launch_bounds__(kCrsOpThreads) fltx_ctc_rows_stream_collect_ke
   __shared__ __attribute__((aligned(16))) CrsCollectLds fltx_crs_collect_lds;
   crsCollect<LEX>(W, (char*)&fltx_crs_collect_lds);
 }
+/* fltx_stream_partials.h: the partial transcript and the stable prefix of every stream (KIND 0: the classic streams,
+ * 1 / 2: the lexicon-free / lexicon rows streams) */
+template <int KIND>
+__global__ void __launch_bounds__(kSpThreads) fltx_stream_partials_kernel(SpParams Q) {
+  __shared__ __attribute__((aligned(16))) SpLds fltx_sp_lds;
+  spPartials<KIND>(Q, (char*)&fltx_sp_lds);
+}
 __global__ void __launch_bounds__(1024) fltx_streamop_kernel(StreamOpParams Q) {
   __shared__ int32_t sh[kStreamOpLds / 4];
   streamOpUtterance(Q, sh);
@@ -525,6 +534,8 @@ struct TrBufs {
   DBuf desc;  /* rowOff[n] i64, rowLen[n] i32 (the decoder call's rows) */
   DBuf tokens, timesteps, words, wordT, wordEnd;
   HBuf hTotals, hDesc, hOff, hTokens, hTimesteps, hWords, hWordT, hWordEnd;
+  DBuf pack;  /* fltx_stream_partials: the five arrays back to back, and their pinned twin -- one copy home */
+  HBuf hPack;
   std::vector<int64_t> rowFirst;
   /* "time_transcripts": HIP events around the three kernels (and around fltx_pack_results_kernel) */
   int timed = 0;
@@ -815,6 +826,12 @@ struct fltx_decoder {
   HBuf hTokens, hWords, hScores; /* fltx_result_fetch_batch */
   HBuf hTok8, hWordsC, hPackMeta;  /* fltx_result_fetch_batch_compact */
   TrBufs tr;                       /* fltx_result_transcripts */
+  /* fltx_stream_partials: the frames each classic stream has pruned off (int64 [B], zeroed by fltx_stream_begin); what
+   * a call reports ({first_frame, rowOff}[B] int64, scores [B][3], {length, stable_frames, stable_tokens, stable_words,
+   * status}[B] int32) with its pinned twin; the frame rows [B][cap]; the transcript's buffers, apart from tr's */
+  DBuf uttFirst, spOut, spTok, spWrd;
+  HBuf hSpOut;
+  TrBufs spTr;
   HBuf hSync;                      /* syncResults */
   HBuf hStat;                      /* DecodeParams::statusHost */
   DBuf dTok8, dWordsC, dPackMeta;
@@ -3896,6 +3913,7 @@ int launchStreamOp(fltx_decoder* d, int op, int lookBack, int cap) {
   Q.uttFrame = d->uttFrame.as<int32_t>();
   Q.uttNBeam = d->uttNBeam.as<int32_t>();
   Q.gScore = d->gScore.as<double>();
+  Q.firstFrame = d->streaming ? d->uttFirst.as<int64_t>() : nullptr;
   Q.outLen = d->bestLen.as<int32_t>();
   Q.outScores = d->bestScores.as<double>();
   Q.outTok = d->bestTok.as<int32_t>();
@@ -4560,6 +4578,9 @@ int fltx_stream_begin(fltx_decoder* d, int32_t B, int32_t N, int32_t maxFrames) 
   d->chunkPending = false;
   d->pendingPrune = -1;
   d->compactions = 0;
+  if (d->uttFirst.ensure(8 * (size_t)B, d->ctx->stream, false) || devMemset(d->uttFirst.p, 0, 8 * (size_t)B, d->ctx->stream)) {
+    return fail(FLTX_ERR_OOM, "stream counters: allocation failed");
+  }
   if ((rc = launchCompact(d, 0))) {
     return rc;
   }
@@ -7417,7 +7438,8 @@ static int trCopyHome(void* h, const void* dv, size_t n, Stream st) {
 /* count, scan, (the host reads the two totals and sizes the output,) write; then the arrays home unless on_device.
  * tok / wrd / rowOff / rowLen: device pointers.  Fills everything of *out but row_first and scores. */
 static int trRun(TrBufs& T, Stream st, const int32_t* tok, const int32_t* wrd, const int64_t* rowOff, const int32_t* rowLen,
-                 int64_t n, int32_t blank, int32_t onDevice, const char* what, fltx_transcripts* out) {
+                 int64_t n, int32_t blank, int32_t onDevice, const char* what, fltx_transcripts* out,
+                 const std::function<int(const TrParams&)>* counted = nullptr) {
   const size_t n1 = (size_t)n + 1;
   const int64_t blocks = (n + kTrRowsPerBlock - 1) / kTrRowsPerBlock;
   if (blocks > 0x7FFFFFFF) {
@@ -7446,7 +7468,14 @@ static int trRun(TrBufs& T, Stream st, const int32_t* tok, const int32_t* wrd, c
     if (trMark(T, 0, st)) {
       return fail(FLTX_ERR_HIP, "%s: event failed", what);
     }
-    S2S_LAUNCH(fltx_transcript_count_kernel, trCountRows, (int)blocks, kTrThreads, 0, st, Q);
+    if (counted) { /* (the caller's kernel makes the rows and counts them: fltx_stream_partials) */
+      const int rc = (*counted)(Q);
+      if (rc) {
+        return rc;
+      }
+    } else {
+      S2S_LAUNCH(fltx_transcript_count_kernel, trCountRows, (int)blocks, kTrThreads, 0, st, Q);
+    }
   }
   if (trMark(T, 1, st)) {
     return fail(FLTX_ERR_HIP, "%s: event failed", what);
@@ -7464,16 +7493,32 @@ static int trRun(TrBufs& T, Stream st, const int32_t* tok, const int32_t* wrd, c
     return fail(FLTX_ERR_INVALID, "%s: a row length is negative", what);
   }
   const size_t nt = (size_t)tot[0], nw = (size_t)tot[1];
-  const size_t bt = 4 * std::max<size_t>(nt, 1), bw = 4 * std::max<size_t>(nw, 1);
-  if (T.tokens.ensure(bt, st, false) || T.timesteps.ensure(bt, st, false) || T.words.ensure(bw, st, false) ||
-      T.wordT.ensure(bw, st, false) || T.wordEnd.ensure(bw, st, false)) {
-    return fail(FLTX_ERR_OOM, "%s: allocation failed", what);
+  /* counted (fltx_stream_partials): the five arrays lie back to back in one allocation -- tokens, timesteps [ntc], words,
+   * wordT, wordEnd [nwc] -- so that host mode brings them home in one copy: per chunk of a stream the copies of a call
+   * cost more than its kernels.  (The other callers keep one buffer per array, at addresses that do not move.) */
+  const bool packed = counted != nullptr;
+  const size_t ntc = std::max<size_t>(nt, 1), nwc = std::max<size_t>(nw, 1);
+  const size_t bt = 4 * ntc, bw = 4 * nwc, packBytes = 2 * bt + 3 * bw;
+  if (packed) {
+    if (T.pack.ensure(packBytes, st, false)) {
+      return fail(FLTX_ERR_OOM, "%s: allocation failed", what);
+    }
+    Q.tokens = T.pack.as<int32_t>();
+    Q.timesteps = Q.tokens + ntc;
+    Q.words = Q.timesteps + ntc;
+    Q.wordT = Q.words + nwc;
+    Q.wordEnd = Q.wordT + nwc;
+  } else {
+    if (T.tokens.ensure(bt, st, false) || T.timesteps.ensure(bt, st, false) || T.words.ensure(bw, st, false) ||
+        T.wordT.ensure(bw, st, false) || T.wordEnd.ensure(bw, st, false)) {
+      return fail(FLTX_ERR_OOM, "%s: allocation failed", what);
+    }
+    Q.tokens = T.tokens.as<int32_t>();
+    Q.timesteps = T.timesteps.as<int32_t>();
+    Q.words = T.words.as<int32_t>();
+    Q.wordT = T.wordT.as<int32_t>();
+    Q.wordEnd = T.wordEnd.as<int32_t>();
   }
-  Q.tokens = T.tokens.as<int32_t>();
-  Q.timesteps = T.timesteps.as<int32_t>();
-  Q.words = T.words.as<int32_t>();
-  Q.wordT = T.wordT.as<int32_t>();
-  Q.wordEnd = T.wordEnd.as<int32_t>();
   const bool wrote = n > 0 && nt + nw > 0;
   if (wrote) {
     if (trMark(T, 3, st)) {
@@ -7496,24 +7541,42 @@ static int trRun(TrBufs& T, Stream st, const int32_t* tok, const int32_t* wrd, c
     out->word_timesteps = Q.wordT;
     out->word_tok_end = Q.wordEnd;
   } else {
-    if (T.hOff.ensure(16 * n1) || T.hTokens.ensure(bt) || T.hTimesteps.ensure(bt) || T.hWords.ensure(bw) ||
-        T.hWordT.ensure(bw) || T.hWordEnd.ensure(bw)) {
+    if (T.hOff.ensure(16 * n1)) {
       return fail(FLTX_ERR_OOM, "%s: pinned buffers: allocation failed", what);
     }
-    if (trCopyHome(T.hOff.p, Q.tokOff, 16 * n1, st) || /* (tokOff and wordOff lie back to back) */
-        (nt && (trCopyHome(T.hTokens.p, Q.tokens, 4 * nt, st) || trCopyHome(T.hTimesteps.p, Q.timesteps, 4 * nt, st))) ||
-        (nw && (trCopyHome(T.hWords.p, Q.words, 4 * nw, st) || trCopyHome(T.hWordT.p, Q.wordT, 4 * nw, st) ||
-                trCopyHome(T.hWordEnd.p, Q.wordEnd, 4 * nw, st))) ||
-        devSync(st)) {
-      return fail(FLTX_ERR_HIP, "%s: copy failed: %s", what, devErr());
+    if (packed) {
+      const size_t home = nw ? packBytes : (nt ? 2 * bt : 0); /* (without words: tokens and timesteps alone) */
+      if (T.hPack.ensure(packBytes)) {
+        return fail(FLTX_ERR_OOM, "%s: pinned buffers: allocation failed", what);
+      }
+      if (trCopyHome(T.hOff.p, Q.tokOff, 16 * n1, st) || (home && trCopyHome(T.hPack.p, T.pack.p, home, st)) || devSync(st)) {
+        return fail(FLTX_ERR_HIP, "%s: copy failed: %s", what, devErr());
+      }
+      out->tokens = (const int32_t*)T.hPack.p;
+      out->timesteps = out->tokens + ntc;
+      out->words = out->timesteps + ntc;
+      out->word_timesteps = out->words + nwc;
+      out->word_tok_end = out->word_timesteps + nwc;
+    } else {
+      if (T.hTokens.ensure(bt) || T.hTimesteps.ensure(bt) || T.hWords.ensure(bw) || T.hWordT.ensure(bw) ||
+          T.hWordEnd.ensure(bw)) {
+        return fail(FLTX_ERR_OOM, "%s: pinned buffers: allocation failed", what);
+      }
+      if (trCopyHome(T.hOff.p, Q.tokOff, 16 * n1, st) || /* (tokOff and wordOff lie back to back) */
+          (nt && (trCopyHome(T.hTokens.p, Q.tokens, 4 * nt, st) || trCopyHome(T.hTimesteps.p, Q.timesteps, 4 * nt, st))) ||
+          (nw && (trCopyHome(T.hWords.p, Q.words, 4 * nw, st) || trCopyHome(T.hWordT.p, Q.wordT, 4 * nw, st) ||
+                  trCopyHome(T.hWordEnd.p, Q.wordEnd, 4 * nw, st))) ||
+          devSync(st)) {
+        return fail(FLTX_ERR_HIP, "%s: copy failed: %s", what, devErr());
+      }
+      out->tokens = (const int32_t*)T.hTokens.p;
+      out->timesteps = (const int32_t*)T.hTimesteps.p;
+      out->words = (const int32_t*)T.hWords.p;
+      out->word_timesteps = (const int32_t*)T.hWordT.p;
+      out->word_tok_end = (const int32_t*)T.hWordEnd.p;
     }
     out->tok_off = (const int64_t*)T.hOff.p;
     out->word_off = out->tok_off + n1;
-    out->tokens = (const int32_t*)T.hTokens.p;
-    out->timesteps = (const int32_t*)T.hTimesteps.p;
-    out->words = (const int32_t*)T.hWords.p;
-    out->word_timesteps = (const int32_t*)T.hWordT.p;
-    out->word_tok_end = (const int32_t*)T.hWordEnd.p;
   }
   if (T.timed) {
     if (n > 0) {
@@ -7610,6 +7673,119 @@ int fltx_result_transcripts(fltx_decoder* d, int32_t maxHyp, int32_t onDevice, f
     d->scoresFetched = true;
     out->scores = (const double*)d->hScores.p;
   }
+  return FLTX_OK;
+}
+
+/* ---- partial transcripts of all streams (fltx_stream_partials.h) -------------------------------------------------------- */
+int fltx_stream_partials(fltx_decoder* d, int32_t lookBack, int32_t onDevice, fltx_stream_partials_out* out) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  if (!d || !out || lookBack < 0) {
+    return fail(FLTX_ERR_INVALID, "fltx_stream_partials: null decoder or out, or look_back < 0");
+  }
+  const bool rows = isCrKind(d->kind);
+  if (isS2sKind(d->kind)) {
+    return fail(FLTX_ERR_STATE, "fltx_stream_partials: a seq2seq decoder has no streams");
+  }
+  if (rows ? !(d->s2s.begun && d->s2s.crStream) : !(d->streaming && !d->ended && d->haveResults)) {
+    return fail(FLTX_ERR_STATE, "fltx_stream_partials: no open stream (%s first)",
+                rows ? "fltx_ctc_rows_stream_begin" : "fltx_stream_begin");
+  }
+  const int B = d->B;
+  int cap = 1;
+  if (rows) {
+    cap = d->s2s.crRing;
+  } else {
+    /* the waits fltx_result_best makes before its launch: a pending chunk is settled, the counts and statuses looked at */
+    int rc = syncResults(d);
+    if (rc) {
+      return rc;
+    }
+    for (int b = 0; b < B; ++b) {
+      cap = std::max(cap, d->hFrame[b] + 1);
+    }
+  }
+  Stream st = d->ctx->stream;
+  const bool lex = kindHasWords(d->kind);
+  const size_t outBytes = 60 * (size_t)B;
+  if (d->spOut.ensure(outBytes, st, false) || d->spTok.ensure(4 * (size_t)B * cap, st, false) ||
+      (lex && d->spWrd.ensure(4 * (size_t)B * cap, st, false)) || (!onDevice && d->hSpOut.ensure(outBytes))) {
+    return fail(FLTX_ERR_OOM, "fltx_stream_partials: allocation failed");
+  }
+  SpParams Q;
+  memset(&Q, 0, sizeof(Q));
+  Q.B = B;
+  Q.K = d->opt.beam_size;
+  Q.lex = lex ? 1 : 0;
+  Q.lookBack = lookBack;
+  Q.cap = cap;
+  Q.blank = d->opt.criterion == FLTX_CRITERION_CTC ? d->blank : -1;
+  Q.errState = FLTX_ERR_STATE;
+  Q.errUnsupported = FLTX_ERR_UNSUPPORTED;
+  if (rows) {
+    const CrsParams X = crsParams(d);
+    Q.hist = d->s2s.hist.p;
+    Q.sHist = X.sHist;
+    Q.nDec = X.nDec;
+    Q.base = X.base;
+    Q.ring = X.ring;
+    Q.beamN = d->s2s.beamN.as<int32_t>();
+    Q.status = d->s2s.status.as<int32_t>();
+  } else {
+    Q.histPT = d->histPT.as<int2>();
+    Q.histW = d->histW.as<int32_t>();
+    Q.histS = d->histS.as<double>();
+    Q.histOff = d->histOffD.as<int64_t>();
+    Q.uttFrame = d->uttFrame.as<int32_t>();
+    Q.uttNBeam = d->uttNBeam.as<int32_t>();
+    Q.uttStatus = d->uttStatus.as<int32_t>();
+    Q.uttFirst = d->uttFirst.as<int64_t>();
+  }
+  Q.rowTok = d->spTok.as<int32_t>();
+  Q.rowWrd = lex ? d->spWrd.as<int32_t>() : nullptr;
+  Q.firstFrame = d->spOut.as<int64_t>();
+  Q.rowOff = Q.firstFrame + B;
+  Q.scores = (double*)(Q.rowOff + B);
+  Q.length = (int32_t*)(Q.scores + 3 * (size_t)B);
+  Q.stableFrames = Q.length + B;
+  Q.stableTokens = Q.stableFrames + B;
+  Q.stableWords = Q.stableTokens + B;
+  Q.outStatus = Q.stableWords + B;
+  const int kind = d->kind;
+  void* hHome = onDevice ? nullptr : d->hSpOut.p;
+  const void* dHome = d->spOut.p;
+  const std::function<int(const TrParams&)> counted = [&Q, B, kind, st, hHome, dHome, outBytes](const TrParams& T) -> int {
+    Q.nTok = T.nTok;
+    Q.nWord = T.nWord;
+    if (kind == FLTX_DECODER_LEX_CTC_ROWS) {
+      S2S_LAUNCH(fltx_stream_partials_kernel<2>, spPartials<2>, B, kSpThreads, sizeof(SpLds), st, Q);
+    } else if (kind == FLTX_DECODER_CTC_ROWS) {
+      S2S_LAUNCH(fltx_stream_partials_kernel<1>, spPartials<1>, B, kSpThreads, sizeof(SpLds), st, Q);
+    } else {
+      S2S_LAUNCH(fltx_stream_partials_kernel<0>, spPartials<0>, B, kSpThreads, sizeof(SpLds), st, Q);
+    }
+    /* (the per-stream numbers home in one copy, which the look at the totals waits behind) */
+    if (hHome && trCopyHome(hHome, dHome, outBytes, st)) {
+      return fail(FLTX_ERR_HIP, "fltx_stream_partials: copy failed: %s", devErr());
+    }
+    return FLTX_OK;
+  };
+  memset(out, 0, sizeof(*out));
+  int rc = trRun(d->spTr, st, Q.rowTok, Q.rowWrd, Q.rowOff, Q.length, B, Q.blank, onDevice, "fltx_stream_partials", &out->t,
+                 &counted);
+  if (rc) {
+    return rc;
+  }
+  const char* home = onDevice ? (const char*)d->spOut.p : (const char*)d->hSpOut.p;
+  out->first_frame = (const int64_t*)home;
+  out->t.scores = (const double*)(home + 16 * (size_t)B);
+  out->length = (const int32_t*)(home + 40 * (size_t)B);
+  out->stable_frames = out->length + B;
+  out->stable_tokens = out->stable_frames + B;
+  out->stable_words = out->stable_tokens + B;
+  out->status = out->stable_words + B;
   return FLTX_OK;
 }
 

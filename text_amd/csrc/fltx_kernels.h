@@ -4639,6 +4639,7 @@ struct StreamOpParams {
   int32_t* uttFrame;
   const int32_t* uttNBeam;
   double* gScore;     /* current beam scores (normalised by prune) */
+  int64_t* firstFrame; /* [B] frames pruned off since the stream began (prune advances it; fltx_stream_partials reports it) */
   /* op 0 outputs */
   int32_t* outLen;    /* [B] length of the result (0 = empty DecodeResult) */
   double* outScores;  /* [B*3] */
@@ -4854,6 +4855,9 @@ FLTX_DEV void streamOpUtterance(const StreamOpParams& Q, int32_t* sh) {
   }
   if (tid == 0) {
     Q.uttFrame[b] = n;
+    if (Q.firstFrame) {
+      Q.firstFrame[b] += startFrame;
+    }
   }
 }
 #endif /* !FLTX_HOST_ONLY */

@@ -48,21 +48,14 @@ struct TrScanLds {
   int bad[kTrScanThreads / kWave];
 };
 
-/* The walk of one row by one wave.  WRITE = false counts, WRITE = true stores at the row's offsets.
- * -> kept tokens in nk, words in nw (the same in every lane). */
-template <bool WRITE>
-FLTX_DEV void trWalkRow(const TrParams& Q, int64_t row, int& nkOut, int& nwOut) {
+/* The walk of one row -- len entries at t (and w, which may be null) -- by one wave.  WRITE = false counts, WRITE = true
+ * stores at the offsets to / wo.  -> kept tokens in nk, words in nw (the same in every lane); LIMIT: those of them at
+ * positions below `limit` in nkBelow / nwBelow as well (fltx_stream_partials.h: the stable part of a partial result). */
+template <bool WRITE, bool LIMIT>
+FLTX_DEV void trWalkSpan(const TrParams& Q, const int32_t* t, const int32_t* w, int len, int64_t to, int64_t wo, int limit,
+                         int& nkOut, int& nwOut, int& nkBelow, int& nwBelow) {
   const int lane = laneId();
-  const int len = Q.rowLen[row];
-  const int64_t at = Q.rowOff[row];
-  const int32_t* t = Q.tok + at;
-  const int32_t* w = Q.wrd ? Q.wrd + at : nullptr;
-  int64_t to = 0, wo = 0;
-  if (WRITE) {
-    to = Q.tokOff[row];
-    wo = Q.wordOff[row];
-  }
-  int nk = 0, nw = 0;
+  int nk = 0, nw = 0, nkb = 0, nwb = 0;
   int32_t carry = -1; /* the last entry of the tile before (tile 0: position 0 compares with nothing) */
   for (int64_t base = 0; base < (int64_t)len; base += kWave) {
     const int64_t i = base + lane;
@@ -76,6 +69,9 @@ FLTX_DEV void trWalkRow(const TrParams& Q, int64_t row, int& nkOut, int& nwOut) 
     const bool keep = in && v >= 0 && v != Q.blank && (i == 0 || v != prev);
     const unsigned long long km = waveBallot(keep);
     const int kBelow = wavePrefixCount(km);
+    if (LIMIT) {
+      nkb += popc64(waveBallot(keep && i < (int64_t)limit));
+    }
     if (WRITE && keep) {
       Q.tokens[to + nk + kBelow] = v;
       Q.timesteps[to + nk + kBelow] = (int32_t)i;
@@ -90,11 +86,25 @@ FLTX_DEV void trWalkRow(const TrParams& Q, int64_t row, int& nkOut, int& nwOut) 
         Q.wordEnd[o] = nk + kBelow + (keep ? 1 : 0);
       }
       nw += popc64(wm);
+      if (LIMIT) {
+        nwb += popc64(waveBallot(x >= 0 && i < (int64_t)limit));
+      }
     }
     nk += popc64(km);
   }
   nkOut = nk;
   nwOut = nw;
+  nkBelow = nkb;
+  nwBelow = nwb;
+}
+
+/* ... of row `row` of Q */
+template <bool WRITE>
+FLTX_DEV void trWalkRow(const TrParams& Q, int64_t row, int& nkOut, int& nwOut) {
+  const int64_t at = Q.rowOff[row];
+  int below0 = 0, below1 = 0;
+  trWalkSpan<WRITE, false>(Q, Q.tok + at, Q.wrd ? Q.wrd + at : nullptr, Q.rowLen[row], WRITE ? Q.tokOff[row] : 0,
+                           WRITE ? Q.wordOff[row] : 0, 0, nkOut, nwOut, below0, below1);
 }
 
 FLTX_DEV void trCountRows(const TrParams& Q, char*) {
