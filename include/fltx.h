@@ -486,6 +486,29 @@ FLTX_API int fltx_ctc_rows_decoder_create(fltx_ctx* ctx, const fltx_options* opt
 FLTX_API int fltx_ctc_rows_begin(fltx_decoder* dec, const float* emissions, int32_t on_device, const int64_t* offsets,
                                  const int32_t* T, int32_t B, int32_t N, int32_t* next_token, int32_t* next_src_row,
                                  int32_t* next_state, int32_t* n_rows);
+/* fltx_ctc_rows_begin on the emissions as the acoustic model produces them: elements of `dtype` (a fltx_dtype), `kind`
+ * FLTX_S2S_LOG_PROBS or FLTX_S2S_LOGITS.  Frame f of utterance b starts at emissions + (offsets[b] + f * frame_stride)
+ * ELEMENTS; frame_stride >= N, 0 means N; offsets NULL: utterance b starts at frame_stride times the total of
+ * T[0 .. b-1].  Frames of the 2-byte types need only be 2-byte aligned: an odd N, an odd offset and an odd stride are
+ * legal.  The emission of token n in a frame is e[n]: the element widened exactly for log-probs; for logits
+ * (float)((double)x_n - lse), lse as fltx_s2s_step_typed defines it over the frame's N elements (an all-NaN frame and a
+ * frame whose maximum is -inf have lse = that maximum and no candidates).  Everything fltx_ctc_rows_step and the lexicon
+ * kind say about a frame -- the token beam with its ties to the lower token, the three CTC branches, the lexicon kind's
+ * blank and same-node candidates, NaN and -inf -- is said about this e; a decode is bit for bit the decode of
+ * fltx_ctc_rows_begin on the float32 matrix e.  No float32 copy of the emissions is made, on the device or on the host:
+ * a host buffer is staged in its own type (and stride), the token beams are taken from the typed frames in this call
+ * (one launch: a wave per frame up to the width fltx_decoder_get(dec, "emissions_narrow_max") reports, a workgroup per
+ * frame beyond it; fltx_decoder_set changes the width, 0 .. 1024), and the lexicon step reads its two emissions from the
+ * typed buffer with the frame's lse, which the decoder keeps in a buffer of its own.  A DEVICE buffer must stay valid
+ * and unchanged as fltx_ctc_rows_begin demands.
+ * frame_lse: NULL, or a DEVICE buffer of one double per frame of the call, utterance after utterance (the sum of the
+ * T[b]); logits mode writes each frame's lse there, log-probs mode leaves it untouched.
+ * FLTX_ERR_INVALID on a bad dtype or kind and on 0 < frame_stride < N; every other refusal is fltx_ctc_rows_begin's.
+ * Works on both CTC rows kinds; step, end, plan, the stream calls and the results keep their contracts. */
+FLTX_API int fltx_ctc_rows_begin_typed(fltx_decoder* dec, const void* emissions, int32_t dtype, int32_t kind,
+                                       int32_t on_device, const int64_t* offsets, int64_t frame_stride,
+                                       const int32_t* T, int32_t B, int32_t N, double* frame_lse, int32_t* next_token,
+                                       int32_t* next_src_row, int32_t* next_state, int32_t* n_rows);
 /* One frame of every utterance that has frames left (:41-123).  lm_scores: n_lm_rows rows of lm_width entries of
  * lm_dtype, row i at lm_scores + i * lm_row_stride ELEMENTS (lm_row_stride >= lm_width); lm_row_of (B*K int32, may be
  * NULL: identity, n_lm_rows taken as B*K) names the LM row of each decoder row -- one LM row can serve many.  An entry
@@ -589,6 +612,15 @@ FLTX_API int fltx_ctc_rows_stream_begin(fltx_decoder* dec, int32_t B, int32_t N,
  * fltx_ctc_rows_begin; FLTX_ERR_INVALID on a negative T[b]. */
 FLTX_API int fltx_ctc_rows_stream_append(fltx_decoder* dec, const float* emissions, int32_t on_device,
                                          const int64_t* offsets, const int32_t* T);
+/* fltx_ctc_rows_stream_append on a typed chunk, laid out and read as fltx_ctc_rows_begin_typed's emissions; frame_lse
+ * (NULL, or one double per frame of the CHUNK on the device, stream after stream) as there.  Each append names its own
+ * dtype, kind and stride: a stream may change them from chunk to chunk and may mix these appends with
+ * fltx_ctc_rows_stream_append.  A host chunk is staged in its own type before the call returns; a DEVICE chunk must stay
+ * valid and unchanged until the next append, end or begin has been queued.  FLTX_ERR_INVALID on a bad dtype or kind and
+ * on 0 < frame_stride < N; every other refusal is fltx_ctc_rows_stream_append's. */
+FLTX_API int fltx_ctc_rows_stream_append_typed(fltx_decoder* dec, const void* emissions, int32_t dtype, int32_t kind,
+                                               int32_t on_device, const int64_t* offsets, int64_t frame_stride,
+                                               const int32_t* T, double* frame_lse);
 /* prune(lookBack) of every stream (LexiconFreeDecoder.cpp:205-227, LexiconDecoder.cpp:304-325), no host
  * synchronisation.  findBestAncestor (Utils.h:268-310): from the first best of the current beam (strict >) look_back
  * frames up, for the lexicon kind further while the hypothesis is not complete (its parent ended no word), look_back + 100

@@ -149,6 +149,7 @@ class Lib:
         "fltx_lm_rows_create", "fltx_s2s_step_lm_rows",
         "fltx_lm_word_rows_create", "fltx_s2s_step_word_lm_rows",
         "fltx_ctc_rows_decoder_create", "fltx_ctc_rows_lex_decoder_create", "fltx_ctc_rows_begin", "fltx_ctc_rows_step", "fltx_ctc_rows_end",
+        "fltx_ctc_rows_begin_typed", "fltx_ctc_rows_stream_append_typed",
         "fltx_ctc_rows_stream_begin", "fltx_ctc_rows_stream_append", "fltx_ctc_rows_stream_prune",
         "fltx_ctc_rows_stream_frames_in_buffer", "fltx_ctc_rows_stream_collect",
         "fltx_ctc_rows_plan_begin", "fltx_ctc_rows_plan", "fltx_ctc_rows_plan_release",
@@ -239,6 +240,8 @@ class Lib:
             "fltx_ctc_rows_decoder_create": [vp, C.POINTER(Options), vp, i32, i32, pvp],
             "fltx_ctc_rows_lex_decoder_create": [vp, C.POINTER(Options), vp, vp, i32, i32, i32, i32, pvp],
             "fltx_ctc_rows_begin": [vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp],
+            "fltx_ctc_rows_begin_typed": [vp, vp, i32, i32, i32, vp, i64, vp, i32, i32, vp, vp, vp, vp, vp],
+            "fltx_ctc_rows_stream_append_typed": [vp, vp, i32, i32, i32, vp, i64, vp, vp],
             "fltx_ctc_rows_step": [vp, vp, i32, i32, i64, vp, i32, i32, vp, vp, vp, vp, vp],
             "fltx_ctc_rows_end": [vp, vp, i32, i32, i64, vp, i32, i32, vp],
             "fltx_ctc_rows_stream_begin": [vp, i32, i32, i32, vp, vp, vp, vp],
@@ -1043,6 +1046,11 @@ S2S_KINDS = {"log_probs": 0, "logits": 1}
 _NP_DTYPES = {DTYPE_F32: np.float32, DTYPE_F16: np.float16, DTYPE_BF16: np.uint16}
 
 
+def _torch_dtypes():
+    import torch
+    return {torch.float32: DTYPE_F32, torch.float16: DTYPE_F16, torch.bfloat16: DTYPE_BF16}
+
+
 class Seq2SeqBatchDecoder(BatchDecoder):
     """fltx_s2s_*: LexiconFreeSeq2SeqDecoder for B utterances at once, one device step per model call.
 
@@ -1372,14 +1380,76 @@ class CtcRowsBatchDecoder(BatchDecoder):
         if key == "max_states":  # (takes effect at the next begin: an open stream keeps its table)
             self._max_states = int(value)
 
-    def begin(self, emissions, T, N, offsets=None, device_ptr=None):
+    def _frames_in(self, emissions, dtype, kind, offsets, T, N):
+        """The typed forms of begin() / append() -> None for the float32 log-probs numpy route of the existing entry
+        points, else (the array kept alive, fltx_dtype, address, on_device, offsets, frame stride in elements)"""
+        if kind not in S2S_KINDS:
+            raise ValueError("kind: one of %s" % sorted(S2S_KINDS))
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        if hasattr(emissions, "data_ptr"):  # a torch tensor
+            dts = _torch_dtypes()
+            assert emissions.dtype in dts, "emissions: float32 / float16 / bfloat16"
+            e, dt = emissions, dts[emissions.dtype]
+            shape, strides = tuple(e.shape), tuple(e.stride())
+            ptr, on_dev = e.data_ptr(), 0 if e.device.type == "cpu" else 1
+        else:
+            if dtype is not None:
+                if dtype not in ("bf16", "bfloat16") or getattr(emissions, "dtype", None) != np.uint16:
+                    raise TypeError("dtype=%r: numpy emissions of bfloat16 bits are uint16 with dtype='bf16'" % (dtype,))
+                dt = DTYPE_BF16
+            elif getattr(emissions, "dtype", None) == np.float16:
+                dt = DTYPE_F16
+            elif kind == "log_probs":
+                return None
+            else:
+                dt = DTYPE_F32
+            e = np.asarray(emissions, dtype=_NP_DTYPES[dt])
+            if e.ndim < 2 or e.strides[-1] != e.itemsize or any(st % e.itemsize for st in e.strides):
+                e = np.ascontiguousarray(e).reshape(-1)  # (flat layout: frame after frame)
+            shape, strides = e.shape, tuple(st // e.itemsize for st in e.strides)
+            ptr, on_dev = e.ctypes.data, 1 if self._emu else 0
+        stride = N
+        if len(shape) > 1:
+            assert shape[-1] == N and strides[-1] == 1 and len(shape) <= 3, \
+                "emissions: [frames * N], [frames, N] or [B, T_max, N], unit column stride"
+            if len(shape) == 3:  # one plane per utterance, any plane and frame strides
+                assert shape[0] == len(T) and int(max(T, default=0)) <= shape[1] and off is None, \
+                    "emissions [B, T_max, N]: one plane per utterance, no offsets"
+                off = np.arange(len(T), dtype=np.int64) * strides[0]
+            stride = strides[-2] if shape[-2] > 1 else N
+        return e, dt, ptr, on_dev, off, stride
+
+    def _frame_lse_ptr(self, lse_out, T):
+        if lse_out is None:
+            return None
+        n = lse_out.size if isinstance(lse_out, np.ndarray) else lse_out.numel()
+        assert n >= int(np.sum(T)) and str(lse_out.dtype).endswith("float64"), "lse_out: sum(T) float64 on the device"
+        return self._addr(lse_out)
+
+    def begin(self, emissions, T, N, offsets=None, device_ptr=None, *, kind="log_probs", dtype=None, lse_out=None):
         """emissions: a host float32 array (flat layout, copied by the call), or None when device_ptr (int) addresses
-        emissions in HBM -- those must stay valid until end().  -> (token, src_row, state, n_rows): the roots."""
+        float32 log-probs in HBM -- those must stay valid until end(); both go through fltx_ctc_rows_begin.  Or the
+        acoustic model's output as it is (fltx_ctc_rows_begin_typed, no float32 copy is made): a torch tensor of
+        float32, float16 or bfloat16 on the device or the host with unit column stride -- [B, T_max, N] with any plane
+        and frame strides (utterance b reads its first T[b] frames), or [frames, N] / flat with `offsets` in elements --
+        a numpy float16 array, or numpy uint16 holding bfloat16 bits with dtype="bf16" (flat layout).  kind "logits":
+        the decoder takes each frame's log-softmax itself; lse_out (device float64, sum(T), utterance after utterance)
+        then receives each frame's log-sum-exp.  A device tensor is kept referenced until the next begin().
+        -> (token, src_row, state, n_rows): the roots."""
         T = np.ascontiguousarray(T, dtype=np.int32)
         self.B, self.N, self._T = len(T), int(N), T
-        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
         out = self._rows()
         ptrs = [self._addr(o) for o in out]
+        typed = None if device_ptr is not None else self._frames_in(emissions, dtype, kind, offsets, T, self.N)
+        if typed is not None:
+            e, dt, ptr, on_dev, off, stride = typed
+            self._chk(self.L.lib.fltx_ctc_rows_begin_typed(self.h, ptr, dt, S2S_KINDS[kind], on_dev, _ptr(off), stride,
+                                                           _ptr(T), self.B, self.N, self._frame_lse_ptr(lse_out, T),
+                                                           *ptrs))
+            self._emissions = e
+            return tuple(out)
+        assert kind == "log_probs" and dtype is None, "device_ptr: float32 log-probs"
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
         if device_ptr is not None:
             self._chk(self.L.lib.fltx_ctc_rows_begin(self.h, device_ptr, 1, _ptr(off), _ptr(T), self.B, self.N, *ptrs))
         else:
@@ -1400,12 +1470,23 @@ class CtcRowsBatchDecoder(BatchDecoder):
         self._stream_states = self._max_states
         return tuple(out)
 
-    def append(self, emissions, T, offsets=None, device_ptr=None):
+    def append(self, emissions, T, offsets=None, device_ptr=None, *, kind="log_probs", dtype=None, lse_out=None):
         """The next chunk: T[b] >= 0 frames of stream b; emissions a host float32 array (flat layout, copied by the
         call), or None when device_ptr (int) addresses the chunk in HBM -- that must stay valid until the next append()
-        or end().  -> the number of step() calls that consume the chunk (max T)."""
+        or end().  Or a typed chunk in the forms begin() takes, with kind / dtype / lse_out as there
+        (fltx_ctc_rows_stream_append_typed); every chunk names its own.  A device tensor is kept referenced until the
+        next append().  -> the number of step() calls that consume the chunk (max T)."""
         T = np.ascontiguousarray(T, dtype=np.int32)
         assert len(T) == self.B, "T: one entry per stream"
+        typed = None if device_ptr is not None else self._frames_in(emissions, dtype, kind, offsets, T, self.N)
+        if typed is not None:
+            e, dt, ptr, on_dev, off, stride = typed
+            self._chk(self.L.lib.fltx_ctc_rows_stream_append_typed(self.h, ptr, dt, S2S_KINDS[kind], on_dev, _ptr(off),
+                                                                   stride, _ptr(T), self._frame_lse_ptr(lse_out, T)))
+            self._emissions = e
+            self._T = T
+            return int(T.max()) if len(T) else 0
+        assert kind == "log_probs" and dtype is None, "device_ptr: float32 log-probs"
         off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
         if device_ptr is not None:
             self._chk(self.L.lib.fltx_ctc_rows_stream_append(self.h, device_ptr, 1, _ptr(off), _ptr(T)))
@@ -1489,13 +1570,16 @@ class CtcRowsBatchDecoder(BatchDecoder):
             raise RuntimeError("LM row store full: %d states got no row (row_capacity = lm_store.shape[0] is too "
                                "small; a stream can collect_every)" % int(counts[3]))
 
-    def decode_device(self, emissions, T, N, lm_store, lm_new, *, offsets=None, device_ptr=None, lm_kind="log_probs"):
+    def decode_device(self, emissions, T, N, lm_store, lm_new, *, offsets=None, device_ptr=None, lm_kind="log_probs",
+                      kind="log_probs", dtype=None, lse_out=None):
         """decode() without the host in the loop: lm_store is the caller's [row_capacity, >= lm_width] array of LM rows
         (a torch tensor on the context's device; numpy on the emulator library) and lm_new(p, n_new) writes its rows
         p.new_row[:n_new] -- row i the LM's scores after the state of row p.new_parent_row[i] (-1: the start) advanced
         by p.new_edge[i]; p.new_dec_row[i] // K is the utterance.  Per frame the host reads the plan's four counts and
-        nothing else.  RuntimeError "LM row store full" if a state got no row.  Returns results_batch()."""
-        lists = self.begin(emissions, T, N, offsets=offsets, device_ptr=device_ptr)
+        nothing else.  kind / dtype / lse_out: begin()'s.  RuntimeError "LM row store full" if a state got no row.
+        Returns results_batch()."""
+        lists = self.begin(emissions, T, N, offsets=offsets, device_ptr=device_ptr, kind=kind, dtype=dtype,
+                           lse_out=lse_out)
         self.plan_begin(lm_store.shape[0])
         for _ in range(int(self._T.max()) if self.B else 0):
             p, _c = self._planned(lists, lm_store, lm_new)
@@ -1506,8 +1590,8 @@ class CtcRowsBatchDecoder(BatchDecoder):
         return self.results_batch()
 
     def decode_stream_device(self, chunks, lm_store, lm_new, look_back=None, *, N=None, max_frames=None,
-                             collect_every=None, lm_kind="log_probs"):
-        """decode_stream() on decode_device()'s terms: chunks, look_back, N, max_frames and collect_every as there,
+                             collect_every=None, lm_kind="log_probs", kind="log_probs", dtype=None):
+        """decode_stream() on decode_device()'s terms: chunks, look_back, N, max_frames, collect_every, kind and dtype as there,
         lm_store and lm_new as in decode_device.  A collect's released ids go straight to plan_release() on the
         device: their rows of lm_store are handed out again.  Yields what decode_stream() yields."""
         N = self.N if N is None else int(N)
@@ -1520,7 +1604,7 @@ class CtcRowsBatchDecoder(BatchDecoder):
         chunk = first
         n_chunks = 0
         while chunk is not None:
-            for _ in range(self.append(chunk[0], chunk[1])):
+            for _ in range(self.append(chunk[0], chunk[1], **self._chunk_kw(chunk, kind, dtype))):
                 lists = self.step(lm_store, lm_row_of=p.lm_row_of, lm_kind=lm_kind)
                 p, counts = self._planned(lists, lm_store, lm_new)
             if look_back is not None:
@@ -1587,14 +1671,22 @@ class CtcRowsBatchDecoder(BatchDecoder):
         self._chk(self.L.lib.fltx_ctc_rows_end(self.h, *args))
         self._inputs = keep
 
-    def decode(self, emissions, T, N, lm_rows, *, offsets=None, device_ptr=None, lm_kind="log_probs"):
+    @staticmethod
+    def _chunk_kw(chunk, kind, dtype):
+        """append()'s keywords for a chunk: the stream's, or those the chunk's own third element names"""
+        return dict({"kind": kind, "dtype": dtype}, **(chunk[2] if len(chunk) > 2 else {}))
+
+    def decode(self, emissions, T, N, lm_rows, *, offsets=None, device_ptr=None, lm_kind="log_probs", kind="log_probs",
+               dtype=None, lse_out=None):
         """The whole batch from a callable: lm_rows(state_keys) -> rows, where state_keys is a list of (b, prefix) --
         utterance and the tuple of tokens the state stands for -- one per LM state the search has just entered, and
         rows is [len(state_keys), >= lm_width] (a torch tensor on the context's device; numpy on the emulator library),
         row i the LM's scores after state_keys[i].  One row is kept per state id and shared through lm_row_of, so the
-        LM runs once per state, however many hypotheses and frames are in it.  Returns results_batch().  (The rows are
+        LM runs once per state, however many hypotheses and frames are in it.  kind / dtype / lse_out: begin()'s -- the
+        acoustic model's fp16 / bf16 output or raw logits go in as they are.  Returns results_batch().  (The rows are
         read on the host once per frame to name the new states.)"""
-        tok, src, state, n = self.begin(emissions, T, N, offsets=offsets, device_ptr=device_ptr)
+        tok, src, state, n = self.begin(emissions, T, N, offsets=offsets, device_ptr=device_ptr, kind=kind, dtype=dtype,
+                                        lse_out=lse_out)
         lister = _RowLister(self, self.B, int(self.options.beam_size), lm_rows)
         for _ in range(int(self._T.max()) if self.B else 0):
             rows, ro = lister.rows(tok, src, state, n)
@@ -1604,9 +1696,10 @@ class CtcRowsBatchDecoder(BatchDecoder):
         return self.results_batch()
 
     def decode_stream(self, chunks, lm_rows, look_back=None, *, N=None, max_frames=None, lm_kind="log_probs",
-                      collect_every=None, on_release=None):
+                      collect_every=None, on_release=None, kind="log_probs", dtype=None):
         """B streams from an iterable of chunks, each (emissions, T): a host float32 array in flat layout and the B
-        frame counts (0 allowed).  lm_rows is decode()'s callable.  A generator: after every chunk it yields the list
+        frame counts (0 allowed) -- or emissions in any form append() takes, with kind / dtype for all chunks, or
+        (emissions, T, {"kind": ..., "dtype": ...}) for a chunk that names its own.  lm_rows is decode()'s callable.  A generator: after every chunk it yields the list
         of best(b) per stream -- after prune(look_back) when look_back is given -- and, when the chunks are used up,
         ends the streams and yields results_batch().  N: the token-set size (default: that of the last begin);
         max_frames: the frames a stream holds between prunes (default: 4096).
@@ -1626,7 +1719,7 @@ class CtcRowsBatchDecoder(BatchDecoder):
         chunk = first
         n_chunks = 0
         while chunk is not None:
-            for _ in range(self.append(chunk[0], chunk[1])):
+            for _ in range(self.append(chunk[0], chunk[1], **self._chunk_kw(chunk, kind, dtype))):
                 tok, src, state, n = self.step(args[0], lm_row_of=args[1], lm_kind=lm_kind)
                 args = lister.rows(tok, src, state, n)
             if look_back is not None:

@@ -33,6 +33,7 @@
 #include "fltx_s2s.h"
 #include "fltx_s2s_lex.h"
 #include "fltx_ctc_rows.h"
+#include "fltx_ctc_rows_typed.h"
 #include "fltx_ctc_rows_lex.h"
 #include "fltx_ctc_rows_stream.h"
 #include "fltx_transcript.h"
@@ -275,6 +276,24 @@ __global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_lex_end_kernel(
 __global__ void __launch_bounds__(kS2sBeginThreads) fltx_ctc_rows_lex_begin_kernel(CrlParams R) {
   crlBeginUtterance(R, nullptr);
 }
+/* fltx_ctc_rows_typed.h: the typed frame front end (fp16 / bf16 / float32 frames of any stride, log-probs or logits) --
+ * a wave per narrow frame, a workgroup per wide one -- and the lexicon step that reads its blank and same-node emissions
+ * from the typed frames */
+template <int DT, bool LOGITS>
+__global__ void __launch_bounds__(256) fltx_ctc_rows_typed_wave_kernel(CrTypedParams Z) {
+  __shared__ __attribute__((aligned(16))) CrTypedWaveLds fltx_crt_wave_lds[4];
+  crTypedWaveRows<DT, LOGITS>(Z, (char*)fltx_crt_wave_lds);
+}
+template <int DT, bool LOGITS>
+__global__ void __launch_bounds__(kS2sTypedThreads) fltx_ctc_rows_typed_wg_kernel(CrTypedParams Z) {
+  __shared__ __attribute__((aligned(16))) S2sTypedLds fltx_crt_wg_lds;
+  crTypedWgRows<DT, LOGITS>(Z, (char*)&fltx_crt_wg_lds);
+}
+template <int SRC, int DT, bool LOGITS>
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_lex_typed_step_kernel(CrlTypedParams Y) {
+  __shared__ __attribute__((aligned(16))) CrlStepLds fltx_crlt_step_lds;
+  crlStepTyped<SRC, DT, LOGITS>(Y, (char*)&fltx_crlt_step_lds);
+}
 /* fltx_ctc_rows_stream.h: streams on the two CTC rows kinds -- the start, the frame step and its finish variant on the
  * streams' own counts and history ring; getBestHypothesis and prune */
 __global__ void __launch_bounds__(kS2sBeginThreads) fltx_ctc_rows_stream_begin_kernel(CrStreamParams Z) {
@@ -300,6 +319,11 @@ template <int SRC>
 __global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_lex_stream_end_kernel(CrlStreamParams Z) {
   __shared__ __attribute__((aligned(16))) CrlStepLds fltx_crls_end_lds;
   crlsStepStream<SRC, true>(Z, (char*)&fltx_crls_end_lds);
+}
+template <int SRC, int DT, bool LOGITS>
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_lex_typed_stream_step_kernel(CrlTypedStreamParams Y) {
+  __shared__ __attribute__((aligned(16))) CrlStepLds fltx_crlts_step_lds;
+  crlsStepStreamTyped<SRC, DT, LOGITS>(Y, (char*)&fltx_crlts_step_lds);
 }
 template <bool LEX>
 __global__ void __launch_bounds__(kCrsOpThreads) fltx_ctc_rows_stream_best_kernel(CrsOpParams W) {
@@ -886,6 +910,15 @@ struct fltx_decoder {
     DBuf crMeta, crEmis;
     std::vector<int64_t> crMetaHost;
     const float* crEmisDev = nullptr;
+    /* typed emissions (fltx_ctc_rows_begin_typed / _stream_append_typed, fltx_ctc_rows_typed.h) of the batch or the
+     * current chunk: the dtype (kCrEmPlain: the float32 log-probs above), logits, the frame stride in elements, the
+     * frames on the device (crEmis holds a host buffer's copy in its own type), each frame record's lse, and the
+     * widest frame the wave-per-frame front end takes ("emissions_narrow_max") */
+    int crEmDt = kCrEmPlain, crNarrowMax = kCrTypedNarrowMax;
+    bool crEmLogits = false;
+    int64_t crEmStride = 0;
+    const void* crEmX = nullptr;
+    DBuf crLse;
     /* lexicon CTC with a rows LM (kind FLTX_DECODER_LEX_CTC_ROWS, fltx_ctc_rows_lex.h; the compact trie, slots = S,
      * isLmToken and rowNode above are its too): the publisher's beam index, which is nobody's output */
     DBuf crOutBeam;
@@ -2117,6 +2150,8 @@ int fltx_decoder_get(fltx_decoder* d, const char* key, int64_t* value) {
     /* "time_transcripts": device time of the last fltx_result_transcripts' three kernels / of the last
      * fltx_pack_results_kernel (HIP events around each; 0 when not timed or not launched) */
     *value = (int64_t)((double)d->tr.ms[trTimedSlot(key)] * 1e6 + 0.5);
+  } else if (!strcmp(key, "emissions_narrow_max")) { /* see fltx_decoder_set */
+    *value = d->s2s.crNarrowMax;
   } else if (!strcmp(key, "ws_bytes")) { /* d->wsBytes: the workspace bytes of one utterance that prepare() sized */
     *value = (int64_t)d->wsBytes;
   } else {
@@ -2139,6 +2174,13 @@ int fltx_decoder_set(fltx_decoder* d, const char* key, int64_t value) {
                                     "fltx_ctc_rows_lex_decoder_create) and a count >= 1");
     }
     d->s2s.maxStates = (int)value;
+    return FLTX_OK;
+  }
+  if (!strcmp(key, "emissions_narrow_max")) { /* a CTC rows decoder: the widest typed frame a wave takes (0: none) */
+    if (!isCrKind(d->kind) || value < 0 || value > kCrTypedNarrowCap) {
+      return fail(FLTX_ERR_INVALID, "emissions_narrow_max: a CTC rows decoder and a width in [0, %d]", kCrTypedNarrowCap);
+    }
+    d->s2s.crNarrowMax = (int)value;
     return FLTX_OK;
   }
   if (!strcmp(key, "time_transcripts")) { /* measurement: see fltx_decoder_get "transcript_count_ns" */
@@ -6534,9 +6576,109 @@ static CrsParams crsParams(fltx_decoder* d) {
   return X;
 }
 
-/* decodeBegin of a batch (maxFrames < 0: fltx_ctc_rows_begin) or of B streams that hold up to maxFrames frames each
- * (fltx_ctc_rows_stream_begin; T: null) */
-static int crBegin(fltx_decoder* d, const char* what, const float* emissions, int32_t onDevice, const int64_t* offsets,
+/* the emissions of a begin or an append: float32 log-probs, frame after frame (dt == kCrEmPlain: fltx_ctc_rows_begin,
+ * fltx_ctc_rows_stream_append), or typed frames (fltx_ctc_rows_begin_typed, fltx_ctc_rows_stream_append_typed) */
+struct CrEmIn {
+  const void* x = nullptr;
+  int dt = kCrEmPlain; /* else a fltx_dtype */
+  int kind = FLTX_S2S_LOG_PROBS;
+  int64_t stride = 0;  /* elements between two frames; 0: N */
+  double* frameLse = nullptr;
+  size_t elem() const { return dt == kCrEmPlain || dt == FLTX_DTYPE_F32 ? 4 : 2; }
+};
+
+static int crEmCheck(const char* what, const CrEmIn& in) {
+  if (in.dt != kCrEmPlain && in.dt != FLTX_DTYPE_F32 && in.dt != FLTX_DTYPE_F16 && in.dt != FLTX_DTYPE_BF16) {
+    return fail(FLTX_ERR_INVALID, "%s: dtype %d", what, in.dt);
+  }
+  if (in.kind != FLTX_S2S_LOG_PROBS && in.kind != FLTX_S2S_LOGITS) {
+    return fail(FLTX_ERR_INVALID, "%s: kind %d", what, in.kind);
+  }
+  return FLTX_OK;
+}
+
+/* the frames on the device: a host buffer is copied, in its own type and with its own stride, utterance after utterance
+ * (meta: frameOff[B + 1], emOff[B] as the kernels read them); then the decoder reads these emissions until the next
+ * begin or append */
+static int crEmStage(fltx_decoder* d, const char* what, const CrEmIn& in, int64_t stride, int32_t onDevice, bool packed,
+                     const int64_t* offsets, const int32_t* T, int64_t frames, Stream st) {
+  const int B = d->B, N = d->N;
+  const std::vector<int64_t>& meta = d->s2s.crMetaHost;
+  const void* x = in.x;
+  if (!onDevice && frames > 0) {
+    const size_t es = in.elem();
+    char* dst = (char*)d->s2s.crEmis.p;
+    const char* src = (const char*)in.x;
+    int bad = 0;
+    if (packed) { /* (the last frame ends after N elements, not after a stride) */
+      bad = devCopyH2D(dst, src + es * (size_t)(offsets ? offsets[0] : 0), es * (size_t)((frames - 1) * stride + N), st);
+    } else {
+      for (int b = 0; b < B && !bad; ++b) {
+        if (T[b] > 0) {
+          bad = devCopyH2D(dst + es * (size_t)(meta[(size_t)b] * stride), src + es * (size_t)offsets[b],
+                           es * (size_t)((int64_t)(T[b] - 1) * stride + N), st);
+        }
+      }
+    }
+    if (bad || devSync(st)) { /* (the caller's buffer is only borrowed for the call) */
+      return fail(FLTX_ERR_HIP, "%s: emission upload failed", what);
+    }
+    x = dst;
+  }
+  d->s2s.crEmDt = in.dt;
+  d->s2s.crEmLogits = in.kind == FLTX_S2S_LOGITS;
+  d->s2s.crEmStride = stride;
+  d->s2s.crEmX = x;
+  d->s2s.crEmisDev = in.dt == kCrEmPlain ? (const float*)x : nullptr;
+  return FLTX_OK;
+}
+
+static CrTypedEm crTypedEm(fltx_decoder* d) {
+  CrTypedEm E;
+  E.x = d->s2s.crEmX;
+  E.stride = d->s2s.crEmStride;
+  E.lse = d->s2s.crLse.as<double>();
+  return E;
+}
+
+extern "C++" {
+template <int DT, bool LOGITS>
+static int crTypedFrontLaunch(fltx_decoder* d, int64_t frames, Stream st, const CrTypedParams& Z) {
+  if (d->N <= d->s2s.crNarrowMax) {
+    S2S_LAUNCH((fltx_ctc_rows_typed_wave_kernel<DT, LOGITS>), (crTypedWaveRows<DT, LOGITS>), (int)((frames + 3) / 4), 256,
+               4 * sizeof(CrTypedWaveLds), st, Z);
+  } else {
+    S2S_LAUNCH((fltx_ctc_rows_typed_wg_kernel<DT, LOGITS>), (crTypedWgRows<DT, LOGITS>), (int)frames, kS2sTypedThreads,
+               sizeof(S2sTypedLds), st, Z);
+  }
+  return FLTX_OK;
+}
+}
+
+/* the token beams of the call's frames: one launch */
+static int crFrontEnd(fltx_decoder* d, int64_t frames, Stream st, const CrParams& Q, double* frameLse) {
+  if (d->s2s.crEmDt == kCrEmPlain) {
+    S2S_LAUNCH(fltx_ctc_rows_tokbeam_kernel, crTokBeamRows, (int)((frames + 3) / 4), 256, 4 * sizeof(S2sFrontLds), st, Q);
+    return FLTX_OK;
+  }
+  CrTypedParams Z;
+  memset(&Z, 0, sizeof(Z));
+  Z.c = Q;
+  Z.e = crTypedEm(d);
+  Z.lseOut = frameLse;
+  switch (d->s2s.crEmDt * 2 + (d->s2s.crEmLogits ? 1 : 0)) {
+    case 0: return crTypedFrontLaunch<kS2sDtF32, false>(d, frames, st, Z);
+    case 1: return crTypedFrontLaunch<kS2sDtF32, true>(d, frames, st, Z);
+    case 2: return crTypedFrontLaunch<kS2sDtF16, false>(d, frames, st, Z);
+    case 3: return crTypedFrontLaunch<kS2sDtF16, true>(d, frames, st, Z);
+    case 4: return crTypedFrontLaunch<kS2sDtBf16, false>(d, frames, st, Z);
+    default: return crTypedFrontLaunch<kS2sDtBf16, true>(d, frames, st, Z);
+  }
+}
+
+/* decodeBegin of a batch (maxFrames < 0: fltx_ctc_rows_begin, fltx_ctc_rows_begin_typed) or of B streams that hold up to
+ * maxFrames frames each (fltx_ctc_rows_stream_begin; T: null) */
+static int crBegin(fltx_decoder* d, const char* what, const CrEmIn& in, int32_t onDevice, const int64_t* offsets,
                    const int32_t* T, int32_t B, int32_t N, int32_t maxFrames, int32_t* nextTok, int32_t* nextSrc,
                    int32_t* nextState, int32_t* nRows) {
   DeviceScope devScope(d ? d->ctx : nullptr);
@@ -6544,9 +6686,10 @@ static int crBegin(fltx_decoder* d, const char* what, const float* emissions, in
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
   int rc = crCheck(d, what);
-  if (rc) {
+  if (rc || (rc = crEmCheck(what, in))) {
     return rc;
   }
+  const void* emissions = in.x;
   const bool stream = maxFrames >= 0;
   if (B < 1 || N < 1 || (!T && !stream) || (stream && maxFrames < 1) || !nextTok || !nextSrc || !nextState || !nRows) {
     return fail(FLTX_ERR_INVALID, "%s: bad argument", what);
@@ -6559,6 +6702,10 @@ static int crBegin(fltx_decoder* d, const char* what, const float* emissions, in
   if (N > kS2sMaxV) {
     return fail(FLTX_ERR_UNSUPPORTED, "CTC rows: N = %d > %d", N, kS2sMaxV);
   }
+  if (in.stride != 0 && in.stride < N) {
+    return fail(FLTX_ERR_INVALID, "%s: frame_stride %lld < N = %d", what, (long long)in.stride, N);
+  }
+  const int64_t stride = in.stride ? in.stride : N;
   const int K = d->opt.beam_size, cap = std::min(d->opt.beam_size_token, N);
   if (cap > kS2lMaxKt) {
     return fail(FLTX_ERR_UNSUPPORTED, "CTC rows: a token beam of %d (beam_size_token, N = %d) > %d", cap, N, kS2lMaxKt);
@@ -6591,8 +6738,8 @@ static int crBegin(fltx_decoder* d, const char* what, const float* emissions, in
       return fail(FLTX_ERR_INVALID, "T[%d] = %d is negative", b, T[b]);
     }
     meta[(size_t)b] = frames;
-    packed = packed && (!offsets || offsets[b] == frames * N);
-    meta[(size_t)B + 1 + b] = onDevice && offsets ? offsets[b] : frames * N;
+    packed = packed && (!offsets || offsets[b] == frames * stride);
+    meta[(size_t)B + 1 + b] = onDevice && offsets ? offsets[b] : frames * stride;
     hT[b] = T[b];
     d->histOff[(size_t)b] = off;
     off += (int64_t)(stream ? ring : T[b] + 2) * K; /* (a stream's results: frames in buffer + 1 <= ring entries) */
@@ -6637,7 +6784,8 @@ static int crBegin(fltx_decoder* d, const char* what, const float* emissions, in
       d->s2s.sVal.ensure(4 * (size_t)B * d->s2s.sSize, st, false) || d->s2s.sCount.ensure(4 * (size_t)B, st, false) ||
       d->s2s.status.ensure(4 * (size_t)B, st, false) || d->s2s.merges.ensure(4 * (size_t)B, st, false) ||
       d->s2s.crMeta.ensure(8 * meta.size(), st, false) ||
-      (!onDevice && d->s2s.crEmis.ensure(4 * nF * N, st, false))) {
+      (!onDevice && d->s2s.crEmis.ensure(in.elem() * nF * (size_t)stride, st, false)) ||
+      (in.kind == FLTX_S2S_LOGITS && d->s2s.crLse.ensure(8 * nF, st, false))) {
     return fail(FLTX_ERR_OOM, "CTC rows workspace: device allocation failed (B=%d K=%d N=%d, %lld frames)", B, K, N,
                 (long long)frames);
   }
@@ -6645,26 +6793,11 @@ static int crBegin(fltx_decoder* d, const char* what, const float* emissions, in
       devCopyH2D(d->s2s.crMeta.p, meta.data(), 8 * meta.size(), st)) {
     return fail(FLTX_ERR_HIP, "CTC rows: upload failed");
   }
-  d->s2s.crEmisDev = emissions;
-  if (!onDevice && frames > 0) { /* host emissions: copied here, utterance after utterance */
-    float* dst = d->s2s.crEmis.as<float>();
-    int bad = 0;
-    if (packed) {
-      bad = devCopyH2D(dst, emissions + (offsets ? offsets[0] : 0), 4 * (size_t)frames * N, st);
-    } else {
-      for (int b = 0; b < B && !bad; ++b) {
-        if (T[b] > 0) {
-          bad = devCopyH2D(dst + meta[(size_t)b] * N, emissions + offsets[b], 4 * (size_t)T[b] * N, st);
-        }
-      }
-    }
-    if (bad || devSync(st)) { /* (the caller's buffer is only borrowed for the call) */
-      return fail(FLTX_ERR_HIP, "CTC rows: emission upload failed");
-    }
-    d->s2s.crEmisDev = dst;
-  }
   d->B = B;
   d->N = N;
+  if ((rc = crEmStage(d, what, in, stride, onDevice, packed, offsets, T, frames, st))) {
+    return rc;
+  }
   d->s2s.t = 0;
   d->s2s.crMaxT = maxT;
   d->s2s.crFrames = frames;
@@ -6696,8 +6829,8 @@ static int crBegin(fltx_decoder* d, const char* what, const float* emissions, in
     }
     return FLTX_OK;
   }
-  if (frames > 0) {
-    S2S_LAUNCH(fltx_ctc_rows_tokbeam_kernel, crTokBeamRows, (int)((frames + 3) / 4), 256, 4 * sizeof(S2sFrontLds), st, Q);
+  if (frames > 0 && (rc = crFrontEnd(d, frames, st, Q, in.frameLse))) {
+    return rc;
   }
   if (lex) {
     const CrlParams R = crlParams(d, Q);
@@ -6713,7 +6846,21 @@ static int crBegin(fltx_decoder* d, const char* what, const float* emissions, in
 int fltx_ctc_rows_begin(fltx_decoder* d, const float* emissions, int32_t onDevice, const int64_t* offsets,
                         const int32_t* T, int32_t B, int32_t N, int32_t* nextTok, int32_t* nextSrc, int32_t* nextState,
                         int32_t* nRows) {
-  return crBegin(d, "fltx_ctc_rows_begin", emissions, onDevice, offsets, T, B, N, -1, nextTok, nextSrc, nextState, nRows);
+  CrEmIn in;
+  in.x = emissions;
+  return crBegin(d, "fltx_ctc_rows_begin", in, onDevice, offsets, T, B, N, -1, nextTok, nextSrc, nextState, nRows);
+}
+
+int fltx_ctc_rows_begin_typed(fltx_decoder* d, const void* emissions, int32_t dtype, int32_t kind, int32_t onDevice,
+                              const int64_t* offsets, int64_t frameStride, const int32_t* T, int32_t B, int32_t N,
+                              double* frameLse, int32_t* nextTok, int32_t* nextSrc, int32_t* nextState, int32_t* nRows) {
+  CrEmIn in;
+  in.x = emissions;
+  in.dt = dtype == kCrEmPlain ? -2 : dtype; /* (no dtype of the ABI means "plain") */
+  in.kind = kind;
+  in.stride = frameStride;
+  in.frameLse = frameLse;
+  return crBegin(d, "fltx_ctc_rows_begin_typed", in, onDevice, offsets, T, B, N, -1, nextTok, nextSrc, nextState, nRows);
 }
 
 int fltx_ctc_rows_stream_begin(fltx_decoder* d, int32_t B, int32_t N, int32_t maxFrames, int32_t* nextTok,
@@ -6723,7 +6870,7 @@ int fltx_ctc_rows_stream_begin(fltx_decoder* d, int32_t B, int32_t N, int32_t ma
     int rc = crCheck(d, "fltx_ctc_rows_stream_begin");
     return rc ? rc : fail(FLTX_ERR_INVALID, "fltx_ctc_rows_stream_begin: max_frames = %d (>= 1)", maxFrames);
   }
-  return crBegin(d, "fltx_ctc_rows_stream_begin", nullptr, 1, nullptr, nullptr, B, N, maxFrames, nextTok, nextSrc,
+  return crBegin(d, "fltx_ctc_rows_stream_begin", CrEmIn(), 1, nullptr, nullptr, B, N, maxFrames, nextTok, nextSrc,
                  nextState, nRows);
 }
 
@@ -6825,6 +6972,34 @@ static int crLmRowsIn(fltx_decoder* d, const char* what, bool fin, bool idle, co
   }
 }
 
+/* the lexicon kind's frame step on typed emissions (fltx_ctc_rows_typed.h): an instantiation per (LM level, dtype, kind) */
+extern "C++" {
+template <int SRC, int DT, bool LOGITS>
+static int crlTypedStepLaunch(fltx_decoder* d, const CrParams& Q) {
+  if (d->s2s.crStream) {
+    const CrlTypedStreamParams Y = {crlParams(d, Q), crsParams(d), crTypedEm(d)};
+    S2S_LAUNCH((fltx_ctc_rows_lex_typed_stream_step_kernel<SRC, DT, LOGITS>), (crlsStepStreamTyped<SRC, DT, LOGITS>), d->B,
+               kS2sStepThreads, sizeof(CrlStepLds), d->ctx->stream, Y);
+  } else {
+    const CrlTypedParams Y = {crlParams(d, Q), crTypedEm(d)};
+    S2S_LAUNCH((fltx_ctc_rows_lex_typed_step_kernel<SRC, DT, LOGITS>), (crlStepTyped<SRC, DT, LOGITS>), d->B,
+               kS2sStepThreads, sizeof(CrlStepLds), d->ctx->stream, Y);
+  }
+  return FLTX_OK;
+}
+template <int SRC>
+static int crlTypedStep(fltx_decoder* d, const CrParams& Q) {
+  switch (d->s2s.crEmDt * 2 + (d->s2s.crEmLogits ? 1 : 0)) {
+    case 0: return crlTypedStepLaunch<SRC, kS2sDtF32, false>(d, Q);
+    case 1: return crlTypedStepLaunch<SRC, kS2sDtF32, true>(d, Q);
+    case 2: return crlTypedStepLaunch<SRC, kS2sDtF16, false>(d, Q);
+    case 3: return crlTypedStepLaunch<SRC, kS2sDtF16, true>(d, Q);
+    case 4: return crlTypedStepLaunch<SRC, kS2sDtBf16, false>(d, Q);
+    default: return crlTypedStepLaunch<SRC, kS2sDtBf16, true>(d, Q);
+  }
+}
+}
+
 int fltx_ctc_rows_step(fltx_decoder* d, const void* lmScores, int32_t lmDtype, int32_t lmKind, int64_t lmRowStride,
                        const int32_t* lmRowOf, int32_t nLmRows, int32_t onDevice, double* lmRowLse, int32_t* nextTok,
                        int32_t* nextSrc, int32_t* nextState, int32_t* nRows) {
@@ -6853,7 +7028,11 @@ int fltx_ctc_rows_step(fltx_decoder* d, const void* lmScores, int32_t lmDtype, i
     return rc;
   }
   d->s2s.crBestLb = -1;
-  if (d->s2s.crStream) { /* the same step on the streams' own counts (fltx_ctc_rows_stream.h) */
+  if (d->kind == FLTX_DECODER_LEX_CTC_ROWS && d->s2s.crEmDt != kCrEmPlain) {
+    if ((rc = d->s2s.isLmToken ? crlTypedStep<kCrlLmTokenRows>(d, Q) : crlTypedStep<kCrlLmWordRows>(d, Q))) {
+      return rc;
+    }
+  } else if (d->s2s.crStream) { /* the same step on the streams' own counts (fltx_ctc_rows_stream.h) */
     if (d->kind == FLTX_DECODER_LEX_CTC_ROWS) {
       const CrlStreamParams Z = {crlParams(d, Q), crsParams(d)};
       if (d->s2s.isLmToken) {
@@ -6990,28 +7169,33 @@ static int crsReadCounts(fltx_decoder* d, std::vector<int32_t>& cnt) {
   return FLTX_OK;
 }
 
-int fltx_ctc_rows_stream_append(fltx_decoder* d, const float* emissions, int32_t onDevice, const int64_t* offsets,
-                                const int32_t* T) {
+static int crsAppend(fltx_decoder* d, const char* what, const CrEmIn& in, int32_t onDevice, const int64_t* offsets,
+                     const int32_t* T) {
   DeviceScope devScope(d ? d->ctx : nullptr);
   if (devScope.failed) {
     return fail(FLTX_ERR_HIP, "hipSetDevice failed");
   }
-  int rc = crsCheck(d, "fltx_ctc_rows_stream_append");
-  if (rc) {
+  int rc = crsCheck(d, what);
+  if (rc || (rc = crEmCheck(what, in))) {
     return rc;
   }
   if (!T) {
-    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_stream_append: bad argument");
+    return fail(FLTX_ERR_INVALID, "%s: bad argument", what);
   }
+  const void* emissions = in.x;
   const int B = d->B, N = d->N, cap = d->s2s.cap;
+  if (in.stride != 0 && in.stride < N) {
+    return fail(FLTX_ERR_INVALID, "%s: frame_stride %lld < N = %d", what, (long long)in.stride, N);
+  }
+  const int64_t stride = in.stride ? in.stride : N;
   for (int b = 0; b < B; ++b) {
     if (T[b] < 0) {
       return fail(FLTX_ERR_INVALID, "T[%d] = %d is negative", b, T[b]);
     }
   }
   if (d->s2s.t < d->s2s.crMaxT) {
-    return fail(FLTX_ERR_STATE, "fltx_ctc_rows_stream_append: %d frames of the previous chunk are unstepped "
-                                "(fltx_ctc_rows_step)", d->s2s.crMaxT - d->s2s.t);
+    return fail(FLTX_ERR_STATE, "%s: %d frames of the previous chunk are unstepped (fltx_ctc_rows_step)", what,
+                d->s2s.crMaxT - d->s2s.t);
   }
   std::vector<int32_t>& buf = d->s2s.crBuf;
   for (int pass = 0; pass < 2; ++pass) {
@@ -7049,42 +7233,29 @@ int fltx_ctc_rows_stream_append(fltx_decoder* d, const float* emissions, int32_t
   bool packed = true;
   for (int b = 0; b < B; ++b) {
     meta[(size_t)b] = frames;
-    packed = packed && (!offsets || offsets[b] == frames * N);
-    meta[(size_t)B + 1 + b] = onDevice && offsets ? offsets[b] : frames * N;
+    packed = packed && (!offsets || offsets[b] == frames * stride);
+    meta[(size_t)B + 1 + b] = onDevice && offsets ? offsets[b] : frames * stride;
     hT[b] = T[b];
     frames += T[b];
     maxT = std::max(maxT, T[b]);
   }
   meta[(size_t)B] = frames;
   if (frames > 0 && !emissions) {
-    return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_stream_append: null emissions");
+    return fail(FLTX_ERR_INVALID, "%s: null emissions", what);
   }
   Stream st = d->ctx->stream;
   const size_t nF = (size_t)std::max<int64_t>(frames, 1);
   if (d->s2s.recTok.ensure(4 * nF * cap, st, false) || d->s2s.recAm.ensure(4 * nF * cap, st, false) ||
-      d->s2s.recN.ensure(4 * nF, st, false) || (!onDevice && d->s2s.crEmis.ensure(4 * nF * N, st, false))) {
+      d->s2s.recN.ensure(4 * nF, st, false) ||
+      (!onDevice && d->s2s.crEmis.ensure(in.elem() * nF * (size_t)stride, st, false)) ||
+      (in.kind == FLTX_S2S_LOGITS && d->s2s.crLse.ensure(8 * nF, st, false))) {
     return fail(FLTX_ERR_OOM, "CTC rows stream: device allocation failed (%lld frames)", (long long)frames);
   }
   if (devCopyH2D(d->s2s.crMeta.p, meta.data(), 8 * meta.size(), st)) {
     return fail(FLTX_ERR_HIP, "CTC rows stream: upload failed");
   }
-  d->s2s.crEmisDev = emissions;
-  if (!onDevice && frames > 0) { /* a host chunk: copied here, stream after stream */
-    float* dst = d->s2s.crEmis.as<float>();
-    int bad = 0;
-    if (packed) {
-      bad = devCopyH2D(dst, emissions + (offsets ? offsets[0] : 0), 4 * (size_t)frames * N, st);
-    } else {
-      for (int b = 0; b < B && !bad; ++b) {
-        if (T[b] > 0) {
-          bad = devCopyH2D(dst + meta[(size_t)b] * N, emissions + offsets[b], 4 * (size_t)T[b] * N, st);
-        }
-      }
-    }
-    if (bad || devSync(st)) { /* (the caller's buffer is only borrowed for the call) */
-      return fail(FLTX_ERR_HIP, "CTC rows stream: emission upload failed");
-    }
-    d->s2s.crEmisDev = dst;
+  if ((rc = crEmStage(d, what, in, stride, onDevice, packed, offsets, T, frames, st))) { /* (a host chunk is copied here) */
+    return rc;
   }
   d->s2s.t = 0;
   d->s2s.crMaxT = maxT;
@@ -7094,10 +7265,28 @@ int fltx_ctc_rows_stream_append(fltx_decoder* d, const float* emissions, int32_t
     buf[(size_t)b] += T[b];
   }
   if (frames > 0) {
-    CrParams Q = crParams(d);
-    S2S_LAUNCH(fltx_ctc_rows_tokbeam_kernel, crTokBeamRows, (int)((frames + 3) / 4), 256, 4 * sizeof(S2sFrontLds), st, Q);
+    return crFrontEnd(d, frames, st, crParams(d), in.frameLse);
   }
   return FLTX_OK;
+}
+
+int fltx_ctc_rows_stream_append(fltx_decoder* d, const float* emissions, int32_t onDevice, const int64_t* offsets,
+                                const int32_t* T) {
+  CrEmIn in;
+  in.x = emissions;
+  return crsAppend(d, "fltx_ctc_rows_stream_append", in, onDevice, offsets, T);
+}
+
+int fltx_ctc_rows_stream_append_typed(fltx_decoder* d, const void* emissions, int32_t dtype, int32_t kind,
+                                      int32_t onDevice, const int64_t* offsets, int64_t frameStride, const int32_t* T,
+                                      double* frameLse) {
+  CrEmIn in;
+  in.x = emissions;
+  in.dt = dtype == kCrEmPlain ? -2 : dtype; /* (no dtype of the ABI means "plain") */
+  in.kind = kind;
+  in.stride = frameStride;
+  in.frameLse = frameLse;
+  return crsAppend(d, "fltx_ctc_rows_stream_append_typed", in, onDevice, offsets, T);
 }
 
 static CrsOpParams crsOpParams(fltx_decoder* d, int lookBack) {

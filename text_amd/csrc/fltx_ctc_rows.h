@@ -145,15 +145,9 @@ FLTX_DEV void crsStepDone(const CrParams& Q, const CrsParams& X, int b, int nd, 
 }
 
 /* ---- front end: the token beam of every frame, once ------------------------------------------------------------------ */
-/* workgroup = four waves, wave = frame record fr of the batch */
-FLTX_DEV void crTokBeamRows(const CrParams& Q, char* smem) {
-  const S2sParams& P = Q.s;
-  const int wave = waveUniform(waveId());
-  const int64_t fr = (int64_t)blockIdx.x * ((int)blockDim.x >> 6) + wave;
-  if (fr >= Q.frameOff[P.B]) {
-    return;
-  }
-  int lo = 0, hi = P.B - 1; /* the last utterance whose first record is <= fr (utterances without frames share theirs) */
+/* the utterance of frame record fr: the last one whose first record is <= fr (utterances without frames share theirs) */
+FLTX_DEV int crFrameUtterance(const CrParams& Q, int64_t fr) {
+  int lo = 0, hi = Q.s.B - 1;
   while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
     if (Q.frameOff[mid] <= fr) {
@@ -162,7 +156,18 @@ FLTX_DEV void crTokBeamRows(const CrParams& Q, char* smem) {
       hi = mid - 1;
     }
   }
-  const int b = waveUniform(lo);
+  return waveUniform(lo);
+}
+
+/* workgroup = four waves, wave = frame record fr of the batch */
+FLTX_DEV void crTokBeamRows(const CrParams& Q, char* smem) {
+  const S2sParams& P = Q.s;
+  const int wave = waveUniform(waveId());
+  const int64_t fr = (int64_t)blockIdx.x * ((int)blockDim.x >> 6) + wave;
+  if (fr >= Q.frameOff[P.B]) {
+    return;
+  }
+  const int b = crFrameUtterance(Q, fr);
   const float* row = Q.emissions + Q.emOff[b] + (fr - Q.frameOff[b]) * (int64_t)P.V;
   S2sFrontLds& S = ((S2sFrontLds*)smem)[wave];
   s2sTokBeamRow(P, S, row, P.recTok + fr * P.cap, P.recAm + fr * P.cap, P.recN + fr);

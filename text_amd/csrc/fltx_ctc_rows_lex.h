@@ -172,9 +172,9 @@ struct CrlStepLds {
 /* candidate j of the utterance (LexiconDecoder.cpp:55-213, the same double operations in the same order): hypothesis
  * k = j / per, slot q = j % per -- q < cap * (1 + S): entry e = q / (1 + S) of the frame's record, sub-slot 0 the move,
  * 1.. the word ends; then the same node and blank.  FIN: hypothesis j, decodeEnd's (:241-262).  false: none */
-template <int SRC, bool FIN>
-FLTX_DEV bool crlCand(const CrlParams& R, const CrlHyp* prev, const float* em, int64_t fr, int nE, int64_t rb, int nice,
-                      int64_t j, CrlCand& c) {
+template <int SRC, bool FIN, int EM = kCrEmPlain, bool LOGITS = false>
+FLTX_DEV bool crlCand(const CrlParams& R, const CrlHyp* prev, const void* em, double lse, int64_t fr, int nE, int64_t rb,
+                      int nice, int64_t j, CrlCand& c) {
   const CrParams& Q = R.c;
   const S2sParams& P = Q.s;
   const int cap = P.cap;
@@ -211,7 +211,7 @@ FLTX_DEV bool crlCand(const CrlParams& R, const CrlHyp* prev, const float* em, i
         }
         n = h.node == 0 ? Q.sil : h.token;
       }
-      const float a = em[n];
+      const float a = crEmission<EM, LOGITS>(em, n, lse);
       double score = h.score + (double)a;
       if (q == cap * S1 && n == Q.sil) {
         score += Q.silScore;
@@ -308,8 +308,12 @@ struct CrlRowState {
   __device__ __forceinline__ void none(int64_t r) const { outState[r] = -1; }
 };
 
-template <int SRC, bool FIN, bool STREAM = false>
-FLTX_DEV void crlStepUtterance(const CrlParams& R, char* smem, const CrsParams* Z = nullptr) {
+/* EM / LOGITS: what the frame's emissions are read as (kCrEmPlain: the float32 log-probs of fltx_ctc_rows_begin; a
+ * dtype: the typed frames E names, fltx_ctc_rows_typed.h) -- compile-time, so that the plain step stays the code it was */
+template <int SRC, bool FIN, bool STREAM = false, int EM = kCrEmPlain, bool LOGITS = false>
+FLTX_DEV void crlStepUtterance(const CrlParams& R, char* smem, const CrsParams* Z = nullptr,
+                               const CrTypedEm* E = nullptr) {
+  static_assert(!FIN || EM == kCrEmPlain, "decodeEnd reads no emissions");
   const CrParams& Q = R.c;
   const S2sParams& P = Q.s;
   CrlStepLds& X = *(CrlStepLds*)smem;
@@ -364,7 +368,16 @@ FLTX_DEV void crlStepUtterance(const CrlParams& R, char* smem, const CrsParams* 
   int32_t* mTab = Q.mTab + (size_t)b * Q.mSize;
   const int64_t fr = Q.frameOff[b] + (FIN ? 0 : P.t);
   const int nE = FIN ? 1 : P.recN[fr];
-  const float* em = Q.emissions + Q.emOff[b] + (FIN ? (int64_t)0 : (int64_t)P.t * P.V);
+  const void* em;
+  double lse = 0.0;
+  if constexpr (EM == kCrEmPlain) {
+    em = Q.emissions + Q.emOff[b] + (FIN ? (int64_t)0 : (int64_t)P.t * P.V);
+  } else {
+    em = (const char*)E->x + (Q.emOff[b] + (int64_t)P.t * E->stride) * (EM == kS2sDtF32 ? 4 : 2);
+    if constexpr (LOGITS) {
+      lse = E->lse[fr];
+    }
+  }
   const int64_t n = FIN ? (int64_t)nPrev : (int64_t)nPrev * (P.cap * (1 + R.S) + 2);
   for (int j = tid; j < Q.mSize; j += kS2sStepThreads) {
     mTab[j] = -1;
@@ -373,7 +386,7 @@ FLTX_DEV void crlStepUtterance(const CrlParams& R, char* smem, const CrsParams* 
   for (int64_t j = tid; j < n; j += kS2sStepThreads) {
     unsigned long long key = 0ull;
     CrlCand c;
-    if (crlCand<SRC, FIN>(R, prev, em, fr, nE, rb, nice, j, c)) {
+    if (crlCand<SRC, FIN, EM, LOGITS>(R, prev, em, lse, fr, nE, rb, nice, j, c)) {
       key = s2sScoreKey(c.score);
       cScore[j] = c.score;
       cMk[j] = crlMergeKey(c, prev[c.hyp]);
@@ -399,7 +412,7 @@ FLTX_DEV void crlStepUtterance(const CrlParams& R, char* smem, const CrsParams* 
   CrlCand c = {};
   if (tid < nSel) {
     const int64_t j = S.selIdx[S.order[tid]];
-    crlCand<SRC, FIN>(R, prev, em, fr, nE, rb, nice, j, c);
+    crlCand<SRC, FIN, EM, LOGITS>(R, prev, em, lse, fr, nE, rb, nice, j, c);
     const CrlHyp& h = prev[c.hyp];
     nh = h;
     nh.parent = c.hyp;
@@ -529,6 +542,17 @@ FLTX_DEV void crlStepUtterance(const CrlParams& R, char* smem, const CrsParams* 
       crsStepDone(Q, *Z, b, nd, nSel, nh);
     }
   }
+}
+
+/* the frame step on typed emissions (fltx_ctc_rows_begin_typed): the same step, its two direct emission reads typed */
+struct CrlTypedParams {
+  CrlParams r; /* (r.c.emissions is not read; r.c.emOff counts elements of e.x) */
+  CrTypedEm e;
+};
+
+template <int SRC, int DT, bool LOGITS>
+FLTX_DEV void crlStepTyped(const CrlTypedParams& Y, char* smem) {
+  crlStepUtterance<SRC, false, false, DT, LOGITS>(Y.r, smem, nullptr, &Y.e);
 }
 
 /* decodeBegin (:21-30): the root (token sil) at the trie's root in LM::start's state (sid 0); the first call's single

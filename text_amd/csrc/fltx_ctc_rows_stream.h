@@ -78,6 +78,17 @@ FLTX_DEV void crlsStepStream(const CrlStreamParams& Z, char* smem) {
   crlStepUtterance<SRC, FIN, true>(Z.r, smem, &Z.x);
 }
 
+struct CrlTypedStreamParams { /* a chunk of typed emissions (fltx_ctc_rows_stream_append_typed) */
+  CrlParams r;
+  CrsParams x;
+  CrTypedEm e;
+};
+
+template <int SRC, int DT, bool LOGITS>
+FLTX_DEV void crlsStepStreamTyped(const CrlTypedStreamParams& Y, char* smem) {
+  crlStepUtterance<SRC, false, true, DT, LOGITS>(Y.r, smem, &Y.x, &Y.e);
+}
+
 /* ---- getBestHypothesis and prune ------------------------------------------------------------------------------------------ */
 struct CrsOpParams {
   int32_t B, K, lookBack, maxLen;

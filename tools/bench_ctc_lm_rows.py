@@ -19,10 +19,19 @@ batch decode holds every state the decode can enter, B * (K * T + 2) rows; where
 leg runs as B streams instead -- chunks of --plan-chunk frames, a collect and plan_release after each, max_states 1024
 per stream -- and says so ("mode").  --plan-read-counts: the leg reads the plan's counts every frame (16 bytes, a
 synchronisation) and fills the n_new listed rows only, as a caller with wide LM rows would.
+--emissions DTYPE_KIND (f32 / f16 / bf16, log_probs / logits; default f32_log_probs, the float32 entry points) feeds the
+legs a, b and p the acoustic model's output as it is, through fltx_ctc_rows_begin_typed.
+--front N1,N2,..: the front end alone, on --front-dtype logits of B * T frames per width in HBM -- (typed) the typed
+begin; (torch) what a caller did before it: .float().log_softmax(-1), then fltx_ctc_rows_begin -- in alternating runs,
+medians with their spread, and the device bytes each holds at its peak (what the driver reports used after the call
+above an emptied cache before it: the caching allocator keeps torch's high-water mark, the decoder its buffers).
+--front-sweep N1,N2,..: the typed begin per width with the wave-per-frame and with the workgroup-per-frame front end
+(fltx_decoder_set "emissions_narrow_max"), alternating: what the switch-over width was chosen from.
 The per-kernel split comes from a separate run under `rocprofv3 --kernel-trace --stats` (the program after `--`; --only
 keeps that run to one leg).
 
     python tools/bench_ctc_lm_rows.py [--T 200] [--warmup 1] [--only a,b,c] [--sets letters,word_piece] [--plan]
+                                      [--emissions bf16_logits] [--front 29,1024,8192] [--front-sweep 29,64,...]
 """
 import argparse
 import json
@@ -39,6 +48,87 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from text_amd import _capi  # noqa: E402
 from bench_lex_s2s import timed  # noqa: E402
+
+
+TORCH_DTYPES = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
+EMISSIONS = ["%s_%s" % (d, k) for d in TORCH_DTYPES for k in ("log_probs", "logits")]
+
+
+def emissions(frames, N, spec):
+    """[frames, N] emissions in HBM as `spec` names them -> (the tensor, begin(dec, Ts) that hands them to a decoder)"""
+    dt, kind = spec.split("_", 1)
+    x = torch.randn(frames, N, device="cuda")
+    em = (x.log_softmax(-1) if kind == "log_probs" else x * 3).to(TORCH_DTYPES[dt]).contiguous()
+    if spec == "f32_log_probs":  # the float32 entry points, as before
+        return em, lambda dec, Ts, **kw: dec.begin(None, Ts, N, device_ptr=em.data_ptr(), **kw)
+    return em, lambda dec, Ts, **kw: dec.begin(em, Ts, N, kind=kind, **kw)
+
+
+def spread(v):
+    v = sorted(v)
+    return {"median": v[len(v) // 2], "min": v[0], "max": v[-1]}
+
+
+def front_end(a, ctx, stream, widths, sweep):
+    """--front / --front-sweep: see the module's text"""
+    B, T = a.B, a.T
+    Ts = np.full(B, T, np.int32)
+    dt = TORCH_DTYPES[a.front_dtype]
+
+    def held(fn):
+        torch.cuda.synchronize()
+        torch.cuda.empty_cache()
+        free0 = torch.cuda.mem_get_info()[0]
+        fn()
+        torch.cuda.synchronize()
+        return free0 - torch.cuda.mem_get_info()[0]
+    for N in sorted(set(widths) | set(sweep)):
+        lm = _capi.RowsLM(N + 1, None, N)
+        opts = _capi.make_options(a.K, min(N, 50), 25.0, 0.7)
+        x = (torch.randn(B * T, N, device="cuda") * 3).to(dt)
+        out = {"config": {"N": N, "B": B, "T": T, "dtype": a.front_dtype, "kind": "logits", "runs": a.front_runs,
+                          "emissions_bytes": x.numel() * x.element_size()}}
+        if N in widths:
+            def typed(dec):
+                dec.begin(x, Ts, N, kind="logits")
+
+            def torch_then_f32(dec):
+                e = x.float().log_softmax(-1)
+                dec.begin(None, Ts, N, device_ptr=e.data_ptr())
+                return e
+            legs = {"typed_begin": typed, "torch_log_softmax_then_begin": torch_then_f32}
+            ms, mem = {k: [] for k in legs}, {}
+            for k, fn in legs.items():  # a fresh decoder per leg: its buffers are part of what the leg holds
+                dec = _capi.CtcRowsBatchDecoder(ctx, opts, lm, 0, 1)
+                mem[k] = held(lambda: fn(dec))
+                dec.close()
+            decs = {k: _capi.CtcRowsBatchDecoder(ctx, opts, lm, 0, 1) for k in legs}
+            for k, fn in legs.items():
+                fn(decs[k])
+            for _ in range(a.front_runs):
+                for k, fn in legs.items():
+                    ms[k].append(timed(lambda: fn(decs[k]), stream))
+            out["begin_ms"] = {k: spread(v) for k, v in ms.items()}
+            out["device_bytes_held"] = mem
+            for d in decs.values():
+                d.close()
+        if N in sweep and N <= 1024:
+            decs = {}
+            for k, nm in (("wave_per_frame", 1024), ("workgroup_per_frame", 0)):
+                decs[k] = _capi.CtcRowsBatchDecoder(ctx, opts, lm, 0, 1)
+                decs[k].set("emissions_narrow_max", nm)
+                decs[k].begin(x, Ts, N, kind="logits")
+            ms = {k: [] for k in decs}
+            for _ in range(a.front_runs):
+                for k, d in decs.items():
+                    ms[k].append(timed(lambda: d.begin(x, Ts, N, kind="logits"), stream))
+            out["sweep_begin_ms"] = {k: spread(v) for k, v in ms.items()}
+            for d in decs.values():
+                d.close()
+        print(json.dumps(out), flush=True)
+        lm.close()
+        del x
+        torch.cuda.empty_cache()
 
 
 class TableLM:
@@ -85,6 +175,12 @@ def main():
     ap.add_argument("--plan-chunk", type=int, default=10)
     ap.add_argument("--plan-read-counts", action="store_true",
                     help="leg p reads the plan's counts (16 bytes, a synchronisation per frame) and fills n_new rows only")
+    ap.add_argument("--emissions", default="f32_log_probs", choices=EMISSIONS,
+                    help="what the legs a, b and p hand to begin: dtype and kind of the emissions in HBM")
+    ap.add_argument("--front", default="", help="widths N1,N2,..: time the front end alone, typed against torch + float32")
+    ap.add_argument("--front-sweep", default="", help="widths N1,N2,..: wave-per-frame against workgroup-per-frame")
+    ap.add_argument("--front-dtype", default="bf16", choices=sorted(TORCH_DTYPES))
+    ap.add_argument("--front-runs", type=int, default=9)
     a = ap.parse_args()
     only = set(a.only.split(",")) | ({"p"} if a.plan else set())
     torch.manual_seed(0)
@@ -92,11 +188,14 @@ def main():
     torch.cuda.set_stream(stream)
     ctx = _capi.Context(stream=stream.cuda_stream)
     B, K, T = a.B, a.K, a.T
+    if a.front or a.front_sweep:
+        front_end(a, ctx, stream, [int(n) for n in a.front.split(",") if n], [int(n) for n in a.front_sweep.split(",") if n])
+        return
     for name, N, Kt in (("letters", 29, 29), ("word_piece", 10000, 50)):
         if name not in a.sets.split(","):
             continue
         W = N + 1
-        em = torch.randn(B * T, N, device="cuda").log_softmax(-1).contiguous()
+        em, begin = emissions(B * T, N, a.emissions)
         logits = (torch.randn(a.ctx, W, device="cuda") * 3).to(torch.bfloat16)
         log_probs = torch.log_softmax(logits.float(), -1).to(torch.bfloat16)
         Ts = np.full(B, T, np.int32)
@@ -114,14 +213,14 @@ def main():
                 return torch.where(state >= 0, r, torch.full_like(r, -1)).to(torch.int32)
 
             def loop():
-                tok, src, state, n = dec.begin(None, Ts, N, device_ptr=em.data_ptr())
+                tok, src, state, n = begin(dec, Ts)
                 for _ in range(T):
                     tok, src, state, n = dec.step(rows, lm_row_of=row_of(state), lm_kind=kind)
                 dec.end(rows, lm_row_of=row_of(state), lm_kind=kind)
             for _ in range(a.warmup):
                 loop()
             ms[leg] = timed(loop, stream) / T
-            begin_ms = timed(lambda: dec.begin(None, Ts, N, device_ptr=em.data_ptr()), stream)
+            begin_ms = timed(lambda: begin(dec, Ts), stream)
             loop()
             hyps = dec.results(0)
             extra[leg] = {"begin_ms": begin_ms, "hyps_utt0": len(hyps), "best_utt0": hyps[0].score}
@@ -148,7 +247,7 @@ def main():
 
             def plan_loop():
                 if batch:
-                    lists = dec.begin(None, Ts, N, device_ptr=em.data_ptr())
+                    lists = begin(dec, Ts)
                     dec.plan_begin(cap)
                     for _ in range(T):
                         lists = dec.step(store[:cap], lm_row_of=planned(lists))
@@ -161,7 +260,9 @@ def main():
                 for t0 in range(0, T, a.plan_chunk):  # (utterance-major emissions: a chunk is named by its offsets)
                     n = min(a.plan_chunk, T - t0)
                     off = (np.arange(B, dtype=np.int64) * T + t0) * N
-                    for _ in range(dec.append(None, np.full(B, n, np.int32), offsets=off, device_ptr=em.data_ptr())):
+                    tn = np.full(B, n, np.int32)
+                    for _ in range(dec.append(None, tn, offsets=off, device_ptr=em.data_ptr()) if a.emissions == "f32_log_probs"
+                                   else dec.append(em, tn, offsets=off, kind=a.emissions.split("_", 1)[1])):
                         ro = planned(dec.step(store[:cap], lm_row_of=ro))
                     dec.prune(0)
                     rel, n_rel, _ = dec.collect(max_states)
@@ -182,7 +283,7 @@ def main():
             hb = a.host_B
             host = _capi.HostLM(TableLM(log_probs[:, :].float().cpu().numpy(), a.ctx))
             ref = _capi.BatchDecoder(ctx, _capi.LEXFREE, opts, host, 0, 1)
-            e_host = em[:hb * T].cpu().numpy()
+            e_host = em[:hb * T].float().log_softmax(-1).cpu().numpy()
             ref.decode_batch(e_host, Ts[:hb], N)  # warm-up
             ref.count(0)
             t0 = time.perf_counter()
@@ -193,9 +294,10 @@ def main():
             ref.close()
             host.close()
         print(json.dumps({"config": {"name": name, "B": B, "K": K, "Kt": Kt, "N": N, "T": T, "lm_width": W,
-                                     "lm_table_rows": a.ctx, "lm_weight": 0.7},
+                                     "lm_table_rows": a.ctx, "lm_weight": 0.7, "emissions": a.emissions},
                           "ms_per_frame_step": ms, "search": extra,
-                          "bytes": {"emissions_f32": B * T * N * 4, "lm_bf16_table": a.ctx * W * 2}}), flush=True)
+                          "bytes": {"emissions": em.numel() * em.element_size(), "lm_bf16_table": a.ctx * W * 2}}),
+              flush=True)
         lm.close()
         del em, logits, log_probs
         torch.cuda.empty_cache()

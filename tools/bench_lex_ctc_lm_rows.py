@@ -16,8 +16,11 @@ table; `ratio_to_lexfree` is (a) / (d).
 The per-kernel split comes from a separate run under `rocprofv3 --kernel-trace --stats` (the program after `--`; --only
 and --levels keep that run to one leg).
 
+--emissions DTYPE_KIND: the emissions as bench_ctc_lm_rows.py's option names them (default f32_log_probs); anything
+else goes through fltx_ctc_rows_begin_typed, and the step reads its blank and same-node emissions from the typed frames.
+
     python tools/bench_lex_ctc_lm_rows.py [--T 200] [--warmup 1] [--only a,b,c,d] [--sets letters,word_piece]
-                                          [--levels word,token]
+                                          [--levels word,token] [--emissions bf16_logits]
 """
 import argparse
 import json
@@ -33,7 +36,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from text_amd import _capi, synth  # noqa: E402
-from bench_ctc_lm_rows import TableLM  # noqa: E402
+from bench_ctc_lm_rows import EMISSIONS, TableLM, emissions  # noqa: E402
 from bench_lex_s2s import timed  # noqa: E402
 
 
@@ -57,6 +60,8 @@ def main():
     ap.add_argument("--only", default="a,b,c,d")
     ap.add_argument("--sets", default="letters,word_piece")
     ap.add_argument("--levels", default="word,token")
+    ap.add_argument("--emissions", default="f32_log_probs", choices=EMISSIONS,
+                    help="what begin is handed: dtype and kind of the emissions in HBM (bench_ctc_lm_rows.py)")
     a = ap.parse_args()
     only = set(a.only.split(","))
     torch.manual_seed(0)
@@ -68,7 +73,7 @@ def main():
         if name not in a.sets.split(","):
             continue
         spell = lexicons(name, N)
-        em = torch.randn(B * T, N, device="cuda").log_softmax(-1).contiguous()
+        em, begin = emissions(B * T, N, a.emissions)
         Ts = np.full(B, T, np.int32)
         utt = (torch.arange(B, device="cuda", dtype=torch.int64) * 97)[:, None]
         for level in a.levels.split(","):
@@ -91,14 +96,14 @@ def main():
 
             def run(dec, rows, kind):
                 def loop():
-                    tok, src, state, n = dec.begin(None, Ts, N, device_ptr=em.data_ptr())
+                    tok, src, state, n = begin(dec, Ts)
                     for _ in range(T):
                         tok, src, state, n = dec.step(rows, lm_row_of=row_of(state), lm_kind=kind)
                     dec.end(rows, lm_row_of=row_of(state), lm_kind=kind)
                 for _ in range(a.warmup):
                     loop()
                 per = timed(loop, stream) / T
-                begin_ms = timed(lambda: dec.begin(None, Ts, N, device_ptr=em.data_ptr()), stream)
+                begin_ms = timed(lambda: begin(dec, Ts), stream)
                 loop()
                 hyps = dec.results(0)
                 dec.close()
@@ -118,7 +123,7 @@ def main():
                 host = _capi.HostLM(TableLM(log_probs.float().cpu().numpy(), a.ctx))
                 dtrie = trie.upload(ctx)
                 ref = _capi.BatchDecoder(ctx, _capi.LEXICON, opts, host, sil, blank, -1, trie=dtrie, is_lm_token=tokl)
-                e_host = em[:hb * T].cpu().numpy()
+                e_host = em[:hb * T].float().log_softmax(-1).cpu().numpy()
                 ref.decode_batch(e_host, Ts[:hb], N)  # warm-up
                 ref.count(0)
                 t0 = time.perf_counter()
@@ -132,7 +137,8 @@ def main():
                                          "words": len(spell), "trie_nodes": trie.num_nodes(), "lm_width": W,
                                          "lm_table_rows": a.ctx, "lm_weight": 0.7, "word_score": 0.5},
                               "ms_per_frame_step": ms, "search": extra,
-                              "bytes": {"emissions_f32": B * T * N * 4, "lm_bf16_table": a.ctx * W * 2}}), flush=True)
+                              "emissions": a.emissions,
+                              "bytes": {"emissions": em.numel() * em.element_size(), "lm_bf16_table": a.ctx * W * 2}}), flush=True)
             lm.close()
             trie.close()
             del logits, log_probs
