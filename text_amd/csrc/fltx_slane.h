@@ -47,6 +47,15 @@
  *     LMState::child (lm/LM.h:24-34): nothing else is written per frame.  The
  *     rare re-entry of a state that had dropped out of the beam (about one
  *     frame in a hundred on the benchmark inputs) scans the rows.
+ *   * What a frame knows before it starts is not computed in it: silScore is added at sil's own list position, by the
+ *     one wave that holds it and only when it is not zero (slSilAdd: two wave-uniform conditions), and a token wave
+ *     none of whose candidates survived -- 92.5 % of the token wave-frames on the benchmark inputs -- does not walk
+ *     its list positions in the build (C2: 183 -> 156 vector and 137 -> 113 scalar instructions per wave and frame,
+ *     2.16 -> 2.00 ms per kernel with a second batch co-resident; profiles/slane_frame).  Tried and taken out again:
+ *     sil / blank / the criterion / the row helpers' options pinned in registers so that no frame loop loads a kernel
+ *     argument (the own-groups and the staging wave of <512, 5> do, once or twice per frame, with a full wait).  All
+ *     those loads gone, the kernel was as fast as with them, to within the spread of the runs: they hit the scalar
+ *     cache, and the LDS reads their wait drains were about to be waited for.
  *
  * Three barriers per frame.
  */
@@ -709,6 +718,31 @@ FLTX_DEV __attribute__((noinline)) void tlReenter(TlaneLds& S, const int2* histP
     }                                                         \
   } while (0)
 
+/* silScore on a token wave's candidates c1[j] = m + e[j] (and, logAdd, the group's second members c2[j]): sil holds one
+ * list position, so at most one position of one wave pays the add -- (m + e) + silScore, the reference's order -- and
+ * with silScore == 0 nobody does.  Both conditions are wave-uniform: a scalar branch around the whole thing.  (Written
+ * as `if (j == silJ) c += silScore` in the candidate loop, every position of every token wave added silScore and
+ * selected the plain sum back: five instructions per position and frame for nothing.) */
+template <int GT, bool LA>
+FLTX_DEV void slSilAdd(double (&c1)[GT], double (&c2)[GT], bool silOn, int silPos, int wave, double silScore) {
+  if (!silOn) {
+    return;
+  }
+  const int silJ = waveUniform(silPos) - wave * GT; /* list position of sil relative to this wave's first */
+  if ((unsigned)silJ >= (unsigned)GT) {
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < GT; ++j) { /* (selects: a store under `if (j == silJ)` becomes an indexed one, the arrays scratch memory) */
+    const double a1 = c1[j] + silScore;
+    c1[j] = j == silJ ? a1 : c1[j];
+    if (LA) {
+      const double a2 = c2[j] + silScore;
+      c2[j] = j == silJ ? a2 : c2[j];
+    }
+  }
+}
+
 /* logAdd merge of two members (Utils.h:186-193): hi is the larger */
 FLTX_DEV double slLogAdd(double hi, double lo) { return hi + log1p(exp(lo - hi)); }
 
@@ -936,6 +970,10 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
   const int sil = P.sil, blank = P.blank;
   double silScore = P.silScore;
   double lmW = TL ? P.lmWeight : 0.0;
+  /* silScore != 0.0 as a wave-uniform flag (silScore itself lives in a vector register, below): said with integers --
+   * the bits of neither zero -- so that the scalar unit computes it; NaN counts */
+  const unsigned long long silBits = (unsigned long long)__double_as_longlong(P.silScore) << 1;
+  uint32_t silOnI = (uint32_t)(silBits >> 32) | (uint32_t)silBits;
 #ifndef FLTX_EMU
   /* (kept in a vector register: the frame loop is short of scalar ones, and the compiler would rather load the option
    * from the kernel arguments again at each of its uses -- a scalar load and a full wait per candidate) */
@@ -943,7 +981,10 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
   if (TL) {
     __asm__ volatile("" : "+v"(lmW));
   }
+  /* (... and the flag in a scalar one, for the same reason: the token waves' frame has no scalar load, and gets none) */
+  __asm__ volatile("" : "+s"(silOnI));
 #endif
+  const bool silOn = silOnI != 0u;
   const int2* const tokLm = TL ? P.tokLm : nullptr;
   const int tokStride = TL ? P.tokLmStride : 0;
   int2* const histPT = P.histPT;
@@ -1209,21 +1250,21 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
       const uint32_t lastLo = last < 32 ? 1u << last : 0u, lastHi = last < 32 ? 0u : 1u << (last - 32);
       const uint32_t skLo = live ? ((uint32_t)cm | lastLo) : 0xFFFFFFFFu;
       const uint32_t skHi = live ? ((uint32_t)(cm >> 32) | lastHi) : 0xFFFFFFFFu;
-      const int silJ = silPos - wave * GT; /* list position of sil relative to this wave's first */
+      double c1[GT], c2v[GT];
 #pragma unroll
       for (int j = 0; j < GT; ++j) {
-        double c = m + ev[j]; /* NaN past the end of the list */
-        if (j == silJ) {
-          c = c + silScore;
-        }
+        c1[j] = m + ev[j]; /* NaN past the end of the list */
+        c2v[j] = LA ? (whichB ? nb : bb) + ev[j] : 0.0;
+      }
+      slSilAdd<GT, LA>(c1, c2v, silOn, silPos, wave, silScore);
+#pragma unroll
+      for (int j = 0; j < GT; ++j) {
+        double c = c1[j];
         const uint32_t hit = (skLo & (uint32_t)tb[j]) | (skHi & (uint32_t)(tb[j] >> 32));
         const bool ok = hit == 0u && c >= thr;
         if (LA) { /* the state's other hypothesis reaches the same child state: fl(a + e) is monotone, so it
                      is the smaller member */
-          double c2 = (whichB ? nb : bb) + ev[j];
-          if (j == silJ) {
-            c2 = c2 + silScore;
-          }
+          const double c2 = c2v[j];
           if (ok && (whichB ? hypNB : hypB) != kSlNoHyp && c2 >= thr) {
             c = slLogAdd(c, c2);
           }
@@ -1263,7 +1304,7 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
       double r2 = has2 ? par.b + eLast : NEG;
       /* (S.last, last, false) from (S, blank, true) when no lane holds S.last */
       double cL = bb + eLast;
-      if (silScore != 0.0) {
+      if (silOn) {
         r0 = lastSil ? r0 + silScore : r0;
         r1 = lastSil ? r1 + silScore : r1;
         r2 = lastSil ? r2 + silScore : r2;
@@ -1340,25 +1381,23 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
         const uint32_t lastLo = last < 32 ? 1u << last : 0u, lastHi = last < 32 ? 0u : 1u << (last - 32);
         const uint32_t skLo = live ? ((uint32_t)cm | lastLo) : 0xFFFFFFFFu;
         const uint32_t skHi = live ? ((uint32_t)(cm >> 32) | lastHi) : 0xFFFFFFFFu;
-        const int silJ = silPos - wave * GT;
         hasOther = (whichB ? hypNB : hypB) != kSlNoHyp;
+        double c1[GT];
+#pragma unroll
+        for (int j = 0; j < GT; ++j) {
+          c1[j] = m + ev[j]; /* NaN past the end of the list */
+          c2v[j] = LA ? (whichB ? nb : bb) + ev[j] : NEG;
+        }
+        slSilAdd<GT, LA>(c1, c2v, silOn, silPos, wave, silScore);
 #pragma unroll
         for (int j = 0; j < GT; ++j) {
           /* LexiconFreeDecoder.cpp:64-67,69-85: score = prev.score + e (+ silScore), candidate = score + lmWeight * lmScore */
           const double wl = lmW * (double)__uint_as_float((uint32_t)lmv[j].x);
-          double c = m + ev[j]; /* NaN past the end of the list */
-          if (j == silJ) {
-            c = c + silScore;
-          }
-          c = c + wl;
+          const double c = c1[j] + wl;
           const uint32_t hit = (skLo & (uint32_t)tb[j]) | (skHi & (uint32_t)(tb[j] >> 32));
           pre[j] = hit == 0u && c == c;
           if (LA) {
-            double c2 = (whichB ? nb : bb) + ev[j];
-            if (j == silJ) {
-              c2 = c2 + silScore;
-            }
-            c2v[j] = c2 + wl;
+            c2v[j] = c2v[j] + wl;
           }
           cs[j] = c;
         }
@@ -1392,7 +1431,7 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
         r1 = par.nb + eLast;
         r2 = par.b + eLast;
         double cL = bb + eLast; /* (S.last, last, false) from (S, blank, true) when no lane holds S.last */
-        if (silScore != 0.0) {
+        if (silOn) {
           r0 = lastSil ? r0 + silScore : r0;
           r1 = lastSil ? r1 + silScore : r1;
           r2 = lastSil ? r2 + silScore : r2;
@@ -1671,6 +1710,10 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
       if (lane > wave && lane <= selfWave + 1 && nNewWave > 0) {
         atomAdd32(&S.off[lane], (uint32_t)nNewWave);
       }
+      if (PROF && !TL && nNewWave == 0) { /* (profile of a token wave: 1e6 x its frames without a survivor, on top of the
+                                             members of the ranked bins -- those stay below 1e3 per frame) */
+        acc[7] += 1000000ull;
+      }
     } else {
       const unsigned long long balB = selMask[0], balR = selMask[1], balL = selMask[2];
       const unsigned long long balS = balB | balR;
@@ -1711,9 +1754,17 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
     ldsBarrier(); /* 2 */
     /* ---- phase 3: every survivor is written by the lane that evaluated it ---------------- */
     const int nSurv = (int)S.scal[SL_NSURV], nHSurv = (int)S.scal[SL_NHSURV];
-    const int offW = (int)S.off[wave], nNew = (int)S.off[selfWave + 1];
-    const int myNewLane = S.newLane[lane];
-    const int plNew = S.newLane[pl >= 0 ? pl : 0];
+    const int nNew = (int)S.off[selfWave + 1];
+    /* A token wave none of whose candidates survived (nNewWave, a scalar, is 0) builds nothing: it skips the walk over
+     * its list positions -- a test of a ballot, the lane's bit and a branch per position -- and the two reads only
+     * that walk uses. */
+    const bool builds = isSelf || (!isSvc && nNewWave != 0);
+    int offW = 0, myNewLane = -1;
+    if (builds) {
+      offW = (int)S.off[wave];
+      myNewLane = S.newLane[lane];
+    }
+    const int plNew = isSelf ? S.newLane[pl >= 0 ? pl : 0] : -1;
     auto plainRec = [&](uint32_t hp, int n) { return make_int2(hp == kSlNoHyp ? -1 : (int)hp, n); };
     auto scoreRec = [&](int64_t at, double c, double am, double lmv) {
       if (P.histS) {
@@ -1859,7 +1910,7 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
           }
         }
       }
-      if (!gathered) {
+      if (!gathered && nNewWave != 0) { /* (no survivor in this wave: nothing to walk) */
 #pragma unroll
       for (int j = 0; j < GT; ++j) {
         if (selMask[j] != 0ull) { /* (most positions of most frames have no survivor at all) */
