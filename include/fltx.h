@@ -685,6 +685,61 @@ FLTX_API int fltx_ctc_rows_plan(fltx_decoder* dec, const int32_t* next_token, co
  * or without fltx_ctc_rows_plan_begin; FLTX_ERR_INVALID on NULL or release_cap < 1. */
 FLTX_API int fltx_ctc_rows_plan_release(fltx_decoder* dec, const int32_t* released, const int32_t* n_released,
                                         int32_t release_cap);
+/* ---- finish and restart single streams of a stream batch -------------------------------------------------------------
+ * Sessions start and stop at different times: fltx_ctc_rows_stream_finish ends the utterances of the streams `which`
+ * names (a HOST array of B, != 0: named) and restarts those slots from the root, in one call, and leaves every other
+ * stream alone.
+ *
+ * A named stream b first gets exactly fltx_ctc_rows_end's decodeEnd: the entry at finish_index of each hypothesis' LM row
+ * (lexicon kind: only the hypotheses at the root finish, if there are any), merge, sort best first, the walk back over
+ * the frames in the buffer by count -- frames in buffer + 1 entries per hypothesis.  The LM rows are passed as to
+ * fltx_ctc_rows_end, for the rows the last call listed; only rows of named streams are read (through lm_row_of or not),
+ * lm_row_lse is written for those rows only, and lm_scores may be NULL when no stream is named.  A stream that had stopped
+ * (table full, empty beam) is finished as fltx_ctc_rows_end finishes it: status[b] says why it had stopped.
+ * Then, in the same call, slot b is in exactly the state fltx_ctc_rows_stream_begin leaves a stream in: no frames decoded
+ * and none pruned, the root in the beam, its scores in the score ring, the LM-state ids started over (root id 0, nothing
+ * free, the stream's table empty), status and the stopped flag cleared, the host's frame bound for append back to zero.
+ * max_frames, max_states and the rings' size stay; the rings are not cleared, and nothing reads a row of the utterance
+ * before.
+ * Of every other stream nothing is written and only the current beam's state ids are read; every later call decides for
+ * it, bit for bit, what it would have decided without this call.
+ *
+ * The four lists (DEVICE, as fltx_ctc_rows_step's): a named stream lists its root as fltx_ctc_rows_stream_begin does --
+ * one row, next_src_row -1, next_state 0, next_token sil (-1: lexicon kind); every other stream lists its beam again as
+ * a step without frames does -- next_src_row the slot itself, next_token -1, the same ids.
+ *
+ * With fltx_ctc_rows_plan_begin in force the named streams' LM rows go back to the planner in the same call, on the
+ * device: streams ascending, within a stream ids ascending, a row an id has goes on the free stack, and every id of the
+ * stream is unplanned (the dropped ones too; the count of dropped states stays).  The finish's list is then planned like
+ * any other list before the next step: the root is a new state with new_parent_row -1 and new_edge -1.
+ *
+ * Results, in `out`: results_on_device != 0 -- the pointers address HBM, written in the order of the context's stream;
+ * nothing crosses PCIe, and tokens / words / row_off / length are valid inputs of fltx_collapse_rows.
+ * results_on_device == 0 -- pinned host buffers, complete when the call returns (the only case in which it waits): the
+ * counts of all B streams cross, then n_hyp * length entries and 3 n_hyp scores of each named stream.  Both stay valid
+ * until the next finish, fltx_ctc_rows_end or begin on this decoder; steps, appends, prunes, collects and
+ * fltx_result_best do not disturb them, and fltx_result_* keep returning what they returned before the call.
+ *
+ * A call that names no stream is legal, reads no LM row and changes nothing: it lists every beam again.
+ * FLTX_ERR_STATE outside a rows stream, on a decoder begun with fltx_ctc_rows_begin, on every other kind, while frames
+ * of the last chunk are unstepped, and -- with planning active -- when a fltx_ctc_rows_stream_collect was queued without
+ * its fltx_ctc_rows_plan_release.  FLTX_ERR_INVALID on a NULL which, list or out, and, when a stream is named, on a bad
+ * lm_dtype or lm_kind, lm_row_stride < lm_width or NULL lm_scores. */
+typedef struct fltx_finished_out {
+  const int32_t* n_hyp;   /* [B]  0 for a stream the call did not name */
+  const int32_t* length;  /* [B]  entries per hypothesis = frames in buffer + 1; 0 for a stream not named */
+  const int32_t* status;  /* [B]  0, or the FLTX_ERR_* fltx_result_count would report for it after fltx_ctc_rows_end */
+  const double* scores;   /* [B*K*3] score, emitting-model score, LM score, as fltx_result_fetch_batch */
+  const int32_t* tokens;  /* hypothesis k of stream b: row_off[b] + k * length[b] */
+  const int32_t* words;   /* likewise; NULL for the lexicon-free kind */
+  const int64_t* row_off; /* [B] fixed for the life of the stream batch */
+} fltx_finished_out;
+FLTX_API int fltx_ctc_rows_stream_finish(fltx_decoder* dec, const int32_t* which, const void* lm_scores,
+                                         int32_t lm_dtype, int32_t lm_kind, int64_t lm_row_stride,
+                                         const int32_t* lm_row_of, int32_t n_lm_rows, int32_t on_device,
+                                         double* lm_row_lse, int32_t* next_token, int32_t* next_src_row,
+                                         int32_t* next_state, int32_t* n_rows, int32_t results_on_device,
+                                         fltx_finished_out* out);
 /* nDecodedFramesInBuffer of stream b (synchronises). */
 FLTX_API int fltx_ctc_rows_stream_frames_in_buffer(fltx_decoder* dec, int32_t b, int32_t* n);
 /* Inside such a stream fltx_result_best(dec, b, look_back, ...) is getBestHypothesis(lookBack): the ancestor's score,

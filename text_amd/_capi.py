@@ -95,6 +95,11 @@ class StreamPartialsOut(C.Structure):
     ]
 
 
+class FinishedOut(C.Structure):
+    """fltx_finished_out (include/fltx.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("n_hyp", "length", "status", "scores", "tokens", "words", "row_off")]
+
+
 def _view(ptr, ctype, n):
     """n elements at a host address as a NumPy array (no copy)"""
     if n == 0 or not ptr:
@@ -151,7 +156,7 @@ class Lib:
         "fltx_ctc_rows_decoder_create", "fltx_ctc_rows_lex_decoder_create", "fltx_ctc_rows_begin", "fltx_ctc_rows_step", "fltx_ctc_rows_end",
         "fltx_ctc_rows_begin_typed", "fltx_ctc_rows_stream_append_typed",
         "fltx_ctc_rows_stream_begin", "fltx_ctc_rows_stream_append", "fltx_ctc_rows_stream_prune",
-        "fltx_ctc_rows_stream_frames_in_buffer", "fltx_ctc_rows_stream_collect",
+        "fltx_ctc_rows_stream_frames_in_buffer", "fltx_ctc_rows_stream_collect", "fltx_ctc_rows_stream_finish",
         "fltx_ctc_rows_plan_begin", "fltx_ctc_rows_plan", "fltx_ctc_rows_plan_release",
         "fltx_collapse_rows", "fltx_result_transcripts", "fltx_stream_partials",
     ]
@@ -249,6 +254,8 @@ class Lib:
             "fltx_ctc_rows_stream_prune": [vp, i32],
             "fltx_ctc_rows_stream_frames_in_buffer": [vp, i32, vp],
             "fltx_ctc_rows_stream_collect": [vp, i32, vp, vp, vp],
+            "fltx_ctc_rows_stream_finish": [vp, vp, vp, i32, i32, i64, vp, i32, i32, vp, vp, vp, vp, vp, i32,
+                                            C.POINTER(FinishedOut)],
             "fltx_ctc_rows_plan_begin": [vp, i32],
             "fltx_ctc_rows_plan": [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp],
             "fltx_ctc_rows_plan_release": [vp, vp, vp, i32],
@@ -1336,7 +1343,8 @@ class CtcRowsBatchDecoder(BatchDecoder):
     all from a callable.  Streams: stream_begin(B, N, max_frames), then append(chunk, T) and as many step() calls as it
     returns, prune(look_back), best(b, look_back) -- getBestHypothesis(lookBack), an empty result has no tokens --
     frames_in_buffer(b), and end(); decode_stream() drives those.  A stream's state ids stay stable until collect()
-    lists them as released: a released id may come back for another state.  plan_begin(row_capacity), plan(lists) and
+    lists them as released: a released id may come back for another state.  stream_finish(which, lm_scores) ends the
+    utterances of single streams and restarts those slots while the others decode on.  plan_begin(row_capacity), plan(lists) and
     plan_release(released, n_released) keep the LM rows of the state ids on the device (fltx_ctc_rows_plan_*);
     decode_device() and decode_stream_device() are decode() and decode_stream() on those."""
 
@@ -1670,6 +1678,43 @@ class CtcRowsBatchDecoder(BatchDecoder):
         args, keep = self._lm_in(lm_scores, lm_row_of, lm_kind, lm_lse_out, lm_dtype)
         self._chk(self.L.lib.fltx_ctc_rows_end(self.h, *args))
         self._inputs = keep
+
+    def stream_finish(self, which, lm_scores, *, lm_row_of=None, lm_kind="log_probs", lm_dtype=None, lm_lse_out=None,
+                      device=False):
+        """End the utterances of the streams `which` names (B flags) and restart those slots from the root, leaving every
+        other stream as it is (fltx_ctc_rows_stream_finish).  lm_scores / lm_row_of / lm_kind / lm_dtype / lm_lse_out as
+        end() takes them, for the rows the last call listed; only the named streams' rows are read, and lm_scores may
+        be None when no stream is named.  -> ((token, src_row, state, n_rows), finished): the lists name the root of a
+        named stream and every other beam again, unchanged.  finished, device=False: a dict with n_hyp, length, status
+        ([B] int32 copies; status 0 or the error code count(b) would raise with after end()) and hyps = {b: the list of
+        Hyp that results(b) gives after end()} for the named streams.  device=True: nothing is copied; the dict holds
+        the integer device addresses n_hyp, length, status, scores, tokens, words (None: lexicon-free), row_off --
+        tokens / words / row_off / length are what Context.collapse_rows(device=True) takes.  Both stay valid until
+        the next stream_finish(), end() or begin."""
+        w = np.ascontiguousarray(np.asarray(which) != 0, dtype=np.int32)
+        assert w.size == self.B, "which: one flag per stream"
+        out = self._rows()
+        args, keep = self._lm_in(lm_scores, lm_row_of, lm_kind, lm_lse_out, lm_dtype)
+        fo = FinishedOut()
+        self._chk(self.L.lib.fltx_ctc_rows_stream_finish(self.h, _ptr(w), *args, *[self._addr(o) for o in out],
+                                                         1 if device else 0, C.byref(fo)))
+        self._inputs = keep
+        if device:
+            return tuple(out), {f: getattr(fo, f) for f, _ in FinishedOut._fields_}
+        B, K = self.B, int(self.options.beam_size)
+        n_hyp, length, status = (_view(p, C.c_int32, B).copy() for p in (fo.n_hyp, fo.length, fo.status))
+        row_off = _view(fo.row_off, C.c_int64, B)
+        scores = _view(fo.scores, C.c_double, 3 * B * K)
+        hyps = {}
+        for b in np.flatnonzero(w):
+            n, ln, at = int(n_hyp[b]), int(length[b]), int(row_off[b])
+            hyps[int(b)] = []
+            for i in range(n if status[b] == 0 else 0):
+                tk = _view(fo.tokens + 4 * (at + i * ln), C.c_int32, ln).copy()
+                wd = _view(fo.words + 4 * (at + i * ln), C.c_int32, ln).copy() if fo.words else np.full(ln, -1, np.int32)
+                s = scores[3 * (b * K + i):3 * (b * K + i) + 3]
+                hyps[int(b)].append(Hyp(float(s[0]), float(s[1]), float(s[2]), tk, wd))
+        return tuple(out), {"n_hyp": n_hyp, "length": length, "status": status, "hyps": hyps}
 
     @staticmethod
     def _chunk_kw(chunk, kind, dtype):

@@ -340,6 +340,28 @@ __global__ void __launch_bounds__(kCrsOpThreads) fltx_ctc_rows_stream_collect_ke
   __shared__ __attribute__((aligned(16))) CrsCollectLds fltx_crs_collect_lds;
   crsCollect<LEX>(W, (char*)&fltx_crs_collect_lds);
 }
+/* fltx_ctc_rows_stream_finish: which rows its gather reads; decodeEnd and decodeBegin of the named streams in one launch,
+ * a workgroup per stream; the planner's rows of their ids given back (fltx_ctc_rows_plan.h) */
+__global__ void __launch_bounds__(kS2sBeginThreads) fltx_ctc_rows_stream_finish_mask_kernel(CrFinishParams Z) {
+  crsFinishMask(Z, nullptr);
+}
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_stream_finish_kernel(CrFinishParams Z) {
+  __shared__ __attribute__((aligned(16))) S2lStepLds fltx_crs_finish_lds;
+  crsFinishStream(Z, (char*)&fltx_crs_finish_lds);
+}
+template <int SRC>
+__global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_lex_stream_finish_kernel(CrlFinishParams Z) {
+  __shared__ __attribute__((aligned(16))) CrlStepLds fltx_crls_finish_lds;
+  crlsFinishStream<SRC>(Z, (char*)&fltx_crls_finish_lds);
+}
+__global__ void __launch_bounds__(kCpThreads) fltx_ctc_rows_plan_finish_count_kernel(CpFinishParams F) {
+  __shared__ CpLds lds;
+  cpFinishCount(F, (char*)&lds);
+}
+__global__ void __launch_bounds__(kCpThreads) fltx_ctc_rows_plan_finish_release_kernel(CpFinishParams F) {
+  __shared__ CpLds lds;
+  cpFinishRelease(F, (char*)&lds);
+}
 /* fltx_stream_partials.h: the partial transcript and the stable prefix of every stream (KIND 0: the classic streams,
  * 1 / 2: the lexicon-free / lexicon rows streams) */
 template <int KIND>
@@ -940,6 +962,12 @@ struct fltx_decoder {
     bool plOn = false, plFresh = false, plSkipped = false;
     int plRowCap = 0, plMetaPar = 0, plPrevPar = 0, plCollects = 0;
     DBuf plRowOf, plFree, plMeta, plPrev, plCnt, plRank;
+    /* fltx_ctc_rows_stream_finish: its results, apart from those of fltx_ctc_rows_end -- scores [B*K*3], tokens and
+     * words laid out by histOff, {n_hyp, length, status}[B] -- on the device and in pinned host memory; what it uploads
+     * per call, {row_off[B] int64, which[B] int32}, through pinned staging; the gather's mask */
+    DBuf finScores, finTok, finWrd, finMeta, finIn, finSkip;
+    HBuf hFinScores, hFinTok, hFinWrd, hFinMeta;
+    Staging finStage;
   } s2s;
 };
 
@@ -7585,6 +7613,170 @@ int fltx_ctc_rows_plan_release(fltx_decoder* d, const int32_t* released, const i
   S2S_LAUNCH(fltx_ctc_rows_plan_release_kernel, cpRelease, d->B, kCpThreads, sizeof(CpLds), d->ctx->stream, P);
   d->s2s.plMetaPar ^= 1;
   d->s2s.plCollects = std::max(0, d->s2s.plCollects - 1);
+  return FLTX_OK;
+}
+
+/* ---- finish and restart single streams (fltx_ctc_rows_stream.h) --------------------------------------------------------- */
+/* a copy home that waits for nothing: the caller synchronises once behind the last one */
+static int crsCopyHomeAsync(void* h, const void* dv, size_t n, Stream st) {
+#ifdef FLTX_EMU
+  (void)st;
+  memcpy(h, dv, n);
+  return 0;
+#else
+  return hipMemcpyAsync(h, dv, n, hipMemcpyDeviceToHost, st) == hipSuccess ? 0 : 1;
+#endif
+}
+
+int fltx_ctc_rows_stream_finish(fltx_decoder* d, const int32_t* which, const void* lmScores, int32_t lmDtype,
+                                int32_t lmKind, int64_t lmRowStride, const int32_t* lmRowOf, int32_t nLmRows,
+                                int32_t onDevice, double* lmRowLse, int32_t* nextTok, int32_t* nextSrc,
+                                int32_t* nextState, int32_t* nRows, int32_t resultsOnDevice, fltx_finished_out* out) {
+  const char* what = "fltx_ctc_rows_stream_finish";
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = crsCheck(d, what);
+  if (rc) {
+    return rc;
+  }
+  if (!which || !nextTok || !nextSrc || !nextState || !nRows || !out) {
+    return fail(FLTX_ERR_INVALID, "%s: null which, list or out", what);
+  }
+  if (d->s2s.t < d->s2s.crMaxT) {
+    return fail(FLTX_ERR_STATE, "%s: %d frames of the last chunk are unstepped (fltx_ctc_rows_step)", what,
+                d->s2s.crMaxT - d->s2s.t);
+  }
+  if (d->s2s.plOn && d->s2s.plCollects > 0) {
+    return fail(FLTX_ERR_STATE, "%s: fltx_ctc_rows_plan_release first (%d fltx_ctc_rows_stream_collect since the last "
+                                "plan)", what, d->s2s.plCollects);
+  }
+  Stream st = d->ctx->stream;
+  const int B = d->B, K = d->opt.beam_size;
+  const bool lex = d->kind == FLTX_DECODER_LEX_CTC_ROWS;
+  bool named = false;
+  for (int b = 0; b < B; ++b) {
+    named = named || which[b] != 0;
+  }
+  const size_t nRec = (size_t)std::max<int64_t>(d->histRecords, 1), inBytes = 12 * (size_t)B;
+  if (d->s2s.finScores.ensure(24 * (size_t)B * K, st, false) || d->s2s.finTok.ensure(4 * nRec, st, false) ||
+      (lex && d->s2s.finWrd.ensure(4 * nRec, st, false)) || d->s2s.finMeta.ensure(12 * (size_t)B, st, false) ||
+      d->s2s.finIn.ensure(inBytes, st, false) || d->s2s.finSkip.ensure(4 * (size_t)B, st, false) ||
+      (!resultsOnDevice && (d->s2s.hFinScores.ensure(24 * (size_t)B * K) || d->s2s.hFinTok.ensure(4 * nRec) ||
+                            (lex && d->s2s.hFinWrd.ensure(4 * nRec)) || d->s2s.hFinMeta.ensure(12 * (size_t)B)))) {
+    return fail(FLTX_ERR_OOM, "%s: allocation failed (B=%d K=%d)", what, B, K);
+  }
+  char* stage = (char*)d->s2s.finStage.acquire(inBytes);
+  if (!stage) {
+    return fail(FLTX_ERR_OOM, "%s: staging allocation failed", what);
+  }
+  memcpy(stage, d->histOff.data(), 8 * (size_t)B);
+  int32_t* stWhich = (int32_t*)(stage + 8 * (size_t)B);
+  for (int b = 0; b < B; ++b) {
+    stWhich[b] = which[b] != 0 ? 1 : 0;
+  }
+  if (devCopyH2D(d->s2s.finIn.p, stage, inBytes, st) || d->s2s.finStage.sent(st)) {
+    return fail(FLTX_ERR_HIP, "%s: upload failed", what);
+  }
+  int32_t* meta = d->s2s.finMeta.as<int32_t>();
+  CrParams Q = crParams(d);
+  Q.s.outTok = nextTok;
+  Q.s.outSrc = nextSrc;
+  Q.s.outN = nRows;
+  Q.outState = nextState;
+  Q.histOff = d->s2s.finIn.as<int64_t>();
+  Q.s.outScores = d->s2s.finScores.as<double>();
+  Q.s.tokens = d->s2s.finTok.as<int32_t>();
+  Q.s.outNHyp = meta;
+  Q.s.uttNBeam = meta;
+  Q.s.uttFrame = meta + B;
+  Q.s.uttStatus = meta + 2 * (size_t)B;
+  CrsFinishParams F;
+  memset(&F, 0, sizeof(F));
+  F.which = (const int32_t*)(Q.histOff + B);
+  F.skip = d->s2s.finSkip.as<int32_t>();
+  F.errUnsupported = FLTX_ERR_UNSUPPORTED;
+  F.errState = FLTX_ERR_STATE;
+  const CrFinishParams Z = {Q, crsParams(d), F};
+  if (named) { /* the finish entries of the named streams' rows, of those alone */
+    S2S_LAUNCH(fltx_ctc_rows_stream_finish_mask_kernel, crsFinishMask, (B + kS2sBeginThreads - 1) / kS2sBeginThreads,
+               kS2sBeginThreads, 0, st, Z);
+    CrParams G = Q;
+    G.s.done = F.skip;
+    if ((rc = crLmRowsIn(d, what, true, false, lmScores, lmDtype, lmKind, lmRowStride, lmRowOf, nLmRows, onDevice,
+                         lmRowLse, G))) {
+      return rc;
+    }
+    if (d->s2s.plOn) { /* their LM rows back to the planner, while the ids' count still stands */
+      CpFinishParams R;
+      memset(&R, 0, sizeof(R));
+      R.p = cpParams(d);
+      R.which = F.which;
+      R.sCount = Q.sCount;
+      S2S_LAUNCH(fltx_ctc_rows_plan_finish_count_kernel, cpFinishCount, B, kCpThreads, sizeof(CpLds), st, R);
+      S2S_LAUNCH(fltx_ctc_rows_plan_finish_release_kernel, cpFinishRelease, B, kCpThreads, sizeof(CpLds), st, R);
+      d->s2s.plMetaPar ^= 1;
+    }
+  }
+  if (lex) {
+    CrlFinishParams Y = {crlParams(d, Q), Z.x, F};
+    Y.r.words = d->s2s.finWrd.as<int32_t>();
+    if (d->s2s.isLmToken) {
+      S2S_LAUNCH(fltx_ctc_rows_lex_stream_finish_kernel<kCrlLmTokenRows>, crlsFinishStream<kCrlLmTokenRows>, B,
+                 kS2sStepThreads, sizeof(CrlStepLds), st, Y);
+    } else {
+      S2S_LAUNCH(fltx_ctc_rows_lex_stream_finish_kernel<kCrlLmWordRows>, crlsFinishStream<kCrlLmWordRows>, B,
+                 kS2sStepThreads, sizeof(CrlStepLds), st, Y);
+    }
+  } else {
+    S2S_LAUNCH(fltx_ctc_rows_stream_finish_kernel, crsFinishStream, B, kS2sStepThreads, sizeof(S2lStepLds), st, Z);
+  }
+  d->s2s.crBestLb = -1;
+  for (int b = 0; b < B; ++b) {
+    if (which[b] != 0) {
+      d->s2s.crBuf[(size_t)b] = 0;
+    }
+  }
+  d->s2s.plSkipped = d->s2s.plSkipped || d->s2s.plFresh; /* (the list before this one was never planned) */
+  d->s2s.plFresh = true;
+  memset(out, 0, sizeof(*out));
+  if (resultsOnDevice) {
+    out->n_hyp = meta;
+    out->length = meta + B;
+    out->status = meta + 2 * (size_t)B;
+    out->scores = d->s2s.finScores.as<double>();
+    out->tokens = d->s2s.finTok.as<int32_t>();
+    out->words = lex ? d->s2s.finWrd.as<int32_t>() : nullptr;
+    out->row_off = Q.histOff;
+    return FLTX_OK;
+  }
+  /* home: the counts first, then what the named streams really have -- n_hyp * length entries each */
+  int32_t* hMeta = (int32_t*)d->s2s.hFinMeta.p;
+  if (devCopyD2H(hMeta, meta, 12 * (size_t)B, st)) {
+    return fail(FLTX_ERR_HIP, "%s: result copy failed: %s", what, devErr());
+  }
+  int bad = 0;
+  for (int b = 0; b < B && !bad; ++b) {
+    const size_t n = (size_t)hMeta[b], at = (size_t)d->histOff[(size_t)b], cnt = n * (size_t)hMeta[(size_t)B + b];
+    if (n == 0) {
+      continue;
+    }
+    const size_t sAt = 3 * (size_t)b * K;
+    bad = crsCopyHomeAsync((double*)d->s2s.hFinScores.p + sAt, d->s2s.finScores.as<double>() + sAt, 24 * n, st) ||
+          crsCopyHomeAsync((int32_t*)d->s2s.hFinTok.p + at, d->s2s.finTok.as<int32_t>() + at, 4 * cnt, st) ||
+          (lex && crsCopyHomeAsync((int32_t*)d->s2s.hFinWrd.p + at, d->s2s.finWrd.as<int32_t>() + at, 4 * cnt, st));
+  }
+  if (bad || devSync(st)) {
+    return fail(FLTX_ERR_HIP, "%s: result copy failed: %s", what, devErr());
+  }
+  out->n_hyp = hMeta;
+  out->length = hMeta + B;
+  out->status = hMeta + 2 * (size_t)B;
+  out->scores = (const double*)d->s2s.hFinScores.p;
+  out->tokens = (const int32_t*)d->s2s.hFinTok.p;
+  out->words = lex ? (const int32_t*)d->s2s.hFinWrd.p : nullptr;
+  out->row_off = d->histOff.data();
   return FLTX_OK;
 }
 

@@ -620,12 +620,8 @@ FLTX_DEV void crStepUtterance(const CrParams& Q, char* smem, const CrsParams* X 
 }
 
 /* decodeBegin (:20-28): the root (token sil) in LM::start's state (sid 0); the first call's single row */
-FLTX_DEV void crBeginUtterance(const CrParams& Q, char*) {
+FLTX_DEV void crBeginOne(const CrParams& Q, int b) {
   const S2sParams& P = Q.s;
-  const int b = (int)(blockIdx.x * kS2sBeginThreads + threadIdx.x);
-  if (b >= P.B) {
-    return;
-  }
   const int64_t rb = (int64_t)b * P.K;
   CrHyp h;
   h.score = 0.0;
@@ -653,6 +649,13 @@ FLTX_DEV void crBeginUtterance(const CrParams& Q, char*) {
     Q.outState[rb + k] = k == 0 ? 0 : -1;
   }
   P.outN[b] = 1;
+}
+
+FLTX_DEV void crBeginUtterance(const CrParams& Q, char*) {
+  const int b = (int)(blockIdx.x * kS2sBeginThreads + threadIdx.x);
+  if (b < Q.s.B) {
+    crBeginOne(Q, b);
+  }
 }
 
 } // namespace fltx

@@ -557,13 +557,9 @@ FLTX_DEV void crlStepTyped(const CrlTypedParams& Y, char* smem) {
 
 /* decodeBegin (:21-30): the root (token sil) at the trie's root in LM::start's state (sid 0); the first call's single
  * row, made by no edge */
-FLTX_DEV void crlBeginUtterance(const CrlParams& R, char*) {
+FLTX_DEV void crlBeginOne(const CrlParams& R, int b) {
   const CrParams& Q = R.c;
   const S2sParams& P = Q.s;
-  const int b = (int)(blockIdx.x * kS2sBeginThreads + threadIdx.x);
-  if (b >= P.B) {
-    return;
-  }
   const int64_t rb = (int64_t)b * P.K;
   CrlHyp h;
   h.score = 0.0;
@@ -599,6 +595,13 @@ FLTX_DEV void crlBeginUtterance(const CrlParams& R, char*) {
     Q.outState[rb + k] = k == 0 ? 0 : -1;
   }
   P.outN[b] = 1;
+}
+
+FLTX_DEV void crlBeginUtterance(const CrlParams& R, char*) {
+  const int b = (int)(blockIdx.x * kS2sBeginThreads + threadIdx.x);
+  if (b < R.c.s.B) {
+    crlBeginOne(R, b);
+  }
 }
 
 } // namespace fltx

@@ -20,7 +20,9 @@
  *              then rowOf, the four lists, lm_row_of and its copy.  meta and prev are kept twice and read from one half,
  *              written to the other: a workgroup never reads what another one writes.
  * A release is the same pair: cpReleaseCount counts the listed ids of a stream that hold a row, cpRelease pushes those
- * rows -- stream b ascending, in listed order -- and clears rowOf (for a dropped id too).
+ * rows -- stream b ascending, in listed order -- and clears rowOf (for a dropped id too).  fltx_ctc_rows_stream_finish
+ * releases every id of the streams it names with the same pair on the ids themselves (cpFinishCount, cpFinishRelease):
+ * stream b ascending, ids ascending.
  *
  * The bodies are FLTX_DEV functions on fltx_rt.h's primitives, so tests/emu runs them as it runs the other steps.
  */
@@ -237,6 +239,67 @@ FLTX_DEV void cpRelease(const CpParams& P, char* smem) {
     const int r = cpBlockRank(L, holds, total);
     if (id >= 0 && id < P.sMax) {
       int32_t* at0 = P.rowOf + (int64_t)b * P.sMax + id;
+      if (holds && at + r < P.rowCap) { /* (rows pushed <= rows handed out <= rowCap) */
+        P.freeRows[at + r] = *at0;
+      }
+      *at0 = -1;
+    }
+    at += total;
+  }
+  if (b == 0 && tid == 0) {
+    nxt[0] = nFree + all < P.rowCap ? nFree + all : P.rowCap;
+    nxt[1] = cur[1];
+    nxt[2] = cur[2];
+  }
+}
+
+/* fltx_ctc_rows_stream_finish: every id of a named stream below its high-water mark is released, ascending -- the same
+ * pair on the ids themselves, queued BEFORE the finish kernel starts the stream's count over */
+struct CpFinishParams {
+  CpParams p;
+  const int32_t* which;  /* [B] != 0: the stream is named */
+  const int32_t* sCount; /* [B] ids handed out (may have passed sMax on a full table) */
+};
+
+FLTX_DEV int cpFinishIds(const CpFinishParams& F, int b) {
+  const int n = F.sCount[b];
+  return F.which[b] == 0 || n < 0 ? 0 : n > F.p.sMax ? F.p.sMax : n;
+}
+
+FLTX_DEV void cpFinishCount(const CpFinishParams& F, char* smem) {
+  const CpParams& P = F.p;
+  CpLds& L = *(CpLds*)smem;
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+  const int n = cpFinishIds(F, b);
+  int sum = 0;
+  for (int base = 0; base < n; base += kCpThreads) {
+    int total;
+    cpBlockRank(L, base + tid < n && P.rowOf[(int64_t)b * P.sMax + base + tid] >= 0, total);
+    sum += total;
+  }
+  if (tid == 0) {
+    P.cnt[b] = sum;
+  }
+}
+
+FLTX_DEV void cpFinishRelease(const CpFinishParams& F, char* smem) {
+  const CpParams& P = F.p;
+  CpLds& L = *(CpLds*)smem;
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+  int off, all;
+  cpSums(P, L, b, off, all);
+  const int32_t* cur = P.meta + 4 * P.metaPar;
+  int32_t* nxt = P.meta + 4 * (P.metaPar ^ 1);
+  const int nFree = cur[0];
+  const int n = cpFinishIds(F, b);
+  int at = nFree + off;
+  for (int base = 0; base < n; base += kCpThreads) {
+    const int id = base + tid;
+    int32_t* at0 = P.rowOf + (int64_t)b * P.sMax + id;
+    const bool holds = id < n && *at0 >= 0;
+    int total;
+    const int r = cpBlockRank(L, holds, total);
+    if (id < n) {
       if (holds && at + r < P.rowCap) { /* (rows pushed <= rows handed out <= rowCap) */
         P.freeRows[at + r] = *at0;
       }

@@ -22,6 +22,13 @@
  *                                           the lexicon kind, on to a complete hypothesis (its parent ended a word, or
  *                                           it has none), lookBack + kLookBackLimit steps at most.  best writes the
  *                                           ancestor's scores and its path; prune the new base and the normalised scores.
+ *   fltx_ctc_rows_stream_collect_kernel<LEX> the LM-state ids nothing can meet again, back to the stream's free stack
+ *   fltx_ctc_rows_stream_finish_kernel,     fltx_ctc_rows_stream_finish: one workgroup per stream.  A stream the call
+ *   fltx_ctc_rows_lex_stream_finish_kernel  does not name lists its beam again and returns.  A named one runs the end
+ *                                           variant's body against the finish's own result buffers and then, behind a
+ *                                           barrier, the begin for this b: the root in the beam and both rings, the
+ *                                           counts and the ids started over, and its slice of the state table emptied --
+ *                                           the one part whose cost grows with max_states (1 MB of keys at the default).
  */
 #pragma once
 
@@ -40,12 +47,8 @@ struct CrlStreamParams {
 };
 
 /* ---- begin, step, end: the offline bodies on a stream's counts -------------------------------------------------------- */
-FLTX_DEV void crsBeginCounts(const CrParams& Q, const CrsParams& X) {
+FLTX_DEV void crsBeginCountsOne(const CrParams& Q, const CrsParams& X, int b) {
   const S2sParams& P = Q.s;
-  const int b = (int)(blockIdx.x * kS2sBeginThreads + threadIdx.x);
-  if (b >= P.B) {
-    return;
-  }
   X.nDec[b] = 0;
   X.base[b] = 0;
   X.sFreeN[b] = 0; /* no id is free; id 0, LM::start, is allocated and has no table entry */
@@ -56,6 +59,13 @@ FLTX_DEV void crsBeginCounts(const CrParams& Q, const CrsParams& X) {
   sc[0] = 0.0;
   sc[1] = 0.0;
   sc[2] = 0.0;
+}
+
+FLTX_DEV void crsBeginCounts(const CrParams& Q, const CrsParams& X) {
+  const int b = (int)(blockIdx.x * kS2sBeginThreads + threadIdx.x);
+  if (b < Q.s.B) {
+    crsBeginCountsOne(Q, X, b);
+  }
 }
 
 FLTX_DEV void crsBeginStream(const CrStreamParams& Z, char* smem) {
@@ -417,6 +427,104 @@ FLTX_DEV void crsCollect(const CrsCollectParams& W, char* smem) {
       }
       slot = (slot + 1u) & sMask;
     }
+  }
+}
+
+/* ---- finish: decodeEnd and decodeBegin of the named streams, the others untouched ------------------------------------- */
+struct CrsFinishParams {
+  const int32_t* which; /* [B] != 0: the stream is named */
+  int32_t* skip;        /* [B] what the finish's gather reads as `done`: the stream stopped, or is not named */
+  int32_t errUnsupported, errState; /* the FLTX_ERR_* of a stopped stream's status */
+};
+
+struct CrFinishParams {
+  CrParams c; /* c.s.outScores / tokens / outNHyp (= uttNBeam) / uttFrame / uttStatus, c.histOff: the finish's results */
+  CrsParams x;
+  CrsFinishParams f;
+};
+
+struct CrlFinishParams {
+  CrlParams r; /* likewise, and r.words */
+  CrsParams x;
+  CrsFinishParams f;
+};
+
+/* before the gather: only rows of named streams that have not stopped are read (crRowLive) */
+FLTX_DEV void crsFinishMask(const CrFinishParams& Z, char*) {
+  const int b = (int)(blockIdx.x * kS2sBeginThreads + threadIdx.x);
+  if (b < Z.c.s.B) {
+    Z.f.skip[b] = Z.c.s.done[b] || Z.f.which[b] == 0 ? 1 : 0;
+  }
+}
+
+/* a stream the call does not name: its beam listed again as a step without frames lists it, an empty result */
+template <typename Hyp>
+FLTX_DEV void crsFinishIdle(const CrParams& Q, const Hyp* beam, int b, int nd) {
+  const S2sParams& P = Q.s;
+  const int K = P.K;
+  const int64_t rb = (int64_t)b * K;
+  const Hyp* prev = beam + (size_t)(nd & 1) * P.B * K + rb;
+  const int nPrev = P.done[b] ? 0 : P.beamN[b];
+  for (int k = (int)threadIdx.x; k < K; k += kS2sStepThreads) {
+    const bool in = k < nPrev;
+    P.outTok[rb + k] = -1;
+    P.outBeam[rb + k] = in ? k : -1;
+    P.outSrc[rb + k] = in ? (int32_t)(rb + k) : -1;
+    Q.outState[rb + k] = in ? prev[k].sid : -1;
+  }
+  if (threadIdx.x == 0) {
+    P.outN[b] = nPrev;
+    P.outNHyp[b] = 0;
+    P.uttFrame[b] = 0;
+    P.uttStatus[b] = 0;
+  }
+}
+
+/* behind a named stream's decodeEnd and a barrier: its state table emptied (16 bytes a store), and what the finish body
+ * left in uttFrame / uttStatus turned into the entries per hypothesis and the FLTX_ERR_* of the status.  Thread 0 then
+ * runs the kind's decodeBegin for this b. */
+FLTX_DEV void crsFinishRestart(const CrParams& Q, const CrsFinishParams& F, int b) {
+  const S2sParams& P = Q.s;
+  uint4* keys = (uint4*)(Q.sKey + (size_t)b * Q.sSize); /* (sSize is a power of two >= 2: whole 16-byte pairs) */
+  for (int i = (int)threadIdx.x; i < Q.sSize / 2; i += kS2sStepThreads) {
+    keys[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
+  }
+  if (threadIdx.x == 0) {
+    const int s = P.uttStatus[b];
+    P.uttFrame[b] += 1;
+    P.uttStatus[b] = (s & (ST_CAND_OVERFLOW | ST_TABLE_FULL | ST_SELECT_FALLBACK)) ? F.errUnsupported
+                                                                                    : (s & ST_HLM_MISS) ? F.errState : 0;
+  }
+}
+
+FLTX_DEV void crsFinishStream(const CrFinishParams& Z, char* smem) {
+  const int b = (int)blockIdx.x;
+  if (Z.f.which[b] == 0) {
+    crsFinishIdle(Z.c, Z.c.beam, b, Z.x.nDec[b]);
+    return;
+  }
+  crStepUtterance<true, true>(Z.c, smem, &Z.x);
+  __syncthreads(); /* (the walks have read the rings and the beam the begin writes to) */
+  crsFinishRestart(Z.c, Z.f, b);
+  if (threadIdx.x == 0) {
+    crBeginOne(Z.c, b);
+    crsBeginCountsOne(Z.c, Z.x, b);
+  }
+}
+
+template <int SRC>
+FLTX_DEV void crlsFinishStream(const CrlFinishParams& Z, char* smem) {
+  const int b = (int)blockIdx.x;
+  if (Z.f.which[b] == 0) {
+    crsFinishIdle(Z.r.c, Z.r.beam, b, Z.x.nDec[b]);
+    return;
+  }
+  crlStepUtterance<SRC, true, true>(Z.r, smem, &Z.x);
+  __syncthreads();
+  crsFinishRestart(Z.r.c, Z.f, b);
+  if (threadIdx.x == 0) {
+    crlBeginOne(Z.r, b);
+    crsBeginCountsOne(Z.r.c, Z.x, b);
   }
 }
 
