@@ -408,6 +408,61 @@ FLTX_API int fltx_s2s_done(fltx_decoder* dec, int32_t* done);
  * hypotheses -- becomes the decoder's results. */
 FLTX_API int fltx_s2s_end(fltx_decoder* dec);
 
+/* ---- seq2seq: finish and restart single utterances of a running batch ------------------------------------------------
+ * Autoregressive utterances end after very different numbers of steps, and the model runs on the rows the step lists:
+ * fltx_s2s_finish ends the utterances of the slots `which` names (a HOST array of B: 0 leave, 1 finish + restart,
+ * 2 finish + park), hands out their n-best and restarts or parks those slots, in one call, and leaves every other
+ * utterance alone.  Both seq2seq kinds, every LM (ZeroLM / n-gram, token rows, word rows).  Every slot counts its own
+ * steps: max_output_length holds per utterance, from its (re)start, whatever the batch has done before.
+ *
+ * A named slot b first gets fltx_s2s_end's back-trace for that utterance alone: its last non-empty beam, which may hold
+ * unfinished hypotheses -- naming a running utterance aborts it.  Rows and scores are bit for bit what fltx_s2s_end would
+ * have written for it; they go into result buffers of the finish's own, and fltx_result_* keep returning what they
+ * returned before the call.  An utterance that had stopped (lexicon kind: state table full) is finished as fltx_s2s_end
+ * finishes it: status[b] says why it had stopped.
+ * A slot named with 1 is then in exactly the state fltx_s2s_begin leaves an utterance in: the root in the current beam,
+ * local step 0, `done` cleared; lexicon kind: the slot's state table empty and its count started over (max_states
+ * stays), its status and its merge count (fltx_s2s_lex_info) cleared; word rows: the listed root row's trie node is the
+ * root.  Nothing later reads a record of the utterance before.
+ * A slot named with 2 is parked: it lists no rows, steps skip it, fltx_s2s_done and fltx_s2s_done_each count it as done,
+ * fltx_s2s_end returns n_hyp 0 for it.  A later finish that names a parked slot with 1 restarts it and reports n_hyp 0,
+ * steps 0, status 0 for it; naming it with 2 again changes nothing.
+ * Of every other slot nothing is written; every later call decides for it, bit for bit, what it would have decided
+ * without this call.
+ *
+ * The lists (DEVICE, as fltx_s2s_step's; next_word: required with a word-level rows LM, else NULL): a restarted slot
+ * lists the root as fltx_s2s_begin does -- one row, next_token -1, next_beam_idx -1, next_src_row -1, next_word -1; a
+ * parked slot lists none; every other slot lists its current rows again with next_src_row the row itself (b*K + k) --
+ * the model's index_select is the identity for it -- and next_token, next_beam_idx and next_word what the last step
+ * listed (they are read back from the slot's beam, which holds them).  The call after a finish is a step: the model
+ * runs on these lists, a restarted slot's root row with fresh state.
+ *
+ * Results, in `out`: results_on_device != 0 -- the pointers address HBM, written in the order of the context's stream;
+ * nothing crosses PCIe and the call does not wait.  results_on_device == 0 -- pinned host buffers, complete when the
+ * call returns: the counts of all B slots cross, then n_hyp * length entries and 3 n_hyp scores of each named slot.
+ * Both stay valid until the next finish, fltx_s2s_end or fltx_s2s_begin on this decoder; steps do not disturb them.
+ *
+ * A call that names nothing is legal and changes nothing: it lists every slot's rows again.
+ * fltx_s2s_end after finishes still ends all slots: a restarted slot returns what it has decoded since its restart, a
+ * parked slot n_hyp 0.
+ * FLTX_ERR_STATE before fltx_s2s_begin, after fltx_s2s_end, and on every kind that is not seq2seq.  FLTX_ERR_INVALID on a
+ * NULL which, list or out, a which entry outside 0..2, and a NULL next_word on a word-rows decoder. */
+typedef struct fltx_s2s_finished_out {
+  const int32_t* n_hyp;   /* [B] 0 for a slot not named and for a parked slot */
+  const int32_t* steps;   /* [B] local steps the finished utterance took; 0 for a slot not named */
+  const int32_t* status;  /* [B] 0, or the FLTX_ERR_* fltx_result_count would report after fltx_s2s_end */
+  const double* scores;   /* [B*K*3] score, emitting-model score, LM score */
+  const int32_t* tokens;  /* hypothesis k of slot b at (b*K + k) * length, right-aligned, -1 in front, as fltx_s2s_end */
+  const int32_t* words;   /* likewise; NULL for the lexicon-free kind */
+  int32_t length;         /* max_output_length + 3 */
+} fltx_s2s_finished_out;
+FLTX_API int fltx_s2s_finish(fltx_decoder* dec, const int32_t* which, int32_t* next_token, int32_t* next_beam_idx,
+                             int32_t* next_src_row, int32_t* n_rows, int32_t* next_word, int32_t results_on_device,
+                             fltx_s2s_finished_out* out);
+/* done[b] (HOST, B entries) = 1 when the utterance in slot b is done or the slot is parked: fltx_s2s_done per slot (one
+ * copy; synchronises).  What a server names in fltx_s2s_finish. */
+FLTX_API int fltx_s2s_done_each(fltx_decoder* dec, int32_t* done);
+
 /* ---- seq2seq: LexiconSeq2SeqDecoder as a batched device step --------------- */
 /* LexiconSeq2SeqDecoderOptions (decoder/LexiconSeq2SeqDecoder.h:23-31). */
 typedef struct fltx_s2s_lex_options {

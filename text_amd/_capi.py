@@ -100,6 +100,12 @@ class FinishedOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("n_hyp", "length", "status", "scores", "tokens", "words", "row_off")]
 
 
+class S2sFinishedOut(C.Structure):
+    """fltx_s2s_finished_out (include/fltx.h)"""
+    _fields_ = [(n, C.c_void_p) for n in ("n_hyp", "steps", "status", "scores", "tokens", "words")] + \
+        [("length", C.c_int32)]
+
+
 def _view(ptr, ctype, n):
     """n elements at a host address as a NumPy array (no copy)"""
     if n == 0 or not ptr:
@@ -150,7 +156,7 @@ class Lib:
         "fltx_decoder_bytes", "fltx_htrie_node", "fltx_group_create", "fltx_group_destroy", "fltx_group_size", "fltx_group_decoder",
         "fltx_group_decode_batch", "fltx_group_result_count", "fltx_group_result_fetch", "fltx_group_synchronize",
         "fltx_s2s_decoder_create", "fltx_s2s_begin", "fltx_s2s_step", "fltx_s2s_step_typed", "fltx_s2s_done",
-        "fltx_s2s_end", "fltx_s2s_lex_decoder_create", "fltx_s2s_lex_set_max_states", "fltx_s2s_lex_info",
+        "fltx_s2s_end", "fltx_s2s_finish", "fltx_s2s_done_each", "fltx_s2s_lex_decoder_create", "fltx_s2s_lex_set_max_states", "fltx_s2s_lex_info",
         "fltx_lm_rows_create", "fltx_s2s_step_lm_rows",
         "fltx_lm_word_rows_create", "fltx_s2s_step_word_lm_rows",
         "fltx_ctc_rows_decoder_create", "fltx_ctc_rows_lex_decoder_create", "fltx_ctc_rows_begin", "fltx_ctc_rows_step", "fltx_ctc_rows_end",
@@ -239,6 +245,8 @@ class Lib:
                                            vp, vp],
             "fltx_s2s_done": [vp, vp],
             "fltx_s2s_end": [vp],
+            "fltx_s2s_finish": [vp, vp, vp, vp, vp, vp, vp, i32, C.POINTER(S2sFinishedOut)],
+            "fltx_s2s_done_each": [vp, vp],
             "fltx_s2s_lex_decoder_create": [vp, C.POINTER(S2sLexOptions), vp, vp, i32, i32, i32, pvp],
             "fltx_s2s_lex_set_max_states": [vp, i32],
             "fltx_s2s_lex_info": [vp, vp, vp, vp, vp],
@@ -1192,6 +1200,124 @@ class Seq2SeqBatchDecoder(BatchDecoder):
     def end(self):
         self._chk(self.L.lib.fltx_s2s_end(self.h))
         self.N = self.V
+
+    def done_each(self):
+        """-> [B] bool: the utterance in the slot is done, or the slot is parked (fltx_s2s_done_each; a host wait)"""
+        v = np.zeros(max(self.B, 1), np.int32)
+        self.L.check(self.L.lib.fltx_s2s_done_each(self.h, _ptr(v)))
+        return v[:self.B] != 0
+
+    def finish(self, which, results_on_device=False):
+        """End the utterances of the slots `which` names (B entries: 0 leave, 1 finish + restart, 2 finish + park),
+        leaving every other utterance as it is (fltx_s2s_finish).  -> (lists, finished): the lists are step()'s
+        (token, beam_idx, src_row, n_rows[, next_word]) -- the root for a restarted slot, nothing for a parked one,
+        every other slot's rows again with src_row the row itself.  finished, results_on_device=False: a dict with
+        n_hyp, steps, status ([B] int32 copies; status 0 or the error code count(b) would raise with after end()) and
+        hyps = {b: the list of Hyp that results(b) gives after end()} for the named slots.  results_on_device=True:
+        nothing is copied and the call does not wait; the dict holds the integer device addresses n_hyp, steps, status,
+        scores, tokens, words (None: lexicon-free) and `length`.  Both stay valid until the next finish(), end() or
+        begin(); steps do not disturb them."""
+        w = np.ascontiguousarray(np.asarray(which), dtype=np.int32).reshape(-1)
+        assert w.size == self.B, "which: one entry per slot"
+        out = self._rows()
+        word = None
+        if isinstance(self._keep[0], WordRowsLM):
+            word = out[0].copy() if self._emu else out[0].clone()
+        fo = S2sFinishedOut()
+        self._chk(self.L.lib.fltx_s2s_finish(self.h, _ptr(w), *[self._addr(o) for o in out],
+                                             None if word is None else self._addr(word),
+                                             1 if results_on_device else 0, C.byref(fo)))
+        if word is not None:
+            out.append(word)
+        if results_on_device:
+            return tuple(out), {f: getattr(fo, f) for f, _ in S2sFinishedOut._fields_}
+        B, K, ln = self.B, int(self.options.beam_size), int(fo.length)
+        n_hyp, steps, status = (_view(p, C.c_int32, B).copy() for p in (fo.n_hyp, fo.steps, fo.status))
+        scores = _view(fo.scores, C.c_double, 3 * B * K)
+        hyps = {}
+        for b in map(int, np.flatnonzero(w)):
+            hyps[b] = []
+            for i in range(int(n_hyp[b]) if status[b] == 0 else 0):
+                at = (b * K + i) * ln
+                tk = _view(fo.tokens + 4 * at, C.c_int32, ln).copy()
+                wd = _view(fo.words + 4 * at, C.c_int32, ln).copy() if fo.words else np.full(ln, -1, np.int32)
+                s = scores[3 * (b * K + i):3 * (b * K + i) + 3]
+                hyps[b].append(Hyp(float(s[0]), float(s[1]), float(s[2]), tk, wd))
+        return tuple(out), {"n_hyp": n_hyp, "steps": steps, "status": status, "hyps": hyps}
+
+    def _finish_between(self, listed, which):
+        """finish(which) between the call that returned `listed` and the step_fn call that consumes it.  step_fn gathers
+        its state and advances it in one call and has not seen `listed` yet: the slots that are not named keep the
+        src_row `listed` has for them (-1 on a root row; the finish lists the same rows with src_row the row itself),
+        the named ones take the finish's.  -> (lists, finished)"""
+        lists, fin = self.finish(which)
+        named = np.asarray(which) != 0
+        if self._emu:
+            src = np.where(named[:, None], lists[2], listed[2])
+        else:
+            import torch
+            src = torch.where(torch.as_tensor(named, device=lists[2].device)[:, None], lists[2], listed[2])
+        return lists[:2] + (src,) + lists[3:], fin
+
+    def decode_queue(self, step_fn, n_utterances, B, V, check_every=4, *, kind="log_probs"):
+        """Continuous batching: n_utterances go through B slots, none waits for another.  The loop steps, asks
+        done_each() every `check_every` steps (a host wait), finishes the done slots, admits the next utterances of
+        the queue into them and parks slots once the queue is empty.  step_fn(token [B*K], src_row [B*K], row_mask
+        [B*K] bool, t, slot_utt, restarted) -> what decode()'s step_fn returns (a decoder made with a RowsLM:
+        (scores, row_valid, lm_scores)); slot_utt [B] int64 (host): the queue entry in each slot, -1 for a parked one;
+        restarted [B] bool (host): the slots whose single listed row is a new utterance's root -- the model starts
+        their state afresh (src_row is -1 there).  A decoder with a WordRowsLM is stepped by hand (lm_row_of is the
+        caller's).  -> [[Hyp]] in queue order, each what decode() returns for that utterance."""
+        assert not isinstance(self._keep[0], WordRowsLM), "decode_queue: step a WordRowsLM decoder by hand"
+        K = int(self.options.beam_size)
+        n_utt, B = int(n_utterances), int(B)
+        results = [None] * n_utt
+        slot_utt = np.full(B, -1, np.int64)
+        lists = self.begin(B, V)
+        nxt = min(B, n_utt)
+        slot_utt[:nxt] = np.arange(nxt)
+        restarted = slot_utt >= 0
+        if nxt < B:  # fewer utterances than slots: the rest is parked before the first step
+            lists, _ = self._finish_between(lists, np.where(slot_utt >= 0, 0, 2).astype(np.int32))
+        if self._emu:
+            ar = np.arange(K, dtype=np.int32)
+        else:
+            import torch
+            ar = torch.arange(K, device=lists[3].device, dtype=torch.int32)
+        t = since = 0
+        while (slot_utt >= 0).any():
+            tok, beam, src, n = lists[:4]
+            mask = (ar[None, :] < n[:, None]).reshape(-1)
+            r = step_fn(tok.reshape(-1), src.reshape(-1), mask, t, slot_utt.copy(), restarted.copy())
+            r = r if isinstance(r, tuple) else (r, None)
+            kw = {"lm_scores": r[2]} if len(r) > 2 else {}
+            lists = self.step(r[0], r[1], kind=kind, **kw)
+            restarted = np.zeros(B, bool)
+            t += 1
+            since += 1
+            if since < min(check_every, self.max_output_length):
+                continue
+            since = 0
+            done = self.done_each() & (slot_utt >= 0)
+            if not done.any():
+                continue
+            which = np.zeros(B, np.int32)
+            for b in np.flatnonzero(done):
+                which[b] = 1 if nxt < n_utt else 2
+                nxt += which[b] == 1
+            lists, fin = self._finish_between(lists, which)
+            for b in np.flatnonzero(done):
+                if fin["status"][b] != 0:
+                    raise FltxError(int(fin["status"][b]), "decode_queue: utterance %d stopped" % slot_utt[b])
+                results[slot_utt[b]] = fin["hyps"][int(b)]
+            adm = nxt - int((which == 1).sum())
+            for b in np.flatnonzero(which == 1):
+                slot_utt[b] = adm
+                adm += 1
+                restarted[b] = True
+            slot_utt[which == 2] = -1
+        self.end()
+        return results
 
     def decode(self, step_fn, B, V, check_every=8, *, kind="log_probs"):
         """The whole search: step_fn(token [B*K], src_row [B*K], row_mask [B*K] bool, t) -> scores [B*K, V] (or

@@ -192,6 +192,11 @@ __global__ void __launch_bounds__(kS2sBeginThreads) fltx_s2s_begin_kernel(S2sPar
 __global__ void __launch_bounds__(kS2sEndThreads) fltx_s2s_end_kernel(S2sParams P) {
   s2sEndUtterance(P, nullptr);
 }
+/* fltx_s2s_finish: a named slot's back-trace, then its restart or parking; every other slot's rows listed again */
+__global__ void __launch_bounds__(kS2sEndThreads) fltx_s2s_finish_kernel(S2sFinishKernelParams Z) {
+  __shared__ S2sFinishLds fltx_s2s_finish_lds;
+  s2sFinishUtterance(Z, (char*)&fltx_s2s_finish_lds);
+}
 /* the typed front end (fltx_s2s_step_typed): fp16 / bf16 rows, and logits of any of the three types */
 template <int DT, bool LOGITS>
 __global__ void __launch_bounds__(kS2sTypedThreads) fltx_s2s_typed_kernel(S2sTypedParams Q) {
@@ -233,6 +238,10 @@ __global__ void __launch_bounds__(kS2sBeginThreads) fltx_s2s_lex_begin_kernel(S2
 }
 __global__ void __launch_bounds__(kS2sEndThreads) fltx_s2s_lex_end_kernel(S2lParams Q) {
   s2lEndUtterance(Q, nullptr);
+}
+__global__ void __launch_bounds__(kS2sEndThreads) fltx_s2s_lex_finish_kernel(S2lFinishKernelParams Z) {
+  __shared__ S2sFinishLds fltx_s2l_finish_lds;
+  s2lFinishUtterance(Z, (char*)&fltx_s2l_finish_lds);
 }
 /* fltx_ctc_rows.h: lexicon-free CTC with a rows LM -- the frames' token beams (once), the LM entries of a frame's kept
  * tokens, the frame step and its finish variant (decodeEnd + back-trace), the start */
@@ -924,6 +933,13 @@ struct fltx_decoder {
     int64_t nodes = 0, edges = 0, labels = 0, trieBytes = 0;
     DBuf trieMax, kidOff, kidTok, kidNode, labOff, lab; /* the compact trie */
     DBuf cScore, cMk, cGrp, cList, cNext, mTab, sKey, sVal, sCount, status, merges;
+    /* a step count per slot (fltx_s2s_finish): origin[B] and parked[B] live behind finalStep on the device (s2sOrigin);
+     * this is what the host knows of them from `which` -- the batch's step count at each slot's last (re)start, the
+     * parked slots, and the step count from which no slot can be live any more (the largest origin + max_output_length
+     * of a slot not parked) */
+    std::vector<int32_t> hOrigin;
+    std::vector<uint8_t> hParked;
+    int liveUntil = 0;
     /* lexicon-free CTC with a rows LM (kind FLTX_DECODER_CTC_ROWS, fltx_ctc_rows.h; it shares the buffers above): the
      * longest utterance, frames in all, {frameOff[B + 1], emOff[B]} int64 then T[B] int32 on the device and their host
      * copy, the device copy of host emissions */
@@ -964,7 +980,10 @@ struct fltx_decoder {
     DBuf plRowOf, plFree, plMeta, plPrev, plCnt, plRank;
     /* fltx_ctc_rows_stream_finish: its results, apart from those of fltx_ctc_rows_end -- scores [B*K*3], tokens and
      * words laid out by histOff, {n_hyp, length, status}[B] -- on the device and in pinned host memory; what it uploads
-     * per call, {row_off[B] int64, which[B] int32}, through pinned staging; the gather's mask */
+     * per call, {row_off[B] int64, which[B] int32}, through pinned staging; the gather's mask.
+     * fltx_s2s_finish shares these buffers (a decoder is of one kind): its results, apart from those of fltx_s2s_end, are
+     * scores [B*K*3], tokens and words [B*K][len] and {n_hyp, steps, status, the back-trace's two other counts}[B] in
+     * finMeta; which[B] goes up through finStage into finIn */
     DBuf finScores, finTok, finWrd, finMeta, finIn, finSkip;
     HBuf hFinScores, hFinTok, hFinWrd, hFinMeta;
     Staging finStage;
@@ -5472,7 +5491,7 @@ static S2sParams s2sParams(fltx_decoder* d) {
   P.V = d->N;
   P.eos = d->s2s.eos;
   P.maxOut = d->s2s.maxOut;
-  P.t = std::min(d->s2s.t, d->s2s.maxOut);
+  P.t = d->s2s.t;
   P.cap = d->s2s.cap;
   P.mSel = d->s2s.mSel;
   P.eosExtra = d->s2s.eosExtra;
@@ -5928,7 +5947,7 @@ int fltx_s2s_begin(fltx_decoder* d, int32_t B, int32_t V, int32_t* nextTok, int3
   if (d->s2s.beam.ensure(2 * BK * hypBytes, st, false) || d->s2s.beamN.ensure(8 * (size_t)B, st, false) ||
       d->s2s.hist.ensure((size_t)(d->s2s.maxOut + 1) * BK * recBytes, st, false) ||
       d->s2s.rowsInt.ensure(4 * (size_t)B, st, false) || d->s2s.done.ensure(4 * (size_t)B, st, false) ||
-      d->s2s.finalStep.ensure(4 * (size_t)B, st, false) ||
+      d->s2s.finalStep.ensure(12 * (size_t)B, st, false) || /* (finalStep, origin, parked: s2sOrigin) */
       d->s2s.recTok.ensure(4 * BK * d->s2s.cap, st, false) || d->s2s.recAm.ensure(4 * BK * d->s2s.cap, st, false) ||
       d->s2s.recN.ensure(4 * BK, st, false) || d->s2s.cKey.ensure(8 * (size_t)B * (size_t)nC, st, false) ||
       (d->lm->kind == 3 && d->s2s.recLm.ensure(4 * BK * d->s2s.cap, st, false)) ||
@@ -5947,6 +5966,9 @@ int fltx_s2s_begin(fltx_decoder* d, int32_t B, int32_t V, int32_t* nextTok, int3
   d->N = V;
   d->s2s.t = 0;
   d->s2s.begun = true;
+  d->s2s.hOrigin.assign((size_t)B, 0);
+  d->s2s.hParked.assign((size_t)B, 0);
+  d->s2s.liveUntil = d->s2s.maxOut;
   d->haveResults = false;
   d->ended = false;
   d->backtraced = false;
@@ -6024,11 +6046,12 @@ static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_
   if (!d->s2s.begun) {
     return fail(FLTX_ERR_STATE, "%s: fltx_s2s_begin first", what);
   }
-  if (lmIn && ((!lmIn->scores && d->s2s.t < d->s2s.maxOut) || lmIn->rowStride < d->s2s.lmWidth)) {
+  const bool last = d->s2s.t >= d->s2s.liveUntil; /* no slot can be live: the kernels only list no rows */
+  if (lmIn && ((!lmIn->scores && !last) || lmIn->rowStride < d->s2s.lmWidth)) {
     return fail(FLTX_ERR_INVALID, "%s: bad argument (lm_row_stride %lld, lm_width = %d)", what,
                 (long long)lmIn->rowStride, d->s2s.lmWidth);
   }
-  if (!nextTok || !nextBeam || !nextSrc || !nRows || (!scores && d->s2s.t < d->s2s.maxOut) || rowStride < d->N) {
+  if (!nextTok || !nextBeam || !nextSrc || !nRows || (!scores && !last) || rowStride < d->N) {
     return fail(FLTX_ERR_INVALID, "%s: bad argument (row_stride %lld, V = %d)", what, (long long)rowStride, d->N);
   }
   const bool typed = dtype != FLTX_DTYPE_F32 || logits;
@@ -6038,7 +6061,6 @@ static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_
   Stream st = d->ctx->stream;
   const size_t BK = (size_t)d->B * d->s2s.opt.beam_size;
   const size_t elem = dtype == FLTX_DTYPE_F32 ? 4 : 2;
-  const bool last = d->s2s.t >= d->s2s.maxOut; /* nothing to score: the kernels only list no rows */
   const size_t nLmRows = wordRows && lmIn->lmRowOf ? (size_t)std::max(lmIn->nLmRows, 0) : BK;
   if (wordRows && (!lmIn->nextWord || (lmIn->lmRowOf && lmIn->nLmRows < 1 && !last))) {
     return fail(FLTX_ERR_INVALID, "%s: bad argument (next_word is required; n_lm_rows %d with lm_row_of)", what,
@@ -6308,7 +6330,7 @@ int fltx_s2s_done(fltx_decoder* d, int32_t* done) {
   if (!d->s2s.begun) {
     return fail(FLTX_ERR_STATE, "fltx_s2s_done: fltx_s2s_begin first");
   }
-  if (d->s2s.t >= d->s2s.maxOut) {
+  if (d->s2s.t >= d->s2s.liveUntil) { /* every slot has had its max_output_length steps, or is parked */
     *done = 1;
     return FLTX_OK;
   }
@@ -7777,6 +7799,157 @@ int fltx_ctc_rows_stream_finish(fltx_decoder* d, const int32_t* which, const voi
   out->tokens = (const int32_t*)d->s2s.hFinTok.p;
   out->words = lex ? (const int32_t*)d->s2s.hFinWrd.p : nullptr;
   out->row_off = d->histOff.data();
+  return FLTX_OK;
+}
+
+/* ---- seq2seq: finish and restart single utterances of a running batch (fltx_s2s.h: s2sFinishSlot) ---------------------- */
+int fltx_s2s_done_each(fltx_decoder* d, int32_t* done) {
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = s2sCheck(d, "fltx_s2s_done_each");
+  if (rc) {
+    return rc;
+  }
+  if (!done) {
+    return fail(FLTX_ERR_INVALID, "fltx_s2s_done_each: null argument");
+  }
+  if (!d->s2s.begun) {
+    return fail(FLTX_ERR_STATE, "fltx_s2s_done_each: fltx_s2s_begin first");
+  }
+  if (devCopyD2H(done, d->s2s.done.p, 4 * (size_t)d->B, d->ctx->stream) || devSync(d->ctx->stream)) {
+    return fail(FLTX_ERR_HIP, "fltx_s2s_done_each: copy failed: %s", devErr());
+  }
+  for (int b = 0; b < d->B; ++b) {
+    done[b] = done[b] != 0 ? 1 : 0;
+  }
+  return FLTX_OK;
+}
+
+int fltx_s2s_finish(fltx_decoder* d, const int32_t* which, int32_t* nextTok, int32_t* nextBeam, int32_t* nextSrc,
+                    int32_t* nRows, int32_t* nextWord, int32_t resultsOnDevice, fltx_s2s_finished_out* out) {
+  const char* what = "fltx_s2s_finish";
+  DeviceScope devScope(d ? d->ctx : nullptr);
+  if (devScope.failed) {
+    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  }
+  int rc = s2sCheck(d, what);
+  if (rc) {
+    return rc;
+  }
+  if (!d->s2s.begun || d->ended) {
+    return fail(FLTX_ERR_STATE, "%s: between fltx_s2s_begin and fltx_s2s_end", what);
+  }
+  if (!which || !nextTok || !nextBeam || !nextSrc || !nRows || !out) {
+    return fail(FLTX_ERR_INVALID, "%s: null which, list or out", what);
+  }
+  const bool wordRows = d->lm->kind == 4;
+  if (wordRows && !nextWord) {
+    return fail(FLTX_ERR_INVALID, "%s: a decoder with a word-level rows LM lists next_word", what);
+  }
+  const int B = d->B, K = d->s2s.opt.beam_size, len = d->s2s.maxOut + 3;
+  for (int b = 0; b < B; ++b) {
+    if (which[b] < 0 || which[b] > 2) {
+      return fail(FLTX_ERR_INVALID, "%s: which[%d] = %d (0 leave, 1 finish + restart, 2 finish + park)", what, b, which[b]);
+    }
+  }
+  Stream st = d->ctx->stream;
+  const bool lex = d->kind == FLTX_DECODER_S2S_LEXICON;
+  const size_t nRec = (size_t)B * K * len;
+  if (d->s2s.finScores.ensure(24 * (size_t)B * K, st, false) || d->s2s.finTok.ensure(4 * nRec, st, false) ||
+      (lex && d->s2s.finWrd.ensure(4 * nRec, st, false)) || d->s2s.finMeta.ensure(20 * (size_t)B, st, false) ||
+      d->s2s.finIn.ensure(4 * (size_t)B, st, false) ||
+      (!resultsOnDevice && (d->s2s.hFinScores.ensure(24 * (size_t)B * K) || d->s2s.hFinTok.ensure(4 * nRec) ||
+                            (lex && d->s2s.hFinWrd.ensure(4 * nRec)) || d->s2s.hFinMeta.ensure(12 * (size_t)B)))) {
+    return fail(FLTX_ERR_OOM, "%s: allocation failed (B=%d K=%d)", what, B, K);
+  }
+  int32_t* stage = (int32_t*)d->s2s.finStage.acquire(4 * (size_t)B);
+  if (!stage) {
+    return fail(FLTX_ERR_OOM, "%s: staging allocation failed", what);
+  }
+  memcpy(stage, which, 4 * (size_t)B);
+  if (devCopyH2D(d->s2s.finIn.p, stage, 4 * (size_t)B, st) || d->s2s.finStage.sent(st)) {
+    return fail(FLTX_ERR_HIP, "%s: upload failed", what);
+  }
+  int32_t* meta = d->s2s.finMeta.as<int32_t>(); /* n_hyp, steps, status, then the back-trace's beam and frame counts */
+  S2lFinishKernelParams Z;
+  memset(&Z, 0, sizeof(Z));
+  Z.q = s2sStepParams(d);
+  Z.q.words = lex ? d->s2s.finWrd.as<int32_t>() : nullptr;
+  S2sParams& P = Z.q.s;
+  P.outTok = nextTok;
+  P.outBeam = nextBeam;
+  P.outSrc = nextSrc;
+  P.outN = nRows;
+  P.outScores = d->s2s.finScores.as<double>();
+  P.tokens = d->s2s.finTok.as<int32_t>();
+  P.outNHyp = meta;
+  P.uttStatus = meta + 2 * (size_t)B;
+  P.uttNBeam = meta + 3 * (size_t)B;
+  P.uttFrame = meta + 4 * (size_t)B;
+  Z.f.which = d->s2s.finIn.as<int32_t>();
+  Z.f.steps = meta + B;
+  Z.f.errUnsupported = FLTX_ERR_UNSUPPORTED;
+  Z.outWord = wordRows ? nextWord : nullptr;
+  Z.rowNode = wordRows ? d->s2s.rowNode.as<int32_t>() : nullptr;
+  if (lex) {
+    S2S_LAUNCH(fltx_s2s_lex_finish_kernel, s2lFinishUtterance, B, kS2sEndThreads, sizeof(S2sFinishLds), st, Z);
+  } else {
+    const S2sFinishKernelParams Y = {P, Z.f};
+    S2S_LAUNCH(fltx_s2s_finish_kernel, s2sFinishUtterance, B, kS2sEndThreads, sizeof(S2sFinishLds), st, Y);
+  }
+  /* what the host knows of the slots from here on */
+  for (int b = 0; b < B; ++b) {
+    if (which[b] == 1) {
+      d->s2s.hOrigin[(size_t)b] = d->s2s.t;
+      d->s2s.hParked[(size_t)b] = 0;
+    } else if (which[b] == 2) {
+      d->s2s.hParked[(size_t)b] = 1;
+    }
+  }
+  d->s2s.liveUntil = 0;
+  for (int b = 0; b < B; ++b) {
+    if (!d->s2s.hParked[(size_t)b]) {
+      d->s2s.liveUntil = std::max(d->s2s.liveUntil, d->s2s.hOrigin[(size_t)b] + d->s2s.maxOut);
+    }
+  }
+  memset(out, 0, sizeof(*out));
+  out->length = len;
+  if (resultsOnDevice) {
+    out->n_hyp = meta;
+    out->steps = meta + B;
+    out->status = meta + 2 * (size_t)B;
+    out->scores = d->s2s.finScores.as<double>();
+    out->tokens = d->s2s.finTok.as<int32_t>();
+    out->words = lex ? d->s2s.finWrd.as<int32_t>() : nullptr;
+    return FLTX_OK;
+  }
+  /* home: the counts first, then what the named slots really have -- n_hyp * length entries each */
+  int32_t* hMeta = (int32_t*)d->s2s.hFinMeta.p;
+  if (devCopyD2H(hMeta, meta, 12 * (size_t)B, st)) {
+    return fail(FLTX_ERR_HIP, "%s: result copy failed: %s", what, devErr());
+  }
+  int bad = 0;
+  for (int b = 0; b < B && !bad; ++b) {
+    const size_t n = (size_t)hMeta[b], at = (size_t)b * K * len, cnt = n * (size_t)len;
+    if (n == 0) {
+      continue;
+    }
+    const size_t sAt = 3 * (size_t)b * K;
+    bad = crsCopyHomeAsync((double*)d->s2s.hFinScores.p + sAt, d->s2s.finScores.as<double>() + sAt, 24 * n, st) ||
+          crsCopyHomeAsync((int32_t*)d->s2s.hFinTok.p + at, d->s2s.finTok.as<int32_t>() + at, 4 * cnt, st) ||
+          (lex && crsCopyHomeAsync((int32_t*)d->s2s.hFinWrd.p + at, d->s2s.finWrd.as<int32_t>() + at, 4 * cnt, st));
+  }
+  if (bad || devSync(st)) {
+    return fail(FLTX_ERR_HIP, "%s: result copy failed: %s", what, devErr());
+  }
+  out->n_hyp = hMeta;
+  out->steps = hMeta + B;
+  out->status = hMeta + 2 * (size_t)B;
+  out->scores = (const double*)d->s2s.hFinScores.p;
+  out->tokens = (const int32_t*)d->s2s.hFinTok.p;
+  out->words = lex ? (const int32_t*)d->s2s.hFinWrd.p : nullptr;
   return FLTX_OK;
 }
 

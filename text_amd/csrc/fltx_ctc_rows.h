@@ -611,7 +611,7 @@ FLTX_DEV void crStepUtterance(const CrParams& Q, char* smem, const CrsParams* X 
       Q.merges[b] += nMerged;
     }
     const bool in = tid < nSel;
-    s2sPublishStepWith(P, S, b, nSel, in, in && c.isNew ? c.token : -1, in ? nh.parent : -1,
+    s2sPublishStepWith(P, S, b, P.t, nSel, in, in && c.isNew ? c.token : -1, in ? nh.parent : -1,
                        in ? (int)rb + nh.parent : -1, CrRowState{Q.outState, nh.sid});
     if constexpr (STREAM) {
       crsStepDone(Q, *X, b, nd, nSel, nh);

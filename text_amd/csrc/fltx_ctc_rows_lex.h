@@ -536,7 +536,7 @@ FLTX_DEV void crlStepUtterance(const CrlParams& R, char* smem, const CrsParams* 
       Q.merges[b] += nMerged;
     }
     const bool in = tid < nSel;
-    s2sPublishStepWith(P, S, b, nSel, in, in && c.isNew ? c.edge : -1, in ? nh.parent : -1,
+    s2sPublishStepWith(P, S, b, P.t, nSel, in, in && c.isNew ? c.edge : -1, in ? nh.parent : -1,
                        in ? (int)rb + nh.parent : -1, CrlRowState{Q.outState, R.rowNode, nh.sid, nh.node});
     if constexpr (STREAM) {
       crsStepDone(Q, *Z, b, nd, nSel, nh);

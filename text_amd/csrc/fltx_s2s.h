@@ -42,7 +42,7 @@ struct S2sHyp { /* one hypothesis of a beam, 56 B */
 struct S2sParams {
   DecodeParams lmp; /* the LM fields only (ngScore reads them) */
   int32_t B, K, Kt, V, eos, maxOut;
-  int32_t t;        /* steps taken before this one (beam parity t & 1 is the current beam) */
+  int32_t t;        /* steps the batch has taken before this one (beam parity t & 1 is the current beam) */
   int32_t cap;      /* entries per row record */
   int32_t mSel;     /* tokens per row the front end keeps */
   int32_t eosExtra; /* 1: mSel < min(Kt, V) (exact shortcut without LM terms): eos is added when it is in the top Kt */
@@ -56,7 +56,9 @@ struct S2sParams {
   int2* hist;              /* [maxOut + 1][B*K]: (token, parent) of the hypotheses of step s */
   int32_t* nRowsInt;       /* [B] rows of the current step */
   int32_t* done;           /* [B] */
-  int32_t* finalStep;      /* [B] the step whose beam is the final one (valid when done) */
+  int32_t* finalStep;      /* [B] the step whose beam is the final one (valid when done), counted as s2sLocalT counts;
+                            * seq2seq: [3][B], see s2sOrigin (no field of its own: the CTC rows kernels share this
+                            * struct and keep their argument layout) */
   int32_t* recTok;         /* [B*K][cap] */
   float* recAm;
   int32_t* recN;           /* [B*K] */
@@ -70,6 +72,17 @@ struct S2sParams {
   int32_t *outNHyp, *uttNBeam, *uttFrame, *uttStatus;
   int32_t len;
 };
+
+/* seq2seq: behind finalStep[B], origin[B] -- the batch's step count when the utterance in slot b was (re)started
+ * (fltx_s2s_begin: 0, fltx_s2s_finish: t) -- and parked[B], 1 for a parked slot.
+ * The steps the utterance in slot b has taken: what the length limit, the history row, finalStep and the back-trace
+ * count in.  The beam parity stays the batch's (t & 1): a restart writes its root into the current half */
+FLTX_DEV int32_t* s2sOrigin(const S2sParams& P) { return P.finalStep + P.B; }
+FLTX_DEV int s2sLocalT(const S2sParams& P, int b) { return P.t - s2sOrigin(P)[b]; }
+/* The length limit needs no test of its own where `done` is read: the step that takes an utterance to max_output_length
+ * sets done[b] (s2sPublishStepWith), and so does a (re)start with max_output_length 0 -- a slot that is not done has
+ * local steps left.  So the front ends and the steps' entry test read done[b] alone, and the origin is loaded where the
+ * step first needs it: the history row. */
 
 /* ---- LM ------------------------------------------------------------------------------------------------------- */
 /* LM::score (KenLM.cpp:63-75: child state per token) over the LM's user ids, and LM::finish, of the n-gram tables;
@@ -196,7 +209,7 @@ FLTX_DEV void s2sTokBeamRows(const S2sParams& P, char* smem) {
     return;
   }
   const int b = (int)(r / P.K), k = (int)(r % P.K);
-  const bool live = !P.done[b] && P.t < P.maxOut && k < P.nRowsInt[b] && (P.rowValid == nullptr || P.rowValid[r] != 0);
+  const bool live = !P.done[b] && k < P.nRowsInt[b] && (P.rowValid == nullptr || P.rowValid[r] != 0);
   if (!live) {
     if (laneId() == 0) {
       P.recN[r] = 0;
@@ -474,7 +487,7 @@ FLTX_DEV void s2sTypedRows(const S2sTypedParams& Q, char* smem) {
   const S2sParams& P = Q.s;
   const int64_t r = (int64_t)blockIdx.x;
   const int b = (int)(r / P.K), k = (int)(r % P.K);
-  const bool live = !P.done[b] && P.t < P.maxOut && k < P.nRowsInt[b] && (P.rowValid == nullptr || P.rowValid[r] != 0);
+  const bool live = !P.done[b] && k < P.nRowsInt[b] && (P.rowValid == nullptr || P.rowValid[r] != 0);
   if (!live) {
     if (threadIdx.x == 0) {
       P.recN[r] = 0;
@@ -678,15 +691,16 @@ struct S2sNoRowExtra { /* nothing more per listed row */
 };
 
 /* ... `extra` says what else a row of the next call's list gets: put(r) for the listed row r of this thread's
- * hypothesis, none(r) for a padding row (the lexicon step with word-level LM rows: next_word and the row's trie node) */
+ * hypothesis, none(r) for a padding row (the lexicon step with word-level LM rows: next_word and the row's trie node).
+ * lt: the steps the utterance had taken before this one (s2sLocalT; the CTC rows steps: the frame, P.t) */
 template <typename Extra>
-FLTX_DEV void s2sPublishStepWith(const S2sParams& P, S2sStepLds& S, int b, int nSel, bool isLive, int token, int parent,
-                                 int srcRow, const Extra& extra) {
+FLTX_DEV void s2sPublishStepWith(const S2sParams& P, S2sStepLds& S, int b, int lt, int nSel, bool isLive, int token,
+                                 int parent, int srcRow, const Extra& extra) {
   const int tid = (int)threadIdx.x, K = P.K, par = P.t & 1;
   const int64_t rb = (int64_t)b * K;
   int nLive;
   const int q = s2sBlockRank(S, isLive, &nLive);
-  const bool fin = nSel == 0 || nLive == 0 || P.t + 1 >= P.maxOut;
+  const bool fin = nSel == 0 || nLive == 0 || lt + 1 >= P.maxOut;
   if (fin) {
     nLive = 0;
   }
@@ -710,14 +724,14 @@ FLTX_DEV void s2sPublishStepWith(const S2sParams& P, S2sStepLds& S, int b, int n
     }
     if (fin) {
       P.done[b] = 1;
-      P.finalStep[b] = nSel > 0 ? P.t + 1 : P.t; /* the last non-empty beam (:152-158; lexicon: :204-207) */
+      P.finalStep[b] = nSel > 0 ? lt + 1 : lt; /* the last non-empty beam (:152-158; lexicon: :204-207) */
     }
   }
 }
 
-FLTX_DEV void s2sPublishStep(const S2sParams& P, S2sStepLds& S, int b, int nSel, bool isLive, int token, int parent,
-                             int srcRow) {
-  s2sPublishStepWith(P, S, b, nSel, isLive, token, parent, srcRow, S2sNoRowExtra{});
+FLTX_DEV void s2sPublishStep(const S2sParams& P, S2sStepLds& S, int b, int lt, int nSel, bool isLive, int token,
+                             int parent, int srcRow) {
+  s2sPublishStepWith(P, S, b, lt, nSel, isLive, token, parent, srcRow, S2sNoRowExtra{});
 }
 
 /* decodeStep's start (:30-32): the root's fields that every hypothesis type has ... */
@@ -741,6 +755,8 @@ FLTX_DEV void s2sBeginReset(const S2sParams& P, int b) {
   P.nRowsInt[b] = live;
   P.done[b] = live ? 0 : 1;
   P.finalStep[b] = 0;
+  s2sOrigin(P)[b] = 0;
+  s2sOrigin(P)[P.B + b] = 0;
   for (int k = 0; k < P.K; ++k) {
     P.outTok[rb + k] = -1;
     P.outBeam[rb + k] = -1;
@@ -759,8 +775,9 @@ FLTX_DEV void s2sBackTrace(const S2sParams& P, const Hyp* beams, const Rec* hist
   const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
   const int K = P.K;
   const int64_t rb = (int64_t)b * K;
-  const int fs = P.done[b] ? P.finalStep[b] : P.t;
-  const int par = fs & 1;
+  const int origin = s2sOrigin(P)[b];
+  const int fs = P.done[b] ? P.finalStep[b] : P.t - origin;
+  const int par = (origin + fs) & 1; /* (the half the final beam was written under) */
   const int n = P.beamN[par * P.B + b];
   const Hyp* beam = beams + (size_t)par * P.B * K + rb;
   const int len = P.len;
@@ -799,7 +816,7 @@ FLTX_DEV void s2sStepUtteranceOn(const S2sParams& P, char* smem, const float* re
   const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
   const int K = P.K;
   const int64_t rb = (int64_t)b * K;
-  if (P.done[b] || P.t >= P.maxOut) { /* a step after the last one: nothing to score */
+  if (P.done[b]) { /* a step after the last one, a parked slot: nothing to score */
     s2sIdleStep(P, b);
     return;
   }
@@ -854,6 +871,7 @@ FLTX_DEV void s2sStepUtteranceOn(const S2sParams& P, char* smem, const float* re
   /* 4. the K best survivors, sorted best first */
   const int nSel = s2sSelectTopK(S, cKey, n, K, s2sBlockSum(S.wcnt, surv));
   /* 5. the new beam, its history records and the next call's rows */
+  const int lt = s2sLocalT(P, b); /* (loaded here, where the step first needs it: not kept across the search) */
   S2sHyp nh;
   bool isLive = false;
   int srcRow = -1, token = -1, parent = -1;
@@ -886,11 +904,11 @@ FLTX_DEV void s2sStepUtteranceOn(const S2sParams& P, char* smem, const float* re
       nh.parent = i;
     }
     next[tid] = nh;
-    P.hist[(size_t)(P.t + 1) * P.B * K + rb + tid] = make_int2(nh.token, nh.parent);
+    P.hist[(size_t)(lt + 1) * P.B * K + rb + tid] = make_int2(nh.token, nh.parent);
     token = nh.token;
     parent = nh.parent;
   }
-  s2sPublishStep(P, S, b, nSel, isLive, token, parent, srcRow);
+  s2sPublishStep(P, S, b, lt, nSel, isLive, token, parent, srcRow);
 }
 
 FLTX_DEV void s2sStepUtterance(const S2sParams& P, char* smem) { s2sStepUtteranceOn<false>(P, smem, nullptr); }
@@ -918,6 +936,148 @@ struct S2sPath { /* a path's records: the tokens row */
 
 FLTX_DEV void s2sEndUtterance(const S2sParams& P, char*) {
   s2sBackTrace(P, P.beam, P.hist, S2sPath{P.tokens}, 0);
+}
+
+/* ---- fltx_s2s_finish: end the utterances of named slots, restart or park those slots -------------------------------------
+ * One workgroup of kS2sEndThreads per slot, by which[b]:
+ *   0  the slot is left alone: nothing of it is written.  Its rows are listed again from its current beam -- the live
+ *      hypotheses in beam order, which is the order the last step listed them in (s2sMapRows / s2sPublishStepWith), with
+ *      their token and parent; next_src_row is the row itself, so the model's index_select is the identity for it;
+ *   1  s2sBackTrace for this utterance alone into the finish's own result buffers (P.outScores / tokens / outNHyp /
+ *      uttStatus are those), then the slot is what the begin kernel leaves: the root in the CURRENT half of the beam,
+ *      origin[b] = t (local step 0), done cleared, one row listed;
+ *   2  the same back-trace, then the slot is parked: done, no rows, an empty beam (fltx_s2s_end: n_hyp 0).
+ * A parked slot has no utterance: named, it reports n_hyp 0, steps 0, status 0; 1 restarts it, 2 leaves it parked.
+ * The back-trace's reads of the beam and the root's store are ordered by the workgroup's barrier.
+ * `kind` is the decoder's: root(h) the root hypothesis; restart(b) / park(b) the rest of the utterance's state (the
+ * lexicon kind's state table and counters), called by every thread; listed(r, h) / padding(r) what else a listed row
+ * gets (next_word). */
+struct S2sFinishParams {
+  const int32_t* which; /* [B] */
+  int32_t* steps;       /* [B] local steps the finished utterance took */
+  int32_t errUnsupported; /* the FLTX_ERR_* of a stopped utterance's status */
+};
+
+struct S2sFinishLds {
+  int32_t wcnt[kS2sEndThreads / 64];
+};
+
+static_assert(kS2sMaxBeam <= kS2sEndThreads, "s2sFinishSlot: a thread per hypothesis of the beam");
+
+template <typename Hyp, typename Rec, typename Path, typename Kind>
+FLTX_DEV void s2sFinishSlot(const S2sParams& P, const S2sFinishParams& F, S2sFinishLds& S, Hyp* beams, const Rec* hist,
+                            const Path& path, int status, const Kind& kind) {
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+  const int K = P.K, par = P.t & 1;
+  const int64_t rb = (int64_t)b * K;
+  const int w = F.which[b];
+  const bool parked = s2sOrigin(P)[P.B + b] != 0;
+  Hyp* cur = beams + (size_t)par * P.B * K + rb;
+  if (w == 0) {
+    const int nRows = P.done[b] ? 0 : P.nRowsInt[b];
+    const int nCur = nRows > 0 ? P.beamN[par * P.B + b] : 0;
+    const Hyp h = cur[tid < nCur ? tid : 0];
+    const bool isLive = tid < nCur && h.token != P.eos;
+    const unsigned long long bl = waveBallot(isLive);
+    if (laneId() == 0) {
+      S.wcnt[waveId()] = popc64(bl);
+    }
+    __syncthreads();
+    int q = wavePrefixCount(bl);
+    for (int v = 0; v < waveId(); ++v) {
+      q += S.wcnt[v];
+    }
+    if (isLive && q < nRows) {
+      P.outTok[rb + q] = h.token;
+      P.outBeam[rb + q] = h.parent;
+      P.outSrc[rb + q] = (int32_t)(rb + q);
+      kind.listed(rb + q, h);
+    }
+    for (int k = nRows + tid; k < K; k += kS2sEndThreads) {
+      P.outTok[rb + k] = -1;
+      P.outBeam[rb + k] = -1;
+      P.outSrc[rb + k] = -1;
+      kind.padding(rb + k);
+    }
+    if (tid == 0) {
+      P.outN[b] = nRows;
+      P.outNHyp[b] = 0;
+      F.steps[b] = 0;
+      P.uttStatus[b] = 0;
+    }
+    return;
+  }
+  if (!parked) {
+    const int fs = P.done[b] ? P.finalStep[b] : s2sLocalT(P, b);
+    s2sBackTrace(P, beams, hist, path, status);
+    if (tid == 0) {
+      F.steps[b] = fs;
+    }
+  } else if (tid == 0) {
+    P.outNHyp[b] = 0;
+    F.steps[b] = 0;
+    P.uttStatus[b] = 0;
+  }
+  for (int k = tid; k < K; k += kS2sEndThreads) {
+    P.outTok[rb + k] = -1;
+    P.outBeam[rb + k] = -1;
+    P.outSrc[rb + k] = -1;
+    kind.padding(rb + k);
+  }
+  if (w == 2 && parked) {
+    if (tid == 0) {
+      P.outN[b] = 0;
+    }
+    return;
+  }
+  __syncthreads();
+  if (w == 1) {
+    const int live = P.maxOut > 0 ? 1 : 0;
+    if (tid == 0) {
+      Hyp root;
+      kind.root(P, root);
+      cur[0] = root;
+      P.beamN[par * P.B + b] = 1;
+      P.nRowsInt[b] = live;
+      P.done[b] = live ? 0 : 1;
+      P.finalStep[b] = 0;
+      s2sOrigin(P)[b] = P.t;
+      s2sOrigin(P)[P.B + b] = 0;
+      P.outN[b] = live;
+    }
+    kind.restart(b);
+  } else {
+    if (tid == 0) {
+      P.beamN[par * P.B + b] = 0;
+      P.nRowsInt[b] = 0;
+      P.done[b] = 1;
+      P.finalStep[b] = 0;
+      s2sOrigin(P)[b] = P.t;
+      s2sOrigin(P)[P.B + b] = 1;
+      P.outN[b] = 0;
+    }
+    kind.park(b);
+  }
+}
+
+struct S2sFinishKind { /* the lexicon-free decoder: the beam is all there is */
+  __device__ __forceinline__ void root(const S2sParams& P, S2sHyp& h) const {
+    s2sRootHyp(P, h);
+    h.pad = 0;
+  }
+  __device__ __forceinline__ void restart(int) const {}
+  __device__ __forceinline__ void park(int) const {}
+  __device__ __forceinline__ void listed(int64_t, const S2sHyp&) const {}
+  __device__ __forceinline__ void padding(int64_t) const {}
+};
+
+struct S2sFinishKernelParams {
+  S2sParams s;
+  S2sFinishParams f;
+};
+
+FLTX_DEV void s2sFinishUtterance(const S2sFinishKernelParams& Z, char* smem) {
+  s2sFinishSlot(Z.s, Z.f, *(S2sFinishLds*)smem, Z.s.beam, Z.s.hist, S2sPath{Z.s.tokens}, 0, S2sFinishKind{});
 }
 
 /* ---- a rows LM (fltx_lm_rows_create): the LM's answers arrive as rows next to the model's ------------------------------
@@ -956,7 +1116,7 @@ struct S2sLmRowsLds {
 
 FLTX_DEV bool s2sRowLive(const S2sParams& P, int64_t r) {
   const int b = (int)(r / P.K), k = (int)(r % P.K);
-  return !P.done[b] && P.t < P.maxOut && k < P.nRowsInt[b] && (P.rowValid == nullptr || P.rowValid[r] != 0);
+  return !P.done[b] && k < P.nRowsInt[b] && (P.rowValid == nullptr || P.rowValid[r] != 0);
 }
 
 /* the LM scores of row r's record: entry e by thread `tid` of `nThreads` */

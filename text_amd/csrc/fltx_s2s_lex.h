@@ -326,7 +326,7 @@ FLTX_DEV void s2lStepUtteranceOn(const S2lParams& Q, char* smem, const float* re
   const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
   const int K = P.K;
   const int64_t rb = (int64_t)b * K;
-  if (P.done[b] || P.t >= P.maxOut) { /* a step after the last one: nothing to score */
+  if (P.done[b]) { /* a step after the last one, a parked slot: nothing to score */
     s2sIdleStep(P, b);
     if constexpr (SRC == kS2lLmWordRows) {
       s2lNoWords(P, b, outWord);
@@ -521,10 +521,11 @@ FLTX_DEV void s2lStepUtteranceOn(const S2lParams& Q, char* smem, const float* re
       Q.status[b] |= ST_TABLE_FULL;
       P.nRowsInt[b] = 0;
       P.done[b] = 1;
-      P.finalStep[b] = P.t;
+      P.finalStep[b] = s2sLocalT(P, b);
     }
     return;
   }
+  const int lt = s2sLocalT(P, b); /* (loaded here, where the step first needs it: not kept across the search) */
   if (tid < nSel) {
     if (hasNew) {
       nh.sid = (int32_t)loadCoherent32((const uint32_t*)&sVal[sslot]);
@@ -536,7 +537,7 @@ FLTX_DEV void s2lStepUtteranceOn(const S2lParams& Q, char* smem, const float* re
       rec.word = nh.word;
       rec.parent = nh.parent;
       rec.pad = 0;
-      Q.hist[(size_t)(P.t + 1) * P.B * K + rb + tid] = rec;
+      Q.hist[(size_t)(lt + 1) * P.B * K + rb + tid] = rec;
     }
     token = nh.token;
     parent = nh.parent;
@@ -546,9 +547,10 @@ FLTX_DEV void s2lStepUtteranceOn(const S2lParams& Q, char* smem, const float* re
     Q.merges[b] += nMerged;
   }
   if constexpr (SRC == kS2lLmWordRows) {
-    s2sPublishStepWith(P, S, b, nSel, isLive, token, parent, srcRow, S2lRowExtra{outWord, rowNode, nh.word, nh.node});
+    s2sPublishStepWith(P, S, b, lt, nSel, isLive, token, parent, srcRow,
+                       S2lRowExtra{outWord, rowNode, nh.word, nh.node});
   } else {
-    s2sPublishStep(P, S, b, nSel, isLive, token, parent, srcRow);
+    s2sPublishStep(P, S, b, lt, nSel, isLive, token, parent, srcRow);
   }
 }
 
@@ -718,6 +720,73 @@ struct S2lPath { /* a path's records: the tokens row and the words row */
 /* getAllFinalHypothesis (:209-211, Utils.h:230-266): tokens and words of the final beam's paths */
 FLTX_DEV void s2lEndUtterance(const S2lParams& Q, char*) {
   s2sBackTrace(Q.s, Q.beam, Q.hist, S2lPath{Q.s.tokens, Q.words}, Q.status[blockIdx.x]);
+}
+
+/* fltx_s2s_finish (s2sFinishSlot) on the lexicon kind: a restarted slot also gets back what s2lBeginUtterance and
+ * fltx_s2s_begin's memsets leave -- the utterance's state table empty (cleared only when a state was ever inserted:
+ * every insert counts in sCount), the count started over, status and merges cleared, and with a word rows LM the trie
+ * node of the listed root row at the root.  Word rows: a row listed again keeps its rowNode, next_word is its
+ * hypothesis' word, as the last step listed it */
+struct S2lFinishKind {
+  S2lParams q;
+  int32_t *outWord, *rowNode; /* null unless a word rows LM */
+  bool dirty;                 /* the slot's state table holds entries */
+  __device__ __forceinline__ void root(const S2sParams& P, S2lHyp& h) const {
+    s2sRootHyp(P, h);
+    h.word = -1;
+    h.node = 0;
+    h.sid = 0;
+    h.psid = -1;
+    h.edge = -1;
+  }
+  __device__ __forceinline__ void restart(int b) const {
+    const int tid = (int)threadIdx.x;
+    if (dirty) {
+      uint4* tab = (uint4*)(q.sKey + (size_t)b * q.sSize); /* (sSize: a power of two >= 2, 8 bytes an entry) */
+      for (int i = tid; i < q.sSize / 2; i += kS2sEndThreads) {
+        tab[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
+      }
+    }
+    if (tid == 0) {
+      q.sCount[b] = 1;
+      q.status[b] = 0;
+      q.merges[b] = 0;
+      if (rowNode) {
+        rowNode[(int64_t)b * q.s.K] = 0;
+      }
+    }
+  }
+  __device__ __forceinline__ void park(int b) const {
+    if (threadIdx.x == 0) {
+      q.status[b] = 0;
+      q.merges[b] = 0;
+    }
+  }
+  __device__ __forceinline__ void listed(int64_t r, const S2lHyp& h) const {
+    if (outWord) {
+      outWord[r] = h.word;
+    }
+  }
+  __device__ __forceinline__ void padding(int64_t r) const {
+    if (outWord) {
+      outWord[r] = -1;
+    }
+  }
+};
+
+struct S2lFinishKernelParams {
+  S2lParams q;
+  S2sFinishParams f;
+  int32_t *outWord, *rowNode;
+};
+
+FLTX_DEV void s2lFinishUtterance(const S2lFinishKernelParams& Z, char* smem) {
+  const S2lParams& Q = Z.q;
+  const int b = (int)blockIdx.x;
+  const int st = Q.status[b]; /* (read, like sCount, before the barrier behind which a restart clears them) */
+  const int status = (st & (ST_CAND_OVERFLOW | ST_TABLE_FULL | ST_SELECT_FALLBACK)) ? Z.f.errUnsupported : 0;
+  s2sFinishSlot(Q.s, Z.f, *(S2sFinishLds*)smem, Q.beam, Q.hist, S2lPath{Q.s.tokens, Q.words}, status,
+                S2lFinishKind{Q, Z.outWord, Z.rowNode, Q.sCount[b] != 1});
 }
 
 } // namespace fltx
