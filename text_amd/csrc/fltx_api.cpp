@@ -16,6 +16,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <thread>
+#include <type_traits>
 #include <limits>
 #include <functional>
 #include <map>
@@ -1002,6 +1003,22 @@ static bool kindHasWords(int kind) {
   return kind == FLTX_DECODER_LEXICON || kind == FLTX_DECODER_S2S_LEXICON || kind == FLTX_DECODER_LEX_CTC_ROWS;
 }
 
+/* how an entry point opens: the device of its context (or of its decoder's) selected for the call -- DeviceScope puts
+ * the caller's back on every return path -- and then, for the entry points of the step decoders, the check that comes
+ * first (s2sCheck, crCheck, crsCheck) under the call's name.  rc != 0 is what the call returns */
+struct EntryScope {
+  DeviceScope dev;
+  int rc;
+  explicit EntryScope(const fltx_ctx* ctx)
+      : dev(ctx), rc(dev.failed ? fail(FLTX_ERR_HIP, "hipSetDevice failed") : (int)FLTX_OK) {}
+  explicit EntryScope(fltx_decoder* d, const char* what = nullptr, int (*check)(fltx_decoder*, const char*) = nullptr)
+      : EntryScope(d ? d->ctx : nullptr) {
+    if (!rc && check) {
+      rc = check(d, what);
+    }
+  }
+};
+
 /* ------------------------------------------------------------------------ */
 extern "C" {
 
@@ -1565,9 +1582,9 @@ int fltx_trie_create(fltx_ctx* ctx, int64_t nNodes, int32_t nTokens, const int32
   if (nNodes >= (1ll << 31)) {
     return fail(FLTX_ERR_UNSUPPORTED, "trie too large");
   }
-  DeviceScope devScope(ctx);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(ctx);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (nNodes >= (1ll << 28) || (int64_t)labelOff[nNodes] >= (1ll << 28)) {
     return fail(FLTX_ERR_UNSUPPORTED, "trie too large for the packed edge records");
@@ -1973,9 +1990,9 @@ int fltx_decoder_create(fltx_ctx* ctx, int32_t kind, const fltx_options* opt, co
   if (trie && trie->ctx != ctx) {
     return fail(FLTX_ERR_INVALID, "fltx_decoder_create: the trie was uploaded to another context (device)");
   }
-  DeviceScope devScope(ctx);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(ctx);
+  if (entry.rc) {
+    return entry.rc;
   }
   fltx_lm::Dev* lmDev = nullptr;
   {
@@ -2013,9 +2030,9 @@ int fltx_decoder_create(fltx_ctx* ctx, int32_t kind, const fltx_options* opt, co
 }
 
 int fltx_decoder_destroy(fltx_decoder* d) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (d) {
     devSync(d->ctx->stream);
@@ -4345,9 +4362,9 @@ extern "C" {
 
 int fltx_decode_batch(fltx_decoder* d, const float* emissions, int32_t onDevice, const int64_t* offsets,
                       const int32_t* T, int32_t B, int32_t N) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (d && stepKindCalls(d->kind)) {
     return fail(FLTX_ERR_STATE, "fltx_decode_batch: %s", stepKindCalls(d->kind));
@@ -4601,9 +4618,9 @@ static int offlineAttempts(fltx_decoder* d, const float* emissions, int32_t onDe
 extern "C" {
 
 int fltx_stream_begin(fltx_decoder* d, int32_t B, int32_t N, int32_t maxFrames) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (d && stepKindCalls(d->kind)) {
     return fail(FLTX_ERR_STATE, "fltx_stream_begin: %s", stepKindCalls(d->kind));
@@ -4694,9 +4711,9 @@ int fltx_stream_begin(fltx_decoder* d, int32_t B, int32_t N, int32_t maxFrames) 
 
 int fltx_stream_step(fltx_decoder* d, const float* emissions, int32_t onDevice, const int64_t* offsets,
                      const int32_t* T) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (d && stepKindCalls(d->kind)) {
     return fail(FLTX_ERR_STATE, "fltx_stream_step: %s", stepKindCalls(d->kind));
@@ -4798,9 +4815,9 @@ int fltx_stream_step(fltx_decoder* d, const float* emissions, int32_t onDevice, 
 }
 
 int fltx_stream_end(fltx_decoder* d) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (d && stepKindCalls(d->kind)) {
     return fail(FLTX_ERR_STATE, "fltx_stream_end: %s", stepKindCalls(d->kind));
@@ -4840,9 +4857,9 @@ int fltx_stream_end(fltx_decoder* d) {
 }
 
 int fltx_stream_prune(fltx_decoder* d, int32_t lookBack) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (d && stepKindCalls(d->kind)) {
     return fail(FLTX_ERR_STATE, "fltx_stream_prune: %s", stepKindCalls(d->kind));
@@ -4888,9 +4905,9 @@ int fltx_stream_prune(fltx_decoder* d, int32_t lookBack) {
 static int checkStatus(fltx_decoder* d, int b);
 
 int fltx_stream_frames_in_buffer(fltx_decoder* d, int32_t b, int32_t* n) {
-  DeviceScope devScope(d ? d->ctx : nullptr); /* (syncResults may run the deferred second pass of a chunk) */
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d); /* (syncResults may run the deferred second pass of a chunk) */
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d || !n || b < 0 || b >= d->B) {
     return fail(FLTX_ERR_INVALID, "bad argument");
@@ -4921,9 +4938,9 @@ static int checkStatus(fltx_decoder* d, int b) {
 }
 
 int fltx_result_count(fltx_decoder* d, int32_t b, int32_t* nHyp, int32_t* length) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d || b < 0 || b >= d->B) {
     return fail(FLTX_ERR_INVALID, "fltx_result_count: bad argument");
@@ -5012,9 +5029,9 @@ int fltx_result_fetch(fltx_decoder* d, int32_t b, int32_t maxHyp, double* scores
 
 int fltx_result_fetch_batch(fltx_decoder* d, const int32_t** nHyp, const int32_t** length, const double** scores,
                             const int32_t** tokens, const int32_t** words, const int64_t** offsets) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d) {
     return fail(FLTX_ERR_INVALID, "fltx_result_fetch_batch: null decoder");
@@ -5083,9 +5100,9 @@ static void trElapsed(TrBufs& T, int from, int to, int slot);
 int fltx_result_fetch_batch_compact(fltx_decoder* d, const int32_t** nHyp, const int32_t** length,
                                     const double** scores, const uint8_t** tokensU8, const int32_t** words,
                                     const int64_t** offsets) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d) {
     return fail(FLTX_ERR_INVALID, "fltx_result_fetch_batch_compact: null decoder");
@@ -5204,9 +5221,9 @@ static int crsResultBest(fltx_decoder* d, int32_t b, int32_t lookBack, double* s
 
 int fltx_result_best(fltx_decoder* d, int32_t b, int32_t lookBack, double* scores, int32_t* tokens,
                      int32_t* words, int32_t capacity, int32_t* length) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d || b < 0 || b >= d->B || lookBack < 0 || !length) {
     return fail(FLTX_ERR_INVALID, "fltx_result_best: bad argument");
@@ -5288,9 +5305,9 @@ int fltx_result_best(fltx_decoder* d, int32_t b, int32_t lookBack, double* score
 
 int fltx_result_device(fltx_decoder* d, const int32_t** nHyp, const double** scores,
                        const int32_t** tokens, const int32_t** words, const int64_t** tokOff) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d || !d->haveResults) {
     return fail(FLTX_ERR_STATE, "no decode has been run");
@@ -5329,9 +5346,9 @@ int fltx_result_device(fltx_decoder* d, const int32_t** nHyp, const double** sco
  * utterances of the batch (0 prep, 1 generate, 2 fold, 3 select, 4 build,
  * 5 row hand-over) */
 int fltx_decoder_profile(fltx_decoder* d, uint64_t* out) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d || !out) {
     return fail(FLTX_ERR_INVALID, "null argument");
@@ -5353,9 +5370,9 @@ int fltx_decoder_profile(fltx_decoder* d, uint64_t* out) {
 }
 
 int fltx_decoder_timing(fltx_decoder* d, float* decodeMs, float* backtraceMs) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d) {
     return fail(FLTX_ERR_INVALID, "null decoder");
@@ -5388,9 +5405,9 @@ int fltx_decoder_timing(fltx_decoder* d, float* decodeMs, float* backtraceMs) {
 
 int fltx_decoder_stats(fltx_decoder* d, int64_t* frames, int64_t* bytes, int32_t* threads,
                        int32_t* ldsBytes) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d) {
     return fail(FLTX_ERR_INVALID, "null decoder");
@@ -5417,9 +5434,9 @@ int fltx_decoder_stats(fltx_decoder* d, int64_t* frames, int64_t* bytes, int32_t
 }
 
 int fltx_decoder_bytes(fltx_decoder* d, int64_t* decodeBytes, int64_t* epilogueBytes, int64_t* lmBytes) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d) {
     return fail(FLTX_ERR_INVALID, "null decoder");
@@ -5467,6 +5484,200 @@ static int s2sCheck(fltx_decoder* d, const char* what) {
     HIPCHK(hipGetLastError());                                               \
   } while (0)
 #endif
+
+/* ---- what the step decoders' host code decides once (seq2seq, the CTC rows kinds, their streams and finishes) ---------- */
+/* a fltx_dtype and a kind of the ABI, and the bytes of an element */
+static bool s2sDtypeOk(int32_t dtype) {
+  return dtype == FLTX_DTYPE_F32 || dtype == FLTX_DTYPE_F16 || dtype == FLTX_DTYPE_BF16;
+}
+static bool s2sKindOk(int32_t kind) { return kind == FLTX_S2S_LOG_PROBS || kind == FLTX_S2S_LOGITS; }
+static size_t s2sDtypeBytes(int32_t dtype) { return dtype == FLTX_DTYPE_F32 ? 4 : 2; }
+
+extern "C++" { /* (templates, inside this file's extern "C" block) */
+/* the one map from a checked (dtype, logits) to the <DT, LOGITS> of a kernel: f(dt, lg) gets the pair as compile-time
+ * constants -- S2S_DT_LOGITS names them inside a generic lambda, in both builds */
+template <class F>
+static int s2sTypedDispatch(int32_t dtype, bool logits, F&& f) {
+  using F32 = std::integral_constant<int, kS2sDtF32>;
+  using F16 = std::integral_constant<int, kS2sDtF16>;
+  using Bf16 = std::integral_constant<int, kS2sDtBf16>;
+  switch (dtype * 2 + (logits ? 1 : 0)) {
+    case 0: return f(F32(), std::false_type());
+    case 1: return f(F32(), std::true_type());
+    case 2: return f(F16(), std::false_type());
+    case 3: return f(F16(), std::true_type());
+    case 4: return f(Bf16(), std::false_type());
+    default: return f(Bf16(), std::true_type());
+  }
+}
+}
+#define S2S_DT_LOGITS(dt, lg)              \
+  constexpr int DT = decltype(dt)::value; \
+  constexpr bool LOGITS = decltype(lg)::value
+/* the gather of a rows LM's scores into recLm by `kernel` / `body`, templates on the LM rows' <DT, LOGITS>: log-probs
+ * take a wave per row, four rows per workgroup; logits a workgroup per row */
+#define S2S_LM_ROWS_LAUNCH(kernel, body, dtype, logits, nRows, st, params)                                      \
+  s2sTypedDispatch((dtype), (logits), [&](auto dt, auto lg) -> int {                                             \
+    S2S_DT_LOGITS(dt, lg);                                                                                       \
+    S2S_LAUNCH((kernel<DT, LOGITS>), (body<DT, LOGITS>), LOGITS ? (nRows) : ((nRows) + 3) / 4, kS2sLmThreads,    \
+               sizeof(S2sLmRowsLds), (st), (params));                                                            \
+    return FLTX_OK;                                                                                              \
+  })
+
+/* the rows of a rows LM of either level as the gather kernels take them (R.s is the caller's) */
+static void s2sLmRowsFill(S2sLmRowsParams& R, fltx_decoder* d, const void* x, int64_t rowStride, bool logits,
+                          double* rowLse) {
+  R.x = x;
+  R.rowStride = rowStride;
+  R.width = d->s2s.lmWidth;
+  R.finishIdx = d->s2s.lmFinish;
+  R.usrToLm = d->lm->rowsMap ? d->lmDev->usrToLm.as<int32_t>() : nullptr;
+  R.recLm = d->s2s.recLm.as<float>();
+  R.rowLse = logits ? rowLse : nullptr;
+}
+
+/* a call's LM rows on the device: the host's nLm rows are copied into the decoder's staging buffer in their own type --
+ * the last row ends after the LM's width, not after a stride -- and so are the B*K entries of lm_row_of when it is
+ * given; the pointers then name the copies.  `who` starts the message of a failure */
+static int s2sStageLmRows(fltx_decoder* d, const char* who, int32_t dtype, int64_t rowStride, size_t nLm, size_t BK,
+                          const void** lmScores, const int32_t** lmRowOf, Stream st) {
+  const size_t bytes = s2sDtypeBytes(dtype) * ((nLm - 1) * (size_t)rowStride + (size_t)d->s2s.lmWidth);
+  if (d->s2s.lmScores.ensure(bytes, st, false) || (*lmRowOf && d->s2s.lmRowOf.ensure(4 * BK, st, false))) {
+    return fail(FLTX_ERR_OOM, "%s: staging allocation failed", who);
+  }
+  if (devCopyH2D(d->s2s.lmScores.p, *lmScores, bytes, st) ||
+      (*lmRowOf && devCopyH2D(d->s2s.lmRowOf.p, *lmRowOf, 4 * BK, st))) {
+    return fail(FLTX_ERR_HIP, "%s: upload failed", who);
+  }
+  *lmScores = d->s2s.lmScores.p;
+  *lmRowOf = *lmRowOf ? d->s2s.lmRowOf.as<int32_t>() : nullptr;
+  return FLTX_OK;
+}
+
+/* a call with nothing to score still answers a logits caller: every row's lse a NaN (all-ones) */
+static int s2sIdleLse(const char* what, bool logits, double* rowLse, size_t BK, Stream st) {
+  if (logits && rowLse && devMemset(rowLse, 0xFF, 8 * BK, st)) {
+    return fail(FLTX_ERR_HIP, "%s: memset failed", what);
+  }
+  return FLTX_OK;
+}
+
+/* where a back-trace leaves its results: the decoder's own buffers (an end) or the fin* ones (a finish) */
+struct StepResults {
+  double* scores;
+  int32_t *tokens, *nHyp, *nBeam, *frame, *status;
+};
+static void s2sSetResults(S2sParams& P, const StepResults& r) {
+  P.outScores = r.scores;
+  P.tokens = r.tokens;
+  P.outNHyp = r.nHyp;
+  P.uttNBeam = r.nBeam;
+  P.uttFrame = r.frame;
+  P.uttStatus = r.status;
+}
+
+/* the results of an end (fltx_s2s_end, fltx_ctc_rows_end) as every decoder's results are read: the buffers -- words
+ * where the kind has words -- histOff on the device, and P's result pointers.  `who` starts the message of a failure */
+static int stepEndResults(fltx_decoder* d, const char* who, S2sParams& P) {
+  Stream st = d->ctx->stream;
+  const size_t B = (size_t)d->B, nRec = (size_t)std::max<int64_t>(d->histRecords, 1);
+  if (d->outScores.ensure(24 * B * d->opt.beam_size, st, false) || d->tokens.ensure(4 * nRec, st, false) ||
+      d->outN.ensure(4 * B, st, false) || ensureUttRes(d, d->B, st) || d->histOffD.ensure(8 * (B + 1), st, false) ||
+      (kindHasWords(d->kind) && d->words.ensure(4 * nRec, st, false))) {
+    return fail(FLTX_ERR_OOM, "%s results: device allocation failed", who);
+  }
+  if (uploadHistOff(d, st)) {
+    return fail(FLTX_ERR_HIP, "%s results: upload failed", who);
+  }
+  s2sSetResults(P, {d->outScores.as<double>(), d->tokens.as<int32_t>(), d->outN.as<int32_t>(),
+                    d->uttNBeam.as<int32_t>(), d->uttFrame.as<int32_t>(), d->uttStatus.as<int32_t>()});
+  return FLTX_OK;
+}
+/* ... and what the decoder knows once the end's kernels are queued */
+static void stepEnded(fltx_decoder* d) {
+  d->haveResults = true;
+  d->ended = true;
+  d->backtraced = true;
+  d->streaming = false;
+  d->resultsSynced = false;
+  d->hostFetched = false;
+  d->compactFetched = false;
+  d->scoresFetched = false;
+  d->offlinePending = false;
+  d->lookQueued = false;
+}
+
+/* a copy home that waits for nothing: the caller synchronises once behind the last one */
+static int crsCopyHomeAsync(void* h, const void* dv, size_t n, Stream st) {
+#ifdef FLTX_EMU
+  (void)st;
+  memcpy(h, dv, n);
+  return 0;
+#else
+  return hipMemcpyAsync(h, dv, n, hipMemcpyDeviceToHost, st) == hipSuccess ? 0 : 1;
+#endif
+}
+
+/* the buffers of a finish (fltx_ctc_rows_stream_finish and fltx_s2s_finish share them by design): scores [B*K*3], nRec
+ * tokens and words, the counts in finMeta, the call's input in finIn and, for the streams, finSkip; their pinned twins
+ * unless the results stay */
+static int stepFinishBuffers(fltx_decoder* d, const char* what, size_t nRec, size_t metaBytes, size_t inBytes,
+                             size_t skipBytes, int32_t resultsOnDevice) {
+  Stream st = d->ctx->stream;
+  const size_t B = (size_t)d->B, K = (size_t)d->opt.beam_size;
+  const bool lex = kindHasWords(d->kind);
+  if (d->s2s.finScores.ensure(24 * B * K, st, false) || d->s2s.finTok.ensure(4 * nRec, st, false) ||
+      (lex && d->s2s.finWrd.ensure(4 * nRec, st, false)) || d->s2s.finMeta.ensure(metaBytes, st, false) ||
+      d->s2s.finIn.ensure(inBytes, st, false) || (skipBytes && d->s2s.finSkip.ensure(skipBytes, st, false)) ||
+      (!resultsOnDevice && (d->s2s.hFinScores.ensure(24 * B * K) || d->s2s.hFinTok.ensure(4 * nRec) ||
+                            (lex && d->s2s.hFinWrd.ensure(4 * nRec)) || d->s2s.hFinMeta.ensure(12 * B)))) {
+    return fail(FLTX_ERR_OOM, "%s: allocation failed (B=%d K=%d)", what, d->B, d->opt.beam_size);
+  }
+  return FLTX_OK;
+}
+
+extern "C++" {
+/* the results of a finish: *out points at the device's, or at the host's after copying them home -- the counts
+ * {n_hyp, counts, status}[B] of finMeta first, then what the named slots really have, n_hyp hypotheses each, and one
+ * wait.  Slot b's rows start at rowOff[b] (null: b * K * len) and a hypothesis has len entries (0: the slot's own
+ * count).  `counts` is the member of OUT the second count goes by; what else OUT has is the caller's */
+template <class OUT>
+static int stepFinishResults(fltx_decoder* d, const char* what, int32_t resultsOnDevice, const int64_t* rowOff,
+                             int32_t len, const int32_t* OUT::*counts, OUT* out) {
+  Stream st = d->ctx->stream;
+  const size_t B = (size_t)d->B, K = (size_t)d->opt.beam_size;
+  const bool lex = kindHasWords(d->kind);
+  const int32_t* meta = d->s2s.finMeta.as<int32_t>();
+  if (!resultsOnDevice) {
+    int32_t* hMeta = (int32_t*)d->s2s.hFinMeta.p;
+    if (devCopyD2H(hMeta, meta, 12 * B, st)) {
+      return fail(FLTX_ERR_HIP, "%s: result copy failed: %s", what, devErr());
+    }
+    int bad = 0;
+    for (size_t b = 0; b < B && !bad; ++b) {
+      const size_t n = (size_t)hMeta[b], at = rowOff ? (size_t)rowOff[b] : b * K * (size_t)len;
+      const size_t cnt = n * (size_t)(len ? len : hMeta[B + b]), sAt = 3 * b * K;
+      if (n == 0) {
+        continue;
+      }
+      bad = crsCopyHomeAsync((double*)d->s2s.hFinScores.p + sAt, d->s2s.finScores.as<double>() + sAt, 24 * n, st) ||
+            crsCopyHomeAsync((int32_t*)d->s2s.hFinTok.p + at, d->s2s.finTok.as<int32_t>() + at, 4 * cnt, st) ||
+            (lex && crsCopyHomeAsync((int32_t*)d->s2s.hFinWrd.p + at, d->s2s.finWrd.as<int32_t>() + at, 4 * cnt, st));
+    }
+    if (bad || devSync(st)) {
+      return fail(FLTX_ERR_HIP, "%s: result copy failed: %s", what, devErr());
+    }
+    meta = hMeta;
+  }
+  out->n_hyp = meta;
+  out->*counts = meta + B;
+  out->status = meta + 2 * B;
+  out->scores = resultsOnDevice ? d->s2s.finScores.as<double>() : (const double*)d->s2s.hFinScores.p;
+  out->tokens = resultsOnDevice ? d->s2s.finTok.as<int32_t>() : (const int32_t*)d->s2s.hFinTok.p;
+  out->words = !lex ? nullptr : resultsOnDevice ? d->s2s.finWrd.as<int32_t>() : (const int32_t*)d->s2s.hFinWrd.p;
+  return FLTX_OK;
+}
+}
 
 static S2sParams s2sParams(fltx_decoder* d) {
   S2sParams P;
@@ -5547,9 +5758,9 @@ static int s2sDecoderCreate(fltx_ctx* ctx, const fltx_s2s_options* opt, const fl
   if (lm->kind == 1 && lm->order - 1 > kS2sCtx) {
     return fail(FLTX_ERR_UNSUPPORTED, "seq2seq: n-gram order %d > %d", lm->order, kS2sCtx + 1);
   }
-  DeviceScope devScope(ctx);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(ctx);
+  if (entry.rc) {
+    return entry.rc;
   }
   fltx_lm::Dev* lmDev = nullptr;
   int rc = lmEnsureUploaded(const_cast<fltx_lm*>(lm), ctx, &lmDev);
@@ -5741,10 +5952,10 @@ int fltx_s2s_lex_decoder_create(fltx_ctx* ctx, const fltx_s2s_lex_options* opt, 
   if (rc) {
     return rc;
   }
-  DeviceScope devScope(ctx);
-  if (devScope.failed) {
+  EntryScope entry(ctx);
+  if (entry.rc) {
     delete d;
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+    return entry.rc;
   }
   d->kind = FLTX_DECODER_S2S_LEXICON;
   d->opt.word_score = opt->word_score;
@@ -5802,9 +6013,9 @@ int fltx_s2s_lex_info(fltx_decoder* d, int64_t* trieBytes, int64_t* nNodes, int6
   if (d->kind != FLTX_DECODER_S2S_LEXICON) {
     return fail(FLTX_ERR_STATE, "fltx_s2s_lex_info: not a lexicon seq2seq decoder");
   }
-  DeviceScope devScope(d->ctx);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d->ctx);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (trieBytes) {
     *trieBytes = d->s2s.trieBytes;
@@ -5922,13 +6133,9 @@ static int s2sAllocLexicon(fltx_decoder* d, int32_t B, int32_t V, int64_t nC) {
 
 int fltx_s2s_begin(fltx_decoder* d, int32_t B, int32_t V, int32_t* nextTok, int32_t* nextBeam, int32_t* nextSrc,
                    int32_t* nRows) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = s2sCheck(d, "fltx_s2s_begin");
-  if (rc) {
-    return rc;
+  EntryScope entry(d, "fltx_s2s_begin", s2sCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (B < 1 || V < 1 || !nextTok || !nextBeam || !nextSrc || !nRows) {
     return fail(FLTX_ERR_INVALID, "fltx_s2s_begin: bad argument");
@@ -5938,7 +6145,8 @@ int fltx_s2s_begin(fltx_decoder* d, int32_t B, int32_t V, int32_t* nextTok, int3
   }
   const bool lex = d->kind == FLTX_DECODER_S2S_LEXICON;
   int64_t nC = 0;
-  if ((rc = lex ? s2sPlanLexicon(d, V, &nC) : s2sPlanLexFree(d, V, &nC))) {
+  int rc = lex ? s2sPlanLexicon(d, V, &nC) : s2sPlanLexFree(d, V, &nC);
+  if (rc) {
     return rc;
   }
   Stream st = d->ctx->stream;
@@ -5991,28 +6199,6 @@ int fltx_s2s_begin(fltx_decoder* d, int32_t B, int32_t V, int32_t* nextTok, int3
   return FLTX_OK;
 }
 
-extern "C++" { /* (templates, inside this file's extern "C" block) */
-template <int DT, bool LOGITS>
-static int s2sTypedLaunch(int nRows, Stream st, const S2sTypedParams& T) {
-  S2S_LAUNCH((fltx_s2s_typed_kernel<DT, LOGITS>), (s2sTypedRows<DT, LOGITS>), nRows, kS2sTypedThreads,
-             sizeof(S2sTypedLds), st, T);
-  return FLTX_OK;
-}
-/* log-probs: a wave per row, four rows per workgroup; logits: a workgroup per row */
-template <int DT, bool LOGITS>
-static int s2sLmRowsLaunch(int nRows, Stream st, const S2sLmRowsParams& Q) {
-  S2S_LAUNCH((fltx_s2s_lm_rows_kernel<DT, LOGITS>), (s2sLmRows<DT, LOGITS>), LOGITS ? nRows : (nRows + 3) / 4,
-             kS2sLmThreads, sizeof(S2sLmRowsLds), st, Q);
-  return FLTX_OK;
-}
-template <int DT, bool LOGITS>
-static int s2lWordLmRowsLaunch(int nRows, Stream st, const S2lWordLmParams& W) {
-  S2S_LAUNCH((fltx_s2s_lex_word_lm_rows_kernel<DT, LOGITS>), (s2lWordLmRows<DT, LOGITS>),
-             LOGITS ? nRows : (nRows + 3) / 4, kS2sLmThreads, sizeof(S2sLmRowsLds), st, W);
-  return FLTX_OK;
-}
-}
-
 /* the LM's rows of fltx_s2s_step_lm_rows */
 struct S2sLmIn {
   const void* scores;
@@ -6060,7 +6246,7 @@ static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_
   }
   Stream st = d->ctx->stream;
   const size_t BK = (size_t)d->B * d->s2s.opt.beam_size;
-  const size_t elem = dtype == FLTX_DTYPE_F32 ? 4 : 2;
+  const size_t elem = s2sDtypeBytes(dtype);
   const size_t nLmRows = wordRows && lmIn->lmRowOf ? (size_t)std::max(lmIn->nLmRows, 0) : BK;
   if (wordRows && (!lmIn->nextWord || (lmIn->lmRowOf && lmIn->nLmRows < 1 && !last))) {
     return fail(FLTX_ERR_INVALID, "%s: bad argument (next_word is required; n_lm_rows %d with lm_row_of)", what,
@@ -6079,32 +6265,15 @@ static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_
     rowValid = rowValid ? d->s2s.valid.as<uint8_t>() : nullptr;
   }
   const void* lmScores = lmIn ? lmIn->scores : nullptr;
-  if (lmIn && !onDevice && !last) { /* the LM's rows, staged in their own type */
-    const size_t lmElem = lmIn->dtype == FLTX_DTYPE_F32 ? 4 : 2;
-    const size_t nE = (nLmRows - 1) * (size_t)lmIn->rowStride + (size_t)d->s2s.lmWidth;
-    if (d->s2s.lmScores.ensure(lmElem * nE, st, false)) {
-      return fail(FLTX_ERR_OOM, "seq2seq: staging allocation failed");
-    }
-    if (devCopyH2D(d->s2s.lmScores.p, lmScores, lmElem * nE, st)) {
-      return fail(FLTX_ERR_HIP, "seq2seq: upload failed");
-    }
-    lmScores = d->s2s.lmScores.p;
-  }
   const int32_t* lmRowOf = wordRows ? lmIn->lmRowOf : nullptr;
-  if (lmRowOf && !onDevice && !last) {
-    if (d->s2s.lmRowOf.ensure(4 * BK, st, false)) {
-      return fail(FLTX_ERR_OOM, "seq2seq: staging allocation failed");
-    }
-    if (devCopyH2D(d->s2s.lmRowOf.p, lmRowOf, 4 * BK, st)) {
-      return fail(FLTX_ERR_HIP, "seq2seq: upload failed");
-    }
-    lmRowOf = d->s2s.lmRowOf.as<int32_t>();
+  int rc;
+  if (lmIn && !onDevice && !last &&
+      (rc = s2sStageLmRows(d, "seq2seq", lmIn->dtype, lmIn->rowStride, nLmRows, BK, &lmScores, &lmRowOf, st))) {
+    return rc;
   }
-  if (last && logits && rowLse && devMemset(rowLse, 0xFF, 8 * BK, st)) { /* (all-ones: a NaN) */
-    return fail(FLTX_ERR_HIP, "%s: memset failed", what);
-  }
-  if (last && lmIn && lmIn->logits && lmIn->rowLse && devMemset(lmIn->rowLse, 0xFF, 8 * BK, st)) {
-    return fail(FLTX_ERR_HIP, "%s: memset failed", what);
+  if (last && ((rc = s2sIdleLse(what, logits, rowLse, BK, st)) ||
+               (lmIn && (rc = s2sIdleLse(what, lmIn->logits, lmIn->rowLse, BK, st))))) {
+    return rc;
   }
   S2lParams Q = s2sStepParams(d);
   S2sParams& P = Q.s;
@@ -6122,14 +6291,14 @@ static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_
     T.s = P;
     T.x = scores;
     T.rowLse = logits ? rowLse : nullptr;
-    int rc;
-    switch (dtype * 2 + (logits ? 1 : 0)) {
-      case 1: rc = s2sTypedLaunch<kS2sDtF32, true>((int)BK, st, T); break;
-      case 2: rc = s2sTypedLaunch<kS2sDtF16, false>((int)BK, st, T); break;
-      case 3: rc = s2sTypedLaunch<kS2sDtF16, true>((int)BK, st, T); break;
-      case 4: rc = s2sTypedLaunch<kS2sDtBf16, false>((int)BK, st, T); break;
-      default: rc = s2sTypedLaunch<kS2sDtBf16, true>((int)BK, st, T); break;
-    }
+    rc = s2sTypedDispatch(dtype, logits, [&](auto dt, auto lg) -> int {
+      S2S_DT_LOGITS(dt, lg);
+      if constexpr (DT != kS2sDtF32 || LOGITS) { /* (float32 log-probs are the untyped front end's: no such kernel) */
+        S2S_LAUNCH((fltx_s2s_typed_kernel<DT, LOGITS>), (s2sTypedRows<DT, LOGITS>), (int)BK, kS2sTypedThreads,
+                   sizeof(S2sTypedLds), st, T);
+      }
+      return FLTX_OK;
+    });
     if (rc) {
       return rc;
     }
@@ -6138,31 +6307,15 @@ static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_
     S2lWordLmParams W;
     memset(&W, 0, sizeof(W));
     W.r.s = P;
-    W.r.x = lmScores;
-    W.r.rowStride = lmIn->rowStride;
-    W.r.width = d->s2s.lmWidth;
-    W.r.finishIdx = d->s2s.lmFinish;
-    W.r.usrToLm = d->lm->rowsMap ? d->lmDev->usrToLm.as<int32_t>() : nullptr;
-    W.r.recLm = d->s2s.recLm.as<float>();
-    W.r.rowLse = lmIn->logits ? lmIn->rowLse : nullptr;
+    s2sLmRowsFill(W.r, d, lmScores, lmIn->rowStride, lmIn->logits, lmIn->rowLse);
     W.trie = Q.trie;
     W.rowNode = d->s2s.rowNode.as<int32_t>();
     W.lmRowOf = lmRowOf;
     W.nLmRows = (int32_t)nLmRows;
     W.S = Q.S;
-    if (!last) {
-      int rc;
-      switch (lmIn->dtype * 2 + (lmIn->logits ? 1 : 0)) {
-        case 0: rc = s2lWordLmRowsLaunch<kS2sDtF32, false>((int)BK, st, W); break;
-        case 1: rc = s2lWordLmRowsLaunch<kS2sDtF32, true>((int)BK, st, W); break;
-        case 2: rc = s2lWordLmRowsLaunch<kS2sDtF16, false>((int)BK, st, W); break;
-        case 3: rc = s2lWordLmRowsLaunch<kS2sDtF16, true>((int)BK, st, W); break;
-        case 4: rc = s2lWordLmRowsLaunch<kS2sDtBf16, false>((int)BK, st, W); break;
-        default: rc = s2lWordLmRowsLaunch<kS2sDtBf16, true>((int)BK, st, W); break;
-      }
-      if (rc) {
-        return rc;
-      }
+    if (!last && (rc = S2S_LM_ROWS_LAUNCH(fltx_s2s_lex_word_lm_rows_kernel, s2lWordLmRows, lmIn->dtype, lmIn->logits,
+                                          (int)BK, st, W))) {
+      return rc;
     }
     S2lWordLmStepParams RW;
     RW.q = Q;
@@ -6176,26 +6329,10 @@ static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_
   } else if (lmIn) {
     S2sLmRowsParams R;
     R.s = P;
-    R.x = lmScores;
-    R.rowStride = lmIn->rowStride;
-    R.width = d->s2s.lmWidth;
-    R.finishIdx = d->s2s.lmFinish;
-    R.usrToLm = d->lm->rowsMap ? d->lmDev->usrToLm.as<int32_t>() : nullptr;
-    R.recLm = d->s2s.recLm.as<float>();
-    R.rowLse = lmIn->logits ? lmIn->rowLse : nullptr;
-    if (!last) {
-      int rc;
-      switch (lmIn->dtype * 2 + (lmIn->logits ? 1 : 0)) {
-        case 0: rc = s2sLmRowsLaunch<kS2sDtF32, false>((int)BK, st, R); break;
-        case 1: rc = s2sLmRowsLaunch<kS2sDtF32, true>((int)BK, st, R); break;
-        case 2: rc = s2sLmRowsLaunch<kS2sDtF16, false>((int)BK, st, R); break;
-        case 3: rc = s2sLmRowsLaunch<kS2sDtF16, true>((int)BK, st, R); break;
-        case 4: rc = s2sLmRowsLaunch<kS2sDtBf16, false>((int)BK, st, R); break;
-        default: rc = s2sLmRowsLaunch<kS2sDtBf16, true>((int)BK, st, R); break;
-      }
-      if (rc) {
-        return rc;
-      }
+    s2sLmRowsFill(R, d, lmScores, lmIn->rowStride, lmIn->logits, lmIn->rowLse);
+    if (!last &&
+        (rc = S2S_LM_ROWS_LAUNCH(fltx_s2s_lm_rows_kernel, s2sLmRows, lmIn->dtype, lmIn->logits, (int)BK, st, R))) {
+      return rc;
     }
     if (d->kind == FLTX_DECODER_S2S_LEXICON) {
       S2lLmRowsParams RL;
@@ -6217,13 +6354,9 @@ static int s2sStep(fltx_decoder* d, const char* what, const void* scores, int32_
 
 int fltx_s2s_step(fltx_decoder* d, const float* scores, int32_t onDevice, int64_t rowStride, const uint8_t* rowValid,
                   int32_t* nextTok, int32_t* nextBeam, int32_t* nextSrc, int32_t* nRows) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = s2sCheck(d, "fltx_s2s_step");
-  if (rc) {
-    return rc;
+  EntryScope entry(d, "fltx_s2s_step", s2sCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   return s2sStep(d, "fltx_s2s_step", scores, FLTX_DTYPE_F32, false, onDevice, rowStride, rowValid, nullptr, nextTok,
                  nextBeam, nextSrc, nRows);
@@ -6233,18 +6366,14 @@ int fltx_s2s_step(fltx_decoder* d, const float* scores, int32_t onDevice, int64_
 int fltx_s2s_step_typed(fltx_decoder* d, const void* scores, int32_t dtype, int32_t kind, int32_t onDevice,
                         int64_t rowStride, const uint8_t* rowValid, double* rowLse, int32_t* nextTok,
                         int32_t* nextBeam, int32_t* nextSrc, int32_t* nRows) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d, "fltx_s2s_step_typed", s2sCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
-  int rc = s2sCheck(d, "fltx_s2s_step_typed");
-  if (rc) {
-    return rc;
-  }
-  if (dtype != FLTX_DTYPE_F32 && dtype != FLTX_DTYPE_F16 && dtype != FLTX_DTYPE_BF16) {
+  if (!s2sDtypeOk(dtype)) {
     return fail(FLTX_ERR_INVALID, "fltx_s2s_step_typed: dtype %d", dtype);
   }
-  if (kind != FLTX_S2S_LOG_PROBS && kind != FLTX_S2S_LOGITS) {
+  if (!s2sKindOk(kind)) {
     return fail(FLTX_ERR_INVALID, "fltx_s2s_step_typed: kind %d", kind);
   }
   return s2sStep(d, "fltx_s2s_step_typed", scores, dtype, kind == FLTX_S2S_LOGITS, onDevice, rowStride, rowValid,
@@ -6256,23 +6385,17 @@ int fltx_s2s_step_lm_rows(fltx_decoder* d, const void* scores, int32_t dtype, in
                           const void* lmScores, int32_t lmDtype, int32_t lmKind, int64_t lmRowStride, int32_t onDevice,
                           const uint8_t* rowValid, double* rowLse, double* lmRowLse, int32_t* nextTok,
                           int32_t* nextBeam, int32_t* nextSrc, int32_t* nRows) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = s2sCheck(d, "fltx_s2s_step_lm_rows");
-  if (rc) {
-    return rc;
+  EntryScope entry(d, "fltx_s2s_step_lm_rows", s2sCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (d->lm->kind != 3) {
     return fail(FLTX_ERR_STATE, "fltx_s2s_step_lm_rows: the decoder has no rows LM (fltx_lm_rows_create)");
   }
-  if ((dtype != FLTX_DTYPE_F32 && dtype != FLTX_DTYPE_F16 && dtype != FLTX_DTYPE_BF16) ||
-      (lmDtype != FLTX_DTYPE_F32 && lmDtype != FLTX_DTYPE_F16 && lmDtype != FLTX_DTYPE_BF16)) {
+  if (!s2sDtypeOk(dtype) || !s2sDtypeOk(lmDtype)) {
     return fail(FLTX_ERR_INVALID, "fltx_s2s_step_lm_rows: dtype %d, lm_dtype %d", dtype, lmDtype);
   }
-  if ((kind != FLTX_S2S_LOG_PROBS && kind != FLTX_S2S_LOGITS) ||
-      (lmKind != FLTX_S2S_LOG_PROBS && lmKind != FLTX_S2S_LOGITS)) {
+  if (!s2sKindOk(kind) || !s2sKindOk(lmKind)) {
     return fail(FLTX_ERR_INVALID, "fltx_s2s_step_lm_rows: kind %d, lm_kind %d", kind, lmKind);
   }
   const S2sLmIn lmIn{lmScores, lmDtype, lmKind == FLTX_S2S_LOGITS, lmRowStride, lmRowLse};
@@ -6286,24 +6409,18 @@ int fltx_s2s_step_word_lm_rows(fltx_decoder* d, const void* scores, int32_t dtyp
                                const int32_t* lmRowOf, int32_t nLmRows, int32_t onDevice, const uint8_t* rowValid,
                                double* rowLse, double* lmRowLse, int32_t* nextTok, int32_t* nextBeam, int32_t* nextSrc,
                                int32_t* nextWord, int32_t* nRows) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = s2sCheck(d, "fltx_s2s_step_word_lm_rows");
-  if (rc) {
-    return rc;
+  EntryScope entry(d, "fltx_s2s_step_word_lm_rows", s2sCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (d->lm->kind != 4) {
     return fail(FLTX_ERR_STATE, "fltx_s2s_step_word_lm_rows: the decoder has no word-level rows LM "
                                 "(fltx_lm_word_rows_create)");
   }
-  if ((dtype != FLTX_DTYPE_F32 && dtype != FLTX_DTYPE_F16 && dtype != FLTX_DTYPE_BF16) ||
-      (lmDtype != FLTX_DTYPE_F32 && lmDtype != FLTX_DTYPE_F16 && lmDtype != FLTX_DTYPE_BF16)) {
+  if (!s2sDtypeOk(dtype) || !s2sDtypeOk(lmDtype)) {
     return fail(FLTX_ERR_INVALID, "fltx_s2s_step_word_lm_rows: dtype %d, lm_dtype %d", dtype, lmDtype);
   }
-  if ((kind != FLTX_S2S_LOG_PROBS && kind != FLTX_S2S_LOGITS) ||
-      (lmKind != FLTX_S2S_LOG_PROBS && lmKind != FLTX_S2S_LOGITS)) {
+  if (!s2sKindOk(kind) || !s2sKindOk(lmKind)) {
     return fail(FLTX_ERR_INVALID, "fltx_s2s_step_word_lm_rows: kind %d, lm_kind %d", kind, lmKind);
   }
   S2sLmIn lmIn{lmScores, lmDtype, lmKind == FLTX_S2S_LOGITS, lmRowStride, lmRowLse};
@@ -6316,13 +6433,9 @@ int fltx_s2s_step_word_lm_rows(fltx_decoder* d, const void* scores, int32_t dtyp
 }
 
 int fltx_s2s_done(fltx_decoder* d, int32_t* done) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = s2sCheck(d, "fltx_s2s_done");
-  if (rc) {
-    return rc;
+  EntryScope entry(d, "fltx_s2s_done", s2sCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!done) {
     return fail(FLTX_ERR_INVALID, "fltx_s2s_done: null argument");
@@ -6346,13 +6459,9 @@ int fltx_s2s_done(fltx_decoder* d, int32_t* done) {
 }
 
 int fltx_s2s_end(fltx_decoder* d) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = s2sCheck(d, "fltx_s2s_end");
-  if (rc) {
-    return rc;
+  EntryScope entry(d, "fltx_s2s_end", s2sCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d->s2s.begun) {
     return fail(FLTX_ERR_STATE, "fltx_s2s_end: fltx_s2s_begin first");
@@ -6364,42 +6473,20 @@ int fltx_s2s_end(fltx_decoder* d) {
     d->histOff[b] = (int64_t)b * K * len;
   }
   d->histRecords = (int64_t)B * K * len;
-  if (d->outScores.ensure(24 * (size_t)B * K, st, false) || d->tokens.ensure(4 * (size_t)d->histRecords, st, false) ||
-      d->outN.ensure(4 * (size_t)B, st, false) || ensureUttRes(d, B, st) ||
-      d->histOffD.ensure(8 * ((size_t)B + 1), st, false)) {
-    return fail(FLTX_ERR_OOM, "seq2seq results: device allocation failed");
-  }
-  if (uploadHistOff(d, st)) {
-    return fail(FLTX_ERR_HIP, "seq2seq results: upload failed");
+  S2lParams Q = s2sStepParams(d);
+  S2sParams& P = Q.s;
+  int rc = stepEndResults(d, "seq2seq", P);
+  if (rc) {
+    return rc;
   }
   const bool lex = d->kind == FLTX_DECODER_S2S_LEXICON;
-  if (lex && d->words.ensure(4 * (size_t)d->histRecords, st, false)) {
-    return fail(FLTX_ERR_OOM, "seq2seq results: device allocation failed");
-  }
-  S2lParams Q = s2sStepParams(d);
   Q.words = lex ? d->words.as<int32_t>() : nullptr;
-  S2sParams& P = Q.s;
-  P.outScores = d->outScores.as<double>();
-  P.tokens = d->tokens.as<int32_t>();
-  P.outNHyp = d->outN.as<int32_t>();
-  P.uttNBeam = d->uttNBeam.as<int32_t>();
-  P.uttFrame = d->uttFrame.as<int32_t>();
-  P.uttStatus = d->uttStatus.as<int32_t>();
   if (lex) {
     S2S_LAUNCH(fltx_s2s_lex_end_kernel, s2lEndUtterance, B, kS2sEndThreads, 0, st, Q);
   } else {
     S2S_LAUNCH(fltx_s2s_end_kernel, s2sEndUtterance, B, kS2sEndThreads, 0, st, P);
   }
-  d->haveResults = true;
-  d->ended = true;
-  d->backtraced = true;
-  d->streaming = false;
-  d->resultsSynced = false;
-  d->hostFetched = false;
-  d->compactFetched = false;
-  d->scoresFetched = false;
-  d->offlinePending = false;
-  d->lookQueued = false;
+  stepEnded(d);
   return FLTX_OK;
 }
 
@@ -6522,9 +6609,9 @@ int fltx_ctc_rows_lex_decoder_create(fltx_ctx* ctx, const fltx_options* opt, con
   if (opt->unk_score > -std::numeric_limits<double>::infinity() && unk < 0) { /* (the unknown word's id is listed and stored) */
     return fail(FLTX_ERR_INVALID, "lexicon CTC rows: unk_score > -inf needs an unk word id >= 0 (unk = %d)", unk);
   }
-  DeviceScope devScope(ctx);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(ctx);
+  if (entry.rc) {
+    return entry.rc;
   }
   fltx_lm::Dev* lmDev = nullptr;
   int rc = lmEnsureUploaded(const_cast<fltx_lm*>(lm), ctx, &lmDev);
@@ -6590,9 +6677,9 @@ int fltx_ctc_rows_decoder_create(fltx_ctx* ctx, const fltx_options* opt, const f
   if (opt->beam_size > kS2sMaxBeam) {
     return fail(FLTX_ERR_UNSUPPORTED, "CTC rows: beam_size %d > %d", opt->beam_size, kS2sMaxBeam);
   }
-  DeviceScope devScope(ctx);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(ctx);
+  if (entry.rc) {
+    return entry.rc;
   }
   fltx_lm::Dev* lmDev = nullptr;
   int rc = lmEnsureUploaded(const_cast<fltx_lm*>(lm), ctx, &lmDev);
@@ -6638,10 +6725,10 @@ struct CrEmIn {
 };
 
 static int crEmCheck(const char* what, const CrEmIn& in) {
-  if (in.dt != kCrEmPlain && in.dt != FLTX_DTYPE_F32 && in.dt != FLTX_DTYPE_F16 && in.dt != FLTX_DTYPE_BF16) {
+  if (in.dt != kCrEmPlain && !s2sDtypeOk(in.dt)) {
     return fail(FLTX_ERR_INVALID, "%s: dtype %d", what, in.dt);
   }
-  if (in.kind != FLTX_S2S_LOG_PROBS && in.kind != FLTX_S2S_LOGITS) {
+  if (!s2sKindOk(in.kind)) {
     return fail(FLTX_ERR_INVALID, "%s: kind %d", what, in.kind);
   }
   return FLTX_OK;
@@ -6716,14 +6803,37 @@ static int crFrontEnd(fltx_decoder* d, int64_t frames, Stream st, const CrParams
   Z.c = Q;
   Z.e = crTypedEm(d);
   Z.lseOut = frameLse;
-  switch (d->s2s.crEmDt * 2 + (d->s2s.crEmLogits ? 1 : 0)) {
-    case 0: return crTypedFrontLaunch<kS2sDtF32, false>(d, frames, st, Z);
-    case 1: return crTypedFrontLaunch<kS2sDtF32, true>(d, frames, st, Z);
-    case 2: return crTypedFrontLaunch<kS2sDtF16, false>(d, frames, st, Z);
-    case 3: return crTypedFrontLaunch<kS2sDtF16, true>(d, frames, st, Z);
-    case 4: return crTypedFrontLaunch<kS2sDtBf16, false>(d, frames, st, Z);
-    default: return crTypedFrontLaunch<kS2sDtBf16, true>(d, frames, st, Z);
+  return s2sTypedDispatch(d->s2s.crEmDt, d->s2s.crEmLogits, [&](auto dt, auto lg) -> int {
+    S2S_DT_LOGITS(dt, lg);
+    return crTypedFrontLaunch<DT, LOGITS>(d, frames, st, Z);
+  });
+}
+
+/* the meta of a begin's utterances or of an append's chunk, as the kernels read it (crParams): frameOff[B + 1], emOff[B],
+ * then T[B] as int32.  frames: the sum of T; packed: the utterances' emissions follow each other */
+struct CrChunk {
+  int64_t frames = 0;
+  int maxT = 0;
+  bool packed = true;
+};
+static int crChunkMeta(fltx_decoder* d, int B, const int32_t* T, const int64_t* offsets, int64_t stride, int32_t onDevice,
+                       CrChunk* c) {
+  std::vector<int64_t>& meta = d->s2s.crMetaHost;
+  meta.assign((size_t)2 * B + 1 + ((size_t)B + 1) / 2, 0);
+  int32_t* hT = (int32_t*)(meta.data() + 2 * (size_t)B + 1);
+  for (int b = 0; b < B; ++b) {
+    if (T[b] < 0) {
+      return fail(FLTX_ERR_INVALID, "T[%d] = %d is negative", b, T[b]);
+    }
+    meta[(size_t)b] = c->frames;
+    c->packed = c->packed && (!offsets || offsets[b] == c->frames * stride);
+    meta[(size_t)B + 1 + b] = onDevice && offsets ? offsets[b] : c->frames * stride;
+    hT[b] = T[b];
+    c->frames += T[b];
+    c->maxT = std::max(c->maxT, T[b]);
   }
+  meta[(size_t)B] = c->frames;
+  return FLTX_OK;
 }
 
 /* decodeBegin of a batch (maxFrames < 0: fltx_ctc_rows_begin, fltx_ctc_rows_begin_typed) or of B streams that hold up to
@@ -6731,12 +6841,12 @@ static int crFrontEnd(fltx_decoder* d, int64_t frames, Stream st, const CrParams
 static int crBegin(fltx_decoder* d, const char* what, const CrEmIn& in, int32_t onDevice, const int64_t* offsets,
                    const int32_t* T, int32_t B, int32_t N, int32_t maxFrames, int32_t* nextTok, int32_t* nextSrc,
                    int32_t* nextState, int32_t* nRows) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d, what, crCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
-  int rc = crCheck(d, what);
-  if (rc || (rc = crEmCheck(what, in))) {
+  int rc = crEmCheck(what, in);
+  if (rc) {
     return rc;
   }
   const void* emissions = in.x;
@@ -6776,27 +6886,19 @@ static int crBegin(fltx_decoder* d, const char* what, const CrEmIn& in, int32_t 
     return rc;
   }
   d->s2s.lmFinish = d->lm->rowsFinish;
-  std::vector<int64_t>& meta = d->s2s.crMetaHost; /* frameOff[B + 1], emOff[B], then T[B] as int32 */
-  meta.assign((size_t)2 * B + 1 + ((size_t)B + 1) / 2, 0);
-  int32_t* hT = (int32_t*)(meta.data() + 2 * (size_t)B + 1);
+  CrChunk chunk;
+  if ((rc = crChunkMeta(d, B, T, offsets, stride, onDevice, &chunk))) {
+    return rc;
+  }
+  const std::vector<int64_t>& meta = d->s2s.crMetaHost;
+  const int64_t frames = chunk.frames;
+  const int maxT = chunk.maxT;
   d->histOff.resize((size_t)B + 1);
-  int64_t frames = 0, off = 0;
-  int maxT = 0;
-  bool packed = true; /* the utterances' emissions follow each other */
+  int64_t off = 0;
   for (int b = 0; b < B; ++b) {
-    if (T[b] < 0) {
-      return fail(FLTX_ERR_INVALID, "T[%d] = %d is negative", b, T[b]);
-    }
-    meta[(size_t)b] = frames;
-    packed = packed && (!offsets || offsets[b] == frames * stride);
-    meta[(size_t)B + 1 + b] = onDevice && offsets ? offsets[b] : frames * stride;
-    hT[b] = T[b];
     d->histOff[(size_t)b] = off;
     off += (int64_t)(stream ? ring : T[b] + 2) * K; /* (a stream's results: frames in buffer + 1 <= ring entries) */
-    frames += T[b];
-    maxT = std::max(maxT, T[b]);
   }
-  meta[(size_t)B] = frames;
   d->histOff[(size_t)B] = off;
   d->histRecords = off;
   if (frames > 0 && !emissions) {
@@ -6845,7 +6947,7 @@ static int crBegin(fltx_decoder* d, const char* what, const CrEmIn& in, int32_t 
   }
   d->B = B;
   d->N = N;
-  if ((rc = crEmStage(d, what, in, stride, onDevice, packed, offsets, T, frames, st))) {
+  if ((rc = crEmStage(d, what, in, stride, onDevice, chunk.packed, offsets, T, frames, st))) {
     return rc;
   }
   d->s2s.t = 0;
@@ -6924,32 +7026,14 @@ int fltx_ctc_rows_stream_begin(fltx_decoder* d, int32_t B, int32_t N, int32_t ma
                  nextState, nRows);
 }
 
-extern "C++" {
-template <int DT, bool LOGITS>
-static int crLmRowsLaunch(int nRows, Stream st, const CrLmParams& W) {
-  S2S_LAUNCH((fltx_ctc_rows_lm_kernel<DT, LOGITS>), (crLmRows<DT, LOGITS>), LOGITS ? nRows : (nRows + 3) / 4,
-             kS2sLmThreads, sizeof(S2sLmRowsLds), st, W);
-  return FLTX_OK;
-}
-}
-
-extern "C++" {
-template <int DT, bool LOGITS>
-static int crlWordLmRowsLaunch(int nRows, Stream st, const CrlWordLmParams& W) {
-  S2S_LAUNCH((fltx_ctc_rows_lex_word_lm_kernel<DT, LOGITS>), (crlWordLmRows<DT, LOGITS>),
-             LOGITS ? nRows : (nRows + 3) / 4, kS2sLmThreads, sizeof(S2sLmRowsLds), st, W);
-  return FLTX_OK;
-}
-}
-
 /* the LM rows of a step or of the end (fin): checked, staged when they are the host's, and gathered into recLm */
 static int crLmRowsIn(fltx_decoder* d, const char* what, bool fin, bool idle, const void* lmScores, int32_t lmDtype,
                       int32_t lmKind, int64_t lmRowStride, const int32_t* lmRowOf, int32_t nLmRows, int32_t onDevice,
                       double* lmRowLse, const CrParams& Q) {
-  if (lmDtype != FLTX_DTYPE_F32 && lmDtype != FLTX_DTYPE_F16 && lmDtype != FLTX_DTYPE_BF16) {
+  if (!s2sDtypeOk(lmDtype)) {
     return fail(FLTX_ERR_INVALID, "%s: lm_dtype %d", what, lmDtype);
   }
-  if (lmKind != FLTX_S2S_LOG_PROBS && lmKind != FLTX_S2S_LOGITS) {
+  if (!s2sKindOk(lmKind)) {
     return fail(FLTX_ERR_INVALID, "%s: lm_kind %d", what, lmKind);
   }
   if ((!lmScores && !idle) || lmRowStride < d->s2s.lmWidth || (lmRowOf && nLmRows < 1 && !idle)) {
@@ -6960,35 +7044,17 @@ static int crLmRowsIn(fltx_decoder* d, const char* what, bool fin, bool idle, co
   const size_t BK = (size_t)d->B * d->opt.beam_size;
   const bool logits = lmKind == FLTX_S2S_LOGITS;
   if (idle) { /* nothing to score */
-    if (logits && lmRowLse && devMemset(lmRowLse, 0xFF, 8 * BK, st)) { /* (all-ones: a NaN) */
-      return fail(FLTX_ERR_HIP, "%s: memset failed", what);
-    }
-    return FLTX_OK;
+    return s2sIdleLse(what, logits, lmRowLse, BK, st);
   }
   const size_t nLm = lmRowOf ? (size_t)nLmRows : BK;
-  if (!onDevice) {
-    const size_t lmElem = lmDtype == FLTX_DTYPE_F32 ? 4 : 2;
-    const size_t nE = (nLm - 1) * (size_t)lmRowStride + (size_t)d->s2s.lmWidth;
-    if (d->s2s.lmScores.ensure(lmElem * nE, st, false) || (lmRowOf && d->s2s.lmRowOf.ensure(4 * BK, st, false))) {
-      return fail(FLTX_ERR_OOM, "%s: staging allocation failed", what);
-    }
-    if (devCopyH2D(d->s2s.lmScores.p, lmScores, lmElem * nE, st) ||
-        (lmRowOf && devCopyH2D(d->s2s.lmRowOf.p, lmRowOf, 4 * BK, st))) {
-      return fail(FLTX_ERR_HIP, "%s: upload failed", what);
-    }
-    lmScores = d->s2s.lmScores.p;
-    lmRowOf = lmRowOf ? d->s2s.lmRowOf.as<int32_t>() : nullptr;
+  int rc;
+  if (!onDevice && (rc = s2sStageLmRows(d, what, lmDtype, lmRowStride, nLm, BK, &lmScores, &lmRowOf, st))) {
+    return rc;
   }
   CrLmParams W;
   memset(&W, 0, sizeof(W));
   W.r.s = Q.s;
-  W.r.x = lmScores;
-  W.r.rowStride = lmRowStride;
-  W.r.width = d->s2s.lmWidth;
-  W.r.finishIdx = d->s2s.lmFinish;
-  W.r.usrToLm = d->lm->rowsMap ? d->lmDev->usrToLm.as<int32_t>() : nullptr;
-  W.r.recLm = d->s2s.recLm.as<float>();
-  W.r.rowLse = logits ? lmRowLse : nullptr;
+  s2sLmRowsFill(W.r, d, lmScores, lmRowStride, logits, lmRowLse);
   W.T = Q.T;
   W.frameOff = Q.frameOff;
   W.lmRowOf = lmRowOf;
@@ -7003,63 +7069,47 @@ static int crLmRowsIn(fltx_decoder* d, const char* what, bool fin, bool idle, co
     X.rowNode = R.rowNode;
     X.S = R.S;
     X.unk = R.unk;
-    switch (lmDtype * 2 + (logits ? 1 : 0)) {
-      case 0: return crlWordLmRowsLaunch<kS2sDtF32, false>((int)BK, st, X);
-      case 1: return crlWordLmRowsLaunch<kS2sDtF32, true>((int)BK, st, X);
-      case 2: return crlWordLmRowsLaunch<kS2sDtF16, false>((int)BK, st, X);
-      case 3: return crlWordLmRowsLaunch<kS2sDtF16, true>((int)BK, st, X);
-      case 4: return crlWordLmRowsLaunch<kS2sDtBf16, false>((int)BK, st, X);
-      default: return crlWordLmRowsLaunch<kS2sDtBf16, true>((int)BK, st, X);
-    }
+    return S2S_LM_ROWS_LAUNCH(fltx_ctc_rows_lex_word_lm_kernel, crlWordLmRows, lmDtype, logits, (int)BK, st, X);
   }
-  switch (lmDtype * 2 + (logits ? 1 : 0)) {
-    case 0: return crLmRowsLaunch<kS2sDtF32, false>((int)BK, st, W);
-    case 1: return crLmRowsLaunch<kS2sDtF32, true>((int)BK, st, W);
-    case 2: return crLmRowsLaunch<kS2sDtF16, false>((int)BK, st, W);
-    case 3: return crLmRowsLaunch<kS2sDtF16, true>((int)BK, st, W);
-    case 4: return crLmRowsLaunch<kS2sDtBf16, false>((int)BK, st, W);
-    default: return crLmRowsLaunch<kS2sDtBf16, true>((int)BK, st, W);
-  }
+  return S2S_LM_ROWS_LAUNCH(fltx_ctc_rows_lm_kernel, crLmRows, lmDtype, logits, (int)BK, st, W);
 }
+
+/* a launch of the lexicon kind that is an instantiation per LM level: `launch` names the level SRC */
+#define CRL_BY_LM_LEVEL(d, launch)          \
+  if ((d)->s2s.isLmToken) {                 \
+    constexpr int SRC = kCrlLmTokenRows;    \
+    launch;                                 \
+  } else {                                  \
+    constexpr int SRC = kCrlLmWordRows;     \
+    launch;                                 \
+  }
 
 /* the lexicon kind's frame step on typed emissions (fltx_ctc_rows_typed.h): an instantiation per (LM level, dtype, kind) */
 extern "C++" {
-template <int SRC, int DT, bool LOGITS>
-static int crlTypedStepLaunch(fltx_decoder* d, const CrParams& Q) {
-  if (d->s2s.crStream) {
-    const CrlTypedStreamParams Y = {crlParams(d, Q), crsParams(d), crTypedEm(d)};
-    S2S_LAUNCH((fltx_ctc_rows_lex_typed_stream_step_kernel<SRC, DT, LOGITS>), (crlsStepStreamTyped<SRC, DT, LOGITS>), d->B,
-               kS2sStepThreads, sizeof(CrlStepLds), d->ctx->stream, Y);
-  } else {
-    const CrlTypedParams Y = {crlParams(d, Q), crTypedEm(d)};
-    S2S_LAUNCH((fltx_ctc_rows_lex_typed_step_kernel<SRC, DT, LOGITS>), (crlStepTyped<SRC, DT, LOGITS>), d->B,
-               kS2sStepThreads, sizeof(CrlStepLds), d->ctx->stream, Y);
-  }
-  return FLTX_OK;
-}
 template <int SRC>
 static int crlTypedStep(fltx_decoder* d, const CrParams& Q) {
-  switch (d->s2s.crEmDt * 2 + (d->s2s.crEmLogits ? 1 : 0)) {
-    case 0: return crlTypedStepLaunch<SRC, kS2sDtF32, false>(d, Q);
-    case 1: return crlTypedStepLaunch<SRC, kS2sDtF32, true>(d, Q);
-    case 2: return crlTypedStepLaunch<SRC, kS2sDtF16, false>(d, Q);
-    case 3: return crlTypedStepLaunch<SRC, kS2sDtF16, true>(d, Q);
-    case 4: return crlTypedStepLaunch<SRC, kS2sDtBf16, false>(d, Q);
-    default: return crlTypedStepLaunch<SRC, kS2sDtBf16, true>(d, Q);
-  }
+  return s2sTypedDispatch(d->s2s.crEmDt, d->s2s.crEmLogits, [&](auto dt, auto lg) -> int {
+    S2S_DT_LOGITS(dt, lg);
+    if (d->s2s.crStream) {
+      const CrlTypedStreamParams Y = {crlParams(d, Q), crsParams(d), crTypedEm(d)};
+      S2S_LAUNCH((fltx_ctc_rows_lex_typed_stream_step_kernel<SRC, DT, LOGITS>), (crlsStepStreamTyped<SRC, DT, LOGITS>),
+                 d->B, kS2sStepThreads, sizeof(CrlStepLds), d->ctx->stream, Y);
+    } else {
+      const CrlTypedParams Y = {crlParams(d, Q), crTypedEm(d)};
+      S2S_LAUNCH((fltx_ctc_rows_lex_typed_step_kernel<SRC, DT, LOGITS>), (crlStepTyped<SRC, DT, LOGITS>), d->B,
+                 kS2sStepThreads, sizeof(CrlStepLds), d->ctx->stream, Y);
+    }
+    return FLTX_OK;
+  });
 }
 }
 
 int fltx_ctc_rows_step(fltx_decoder* d, const void* lmScores, int32_t lmDtype, int32_t lmKind, int64_t lmRowStride,
                        const int32_t* lmRowOf, int32_t nLmRows, int32_t onDevice, double* lmRowLse, int32_t* nextTok,
                        int32_t* nextSrc, int32_t* nextState, int32_t* nRows) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = crCheck(d, "fltx_ctc_rows_step");
-  if (rc) {
-    return rc;
+  EntryScope entry(d, "fltx_ctc_rows_step", crCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d->s2s.begun) {
     return fail(FLTX_ERR_STATE, "fltx_ctc_rows_step: fltx_ctc_rows_begin first");
@@ -7073,8 +7123,9 @@ int fltx_ctc_rows_step(fltx_decoder* d, const void* lmScores, int32_t lmDtype, i
   Q.s.outSrc = nextSrc;
   Q.s.outN = nRows;
   Q.outState = nextState;
-  if ((rc = crLmRowsIn(d, "fltx_ctc_rows_step", false, last, lmScores, lmDtype, lmKind, lmRowStride, lmRowOf, nLmRows,
-                       onDevice, lmRowLse, Q))) {
+  int rc = crLmRowsIn(d, "fltx_ctc_rows_step", false, last, lmScores, lmDtype, lmKind, lmRowStride, lmRowOf, nLmRows,
+                      onDevice, lmRowLse, Q);
+  if (rc) {
     return rc;
   }
   d->s2s.crBestLb = -1;
@@ -7085,13 +7136,8 @@ int fltx_ctc_rows_step(fltx_decoder* d, const void* lmScores, int32_t lmDtype, i
   } else if (d->s2s.crStream) { /* the same step on the streams' own counts (fltx_ctc_rows_stream.h) */
     if (d->kind == FLTX_DECODER_LEX_CTC_ROWS) {
       const CrlStreamParams Z = {crlParams(d, Q), crsParams(d)};
-      if (d->s2s.isLmToken) {
-        S2S_LAUNCH(fltx_ctc_rows_lex_stream_step_kernel<kCrlLmTokenRows>, (crlsStepStream<kCrlLmTokenRows, false>), d->B,
-                   kS2sStepThreads, sizeof(CrlStepLds), d->ctx->stream, Z);
-      } else {
-        S2S_LAUNCH(fltx_ctc_rows_lex_stream_step_kernel<kCrlLmWordRows>, (crlsStepStream<kCrlLmWordRows, false>), d->B,
-                   kS2sStepThreads, sizeof(CrlStepLds), d->ctx->stream, Z);
-      }
+      CRL_BY_LM_LEVEL(d, S2S_LAUNCH(fltx_ctc_rows_lex_stream_step_kernel<SRC>, (crlsStepStream<SRC, false>), d->B,
+                                    kS2sStepThreads, sizeof(CrlStepLds), d->ctx->stream, Z));
     } else {
       const CrStreamParams Z = {Q, crsParams(d)};
       S2S_LAUNCH(fltx_ctc_rows_stream_step_kernel, crsStepStream<false>, d->B, kS2sStepThreads, sizeof(S2lStepLds),
@@ -7099,13 +7145,8 @@ int fltx_ctc_rows_step(fltx_decoder* d, const void* lmScores, int32_t lmDtype, i
     }
   } else if (d->kind == FLTX_DECODER_LEX_CTC_ROWS) {
     const CrlParams R = crlParams(d, Q);
-    if (d->s2s.isLmToken) {
-      S2S_LAUNCH(fltx_ctc_rows_lex_step_kernel<kCrlLmTokenRows>, (crlStepUtterance<kCrlLmTokenRows, false>), d->B,
-                 kS2sStepThreads, sizeof(CrlStepLds), d->ctx->stream, R);
-    } else {
-      S2S_LAUNCH(fltx_ctc_rows_lex_step_kernel<kCrlLmWordRows>, (crlStepUtterance<kCrlLmWordRows, false>), d->B,
-                 kS2sStepThreads, sizeof(CrlStepLds), d->ctx->stream, R);
-    }
+    CRL_BY_LM_LEVEL(d, S2S_LAUNCH(fltx_ctc_rows_lex_step_kernel<SRC>, (crlStepUtterance<SRC, false>), d->B, kS2sStepThreads,
+                                  sizeof(CrlStepLds), d->ctx->stream, R));
   } else {
     S2S_LAUNCH(fltx_ctc_rows_step_kernel, crStepUtterance<false>, d->B, kS2sStepThreads, sizeof(S2lStepLds),
                d->ctx->stream, Q);
@@ -7120,52 +7161,27 @@ int fltx_ctc_rows_step(fltx_decoder* d, const void* lmScores, int32_t lmDtype, i
 
 int fltx_ctc_rows_end(fltx_decoder* d, const void* lmScores, int32_t lmDtype, int32_t lmKind, int64_t lmRowStride,
                       const int32_t* lmRowOf, int32_t nLmRows, int32_t onDevice, double* lmRowLse) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = crCheck(d, "fltx_ctc_rows_end");
-  if (rc) {
-    return rc;
+  EntryScope entry(d, "fltx_ctc_rows_end", crCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d->s2s.begun) {
     return fail(FLTX_ERR_STATE, "fltx_ctc_rows_end: fltx_ctc_rows_begin first");
   }
   Stream st = d->ctx->stream;
-  const int B = d->B, K = d->opt.beam_size;
-  if (d->outScores.ensure(24 * (size_t)B * K, st, false) ||
-      d->tokens.ensure(4 * (size_t)std::max<int64_t>(d->histRecords, 1), st, false) ||
-      d->outN.ensure(4 * (size_t)B, st, false) || ensureUttRes(d, B, st) ||
-      d->histOffD.ensure(8 * ((size_t)B + 1), st, false) ||
-      (d->kind == FLTX_DECODER_LEX_CTC_ROWS &&
-       d->words.ensure(4 * (size_t)std::max<int64_t>(d->histRecords, 1), st, false))) {
-    return fail(FLTX_ERR_OOM, "CTC rows results: device allocation failed");
-  }
-  if (uploadHistOff(d, st)) {
-    return fail(FLTX_ERR_HIP, "CTC rows results: upload failed");
-  }
+  const int B = d->B;
   CrParams Q = crParams(d);
-  if ((rc = crLmRowsIn(d, "fltx_ctc_rows_end", true, false, lmScores, lmDtype, lmKind, lmRowStride, lmRowOf, nLmRows,
-                       onDevice, lmRowLse, Q))) {
+  int rc = stepEndResults(d, "CTC rows", Q.s);
+  if (rc || (rc = crLmRowsIn(d, "fltx_ctc_rows_end", true, false, lmScores, lmDtype, lmKind, lmRowStride, lmRowOf,
+                             nLmRows, onDevice, lmRowLse, Q))) {
     return rc;
   }
   Q.histOff = d->histOffD.as<int64_t>();
-  Q.s.outScores = d->outScores.as<double>();
-  Q.s.tokens = d->tokens.as<int32_t>();
-  Q.s.outNHyp = d->outN.as<int32_t>();
-  Q.s.uttNBeam = d->uttNBeam.as<int32_t>();
-  Q.s.uttFrame = d->uttFrame.as<int32_t>();
-  Q.s.uttStatus = d->uttStatus.as<int32_t>();
   if (d->s2s.crStream) { /* (frames in buffer + 1 entries per hypothesis: what is left of the stream, and decodeEnd's sil) */
     if (d->kind == FLTX_DECODER_LEX_CTC_ROWS) {
       const CrlStreamParams Z = {crlParams(d, Q), crsParams(d)};
-      if (d->s2s.isLmToken) {
-        S2S_LAUNCH(fltx_ctc_rows_lex_stream_end_kernel<kCrlLmTokenRows>, (crlsStepStream<kCrlLmTokenRows, true>), B,
-                   kS2sStepThreads, sizeof(CrlStepLds), st, Z);
-      } else {
-        S2S_LAUNCH(fltx_ctc_rows_lex_stream_end_kernel<kCrlLmWordRows>, (crlsStepStream<kCrlLmWordRows, true>), B,
-                   kS2sStepThreads, sizeof(CrlStepLds), st, Z);
-      }
+      CRL_BY_LM_LEVEL(d, S2S_LAUNCH(fltx_ctc_rows_lex_stream_end_kernel<SRC>, (crlsStepStream<SRC, true>), B,
+                                    kS2sStepThreads, sizeof(CrlStepLds), st, Z));
     } else {
       const CrStreamParams Z = {Q, crsParams(d)};
       S2S_LAUNCH(fltx_ctc_rows_stream_end_kernel, crsStepStream<true>, B, kS2sStepThreads, sizeof(S2lStepLds), st, Z);
@@ -7175,26 +7191,12 @@ int fltx_ctc_rows_end(fltx_decoder* d, const void* lmScores, int32_t lmDtype, in
     d->s2s.crBestLb = -1;
   } else if (d->kind == FLTX_DECODER_LEX_CTC_ROWS) {
     const CrlParams R = crlParams(d, Q);
-    if (d->s2s.isLmToken) {
-      S2S_LAUNCH(fltx_ctc_rows_lex_end_kernel<kCrlLmTokenRows>, (crlStepUtterance<kCrlLmTokenRows, true>), B,
-                 kS2sStepThreads, sizeof(CrlStepLds), st, R);
-    } else {
-      S2S_LAUNCH(fltx_ctc_rows_lex_end_kernel<kCrlLmWordRows>, (crlStepUtterance<kCrlLmWordRows, true>), B,
-                 kS2sStepThreads, sizeof(CrlStepLds), st, R);
-    }
+    CRL_BY_LM_LEVEL(d, S2S_LAUNCH(fltx_ctc_rows_lex_end_kernel<SRC>, (crlStepUtterance<SRC, true>), B, kS2sStepThreads,
+                                  sizeof(CrlStepLds), st, R));
   } else {
     S2S_LAUNCH(fltx_ctc_rows_end_kernel, crStepUtterance<true>, B, kS2sStepThreads, sizeof(S2lStepLds), st, Q);
   }
-  d->haveResults = true;
-  d->ended = true;
-  d->backtraced = true;
-  d->streaming = false;
-  d->resultsSynced = false;
-  d->hostFetched = false;
-  d->compactFetched = false;
-  d->scoresFetched = false;
-  d->offlinePending = false;
-  d->lookQueued = false;
+  stepEnded(d);
   return FLTX_OK;
 }
 
@@ -7221,12 +7223,12 @@ static int crsReadCounts(fltx_decoder* d, std::vector<int32_t>& cnt) {
 
 static int crsAppend(fltx_decoder* d, const char* what, const CrEmIn& in, int32_t onDevice, const int64_t* offsets,
                      const int32_t* T) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d, what, crsCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
-  int rc = crsCheck(d, what);
-  if (rc || (rc = crEmCheck(what, in))) {
+  int rc = crEmCheck(what, in);
+  if (rc) {
     return rc;
   }
   if (!T) {
@@ -7275,21 +7277,12 @@ static int crsAppend(fltx_decoder* d, const char* what, const CrEmIn& in, int32_
                       "100, Utils.h:28,293-308)"
                     : "");
   }
-  std::vector<int64_t>& meta = d->s2s.crMetaHost; /* frameOff[B + 1], emOff[B], then T[B] as int32: the CHUNK's */
-  meta.assign((size_t)2 * B + 1 + ((size_t)B + 1) / 2, 0);
-  int32_t* hT = (int32_t*)(meta.data() + 2 * (size_t)B + 1);
-  int64_t frames = 0;
-  int maxT = 0;
-  bool packed = true;
-  for (int b = 0; b < B; ++b) {
-    meta[(size_t)b] = frames;
-    packed = packed && (!offsets || offsets[b] == frames * stride);
-    meta[(size_t)B + 1 + b] = onDevice && offsets ? offsets[b] : frames * stride;
-    hT[b] = T[b];
-    frames += T[b];
-    maxT = std::max(maxT, T[b]);
+  CrChunk chunk; /* (the meta is the CHUNK's from here on) */
+  if ((rc = crChunkMeta(d, B, T, offsets, stride, onDevice, &chunk))) {
+    return rc;
   }
-  meta[(size_t)B] = frames;
+  const std::vector<int64_t>& meta = d->s2s.crMetaHost;
+  const int64_t frames = chunk.frames;
   if (frames > 0 && !emissions) {
     return fail(FLTX_ERR_INVALID, "%s: null emissions", what);
   }
@@ -7304,11 +7297,11 @@ static int crsAppend(fltx_decoder* d, const char* what, const CrEmIn& in, int32_
   if (devCopyH2D(d->s2s.crMeta.p, meta.data(), 8 * meta.size(), st)) {
     return fail(FLTX_ERR_HIP, "CTC rows stream: upload failed");
   }
-  if ((rc = crEmStage(d, what, in, stride, onDevice, packed, offsets, T, frames, st))) { /* (a host chunk is copied here) */
+  if ((rc = crEmStage(d, what, in, stride, onDevice, chunk.packed, offsets, T, frames, st))) { /* (a host chunk is copied here) */
     return rc;
   }
   d->s2s.t = 0;
-  d->s2s.crMaxT = maxT;
+  d->s2s.crMaxT = chunk.maxT;
   d->s2s.crFrames = frames;
   d->s2s.crBestLb = -1;
   for (int b = 0; b < B; ++b) {
@@ -7359,13 +7352,9 @@ static CrsOpParams crsOpParams(fltx_decoder* d, int lookBack) {
 }
 
 int fltx_ctc_rows_stream_prune(fltx_decoder* d, int32_t lookBack) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = crsCheck(d, "fltx_ctc_rows_stream_prune");
-  if (rc) {
-    return rc;
+  EntryScope entry(d, "fltx_ctc_rows_stream_prune", crsCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (lookBack < 0) {
     return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_stream_prune: look_back = %d", lookBack);
@@ -7395,13 +7384,9 @@ int fltx_ctc_rows_stream_prune(fltx_decoder* d, int32_t lookBack) {
 
 int fltx_ctc_rows_stream_collect(fltx_decoder* d, int32_t releaseCap, int32_t* released, int32_t* nReleased,
                                  int32_t* nLive) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = crsCheck(d, "fltx_ctc_rows_stream_collect");
-  if (rc) {
-    return rc;
+  EntryScope entry(d, "fltx_ctc_rows_stream_collect", crsCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (releaseCap < 1 || !released || !nReleased) {
     return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_stream_collect: release_cap = %d (>= 1), null released or n_released",
@@ -7437,19 +7422,16 @@ int fltx_ctc_rows_stream_collect(fltx_decoder* d, int32_t releaseCap, int32_t* r
 }
 
 int fltx_ctc_rows_stream_frames_in_buffer(fltx_decoder* d, int32_t b, int32_t* n) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = crsCheck(d, "fltx_ctc_rows_stream_frames_in_buffer");
-  if (rc) {
-    return rc;
+  EntryScope entry(d, "fltx_ctc_rows_stream_frames_in_buffer", crsCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!n || b < 0 || b >= d->B) {
     return fail(FLTX_ERR_INVALID, "fltx_ctc_rows_stream_frames_in_buffer: bad argument");
   }
   std::vector<int32_t> cnt;
-  if ((rc = crsReadCounts(d, cnt))) {
+  int rc = crsReadCounts(d, cnt);
+  if (rc) {
     return rc;
   }
   *n = cnt[(size_t)b] - cnt[(size_t)d->B + b] + 1; /* nDecodedFramesInBuffer: the buffer's first frame counts */
@@ -7527,13 +7509,9 @@ static CpParams cpParams(fltx_decoder* d) {
 }
 
 int fltx_ctc_rows_plan_begin(fltx_decoder* d, int32_t rowCapacity) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = crCheck(d, "fltx_ctc_rows_plan_begin");
-  if (rc) {
-    return rc;
+  EntryScope entry(d, "fltx_ctc_rows_plan_begin", crCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d->s2s.begun || d->ended) {
     return fail(FLTX_ERR_STATE, "fltx_ctc_rows_plan_begin: fltx_ctc_rows_begin or fltx_ctc_rows_stream_begin first");
@@ -7566,13 +7544,9 @@ int fltx_ctc_rows_plan_begin(fltx_decoder* d, int32_t rowCapacity) {
 int fltx_ctc_rows_plan(fltx_decoder* d, const int32_t* nextTok, const int32_t* nextSrc, const int32_t* nextState,
                        const int32_t* nRows, int32_t* lmRowOf, int32_t* newRow, int32_t* newParentRow, int32_t* newEdge,
                        int32_t* newDecRow, int32_t* counts) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = crCheck(d, "fltx_ctc_rows_plan");
-  if (rc) {
-    return rc;
+  EntryScope entry(d, "fltx_ctc_rows_plan", crCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d->s2s.plOn) {
     return fail(FLTX_ERR_STATE, "fltx_ctc_rows_plan: fltx_ctc_rows_plan_begin first (after the decode's begin)");
@@ -7612,13 +7586,9 @@ int fltx_ctc_rows_plan(fltx_decoder* d, const int32_t* nextTok, const int32_t* n
 }
 
 int fltx_ctc_rows_plan_release(fltx_decoder* d, const int32_t* released, const int32_t* nReleased, int32_t releaseCap) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = crsCheck(d, "fltx_ctc_rows_plan_release");
-  if (rc) {
-    return rc;
+  EntryScope entry(d, "fltx_ctc_rows_plan_release", crsCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d->s2s.plOn) {
     return fail(FLTX_ERR_STATE, "fltx_ctc_rows_plan_release: fltx_ctc_rows_plan_begin first");
@@ -7639,29 +7609,14 @@ int fltx_ctc_rows_plan_release(fltx_decoder* d, const int32_t* released, const i
 }
 
 /* ---- finish and restart single streams (fltx_ctc_rows_stream.h) --------------------------------------------------------- */
-/* a copy home that waits for nothing: the caller synchronises once behind the last one */
-static int crsCopyHomeAsync(void* h, const void* dv, size_t n, Stream st) {
-#ifdef FLTX_EMU
-  (void)st;
-  memcpy(h, dv, n);
-  return 0;
-#else
-  return hipMemcpyAsync(h, dv, n, hipMemcpyDeviceToHost, st) == hipSuccess ? 0 : 1;
-#endif
-}
-
 int fltx_ctc_rows_stream_finish(fltx_decoder* d, const int32_t* which, const void* lmScores, int32_t lmDtype,
                                 int32_t lmKind, int64_t lmRowStride, const int32_t* lmRowOf, int32_t nLmRows,
                                 int32_t onDevice, double* lmRowLse, int32_t* nextTok, int32_t* nextSrc,
                                 int32_t* nextState, int32_t* nRows, int32_t resultsOnDevice, fltx_finished_out* out) {
   const char* what = "fltx_ctc_rows_stream_finish";
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = crsCheck(d, what);
-  if (rc) {
-    return rc;
+  EntryScope entry(d, what, crsCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!which || !nextTok || !nextSrc || !nextState || !nRows || !out) {
     return fail(FLTX_ERR_INVALID, "%s: null which, list or out", what);
@@ -7675,19 +7630,16 @@ int fltx_ctc_rows_stream_finish(fltx_decoder* d, const int32_t* which, const voi
                                 "plan)", what, d->s2s.plCollects);
   }
   Stream st = d->ctx->stream;
-  const int B = d->B, K = d->opt.beam_size;
+  const int B = d->B;
   const bool lex = d->kind == FLTX_DECODER_LEX_CTC_ROWS;
   bool named = false;
   for (int b = 0; b < B; ++b) {
     named = named || which[b] != 0;
   }
   const size_t nRec = (size_t)std::max<int64_t>(d->histRecords, 1), inBytes = 12 * (size_t)B;
-  if (d->s2s.finScores.ensure(24 * (size_t)B * K, st, false) || d->s2s.finTok.ensure(4 * nRec, st, false) ||
-      (lex && d->s2s.finWrd.ensure(4 * nRec, st, false)) || d->s2s.finMeta.ensure(12 * (size_t)B, st, false) ||
-      d->s2s.finIn.ensure(inBytes, st, false) || d->s2s.finSkip.ensure(4 * (size_t)B, st, false) ||
-      (!resultsOnDevice && (d->s2s.hFinScores.ensure(24 * (size_t)B * K) || d->s2s.hFinTok.ensure(4 * nRec) ||
-                            (lex && d->s2s.hFinWrd.ensure(4 * nRec)) || d->s2s.hFinMeta.ensure(12 * (size_t)B)))) {
-    return fail(FLTX_ERR_OOM, "%s: allocation failed (B=%d K=%d)", what, B, K);
+  int rc = stepFinishBuffers(d, what, nRec, 12 * (size_t)B, inBytes, 4 * (size_t)B, resultsOnDevice);
+  if (rc) {
+    return rc;
   }
   char* stage = (char*)d->s2s.finStage.acquire(inBytes);
   if (!stage) {
@@ -7708,12 +7660,8 @@ int fltx_ctc_rows_stream_finish(fltx_decoder* d, const int32_t* which, const voi
   Q.s.outN = nRows;
   Q.outState = nextState;
   Q.histOff = d->s2s.finIn.as<int64_t>();
-  Q.s.outScores = d->s2s.finScores.as<double>();
-  Q.s.tokens = d->s2s.finTok.as<int32_t>();
-  Q.s.outNHyp = meta;
-  Q.s.uttNBeam = meta;
-  Q.s.uttFrame = meta + B;
-  Q.s.uttStatus = meta + 2 * (size_t)B;
+  s2sSetResults(Q.s, {d->s2s.finScores.as<double>(), d->s2s.finTok.as<int32_t>(), meta, meta, meta + B,
+                      meta + 2 * (size_t)B});
   CrsFinishParams F;
   memset(&F, 0, sizeof(F));
   F.which = (const int32_t*)(Q.histOff + B);
@@ -7744,13 +7692,8 @@ int fltx_ctc_rows_stream_finish(fltx_decoder* d, const int32_t* which, const voi
   if (lex) {
     CrlFinishParams Y = {crlParams(d, Q), Z.x, F};
     Y.r.words = d->s2s.finWrd.as<int32_t>();
-    if (d->s2s.isLmToken) {
-      S2S_LAUNCH(fltx_ctc_rows_lex_stream_finish_kernel<kCrlLmTokenRows>, crlsFinishStream<kCrlLmTokenRows>, B,
-                 kS2sStepThreads, sizeof(CrlStepLds), st, Y);
-    } else {
-      S2S_LAUNCH(fltx_ctc_rows_lex_stream_finish_kernel<kCrlLmWordRows>, crlsFinishStream<kCrlLmWordRows>, B,
-                 kS2sStepThreads, sizeof(CrlStepLds), st, Y);
-    }
+    CRL_BY_LM_LEVEL(d, S2S_LAUNCH(fltx_ctc_rows_lex_stream_finish_kernel<SRC>, crlsFinishStream<SRC>, B, kS2sStepThreads,
+                                  sizeof(CrlStepLds), st, Y));
   } else {
     S2S_LAUNCH(fltx_ctc_rows_stream_finish_kernel, crsFinishStream, B, kS2sStepThreads, sizeof(S2lStepLds), st, Z);
   }
@@ -7763,54 +7706,16 @@ int fltx_ctc_rows_stream_finish(fltx_decoder* d, const int32_t* which, const voi
   d->s2s.plSkipped = d->s2s.plSkipped || d->s2s.plFresh; /* (the list before this one was never planned) */
   d->s2s.plFresh = true;
   memset(out, 0, sizeof(*out));
-  if (resultsOnDevice) {
-    out->n_hyp = meta;
-    out->length = meta + B;
-    out->status = meta + 2 * (size_t)B;
-    out->scores = d->s2s.finScores.as<double>();
-    out->tokens = d->s2s.finTok.as<int32_t>();
-    out->words = lex ? d->s2s.finWrd.as<int32_t>() : nullptr;
-    out->row_off = Q.histOff;
-    return FLTX_OK;
-  }
-  /* home: the counts first, then what the named streams really have -- n_hyp * length entries each */
-  int32_t* hMeta = (int32_t*)d->s2s.hFinMeta.p;
-  if (devCopyD2H(hMeta, meta, 12 * (size_t)B, st)) {
-    return fail(FLTX_ERR_HIP, "%s: result copy failed: %s", what, devErr());
-  }
-  int bad = 0;
-  for (int b = 0; b < B && !bad; ++b) {
-    const size_t n = (size_t)hMeta[b], at = (size_t)d->histOff[(size_t)b], cnt = n * (size_t)hMeta[(size_t)B + b];
-    if (n == 0) {
-      continue;
-    }
-    const size_t sAt = 3 * (size_t)b * K;
-    bad = crsCopyHomeAsync((double*)d->s2s.hFinScores.p + sAt, d->s2s.finScores.as<double>() + sAt, 24 * n, st) ||
-          crsCopyHomeAsync((int32_t*)d->s2s.hFinTok.p + at, d->s2s.finTok.as<int32_t>() + at, 4 * cnt, st) ||
-          (lex && crsCopyHomeAsync((int32_t*)d->s2s.hFinWrd.p + at, d->s2s.finWrd.as<int32_t>() + at, 4 * cnt, st));
-  }
-  if (bad || devSync(st)) {
-    return fail(FLTX_ERR_HIP, "%s: result copy failed: %s", what, devErr());
-  }
-  out->n_hyp = hMeta;
-  out->length = hMeta + B;
-  out->status = hMeta + 2 * (size_t)B;
-  out->scores = (const double*)d->s2s.hFinScores.p;
-  out->tokens = (const int32_t*)d->s2s.hFinTok.p;
-  out->words = lex ? (const int32_t*)d->s2s.hFinWrd.p : nullptr;
-  out->row_off = d->histOff.data();
-  return FLTX_OK;
+  out->row_off = resultsOnDevice ? Q.histOff : d->histOff.data();
+  /* (home: n_hyp * length entries of each named stream) */
+  return stepFinishResults(d, what, resultsOnDevice, d->histOff.data(), 0, &fltx_finished_out::length, out);
 }
 
 /* ---- seq2seq: finish and restart single utterances of a running batch (fltx_s2s.h: s2sFinishSlot) ---------------------- */
 int fltx_s2s_done_each(fltx_decoder* d, int32_t* done) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = s2sCheck(d, "fltx_s2s_done_each");
-  if (rc) {
-    return rc;
+  EntryScope entry(d, "fltx_s2s_done_each", s2sCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!done) {
     return fail(FLTX_ERR_INVALID, "fltx_s2s_done_each: null argument");
@@ -7830,13 +7735,9 @@ int fltx_s2s_done_each(fltx_decoder* d, int32_t* done) {
 int fltx_s2s_finish(fltx_decoder* d, const int32_t* which, int32_t* nextTok, int32_t* nextBeam, int32_t* nextSrc,
                     int32_t* nRows, int32_t* nextWord, int32_t resultsOnDevice, fltx_s2s_finished_out* out) {
   const char* what = "fltx_s2s_finish";
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
-  }
-  int rc = s2sCheck(d, what);
-  if (rc) {
-    return rc;
+  EntryScope entry(d, what, s2sCheck);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d->s2s.begun || d->ended) {
     return fail(FLTX_ERR_STATE, "%s: between fltx_s2s_begin and fltx_s2s_end", what);
@@ -7856,13 +7757,9 @@ int fltx_s2s_finish(fltx_decoder* d, const int32_t* which, int32_t* nextTok, int
   }
   Stream st = d->ctx->stream;
   const bool lex = d->kind == FLTX_DECODER_S2S_LEXICON;
-  const size_t nRec = (size_t)B * K * len;
-  if (d->s2s.finScores.ensure(24 * (size_t)B * K, st, false) || d->s2s.finTok.ensure(4 * nRec, st, false) ||
-      (lex && d->s2s.finWrd.ensure(4 * nRec, st, false)) || d->s2s.finMeta.ensure(20 * (size_t)B, st, false) ||
-      d->s2s.finIn.ensure(4 * (size_t)B, st, false) ||
-      (!resultsOnDevice && (d->s2s.hFinScores.ensure(24 * (size_t)B * K) || d->s2s.hFinTok.ensure(4 * nRec) ||
-                            (lex && d->s2s.hFinWrd.ensure(4 * nRec)) || d->s2s.hFinMeta.ensure(12 * (size_t)B)))) {
-    return fail(FLTX_ERR_OOM, "%s: allocation failed (B=%d K=%d)", what, B, K);
+  int rc = stepFinishBuffers(d, what, (size_t)B * K * len, 20 * (size_t)B, 4 * (size_t)B, 0, resultsOnDevice);
+  if (rc) {
+    return rc;
   }
   int32_t* stage = (int32_t*)d->s2s.finStage.acquire(4 * (size_t)B);
   if (!stage) {
@@ -7882,12 +7779,8 @@ int fltx_s2s_finish(fltx_decoder* d, const int32_t* which, int32_t* nextTok, int
   P.outBeam = nextBeam;
   P.outSrc = nextSrc;
   P.outN = nRows;
-  P.outScores = d->s2s.finScores.as<double>();
-  P.tokens = d->s2s.finTok.as<int32_t>();
-  P.outNHyp = meta;
-  P.uttStatus = meta + 2 * (size_t)B;
-  P.uttNBeam = meta + 3 * (size_t)B;
-  P.uttFrame = meta + 4 * (size_t)B;
+  s2sSetResults(P, {d->s2s.finScores.as<double>(), d->s2s.finTok.as<int32_t>(), meta, meta + 3 * (size_t)B,
+                    meta + 4 * (size_t)B, meta + 2 * (size_t)B});
   Z.f.which = d->s2s.finIn.as<int32_t>();
   Z.f.steps = meta + B;
   Z.f.errUnsupported = FLTX_ERR_UNSUPPORTED;
@@ -7916,41 +7809,8 @@ int fltx_s2s_finish(fltx_decoder* d, const int32_t* which, int32_t* nextTok, int
   }
   memset(out, 0, sizeof(*out));
   out->length = len;
-  if (resultsOnDevice) {
-    out->n_hyp = meta;
-    out->steps = meta + B;
-    out->status = meta + 2 * (size_t)B;
-    out->scores = d->s2s.finScores.as<double>();
-    out->tokens = d->s2s.finTok.as<int32_t>();
-    out->words = lex ? d->s2s.finWrd.as<int32_t>() : nullptr;
-    return FLTX_OK;
-  }
-  /* home: the counts first, then what the named slots really have -- n_hyp * length entries each */
-  int32_t* hMeta = (int32_t*)d->s2s.hFinMeta.p;
-  if (devCopyD2H(hMeta, meta, 12 * (size_t)B, st)) {
-    return fail(FLTX_ERR_HIP, "%s: result copy failed: %s", what, devErr());
-  }
-  int bad = 0;
-  for (int b = 0; b < B && !bad; ++b) {
-    const size_t n = (size_t)hMeta[b], at = (size_t)b * K * len, cnt = n * (size_t)len;
-    if (n == 0) {
-      continue;
-    }
-    const size_t sAt = 3 * (size_t)b * K;
-    bad = crsCopyHomeAsync((double*)d->s2s.hFinScores.p + sAt, d->s2s.finScores.as<double>() + sAt, 24 * n, st) ||
-          crsCopyHomeAsync((int32_t*)d->s2s.hFinTok.p + at, d->s2s.finTok.as<int32_t>() + at, 4 * cnt, st) ||
-          (lex && crsCopyHomeAsync((int32_t*)d->s2s.hFinWrd.p + at, d->s2s.finWrd.as<int32_t>() + at, 4 * cnt, st));
-  }
-  if (bad || devSync(st)) {
-    return fail(FLTX_ERR_HIP, "%s: result copy failed: %s", what, devErr());
-  }
-  out->n_hyp = hMeta;
-  out->steps = hMeta + B;
-  out->status = hMeta + 2 * (size_t)B;
-  out->scores = (const double*)d->s2s.hFinScores.p;
-  out->tokens = (const int32_t*)d->s2s.hFinTok.p;
-  out->words = lex ? (const int32_t*)d->s2s.hFinWrd.p : nullptr;
-  return FLTX_OK;
+  /* (home: n_hyp * length entries of each named slot) */
+  return stepFinishResults(d, what, resultsOnDevice, nullptr, len, &fltx_s2s_finished_out::steps, out);
 }
 
 /* ---- collapsed transcripts (fltx_transcript.h) -------------------------------------------------------------------------- */
@@ -8146,9 +8006,9 @@ static int trRun(TrBufs& T, Stream st, const int32_t* tok, const int32_t* wrd, c
 
 int fltx_collapse_rows(fltx_ctx* ctx, const int32_t* tokens, const int32_t* words, const int64_t* rowOff,
                        const int32_t* rowLen, int64_t nRows, int32_t blank, int32_t onDevice, fltx_transcripts* out) {
-  DeviceScope devScope(ctx);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(ctx);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!ctx || !out || nRows < 0 || (nRows > 0 && (!tokens || !rowOff || !rowLen))) {
     return fail(FLTX_ERR_INVALID, "fltx_collapse_rows: null ctx, out, tokens, row_off or row_len, or n_rows < 0");
@@ -8158,9 +8018,9 @@ int fltx_collapse_rows(fltx_ctx* ctx, const int32_t* tokens, const int32_t* word
 }
 
 int fltx_result_transcripts(fltx_decoder* d, int32_t maxHyp, int32_t onDevice, fltx_transcripts* out) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d || !out || maxHyp < 1) {
     return fail(FLTX_ERR_INVALID, "fltx_result_transcripts: null decoder or out, or max_hyp < 1");
@@ -8232,9 +8092,9 @@ int fltx_result_transcripts(fltx_decoder* d, int32_t maxHyp, int32_t onDevice, f
 
 /* ---- partial transcripts of all streams (fltx_stream_partials.h) -------------------------------------------------------- */
 int fltx_stream_partials(fltx_decoder* d, int32_t lookBack, int32_t onDevice, fltx_stream_partials_out* out) {
-  DeviceScope devScope(d ? d->ctx : nullptr);
-  if (devScope.failed) {
-    return fail(FLTX_ERR_HIP, "hipSetDevice failed");
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
   }
   if (!d || !out || lookBack < 0) {
     return fail(FLTX_ERR_INVALID, "fltx_stream_partials: null decoder or out, or look_back < 0");
