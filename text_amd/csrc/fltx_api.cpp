@@ -787,6 +787,8 @@ struct fltx_decoder {
   /* diagnostics of the engine a call STARTED on (a retry's prepare() must not overwrite them) */
   int64_t whyFirst = 0;
   int wlaneFirst = 0, slaneFirst = 0, laneGroupsFirst = 0, xlaneFirst = 0, ylaneFirst = 0;
+  int slaneM32First = 0; /* ... on the fltx_slane.h kernel with 32-bit token masks (slaneM32) */
+  int noSlaneM32 = 0;    /* tuning: 64-bit token masks whatever the token set (measurements: fltx_decoder_set "slane_m32" 0) */
   int lastRedo = 0;           /* utterances of the last offline call that had to be decoded again on a general path */
   int packedBits = 8;         /* width of the parent-slot field of those records (fltx_mlane.h: 10) */
   bool batchPacked = false;   /* some utterance of the current results has packed history records (ST_PACKED) */
@@ -2163,6 +2165,8 @@ int fltx_decoder_get(fltx_decoder* d, const char* key, int64_t* value) {
     *value = d->wlaneFirst;
   } else if (!strcmp(key, "slane")) {
     *value = d->slaneFirst;
+  } else if (!strcmp(key, "slane_m32")) { /* 1: the last call started on fltx_slane.h's kernel with 32-bit token masks */
+    *value = d->slaneM32First;
   } else if (!strcmp(key, "tlane")) { /* 1: the last call started on fltx_slane.h's token-LM variant */
     *value = d->tlaneFirst;
   } else if (!strcmp(key, "toklm_contexts")) { /* rows of the LM's dense (context, token) table (0: none built) */
@@ -2385,6 +2389,10 @@ int fltx_decoder_set(fltx_decoder* d, const char* key, int64_t value) {
     d->noYlaneAsg = value ? 0 : 1;
     return FLTX_OK;
   }
+  if (!strcmp(key, "slane_m32")) { /* 0: fltx_slane.h keeps 64-bit token masks whatever the token set (measurements) */
+    d->noSlaneM32 = value ? 0 : 1;
+    return FLTX_OK;
+  }
   if (!strcmp(key, "tune")) { /* development: see DecodeParams::tune */
     d->userTune = (int)value;
     return FLTX_OK;
@@ -2455,12 +2463,19 @@ static const int kSlaneOrderTwo[kSlaneGeoCount] = {3, 2, 1, 4, 0, 5, 6, 7};
 int engineOf(const fltx_decoder* d) {
   return d->ylane ? 6 : d->xlane ? 5 : (d->slane ? 4 : (d->lane ? 3 : (d->lean ? 2 : (d->dense ? 1 : 0))));
 }
+/* fltx_slane.h's offline max-merge kernel keeps its token masks in 32 bits when the token set has at most 32 tokens
+ * (the M32 instantiations: every geometry of FLTX_SLANE_GEOS has one) */
+bool slaneM32(const fltx_decoder* d) {
+  return d->slane && !d->tlane && !d->wlane && d->mlaneNG <= 1 && !d->xlane && !d->ylane && !d->opt.log_add && d->N <= 32 &&
+         !d->noSlaneM32;
+}
 /* what fltx_decoder_get reports about the engine a call started on */
 void latchFirst(fltx_decoder* d) {
   d->engineFirst = engineOf(d);
   d->whyFirst = d->whyNotLane;
   d->wlaneFirst = d->wlane;
   d->slaneFirst = d->slane;
+  d->slaneM32First = slaneM32(d) ? 1 : 0;
   d->tlaneFirst = d->tlane;
   d->xlaneFirst = d->xlane;
   d->ylaneFirst = d->ylane;
@@ -3331,7 +3346,7 @@ void fillParams(fltx_decoder* d, DecodeParams& P) {
 /* The lane-engine kernels, one entry per (family, variant, geometry) of fltx_engines.h.  The emulator build maps the
  * same entries to the host functions the kernels are made of (tests/emu/fltx_emu_launch.inc). */
 enum LaneFamily { kGeneric, kSlane, kTlane, kSstream, kTstream, kMlane, kTmlane, kWlane, kXlane, kYlane };
-enum { kVarLA = 1, kVarProf = 2, kVarHM = 4 }; /* logAdd merges, phase clocks, memo in HBM */
+enum { kVarLA = 1, kVarProf = 2, kVarHM = 4, kVarM32 = 8 }; /* logAdd merges, phase clocks, memo in HBM, 32-bit token masks */
 struct LaneKey {
   int fam, var, threads, g[4];
 };
@@ -3348,7 +3363,9 @@ struct LaneKernel {
 };
 #define FLTX_LK_SLANE(WW, GG)                                                                                       \
   FLTX_LK(kSlane, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_slane<WW, GG, false, false>), (slaneUtterance<GG, false, false, false>)) \
-  FLTX_LK(kSlane, kVarProf, WW, GG, 0, 0, 0, (fltx_decode_kernel_slane<WW, GG, false, true>), (slaneUtterance<GG, false, false, false>)) \
+  FLTX_LK(kSlane, kVarProf, WW, GG, 0, 0, 0, (fltx_decode_kernel_slane<WW, GG, false, true>), (slaneUtterance<GG, false, false, true>)) \
+  FLTX_LK(kSlane, kVarM32, WW, GG, 0, 0, 0, (fltx_decode_kernel_slane<WW, GG, false, false, true>), (slaneUtterance<GG, false, false, false, false, true>)) \
+  FLTX_LK(kSlane, kVarM32 | kVarProf, WW, GG, 0, 0, 0, (fltx_decode_kernel_slane<WW, GG, false, true, true>), (slaneUtterance<GG, false, false, true, false, true>)) \
   FLTX_LK(kSlane, kVarLA, WW, GG, 0, 0, 0, (fltx_decode_kernel_slane<WW, GG, true, false>), (slaneUtterance<GG, true, false, false>)) \
   FLTX_LK(kTlane, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_tlane<WW, GG, false>), (slaneUtterance<GG, false, false, false, true>)) \
   FLTX_LK(kTlane, kVarLA, WW, GG, 0, 0, 0, (fltx_decode_kernel_tlane<WW, GG, true>), (slaneUtterance<GG, true, false, false, true>))
@@ -3404,7 +3421,7 @@ LaneKey laneKeyOf(const fltx_decoder* d) {
   } else if (d->slane && d->wlane) {
     return {kWlane, prof, W, {d->slane, 0, 0, 0}};
   } else if (d->slane) {
-    return {d->tlane ? kTlane : kSlane, la | prof, W, {d->slane, 0, 0, 0}};
+    return {d->tlane ? kTlane : kSlane, la | prof | (slaneM32(d) ? kVarM32 : 0), W, {d->slane, 0, 0, 0}};
   }
   return {kGeneric, 0, W, {0, 0, 0, 0}};
 }

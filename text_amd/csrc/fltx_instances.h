@@ -32,6 +32,7 @@
  * large; W is ignored */
 #include "fltx_engines.h"
 #define FLTX_I_SLANE(WW, GG, LA, PROF) FLTX_INST(fltx_decode_kernel_slane<WW, GG, LA, PROF>)
+#define FLTX_I_SLANE_M32(WW, GG, PROF) FLTX_INST(fltx_decode_kernel_slane<WW, GG, false, PROF, true>)
 #define FLTX_I_TLANE(WW, GG, ...) FLTX_INST(fltx_decode_kernel_tlane<WW, GG, __VA_ARGS__>)
 #define FLTX_I_SSTREAM(WW, GG) FLTX_INST(fltx_decode_kernel_slane_stream<WW, GG>)
 #define FLTX_I_TSTREAM(WW, GG) FLTX_INST(fltx_decode_kernel_tlane_stream<WW, GG>)
@@ -45,6 +46,10 @@
 #define FLTX_I_SLANE_PLAIN(WW, GG) FLTX_I_SLANE(WW, GG, false, false)
 #define FLTX_G11(W) FLTX_SLANE_GEOS(FLTX_I_SLANE_PROF)
 #define FLTX_I_SLANE_PROF(WW, GG) FLTX_I_SLANE(WW, GG, false, true)
+#define FLTX_G41(W) FLTX_SLANE_GEOS(FLTX_I_SLANE_PLAIN32) /* 32-bit token masks: at most 32 tokens */
+#define FLTX_I_SLANE_PLAIN32(WW, GG) FLTX_I_SLANE_M32(WW, GG, false)
+#define FLTX_G42(W) FLTX_SLANE_GEOS(FLTX_I_SLANE_PROF32)
+#define FLTX_I_SLANE_PROF32(WW, GG) FLTX_I_SLANE_M32(WW, GG, true)
 #define FLTX_G15(W) FLTX_SLANE_GEOS(FLTX_I_SLANE_LA) /* logAdd */
 #define FLTX_I_SLANE_LA(WW, GG) FLTX_I_SLANE(WW, GG, true, false)
 #define FLTX_G28(W) FLTX_SLANE_GEOS(FLTX_I_TLANE_PLAIN) FLTX_TLANE_PROF_GEOS(FLTX_I_TLANE_PROF)
@@ -130,6 +135,8 @@ FLTX_G37(0)
 FLTX_G38(0)
 FLTX_G39(0)
 FLTX_G40(0)
+FLTX_G41(0)
+FLTX_G42(0)
 #undef FLTX_ALLG
 #endif
 #undef FLTX_G1
@@ -166,6 +173,8 @@ FLTX_G40(0)
 #undef FLTX_G38
 #undef FLTX_G39
 #undef FLTX_G40
+#undef FLTX_G41
+#undef FLTX_G42
 #undef FLTX_G25
 #undef FLTX_G26
 #undef FLTX_G27
@@ -173,6 +182,7 @@ FLTX_G40(0)
 #undef FLTX_G29
 #undef FLTX_G30
 #undef FLTX_I_SLANE
+#undef FLTX_I_SLANE_M32
 #undef FLTX_I_TLANE
 #undef FLTX_I_SSTREAM
 #undef FLTX_I_TSTREAM

@@ -46,10 +46,11 @@ __global__ void __launch_bounds__(W) fltx_decode_kernel_lane(DecodeParams P) {
   decodeUtterance<1, GT, LOGADD, FULLTOK>(P, fltx_smem);
 }
 /* lane = LM state decode of a whole utterance (fltx_slane.h): the headline configuration */
-template <int W, int GT, bool LA, bool PROF>
+/* M32: token masks of 32 bits in the frame's registers -- token sets of at most 32 tokens */
+template <int W, int GT, bool LA, bool PROF, bool M32 = false>
 __global__ void __launch_bounds__(W) fltx_decode_kernel_slane(DecodeParams P) {
   extern __shared__ __attribute__((aligned(16))) char fltx_smem[];
-  slaneUtterance<GT, LA, false, PROF>(P, fltx_smem);
+  slaneUtterance<GT, LA, false, PROF, false, M32>(P, fltx_smem);
 }
 /* ... with a token-level n-gram LM flattened to a dense (context, token) table (TL) */
 /* (512 threads: the geometry of which two workgroups share a CU -- 75 KB of LDS each with the small memos, and at most

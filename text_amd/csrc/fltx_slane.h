@@ -56,6 +56,14 @@
  *     argument (the own-groups and the staging wave of <512, 5> do, once or twice per frame, with a full wait).  All
  *     those loads gone, the kernel was as fast as with them, to within the spread of the runs: they hit the scalar
  *     cache, and the LDS reads their wait drains were about to be waited for.
+ *   * Nor is what a token set does not need: with at most 32 tokens the frame keeps its token masks in 32 bits (M32:
+ *     the hit test is one AND, every shift, OR and atomic on a mask one word; the arrays in LDS stay 64 bits wide), and
+ *     a token wave counts its lanes' places among the wave's new states in its build, which 92.5 % of the token
+ *     wave-frames do not run, from scalar popcounts of the ballots before it (C2: 225.1 -> 238.7 M frames/s, +6.1 %;
+ *     profiles/slane_narrow).  Reasoned, not measured: screens by the selection window do not pay on the benchmark's
+ *     rows -- the winning token is at -0.5 ... 0, every other at -11 ... -3, the window spans two octaves around the
+ *     K-th best and bin 0 takes everything nearer, so the best state's extension by almost any token is inside or
+ *     nearer than the window and "this position's nearest candidate is beyond it" almost never holds.
  *
  * Three barriers per frame.
  */
@@ -709,6 +717,25 @@ FLTX_DEV __attribute__((noinline)) void tlReenter(TlaneLds& S, const int2* histP
   ldsBarrier();
 }
 
+/* Token masks in registers: one bit per token, 64 bits wide -- or 32 (M32) where the token set has at most 32 tokens,
+ * which halves every mask operation of the frame.  The arrays in LDS are 64 bits wide either way (the narrow kernels
+ * read and write the low words; the high words stay zero as the prologue wiped them), so everything off the frame's
+ * path -- slReenter, the back-trace -- is one text. */
+template <bool M32>
+using SlMaskT = typename std::conditional<M32, uint32_t, unsigned long long>::type;
+template <bool M32>
+FLTX_DEV SlMaskT<M32> slMaskLoad(const unsigned long long* p) {
+  if constexpr (M32) {
+    return *(const uint32_t*)p; /* (little-endian: the low word) */
+  } else {
+    return *p;
+  }
+}
+FLTX_DEV void slMaskOr(unsigned long long* p, uint32_t v) { atomOr32((uint32_t*)p, v); }
+FLTX_DEV void slMaskOr(unsigned long long* p, unsigned long long v) { atomOr64(p, v); }
+FLTX_DEV int slMaskCtz(uint32_t v) { return __builtin_ctz(v); }
+FLTX_DEV int slMaskCtz(unsigned long long v) { return __builtin_ctzll(v); }
+
 #define FLTX_SLPROF(i)                                        \
   do {                                                        \
     if (PROF && P.prof && (int)threadIdx.x == P.profThread) { \
@@ -760,9 +787,13 @@ FLTX_DEV double slLogAdd(double hi, double lo) { return hi + log1p(exp(lo - hi))
  * reduces its candidates to a maximum, one LDS atomic max per wave, one more barrier (the frame shape of fltx_ylane.h);
  * (3) decodeEnd adds lmWeight x finish(context) (:127-158; column N of the row); (4) the LM score of a returned path is
  * re-accumulated by the back-trace like the emitting-model score (new-token steps follow from the tokens alone). */
-template <int GT, bool LA, bool ST, bool PROF, bool TL = false>
+/* M32: token masks of 32 bits in the frame's registers (SlMaskT); the host launches it when N <= 32 (offline, max-merge,
+ * no token LM: the headline configuration) */
+template <int GT, bool LA, bool ST, bool PROF, bool TL = false, bool M32 = false>
 FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
   static_assert(!(LA && ST), "streams with logAdd stay on the lane-per-slot step");
+  static_assert(!M32 || (!LA && !ST && !TL), "32-bit token masks: the offline max-merge kernel without a token LM");
+  using MaskT = SlMaskT<M32>;
   using LdsT = typename std::conditional<TL, TlaneLds, SlaneLds>::type;
   LdsT& S = *(LdsT*)smem;
   TlMemo M = {};
@@ -1017,29 +1048,29 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
       rowDead = (!any || !(best - best == 0.0)) ? 1u : 0u;
     }
     SlRec me = {};
-    unsigned long long cm = 0ull, mk = 0ull;
+    MaskT cm = 0, mk = 0;
     if (!isSvc) { /* (the staging wave has the longest way to the first barrier: it skips what it does not use) */
       me = S.rec[p][lane];
-      cm = S.cmask[p][lane];
-      mk = S.mask[p][lane];
+      cm = slMaskLoad<M32>(&S.cmask[p][lane]);
+      mk = slMaskLoad<M32>(&S.mask[p][lane]);
     }
     double ev[GT];
-    unsigned long long tb[GT];
+    MaskT tb[GT];
     double eBlank = 0.0;
-    unsigned long long allow = 0ull;
+    MaskT allow = 0;
 #pragma unroll
     for (int j = 0; j < GT; ++j) {
       ev[j] = 0.0;
-      tb[j] = 0ull;
+      tb[j] = 0;
     }
     if (isSelf) {
       eBlank = S.eAll[p][ctc ? blank : 0];
-      allow = S.row[p].allow;
+      allow = slMaskLoad<M32>(&S.row[p].allow);
     } else if (!isSvc) {
 #pragma unroll
       for (int j = 0; j < GT; ++j) {
         ev[j] = S.eTok[p][wave * GT + j];
-        tb[j] = S.tokBit[p][wave * GT + j];
+        tb[j] = slMaskLoad<M32>(&S.tokBit[p][wave * GT + j]);
       }
     }
     (void)nList;
@@ -1075,7 +1106,7 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
       } else {
 #pragma unroll
         for (int j = 0; j < GT; ++j) {
-          lmv[j] = lrow[tb[j] != 0ull ? __builtin_ctzll(tb[j]) : 0];
+          lmv[j] = lrow[tb[j] != 0 ? slMaskCtz(tb[j]) : 0];
         }
       }
     }
@@ -1161,8 +1192,8 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
         slReenter(S, histPT, p, nState, hbase, (int64_t)frameOut * K);
       }
       me = S.rec[p][lane];
-      cm = S.cmask[p][lane];
-      mk = S.mask[p][lane];
+      cm = slMaskLoad<M32>(&S.cmask[p][lane]);
+      mk = slMaskLoad<M32>(&S.mask[p][lane]);
     }
     if (TL) {
       FLTX_SLPROF(6); /* (TL: re-entry) */
@@ -1247,9 +1278,12 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
       /* tokens this lane does not extend with here: its own last token (the repeat and the
        * blank-then-last case belong to the self wave) and those whose child state holds a lane
        * (that lane merges the extension into its repeat).  A lane without a state skips all. */
-      const uint32_t lastLo = last < 32 ? 1u << last : 0u, lastHi = last < 32 ? 0u : 1u << (last - 32);
+      /* (64-bit masks: tested as two words -- the shifts and the test are 32-bit instructions either way; M32: skHi is
+       * zero at compile time and its half of the test is gone) */
+      const uint32_t lastLo = (M32 || last < 32) ? 1u << (last & 31) : 0u;
+      const uint32_t lastHi = (M32 || last < 32) ? 0u : 1u << (last - 32);
       const uint32_t skLo = live ? ((uint32_t)cm | lastLo) : 0xFFFFFFFFu;
-      const uint32_t skHi = live ? ((uint32_t)(cm >> 32) | lastHi) : 0xFFFFFFFFu;
+      const uint32_t skHi = M32 ? 0u : (live ? ((uint32_t)((unsigned long long)cm >> 32) | lastHi) : 0xFFFFFFFFu);
       double c1[GT], c2v[GT];
 #pragma unroll
       for (int j = 0; j < GT; ++j) {
@@ -1260,7 +1294,7 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
 #pragma unroll
       for (int j = 0; j < GT; ++j) {
         double c = c1[j];
-        const uint32_t hit = (skLo & (uint32_t)tb[j]) | (skHi & (uint32_t)(tb[j] >> 32));
+        const uint32_t hit = (skLo & (uint32_t)tb[j]) | (skHi & (uint32_t)((unsigned long long)tb[j] >> 32));
         const bool ok = hit == 0u && c >= thr;
         if (LA) { /* the state's other hypothesis reaches the same child state: fl(a + e) is monotone, so it
                      is the smaller member */
@@ -1273,14 +1307,14 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
         cbin[j] = ok ? slBin<LA>(best, c, winShift, winBase) : kSlInvalid;
       }
     } else {
-      const bool lastOk = live && ((allow >> last) & 1ull) != 0ull && !(ctc && last == blank);
+      const bool lastOk = live && ((allow >> last) & 1) != 0 && !(ctc && last == blank);
       const bool lastSil = last == sil;
       /* (S, blank, true): LexiconFreeDecoder.cpp:86-97 */
       double cB = m + eBlank;
       if (blank == sil) {
         cB = cB + silScore;
       }
-      const bool okB = ctc && live && ((allow >> (ctc ? blank : 0)) & 1ull) != 0ull && cB >= thr;
+      const bool okB = ctc && live && ((allow >> (ctc ? blank : 0)) & 1) != 0 && cB >= thr;
       if (LA) {
         double cB2 = (whichB ? nb : bb) + eBlank;
         if (blank == sil) {
@@ -1347,7 +1381,7 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
         }
         cR = okR ? acc : cR;
       }
-      const bool okL = ctc && lastOk && hasB && ((cm >> last) & 1ull) == 0ull && cL >= thr;
+      const bool okL = ctc && lastOk && hasB && ((cm >> last) & 1) == 0 && cL >= thr;
       cs[0] = cB;
       cs[1] = cR;
       cs[2] = cL;
@@ -1402,7 +1436,7 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
           cs[j] = c;
         }
       } else {
-        lastOk = live && ((allow >> last) & 1ull) != 0ull && !(ctc && last == blank);
+        lastOk = live && ((allow >> last) & 1) != 0 && !(ctc && last == blank);
         const bool lastSil = last == sil;
         hasOther = (whichB ? hypNB : hypB) != kSlNoHyp;
         /* (S, blank, true): :86-97, no LM term */
@@ -1410,7 +1444,7 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
         if (blank == sil) {
           cB = cB + silScore;
         }
-        pre[0] = ctc && live && ((allow >> (ctc ? blank : 0)) & 1ull) != 0ull && cB == cB;
+        pre[0] = ctc && live && ((allow >> (ctc ? blank : 0)) & 1) != 0 && cB == cB;
         if (LA) {
           double cB2 = (whichB ? nb : bb) + eBlank;
           if (blank == sil) {
@@ -1458,7 +1492,7 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
         prevR = t2 ? blank : prevR;
         lmR = t2 ? parLmB + (double)lIn : lmR;
         pre[1] = lastOk && (has0 || has1 || has2) && cR == cR;
-        pre[2] = ctc && lastOk && hasB && ((cm >> last) & 1ull) == 0ull && cL == cL;
+        pre[2] = ctc && lastOk && hasB && ((cm >> last) & 1) == 0 && cL == cL;
         cs[0] = cB;
         cs[1] = cR;
         cs[2] = cL;
@@ -1545,7 +1579,9 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
     }
     /* one LDS atomic per candidate inside the window (bin 0 = nearer than the window included);
      * what lies beyond the window (hundreds per frame, they would all hit one address) is not
-     * counted unless the window turns out to hold fewer than K */
+     * counted unless the window turns out to hold fewer than K.  (Tried and taken out again: the add issued by every
+     * lane for every position, the uncounted ones into a word of the lane's own in a spill row, so that no exec mask is
+     * saved and no branch taken per position -- as fast as this to within the spread of the runs; profiles/slane_narrow) */
 #pragma unroll
     for (int j = 0; j < GT; ++j) {
       if (cbin[j] < kSlFar) {
@@ -1592,6 +1628,9 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
           }
           if (lane == 0 && nFar > 0) {
             atomAdd32(&S.hist[p][kSlFar], (uint32_t)nFar);
+          }
+          if (PROF && !TL) { /* (1e6 x the frames that count the far bin, on top of the frames that rank a bin) */
+            acc[6] += 1000000ull;
           }
           full = true;
           ldsBarrier();
@@ -1685,14 +1724,10 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
     FLTX_SLPROF(2);
     /* new lanes: survivors first (self wave), then the new states wave by wave */
     int nNewWave = 0;
-    int myNew[GT];
+    int myNewL = 0; /* self wave: this lane's place among the wave's new states (a token wave counts in its build) */
     int surv = -1;
     uint32_t hNB = kSlNoHyp, hB = kSlNoHyp;
     if (isSvc) {
-#pragma unroll
-      for (int j = 0; j < GT; ++j) {
-        myNew[j] = 0;
-      }
       /* The next frame's row and the other parity's histogram (last read a frame ago) are written here, while the
        * other waves count their new lanes: this wave then has nothing left between the second and the third barrier.
        * (It issues no stores to HBM: it loads an emission row per frame, and a wait for that load would wait for
@@ -1703,8 +1738,8 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
       ((uint4*)S.hist[q])[lane] = make_uint4(0u, 0u, 0u, 0u);
     } else if (!isSelf) {
 #pragma unroll
-      for (int j = 0; j < GT; ++j) { /* (no branch around an empty position: it costs what it would skip) */
-        myNew[j] = nNewWave + wavePrefixCount(selMask[j]);
+      for (int j = 0; j < GT; ++j) { /* (scalar popcounts alone: a lane's place among a position's survivors is only
+                                        read by the build, which most token wave-frames do not run) */
         nNewWave += popc64(selMask[j]);
       }
       if (lane > wave && lane <= selfWave + 1 && nNewWave > 0) {
@@ -1721,11 +1756,7 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
       surv = ((balS >> lane) & 1ull) ? wavePrefixCount(balS) : -1;
       hNB = (uint32_t)(wavePrefixCount(balR) + wavePrefixCount(balB));
       hB = hNB + (sR ? 1u : 0u);
-#pragma unroll
-      for (int j = 0; j < GT; ++j) {
-        myNew[j] = 0;
-      }
-      myNew[2] = wavePrefixCount(balL);
+      myNewL = wavePrefixCount(balL);
       nNewWave = popc64(balL);
       S.newLane[lane] = surv;
       if (lane == 0) {
@@ -1842,8 +1873,8 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
       }
       S.rec[q][nl] = r;
       if (parNewLane >= 0) {
-        atomOr64(&S.cmask[q][parNewLane], 1ull << n);
-        atomOr64(&S.mask[q][parNewLane], 1ull << n);
+        slMaskOr(&S.cmask[q][parNewLane], (MaskT)1 << n);
+        slMaskOr(&S.mask[q][parNewLane], (MaskT)1 << n);
       }
       if (ST) {
         histPT[hrow + hyp] = plainRec(hp, n);
@@ -1864,7 +1895,7 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
       }
     };
     auto newState = [&](int idx, double c, int n, uint32_t hp, double amNew, uint32_t ctxNew, float lNew, double lmNew) {
-      newStateOf(idx, c, n, hp, amNew, ctxNew, lNew, lmNew, me.sid, ((mk >> n) & 1ull) != 0ull, myNewLane, lane);
+      newStateOf(idx, c, n, hp, amNew, ctxNew, lNew, lmNew, me.sid, ((mk >> n) & 1) != 0, myNewLane, lane);
     };
     if (isSvc) {
       /* (its part of the build went ahead of the second barrier) */
@@ -1883,20 +1914,23 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
         if (nNewWave > 1 && nNewWave <= kTlGather) {
           gathered = true;
           uint4* sc4 = (uint4*)((char*)S.memo + wave * kTlGatherBytes);
+          int before = 0; /* survivors of the wave's earlier positions */
 #pragma unroll
           for (int j = 0; j < GT; ++j) {
             if (selMask[j] != 0ull) {
+              const int at = before + wavePrefixCount(selMask[j]);
+              before += popc64(selMask[j]);
               if ((selMask[j] >> lane) & 1ull) {
-                const uint32_t nTok = tb[j] != 0ull ? (uint32_t)__builtin_ctzll(tb[j]) : 0u;
+                const uint32_t nTok = tb[j] != 0 ? (uint32_t)slMaskCtz(tb[j]) : 0u;
                 const float lj = __uint_as_float((uint32_t)lmv[j].x);
                 const unsigned long long cb = (unsigned long long)__double_as_longlong(cs[j]);
                 const unsigned long long ab =
                     (unsigned long long)__double_as_longlong(amStep(amM, ev[j], (int)nTok, whichB ? blank : last));
                 const unsigned long long lb = (unsigned long long)__double_as_longlong(lmM + (double)lj);
                 const uint32_t w0 = nTok | (hypM << 8) | ((uint32_t)(myNewLane + 1) << 16);
-                sc4[3 * myNew[j]] = make_uint4((uint32_t)cb, (uint32_t)(cb >> 32), (uint32_t)ab, (uint32_t)(ab >> 32));
-                sc4[3 * myNew[j] + 1] = make_uint4((uint32_t)lb, (uint32_t)(lb >> 32), w0, me.sid);
-                sc4[3 * myNew[j] + 2] = make_uint4((uint32_t)lmv[j].y, (uint32_t)lmv[j].x, 0u, 0u);
+                sc4[3 * at] = make_uint4((uint32_t)cb, (uint32_t)(cb >> 32), (uint32_t)ab, (uint32_t)(ab >> 32));
+                sc4[3 * at + 1] = make_uint4((uint32_t)lb, (uint32_t)(lb >> 32), w0, me.sid);
+                sc4[3 * at + 2] = make_uint4((uint32_t)lmv[j].y, (uint32_t)lmv[j].x, 0u, 0u);
               }
             }
           }
@@ -1911,13 +1945,17 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
         }
       }
       if (!gathered && nNewWave != 0) { /* (no survivor in this wave: nothing to walk) */
+      int before = 0; /* survivors of the wave's earlier positions: a lane's place among the wave's new states is counted
+                         here, in the positions that have a survivor, and not in every frame of every token wave */
 #pragma unroll
       for (int j = 0; j < GT; ++j) {
         if (selMask[j] != 0ull) { /* (most positions of most frames have no survivor at all) */
+          const int at = before + wavePrefixCount(selMask[j]);
+          before += popc64(selMask[j]);
           if ((selMask[j] >> lane) & 1ull) {
             /* (the position's token from its bit: reading tokId here is an LDS round trip per surviving position) */
-            const int nTok = tb[j] != 0ull ? __builtin_ctzll(tb[j]) : 0;
-            newState(offW + myNew[j], cs[j], nTok, hypM, ST ? amStep(amM, ev[j], nTok, whichB ? blank : last) : 0.0,
+            const int nTok = tb[j] != 0 ? slMaskCtz(tb[j]) : 0;
+            newState(offW + at, cs[j], nTok, hypM, ST ? amStep(amM, ev[j], nTok, whichB ? blank : last) : 0.0,
                      (uint32_t)lmv[j].y, __uint_as_float((uint32_t)lmv[j].x),
                      (ST && TL) ? lmM + (double)__uint_as_float((uint32_t)lmv[j].x) : 0.0);
           }
@@ -1941,10 +1979,10 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
           S.tlIn[q][surv] = lIn;
         }
         if (mk) {
-          atomOr64(&S.mask[q][surv], mk);
+          slMaskOr(&S.mask[q][surv], mk);
         }
         if (pln >= 0) {
-          atomOr64(&S.cmask[q][pln], 1ull << last);
+          slMaskOr(&S.cmask[q][pln], (MaskT)1 << last);
         }
         if (ST) {
           if (sR) {
@@ -1975,7 +2013,7 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
         }
       }
       if ((selMask[2] >> lane) & 1ull) {
-        newState(offW + myNew[2], cs[2], last, hypB, ST ? amStep(amBv, eLast, last, blank) : 0.0, (uint32_t)lmLast.y,
+        newState(offW + myNewL, cs[2], last, hypB, ST ? amStep(amBv, eLast, last, blank) : 0.0, (uint32_t)lmLast.y,
                  __uint_as_float((uint32_t)lmLast.x), (ST && TL) ? lmBv + (double)__uint_as_float((uint32_t)lmLast.x) : 0.0);
       }
     }
