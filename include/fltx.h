@@ -795,6 +795,37 @@ FLTX_API int fltx_ctc_rows_stream_finish(fltx_decoder* dec, const int32_t* which
                                          double* lm_row_lse, int32_t* next_token, int32_t* next_src_row,
                                          int32_t* next_state, int32_t* n_rows, int32_t results_on_device,
                                          fltx_finished_out* out);
+/* The same for the classic streams (fltx_stream_begin / _step / _prune / _end on FLTX_DECODER_LEXFREE and
+ * FLTX_DECODER_LEXICON): fltx_stream_finish ends the utterances of the streams `which` names (a HOST array of B, != 0:
+ * named) and restarts those slots, in one call, and leaves every other stream alone.
+ *
+ * First the call settles what fltx_stream_end settles: the look at a pending optimistic lexicon chunk (its second pass
+ * included) and a prune deferred behind it.  A named stream b then gets exactly fltx_stream_end's decodeEnd and the
+ * back-trace over the frames in its buffer: n_hyp[b], length[b], the token rows, the word rows and the three scores of
+ * each hypothesis are, entry for entry and bit for bit, what fltx_result_count and fltx_result_fetch return for the stream
+ * after fltx_stream_end at the same point (length = that call's length); status[b] is 0 or the FLTX_ERR_* that
+ * fltx_result_count would report (n_hyp[b] is then 0).
+ * Then, in the same call, slot b is in exactly the state fltx_stream_begin leaves a stream in: the root in the beam and
+ * at the first history row, no frames decoded and none pruned (fltx_stream_partials: first_frame 0), status cleared, the
+ * LM-state ids started over (root id 0; the stream's own part of the state table and of the LM score cache emptied), the
+ * host's frame count for max_frames back to zero.  max_frames stays.
+ * Of every other stream nothing observable changes: every later fltx_stream_step, _prune, _end, fltx_result_best,
+ * fltx_stream_partials and fltx_stream_frames_in_buffer returns for it, bit for bit, what it would have returned without
+ * the call, and fltx_result_* serve the live streams as before.
+ *
+ * Results, in `out` (the struct above; words NULL for the lexicon-free kind; row_off fixed for the life of the stream
+ * batch): results_on_device != 0 -- the pointers address HBM, written in the order of the context's stream; no result
+ * crosses PCIe and the call does not wait for the device; tokens / words / row_off / length are valid inputs of
+ * fltx_collapse_rows.  results_on_device == 0 -- pinned host buffers, complete when the call returns: the counts of all B
+ * streams cross, then n_hyp * length entries and 3 n_hyp scores of each named stream.  The buffers are the finish's own
+ * and stay valid until the next finish, fltx_stream_end or fltx_stream_begin on this decoder.
+ *
+ * A call that names no stream is legal and changes nothing; one that names all B equals fltx_stream_end followed by
+ * fltx_stream_begin.  FLTX_ERR_STATE outside a stream, after fltx_stream_end and on the step kinds; FLTX_ERR_INVALID on
+ * a NULL which or out; FLTX_ERR_UNSUPPORTED on a decoder whose LM is a host LM (fltx_lm_host_create): its states are the
+ * callee's and its start / retain protocol is per decoder -- left for later; end and begin all streams together. */
+FLTX_API int fltx_stream_finish(fltx_decoder* dec, const int32_t* which, int32_t results_on_device,
+                                fltx_finished_out* out);
 /* nDecodedFramesInBuffer of stream b (synchronises). */
 FLTX_API int fltx_ctc_rows_stream_frames_in_buffer(fltx_decoder* dec, int32_t b, int32_t* n);
 /* Inside such a stream fltx_result_best(dec, b, look_back, ...) is getBestHypothesis(lookBack): the ancestor's score,

@@ -130,6 +130,24 @@ def _transcript_views(t, device):
             "word_tok_end": _view(t.word_tok_end, C.c_int32, nw)}
 
 
+def _finished_host(fo, w, B, K):
+    """A filled fltx_finished_out with host results, for the streams the flags w name: n_hyp, length, status ([B] int32
+    copies) and hyps = {b: [Hyp]} copied out of the library's pinned buffers."""
+    n_hyp, length, status = (_view(p, C.c_int32, B).copy() for p in (fo.n_hyp, fo.length, fo.status))
+    row_off = _view(fo.row_off, C.c_int64, B)
+    scores = _view(fo.scores, C.c_double, 3 * B * K)
+    hyps = {}
+    for b in np.flatnonzero(w):
+        n, ln, at = int(n_hyp[b]), int(length[b]), int(row_off[b])
+        hyps[int(b)] = []
+        for i in range(n if status[b] == 0 else 0):
+            tk = _view(fo.tokens + 4 * (at + i * ln), C.c_int32, ln).copy()
+            wd = _view(fo.words + 4 * (at + i * ln), C.c_int32, ln).copy() if fo.words else np.full(ln, -1, np.int32)
+            s = scores[3 * (b * K + i):3 * (b * K + i) + 3]
+            hyps[int(b)].append(Hyp(float(s[0]), float(s[1]), float(s[2]), tk, wd))
+    return {"n_hyp": n_hyp, "length": length, "status": status, "hyps": hyps}
+
+
 class FltxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("fltx error %d: %s" % (code, msg))
@@ -164,7 +182,7 @@ class Lib:
         "fltx_ctc_rows_stream_begin", "fltx_ctc_rows_stream_append", "fltx_ctc_rows_stream_prune",
         "fltx_ctc_rows_stream_frames_in_buffer", "fltx_ctc_rows_stream_collect", "fltx_ctc_rows_stream_finish",
         "fltx_ctc_rows_plan_begin", "fltx_ctc_rows_plan", "fltx_ctc_rows_plan_release",
-        "fltx_collapse_rows", "fltx_result_transcripts", "fltx_stream_partials",
+        "fltx_collapse_rows", "fltx_result_transcripts", "fltx_stream_partials", "fltx_stream_finish",
     ]
 
     def __init__(self, path=None):
@@ -270,6 +288,7 @@ class Lib:
             "fltx_collapse_rows": [vp, vp, vp, vp, vp, i64, i32, i32, C.POINTER(Transcripts)],
             "fltx_result_transcripts": [vp, i32, i32, C.POINTER(Transcripts)],
             "fltx_stream_partials": [vp, i32, i32, C.POINTER(StreamPartialsOut)],
+            "fltx_stream_finish": [vp, vp, i32, C.POINTER(FinishedOut)],
         }
         for name, args in sig.items():
             fn = getattr(L, name)
@@ -811,6 +830,27 @@ class BatchDecoder:
 
     def stream_end(self):
         self._chk(self.L.lib.fltx_stream_end(self.h))
+
+    def stream_finish(self, which, device=False):
+        """End the utterances of the streams `which` names (B flags) and restart those slots, leaving every other stream
+        as it is (fltx_stream_finish).  device=False -> {b: the list of Hyp that results(b) gives after stream_end()} for
+        the named streams; a stream whose status is not 0 raises what count(b) would raise after stream_end().
+        device=True: nothing is copied; -> a dict of the integer device addresses n_hyp, length, status, scores, tokens,
+        words (None: lexicon-free), row_off -- tokens / words / row_off / length are what
+        Context.collapse_rows(device=True) takes.  Both stay valid until the next stream_finish(), stream_end() or
+        stream_begin()."""
+        w = np.ascontiguousarray(np.asarray(which) != 0, dtype=np.int32)
+        assert w.size == self.B, "which: one flag per stream"
+        fo = FinishedOut()
+        self._chk(self.L.lib.fltx_stream_finish(self.h, _ptr(w), 1 if device else 0, C.byref(fo)))
+        if device:
+            return {f: getattr(fo, f) for f, _ in FinishedOut._fields_}
+        fin = _finished_host(fo, w, self.B, int(self.options.beam_size))
+        for b in np.flatnonzero(w):
+            if fin["status"][b] != 0:
+                raise FltxError(int(fin["status"][b]), "stream %d stopped before it was finished (status %d)"
+                                % (b, fin["status"][b]))
+        return fin["hyps"]
 
     def stream_prune(self, look_back=0):
         self._chk(self.L.lib.fltx_stream_prune(self.h, look_back))
@@ -1827,20 +1867,7 @@ class CtcRowsBatchDecoder(BatchDecoder):
         self._inputs = keep
         if device:
             return tuple(out), {f: getattr(fo, f) for f, _ in FinishedOut._fields_}
-        B, K = self.B, int(self.options.beam_size)
-        n_hyp, length, status = (_view(p, C.c_int32, B).copy() for p in (fo.n_hyp, fo.length, fo.status))
-        row_off = _view(fo.row_off, C.c_int64, B)
-        scores = _view(fo.scores, C.c_double, 3 * B * K)
-        hyps = {}
-        for b in np.flatnonzero(w):
-            n, ln, at = int(n_hyp[b]), int(length[b]), int(row_off[b])
-            hyps[int(b)] = []
-            for i in range(n if status[b] == 0 else 0):
-                tk = _view(fo.tokens + 4 * (at + i * ln), C.c_int32, ln).copy()
-                wd = _view(fo.words + 4 * (at + i * ln), C.c_int32, ln).copy() if fo.words else np.full(ln, -1, np.int32)
-                s = scores[3 * (b * K + i):3 * (b * K + i) + 3]
-                hyps[int(b)].append(Hyp(float(s[0]), float(s[1]), float(s[2]), tk, wd))
-        return tuple(out), {"n_hyp": n_hyp, "length": length, "status": status, "hyps": hyps}
+        return tuple(out), _finished_host(fo, w, self.B, int(self.options.beam_size))
 
     @staticmethod
     def _chunk_kw(chunk, kind, dtype):

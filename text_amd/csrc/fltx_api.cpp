@@ -39,6 +39,7 @@
 #include "fltx_ctc_rows_stream.h"
 #include "fltx_transcript.h"
 #include "fltx_stream_partials.h"
+#include "fltx_stream_finish.h"
 #include "fltx_ctc_rows_plan.h"
 
 using namespace fltx;
@@ -378,6 +379,15 @@ template <int KIND>
 __global__ void __launch_bounds__(kSpThreads) fltx_stream_partials_kernel(SpParams Q) {
   __shared__ __attribute__((aligned(16))) SpLds fltx_sp_lds;
   spPartials<KIND>(Q, (char*)&fltx_sp_lds);
+}
+/* fltx_stream_finish.h: the back-trace of the named classic streams after their decodeEnd (and the counts of all B), and
+ * the named streams' LM-state ids and tables started over before their decodeBegin; a workgroup per named stream */
+__global__ void __launch_bounds__(kSfThreads) fltx_stream_finish_kernel(SfParams Q) {
+  __shared__ __attribute__((aligned(16))) SfLds fltx_sf_lds;
+  sfFinishStream(Q, (char*)&fltx_sf_lds);
+}
+__global__ void __launch_bounds__(kSfThreads) fltx_stream_restart_kernel(SfRestartParams Q) {
+  sfRestartStream(Q, nullptr);
 }
 __global__ void __launch_bounds__(1024) fltx_streamop_kernel(StreamOpParams Q) {
   __shared__ int32_t sh[kStreamOpLds / 4];
@@ -7724,6 +7734,145 @@ int fltx_ctc_rows_stream_finish(fltx_decoder* d, const int32_t* which, const voi
   d->s2s.plFresh = true;
   memset(out, 0, sizeof(*out));
   out->row_off = resultsOnDevice ? Q.histOff : d->histOff.data();
+  /* (home: n_hyp * length entries of each named stream) */
+  return stepFinishResults(d, what, resultsOnDevice, d->histOff.data(), 0, &fltx_finished_out::length, out);
+}
+
+/* ---- finish and restart single streams of a classic stream batch (fltx_stream_finish.h) ------------------------------- */
+int fltx_stream_finish(fltx_decoder* d, const int32_t* which, int32_t resultsOnDevice, fltx_finished_out* out) {
+  const char* what = "fltx_stream_finish";
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
+  }
+  if (d && stepKindCalls(d->kind)) {
+    return fail(FLTX_ERR_STATE, "%s: %s", what, stepKindCalls(d->kind));
+  }
+  if (!d || !which || !out) {
+    return fail(FLTX_ERR_INVALID, "%s: null decoder, which or out", what);
+  }
+  if (!d->streaming || d->ended) {
+    return fail(FLTX_ERR_STATE, "%s: no open stream (fltx_stream_begin first)", what);
+  }
+  if (d->lm->kind == 2) {
+    /* (a host LM's states are the callee's, and its start / retain protocol is per decoder: left for later) */
+    return fail(FLTX_ERR_UNSUPPORTED, "%s: a decoder with a host LM (fltx_lm_host_create) ends and begins all its streams "
+                                      "together (fltx_stream_end, fltx_stream_begin)", what);
+  }
+  /* what fltx_stream_end settles first: the look at a pending chunk, its second pass, the prune deferred behind it */
+  int rc = settleStream(d);
+  if (rc) {
+    return rc;
+  }
+  Stream st = d->ctx->stream;
+  const int B = d->B;
+  const bool lex = d->kind == FLTX_DECODER_LEXICON;
+  std::vector<int32_t> named;
+  for (int b = 0; b < B; ++b) {
+    if (which[b] != 0) {
+      named.push_back(b);
+    }
+  }
+  const int n = (int)named.size();
+  const size_t nRec = (size_t)std::max<int64_t>(d->histRecords, 1), inBytes = 8 * (size_t)B;
+  if ((rc = stepFinishBuffers(d, what, nRec, 12 * (size_t)B, inBytes, 4 * (size_t)B, resultsOnDevice))) {
+    return rc;
+  }
+  int32_t* meta = d->s2s.finMeta.as<int32_t>();
+  if (n == 0) { /* nobody is named: the counts say so, nothing else happens */
+    if (devMemset(meta, 0, 12 * (size_t)B, st)) {
+      return fail(FLTX_ERR_HIP, "%s: memset failed", what);
+    }
+  } else {
+    int32_t* stage = (int32_t*)d->s2s.finStage.acquire(inBytes); /* the named streams, then the B flags */
+    if (!stage) {
+      return fail(FLTX_ERR_OOM, "%s: staging allocation failed", what);
+    }
+    for (int b = 0; b < B; ++b) {
+      stage[b] = b < n ? named[(size_t)b] : 0;
+      stage[B + b] = which[b] != 0 ? 1 : 0;
+    }
+    if (devCopyH2D(d->s2s.finIn.p, stage, inBytes, st) || d->s2s.finStage.sent(st)) {
+      return fail(FLTX_ERR_HIP, "%s: upload failed", what);
+    }
+    const int32_t* dNamed = d->s2s.finIn.as<int32_t>();
+    /* decodeEnd of the named streams: fltx_stream_end's launch over the list, the n-best's scores into the finish's own */
+    DecodeParams P;
+    fillParams(d, P);
+    std::vector<int32_t> zeroT((size_t)B, 0);
+    if ((rc = uploadStep(d, nullptr, 1, nullptr, zeroT.data(), P))) {
+      return rc;
+    }
+    P.doBegin = 0;
+    P.doEnd = 1;
+    P.hlmFrame = 1 << 30;
+    P.uttMap = dNamed;
+    P.outScores = d->s2s.finScores.as<double>();
+    P.outN = d->s2s.finSkip.as<int32_t>(); /* (the count is read where fltx_result_count reads it: uttNBeam) */
+    d->nLaunch = n;
+    rc = launchDecode(d, P);
+    d->nLaunch = 0;
+    if (rc) {
+      return rc;
+    }
+    SfParams F;
+    memset(&F, 0, sizeof(F));
+    F.B = B;
+    F.K = d->opt.beam_size;
+    F.lex = lex ? 1 : 0;
+    F.nNamed = n;
+    F.errState = FLTX_ERR_STATE;
+    F.errUnsupported = FLTX_ERR_UNSUPPORTED;
+    F.named = dNamed;
+    F.which = dNamed + B;
+    F.histPT = d->histPT.as<int2>();
+    F.histW = d->histW.as<int32_t>();
+    F.histOff = d->histOffD.as<int64_t>();
+    F.uttFrame = d->uttFrame.as<int32_t>();
+    F.uttNBeam = d->uttNBeam.as<int32_t>();
+    F.uttStatus = d->uttStatus.as<int32_t>();
+    F.nHyp = meta;
+    F.length = meta + B;
+    F.status = meta + 2 * (size_t)B;
+    F.tokens = d->s2s.finTok.as<int32_t>();
+    F.words = lex ? d->s2s.finWrd.as<int32_t>() : nullptr;
+    S2S_LAUNCH(fltx_stream_finish_kernel, sfFinishStream, n, kSfThreads, sizeof(SfLds), st, F);
+    /* the slots start over: what launchCompact(d, 0) and a new epoch give a new batch of streams, for these alone */
+    SfRestartParams R;
+    memset(&R, 0, sizeof(R));
+    R.nNamed = n;
+    R.named = dNamed;
+    R.idCap = d->idCap;
+    R.stateCap = d->stateCap;
+    const bool counted = d->lean && !d->slane; /* (prepare(): which family's buffers exist) */
+    R.idPar = d->recycle ? d->idPar.as<uint32_t>() : nullptr;
+    R.uttNextId = (counted || d->recycle) ? d->uttNextId.as<int32_t>() : nullptr;
+    R.maskTab = counted ? d->maskTab.as<unsigned long long>() : nullptr;
+    R.stateTab = (d->lean || d->tlane) ? nullptr : d->stateTab.as<unsigned long long>();
+    R.stateVal = (!counted && d->recycle) ? d->stateVal.as<uint32_t>() : nullptr;
+    R.lmCache = d->useLmCache ? d->lmCache.as<unsigned long long>() : nullptr;
+    R.uttFirst = d->uttFirst.as<int64_t>();
+    S2S_LAUNCH(fltx_stream_restart_kernel, sfRestartStream, n, kSfThreads, 0, st, R);
+    /* decodeBegin of the named streams: fltx_stream_begin's launch over the list */
+    P.doBegin = 1;
+    P.doEnd = 0;
+    d->nLaunch = n;
+    rc = launchDecode(d, P);
+    d->nLaunch = 0;
+    if (rc) {
+      return rc;
+    }
+    for (int b : named) {
+      d->frames[(size_t)b] = 0; /* (exact, whatever the prunes since the last look left of the others' bounds) */
+    }
+    d->resultsSynced = false;
+    d->backtraced = false;
+    d->hostFetched = false;
+    d->compactFetched = false;
+    d->scoresFetched = false;
+  }
+  memset(out, 0, sizeof(*out));
+  out->row_off = resultsOnDevice ? d->histOffD.as<int64_t>() : d->histOff.data();
   /* (home: n_hyp * length entries of each named stream) */
   return stepFinishResults(d, what, resultsOnDevice, d->histOff.data(), 0, &fltx_finished_out::length, out);
 }
