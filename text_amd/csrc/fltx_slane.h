@@ -64,6 +64,16 @@
  *     rows -- the winning token is at -0.5 ... 0, every other at -11 ... -3, the window spans two octaves around the
  *     K-th best and bin 0 takes everything nearer, so the best state's extension by almost any token is inside or
  *     nearer than the window and "this position's nearest candidate is beyond it" almost never holds.
+ *   * Nor is a frame's row read when every wave reads: behind the third barrier sixteen waves of a CU issued a dozen LDS
+ *     reads each at the same moment, most of them of what the staging wave had written before the SECOND barrier of the
+ *     frame before.  The offline max-merge kernels fetch those behind that second barrier, where seven waves of eight
+ *     wait for the one that builds, and hand them to the next frame in registers (PF / SlRowPre: best, thr, a token
+ *     wave's emissions, the own-groups wave's blank emission and token beam); and under a full token beam, whose list
+ *     is the same in every frame, a token wave of the M32 kernel reads its tokBit words and sil's position once (C2:
+ *     238.8 -> 249.7 M frames/s, +4.6 %, either half about +2 %; 123 vector registers; profiles/slane_prefetch).  Not
+ *     ahead: `dead` -- carried across the frames it cost 30 vector registers and twice the scalar spills -- and what the
+ *     build writes (nev, records, masks).  Tried and taken out: the constant list as a second compile-time flavour of the
+ *     token waves' frame (127 registers by itself, 131 with the emissions ahead).
  *
  * Three barriers per frame.
  */
@@ -106,6 +116,21 @@ struct SlRow { /* what a frame needs to know about its emission row, 48 B */
 template <int V>
 struct SlParity {
   static constexpr int value = V;
+};
+
+/* A frame's reads of its emission row, fetched a frame ahead (slaneUtterance, PF): handed from frame to frame in
+ * registers.  A token wave uses ev (and tb / silPos), the own-groups wave eBlank / allow, the staging wave best. */
+#ifndef FLTX_SL_PREFETCH
+#define FLTX_SL_PREFETCH 1 /* (0: every frame reads its row behind the third barrier -- for measurements) */
+#endif
+template <int GT, typename MaskT>
+struct SlRowPre {
+  double best, thr;
+  double ev[GT];
+  double eBlank;
+  MaskT allow;
+  int32_t silPos; /* the M32 kernel's token waves: the list, read once when it is the same in every frame */
+  MaskT tb[GT];
 };
 
 struct SlaneLds {
@@ -1020,18 +1045,87 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
   const int tokStride = TL ? P.tokLmStride : 0;
   int2* const histPT = P.histPT;
 
+  /* PF: what a frame reads of its emission row and the staging wave wrote before the second barrier of the frame
+   * before -- best and thr, a token wave's emissions, the own-groups wave's blank emission and token beam -- is fetched
+   * behind that barrier, where seven waves of eight only wait for the one that builds, and handed to the frame in
+   * registers (SlRowPre): those reads are out of the burst that follows the third barrier.  The offline max-merge
+   * kernels; not with logAdd (best and thr come from mmaxKey, which the build raises), not with a token LM (best is
+   * known after barrier 0), not in a stream (its build still uses this frame's emissions: a token wave would hold two
+   * rows of them).  Never ahead: `nev`, the records and the masks, which the build of this frame writes -- and `dead`,
+   * which decides an early return: carried from frame to frame it took the kernel from 108 to 138 vector registers.
+   * listConst: a token beam that holds every token lists the same tokens at the same positions in every frame (the
+   * condition under which slRowStore pads nothing): a token wave of the M32 kernel then reads its tokBit words and sil's
+   * position once, before the loop -- otherwise into the same registers at the head of every frame, behind one
+   * wave-uniform branch (tune bit 1 takes that branch always, for measurements). */
+  constexpr bool PF = FLTX_SL_PREFETCH && !LA && !TL && !ST;
+  const bool listConst = M32 && P.Kt >= N && !(P.tune & 2);
+  auto rowFetch = [&](auto QT, auto RL, SlRowPre<GT, MaskT>& pre) {
+    constexpr int r = decltype(QT)::value;
+    constexpr bool isSelf = decltype(RL)::value == 1, isSvc = decltype(RL)::value == 2;
+    pre.best = S.row[r].best;
+    if (isSelf) {
+      pre.thr = S.row[r].thr;
+      pre.eBlank = S.eAll[r][ctc ? blank : 0];
+      pre.allow = slMaskLoad<M32>(&S.row[r].allow);
+    } else if (!isSvc) {
+      pre.thr = S.row[r].thr;
+#pragma unroll
+      for (int j = 0; j < GT; ++j) {
+        pre.ev[j] = S.eTok[r][wave * GT + j];
+      }
+    }
+  };
+  /* (an empty statement that "uses" the fetched values, placed before the third barrier: the compiler does not move the
+   * reads behind it, as in phase 1) */
+  auto rowPin = [&](auto RL, SlRowPre<GT, MaskT>& pre) {
+#ifndef FLTX_EMU
+    constexpr bool isSelf = decltype(RL)::value == 1, isSvc = decltype(RL)::value == 2;
+    if (isSvc) {
+      __asm__ volatile("" : "+v"(pre.best));
+    } else if (isSelf) {
+      __asm__ volatile("" : "+v"(pre.best), "+v"(pre.thr), "+v"(pre.eBlank), "+v"(pre.allow));
+    } else {
+      __asm__ volatile("" : "+v"(pre.best), "+v"(pre.thr));
+#pragma unroll
+      for (int j = 0; j < GT; ++j) {
+        __asm__ volatile("" : "+v"(pre.ev[j]));
+      }
+    }
+#else
+    (void)pre;
+#endif
+  };
+  auto listFetch = [&](auto QT, SlRowPre<GT, MaskT>& pre) { /* a token wave's part of the list */
+    constexpr int r = decltype(QT)::value;
+    pre.silPos = S.row[r].silPos;
+#pragma unroll
+    for (int j = 0; j < GT; ++j) {
+      pre.tb[j] = slMaskLoad<M32>(&S.tokBit[r][wave * GT + j]);
+    }
+  };
+
   /* one frame; PT = parity of the frame (compile time: every LDS address is an immediate) */
   /* RL = role of the wave (compile time as well: the three kinds of waves share the barriers and the
    * selection, and nothing else -- each gets its own straight-line frame and its own registers) */
-  auto frameStep = [&](auto PT, auto RL, float& rowReg, const int t) {
+  auto frameStep = [&](auto PT, auto RL, float& rowReg, SlRowPre<GT, MaskT>& pre, const int t) {
     constexpr int p = decltype(PT)::value, q = p ^ 1;
     constexpr bool isSelf = decltype(RL)::value == 1, isSvc = decltype(RL)::value == 2;
     const int frameOut = frame0 + t + 1;
     const int64_t hrow = hbase + (int64_t)frameOut * K;
     /* ---- phase 1: own state, candidates, histogram ------------------------------------- */
     /* every LDS read of the phase is issued here, before anything waits for one */
-    double best = S.row[p].best, thr = S.row[p].thr;
-    const int nList = S.row[p].nList, silPos = S.row[p].silPos;
+    /* (PF: fetched behind the second barrier of the frame before; frame 0: before the loop) */
+    double best = PF ? pre.best : S.row[p].best, thr = PF ? pre.thr : S.row[p].thr;
+    const int nList = S.row[p].nList;
+    int silPos = 0;
+    if (M32 && !isSelf && !isSvc) {
+      if (!listConst) {
+        listFetch(PT, pre);
+      }
+      silPos = pre.silPos;
+    } else {
+      silPos = S.row[p].silPos;
+    }
     uint32_t rowDead = S.row[p].dead;
     const uint32_t nev = S.row[p].nev;
     if (LA && !TL) { /* best candidate = best hypothesis of the beam + best token (sil priced apart: silScore) */
@@ -1064,13 +1158,13 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
       tb[j] = 0;
     }
     if (isSelf) {
-      eBlank = S.eAll[p][ctc ? blank : 0];
-      allow = slMaskLoad<M32>(&S.row[p].allow);
+      eBlank = PF ? pre.eBlank : S.eAll[p][ctc ? blank : 0];
+      allow = PF ? pre.allow : slMaskLoad<M32>(&S.row[p].allow);
     } else if (!isSvc) {
 #pragma unroll
       for (int j = 0; j < GT; ++j) {
-        ev[j] = S.eTok[p][wave * GT + j];
-        tb[j] = slMaskLoad<M32>(&S.tokBit[p][wave * GT + j]);
+        ev[j] = PF ? pre.ev[j] : S.eTok[p][wave * GT + j];
+        tb[j] = M32 ? pre.tb[j] : slMaskLoad<M32>(&S.tokBit[p][wave * GT + j]);
       }
     }
     (void)nList;
@@ -1796,6 +1890,11 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
       myNewLane = S.newLane[lane];
     }
     const int plNew = isSelf ? S.newLane[pl >= 0 ? pl : 0] : -1;
+    if constexpr (PF) {
+      /* the next frame's row, behind the reads this frame's build waits for.  (After the last frame nothing was staged:
+       * what this fetches then is the row of two frames ago, and nobody uses it -- the loop ends here.) */
+      rowFetch(SlParity<q>(), RL, pre);
+    }
     auto plainRec = [&](uint32_t hp, int n) { return make_int2(hp == kSlNoHyp ? -1 : (int)hp, n); };
     auto scoreRec = [&](int64_t at, double c, double am, double lmv) {
       if (P.histS) {
@@ -2020,21 +2119,31 @@ FLTX_DEV void slaneUtterance(const DecodeParams& P, char* smem) {
     nStatePrev = nState;
     nState = nSurv + nNew;
     endBest = best;
+    if constexpr (PF) {
+      rowPin(RL, pre);
+    }
     FLTX_SLPROF(4);
     ldsBarrier(); /* 3 */
     FLTX_SLPROF(5);
   };
   auto frames = [&](auto RL) {
+    SlRowPre<GT, MaskT> pre = {};
+    if constexpr (PF) { /* frame 0: the prologue's row */
+      rowFetch(SlParity<0>(), RL, pre);
+    }
+    if (M32 && decltype(RL)::value == 0) { /* (the prologue's list: every frame's when listConst) */
+      listFetch(SlParity<0>(), pre);
+    }
     int t = 0;
     for (; t + 1 < T && !dead; t += 2) {
-      frameStep(SlParity<0>(), RL, rowA, t);
+      frameStep(SlParity<0>(), RL, rowA, pre, t);
       if (dead) {
         break;
       }
-      frameStep(SlParity<1>(), RL, rowB, t + 1);
+      frameStep(SlParity<1>(), RL, rowB, pre, t + 1);
     }
     if (!dead && t < T) {
-      frameStep(SlParity<0>(), RL, rowA, t);
+      frameStep(SlParity<0>(), RL, rowA, pre, t);
     }
   };
   if (isSvcW) {
