@@ -221,6 +221,31 @@ FLTX_API int fltx_decode_batch(fltx_decoder* dec, const float* emissions,
                                const int64_t* offsets, const int32_t* T,
                                int32_t B, int32_t N);
 
+/* fltx_decode_batch on the emissions as the acoustic model produces them, with the emission arguments of
+ * fltx_ctc_rows_begin_typed: elements of `dtype` (a fltx_dtype), `kind` FLTX_S2S_LOG_PROBS or FLTX_S2S_LOGITS; frame f
+ * of utterance b starts at emissions + (offsets[b] + f * frame_stride) ELEMENTS, frame_stride >= N, 0 means N, offsets
+ * NULL: utterance b starts at frame_stride times the total of T[0 .. b-1].  Frames of the 2-byte types need only be
+ * 2-byte aligned.  The emission of token n in a frame is e[n]: the element widened exactly for log-probs; for logits
+ * (float)((double)x_n - lse), lse as fltx_s2s_step_typed defines it over the frame's N elements (an all-NaN frame and
+ * a frame whose maximum is -inf have lse = that maximum).  The result is the result of fltx_decode_batch on the float32
+ * rows e: the n-best, tokens and all scores bit for bit.
+ * On the word-piece lane engine (LexiconFreeDecoder, ZeroLM, 65 .. 16 384 tokens, token beam <= 64) no float32 copy of
+ * the emissions is made: the token beams are taken from the typed frames and the back-trace gathers the typed element
+ * with the frame's lse, which the decoder keeps.  Every other configuration, and an utterance that engine hands to the
+ * general engines (a frame with NaN, ...), decodes float32 rows e a small kernel widens into the decoder's staging
+ * buffer; fltx_decoder_get(dec, "typed_widened") counts the utterances of the last call that went this way.
+ * A host buffer (emissions_on_device == 0) is staged in its own type and stride before the call returns; a DEVICE
+ * buffer must stay valid and unchanged until the results have been read.  The batch is looked at before the call
+ * returns ("defer_check" applies to fltx_decode_batch only).
+ * frame_lse: NULL, or a DEVICE buffer of one double per frame of the call, utterance after utterance; logits mode
+ * writes each frame's lse there, log-probs mode leaves it untouched.
+ * FLTX_ERR_INVALID on a bad dtype or kind, on 0 < frame_stride < N, a negative T[b] or offset, and on emissions not
+ * aligned to its element; FLTX_ERR_STATE on a decoder with a host LM (fltx_lm_host_create) and on a decoder with an
+ * open stream; every other refusal is fltx_decode_batch's.  fltx_stream_step and fltx_group_decode_batch take float32. */
+FLTX_API int fltx_decode_batch_typed(fltx_decoder* dec, const void* emissions, int32_t dtype, int32_t kind,
+                                     int32_t emissions_on_device, const int64_t* offsets, int64_t frame_stride,
+                                     const int32_t* T, int32_t B, int32_t N, double* frame_lse);
+
 /* Streaming interface for B parallel streams (Decoder::decodeBegin /
  * decodeStep / decodeEnd / prune, decoder/Decoder.h:42-61).  max_frames bounds
  * the total frames buffered per stream between prunes.

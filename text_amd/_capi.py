@@ -165,7 +165,7 @@ class Lib:
         "fltx_ctx_synchronize", "fltx_ctx_stream", "fltx_ctx_uid", "fltx_lm_zero_create",
         "fltx_lm_ngram_create", "fltx_lm_host_create", "fltx_lm_arpa_load", "fltx_lm_state_size", "fltx_lm_start", "fltx_lm_step", "fltx_lm_destroy", "fltx_lm_score_sequence",
         "fltx_trie_create", "fltx_trie_destroy", "fltx_decoder_create",
-        "fltx_decoder_destroy", "fltx_decode_batch", "fltx_stream_begin",
+        "fltx_decoder_destroy", "fltx_decode_batch", "fltx_decode_batch_typed", "fltx_stream_begin",
         "fltx_stream_step", "fltx_stream_end", "fltx_stream_prune",
         "fltx_stream_frames_in_buffer", "fltx_result_count", "fltx_result_fetch", "fltx_result_fetch_batch", "fltx_result_fetch_batch_compact",
         "fltx_result_best", "fltx_result_device", "fltx_decoder_stats",
@@ -219,6 +219,7 @@ class Lib:
             "fltx_decoder_create": [vp, i32, C.POINTER(Options), vp, vp, i32, i32, i32, vp, i32, i32, pvp],
             "fltx_decoder_destroy": [vp],
             "fltx_decode_batch": [vp, vp, i32, vp, vp, i32, i32],
+            "fltx_decode_batch_typed": [vp, vp, i32, i32, i32, vp, i64, vp, i32, i32, vp],
             "fltx_stream_begin": [vp, i32, i32, i32],
             "fltx_stream_step": [vp, vp, i32, vp, vp],
             "fltx_stream_end": [vp],
@@ -807,6 +808,38 @@ class BatchDecoder:
             e = np.ascontiguousarray(emissions, dtype=np.float32)
             self._chk(self.L.lib.fltx_decode_batch(self.h, _ptr(e), 0, _ptr(offsets), _ptr(T), B, N))
         self.B = B
+        self.N = N
+
+    def decode_batch_typed(self, emissions, T, N, offsets=None, *, kind="log_probs", frame_stride=0, frame_lse=None,
+                           dtype=None, on_device=None):
+        """decode_batch on the acoustic model's output as it is (fltx_decode_batch_typed): a torch tensor of float32,
+        float16 or bfloat16 on the device or the host, flat or [frames, N] with unit column stride (a row stride other
+        than N is the frame stride), or an integer address with dtype= (a fltx_dtype: DTYPE_F32 / DTYPE_F16 /
+        DTYPE_BF16) and on_device=.  kind "logits": the decoder takes each frame's log-softmax itself, and frame_lse (a
+        float64 device tensor of sum(T), or its address) receives each frame's log-sum-exp.  offsets and frame_stride
+        are in ELEMENTS (offsets None: utterance after utterance).  A device tensor is kept referenced until the next
+        decode."""
+        if kind not in S2S_KINDS:
+            raise ValueError("kind: one of %s" % sorted(S2S_KINDS))
+        T = np.ascontiguousarray(T, dtype=np.int32)
+        off = None if offsets is None else np.ascontiguousarray(offsets, dtype=np.int64)
+        if hasattr(emissions, "data_ptr"):  # a torch tensor
+            dts = _torch_dtypes()
+            assert emissions.dtype in dts, "emissions: float32 / float16 / bfloat16"
+            assert emissions.stride(-1) == 1 and emissions.dim() <= 2, "emissions: flat or [frames, N], unit column stride"
+            if emissions.dim() == 2:
+                assert emissions.shape[1] == N, "emissions [frames, N]"
+                frame_stride = frame_stride or (emissions.stride(0) if emissions.shape[0] > 1 else 0)
+            dtype, ptr = dts[emissions.dtype], emissions.data_ptr()
+            on_device = 0 if emissions.device.type == "cpu" else 1
+        else:
+            assert dtype is not None and on_device is not None, "an address needs dtype= and on_device="
+            ptr = int(emissions)
+        lse = frame_lse.data_ptr() if hasattr(frame_lse, "data_ptr") else frame_lse
+        self._chk(self.L.lib.fltx_decode_batch_typed(self.h, ptr, int(dtype), S2S_KINDS[kind], int(on_device), _ptr(off),
+                                                     int(frame_stride), _ptr(T), len(T), int(N), lse))
+        self._emissions = emissions
+        self.B = len(T)
         self.N = N
 
     def stream_begin(self, B, N, max_frames):

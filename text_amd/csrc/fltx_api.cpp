@@ -35,6 +35,7 @@
 #include "fltx_s2s_lex.h"
 #include "fltx_ctc_rows.h"
 #include "fltx_ctc_rows_typed.h"
+#include "fltx_typed_entry.h"
 #include "fltx_ctc_rows_lex.h"
 #include "fltx_ctc_rows_stream.h"
 #include "fltx_transcript.h"
@@ -300,6 +301,10 @@ __global__ void __launch_bounds__(kS2sTypedThreads) fltx_ctc_rows_typed_wg_kerne
   __shared__ __attribute__((aligned(16))) S2sTypedLds fltx_crt_wg_lds;
   crTypedWgRows<DT, LOGITS>(Z, (char*)&fltx_crt_wg_lds);
 }
+/* fltx_decode_batch_typed's kernels (fltx_typed_entry.h) are compiled in an object of their own, fltx_typed_kinst.cpp */
+#define FLTX_TYPED_INST(...) extern template __global__ void __VA_ARGS__;
+FLTX_TYPED_ALL(FLTX_TYPED_INST)
+#undef FLTX_TYPED_INST
 template <int SRC, int DT, bool LOGITS>
 __global__ void __launch_bounds__(kS2sStepThreads) fltx_ctc_rows_lex_typed_step_kernel(CrlTypedParams Y) {
   __shared__ __attribute__((aligned(16))) CrlStepLds fltx_crlt_step_lds;
@@ -864,6 +869,21 @@ struct fltx_decoder {
   const void* ldsRaisedFn[2] = {nullptr, nullptr}; /* decode / back-trace kernel whose LDS limit this decoder last raised ... */
   size_t ldsRaisedTo[2] = {0, 0};                  /* ... and to what (raiseMaxLdsOnce) */
   DBuf tokRowsBuf; /* fltx_wlane.h: the token beams of all rows (fltx_tokbeam_kernel) */
+  /* fltx_decode_batch_typed: the call's typed frames (fltx_wlane_typed.h) */
+  struct {
+    bool on = false;       /* the batch being decoded is a typed one */
+    bool front = false;    /* ... and its first attempt took the token beams from the typed frames (fltx_wlane.h) */
+    const void* x = nullptr; /* the frames on the device: the caller's, or `raw` */
+    int dt = 0;
+    bool logits = false;
+    int64_t stride = 0;
+    double* lseOut = nullptr;
+    int64_t frames = 0;
+    int maxT = 0;
+    int64_t widened = 0;   /* "typed_widened": utterances of the last call that went through float32 rows */
+    std::vector<int64_t> meta; /* emOff[B], frameOff[B], wideOff[B] */
+    DBuf raw, metaD, lse;
+  } typed;
   int wlMaxT = 0;  /* ... longest utterance of the call (the front-end kernel's grid) */
   DBuf gScore, gAm, gLm, gState, gSPar, gSEdge, gLex, gTokPb;
   DBuf uttRes;   /* rows of uttRow int32: beam count, final frame, status per utterance -- one allocation, so that
@@ -2149,6 +2169,8 @@ int fltx_decoder_get(fltx_decoder* d, const char* key, int64_t* value) {
       }
     }
     *value = d->lastRedo;
+  } else if (!strcmp(key, "typed_widened")) { /* fltx_decode_batch_typed: utterances whose frames were widened to float32 rows */
+    *value = d->typed.widened;
   } else if (!strcmp(key, "sstream")) {
     *value = d->sstream;
   } else if (!strcmp(key, "tstream")) { /* 1: the stream's chunks run on the token-LM variant of fltx_slane.h */
@@ -3516,6 +3538,18 @@ int raiseMaxLdsOnce(fltx_decoder* d, int which, const void* fn, size_t bytes) {
 }
 #endif
 
+} // namespace
+/* fltx_decode_batch_typed (defined with the step decoders' typed dispatch, below) */
+static int wtLaunchFront(fltx_decoder* d, const DecodeParams& P, int nGrid);
+static int wtLaunchWiden(fltx_decoder* d, const DecodeParams& P, int nGrid);
+static int wtUpload(fltx_decoder* d, bool widen, const int32_t* T, DecodeParams& P);
+#ifdef FLTX_EMU
+static void wtBacktraceEmu(fltx_decoder* d, const BacktraceParams& Q, int narrow, int walkWaves, int btThreads, size_t btLds);
+#else
+static int wtBacktraceFn(fltx_decoder* d, int narrow, int walkWaves, const void** fn);
+#endif
+namespace {
+
 int launchDecode(fltx_decoder* d, const DecodeParams& P) {
   const LaneKey key = laneKeyOf(d);
   const LaneKernel* lane = key.fam == kGeneric ? nullptr : findLaneKernel(key);
@@ -3526,7 +3560,21 @@ int launchDecode(fltx_decoder* d, const DecodeParams& P) {
   const int W = key.threads;
   const int nGrid = d->nLaunch > 0 ? d->nLaunch : d->B;
   const size_t lds = launchLds(d, key);
+  /* a typed batch on fltx_wlane.h: the token beams come from the typed frames (fltx_wlane_typed.h) */
+  const bool typedFront = d->typed.on && d->typed.front && key.fam == kWlane && d->wlMaxT > 0;
 #ifdef FLTX_EMU
+  struct NoFloatFront { /* (the dispatch below launches the float32 front end when wlMaxT > 0) */
+    fltx_decoder* d;
+    int maxT;
+    ~NoFloatFront() { d->wlMaxT = maxT; }
+  } noFloatFront{d, d->wlMaxT};
+  if (typedFront) {
+    int rcF = wtLaunchFront(d, P, nGrid);
+    if (rcF) {
+      return rcF;
+    }
+    d->wlMaxT = 0;
+  }
 #include "fltx_emu_launch.inc" /* tests/emu/: host-thread dispatch over the kernel variants */
 #else
   for (int i = 0; i < 3; ++i) {
@@ -3545,7 +3593,12 @@ int launchDecode(fltx_decoder* d, const DecodeParams& P) {
     case 1024: fn = genericKernel<1024>(d); break;
     default: return fail(FLTX_ERR_INVALID, "threads per utterance must be 64, 128, 256, 512 or 1024");
   }
-  if (key.fam == kWlane && d->wlMaxT > 0) { /* the token beams of all rows first (same stream) */
+  if (typedFront) {
+    int rcF = wtLaunchFront(d, P, nGrid);
+    if (rcF) {
+      return rcF;
+    }
+  } else if (key.fam == kWlane && d->wlMaxT > 0) { /* the token beams of all rows first (same stream) */
     hipLaunchKernelGGL(fltx_tokbeam_kernel, dim3((unsigned)(P.tokRowBlocks * nGrid)), dim3(256), 4 * sizeof(WlFrontLds),
                        d->ctx->stream, P);
   }
@@ -3863,13 +3916,28 @@ int launchBacktrace(fltx_decoder* d) {
     devMemset(d->btProf.p, 0, 8 * (size_t)kBtProfMarks * d->B, st);
     Q.btProf = d->btProf.as<unsigned long long>();
   }
+  /* a typed batch whose packed records are fltx_wlane.h's: the score pass gathers from the typed frames */
+  const bool typedBt = d->typed.on && d->typed.front && Q.amGather && Q.amOut;
+  if (typedBt) {
+    if (narrow == 2) {
+      return fail(FLTX_ERR_UNSUPPORTED, "back-trace: typed emissions with byte records");
+    }
+    const int64_t* meta = d->typed.metaD.as<int64_t>();
+    Q.emissions = (const float*)d->typed.x;
+    Q.emOff = meta;
+    Q.emFrame = meta + d->B;
+    Q.emStride = d->typed.stride;
+    Q.emLse = d->typed.lse.as<double>();
+  }
   d->btWalkWaves = walkWaves;
   d->btNarrow = narrow;
   d->btChunk = narrow ? Q.npF : F;
   d->btStretch = narrow ? Q.npFe : (d->batchPacked && !Q.amGather ? F : 0);
 #ifdef FLTX_EMU
   const BacktraceParams* qq = &Q;
-  if (narrow == 2 && walkWaves > 1) {
+  if (typedBt) {
+    wtBacktraceEmu(d, Q, narrow, walkWaves, btThreads, btLds);
+  } else if (narrow == 2 && walkWaves > 1) {
     emuLaunch(d->B, btThreads, btLds, [qq](char* smem) { backtraceNarrow<uint16_t, true>(*qq, smem); });
   } else if (narrow == 4 && walkWaves > 1) {
     emuLaunch(d->B, btThreads, btLds, [qq](char* smem) { backtraceNarrow<uint32_t, true>(*qq, smem); });
@@ -3886,6 +3954,9 @@ int launchBacktrace(fltx_decoder* d) {
                      : narrow == 4 ? (walkWaves > 1 ? (const void*)fltx_backtrace_narrow_kernel<uint32_t, true>
                                                    : (const void*)fltx_backtrace_narrow_kernel<uint32_t, false>)
                                    : (const void*)fltx_backtrace_kernel;
+  if (typedBt) { /* the same three kernels on the typed frames' dtype and kind */
+    wtBacktraceFn(d, narrow, walkWaves, &btFn);
+  }
   int rcLds = raiseMaxLdsOnce(d, 1, btFn, btLds);
   if (rcLds) {
     return rcLds;
@@ -4425,6 +4496,7 @@ int fltx_decode_batch(fltx_decoder* d, const float* emissions, int32_t onDevice,
   d->compactFetched = false;
   d->scoresFetched = false;
   if (d->lm->kind == 2) {
+    d->typed.on = false;
     return hostLmDecodeBatch(d, emissions, onDevice, offsets, T, B, N);
   }
   d->offT.assign(T, T + B);
@@ -4434,6 +4506,7 @@ int fltx_decode_batch(fltx_decoder* d, const float* emissions, int32_t onDevice,
   }
   d->offN = N;
   d->offlinePending = false;
+  d->typed.on = false;
   return offlineAttempts(d, emissions, onDevice, 0);
 }
 
@@ -4521,7 +4594,16 @@ static int offlineAttempts(fltx_decoder* d, const float* emissions, int32_t onDe
     }
     DecodeParams P;
     fillParams(d, P);
-    if ((rc = uploadStep(d, emissions, onDevice, offsets, T, P))) {
+    /* a typed batch: fltx_wlane.h takes its token beams from the typed frames; every other engine, and the utterances
+     * decoded again, read float32 rows widened into the staging buffer */
+    if (d->typed.on && attempt == 0) {
+      d->typed.front = d->wlane != 0;
+      d->typed.widened = d->typed.front ? 0 : B;
+    } else if (d->typed.on && attempt == 1 && d->typed.front) {
+      d->typed.widened = (int64_t)redoList.size();
+    }
+    const bool widen = d->typed.on && !(attempt == 0 && d->typed.front);
+    if ((rc = d->typed.on ? wtUpload(d, widen, T, P) : uploadStep(d, emissions, onDevice, offsets, T, P))) {
       return rc;
     }
     P.doBegin = 1;
@@ -4535,6 +4617,9 @@ static int offlineAttempts(fltx_decoder* d, const float* emissions, int32_t onDe
       P.uttMap = d->uttMap.as<int32_t>();
       d->nLaunch = (int)redoList.size();
     }
+    if (widen && (rc = wtLaunchWiden(d, P, d->nLaunch > 0 ? d->nLaunch : B))) {
+      return rc;
+    }
     rc = launchDecode(d, P);
     d->nLaunch = 0;
     if (rc) {
@@ -4543,7 +4628,7 @@ static int offlineAttempts(fltx_decoder* d, const float* emissions, int32_t onDe
     } /* !look */
     const bool cutMode = d->CAP2 > 0 || d->cutRecompute;
     const bool needLook = !finalForm && ((d->kind == FLTX_DECODER_LEXICON && (d->wsInLds || cutMode)) || d->lean || d->wlane || d->xlane || d->ylane || d->tlane);
-    if (needLook && attempt == 0 && d->deferCheck) {
+    if (needLook && attempt == 0 && d->deferCheck && !d->typed.on) { /* (a typed batch is looked at before the call returns) */
       /* the caller keeps the emissions where they are until the results are read: launch the back-trace and return;
        * the look happens in syncResults() */
       d->offlinePending = true;
@@ -4698,6 +4783,7 @@ int fltx_stream_begin(fltx_decoder* d, int32_t B, int32_t N, int32_t maxFrames) 
     return rc;
   }
   d->maxFrames = maxFrames;
+  d->typed.on = false;
   d->streaming = true;
   d->ended = false;
   d->haveResults = false;
@@ -7020,6 +7106,201 @@ static int crBegin(fltx_decoder* d, const char* what, const CrEmIn& in, int32_t 
   S2S_LAUNCH(fltx_ctc_rows_begin_kernel, crBeginUtterance, (B + kS2sBeginThreads - 1) / kS2sBeginThreads,
              kS2sBeginThreads, 0, st, Q);
   return FLTX_OK;
+}
+
+/* ---- fltx_decode_batch_typed: the classic batch on typed frames (fltx_wlane_typed.h) --------------------------------- */
+extern "C++" { /* (declared ahead of launchDecode, outside this file's extern "C" block) */
+/* what the two typed kernels read beside the decode's own parameters */
+static WtParams wtParams(fltx_decoder* d, const DecodeParams& P) {
+  WtParams Z;
+  memset(&Z, 0, sizeof(Z));
+  Z.p = P;
+  const int64_t* meta = d->typed.metaD.as<int64_t>();
+  Z.x = d->typed.x;
+  Z.emOff = meta;
+  Z.frameOff = meta + d->B;
+  Z.wideOff = meta + 2 * (size_t)d->B;
+  Z.stride = d->typed.stride;
+  Z.lse = d->typed.lse.as<double>();
+  Z.lseOut = d->typed.lseOut;
+  Z.rowBlocks = std::max(1, (d->typed.maxT + 3) / 4);
+  return Z;
+}
+
+/* the token beams of fltx_wlane.h from the typed frames: one launch, a wave per frame */
+static int wtLaunchFront(fltx_decoder* d, const DecodeParams& P, int nGrid) {
+  const WtParams Z = wtParams(d, P);
+  return s2sTypedDispatch(d->typed.dt, d->typed.logits, [&](auto dt, auto lg) -> int {
+    S2S_DT_LOGITS(dt, lg);
+    S2S_LAUNCH((fltx_tokbeam_typed_kernel<DT, LOGITS>), (wtTokBeamRows<DT, LOGITS>), Z.rowBlocks * nGrid, 256,
+               4 * sizeof(WlFrontLds), d->ctx->stream, Z);
+    return FLTX_OK;
+  });
+}
+
+/* the float32 rows e of the launch's utterances into the staging buffer (P.emissions, P.emOff: wtUpload) */
+static int wtLaunchWiden(fltx_decoder* d, const DecodeParams& P, int nGrid) {
+  WtParams Z = wtParams(d, P);
+  Z.wide = d->emis[d->upSlot].as<float>();
+  Z.haveLse = d->typed.front ? 1 : 0; /* (the front end left every frame's lse: the rows are the e it selected from) */
+  return s2sTypedDispatch(d->typed.dt, d->typed.logits, [&](auto dt, auto lg) -> int {
+    S2S_DT_LOGITS(dt, lg);
+    S2S_LAUNCH((fltx_widen_rows_kernel<DT, LOGITS>), (wtWidenRows<DT, LOGITS>), Z.rowBlocks * nGrid, 256, 0,
+               d->ctx->stream, Z);
+    return FLTX_OK;
+  });
+}
+
+/* uploadStep for an attempt of a typed batch: the decode kernel's emissions are the typed frames themselves (only the
+ * front end and the back-trace read them), or -- widen -- the staging buffer the float32 rows are about to be written to */
+static int wtUpload(fltx_decoder* d, bool widen, const int32_t* T, DecodeParams& P) {
+  const size_t B = (size_t)d->B;
+  if (!widen) {
+    return uploadStep(d, (const float*)d->typed.x, 1, d->typed.meta.data(), T, P);
+  }
+  if (d->emis[d->upSlot].ensure(sizeof(float) * (size_t)std::max<int64_t>(d->typed.frames * d->N, 1), d->ctx->stream, false)) {
+    return fail(FLTX_ERR_OOM, "emissions staging allocation failed");
+  }
+  return uploadStep(d, d->emis[d->upSlot].as<float>(), 1, d->typed.meta.data() + 2 * B, T, P);
+}
+
+#ifdef FLTX_EMU
+static void wtBacktraceEmu(fltx_decoder* d, const BacktraceParams& Q, int narrow, int walkWaves, int btThreads, size_t btLds) {
+  const BacktraceParams* qq = &Q;
+  (void)s2sTypedDispatch(d->typed.dt, d->typed.logits, [&](auto dt, auto lg) -> int {
+    S2S_DT_LOGITS(dt, lg);
+    if (narrow == 4 && walkWaves > 1) {
+      emuLaunch(d->B, btThreads, btLds, [qq](char* smem) { backtraceNarrow<uint32_t, true, DT, LOGITS>(*qq, smem); });
+    } else if (narrow == 4) {
+      emuLaunch(d->B, btThreads, btLds, [qq](char* smem) { backtraceNarrow<uint32_t, false, DT, LOGITS>(*qq, smem); });
+    } else {
+      emuLaunch(d->B, btThreads, btLds, [qq](char* smem) { backtraceUtterance<DT, LOGITS>(*qq, smem); });
+    }
+    return FLTX_OK;
+  });
+}
+#else
+static int wtBacktraceFn(fltx_decoder* d, int narrow, int walkWaves, const void** fn) {
+  return s2sTypedDispatch(d->typed.dt, d->typed.logits, [&](auto dt, auto lg) -> int {
+    S2S_DT_LOGITS(dt, lg);
+    *fn = narrow == 4 ? (walkWaves > 1 ? (const void*)fltx_backtrace_narrow_typed_kernel<true, DT, LOGITS>
+                                       : (const void*)fltx_backtrace_narrow_typed_kernel<false, DT, LOGITS>)
+                      : (const void*)fltx_backtrace_typed_kernel<DT, LOGITS>;
+    return FLTX_OK;
+  });
+}
+#endif
+} /* extern "C++" */
+
+int fltx_decode_batch_typed(fltx_decoder* d, const void* emissions, int32_t dtype, int32_t kind, int32_t onDevice,
+                            const int64_t* offsets, int64_t frameStride, const int32_t* T, int32_t B, int32_t N,
+                            double* frameLse) {
+  EntryScope entry(d);
+  if (entry.rc) {
+    return entry.rc;
+  }
+  if (d && stepKindCalls(d->kind)) {
+    return fail(FLTX_ERR_STATE, "fltx_decode_batch_typed: %s", stepKindCalls(d->kind));
+  }
+  if (!d || !T || B <= 0 || N <= 0) {
+    return fail(FLTX_ERR_INVALID, "fltx_decode_batch_typed: bad argument");
+  }
+  if (!s2sDtypeOk(dtype)) {
+    return fail(FLTX_ERR_INVALID, "fltx_decode_batch_typed: dtype %d", dtype);
+  }
+  if (!s2sKindOk(kind)) {
+    return fail(FLTX_ERR_INVALID, "fltx_decode_batch_typed: kind %d", kind);
+  }
+  if (frameStride < 0 || (frameStride > 0 && frameStride < N)) {
+    return fail(FLTX_ERR_INVALID, "fltx_decode_batch_typed: frame_stride %lld < N = %d", (long long)frameStride, N);
+  }
+  if (d->lm->kind == 2) {
+    return fail(FLTX_ERR_STATE, "fltx_decode_batch_typed: a host LM reads float32 rows on the host (fltx_decode_batch)");
+  }
+  if (d->streaming) {
+    return fail(FLTX_ERR_STATE, "fltx_decode_batch_typed: the decoder has an open stream (fltx_stream_end first)");
+  }
+  const size_t es = s2sDtypeBytes(dtype);
+  const int64_t stride = frameStride ? frameStride : N;
+  std::vector<int64_t>& meta = d->typed.meta;
+  meta.assign(3 * (size_t)B, 0);
+  int64_t frames = 0;
+  int maxT = 0;
+  for (int b = 0; b < B; ++b) {
+    if (T[b] < 0 || (offsets && offsets[b] < 0)) {
+      return fail(FLTX_ERR_INVALID, "fltx_decode_batch_typed: T[%d] = %d, offsets[%d] = %lld", b, T[b], b,
+                  (long long)(offsets ? offsets[b] : 0));
+    }
+    meta[(size_t)b] = onDevice && offsets ? offsets[b] : frames * stride; /* (a host buffer is staged utterance after utterance) */
+    meta[(size_t)B + b] = frames;
+    meta[2 * (size_t)B + b] = frames * N;
+    frames += T[b];
+    maxT = std::max(maxT, T[b]);
+  }
+  if (frames > 0 && (!emissions || ((uintptr_t)emissions & (es - 1)) != 0)) {
+    return fail(FLTX_ERR_INVALID, "fltx_decode_batch_typed: emissions is null or not aligned to its element");
+  }
+  if (d->offlinePending) { /* "defer_check": an unread float32 batch, as fltx_decode_batch settles or drops it */
+    if (d->deferCheck == 2) {
+      d->offlinePending = false;
+      d->lookQueued = false;
+      ++d->looksDropped;
+    } else {
+      int rc = syncResults(d);
+      if (rc) {
+        return rc;
+      }
+      d->unreadRedone += d->lastRedo;
+    }
+  }
+  Stream st = d->ctx->stream;
+  const size_t nF = (size_t)std::max<int64_t>(frames, 1);
+  if ((!onDevice && d->typed.raw.ensure(es * nF * (size_t)stride, st, false)) ||
+      (kind == FLTX_S2S_LOGITS && d->typed.lse.ensure(8 * nF, st, false)) ||
+      d->typed.metaD.ensure(8 * meta.size(), st, false)) {
+    return fail(FLTX_ERR_OOM, "fltx_decode_batch_typed: device allocation failed (%lld frames)", (long long)frames);
+  }
+  d->typed.x = emissions;
+  if (!onDevice && frames > 0) { /* staged in its own type and stride; the last frame ends after N elements */
+    char* dst = (char*)d->typed.raw.p;
+    int bad = 0;
+    for (int b = 0; b < B && !bad; ++b) {
+      if (T[b] > 0) {
+        bad = devCopyH2D(dst + es * (size_t)meta[(size_t)b], (const char*)emissions + es * (size_t)(offsets ? offsets[b] : meta[(size_t)b]),
+                         es * (size_t)((int64_t)(T[b] - 1) * stride + N), st);
+      }
+    }
+    if (bad || devSync(st)) { /* (the caller's buffer is only borrowed for the call) */
+      return fail(FLTX_ERR_HIP, "fltx_decode_batch_typed: emission upload failed");
+    }
+    d->typed.x = dst;
+  }
+  if (devCopyH2D(d->typed.metaD.p, meta.data(), 8 * meta.size(), st)) {
+    return fail(FLTX_ERR_HIP, "fltx_decode_batch_typed: descriptor upload failed");
+  }
+  d->typed.dt = dtype;
+  d->typed.logits = kind == FLTX_S2S_LOGITS;
+  d->typed.stride = stride;
+  d->typed.lseOut = kind == FLTX_S2S_LOGITS ? frameLse : nullptr;
+  d->typed.frames = frames;
+  d->typed.maxT = maxT;
+  d->typed.front = false;
+  d->typed.widened = 0;
+  d->typed.on = true;
+  d->streaming = false;
+  d->chunkPending = false;
+  d->pendingPrune = -1;
+  d->haveResults = false;
+  d->resultsSynced = false;
+  d->backtraced = false;
+  d->hostFetched = false;
+  d->compactFetched = false;
+  d->scoresFetched = false;
+  d->offT.assign(T, T + B);
+  d->offOffsets.clear();
+  d->offN = N;
+  d->offlinePending = false;
+  return offlineAttempts(d, nullptr, 1, 0);
 }
 
 int fltx_ctc_rows_begin(fltx_decoder* d, const float* emissions, int32_t onDevice, const int64_t* offsets,

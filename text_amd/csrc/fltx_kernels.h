@@ -3655,7 +3655,47 @@ struct BacktraceParams {
   int32_t npWaves;       /* waves of the workgroup, each with ceil(npF / npWaves) frames of a chunk; the serial walk ignores it */
   int32_t npEntry;       /* byte offset of the entry map [sub-stretch][K] behind the tile */
   unsigned long long* btProf; /* "bt_profile": kBtProfMarks shader-clock marks per utterance, or null */
+  /* typed emissions (fltx_decode_batch_typed; EM of the kernels is a dtype of fltx_s2s.h): `emissions` is the typed buffer,
+   * frame f of utterance b starts at emOff[b] + f * emStride ELEMENTS and has its lse (logits) at emLse[emFrame[b] + f] */
+  int64_t emStride;
+  const double* emLse;
+  const int64_t* emFrame;
 };
+
+/* What the score passes read: emission[frame][token] of utterance b.  EM = kBtEmPlain: the float32 log-probs of
+ * fltx_decode_batch, N apart; else the typed element with the frame's stored lse (s2sTypedScore, fltx_s2s.h), as
+ * crEmission reads it for the CTC rows kinds -- the dtype and the kind are the kernel's template parameters */
+constexpr int kBtEmPlain = -1;
+template <int DT, bool LOGITS>
+FLTX_DEV float s2sTypedScore(const void* row, int i, double lse);
+struct BtEmission {
+  const void* em;    /* the utterance's first frame */
+  const double* lse; /* ... and its lse (typed logits) */
+  int64_t stride;    /* elements between two frames (typed) */
+};
+template <int EM, bool LOGITS>
+FLTX_DEV BtEmission btEmissionOf(const BacktraceParams& P, int b) {
+  BtEmission E;
+  if constexpr (EM == kBtEmPlain) {
+    E.em = P.emissions + P.emOff[b];
+    E.lse = nullptr;
+    E.stride = P.N;
+  } else {
+    E.em = (const char*)P.emissions + P.emOff[b] * (EM == 0 ? 4 : 2); /* (0: float32 elements) */
+    E.lse = LOGITS ? P.emLse + P.emFrame[b] : nullptr;
+    E.stride = P.emStride;
+  }
+  return E;
+}
+template <int EM, bool LOGITS>
+FLTX_DEV float btEmission(const BtEmission& E, int frame, int tok, int N) {
+  if constexpr (EM == kBtEmPlain) {
+    return ((const float*)E.em)[(size_t)frame * N + tok];
+  } else {
+    return s2sTypedScore<EM, LOGITS>((const char*)E.em + (int64_t)frame * E.stride * (EM == 0 ? 4 : 2), tok,
+                                     LOGITS ? E.lse[frame] : 0.0);
+  }
+}
 
 /* marks of "bt_profile" (thread 0 of an utterance's workgroup, raw shader clocks, reduced by the host): */
 constexpr int kBtProfChunks = 28; /* chunks with marks of their own (the rest of a longer walk falls between two marks) */
@@ -3676,6 +3716,7 @@ constexpr int kBtProfMarks = 8 + 2 * kBtProfChunks;
  * loads (double buffered: the next chunk arrives while this one is walked),
  * every hypothesis walks its F steps there (~100 clocks each), drops its
  * tokens into an LDS tile, and the tile leaves as row-contiguous stores. */
+template <int EM = kBtEmPlain, bool LOGITS = false>
 FLTX_DEV void backtraceUtterance(const BacktraceParams& P, char* smem) {
   const int b = (int)blockIdx.x;
   const int W = (int)blockDim.x, tid = (int)threadIdx.x;
@@ -3814,7 +3855,8 @@ FLTX_DEV void backtraceUtterance(const BacktraceParams& P, char* smem) {
     float* trT = eT + (P.amGather ? 0 : (size_t)F * P.N);              /* [N][N] (ASG) */
     int32_t* tT = (int32_t*)(trT + ((P.transitions && !P.amGather) ? (size_t)P.N * P.N : 0)); /* [nh][F] */
     const int N = P.N;
-    const float* em = P.emissions + P.emOff[b];
+    const BtEmission emOf = btEmissionOf<EM, LOGITS>(P, b);
+    auto emAt = [&](int frame, int tok, int n) { return btEmission<EM, LOGITS>(emOf, frame, tok, n); };
     if (P.transitions && !P.amGather) {
       for (int i = tid; i < N * N; i += W) {
         trT[i] = P.transitions[i];
@@ -3857,7 +3899,11 @@ FLTX_DEV void backtraceUtterance(const BacktraceParams& P, char* smem) {
 #pragma unroll
           for (int u = 0; u < 8; ++u) {
             const int i = base + u * W;
-            v[u] = i < nEm ? em[(size_t)(lo - 1) * N + i] : 0.0f;
+            if constexpr (EM == kBtEmPlain) { /* (rows N apart: the chunk is one block) */
+              v[u] = i < nEm ? emAt(lo - 1, i, N) : 0.0f;
+            } else {
+              v[u] = i < nEm ? emAt(lo - 1 + i / N, i % N, N) : 0.0f;
+            }
           }
 #pragma unroll
           for (int u = 0; u < 8; ++u) {
@@ -3886,7 +3932,7 @@ FLTX_DEV void backtraceUtterance(const BacktraceParams& P, char* smem) {
 #pragma unroll
             for (int u = 0; u < U; ++u) {
               const int jj = j0 + u < nf ? j0 + u : nf - 1;
-              ev[u] = P.amGather ? em[(size_t)(lo - 1 + jj) * N + (tk[u] >= 0 ? tk[u] : 0)] : eT[jj * N + (tk[u] >= 0 ? tk[u] : 0)];
+              ev[u] = P.amGather ? emAt(lo - 1 + jj, tk[u] >= 0 ? tk[u] : 0, N) : eT[jj * N + (tk[u] >= 0 ? tk[u] : 0)];
               tr[u] = 0.0f;
             }
             if (TR) {
@@ -4003,7 +4049,7 @@ constexpr size_t btScoreBytes(int K, int Fe, bool withTrans, bool tokRows, int t
   return (size_t)2 * K * btAddStride(Fe, withTrans ? 2 : 4) * (withTrans ? 8 : 4) + (tokRows ? (size_t)2 * K * Fe * tokBytes : 0);
 }
 
-template <typename RT, bool PW>
+template <typename RT, bool PW, int EM = kBtEmPlain, bool LOGITS = false>
 FLTX_DEV void backtraceNarrow(const BacktraceParams& P, char* smem) {
   typedef typename BtNarrow<RT>::Tok TT;
   constexpr int HB = (int)sizeof(RT) * 4;    /* bits of each half */
@@ -4014,7 +4060,7 @@ FLTX_DEV void backtraceNarrow(const BacktraceParams& P, char* smem) {
   const int len = ff + 1;
   const int L = P.npRow;
   if (!(P.uttStatus[b] & ST_PACKED) || len > L) {
-    backtraceUtterance(P, smem);
+    backtraceUtterance<EM, LOGITS>(P, smem);
     return;
   }
   const int W = (int)blockDim.x, tid = (int)threadIdx.x;
@@ -4350,7 +4396,8 @@ FLTX_DEV void backtraceNarrow(const BacktraceParams& P, char* smem) {
   }
   const int N = P.N;
   const int Fe = P.npFe;
-  const float* em = P.emissions + P.emOff[b];
+  const BtEmission emOf = btEmissionOf<EM, LOGITS>(P, b);
+    auto emAt = [&](int frame, int tok, int n) { return btEmission<EM, LOGITS>(emOf, frame, tok, n); };
   const int Tb = ff - 1; /* frames decoded: history rows 1 .. Tb */
   const bool trLds = P.transitions && !P.amGather;
   float* trT = (float*)scr;                                       /* [N][N] (ASG) */
@@ -4415,7 +4462,7 @@ FLTX_DEV void backtraceNarrow(const BacktraceParams& P, char* smem) {
      * has a token, as the loop this replaces took them; the first decoded frame has none. */
     auto gather = [&](const uint8_t* e0, const uint8_t* e1, int k, int j, int jj, float& ev, float& tr) -> bool {
       const int tk = tokVia(e0, k, j);
-      ev = em[(size_t)(j - 1) * N + (tk >= 0 ? tk : 0)];
+      ev = emAt(j - 1, tk >= 0 ? tk : 0, N);
       tr = 0.0f;
       if (TR) {
         int pv = tokVia(e1, k, j - 1);
