@@ -1065,7 +1065,11 @@ FLTX_API int fltx_decoder_profile(fltx_decoder* dec, uint64_t* out);
  * Round 3: "yshare" (-1 = the lexicon lane engines take the geometry of which several workgroups share a CU when the
  * batch exceeds the CUs; 1 / 0 = always / never), "stream_total_frames" (set before fltx_stream_begin: frames the
  * stream will decode in all -- its LM-state id tables grow with the stream, not with max_frames; default: at least
- * 2048), "sstream" (0 = a lexicon-free stream's chunks stay on the lane-per-slot step), "stream_optimistic" (0 = lexicon
+ * 2048), "sstream" (0 = a lexicon-free stream's chunks stay on the lane-per-slot step), "xstream" (1 = a lexicon
+ * stream's chunks run on the lane = (LM state, trie node) engine where it takes them -- ZeroLM over an unsmeared trie,
+ * one word per spelling, CTC, no <unk>, max-merge, beam and tokens up to 64, an optimistic stream; default 0; set before
+ * fltx_stream_begin; fltx_decoder_get "xstream" answers the positions per token wave chosen for the open stream, or 0;
+ * results are the same bit for bit), "stream_optimistic" (0 = lexicon
  * streams use the worst-case HBM workspace from the start instead of decoding an overflowing chunk again),
  * "stream_defer" (0 = fltx_stream_step of a lexicon stream waits for its chunk; default: the chunk is launched and whether
  * a stream has to decode it again is looked at by the next call that needs the beam -- the next chunk's upload runs

@@ -729,6 +729,7 @@ struct fltx_trie {
    * children are contiguous and in token order, so a child's id is the first child's id plus the
    * number of children with a smaller token; one 32-byte XNode per node, root = 0 */
   DBuf xnode, xdelta, xextra;
+  DBuf xOld2New, xNew2Old; /* node id as uploaded <-> breadth-first id (a stream's parked gLex holds the former) */
   bool xMulti = false;  /* some spelling has several words (Trie.h:19: up to 6 labels per node): fltx_ylane.h's LMK bit 2 */
   std::vector<int32_t> xEndHost; /* XNode::endLabel0 per node (host copy: decoders map it to LM word ids) */
   bool xOk = false;     /* the layout exists and the trie has the shape that engine assumes: */
@@ -826,6 +827,10 @@ struct fltx_decoder {
   int sstream = 0, sstreamThreads = 0, noSstream = 0;
   int tstream = 0; /* ... the stream's chunks run on fltx_slane.h's token-LM variant (ids from the generic engine's table) */
   bool sstreamLaunch = false;
+  /* ... and of the lexicon decoder on the lane = (LM state, trie node) engine (fltx_xlane.h, ST; "xstream" = 1 asks for
+   * it): positions per token wave (0 = not used) and threads of the chunks' launch; begin / end / prune / best and a
+   * chunk decoded again keep the generic geometry prepare() chose */
+  int xstreamAsked = 0, xstream = 0, xstreamThreads = 0;
   /* streams of the lexicon decoder on the optimistic geometry (LDS workspace, cut-off generation): a chunk that
    * overflows is decoded again from the saved beam on the general path (HBM workspace) */
   int userStreamOpt = 1;
@@ -1740,6 +1745,20 @@ int fltx_trie_create(fltx_ctx* ctx, int64_t nNodes, int32_t nTokens, const int32
       }
     }
     t->xZeroSmear = zero;
+    if (ok) { /* the two node maps (fltx_xlane.h's stream chunks restore lanes from, and park them as, the ids as uploaded) */
+      std::vector<uint32_t> new2old(order.size()), old2new(order.size());
+      for (size_t q = 0; q < order.size(); ++q) {
+        new2old[q] = (uint32_t)order[q];
+        old2new[(size_t)order[q]] = (uint32_t)q;
+      }
+      const size_t nb = sizeof(uint32_t) * order.size();
+      if (t->xNew2Old.ensure(nb, st, false) || t->xOld2New.ensure(nb, st, false) ||
+          devCopyH2D(t->xNew2Old.p, new2old.data(), nb, st) || devCopyH2D(t->xOld2New.p, old2new.data(), nb, st) ||
+          devSync(st)) {
+        delete t;
+        return fail(FLTX_ERR_OOM, "trie upload: node maps of the breadth-first layout");
+      }
+    }
     if (!ok) {
       xn.clear();
       xd.clear();
@@ -2173,6 +2192,8 @@ int fltx_decoder_get(fltx_decoder* d, const char* key, int64_t* value) {
     *value = d->typed.widened;
   } else if (!strcmp(key, "sstream")) {
     *value = d->sstream;
+  } else if (!strcmp(key, "xstream")) { /* positions per token wave of fltx_xlane.h's stream kernel chosen for the open stream, or 0 */
+    *value = d->xstream;
   } else if (!strcmp(key, "tstream")) { /* 1: the stream's chunks run on the token-LM variant of fltx_slane.h */
     *value = d->tstream;
   } else if (!strcmp(key, "looks_dropped")) { /* defer_check = 2: batches that were overwritten without a look at their statuses */
@@ -2357,6 +2378,10 @@ int fltx_decoder_set(fltx_decoder* d, const char* key, int64_t value) {
     d->noSstream = value ? 0 : 1;
     return FLTX_OK;
   }
+  if (!strcmp(key, "xstream")) { /* 1: a lexicon stream's chunks run on fltx_xlane.h where it takes them (default 0) */
+    d->xstreamAsked = value ? 1 : 0;
+    return FLTX_OK;
+  }
   if (!strcmp(key, "stream_optimistic")) { /* 0: streams of the lexicon decoder start on the worst-case (HBM) workspace */
     d->userStreamOpt = (int)value;
     return FLTX_OK;
@@ -2480,6 +2505,7 @@ static const LaneGeo kSlaneGeo[] = {FLTX_SLANE_GEOS(FLTX_GEO2)};
 static const LaneGeo kSstreamGeo[] = {FLTX_SSTREAM_GEOS(FLTX_GEO2)};
 static const LaneGeo kWlaneGeo[] = {FLTX_WLANE_GEOS(FLTX_GEO2)};
 static const LaneGeo kXlaneGeo[] = {FLTX_XLANE_GEOS(FLTX_GEO2)};
+static const LaneGeo kXstreamGeo[] = {FLTX_XSTREAM_GEOS(FLTX_GEO2)};
 static const MlaneGeo kMlaneGeo[] = {FLTX_MLANE_GEOS(FLTX_GEO5)}; /* "mlane_geo" = row */
 static const MlaneGeo kTmlaneGeo[] = {FLTX_TMLANE_GEOS(FLTX_GEO5)};
 #undef FLTX_GEO2
@@ -2882,9 +2908,27 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
       !d->offlineCall && d->keepScores && !d->opt.log_add && K <= 64 && d->recycle && optionsOk && chooseSstream()) {
     d->tstream = 1;
   }
+  /* ... and the chunks of a lexicon stream (xlaneUtterance<.., ST>), when asked for: fltx_xlane.h's offline terms, max-merge,
+   * the optimistic stream (a chunk this engine cannot finish is decoded again from the saved beam: streamRedoFlagged --
+   * whose prepare() forces the HBM workspace and so never comes here), recycled ids (the restore asks idPar).  Fields of
+   * its own: begin / end / prune / best and the redo keep the generic geometry chosen above */
+  d->xstream = 0;
+  if (d->xstreamAsked && d->kind == FLTX_DECODER_LEXICON && !d->offlineCall && d->keepScores && d->streamOpt && d->recycle &&
+      !d->forceGlobalWs && !d->genericAsked && !d->opt.log_add && d->lm->kind == 0 && !d->isLmToken && d->trie &&
+      d->trie->xOk && !d->trie->xMulti && d->trie->xZeroSmear && d->trie->xEndTok == d->sil && d->sil != d->blank &&
+      d->opt.criterion == FLTX_CRITERION_CTC && !(d->opt.unk_score > -std::numeric_limits<double>::infinity()) &&
+      K <= 64 && N <= 64 && optionsOk) {
+    for (const LaneGeo& g : kXstreamGeo) {
+      if (nTok <= g.gt * (g.threads / 64 - 3)) {
+        d->xstream = g.gt;
+        d->xstreamThreads = g.threads;
+        break;
+      }
+    }
+  }
   { /* which eligibility terms kept this call off the lane engines (fltx_decoder_get "why_not_lane") */
     int64_t why = 0;
-    if (!(d->slane || d->xlane || d->ylane || d->sstream)) {
+    if (!(d->slane || d->xlane || d->ylane || d->sstream || d->xstream)) {
       const bool lexi = d->kind == FLTX_DECODER_LEXICON;
       const bool unkOn = d->opt.unk_score > -std::numeric_limits<double>::infinity();
       why |= (N > 64 && (lexi || N > kWlMaxN || nTok > 64)) ? FLTX_WHY_TOKENS : 0; /* (lexicon-free: the token BEAM has to fit, fltx_wlane.h) */
@@ -3332,6 +3376,8 @@ void fillParams(fltx_decoder* d, DecodeParams& P) {
   P.prof = nullptr;
   P.xnode = (d->trie && d->trie->xnode.p) ? d->trie->xnode.as<XNode>() : nullptr;
   P.xEndTok = d->trie ? d->trie->xEndTok : -1;
+  P.xOld2New = (d->trie && d->trie->xOld2New.p) ? d->trie->xOld2New.as<uint32_t>() : nullptr;
+  P.xNew2Old = (d->trie && d->trie->xNew2Old.p) ? d->trie->xNew2Old.as<uint32_t>() : nullptr;
   P.xdelta = (d->trie && d->trie->xdelta.p) ? d->trie->xdelta.as<float>() : nullptr;
   P.xextra = (d->trie && d->trie->xextra.p) ? d->trie->xextra.as<uint32_t>() : nullptr;
   P.yTpw = d->ylaneTpw;
@@ -3377,7 +3423,7 @@ void fillParams(fltx_decoder* d, DecodeParams& P) {
 
 /* The lane-engine kernels, one entry per (family, variant, geometry) of fltx_engines.h.  The emulator build maps the
  * same entries to the host functions the kernels are made of (tests/emu/fltx_emu_launch.inc). */
-enum LaneFamily { kGeneric, kSlane, kTlane, kSstream, kTstream, kMlane, kTmlane, kWlane, kXlane, kYlane };
+enum LaneFamily { kGeneric, kSlane, kTlane, kSstream, kTstream, kMlane, kTmlane, kWlane, kXlane, kYlane, kXstream };
 enum { kVarLA = 1, kVarProf = 2, kVarHM = 4, kVarM32 = 8 }; /* logAdd merges, phase clocks, memo in HBM, 32-bit token masks */
 struct LaneKey {
   int fam, var, threads, g[4];
@@ -3419,6 +3465,8 @@ struct LaneKernel {
   FLTX_LK(kXlane, kVarHM, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane<WW, GG, 1, false>), (xlaneUtterance<GG, 1, false>)) \
   FLTX_LK(kXlane, kVarLA, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane<WW, GG, 0, false, true>), (xlaneUtterance<GG, 0, false, true>)) \
   FLTX_LK(kXlane, kVarLA | kVarHM, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane<WW, GG, 1, false, true>), (xlaneUtterance<GG, 1, false, true>))
+#define FLTX_LK_XSTREAM(WW, GG) \
+  FLTX_LK(kXstream, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane_stream<WW, GG>), (xlaneUtterance<GG, 0, false, false, true>))
 #define FLTX_LK_YLANE(WW, NG, RR, HM, LMK) \
   FLTX_LK(kYlane, HM ? kVarHM : 0, WW, NG, RR, LMK, 0, (fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, false>), (ylaneUtterance<NG, RR, LMK, HM, false>))
 #define FLTX_LK_YLANE_PROF(WW, NG, RR, HM, LMK) \
@@ -3426,7 +3474,7 @@ struct LaneKernel {
 static const LaneKernel kLaneKernels[] = {
     FLTX_SLANE_GEOS(FLTX_LK_SLANE) FLTX_TLANE_PROF_GEOS(FLTX_LK_TLANE_PROF) FLTX_SSTREAM_GEOS(FLTX_LK_SSTREAM)
     FLTX_MLANE_GEOS(FLTX_LK_MLANE) FLTX_TMLANE_GEOS(FLTX_LK_TMLANE) FLTX_WLANE_GEOS(FLTX_LK_WLANE)
-    FLTX_XLANE_GEOS(FLTX_LK_XLANE) FLTX_YLANE_KERNELS(FLTX_LK_YLANE) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_LK_YLANE_PROF)};
+    FLTX_XLANE_GEOS(FLTX_LK_XLANE) FLTX_XSTREAM_GEOS(FLTX_LK_XSTREAM) FLTX_YLANE_KERNELS(FLTX_LK_YLANE) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_LK_YLANE_PROF)};
 #undef FLTX_LK
 #undef FLTX_LK_SLANE
 #undef FLTX_LK_TLANE_PROF
@@ -3435,14 +3483,17 @@ static const LaneKernel kLaneKernels[] = {
 #undef FLTX_LK_TMLANE
 #undef FLTX_LK_WLANE
 #undef FLTX_LK_XLANE
+#undef FLTX_LK_XSTREAM
 #undef FLTX_LK_YLANE
 #undef FLTX_LK_YLANE_PROF
 
 /* what launchDecode runs: the lane engine's family, variant and geometry (kGeneric: the per-W kernels) */
 LaneKey laneKeyOf(const fltx_decoder* d) {
-  const int W = d->sstreamLaunch ? d->sstreamThreads : d->threads;
+  const int W = d->sstreamLaunch ? (d->xstream ? d->xstreamThreads : d->sstreamThreads) : d->threads;
   const int la = d->opt.log_add ? kVarLA : 0, prof = d->profile ? kVarProf : 0, hm = d->yshare ? kVarHM : 0;
-  if (d->sstreamLaunch) {
+  if (d->sstreamLaunch && d->xstream) {
+    return {kXstream, 0, W, {d->xstream, 0, 0, 0}};
+  } else if (d->sstreamLaunch) {
     return {d->tstream ? kTstream : kSstream, prof, W, {d->sstream, 0, 0, 0}};
   } else if (d->ylane) { /* (logAdd: LMK bit 3) */
     return {kYlane, prof | hm, W, {d->ylane, d->ylaneRounds, d->ylaneLm, 0}};
@@ -3477,6 +3528,8 @@ size_t launchLds(const fltx_decoder* d, const LaneKey& k) {
     return sizeof(SlaneLds);
   } else if (k.fam == kTstream) {
     return sizeof(TlaneLds) + (size_t)(k.threads / 64) * kTlGatherBytes;
+  } else if (k.fam == kXstream) { /* (the stream members take the LM-state memo's place) */
+    return offsetof(XlaneLds, memo) + sizeof(XlStreamLds);
   }
   return (k.fam == kGeneric && !d->wsInLds) ? d->hotBytes : d->wsBytes;
 }
@@ -3603,7 +3656,7 @@ int launchDecode(fltx_decoder* d, const DecodeParams& P) {
                        d->ctx->stream, P);
   }
   /* (slane, the stream chunks and gwslean launch within the default limit, as they always have) */
-  const bool defaultLimit = key.fam == kSlane || key.fam == kSstream || key.fam == kTstream ||
+  const bool defaultLimit = key.fam == kSlane || key.fam == kSstream || key.fam == kTstream || key.fam == kXstream ||
                             (key.fam == kGeneric && !d->wsInLds && d->lean);
   int rc;
   if (!defaultLimit && (rc = raiseMaxLdsOnce(d, 0, fn, lds))) {
@@ -4060,7 +4113,11 @@ int streamRedoFlagged(fltx_decoder* d) {
   const int32_t* status = (const int32_t*)d->hStat.p;
   std::vector<int32_t> again;
   for (int b = 0; b < d->B; ++b) {
-    if (status[b] & (ST_CAND_OVERFLOW | ST_CUT_RETRY)) {
+    /* (a chunk fltx_xlane.h could not finish -- a per-frame table full, a select that did not converge, no id left --
+     * says ST_SELECT_FALLBACK.  While d->xstream is set every chunk of the stream is launched on that engine and no
+     * other stream path raises this status, so the choice stands for "the launch that wrote the status"; a path that
+     * comes to raise it for another reason needs a test of its own here) */
+    if (status[b] & (ST_CAND_OVERFLOW | ST_CUT_RETRY | (d->xstream ? ST_SELECT_FALLBACK : 0))) {
       again.push_back(b);
     }
   }
@@ -4899,7 +4956,7 @@ int fltx_stream_step(fltx_decoder* d, const float* emissions, int32_t onDevice, 
   if (d->streamOpt && (rc = streamSnapshot(d, 0, nullptr, d->B))) {
     return rc;
   }
-  d->sstreamLaunch = d->sstream != 0;
+  d->sstreamLaunch = d->sstream != 0 || d->xstream != 0;
   rc = d->lm->kind == 2 ? hostLmFrames(d, P, T) : launchDecode(d, P);
   d->sstreamLaunch = false;
   if (rc) {

@@ -43,6 +43,9 @@
  * do not evaluate listed tokens */
 #define FLTX_XLANE_GEOS(X) X(512, 2) X(512, 3) X(640, 2) X(576, 5) X(640, 10)
 
+/* ... a lexicon stream's chunks (xlane_stream), in order of preference */
+#define FLTX_XSTREAM_GEOS(X) X(512, 2) X(576, 5) X(640, 10)
+
 /* fltx_ylane.h, with the LM terms: X(threads, lane groups, rounds, memo in HBM = shares a CU, ...) rows, each compiled
  * for pairs of LM-term variants LMK (bit 0 LM terms, 1 ASG, 2 several words per spelling, 3 logAdd):
  *   FLTX_YLANE_GEOS, FLTX_YLANE4_GEOS:  LMK (0, 1) (2, 3) (8, 9) (10, 11); a phase-clock variant of (0, 1) on the first

@@ -39,6 +39,7 @@
 #define FLTX_I_MLANE(WW, GG, NG, GPW, SPW, LA) FLTX_INST(fltx_decode_kernel_mlane<WW, GG, NG, GPW, SPW, LA>)
 #define FLTX_I_XLANE(WW, GG, ...) FLTX_INST(fltx_decode_kernel_xlane<WW, GG, __VA_ARGS__>)
 #define FLTX_I_WLANE(WW, GG) FLTX_INST(fltx_decode_kernel_wlane<WW, GG>)
+#define FLTX_I_XSTREAM(WW, GG) FLTX_INST(fltx_decode_kernel_xlane_stream<WW, GG>)
 #define FLTX_I_YLANE(WW, NG, RR, HM, LMK) FLTX_INST(fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, false>)
 #define FLTX_I_YLANE_PROF(WW, NG, RR, HM, LMK) FLTX_INST(fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, true>)
 #define FLTX_I_TMLANE(LA, ...) FLTX_INST(fltx_decode_kernel_tmlane<__VA_ARGS__, LA>)
@@ -82,6 +83,7 @@
 #define FLTX_G24(W) FLTX_XLANE_GEOS(FLTX_I_XLANE_LA) FLTX_XLANE_GEOS(FLTX_I_XLANE_LA_HBM) /* logAdd */
 #define FLTX_I_XLANE_LA(WW, GG) FLTX_I_XLANE(WW, GG, 0, false, true)
 #define FLTX_I_XLANE_LA_HBM(WW, GG) FLTX_I_XLANE(WW, GG, 1, false, true)
+#define FLTX_G43(W) FLTX_XSTREAM_GEOS(FLTX_I_XSTREAM) /* a lexicon stream's chunks */
 #define FLTX_G13(W) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_I_YLANE)
 #define FLTX_G14(W) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_I_YLANE_PROF)
 #define FLTX_G20(W) FLTX_YLANE4_GEOS(FLTX_YLMK_01, FLTX_I_YLANE) FLTX_YLANE4_GEOS(FLTX_YLMK_23, FLTX_I_YLANE)
@@ -137,6 +139,7 @@ FLTX_G39(0)
 FLTX_G40(0)
 FLTX_G41(0)
 FLTX_G42(0)
+FLTX_G43(0)
 #undef FLTX_ALLG
 #endif
 #undef FLTX_G1
@@ -175,6 +178,7 @@ FLTX_G42(0)
 #undef FLTX_G40
 #undef FLTX_G41
 #undef FLTX_G42
+#undef FLTX_G43
 #undef FLTX_G25
 #undef FLTX_G26
 #undef FLTX_G27
@@ -189,6 +193,7 @@ FLTX_G42(0)
 #undef FLTX_I_MLANE
 #undef FLTX_I_XLANE
 #undef FLTX_I_WLANE
+#undef FLTX_I_XSTREAM
 #undef FLTX_I_YLANE
 #undef FLTX_I_YLANE_PROF
 #undef FLTX_I_TMLANE

@@ -98,6 +98,15 @@ __global__ void __launch_bounds__(W, HM ? 4 : 1) fltx_decode_kernel_xlane(Decode
   extern __shared__ __attribute__((aligned(16))) char fltx_smem[];
   xlaneUtterance<GT, HM, PROF, LA>(P, fltx_smem);
 }
+/* ... the frames of one decodeStep chunk of a lexicon stream on that engine: beam in and out in the generic engine's parked
+ * format, LM-state ids from its table; its kernels do decodeBegin / decodeEnd / prune / getBestHypothesis.  31 KB of LDS
+ * (no LM-state memo) and, at 512 threads, at most 128 VGPRs (four waves per SIMD): workgroups share a CU when a
+ * server's streams outnumber the CUs */
+template <int W, int GT>
+__global__ void __launch_bounds__(W, W == 512 ? 4 : 1) fltx_decode_kernel_xlane_stream(DecodeParams P) {
+  extern __shared__ __attribute__((aligned(16))) char fltx_smem[];
+  xlaneUtterance<GT, 0, false, false, true>(P, fltx_smem);
+}
 /* ... with a word LM and / or a smeared trie, beams up to 128 (fltx_ylane.h) */
 /* HM = 1: the geometry that shares a CU (LM-state memo in HBM, 77 KB of LDS, at most 128 VGPRs: four
  * waves per SIMD = two workgroups of 512 threads).  LMK bit 2 (several words per spelling): the larger merge table leaves

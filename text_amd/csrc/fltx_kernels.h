@@ -235,6 +235,10 @@ struct DecodeParams {
   /* optional phase profile: [B*8] accumulated shader clocks (bench/tuning) */
   unsigned long long* prof;
   int32_t profThread; /* the thread whose clock is sampled (lane 0 of the wave under study) */
+  /* fltx_xlane.h, stream chunks: a node's id in the trie as uploaded (what gLex and the generic engine hold) -> its
+   * breadth-first id (XNode index), and back; null when the trie has no breadth-first layout */
+  const uint32_t* xOld2New;
+  const uint32_t* xNew2Old;
 };
 
 struct Ws {

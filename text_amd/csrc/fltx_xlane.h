@@ -112,6 +112,14 @@ struct XlaneLds {
   XlMemoSlot memo[kXlMemo];
 };
 
+/* Stream chunks (ST): the LM-state memo does not exist -- states are named through the generic engine's id table in
+ * HBM (tlStreamChild) -- and its place in LDS, from offsetof(XlaneLds, memo) on, holds what only a stream carries: the
+ * launch takes offsetof(XlaneLds, memo) + sizeof(XlStreamLds) bytes, and XlaneLds is the layout the offline kernels know. */
+struct XlStreamLds {
+  double amNB[2][64], amB[2][64]; /* emitting-model score of a lane's two hypotheses (getBestHypothesis reports an ancestor's) */
+  double winAm[kXlRoot];          /* merge table: the winner's, next to winHyp / winWord */
+};
+
 enum { XL_FLAG = 15 }; /* scal[]: a table ran full -> general path */
 
 FLTX_DEV unsigned long long xlKey(uint32_t a, int32_t b) {
@@ -173,9 +181,17 @@ FLTX_DEV unsigned long long xlOrphGet(const XlOrphTab& tab, unsigned long long k
 /* LA: logAdd -- the members of a merge group that pass the frame's threshold are summed instead of maximised
  * (Utils.h:160-165 filters, :167-198 merges): the candidates and the frame's best are found as without it, the sums
  * are formed once the threshold is known (one more barrier for the groups that span lanes: a root's arrivals) */
-template <int GT, int HM, bool PROF, bool LA = false>
+/* ST: the frames of one decodeStep chunk of a LexiconDecoder stream.  The beam comes from the slots the last launch (or
+ * the generic engine's begin / prune) parked and goes back there in that engine's format, so begin, end, prune,
+ * getBestHypothesis, finish and the partial transcripts stay the kernels they are; LM states are named through that
+ * engine's (epoch, parent id, word) -> id table; history rows are its plain records.  Every lane carries the
+ * emitting-model score of its two hypotheses, and the (parent id, word) name of its LM state for the park. */
+template <int GT, int HM, bool PROF, bool LA = false, bool ST = false>
 FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
+  static_assert(!(LA && ST), "streams with logAdd stay on the generic step");
+  static_assert(!(HM && ST), "a stream has no LM-state memo, in LDS or in HBM");
   XlaneLds& S = *(XlaneLds*)smem;
+  XlStreamLds& X = *(XlStreamLds*)(smem + (ST ? offsetof(XlaneLds, memo) : 0)); /* (ST only) */
   const int b = P.uttMap ? P.uttMap[blockIdx.x] : (int)blockIdx.x;
   const int W = (int)blockDim.x, tid = (int)threadIdx.x;
   const int lane = laneId(), wave = waveUniform(waveId());
@@ -202,6 +218,16 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
   unsigned long long acc[8] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
   unsigned long long tPrev = devClock();
   static_assert(GT >= 2, "the self and word waves keep their two groups in the slot arrays");
+  const int frame0 = ST ? P.uttFrame[b] : 0; /* streams: rows already in the buffer */
+  const int total0 = ST ? P.uttTotal[b] : 0; /* ... frames decoded since decodeBegin */
+  if constexpr (ST) {
+    if (T == 0) { /* no frames for this stream in this chunk: its parked beam, counters and history stay as they are */
+      if (tid == 0 && P.statusHost) {
+        P.statusHost[b] = P.uttStatus[b];
+      }
+      return;
+    }
+  }
 
   /* ---- decodeBegin (LexiconDecoder.cpp:21-30): the start state at the root ------------- */
   for (int i = tid; i < 2 * 64; i += W) {
@@ -234,7 +260,7 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
 #ifndef FLTX_EMU
     __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
-  } else {
+  } else if (!ST) {
     for (int i = tid; i < kXlMemo; i += W) {
       S.memo[i].key = 0ull;
     }
@@ -245,6 +271,113 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
   if (tid < 16) {
     S.scal[tid] = 0u;
   }
+  if constexpr (ST) {
+    /* ---- restore: the beam parked by the last launch (sorted slots, one hypothesis each) -> lanes, one per
+     * (LM state, trie node) pair; a slot's number is its hypothesis's slot in the last history row -------------- */
+    if (tid == 0) {
+      S.rootNode = xnode[0];
+      S.row[0].nev = 0u;
+      S.row[1].nev = 0u;
+      S.row[0].dead = 0u;
+      S.row[1].dead = 0u;
+      S.bestKey[0] = 0ull;
+      S.bestKey[1] = 0ull;
+    }
+    ldsBarrier(); /* (the wipes above) */
+    if (tid == 0) {
+      S.scal[SL_NEXTID] = (uint32_t)P.uttNextId[b];
+    }
+    if (wave == 0) {
+      const int nB = P.uttNBeam[b];
+      const bool valid = lane < nB;
+      const size_t g = (size_t)b * K + (valid ? lane : 0);
+      const double sc = P.gScore[g], amv = P.gAm[g];
+      const uint32_t sid = valid ? P.gState[g] : 0xFFFFFFFFu, spar = P.gSPar[g], tp = P.gTokPb[g];
+      const int32_t sedge = P.gSEdge[g];
+      /* (gLex is the node's id in the trie as uploaded; the lanes and XNode speak the breadth-first one) */
+      const uint32_t nd = valid ? P.xOld2New[P.gLex[g]] : 0xFFFFFFFFu;
+      const bool isB = (tp & kPrevBlank) != 0u;
+      int leader = lane;
+      for (int i = 0; i < nB; ++i) {
+        const uint32_t si = waveReadLane32(sid, i), ni = waveReadLane32(nd, i);
+        leader = (valid && si == sid && ni == nd && i < leader) ? i : leader;
+      }
+      const unsigned long long leaders = waveBallot(valid && leader == lane);
+      const int L = popc64(leaders & ((1ull << leader) - 1ull));
+      XlLanes& L0 = S.L[0];
+      if (valid && leader == lane) {
+        const XNode x = xnode[nd]; /* one 32-byte gather */
+        /* the node's own token (a lane that holds only its `b` hypothesis has it in no slot): children are laid out in
+         * token order, so it is the token of the (node - firstChild)-th set bit of the parent's child mask -- a second
+         * gather, once per lane and chunk, and no per-node token array beside the maps */
+        uint32_t tok = (uint32_t)sil;
+        if (nd != 0u) {
+          const XNode px = xnode[x.parent];
+          unsigned long long mm = px.childMask;
+          for (uint32_t r = nd - px.firstChild; r > 0u; --r) {
+            mm &= mm - 1ull;
+          }
+          tok = (uint32_t)__builtin_ctzll(mm | (1ull << 63));
+        }
+        /* The root lane of an LM state takes the words that end on it: arrivals from the state `spar` with the word
+         * `sedge`.  Two kinds of state can take none, and say so in bit 31 (no state id has it): the start state --
+         * nobody is its parent -- and a state whose parent a compaction has cut loose.  That parent was neither in the
+         * beam nor between two states of the beam, so no hypothesis stands in it, and none will: states are entered
+         * from their parent only, under an id the table hands out, and the table was rebuilt without it.  The number
+         * left in gSPar is stale and may since have been given to another state: it must not be matched.
+         * The second test is a guard, not a case the tests reach: compactStates keeps the parent of every state that
+         * has a hypothesis in the beam (its `need` is at least 1), so of the states restored here only the start
+         * state has no parent on record today.  It costs one 4-byte gather per lane and chunk; a compaction that kept
+         * less would otherwise have stale numbers matched without any sign of it. */
+        const bool noArr = sid == 0u || P.idPar[(size_t)b * P.idCap + sid] == kNoParent32;
+        L0.nb[L] = NEG;
+        L0.b[L] = NEG;
+        L0.childMask[L] = x.childMask;
+        L0.kidsMask[L] = x.kidsMask;
+        L0.info[L] = tok | (kSlNoHyp << 16) | (kSlNoHyp << 24);
+        L0.link[L] = 0u;
+        L0.lmSid[L] = sid;
+        L0.node[L] = nd;
+        L0.parent[L] = x.parent;
+        L0.firstChild[L] = x.firstChild;
+        L0.endLabel[L] = x.endLabel0;
+        L0.dPar[L] = spar | (noArr ? 0x80000000u : 0u);
+        L0.dWord[L] = sedge;
+        X.amNB[0][L] = 0.0;
+        X.amB[0][L] = 0.0;
+      }
+      waveSync();
+      if (valid) { /* (the two hypotheses of a lane write different bytes of its info word) */
+        if (isB) {
+          L0.b[L] = sc;
+          X.amB[0][L] = amv;
+          ((volatile uint8_t*)&L0.info[L])[3] = (uint8_t)lane;
+        } else {
+          L0.nb[L] = sc;
+          X.amNB[0][L] = amv;
+          ((volatile uint8_t*)&L0.info[L])[2] = (uint8_t)lane;
+        }
+      }
+      waveSync();
+      /* links: a lane's parent lane holds (same LM state, its parent node); the lanes without one announce themselves
+       * in the orphan table at the head of the first frame, as in every frame */
+      const int nSt = popc64(leaders);
+      const bool lv = lane < nSt;
+      const uint32_t mySid = L0.lmSid[lv ? lane : 0], myNode = L0.node[lv ? lane : 0], myPar = L0.parent[lv ? lane : 0];
+      int plr = -1;
+      for (int i = 0; i < nSt; ++i) {
+        const uint32_t si = waveReadLane32(mySid, i), ni = waveReadLane32(myNode, i);
+        plr = (lv && myNode != 0u && si == mySid && ni == myPar) ? i : plr;
+      }
+      if (plr >= 0) {
+        L0.link[lane] = (uint32_t)plr + 1u;
+        atomOr64(&L0.cmask[plr], 1ull << (L0.info[lane] & 63u));
+      }
+      if (lane == 0) {
+        S.scal[SL_NSTATE] = (uint32_t)nSt;
+      }
+    }
+  } else {
   if (tid == 0) {
     const XNode r0 = xnode[0];
     S.rootNode = r0;
@@ -276,6 +409,7 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
   if (tid > 0 && tid < K) {
     histPT[hbase + tid] = make_int2((int)kSlNoHyp, -1);
   }
+  }
   float rowA = 0.0f, rowB = 0.0f;
   if (isSvc) {
     const float v0 = (T > 0 && lane < N) ? em[lane] : 0.0f;
@@ -289,7 +423,7 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
   }
   ldsBarrier();
 
-  int nState = 1;
+  int nState = ST ? (int)S.scal[SL_NSTATE] : 1;
   int winShift = kSlCoarseShift, winBase = kSlCoarseBase;
   bool dead = false;
 
@@ -301,7 +435,7 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
     constexpr int role = decltype(RL)::value;
     constexpr bool isTok = role == 0, isSelf = role == 1, isWord = role == 2, isSvc = role == 3;
     const int frameOut = t + 1;
-    const int64_t hrow = hbase + (int64_t)frameOut * K;
+    const int64_t hrow = hbase + (int64_t)(frame0 + frameOut) * K;
     XlLanes& Lp = S.L[p];
     XlLanes& Lq = S.L[q];
     /* ---- phase 1a: own lane, candidates, the merge and orphan tables, the frame's best ------ */
@@ -347,6 +481,22 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
       parB = Lp.b[pi];
       parInfo = Lp.info[pi];
     }
+    /* streams: the emitting-model score of the lane's hypotheses, of its parent lane's, of the candidates this lane
+     * evaluates (blank / stay; word end / blank-then-own-token), and whether the lane is a root that takes no arrival */
+    double amNBv = 0.0, amBv = 0.0, parAmNB = 0.0, parAmB = 0.0, amC0 = 0.0, amC1 = 0.0;
+    bool noArr = false;
+    if constexpr (ST) {
+      if (!isSvc) {
+        amNBv = X.amNB[p][lane];
+        amBv = X.amB[p][lane];
+      }
+      if (isSelf) {
+        parAmNB = X.amNB[p][pl >= 0 ? pl : 0];
+        parAmB = X.amB[p][pl >= 0 ? pl : 0];
+        noArr = (Lp.dPar[lane] >> 31) != 0u;
+      }
+    }
+    const double amM = whichB ? amBv : amNBv;
     FLTX_XLPROF(0);
     double cs[GT];
     int cbin[GT];
@@ -436,17 +586,27 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
       }
       double cR = r0;
       parR = atRoot ? hypM : hypNB;
+      if constexpr (ST) { /* (the winning member's: LexiconDecoder.cpp adds the emission alone to it) */
+        amC0 = amM + eBlank;
+        amC1 = (atRoot ? amM : amNBv) + (atRoot ? eSil : eLast);
+      }
       if (has1 && (r1 > cR || (r1 == cR && h1 < parR))) {
         cR = r1;
         parR = h1;
+        if constexpr (ST) {
+          amC1 = parAmNB + eLast;
+        }
       }
       if (has2 && (r2 > cR || (r2 == cR && h2 < parR))) {
         cR = r2;
         parR = h2;
+        if constexpr (ST) {
+          amC1 = parAmB + eLast;
+        }
       }
       cs[1] = cR;
       cok[1] = live && (has0 || has1 || has2);
-      if (live && atRoot) { /* words ending here this frame join through the merge table */
+      if (live && atRoot && !noArr) { /* words ending here this frame join through the merge table */
         rootSlot = xlRootFind(S, xlKey(Lp.dPar[lane], Lp.dWord[lane]));
         if (rootSlot >= 0) {
           S.root.lane[rootSlot] = (uint32_t)lane + 1u;
@@ -481,8 +641,12 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
       }
       cs[1] = cL;
       cok[1] = live && hasB && extLast && allowLast && ((cm >> last) & 1ull) == 0ull && cL == cL;
+      if constexpr (ST) {
+        amC0 = (useB ? amBv : amM) + eEnd;
+        amC1 = amBv + eLast;
+      }
     }
-    if (waveBallot(rootSlot < 0 && ((isSelf && live && atRoot) || (isWord && cok[0]))) != 0ull) {
+    if (waveBallot(rootSlot < 0 && ((isSelf && live && atRoot && !noArr) || (isWord && cok[0]))) != 0ull) {
       dead = true; /* merge table full: general path (uniform after the barrier below via bestKey = ~0) */
       if (lane == 0) {
         S.bestKey[p] = ~0ull;
@@ -626,6 +790,9 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
       if (rep) {
         S.root.winHyp[rootSlot] = useB ? hypB : hypM;
         S.root.winWord[rootSlot] = endLabel;
+        if constexpr (ST) {
+          X.winAm[rootSlot] = amC0;
+        }
       }
       cok[0] = rep && S.root.lane[rootSlot] == 0u;
       if (LA && cok[0]) {
@@ -844,7 +1011,22 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
       }
       if (isWord && ((selMask[0] >> lane) & 1ull)) {
         /* the LM state's number (memo: the same (LM state, word) gives the same state back) */
-        if (HM) {
+        if constexpr (ST) {
+          /* streams: from the generic engine's table, which outlives the launch and which its begin / prune / end and
+           * the compaction know.  One winner per (LM state, word) slot of the merge table: nobody asks about the same
+           * pair twice in a frame, so the look-up waits for no other lane */
+          bool fresh;
+          if ((uint32_t)(endLabel + 1) >= (1u << 24)) {
+            /* the key holds 24 bits of the word: no look-up, which would enter the pair under another word's key, and
+             * the table outlives the chunk.  The chunk is abandoned, so the state's number (0) is never parked */
+            atomOr32(&S.scal[XL_FLAG], 1u);
+          } else {
+            rootSid = tlStreamChild(P, b, lmSid, endLabel, (uint32_t)(total0 + t + 1), &S.scal[SL_NEXTID], &S.scal[SL_STATUS], fresh);
+            if (S.scal[SL_STATUS] != 0u) { /* table or ids ran out: the chunk is decoded again on the general path */
+              atomOr32(&S.scal[XL_FLAG], 1u);
+            }
+          }
+        } else if (HM) {
           const unsigned long long mkey = ((unsigned long long)(lmSid + 1u) << 24) | (unsigned long long)(uint32_t)(endLabel + 1);
           uint32_t h = xlHash(mkey) & (kXlMemoH - 1);
           bool have = false; /* a number was taken from the counter for this state */
@@ -957,7 +1139,16 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
       }
     };
     /* a new lane on the planned child */
-    auto newChild = [&](int idx, double c, uint32_t hp) {
+    /* streams: a record's scores {score, emitting-model score, LM score (ZeroLM: 0)} for getBestHypothesis(lookBack) */
+    auto scoreRec = [&](int64_t at, double c, double am) {
+      if (P.histS) {
+        double* hs = P.histS + 3 * at;
+        hs[0] = c;
+        hs[1] = am;
+        hs[2] = 0.0;
+      }
+    };
+    auto newChild = [&](int idx, double c, uint32_t hp, double am) {
       const int nl = nSurv + idx;
       const uint32_t hyp = (uint32_t)(nHSurv + idx);
       const int n = planN;
@@ -974,8 +1165,16 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
       Lq.parent[nl] = node;
       Lq.firstChild[nl] = cx.firstChild;
       Lq.endLabel[nl] = cx.endLabel0;
-      Lq.dPar[nl] = 0u;
-      Lq.dWord[nl] = -1;
+      if constexpr (ST) { /* (the (parent id, word) name of the lane's LM state goes along: the park writes it) */
+        Lq.dPar[nl] = Lp.dPar[lane];
+        Lq.dWord[nl] = Lp.dWord[lane];
+        X.amNB[q][nl] = am;
+        X.amB[q][nl] = 0.0;
+        scoreRec(hrow + hyp, c, am);
+      } else {
+        Lq.dPar[nl] = 0u;
+        Lq.dWord[nl] = -1;
+      }
       if (myNewLane >= 0) {
         atomOr64(&Lq.cmask[myNewLane], 1ull << n);
       }
@@ -1015,21 +1214,23 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
           double c = cs[0];
           int mn = myNew[0];
           unsigned long long tbj = tb[0];
+          double ej = ev[0];
 #pragma unroll
           for (int j = 1; j < GT; ++j) {
             c = j == j0 ? cs[j] : c;
             mn = j == j0 ? myNew[j] : mn;
             tbj = j == j0 ? tb[j] : tbj;
+            ej = j == j0 ? ev[j] : ej;
           }
           if (!first) {
             planChild(__builtin_ctzll(tbj | (1ull << 63)));
           }
-          newChild(offW + mn, c, hypM);
+          newChild(offW + mn, c, hypM, ST ? amM + ej : 0.0);
         }
         first = false;
       }
     } else if (isSelf) {
-      if (lane >= nHSurv + nNew && lane < K) { /* unused slots of the history row */
+      if (!ST && lane >= nHSurv + nNew && lane < K) { /* unused slots of the history row (a stream's rows are read up to the parked count) */
         histPT[hrow + lane] = make_int2((int)kSlNoHyp, -1);
       }
       if (surv >= 0) {
@@ -1055,18 +1256,29 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
           if (hp == kSlNoHyp) { /* a word ending on this root beat its own stay */
             hp = S.root.winHyp[rootSlot];
             wd = S.root.winWord[rootSlot];
+            if constexpr (ST) {
+              amC1 = X.winAm[rootSlot];
+            }
           }
           histPT[hrow + hNB] = make_int2((int)hp, atRoot ? sil : last);
           histW[hrow + hNB] = wd;
+          if constexpr (ST) {
+            X.amNB[q][surv] = amC1;
+            scoreRec(hrow + hNB, cs[1], amC1);
+          }
         }
         if (sB) {
           histPT[hrow + hB] = make_int2((int)hypM, blank);
           histW[hrow + hB] = -1;
+          if constexpr (ST) {
+            X.amB[q][surv] = amC0;
+            scoreRec(hrow + hB, cs[0], amC0);
+          }
         }
       }
     } else if (isWord) {
       if ((selMask[1] >> lane) & 1ull) {
-        newChild(offW + myNew[1], cs[1], hypB);
+        newChild(offW + myNew[1], cs[1], hypB, amC1);
       }
       if ((selMask[0] >> lane) & 1ull) { /* a word ended and nobody stood on that root: a new root lane */
         const int nl = nSurv + offW + myNew[0];
@@ -1089,6 +1301,11 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
         Lq.dWord[nl] = endLabel;
         histPT[hrow + hyp] = make_int2((int)hp, endTok);
         histW[hrow + hyp] = endLabel;
+        if constexpr (ST) {
+          X.amNB[q][nl] = amC0;
+          X.amB[q][nl] = 0.0;
+          scoreRec(hrow + hyp, cs[0], amC0);
+        }
         adopt(rootOrph, nl);
       }
     }
@@ -1131,6 +1348,103 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
   /* ---- decodeEnd (LexiconDecoder.cpp:231-274): if any hypothesis stands on the root only those
    * finish; finish() keeps the LM state (ZeroLM), token = sil; the two hypotheses of a lane merge;
    * sorted n-best ---------------------------------------------------------------------------- */
+  if constexpr (ST) {
+    /* ---- park the beam for the next launch / prune / getBestHypothesis / decodeEnd: one slot per hypothesis, sorted by
+     * (score descending, history slot ascending), in the generic engine's format; the last history row rewritten in
+     * that order ------------------------------------------------------------------------------------------------ */
+#ifndef FLTX_EMU
+    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* this wave's history records are in L2 */
+#endif
+    ldsBarrier();
+    const int pe = T & 1;
+    if (wave == 0 && !dead) {
+      const bool live = lane < nState;
+      const int li = live ? lane : 0;
+      const XlLanes& Le = S.L[pe];
+      const double nb = Le.nb[li], bb = Le.b[li];
+      const uint32_t info = Le.info[li];
+      const uint32_t sNB = live ? (info >> 16) & 0xFFu : kSlNoHyp, sB = live ? info >> 24 : kSlNoHyp;
+      const bool hasNB = sNB != kSlNoHyp, hasB = sB != kSlNoHyp;
+      const unsigned long long kNB = hasNB ? f64Key(nb) : 0ull, kB = hasB ? f64Key(bb) : 0ull;
+      int rNB = 0, rB = 0;
+      for (int i = 0; i < nState; ++i) {
+        const unsigned long long k1 = ((unsigned long long)waveReadLane32((uint32_t)(kNB >> 32), i) << 32) |
+                                      waveReadLane32((uint32_t)kNB, i);
+        const unsigned long long k2 = ((unsigned long long)waveReadLane32((uint32_t)(kB >> 32), i) << 32) |
+                                      waveReadLane32((uint32_t)kB, i);
+        const uint32_t s1 = waveReadLane32(sNB, i), s2 = waveReadLane32(sB, i);
+        const bool e1 = s1 != kSlNoHyp, e2 = s2 != kSlNoHyp;
+        rNB += (e1 && (k1 > kNB || (k1 == kNB && s1 < sNB))) ? 1 : 0;
+        rNB += (e2 && (k2 > kNB || (k2 == kNB && s2 < sNB))) ? 1 : 0;
+        rB += (e1 && (k1 > kB || (k1 == kB && s1 < sB))) ? 1 : 0;
+        rB += (e2 && (k2 > kB || (k2 == kB && s2 < sB))) ? 1 : 0;
+      }
+      const int nHyp = popc64(waveBallot(hasNB)) + popc64(waveBallot(hasB));
+      const int64_t hlast = hbase + (int64_t)(frame0 + T) * K;
+      const unsigned long long* hrec = (const unsigned long long*)(histPT + hlast);
+      const unsigned long long recNB = hasNB ? loadCoherent64(hrec + sNB) : 0ull;
+      const unsigned long long recB = hasB ? loadCoherent64(hrec + sB) : 0ull;
+      const int32_t wNB = hasNB ? (int32_t)loadCoherent32((const uint32_t*)(histW + hlast) + sNB) : -1;
+      const int32_t wB = hasB ? (int32_t)loadCoherent32((const uint32_t*)(histW + hlast) + sB) : -1;
+      const double aNB = X.amNB[pe][li], aB = X.amB[pe][li];
+      const uint32_t lastTok = info & 0xFFu; /* (a root lane's is sil: the separator) */
+      const uint32_t sidOut = Le.lmSid[li], sparOut = Le.dPar[li] & 0x7FFFFFFFu;
+      const int32_t edgeOut = Le.dWord[li];
+      const uint32_t lexOut = P.xNew2Old[live ? Le.node[li] : 0u];
+#ifndef FLTX_EMU
+      __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* every lane has its old records before any is rewritten */
+#endif
+      waveSync();
+      auto put = [&](int r, double sc, double am, uint32_t tokpb, unsigned long long rec, int32_t wd) {
+        const size_t g = (size_t)b * K + r;
+        P.gScore[g] = sc;
+        P.gAm[g] = am;
+        P.gLm[g] = 0.0;
+        P.gState[g] = sidOut;
+        P.gSPar[g] = sparOut;
+        P.gSEdge[g] = edgeOut;
+        P.gLex[g] = lexOut;
+        P.gLexMax[g] = 0.0f;
+        P.gTokPb[g] = tokpb;
+        ((unsigned long long*)(histPT + hlast))[r] = rec;
+        histW[hlast + r] = wd;
+        if (P.histS) {
+          double* hs = P.histS + 3 * (hlast + r);
+          hs[0] = sc;
+          hs[1] = am;
+          hs[2] = 0.0;
+        }
+      };
+      if (hasNB) {
+        put(rNB, nb, aNB, lastTok, recNB, wNB);
+      }
+      if (hasB) {
+        put(rB, bb, aB, (uint32_t)blank | kPrevBlank, recB, wB);
+      }
+      if (lane == 0) {
+        const int32_t stNow = P.uttStatus[b] | (int32_t)S.scal[SL_STATUS];
+        P.uttNBeam[b] = nHyp;
+        P.uttFrame[b] = frame0 + T;
+        P.uttTotal[b] = total0 + T;
+        P.uttNextId[b] = (int32_t)S.scal[SL_NEXTID];
+        P.uttStatus[b] = stNow;
+        if (P.statusHost) {
+          P.statusHost[b] = stNow;
+        }
+      }
+    }
+    if (dead && tid == 0) {
+      /* a per-frame table ran full, the select did not converge, or the id table ran out: this chunk cannot be finished
+       * here.  The beam the chunk started from is in the host layer's snapshot; it puts it back and decodes the chunk
+       * again on the general path (the ids named so far stay in the table: they are the ones that pass will name) */
+      const int32_t stNow = P.uttStatus[b] | (int32_t)S.scal[SL_STATUS] | ST_SELECT_FALLBACK;
+      P.uttNextId[b] = (int32_t)S.scal[SL_NEXTID];
+      P.uttStatus[b] = stNow;
+      if (P.statusHost) {
+        P.statusHost[b] = stNow;
+      }
+    }
+  } else {
   const int pe = T & 1;
   const int ff = T + 1;
   if (wave == 0 && !dead) {
@@ -1185,6 +1499,7 @@ FLTX_DEV void xlaneUtterance(const DecodeParams& P, char* smem) {
     P.uttFrame[b] = ff;
     P.uttTotal[b] = ff;
     P.uttStatus[b] = ST_SELECT_FALLBACK;
+  }
   }
   if (PROF && P.prof && tid == P.profThread) {
 #pragma unroll

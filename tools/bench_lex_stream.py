@@ -1,0 +1,101 @@
+"""Lexicon stream chunks: the generic frame loop ("xstream" = 0) against fltx_xlane.h's stream kernel ("xstream" = 1).
+
+The shape bench.py streams as C3 (its workload table: LexiconDecoder + ZeroLM over the 90k-word trie, CTC, N = 29,
+beam 50, token beam 10): --B = 256 streams of --T = 1000 frames in --chunk = 50-frame chunks from host memory,
+stream_prune(0) after every chunk, a buffer of 4 chunks + 8 frames, "stream_total_frames" = T.  The two settings are
+timed alternately in one process, --repeat = 3 times each after one warm-up stream of each; the clock is the host's,
+from stream_begin to a synchronise after stream_end.  One JSON line per run:
+  `xstream`, `chosen` (positions per token wave of the chunks' kernel, 0 = the generic loop), `frames_per_s`, `ms`,
+  `stream_redone`, `nbest_equal` (the final n-best of a seeded sample of streams, compared with the first run of the
+  other setting: must be true)
+and a last line with each setting's median, min and max and the ratio of the medians.
+
+    python tools/bench_lex_stream.py [--B 256] [--T 1000] [--chunk 50] [--repeat 3] [--sample 16]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from text_amd import _capi, synth  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--B", type=int, default=256)
+    ap.add_argument("--T", type=int, default=1000)
+    ap.add_argument("--chunk", type=int, default=50)
+    ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--sample", type=int, default=16)
+    a = ap.parse_args()
+    B, T, CH, N, K, Kt = a.B, a.T, a.chunk, 29, 50, 10
+    lexicon = synth.lexicon()
+    W = len(lexicon[1]) - 1
+    e_host = synth.batch("lexspell", B, T, N, lexicon=lexicon, u0=0)
+    ctx = _capi.Context(device=0)
+    lm = _capi.ZeroLM(ctx)
+    opt = _capi.make_options(K, Kt, 25.0, 0.0, 0.0, float("-inf"), 0.0, False, "ctc")
+    ht = _capi.HostTrie(N, 0)
+    ht.insert_many(lexicon[0], lexicon[1], np.arange(W), np.zeros(W, dtype=np.float32))
+    ht.smear(1)
+    trie = ht.upload(ctx)
+    nchunk = T // CH
+    pieces = [np.ascontiguousarray(e_host[:, k * CH:(k + 1) * CH, :]) for k in range(nchunk)]
+    Tc = np.full(B, CH, dtype=np.int32)
+    sample = sorted(np.random.RandomState(4242).choice(B, min(a.sample, B), replace=False).tolist())
+    decs = {}
+    for x in (0, 1):
+        d = decs[x] = _capi.BatchDecoder(ctx, _capi.LEXICON, opt, lm, 0, N - 1, unk=W, trie=trie)
+        d.set("stream_total_frames", T)
+        d.set("xstream", x)
+
+    def run(x):
+        d = decs[x]
+        ctx.synchronize()
+        t0 = time.perf_counter()
+        d.stream_begin(B, N, 4 * CH + 8)
+        chosen = int(d.get("xstream"))
+        for p in pieces:
+            d.stream_step(p, Tc)
+            d.stream_prune(0)
+        d.stream_end()
+        ctx.synchronize()
+        dt = time.perf_counter() - t0
+        nbest = [[(h.score, list(h.tokens), list(h.words)) for h in d.results(b)] for b in sample]
+        return dt, chosen, int(d.get("stream_redone")), nbest
+
+    first, rates = {}, {0: [], 1: []}
+    for rep in range(a.repeat + 1):  # (the first round warms up: buffers are allocated and code objects loaded in it)
+        for x in (0, 1):
+            dt, chosen, redone, nbest = run(x)
+            first.setdefault(x, nbest)
+            if not rep:
+                continue
+            rates[x].append(B * nchunk * CH / dt)
+            print(json.dumps({"xstream": x, "chosen": chosen, "frames_per_s": rates[x][-1], "ms": dt * 1e3,
+                              "stream_redone": redone, "nbest_equal": nbest == first[1 - x] if (1 - x) in first else None}),
+                  flush=True)
+    med = {x: statistics.median(v) for x, v in rates.items()}
+    print(json.dumps({"config": {"B": B, "T": T, "chunk": CH, "K": K, "Kt": Kt, "N": N, "words": W, "repeat": a.repeat,
+                                 "sample": sample},
+                      "xstream_0": {"median": med[0], "min": min(rates[0]), "max": max(rates[0])},
+                      "xstream_1": {"median": med[1], "min": min(rates[1]), "max": max(rates[1])},
+                      "ratio": med[1] / med[0], "nbest_equal": first[0] == first[1]}), flush=True)
+    for d in decs.values():
+        d.close()
+    trie.close()
+    lm.close()
+    ctx.close()
+    if first[0] != first[1]:
+        raise SystemExit("the two settings' n-best differ")
+
+
+if __name__ == "__main__":
+    main()
