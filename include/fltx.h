@@ -1069,7 +1069,11 @@ FLTX_API int fltx_decoder_profile(fltx_decoder* dec, uint64_t* out);
  * stream's chunks run on the lane = (LM state, trie node) engine where it takes them -- ZeroLM over an unsmeared trie,
  * one word per spelling, CTC, no <unk>, max-merge, beam and tokens up to 64, an optimistic stream; default 0; set before
  * fltx_stream_begin; fltx_decoder_get "xstream" answers the positions per token wave chosen for the open stream, or 0;
- * results are the same bit for bit), "stream_optimistic" (0 = lexicon
+ * results are the same bit for bit), "ystream" (1 = a lexicon stream's chunks run on that engine's variant with the LM
+ * terms where it takes them -- an n-gram word LM over any trie or ZeroLM over a trie with label scores, one word per
+ * spelling, CTC, no <unk>, max-merge, beam up to 128 and tokens up to 64, an optimistic stream; default 0; set before
+ * fltx_stream_begin; fltx_decoder_get "ystream" answers the lane groups chosen for the open stream, or 0; where "xstream"
+ * is set too and takes the stream, it keeps it; results are the same bit for bit), "stream_optimistic" (0 = lexicon
  * streams use the worst-case HBM workspace from the start instead of decoding an overflowing chunk again),
  * "stream_defer" (0 = fltx_stream_step of a lexicon stream waits for its chunk; default: the chunk is launched and whether
  * a stream has to decode it again is looked at by the next call that needs the beam -- the next chunk's upload runs

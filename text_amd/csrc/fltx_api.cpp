@@ -831,6 +831,9 @@ struct fltx_decoder {
    * it): positions per token wave (0 = not used) and threads of the chunks' launch; begin / end / prune / best and a
    * chunk decoded again keep the generic geometry prepare() chose */
   int xstreamAsked = 0, xstream = 0, xstreamThreads = 0;
+  /* ... and, with the LM terms (n-gram word LM and / or smeared trie), on fltx_ylane.h (ST; "ystream" = 1 asks for it): lane
+   * groups (0 = not used), threads and list positions per token wave of the chunks' launch */
+  int ystreamAsked = 0, ystream = 0, ystreamThreads = 0, ystreamTpw = 0, ystreamRounds = 0;
   /* streams of the lexicon decoder on the optimistic geometry (LDS workspace, cut-off generation): a chunk that
    * overflows is decoded again from the saved beam on the general path (HBM workspace) */
   int userStreamOpt = 1;
@@ -2194,6 +2197,8 @@ int fltx_decoder_get(fltx_decoder* d, const char* key, int64_t* value) {
     *value = d->sstream;
   } else if (!strcmp(key, "xstream")) { /* positions per token wave of fltx_xlane.h's stream kernel chosen for the open stream, or 0 */
     *value = d->xstream;
+  } else if (!strcmp(key, "ystream")) { /* lane groups of fltx_ylane.h's stream kernel chosen for the open stream, or 0 */
+    *value = d->ystream;
   } else if (!strcmp(key, "tstream")) { /* 1: the stream's chunks run on the token-LM variant of fltx_slane.h */
     *value = d->tstream;
   } else if (!strcmp(key, "looks_dropped")) { /* defer_check = 2: batches that were overwritten without a look at their statuses */
@@ -2382,6 +2387,10 @@ int fltx_decoder_set(fltx_decoder* d, const char* key, int64_t value) {
     d->xstreamAsked = value ? 1 : 0;
     return FLTX_OK;
   }
+  if (!strcmp(key, "ystream")) { /* 1: a lexicon stream's chunks run on fltx_ylane.h where it takes them (default 0) */
+    d->ystreamAsked = value ? 1 : 0;
+    return FLTX_OK;
+  }
   if (!strcmp(key, "stream_optimistic")) { /* 0: streams of the lexicon decoder start on the worst-case (HBM) workspace */
     d->userStreamOpt = (int)value;
     return FLTX_OK;
@@ -2499,16 +2508,22 @@ struct LaneGeo {
 struct MlaneGeo {
   int threads, gt, ng, gpw, spw;
 };
+struct YstreamGeo {
+  int threads, ng, rounds;
+};
 #define FLTX_GEO2(WW, GG) {WW, GG},
+#define FLTX_GEO3(WW, NG, RR) {WW, NG, RR},
 #define FLTX_GEO5(WW, GG, NG, GPW, SPW) {WW, GG, NG, GPW, SPW},
 static const LaneGeo kSlaneGeo[] = {FLTX_SLANE_GEOS(FLTX_GEO2)};
 static const LaneGeo kSstreamGeo[] = {FLTX_SSTREAM_GEOS(FLTX_GEO2)};
 static const LaneGeo kWlaneGeo[] = {FLTX_WLANE_GEOS(FLTX_GEO2)};
 static const LaneGeo kXlaneGeo[] = {FLTX_XLANE_GEOS(FLTX_GEO2)};
 static const LaneGeo kXstreamGeo[] = {FLTX_XSTREAM_GEOS(FLTX_GEO2)};
+static const YstreamGeo kYstreamGeo[] = {FLTX_YSTREAM_GEOS(FLTX_GEO3)};
 static const MlaneGeo kMlaneGeo[] = {FLTX_MLANE_GEOS(FLTX_GEO5)}; /* "mlane_geo" = row */
 static const MlaneGeo kTmlaneGeo[] = {FLTX_TMLANE_GEOS(FLTX_GEO5)};
 #undef FLTX_GEO2
+#undef FLTX_GEO3
 #undef FLTX_GEO5
 constexpr int kMlaneGeoCount = (int)(sizeof(kMlaneGeo) / sizeof(kMlaneGeo[0]));
 constexpr int kSlaneGeoCount = (int)(sizeof(kSlaneGeo) / sizeof(kSlaneGeo[0]));
@@ -2926,9 +2941,31 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
       }
     }
   }
+  /* ... or, with the LM terms, of fltx_ylane.h (ylaneUtterance<.., ST>), when asked for: an n-gram word LM over any trie or
+   * ZeroLM over a smeared one (LMK = 1), one or two lane groups, and otherwise the terms above.  Where both engines
+   * take the stream fltx_xlane.h keeps it: it has no LM terms to carry.  A geometry covers the token beam by the
+   * offline engine's arithmetic: list positions per token wave, and 64 x groups x positions pairs within a wave's 512 */
+  d->ystream = 0;
+  if (d->ystreamAsked && !d->xstream && d->kind == FLTX_DECODER_LEXICON && !d->offlineCall && d->keepScores && d->streamOpt &&
+      d->recycle && !d->forceGlobalWs && !d->genericAsked && !d->opt.log_add && (d->lm->kind == 0 || d->lm->kind == 1) &&
+      !d->isLmToken && d->trie && d->trie->xOk && !d->trie->xMulti && (d->lm->kind == 1 || !d->trie->xZeroSmear) &&
+      d->trie->xEndTok == d->sil && d->sil != d->blank && d->opt.criterion == FLTX_CRITERION_CTC &&
+      !(d->opt.unk_score > -std::numeric_limits<double>::infinity()) && K <= 128 && N <= 64 && optionsOk) {
+    for (const YstreamGeo& g : kYstreamGeo) {
+      const int nTokWaves = g.threads / 64 - g.ng - 2;
+      const int tpw = (nTok + nTokWaves - 1) / nTokWaves;
+      if (K <= 64 * g.ng && tpw * nTokWaves <= 96 && tpw * 64 * g.ng <= kYlPairs && nTokWaves <= 8) {
+        d->ystream = g.ng;
+        d->ystreamThreads = g.threads;
+        d->ystreamTpw = tpw;
+        d->ystreamRounds = g.rounds;
+        break;
+      }
+    }
+  }
   { /* which eligibility terms kept this call off the lane engines (fltx_decoder_get "why_not_lane") */
     int64_t why = 0;
-    if (!(d->slane || d->xlane || d->ylane || d->sstream || d->xstream)) {
+    if (!(d->slane || d->xlane || d->ylane || d->sstream || d->xstream || d->ystream)) {
       const bool lexi = d->kind == FLTX_DECODER_LEXICON;
       const bool unkOn = d->opt.unk_score > -std::numeric_limits<double>::infinity();
       why |= (N > 64 && (lexi || N > kWlMaxN || nTok > 64)) ? FLTX_WHY_TOKENS : 0; /* (lexicon-free: the token BEAM has to fit, fltx_wlane.h) */
@@ -3184,7 +3221,7 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
     d->cutRecompute = 0;
   }
   /* buffers */
-  if (d->ylane && d->lm->kind == 1 && (d->xlmwordTrie != d->trie || d->xlmwordLm != d->lm)) { /* LM word ids of the lexicon's words */
+  if ((d->ylane || d->ystream) && d->lm->kind == 1 && (d->xlmwordTrie != d->trie || d->xlmwordLm != d->lm)) { /* LM word ids of the lexicon's words */
     const std::vector<int32_t>& el = d->trie->xEndHost;
     std::vector<int32_t> w(el.size());
     for (size_t i = 0; i < el.size(); ++i) { /* KenLM::score: usrToLmIdxMap_, unknown words -> <unk> */
@@ -3380,7 +3417,7 @@ void fillParams(fltx_decoder* d, DecodeParams& P) {
   P.xNew2Old = (d->trie && d->trie->xNew2Old.p) ? d->trie->xNew2Old.as<uint32_t>() : nullptr;
   P.xdelta = (d->trie && d->trie->xdelta.p) ? d->trie->xdelta.as<float>() : nullptr;
   P.xextra = (d->trie && d->trie->xextra.p) ? d->trie->xextra.as<uint32_t>() : nullptr;
-  P.yTpw = d->ylaneTpw;
+  P.yTpw = d->ystream ? d->ystreamTpw : d->ylaneTpw; /* (an open stream's only lane-engine launches are its chunks) */
   P.xlmword = d->xlmword.p ? d->xlmword.as<int32_t>() : nullptr;
   P.ymemo = (((d->ylane || d->xlane) && d->yshare) || (d->tlane && d->mlaneNG > 1)) ? d->ymemo.as<unsigned long long>() : nullptr;
   P.ymemoSlots = d->ymemoSlots;
@@ -3423,7 +3460,7 @@ void fillParams(fltx_decoder* d, DecodeParams& P) {
 
 /* The lane-engine kernels, one entry per (family, variant, geometry) of fltx_engines.h.  The emulator build maps the
  * same entries to the host functions the kernels are made of (tests/emu/fltx_emu_launch.inc). */
-enum LaneFamily { kGeneric, kSlane, kTlane, kSstream, kTstream, kMlane, kTmlane, kWlane, kXlane, kYlane, kXstream };
+enum LaneFamily { kGeneric, kSlane, kTlane, kSstream, kTstream, kMlane, kTmlane, kWlane, kXlane, kYlane, kXstream, kYstream };
 enum { kVarLA = 1, kVarProf = 2, kVarHM = 4, kVarM32 = 8 }; /* logAdd merges, phase clocks, memo in HBM, 32-bit token masks */
 struct LaneKey {
   int fam, var, threads, g[4];
@@ -3467,6 +3504,8 @@ struct LaneKernel {
   FLTX_LK(kXlane, kVarLA | kVarHM, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane<WW, GG, 1, false, true>), (xlaneUtterance<GG, 1, false, true>))
 #define FLTX_LK_XSTREAM(WW, GG) \
   FLTX_LK(kXstream, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane_stream<WW, GG>), (xlaneUtterance<GG, 0, false, false, true>))
+#define FLTX_LK_YSTREAM(WW, NG, RR) \
+  FLTX_LK(kYstream, 0, WW, NG, RR, 0, 0, (fltx_decode_kernel_ylane_stream<WW, NG, RR>), (ylaneUtterance<NG, RR, 1, 0, false, true>))
 #define FLTX_LK_YLANE(WW, NG, RR, HM, LMK) \
   FLTX_LK(kYlane, HM ? kVarHM : 0, WW, NG, RR, LMK, 0, (fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, false>), (ylaneUtterance<NG, RR, LMK, HM, false>))
 #define FLTX_LK_YLANE_PROF(WW, NG, RR, HM, LMK) \
@@ -3474,7 +3513,7 @@ struct LaneKernel {
 static const LaneKernel kLaneKernels[] = {
     FLTX_SLANE_GEOS(FLTX_LK_SLANE) FLTX_TLANE_PROF_GEOS(FLTX_LK_TLANE_PROF) FLTX_SSTREAM_GEOS(FLTX_LK_SSTREAM)
     FLTX_MLANE_GEOS(FLTX_LK_MLANE) FLTX_TMLANE_GEOS(FLTX_LK_TMLANE) FLTX_WLANE_GEOS(FLTX_LK_WLANE)
-    FLTX_XLANE_GEOS(FLTX_LK_XLANE) FLTX_XSTREAM_GEOS(FLTX_LK_XSTREAM) FLTX_YLANE_KERNELS(FLTX_LK_YLANE) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_LK_YLANE_PROF)};
+    FLTX_XLANE_GEOS(FLTX_LK_XLANE) FLTX_XSTREAM_GEOS(FLTX_LK_XSTREAM) FLTX_YSTREAM_GEOS(FLTX_LK_YSTREAM) FLTX_YLANE_KERNELS(FLTX_LK_YLANE) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_LK_YLANE_PROF)};
 #undef FLTX_LK
 #undef FLTX_LK_SLANE
 #undef FLTX_LK_TLANE_PROF
@@ -3484,15 +3523,18 @@ static const LaneKernel kLaneKernels[] = {
 #undef FLTX_LK_WLANE
 #undef FLTX_LK_XLANE
 #undef FLTX_LK_XSTREAM
+#undef FLTX_LK_YSTREAM
 #undef FLTX_LK_YLANE
 #undef FLTX_LK_YLANE_PROF
 
 /* what launchDecode runs: the lane engine's family, variant and geometry (kGeneric: the per-W kernels) */
 LaneKey laneKeyOf(const fltx_decoder* d) {
-  const int W = d->sstreamLaunch ? (d->xstream ? d->xstreamThreads : d->sstreamThreads) : d->threads;
+  const int W = d->sstreamLaunch ? (d->xstream ? d->xstreamThreads : (d->ystream ? d->ystreamThreads : d->sstreamThreads)) : d->threads;
   const int la = d->opt.log_add ? kVarLA : 0, prof = d->profile ? kVarProf : 0, hm = d->yshare ? kVarHM : 0;
   if (d->sstreamLaunch && d->xstream) {
     return {kXstream, 0, W, {d->xstream, 0, 0, 0}};
+  } else if (d->sstreamLaunch && d->ystream) {
+    return {kYstream, 0, W, {d->ystream, d->ystreamRounds, 0, 0}};
   } else if (d->sstreamLaunch) {
     return {d->tstream ? kTstream : kSstream, prof, W, {d->sstream, 0, 0, 0}};
   } else if (d->ylane) { /* (logAdd: LMK bit 3) */
@@ -3530,6 +3572,11 @@ size_t launchLds(const fltx_decoder* d, const LaneKey& k) {
     return sizeof(TlaneLds) + (size_t)(k.threads / 64) * kTlGatherBytes;
   } else if (k.fam == kXstream) { /* (the stream members take the LM-state memo's place) */
     return offsetof(XlaneLds, memo) + sizeof(XlStreamLds);
+  } else if (k.fam == kYstream) {
+    /* YlaneLds up to the part of pscore the geometry's token waves use, then the stream members (no LM-state memo):
+     * 82 KB with five token waves (512 threads, one lane group), 88 KB with eight (768, two); next to kXstream's 31 KB */
+    static_assert(offsetof(YlaneLds, pscore) + 8 * 512 * sizeof(float) + sizeof(YlStreamLds) <= 160 * 1024, "one CU's LDS");
+    return offsetof(YlaneLds, pscore) + (size_t)(k.threads / 64 - k.g[0] - 2) * 512 * sizeof(float) + sizeof(YlStreamLds);
   }
   return (k.fam == kGeneric && !d->wsInLds) ? d->hotBytes : d->wsBytes;
 }
@@ -4117,7 +4164,8 @@ int streamRedoFlagged(fltx_decoder* d) {
      * says ST_SELECT_FALLBACK.  While d->xstream is set every chunk of the stream is launched on that engine and no
      * other stream path raises this status, so the choice stands for "the launch that wrote the status"; a path that
      * comes to raise it for another reason needs a test of its own here) */
-    if (status[b] & (ST_CAND_OVERFLOW | ST_CUT_RETRY | (d->xstream ? ST_SELECT_FALLBACK : 0))) {
+    /* (... and likewise a chunk fltx_ylane.h's stream variant could not finish, while d->ystream is set) */
+    if (status[b] & (ST_CAND_OVERFLOW | ST_CUT_RETRY | ((d->xstream || d->ystream) ? ST_SELECT_FALLBACK : 0))) {
       again.push_back(b);
     }
   }
@@ -4956,7 +5004,7 @@ int fltx_stream_step(fltx_decoder* d, const float* emissions, int32_t onDevice, 
   if (d->streamOpt && (rc = streamSnapshot(d, 0, nullptr, d->B))) {
     return rc;
   }
-  d->sstreamLaunch = d->sstream != 0 || d->xstream != 0;
+  d->sstreamLaunch = d->sstream != 0 || d->xstream != 0 || d->ystream != 0;
   rc = d->lm->kind == 2 ? hostLmFrames(d, P, T) : launchDecode(d, P);
   d->sstreamLaunch = false;
   if (rc) {

@@ -65,6 +65,12 @@
 #define FLTX_YLMK_PLAIN(W, NG, R, HM, K) \
   FLTX_YLMK_01(W, NG, R, HM, K) FLTX_YLMK_23(W, NG, R, HM, K) FLTX_YLMK_89(W, NG, R, HM, K) FLTX_YLMK_1011(W, NG, R, HM, K)
 #define FLTX_YLMK_MULTI(W, NG, R, HM, K) FLTX_YLMK_57(W, NG, R, HM, K) FLTX_YLMK_1315(W, NG, R, HM, K)
-/* every compiled fltx_ylane.h kernel: K(threads, groups, rounds, memo in HBM, LMK) */
+/* ... a lexicon stream's chunks with the LM terms (ylane_stream): X(threads, lane groups, rounds), in order of preference.
+ * These are the offline engine's one-workgroup-per-CU geometries.  No 512-thread geometry is offered for sharing a CU
+ * when the streams outnumber the CUs: the stream members (4 KB) put one lane group at 82 KB of LDS, and two workgroups
+ * need 80 KB each (fltx_ylane.h YlStreamLds) */
+#define FLTX_YSTREAM_GEOS(X) X(512, 1, 2) X(768, 2, 4)
+
+/* every compiled offline fltx_ylane.h kernel: K(threads, groups, rounds, memo in HBM, LMK) */
 #define FLTX_YLANE_KERNELS(K) \
   FLTX_YLANE_GEOS(FLTX_YLMK_PLAIN, K) FLTX_YLANE4_GEOS(FLTX_YLMK_PLAIN, K) FLTX_YLANE_MULTI_GEOS(FLTX_YLMK_MULTI, K)

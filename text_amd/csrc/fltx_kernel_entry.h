@@ -116,6 +116,15 @@ __global__ void __launch_bounds__(W, (HM && !(LMK & 4)) ? 4 : 1) fltx_decode_ker
   extern __shared__ __attribute__((aligned(16))) char fltx_smem[];
   ylaneUtterance<NG, R, LMK, HM, PROF>(P, fltx_smem);
 }
+/* ... the frames of one decodeStep chunk of a lexicon stream with the LM terms (n-gram word LM and / or smeared trie) on
+ * that engine: beam in and out in the generic engine's parked format, LM-state ids and n-gram contexts in its tables; its
+ * kernels do decodeBegin / decodeEnd / prune / getBestHypothesis.  No LM-state memo: 82 KB of LDS at 512 threads (one lane
+ * group), 88 KB at 768 (two) -- one workgroup per CU, which may take all the registers its waves can address */
+template <int W, int NG, int R>
+__global__ void __launch_bounds__(W, 1) fltx_decode_kernel_ylane_stream(DecodeParams P) {
+  extern __shared__ __attribute__((aligned(16))) char fltx_smem[];
+  ylaneUtterance<NG, R, 1, 0, false, true>(P, fltx_smem);
+}
 template <int W>
 __global__ void __launch_bounds__(W) fltx_decode_kernel_gwslean(DecodeParams P) { /* streaming lean step, HBM workspace */
   extern __shared__ __attribute__((aligned(16))) char fltx_hot[]; /* histogram & block scalars stay in LDS */

@@ -153,7 +153,24 @@ struct YlaneLdsT {
 };
 using YlaneLds = YlaneLdsT<2>; /* one and two lane groups */
 
-enum { YL_FLAG = 15, YL_NICE = 14, YL_WHYCODE = 13 };
+/* Stream chunks (ST): what only a stream carries.  The LM-state memo does not exist -- states are named through the generic
+ * engine's id table in HBM (tlStreamChild) -- so these members stand behind the part of YlaneLds::pscore the geometry's
+ * token waves use (512 floats each), and the launch takes offsetof(YlaneLds, pscore) + token waves * 2 KB +
+ * sizeof(YlStreamLds) bytes: 82 KB at 512 threads (five token waves), 88 KB at 768 (eight) -- one workgroup per CU
+ * either way (the offline 512-thread kernel that shares a CU has 1.9 KB to spare under 80 KB; these 4 KB do not fit
+ * there, so no stream geometry is offered for sharing).  YlaneLds stays the layout the offline kernels know. */
+struct YlStreamLds {
+  double amNB[128], amB[128]; /* emitting-model score of a lane's two hypotheses (the offline engine leaves it to the back-trace) */
+  double winAm[256];          /* merge table: the winner's, next to winHyp / winWord / winLm */
+};
+/* ... and what restore and park need before the first and after the last frame, in the place of the decodeEnd members
+ * (endKey .. endHyp), which a stream does not use: one entry per parked slot (restore) / per hypothesis of a lane (park) */
+struct YlParkLds {
+  unsigned long long key[256]; /* restore: LM state << 32 | node of slot i; park: score key of lane i / 2's nb (even) and b (odd) */
+  uint32_t slot[256];          /* restore: the first slot with the same key; park: the hypothesis's history slot */
+};
+
+enum { YL_FLAG = 15, YL_NICE = 14, YL_WHYCODE = 13, YL_NPARK = 6 };
 
 template <typename LDS>
 FLTX_DEV int ylRootFind(LDS& S, unsigned long long key) {
@@ -254,8 +271,14 @@ FLTX_DEV uint32_t ylLmWord(const DecodeParams& P, int usr) {
  * unsmeared lexicon (every LM term is zero and left out), 1: smeared trie and / or n-gram LM;
  * HM = 1: the LM-state memo lives in HBM and, with two lane groups, four token waves list twice the
  * pairs each (512 threads: two workgroups share a CU) */
-template <int NG, int R, int LMK, int HM, bool PROF>
+/* ST: the frames of one decodeStep chunk of a LexiconDecoder stream, as in fltx_xlane.h: the beam comes from the slots the
+ * last launch (or the generic engine's begin / prune) parked and goes back there in that engine's format; LM states are
+ * named through that engine's (epoch, parent id, word) -> id table and keep their n-gram context in its stateCtx rows;
+ * history rows are its plain records.  Every lane carries the emitting-model score of its two hypotheses and the
+ * (parent id, word) name of its LM state (dPar / dWord, on every lane: the park writes it). */
+template <int NG, int R, int LMK, int HM, bool PROF, bool ST = false>
 FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
+  static_assert(!ST || (LMK == 1 && HM == 0 && NG <= 2), "streams: the LM terms, CTC, max-merge, one word per spelling, no memo");
   /* LMK: bit 0 = the LM terms (smeared trie and / or n-gram LM), bit 1 = ASG criterion (no blank; transitions[n * N + previous
    * token] enters the emitting-model score from the second frame on, LexiconDecoder.cpp:69-72,172-175) */
   constexpr int LMT = LMK & 1;
@@ -340,6 +363,21 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
   unsigned long long acc[8] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull};
   unsigned long long tPrev = devClock();
   uint32_t nScored = 0u;
+  /* (ST only) the stream members behind the token waves' part of pscore; restore / park scratch over the decodeEnd members */
+  YlStreamLds& X = *(YlStreamLds*)(smem + (ST ? offsetof(LDS, pscore) + (size_t)nTok * 512 * sizeof(float) : 0));
+  YlParkLds& Y = *(YlParkLds*)(smem + (ST ? offsetof(LDS, endKey) : 0));
+  static_assert(!ST || sizeof(YlParkLds) <= offsetof(LDS, rootAcc) - offsetof(LDS, endKey), "the scratch fits the decodeEnd members");
+  static_assert(!ST || (2 * kYlLanes <= 256 && kYlRoot <= 256), "YlStreamLds / YlParkLds are sized for two lane groups");
+  const int frame0 = ST ? P.uttFrame[b] : 0; /* streams: rows already in the buffer */
+  const int total0 = ST ? P.uttTotal[b] : 0; /* ... frames decoded since decodeBegin */
+  if constexpr (ST) {
+    if (T == 0) { /* no frames for this stream in this chunk: its parked beam, counters and history stay as they are */
+      if (tid == 0 && P.statusHost) {
+        P.statusHost[b] = P.uttStatus[b];
+      }
+      return;
+    }
+  }
 
   /* ---- decodeBegin (LexiconDecoder.cpp:21-30): the start state at the root ------------- */
   for (int i = tid; i < 2 * kYlLanes; i += W) {
@@ -373,8 +411,10 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
   uint16_t* const candW = &S.cand[0][0] + (size_t)wave * PAIRS; /* (token waves: wave < 8, or < 4 with twice the pairs) */
   constexpr int PC = LG > 2 ? 0 : 512; /* pairs of a token wave whose score is kept in LDS while the wave ranks them */
   float* const pcW = S.pscore + (size_t)(LG > 2 ? 0 : wave) * PC;
-  for (int i = tid; i < memoSlots; i += W) {
-    memo[i] = 0ull; /* (HBM: at L2 before the barrier below, where the word wave's atomics will find it) */
+  if constexpr (!ST) { /* (a stream has no memo: its place in LDS is not part of the launch) */
+    for (int i = tid; i < memoSlots; i += W) {
+      memo[i] = 0ull; /* (HBM: at L2 before the barrier below, where the word wave's atomics will find it) */
+    }
   }
   if (tid < 32) {
     S.off[tid] = 0u;
@@ -385,6 +425,169 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
   if (tid < kYlMaxGroups + 4) {
     S.offH[tid] = 0u;
   }
+  if constexpr (ST) {
+    /* ---- restore: the beam parked by the last launch (sorted slots, one hypothesis each; a slot's number is its
+     * hypothesis's slot in the last history row) -> lanes, one per (LM state, trie node) pair, in the slots 0 .. lanes - 1.
+     * Wave 0 restores, two slots per thread with two lane groups (once per chunk: the other waves have the row to
+     * stage or nothing to do); it speaks to itself through LDS (waveSync), and the barrier in front of the frame
+     * loop hands the lanes to everybody.  The frame loop reads alive[0], cmask[0] and the lanes; nFree / freeList / surv /
+     * offH are written by every frame before it reads them. */
+    if (tid == 0) {
+      const XNode r0 = xnode[0];
+      S.rootNode = r0;
+      S.rootWord = (ngram && r0.endLabel0 >= 0) ? (int32_t)ylLmWord(P, r0.endLabel0) : -1;
+#pragma unroll
+      for (int g = 0; g < LG; ++g) {
+        S.alive[0][g] = 0ull;
+        S.alive[1][g] = 0ull;
+      }
+      S.row[0].nev = 0u;
+      S.row[1].nev = 0u;
+      S.row[0].dead = 0u;
+      S.row[1].dead = 0u;
+      S.bestKey[0] = 0ull;
+      S.bestKey[1] = 0ull;
+      S.lb[0] = 0ull;
+      S.lb[1] = 0ull;
+      S.lmNext = 0u;
+    }
+    ldsBarrier(); /* (the wipes above: cmask and scal[] are written below) */
+    if (tid == 0) {
+      S.scal[SL_NEXTID] = (uint32_t)P.uttNextId[b];
+    }
+    if (wave == 0) {
+      const int nB0 = P.uttNBeam[b];
+      const int nB = nB0 < 64 * NG ? nB0 : 64 * NG; /* (prepare(): K <= 64 * NG) */
+      uint32_t sidR[NG], ndR[NG];
+#pragma unroll
+      for (int r = 0; r < NG; ++r) {
+        const int i = r * 64 + lane;
+        const bool valid = i < nB;
+        const size_t g = (size_t)b * K + (valid ? i : 0);
+        /* (gLex is the node's id in the trie as uploaded; the lanes and XNode speak the breadth-first one) */
+        sidR[r] = valid ? P.gState[g] : 0xFFFFFFFFu;
+        ndR[r] = valid ? P.xOld2New[P.gLex[g]] : 0xFFFFFFFFu;
+        Y.key[i] = ((unsigned long long)sidR[r] << 32) | ndR[r];
+      }
+      waveSync();
+      int lead[NG], ln[NG];
+#pragma unroll
+      for (int r = 0; r < NG; ++r) {
+        const int i = r * 64 + lane;
+        const unsigned long long mine = Y.key[i];
+        lead[r] = i;
+        for (int j = nB - 1; j >= 0; --j) {
+          lead[r] = (Y.key[j] == mine && j < i) ? j : lead[r];
+        }
+        Y.slot[i] = (uint32_t)lead[r];
+      }
+      waveSync();
+      int nLanes = 0;
+#pragma unroll
+      for (int r = 0; r < NG; ++r) {
+        ln[r] = 0;
+      }
+      for (int j = 0; j < nB; ++j) {
+        const int isL = Y.slot[j] == (uint32_t)j ? 1 : 0;
+        nLanes += isL;
+#pragma unroll
+        for (int r = 0; r < NG; ++r) {
+          ln[r] += (j < lead[r]) ? isL : 0;
+        }
+      }
+#pragma unroll
+      for (int r = 0; r < NG; ++r) {
+        const int i = r * 64 + lane;
+        if (i < nB && lead[r] == i) {
+          const int x = ln[r];
+          const uint32_t sid = sidR[r], nd = ndR[r];
+          const size_t g = (size_t)b * K + i;
+          const XNode xn = xnode[nd]; /* one 32-byte gather */
+          /* the node's own token (a lane that holds only its `b` hypothesis has it in no slot): children are laid out in
+           * token order, so it is the token of the (node - firstChild)-th set bit of the parent's child mask */
+          uint32_t tok = (uint32_t)sil;
+          if (nd != 0u) {
+            const XNode px = xnode[xn.parent];
+            unsigned long long mm = px.childMask;
+            for (uint32_t k = nd - px.firstChild; k > 0u; --k) {
+              mm &= mm - 1ull;
+            }
+            tok = (uint32_t)__builtin_ctzll(mm | (1ull << 63));
+          }
+          /* The root lane of an LM state takes the words that end on it: arrivals from the state gSPar with the word
+           * gSEdge.  The start state and a state whose parent a compaction has cut loose take none, and say so in
+           * bit 31 (no state id has it): the number left in gSPar is stale and may since have been given to another state
+           * (fltx_xlane.h's restore has the argument in full). */
+          const bool noArr = sid == 0u || P.idPar[(size_t)b * P.idCap + sid] == kNoParent32;
+          L.nb[x] = NEG;
+          L.b[x] = NEG;
+          L.lmNB[x] = 0.0;
+          L.lmB[x] = 0.0;
+          X.amNB[x] = 0.0;
+          X.amB[x] = 0.0;
+          L.childMask[x] = xn.childMask;
+          L.kidsMask[x] = xn.kidsMask;
+          L.info[x] = mkInfo(tok, kNoHyp, kNoHyp);
+          L.link[x] = 0u;
+          L.lmSid[x] = sid;
+          L.node[x] = nd;
+          L.parent[x] = xn.parent;
+          L.firstChild[x] = xn.firstChild;
+          L.endLabel[x] = xn.endLabel0;
+          L.dPar[x] = P.gSPar[g] | (noArr ? 0x80000000u : 0u);
+          L.dWord[x] = P.gSEdge[g];
+          L.maxScore[x] = xn.maxScore;
+          L.delta[x] = nd != 0u ? xdelta[nd] : 0.0f; /* (the smearing difference to its parent, as a new lane gets it) */
+          L.endLm[x] = kYlNoLm; /* the word's n-gram score and endCtx: asked again in the chunk's first frame (lmReq) */
+          L.endWord[x] = ngram ? (nd != 0u ? P.xlmword[nd] : S.rootWord) : -1;
+        }
+      }
+      waveSync();
+#pragma unroll
+      for (int r = 0; r < NG; ++r) { /* (the two hypotheses of a lane write different bytes of its info word) */
+        const int i = r * 64 + lane;
+        if (i < nB) {
+          const int x = ln[r];
+          const size_t g = (size_t)b * K + i;
+          if ((P.gTokPb[g] & kPrevBlank) != 0u) {
+            L.b[x] = P.gScore[g];
+            L.lmB[x] = P.gLm[g];
+            X.amB[x] = P.gAm[g];
+            ((volatile uint8_t*)&L.info[x])[3] = (uint8_t)i;
+          } else {
+            L.nb[x] = P.gScore[g];
+            L.lmNB[x] = P.gLm[g];
+            X.amNB[x] = P.gAm[g];
+            ((volatile uint8_t*)&L.info[x])[2] = (uint8_t)i;
+          }
+        }
+      }
+      waveSync();
+      /* links: a lane's parent lane holds (same LM state, its parent node); the lanes without one announce themselves in
+       * the orphan table at the head of the first frame, as in every frame (at most 64 * NG lanes for its 128 * LG slots:
+       * ylOrphAdd / ylOrphFind always meet a free slot, restored beam or not) */
+#pragma unroll
+      for (int r = 0; r < NG; ++r) {
+        const int x = r * 64 + lane;
+        const bool lv = x < nLanes;
+        const uint32_t mySid = L.lmSid[lv ? x : 0], myNode = L.node[lv ? x : 0], myPar = L.parent[lv ? x : 0];
+        int plr = -1;
+        for (int j = 0; j < nLanes; ++j) {
+          plr = (lv && myNode != 0u && L.lmSid[j] == mySid && L.node[j] == myPar) ? j : plr;
+        }
+        if (plr >= 0) {
+          L.link[x] = (uint32_t)plr + 1u;
+          atomOr64(&S.cmask[0][plr], 1ull << (L.info[x] & 63u));
+        }
+      }
+      if (lane == 0) {
+        S.alive[0][0] = nLanes >= 64 ? ~0ull : ((1ull << nLanes) - 1ull);
+        if (NG > 1) {
+          S.alive[0][NG - 1] = nLanes > 64 ? (nLanes >= 128 ? ~0ull : ((1ull << (nLanes - 64)) - 1ull)) : 0ull;
+        }
+      }
+    }
+  } else {
   if (tid == 0) {
     const XNode r0 = xnode[0];
     S.rootNode = r0;
@@ -444,6 +647,7 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
   if (tid > 0 && tid < K) {
     histPT[hbase + tid] = make_int2((int)kNoHyp, -1);
   }
+  }
   float rowA = 0.0f, rowB = 0.0f;
   if (isSvc) {
     const float v0 = (T > 0 && lane < N) ? em[lane] : 0.0f;
@@ -470,7 +674,7 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
     constexpr bool isTok = role == 0, isSelf = role == 1, isWord = role == 2, isSvc = role == 3;
     constexpr int NS = (isWord && NW > NS0) ? NW : NS0; /* candidate slots of a thread (the word wave's further words: its own count) */
     const int frameOut = t + 1;
-    const int64_t hrow = hbase + (int64_t)frameOut * K;
+    const int64_t hrow = hbase + (int64_t)(frame0 + frameOut) * K;
     /* ---- phase 1a: candidates, the merge table, the frame's best --------------------------- */
     const int silPos = S.row[p].silPos;
     const unsigned long long allow = S.row[p].allow;
@@ -492,6 +696,18 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
     float cdl[NS];      /* ... and its smearing difference */
     uint32_t cpl[NS];   /* LM state of the lane the candidate comes from */
     uint32_t cpn[NS];   /* its node (word wave, even slots: the word) */
+    /* streams: the candidate's emitting-model score (its source's + the emission alone, LexiconDecoder.cpp), and the
+     * (parent id, word) name of the source lane's LM state -- like cpl / cpn kept from before the build, in which the
+     * source's slot may be taken again */
+    double cam[ST ? NS : 1];
+    uint32_t cdp[ST ? NS : 1];
+    int32_t cdw[ST ? NS : 1];
+#pragma unroll
+    for (int j = 0; j < (ST ? NS : 1); ++j) {
+      cam[j] = 0.0;
+      cdp[j] = 0u;
+      cdw[j] = -1;
+    }
 #pragma unroll
     for (int j = 0; j < NS; ++j) {
       cs[j] = NEG;
@@ -511,6 +727,8 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
     int last = 0, pl = -1, rootSlot = -1;
     bool whichB = false;
     double lmR = 0.0; /* LM score of the winning member of the stay group */
+    double amC0 = 0.0, amC1 = 0.0; /* streams, self waves: emitting-model score of the lane's blank and stay candidates */
+    bool noArr = false;            /* ... a root lane that takes no arrival (see the restore) */
     /* logAdd, self waves: the members of the lane's blank and stay groups besides the best one */
     double laBlankO = NEG, laR0 = NEG, laR0o = NEG, laR1 = NEG, laR2 = NEG;
     /* word wave, per slot (a lane group's lane, or the thread's further word) */
@@ -595,6 +813,11 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
         cs[g] = cL;
         cok[g] = go && cL == cL;
         cinf[g] = (uint32_t)x | ((uint32_t)xl << 9) | (xhB << 16);
+        if constexpr (ST) {
+          cam[g] = X.amB[x] + S.eAll[p][xl];
+          cdp[g] = L.dPar[x];
+          cdw[g] = L.dWord[x];
+        }
       }
     } else if (isTok) {
       /* the (lane, token) pairs with a child that has children and no lane of its own yet, the
@@ -877,6 +1100,11 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
           if constexpr (LA) {
             coth[r] = co;
           }
+          if constexpr (ST) {
+            cam[r] = (wb ? X.amB[x] : X.amNB[x]) + ev;
+            cdp[r] = L.dPar[x];
+            cdw[r] = L.dWord[x];
+          }
           cok[r] = valid && c == c;
         }
       }
@@ -911,6 +1139,15 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
       }
       lmM = whichB ? lmBv : lmNBv;
       lmOwnNB = lmNBv;
+      double amNBv = 0.0, amBv = 0.0, parAmNB = 0.0, parAmB = 0.0;
+      if constexpr (ST) {
+        amNBv = X.amNB[li];
+        amBv = X.amB[li];
+        parAmNB = X.amNB[pi];
+        parAmB = X.amB[pi];
+        noArr = (L.dPar[li] >> 31) != 0u;
+      }
+      const double amM = whichB ? amBv : amNBv;
       const double eBlank = S.eAll[p][ASG ? 0 : blank], eLast = S.eAll[p][last], eSil = S.eAll[p][sil];
       /* blank (:197-213): always tried */
       cs[0] = m + eBlank;
@@ -952,20 +1189,30 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
       double cR = r0;
       parR = atRoot ? hypM : hypNB;
       lmR = atRoot ? lmM : lmNBv;
+      if constexpr (ST) { /* (the winning member's: the emission alone is added to it) */
+        amC0 = amM + eBlank;
+        amC1 = (atRoot ? amM : amNBv) + (atRoot ? eSil : eLast);
+      }
       if (has1 && (r1 > cR || (r1 == cR && h1 < parR))) {
         cR = r1;
         parR = h1;
         lmR = parLmNB + dl;
+        if constexpr (ST) {
+          amC1 = parAmNB + eLast;
+        }
       }
       if (has2 && (r2 > cR || (r2 == cR && h2 < parR))) {
         cR = r2;
         parR = h2;
         lmR = parLmB + dl;
+        if constexpr (ST) {
+          amC1 = parAmB + eLast;
+        }
       }
       cs[1] = cR;
       clm[1] = lmR;
       cok[1] = live && (has0 || has1 || has2);
-      if (live && atRoot) { /* words ending here this frame join through the merge table */
+      if (live && atRoot && !noArr) { /* words ending here this frame join through the merge table */
         rootSlot = ylRootFind(S, xlKey(L.dPar[li], L.dWord[li]));
         if (rootSlot >= 0) {
           S.root.lane[rootSlot] = (uint32_t)li + 1u;
@@ -1050,6 +1297,9 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
           coth[g] = (co + lmWeight * (double)lmS) + wordScore;
         }
         clm[g] = srcLm + (double)lmS;
+        if constexpr (ST) {
+          cam[g] = (useB || wb ? X.amB[x] : X.amNB[x]) + eEnd;
+        }
         cok[g] = can && c == c;
         cinf[g] = (useB ? xhB : (wb ? xhB : xhNB)) << 16;
         cpl[g] = xlm;
@@ -1150,7 +1400,7 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
       }
     }
     {
-      bool full = isSelf && live && atRoot && rootSlot < 0;
+      bool full = isSelf && live && atRoot && !noArr && rootSlot < 0;
 #pragma unroll
       for (int g = 0; g < NW; ++g) {
         full = full || (isWord && cok[g] && wSlot[g] < 0);
@@ -1283,6 +1533,9 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
           S.root.winHyp[sl] = wUseB[g] ? wHypB[g] : wHypM[g];
           S.root.winWord[sl] = (int32_t)cpn[g];
           S.root.winLm[sl] = clm[g];
+          if constexpr (ST) {
+            X.winAm[sl] = cam[g];
+          }
         }
         cok[g] = rep && S.root.lane[sl] == 0u;
         if (LA && cok[g]) {
@@ -1475,6 +1728,9 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
     }
     uint32_t planLm = 0u, planPar = 0u, planExtra = 0u;
     int32_t planWord = -1;
+    double planAm = 0.0;  /* streams: the planned candidate's emitting-model score and its LM state's name */
+    uint32_t planDp = 0u;
+    int32_t planDw = -1;
     /* (reads nothing of the lanes: a slot whose lane drops out this frame is taken again in the same build) */
     auto planChild = [&](int j) {
       uint32_t cn = cnode[0];
@@ -1485,6 +1741,17 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
         cn = i == j ? cnode[i] : cn;
         planLm = i == j ? cpl[i] : planLm;
         planPar = i == j ? cpn[i] : planPar;
+      }
+      if constexpr (ST) {
+        planAm = cam[0];
+        planDp = cdp[0];
+        planDw = cdw[0];
+#pragma unroll
+        for (int i = 1; i < NS; ++i) {
+          planAm = i == j ? cam[i] : planAm;
+          planDp = i == j ? cdp[i] : planDp;
+          planDw = i == j ? cdw[i] : planDw;
+        }
       }
       planSlot = j;
       planX = xnode[cn];
@@ -1538,7 +1805,42 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
               const int x = further ? (int)(S.xEmit[ar - NG * 64] & 0xFFu) : ar;
               const uint32_t xlm = L.lmSid[x];
               const int32_t el = further ? S.xLabel[ar - NG * 64] : L.endLabel[x];
-              const unsigned long long mkey = ((unsigned long long)(xlm + 1u) << 24) | (unsigned long long)(uint32_t)(el + 1);
+              if constexpr (ST) {
+                /* streams: from the generic engine's table, which outlives the launch and which its begin / prune / end
+                 * and the compaction know.  nrList holds the arrivals that were selected as new root lanes: cok[] of
+                 * such an arrival says it is the one representative (minLane) of its merge-table slot, and a slot is one
+                 * (LM state, word) pair -- so nobody asks about the same pair twice in a frame, as tlStreamChild assumes,
+                 * and the look-up waits for no other lane.  State numbers are 32 bits wide here throughout (nrSid, lmSid,
+                 * cpl, xlKey): the 16-bit packing belongs to the offline memo, which this variant does not have. */
+                uint32_t sid = 0u;
+                if ((uint32_t)(el + 1) >= (1u << 24)) {
+                  /* the key holds 24 bits of the word: no look-up, which would enter the pair under another word's key in
+                   * a table that outlives the chunk.  The chunk is abandoned, so the number (0) is never parked */
+                  atomOr32(&S.scal[YL_FLAG], 1u);
+                } else {
+                  bool fresh;
+                  sid = tlStreamChild(P, b, xlm, el, (uint32_t)(total0 + t + 1), &S.scal[SL_NEXTID], &S.scal[SL_STATUS], fresh);
+                  if (S.scal[SL_STATUS] != 0u) { /* table or ids ran out: the chunk is decoded again on the general path */
+                    atomOr32(&S.scal[YL_FLAG], 1u);
+                  } else if (fresh && ngram) {
+                    /* a new state -- or a number the compaction recycled, whose row is stale: its n-gram context, kept
+                     * with the lane since the look-up.  (Not fresh: the generic engine or an earlier chunk wrote the row) */
+                    const int Lc = P.lmOrder - 1;
+                    int32_t* dst = P.stateCtx + ((size_t)b * P.stateCap + sid) * Lc;
+#pragma unroll
+                    for (int k = 0; k < kMaxNgramOrder - 1; ++k) {
+                      if (k < Lc) {
+                        dst[k] = L.endCtx[k][x];
+                      }
+                    }
+                    wroteCtx = true;
+                  }
+                }
+                S.nrSid[ar] = sid;
+                S.nrOrph[ar] = (int16_t)ylOrphFind(S.orph[p], xlKey(sid, 0));
+                continue;
+              }
+              const unsigned long long mkey =((unsigned long long)(xlm + 1u) << 24) | (unsigned long long)(uint32_t)(el + 1);
               uint32_t h = xlHash(mkey) & memoMask;
               uint32_t sid = 0u;
               bool have = false; /* a number was taken from the counter for this state */
@@ -1687,6 +1989,15 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
         atomOr64(&S.cmask[q][nl], toks);
       }
     };
+    /* streams: a record's scores {score, emitting-model score, LM score} for getBestHypothesis(lookBack) */
+    auto scoreRec = [&](int64_t at, double c, double am, double lmv) {
+      if (P.histS) {
+        double* hs = P.histS + 3 * at;
+        hs[0] = c;
+        hs[1] = am;
+        hs[2] = lmv;
+      }
+    };
     /* a new lane on the planned child */
     auto newChild = [&](int idx, double c, double lmc, uint32_t ci, uint32_t child, float dl) {
       const int nl = freeSlot(idx);
@@ -1713,8 +2024,16 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
         L.endLmX[nl] = kYlNoLm;
         L.endLmX[kYlLanes + nl] = kYlNoLm;
       }
-      L.dPar[nl] = 0u;
-      L.dWord[nl] = -1;
+      if constexpr (ST) { /* (the name of the lane's LM state goes along: the park writes it) */
+        L.dPar[nl] = planDp;
+        L.dWord[nl] = planDw;
+        X.amNB[nl] = planAm;
+        X.amB[nl] = 0.0;
+        scoreRec(hrow + hyp, c, planAm, lmc);
+      } else {
+        L.dPar[nl] = 0u;
+        L.dWord[nl] = -1;
+      }
       L.maxScore[nl] = cx.maxScore;
       L.delta[nl] = dl;
       L.endLm[nl] = kYlNoLm;
@@ -1808,7 +2127,7 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
         first = false;
       }
     } else if (isSelf) {
-      if (li >= nHSurv + nNew && li < K) { /* unused slots of the history row */
+      if (!ST && li >= nHSurv + nNew && li < K) { /* unused slots of the history row (a stream's rows are read up to the parked count) */
         histPT[hrow + li] = make_int2((int)kNoHyp, -1);
       }
       if (surv) {
@@ -1832,13 +2151,24 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
             hp = S.root.winHyp[rootSlot];
             wd = S.root.winWord[rootSlot];
             lmStay = S.root.winLm[rootSlot];
+            if constexpr (ST) {
+              amC1 = X.winAm[rootSlot];
+            }
           }
           histPT[hrow + hNB + hb] = make_int2((int)hp, atRoot ? sil : last);
           histW[hrow + hNB + hb] = wd;
+          if constexpr (ST) {
+            X.amNB[li] = amC1;
+            scoreRec(hrow + hNB + hb, cs[1], amC1, lmStay);
+          }
         }
         if (sB) {
           histPT[hrow + hB + hb] = make_int2((int)hypM, blank);
           histW[hrow + hB + hb] = -1;
+          if constexpr (ST) {
+            X.amB[li] = amC0;
+            scoreRec(hrow + hB + hb, cs[0], amC0, lmM);
+          }
         }
         if (LMT) {
           L.lmNB[li] = lmStay;
@@ -1910,6 +2240,11 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
           atomOr64(&S.alive[q][nl >> 6], 1ull << (nl & 63));
           histPT[hrow + hyp] = make_int2((int)hp, endTok);
           histW[hrow + hyp] = el;
+          if constexpr (ST) {
+            X.amNB[nl] = cam[g];
+            X.amB[nl] = 0.0;
+            scoreRec(hrow + hyp, cs[g], cam[g], clm[g]);
+          }
           adopt(rootOrph[g], nl);
           (void)x;
         }
@@ -1955,7 +2290,109 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
    * merge; sorted n-best ------------------------------------------------------------------------ */
   const int pe = T & 1;
   const int ff = T + 1;
-  if (!dead) {
+  if constexpr (ST) {
+    /* ---- park the beam for the next launch / prune / getBestHypothesis / decodeEnd: one slot per hypothesis, sorted by
+     * (score descending, history slot ascending), in the generic engine's format; the last history row, histW and histS
+     * rewritten in that order.  The lanes' own waves park, a thread the two hypotheses of its lane. --------------- */
+#ifndef FLTX_EMU
+    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* this wave's history records are in L2 */
+#endif
+    ldsBarrier(); /* P1: the last frame's records are written, the decodeEnd members are free for the ranking */
+    const bool parks = isSelfW && !dead;
+    const bool liveP = parks && ((S.alive[pe][grp] >> lane) & 1ull) != 0ull;
+    const int lp = liveP ? li : 0;
+    const double nbP = L.nb[lp], bbP = L.b[lp];
+    const uint32_t infoP = L.info[lp];
+    const uint32_t sNB = liveP ? infoNB(infoP) : kNoHyp, sB = liveP ? infoB(infoP) : kNoHyp;
+    const bool hasNB = sNB != kNoHyp, hasB = sB != kNoHyp;
+    const unsigned long long kNB = hasNB ? f64Key(nbP) : 0ull, kB = hasB ? f64Key(bbP) : 0ull;
+    const int64_t hlast = hbase + (int64_t)(frame0 + T) * K;
+    unsigned long long recNB = 0ull, recB = 0ull;
+    int32_t wNB = -1, wB = -1;
+    if (parks) {
+      Y.key[2 * li] = kNB;
+      Y.key[2 * li + 1] = kB;
+      Y.slot[2 * li] = sNB;
+      Y.slot[2 * li + 1] = sB;
+      const unsigned long long* hrec = (const unsigned long long*)(histPT + hlast);
+      recNB = hasNB ? loadCoherent64(hrec + sNB) : 0ull;
+      recB = hasB ? loadCoherent64(hrec + sB) : 0ull;
+      wNB = hasNB ? (int32_t)loadCoherent32((const uint32_t*)(histW + hlast) + sNB) : -1;
+      wB = hasB ? (int32_t)loadCoherent32((const uint32_t*)(histW + hlast) + sB) : -1;
+      const int nMine = popc64(waveBallot(hasNB)) + popc64(waveBallot(hasB));
+      if (lane == 0) {
+        atomAdd32(&S.scal[YL_NPARK], (uint32_t)nMine);
+      }
+    }
+#ifndef FLTX_EMU
+    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
+    /* P2: with two waves parking, every old record of the last row is in its reader's registers before any slot of the
+     * row is rewritten below -- and every hypothesis's key stands in the ranking list */
+    ldsBarrier();
+    if (parks) {
+      int rNB = 0, rB = 0;
+      for (int i = 0; i < 2 * 64 * NG; ++i) {
+        const unsigned long long k2 = Y.key[i];
+        const uint32_t s2 = Y.slot[i];
+        const bool e2 = s2 != kNoHyp;
+        rNB += (e2 && (k2 > kNB || (k2 == kNB && s2 < sNB))) ? 1 : 0;
+        rB += (e2 && (k2 > kB || (k2 == kB && s2 < sB))) ? 1 : 0;
+      }
+      const uint32_t nodeP = L.node[lp];
+      const uint32_t sidOut = L.lmSid[lp], sparOut = L.dPar[lp] & 0x7FFFFFFFu;
+      const int32_t edgeOut = L.dWord[lp];
+      const uint32_t lexOut = P.xNew2Old[liveP ? nodeP : 0u];
+      /* (what the generic engine keeps in bLexMax: maxScore of the slot's node, 0 at the root -- LexiconDecoder.cpp:58-59) */
+      const float lexMaxOut = nodeP == 0u ? 0.0f : L.maxScore[lp];
+      const uint32_t lastTok = infoP & 63u; /* (a root lane's is sil: the separator) */
+      auto put = [&](int r, double sc, double am, double lmv, uint32_t tokpb, unsigned long long rec, int32_t wd) {
+        const size_t g = (size_t)b * K + r;
+        P.gScore[g] = sc;
+        P.gAm[g] = am;
+        P.gLm[g] = lmv;
+        P.gState[g] = sidOut;
+        P.gSPar[g] = sparOut;
+        P.gSEdge[g] = edgeOut;
+        P.gLex[g] = lexOut;
+        P.gLexMax[g] = lexMaxOut;
+        P.gTokPb[g] = tokpb;
+        ((unsigned long long*)(histPT + hlast))[r] = rec;
+        histW[hlast + r] = wd;
+        if (P.histS) {
+          double* hs = P.histS + 3 * (hlast + r);
+          hs[0] = sc;
+          hs[1] = am;
+          hs[2] = lmv;
+        }
+      };
+      if (hasNB && rNB < K) {
+        put(rNB, nbP, X.amNB[lp], L.lmNB[lp], lastTok, recNB, wNB);
+      }
+      if (hasB && rB < K) {
+        put(rB, bbP, X.amB[lp], L.lmB[lp], (uint32_t)blank | kPrevBlank, recB, wB);
+      }
+    }
+    if (tid == 0) {
+      /* dead: a per-frame table ran full, the select did not converge, a pair list overflowed, the id table or the ids
+       * ran out, or a word id does not fit the table's key -- this chunk cannot be finished here.  The beam it started
+       * from is in the host layer's snapshot; it puts it back and decodes the chunk again on the general path (the ids
+       * named so far stay in the table: they are the ones that pass will name) */
+      const int32_t stNow = P.uttStatus[b] | (int32_t)S.scal[SL_STATUS] | (dead ? (int32_t)ST_SELECT_FALLBACK : 0);
+      if (!dead) {
+        const int nHyp = (int)S.scal[YL_NPARK];
+        P.uttNBeam[b] = nHyp < K ? nHyp : K;
+        P.uttFrame[b] = frame0 + T;
+        P.uttTotal[b] = total0 + T;
+      }
+      P.uttNextId[b] = (int32_t)S.scal[SL_NEXTID];
+      P.uttStatus[b] = stNow;
+      if (P.statusHost) {
+        P.statusHost[b] = stNow;
+      }
+    }
+  }
+  if (!ST && !dead) {
     bool liveE = false, onRoot = false;
     double mE = NEG, lmE = 0.0, oE = NEG; /* (oE: logAdd -- the lane's other hypothesis finishes into the same group) */
     uint32_t hpE = kNoHyp, lmSidE = 0u;
@@ -2048,7 +2485,7 @@ FLTX_DEV void ylaneUtterance(const DecodeParams& P, char* smem) {
     fprintf(stderr, "ylane: utterance %d ends dead=%d with %u LM states\n", b, (int)dead, S.lmNext);
   }
 #endif
-  if (dead) { /* (uniform: every way out of the frame loop passes a barrier that spreads it) */
+  if (!ST && dead) { /* (uniform: every way out of the frame loop passes a barrier that spreads it) */
     if (deadWhy != 0 && lane == 0) {
       atomCas32(&S.scal[YL_WHYCODE], 0u, (uint32_t)deadWhy);
     }

@@ -1,4 +1,7 @@
-"""Lexicon stream chunks: the generic frame loop ("xstream" = 0) against fltx_xlane.h's stream kernel ("xstream" = 1).
+"""Lexicon stream chunks: the generic frame loop against a lane engine's stream kernel -- --shape C3 (the default):
+"xstream" = 0 against 1 (fltx_xlane.h); --shape C4: "ystream" = 0 against 1 (fltx_ylane.h, the LM terms), on bench.py's C4
+workload (the trie with label scores, the synthetic 4-gram, lm_weight 2, word_score 2, sil_score -1, beam 100, token beam
+29, T = 1500 unless --T says otherwise).  Below, `xstream` stands for the shape's tunable.
 
 The shape bench.py streams as C3 (its workload table: LexiconDecoder + ZeroLM over the 90k-word trie, CTC, N = 29,
 beam 50, token beam 10): --B = 256 streams of --T = 1000 frames in --chunk = 50-frame chunks from host memory,
@@ -10,7 +13,7 @@ from stream_begin to a synchronise after stream_end.  One JSON line per run:
   other setting: must be true)
 and a last line with each setting's median, min and max and the ratio of the medians.
 
-    python tools/bench_lex_stream.py [--B 256] [--T 1000] [--chunk 50] [--repeat 3] [--sample 16]
+    python tools/bench_lex_stream.py [--shape C3|C4] [--B 256] [--T 1000] [--chunk 50] [--repeat 3] [--sample 16]
 """
 import argparse
 import json
@@ -30,20 +33,32 @@ from text_amd import _capi, synth  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=256)
-    ap.add_argument("--T", type=int, default=1000)
+    ap.add_argument("--shape", choices=["C3", "C4"], default="C3")
+    ap.add_argument("--T", type=int, default=None, help="frames per stream (C3: 1000, C4: 1500)")
     ap.add_argument("--chunk", type=int, default=50)
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--sample", type=int, default=16)
     a = ap.parse_args()
-    B, T, CH, N, K, Kt = a.B, a.T, a.chunk, 29, 50, 10
+    c4 = a.shape == "C4"
+    key = "ystream" if c4 else "xstream"
+    B, T, CH, N = a.B, a.T or (1500 if c4 else 1000), a.chunk, 29
+    K, Kt = (100, 29) if c4 else (50, 10)
     lexicon = synth.lexicon()
     W = len(lexicon[1]) - 1
     e_host = synth.batch("lexspell", B, T, N, lexicon=lexicon, u0=0)
     ctx = _capi.Context(device=0)
-    lm = _capi.ZeroLM(ctx)
-    opt = _capi.make_options(K, Kt, 25.0, 0.0, 0.0, float("-inf"), 0.0, False, "ctc")
+    wscore = np.zeros(W, dtype=np.float32)
+    if c4:  # (as bench.py sets C4 up: trie label scores = lm.score(start, word))
+        from bench import synthetic_arpa
+        arpa = synthetic_arpa(W)
+        lm = _capi.ArpaLM(arpa[0], arpa[1])
+        opt = _capi.make_options(K, Kt, 25.0, 2.0, 2.0, float("-inf"), -1.0, False, "ctc")
+        wscore = np.array([lm.score_sequence([w], False)[0][0] for w in range(W)], dtype=np.float32)
+    else:
+        lm = _capi.ZeroLM(ctx)
+        opt = _capi.make_options(K, Kt, 25.0, 0.0, 0.0, float("-inf"), 0.0, False, "ctc")
     ht = _capi.HostTrie(N, 0)
-    ht.insert_many(lexicon[0], lexicon[1], np.arange(W), np.zeros(W, dtype=np.float32))
+    ht.insert_many(lexicon[0], lexicon[1], np.arange(W), wscore)
     ht.smear(1)
     trie = ht.upload(ctx)
     nchunk = T // CH
@@ -54,14 +69,14 @@ def main():
     for x in (0, 1):
         d = decs[x] = _capi.BatchDecoder(ctx, _capi.LEXICON, opt, lm, 0, N - 1, unk=W, trie=trie)
         d.set("stream_total_frames", T)
-        d.set("xstream", x)
+        d.set(key, x)
 
     def run(x):
         d = decs[x]
         ctx.synchronize()
         t0 = time.perf_counter()
         d.stream_begin(B, N, 4 * CH + 8)
-        chosen = int(d.get("xstream"))
+        chosen = int(d.get(key))
         for p in pieces:
             d.stream_step(p, Tc)
             d.stream_prune(0)
@@ -79,14 +94,14 @@ def main():
             if not rep:
                 continue
             rates[x].append(B * nchunk * CH / dt)
-            print(json.dumps({"xstream": x, "chosen": chosen, "frames_per_s": rates[x][-1], "ms": dt * 1e3,
+            print(json.dumps({key: x, "chosen": chosen, "frames_per_s": rates[x][-1], "ms": dt * 1e3,
                               "stream_redone": redone, "nbest_equal": nbest == first[1 - x] if (1 - x) in first else None}),
                   flush=True)
     med = {x: statistics.median(v) for x, v in rates.items()}
-    print(json.dumps({"config": {"B": B, "T": T, "chunk": CH, "K": K, "Kt": Kt, "N": N, "words": W, "repeat": a.repeat,
+    print(json.dumps({"config": {"shape": a.shape, "B": B, "T": T, "chunk": CH, "K": K, "Kt": Kt, "N": N, "words": W, "repeat": a.repeat,
                                  "sample": sample},
-                      "xstream_0": {"median": med[0], "min": min(rates[0]), "max": max(rates[0])},
-                      "xstream_1": {"median": med[1], "min": min(rates[1]), "max": max(rates[1])},
+                      key + "_0": {"median": med[0], "min": min(rates[0]), "max": max(rates[0])},
+                      key + "_1": {"median": med[1], "min": min(rates[1]), "max": max(rates[1])},
                       "ratio": med[1] / med[0], "nbest_equal": first[0] == first[1]}), flush=True)
     for d in decs.values():
         d.close()
