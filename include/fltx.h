@@ -1073,7 +1073,12 @@ FLTX_API int fltx_decoder_profile(fltx_decoder* dec, uint64_t* out);
  * terms where it takes them -- an n-gram word LM over any trie or ZeroLM over a trie with label scores, one word per
  * spelling, CTC, no <unk>, max-merge, beam up to 128 and tokens up to 64, an optimistic stream; default 0; set before
  * fltx_stream_begin; fltx_decoder_get "ystream" answers the lane groups chosen for the open stream, or 0; where "xstream"
- * is set too and takes the stream, it keeps it; results are the same bit for bit), "stream_optimistic" (0 = lexicon
+ * is set too and takes the stream, it keeps it; results are the same bit for bit), "wstream" (1 = a lexicon-free stream's
+ * chunks over a token set beyond 64 run on the lane = LM state engine for word pieces where it takes them -- ZeroLM,
+ * max-merge, up to 16 384 tokens, beam and token beam up to 64; the stream is then an optimistic one: a chunk that engine
+ * cannot finish, such as one with a frame of equal values, is decoded again on the general path; default 0; set before
+ * fltx_stream_begin; fltx_decoder_get "wstream" answers the positions per token wave chosen for the open stream, or 0;
+ * results are the same bit for bit), "stream_optimistic" (0 = lexicon
  * streams use the worst-case HBM workspace from the start instead of decoding an overflowing chunk again),
  * "stream_defer" (0 = fltx_stream_step of a lexicon stream waits for its chunk; default: the chunk is launched and whether
  * a stream has to decode it again is looked at by the next call that needs the beam -- the next chunk's upload runs

@@ -103,6 +103,11 @@ __global__ void __launch_bounds__(256) fltx_tokbeam_kernel(DecodeParams P) {
   extern __shared__ __attribute__((aligned(16))) char fltx_tb_smem[];
   wlTokBeamRows(P, fltx_tb_smem);
 }
+/* ... of the rows of a stream call's chunks, indexed by the call's frames */
+__global__ void __launch_bounds__(256) fltx_tokbeam_stream_kernel(DecodeParams P) {
+  extern __shared__ __attribute__((aligned(16))) char fltx_tb_smem[];
+  wlTokBeamRowsCall(P, fltx_tb_smem);
+}
 /* streams: LM-state ids nothing can meet again go back to the utterance's free list (compactStates) */
 __global__ void __launch_bounds__(1024) fltx_compact_states_kernel(CompactParams Q) {
   extern __shared__ __attribute__((aligned(16))) char fltx_cs_smem[];
@@ -834,6 +839,10 @@ struct fltx_decoder {
   /* ... and, with the LM terms (n-gram word LM and / or smeared trie), on fltx_ylane.h (ST; "ystream" = 1 asks for it): lane
    * groups (0 = not used), threads and list positions per token wave of the chunks' launch */
   int ystreamAsked = 0, ystream = 0, ystreamThreads = 0, ystreamTpw = 0, ystreamRounds = 0;
+  /* ... and of the lexicon-free decoder over a large token set on fltx_wlane.h (ST; "wstream" = 1 asks for it, and makes the
+   * stream an optimistic one: a chunk that engine cannot finish is decoded again): positions per token wave (0 = not
+   * used) and threads of the chunks' launch */
+  int wstreamAsked = 0, wstream = 0, wstreamThreads = 0;
   /* streams of the lexicon decoder on the optimistic geometry (LDS workspace, cut-off generation): a chunk that
    * overflows is decoded again from the saved beam on the general path (HBM workspace) */
   int userStreamOpt = 1;
@@ -2199,6 +2208,8 @@ int fltx_decoder_get(fltx_decoder* d, const char* key, int64_t* value) {
     *value = d->xstream;
   } else if (!strcmp(key, "ystream")) { /* lane groups of fltx_ylane.h's stream kernel chosen for the open stream, or 0 */
     *value = d->ystream;
+  } else if (!strcmp(key, "wstream")) { /* positions per token wave of fltx_wlane.h's stream kernel chosen for the open stream, or 0 */
+    *value = d->wstream;
   } else if (!strcmp(key, "tstream")) { /* 1: the stream's chunks run on the token-LM variant of fltx_slane.h */
     *value = d->tstream;
   } else if (!strcmp(key, "looks_dropped")) { /* defer_check = 2: batches that were overwritten without a look at their statuses */
@@ -2391,6 +2402,10 @@ int fltx_decoder_set(fltx_decoder* d, const char* key, int64_t value) {
     d->ystreamAsked = value ? 1 : 0;
     return FLTX_OK;
   }
+  if (!strcmp(key, "wstream")) { /* 1: a word-piece stream's chunks run on fltx_wlane.h where it takes them (default 0) */
+    d->wstreamAsked = value ? 1 : 0;
+    return FLTX_OK;
+  }
   if (!strcmp(key, "stream_optimistic")) { /* 0: streams of the lexicon decoder start on the worst-case (HBM) workspace */
     d->userStreamOpt = (int)value;
     return FLTX_OK;
@@ -2519,6 +2534,7 @@ static const LaneGeo kSstreamGeo[] = {FLTX_SSTREAM_GEOS(FLTX_GEO2)};
 static const LaneGeo kWlaneGeo[] = {FLTX_WLANE_GEOS(FLTX_GEO2)};
 static const LaneGeo kXlaneGeo[] = {FLTX_XLANE_GEOS(FLTX_GEO2)};
 static const LaneGeo kXstreamGeo[] = {FLTX_XSTREAM_GEOS(FLTX_GEO2)};
+static const LaneGeo kWstreamGeo[] = {FLTX_WSTREAM_GEOS(FLTX_GEO2)};
 static const YstreamGeo kYstreamGeo[] = {FLTX_YSTREAM_GEOS(FLTX_GEO3)};
 static const MlaneGeo kMlaneGeo[] = {FLTX_MLANE_GEOS(FLTX_GEO5)}; /* "mlane_geo" = row */
 static const MlaneGeo kTmlaneGeo[] = {FLTX_TMLANE_GEOS(FLTX_GEO5)};
@@ -2963,9 +2979,25 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
       }
     }
   }
+  /* ... and the chunks of a word-piece stream (wlaneUtterance<.., ST>), when asked for: fltx_wlane.h's offline terms, the
+   * optimistic stream (fltx_stream_begin makes a lexicon-free stream one when "wstream" asks; a chunk this engine cannot
+   * finish is decoded again by streamRedoFlagged, whose prepare() forces the HBM workspace and so never comes here),
+   * recycled ids (the restore asks idPar).  Fields of its own, as "xstream" */
+  d->wstream = 0;
+  if (d->wstreamAsked && d->kind == FLTX_DECODER_LEXFREE && !d->noSlane && !d->noWlane && !d->genericAsked && !d->offlineCall &&
+      d->keepScores && d->streamOpt && d->recycle && !d->forceGlobalWs && !d->opt.log_add && d->lm->kind == 0 &&
+      !d->isLmToken && N > 64 && N <= kWlMaxN && K <= 64 && nTok <= 64 && optionsOk) {
+    for (const LaneGeo& g : kWstreamGeo) {
+      if (nTok <= g.gt * (g.threads / 64 - 2)) {
+        d->wstream = g.gt;
+        d->wstreamThreads = g.threads;
+        break;
+      }
+    }
+  }
   { /* which eligibility terms kept this call off the lane engines (fltx_decoder_get "why_not_lane") */
     int64_t why = 0;
-    if (!(d->slane || d->xlane || d->ylane || d->sstream || d->xstream || d->ystream)) {
+    if (!(d->slane || d->xlane || d->ylane || d->sstream || d->xstream || d->ystream || d->wstream)) {
       const bool lexi = d->kind == FLTX_DECODER_LEXICON;
       const bool unkOn = d->opt.unk_score > -std::numeric_limits<double>::infinity();
       why |= (N > 64 && (lexi || N > kWlMaxN || nTok > 64)) ? FLTX_WHY_TOKENS : 0; /* (lexicon-free: the token BEAM has to fit, fltx_wlane.h) */
@@ -3382,7 +3414,7 @@ void fillParams(fltx_decoder* d, DecodeParams& P) {
   P.gLex = d->gLex.as<uint32_t>();
   P.gTokPb = d->gTokPb.as<uint32_t>();
   P.histPT = d->histPT.as<int2>();
-  P.tokRows = d->wlane ? d->tokRowsBuf.p : nullptr;
+  P.tokRows = (d->wlane || d->wstream) ? d->tokRowsBuf.p : nullptr; /* (a stream's chunk: sized and blocked by fltx_stream_step) */
   P.tokRowBlocks = d->wlane ? std::max(1, (d->wlMaxT + 3) / 4) : 1;
   P.histW = d->histW.as<int32_t>();
   P.histS = d->keepScores ? d->histS.as<double>() : nullptr;
@@ -3460,7 +3492,7 @@ void fillParams(fltx_decoder* d, DecodeParams& P) {
 
 /* The lane-engine kernels, one entry per (family, variant, geometry) of fltx_engines.h.  The emulator build maps the
  * same entries to the host functions the kernels are made of (tests/emu/fltx_emu_launch.inc). */
-enum LaneFamily { kGeneric, kSlane, kTlane, kSstream, kTstream, kMlane, kTmlane, kWlane, kXlane, kYlane, kXstream, kYstream };
+enum LaneFamily { kGeneric, kSlane, kTlane, kSstream, kTstream, kMlane, kTmlane, kWlane, kXlane, kYlane, kXstream, kYstream, kWstream };
 enum { kVarLA = 1, kVarProf = 2, kVarHM = 4, kVarM32 = 8 }; /* logAdd merges, phase clocks, memo in HBM, 32-bit token masks */
 struct LaneKey {
   int fam, var, threads, g[4];
@@ -3504,6 +3536,8 @@ struct LaneKernel {
   FLTX_LK(kXlane, kVarLA | kVarHM, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane<WW, GG, 1, false, true>), (xlaneUtterance<GG, 1, false, true>))
 #define FLTX_LK_XSTREAM(WW, GG) \
   FLTX_LK(kXstream, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane_stream<WW, GG>), (xlaneUtterance<GG, 0, false, false, true>))
+#define FLTX_LK_WSTREAM(WW, GG) \
+  FLTX_LK(kWstream, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_wlane_stream<WW, GG>), (wlaneUtterance<GG, true>))
 #define FLTX_LK_YSTREAM(WW, NG, RR) \
   FLTX_LK(kYstream, 0, WW, NG, RR, 0, 0, (fltx_decode_kernel_ylane_stream<WW, NG, RR>), (ylaneUtterance<NG, RR, 1, 0, false, true>))
 #define FLTX_LK_YLANE(WW, NG, RR, HM, LMK) \
@@ -3513,7 +3547,7 @@ struct LaneKernel {
 static const LaneKernel kLaneKernels[] = {
     FLTX_SLANE_GEOS(FLTX_LK_SLANE) FLTX_TLANE_PROF_GEOS(FLTX_LK_TLANE_PROF) FLTX_SSTREAM_GEOS(FLTX_LK_SSTREAM)
     FLTX_MLANE_GEOS(FLTX_LK_MLANE) FLTX_TMLANE_GEOS(FLTX_LK_TMLANE) FLTX_WLANE_GEOS(FLTX_LK_WLANE)
-    FLTX_XLANE_GEOS(FLTX_LK_XLANE) FLTX_XSTREAM_GEOS(FLTX_LK_XSTREAM) FLTX_YSTREAM_GEOS(FLTX_LK_YSTREAM) FLTX_YLANE_KERNELS(FLTX_LK_YLANE) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_LK_YLANE_PROF)};
+    FLTX_XLANE_GEOS(FLTX_LK_XLANE) FLTX_XSTREAM_GEOS(FLTX_LK_XSTREAM) FLTX_WSTREAM_GEOS(FLTX_LK_WSTREAM) FLTX_YSTREAM_GEOS(FLTX_LK_YSTREAM) FLTX_YLANE_KERNELS(FLTX_LK_YLANE) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_LK_YLANE_PROF)};
 #undef FLTX_LK
 #undef FLTX_LK_SLANE
 #undef FLTX_LK_TLANE_PROF
@@ -3523,18 +3557,21 @@ static const LaneKernel kLaneKernels[] = {
 #undef FLTX_LK_WLANE
 #undef FLTX_LK_XLANE
 #undef FLTX_LK_XSTREAM
+#undef FLTX_LK_WSTREAM
 #undef FLTX_LK_YSTREAM
 #undef FLTX_LK_YLANE
 #undef FLTX_LK_YLANE_PROF
 
 /* what launchDecode runs: the lane engine's family, variant and geometry (kGeneric: the per-W kernels) */
 LaneKey laneKeyOf(const fltx_decoder* d) {
-  const int W = d->sstreamLaunch ? (d->xstream ? d->xstreamThreads : (d->ystream ? d->ystreamThreads : d->sstreamThreads)) : d->threads;
+  const int W = d->sstreamLaunch ? (d->xstream ? d->xstreamThreads : (d->ystream ? d->ystreamThreads : (d->wstream ? d->wstreamThreads : d->sstreamThreads))) : d->threads;
   const int la = d->opt.log_add ? kVarLA : 0, prof = d->profile ? kVarProf : 0, hm = d->yshare ? kVarHM : 0;
   if (d->sstreamLaunch && d->xstream) {
     return {kXstream, 0, W, {d->xstream, 0, 0, 0}};
   } else if (d->sstreamLaunch && d->ystream) {
     return {kYstream, 0, W, {d->ystream, d->ystreamRounds, 0, 0}};
+  } else if (d->sstreamLaunch && d->wstream) {
+    return {kWstream, 0, W, {d->wstream, 0, 0, 0}};
   } else if (d->sstreamLaunch) {
     return {d->tstream ? kTstream : kSstream, prof, W, {d->sstream, 0, 0, 0}};
   } else if (d->ylane) { /* (logAdd: LMK bit 3) */
@@ -3572,6 +3609,8 @@ size_t launchLds(const fltx_decoder* d, const LaneKey& k) {
     return sizeof(TlaneLds) + (size_t)(k.threads / 64) * kTlGatherBytes;
   } else if (k.fam == kXstream) { /* (the stream members take the LM-state memo's place) */
     return offsetof(XlaneLds, memo) + sizeof(XlStreamLds);
+  } else if (k.fam == kWstream) { /* (no Bloom filter, no edge memo: 31 KB) */
+    return sizeof(WlStreamLds);
   } else if (k.fam == kYstream) {
     /* YlaneLds up to the part of pscore the geometry's token waves use, then the stream members (no LM-state memo):
      * 82 KB with five token waves (512 threads, one lane group), 88 KB with eight (768, two); next to kXstream's 31 KB */
@@ -3675,6 +3714,10 @@ int launchDecode(fltx_decoder* d, const DecodeParams& P) {
     }
     d->wlMaxT = 0;
   }
+  if (key.fam == kWstream) { /* the token beams of the rows of this call's chunks, ahead of the chunks' kernel */
+    const DecodeParams* pf = &P;
+    emuLaunch(P.tokRowBlocks * nGrid, 256, 4 * sizeof(WlFrontLds), [pf](char* smem) { wlTokBeamRowsCall(*pf, smem); });
+  }
 #include "fltx_emu_launch.inc" /* tests/emu/: host-thread dispatch over the kernel variants */
 #else
   for (int i = 0; i < 3; ++i) {
@@ -3701,9 +3744,12 @@ int launchDecode(fltx_decoder* d, const DecodeParams& P) {
   } else if (key.fam == kWlane && d->wlMaxT > 0) { /* the token beams of all rows first (same stream) */
     hipLaunchKernelGGL(fltx_tokbeam_kernel, dim3((unsigned)(P.tokRowBlocks * nGrid)), dim3(256), 4 * sizeof(WlFrontLds),
                        d->ctx->stream, P);
+  } else if (key.fam == kWstream) { /* ... of the rows of this call's chunks */
+    hipLaunchKernelGGL(fltx_tokbeam_stream_kernel, dim3((unsigned)(P.tokRowBlocks * nGrid)), dim3(256), 4 * sizeof(WlFrontLds),
+                       d->ctx->stream, P);
   }
   /* (slane, the stream chunks and gwslean launch within the default limit, as they always have) */
-  const bool defaultLimit = key.fam == kSlane || key.fam == kSstream || key.fam == kTstream || key.fam == kXstream ||
+  const bool defaultLimit = key.fam == kSlane || key.fam == kSstream || key.fam == kTstream || key.fam == kXstream || key.fam == kWstream ||
                             (key.fam == kGeneric && !d->wsInLds && d->lean);
   int rc;
   if (!defaultLimit && (rc = raiseMaxLdsOnce(d, 0, fn, lds))) {
@@ -4165,7 +4211,7 @@ int streamRedoFlagged(fltx_decoder* d) {
      * other stream path raises this status, so the choice stands for "the launch that wrote the status"; a path that
      * comes to raise it for another reason needs a test of its own here) */
     /* (... and likewise a chunk fltx_ylane.h's stream variant could not finish, while d->ystream is set) */
-    if (status[b] & (ST_CAND_OVERFLOW | ST_CUT_RETRY | ((d->xstream || d->ystream) ? ST_SELECT_FALLBACK : 0))) {
+    if (status[b] & (ST_CAND_OVERFLOW | ST_CUT_RETRY | ((d->xstream || d->ystream || d->wstream) ? ST_SELECT_FALLBACK : 0))) {
       again.push_back(b);
     }
   }
@@ -4864,13 +4910,17 @@ int fltx_stream_begin(fltx_decoder* d, int32_t B, int32_t N, int32_t maxFrames) 
    * can be decoded again: the beam a chunk starts from is saved, the state table is idempotent (same
    * (parent, edge) -> same id), history rows are rewritten in place.  (The lexicon-free engines never
    * overflow and number their states with a counter: always one pass.) */
-  d->streamOpt = d->kind == FLTX_DECODER_LEXICON && d->userStreamOpt != 0 && !d->forceGlobalWs && d->lm->kind != 2;
+  /* ("wstream": the chunks of a lexicon-free stream on fltx_wlane.h can be abandoned -- a row without a defined token
+   * beam -- and are decoded again the same way; where that engine does not take the stream nothing optimistic is left) */
+  const bool wAsked = d->kind == FLTX_DECODER_LEXFREE && d->wstreamAsked != 0;
+  d->streamOpt = (d->kind == FLTX_DECODER_LEXICON || wAsked) && d->userStreamOpt != 0 && !d->forceGlobalWs && d->lm->kind != 2;
   d->streamRedone = 0;
   int rc = prepare(d, B, N, Tm.data(), !d->streamOpt);
   if (rc) {
     return rc;
   }
-  if (d->streamOpt && (d->lean || !(d->wsInLds || d->CAP2 > 0 || d->cutRecompute))) {
+  if (d->streamOpt && (d->kind == FLTX_DECODER_LEXFREE ? d->wstream == 0
+                                                       : (d->lean || !(d->wsInLds || d->CAP2 > 0 || d->cutRecompute)))) {
     d->streamOpt = false; /* nothing optimistic came out of it */
     if ((rc = prepare(d, B, N, Tm.data(), true))) {
       return rc;
@@ -4997,14 +5047,30 @@ int fltx_stream_step(fltx_decoder* d, const float* emissions, int32_t onDevice, 
     d->idsUsedBound += want;
   }
   DecodeParams P;
+  if (d->wstream) { /* fltx_wlane.h's front end leaves one record per frame of this call: stream b's from sum(T[0 .. b)) on */
+    int64_t rows = 0;
+    for (int b = 0; b < d->B; ++b) {
+      rows += T[b];
+    }
+    if (d->tokRowsBuf.ensure(sizeof(WlTokRow) * (size_t)std::max<int64_t>(rows, 1), d->ctx->stream, false)) {
+      return fail(FLTX_ERR_OOM, "token-beam records: allocation failed");
+    }
+  }
   fillParams(d, P); /* (emOff / stepT: the slot uploadStep has just filled) */
   P.emissions = up.emissions;
   P.doBegin = 0;
   P.doEnd = 0;
+  if (d->wstream) {
+    int maxT = 0;
+    for (int b = 0; b < d->B; ++b) {
+      maxT = std::max(maxT, T[b]);
+    }
+    P.tokRowBlocks = std::max(1, (maxT + 3) / 4);
+  }
   if (d->streamOpt && (rc = streamSnapshot(d, 0, nullptr, d->B))) {
     return rc;
   }
-  d->sstreamLaunch = d->sstream != 0 || d->xstream != 0 || d->ystream != 0;
+  d->sstreamLaunch = d->sstream != 0 || d->xstream != 0 || d->ystream != 0 || d->wstream != 0;
   rc = d->lm->kind == 2 ? hostLmFrames(d, P, T) : launchDecode(d, P);
   d->sstreamLaunch = false;
   if (rc) {

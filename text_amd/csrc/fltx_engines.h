@@ -39,6 +39,10 @@
 /* fltx_wlane.h, token beams over large token sets: X(threads, list positions per wave) */
 #define FLTX_WLANE_GEOS(X) X(576, 5) X(576, 8) X(576, 10)
 
+/* ... a word-piece stream's chunks (wlane_stream), in order of preference: the offline rows.  31 KB of LDS, but 9 waves
+ * of 140 and more VGPRs each: no geometry is offered for two workgroups on a CU */
+#define FLTX_WSTREAM_GEOS(X) X(576, 5) X(576, 8) X(576, 10)
+
 /* fltx_xlane.h, lane = (LM state, trie node): X(threads, list positions per wave), in order of preference; three waves
  * do not evaluate listed tokens */
 #define FLTX_XLANE_GEOS(X) X(512, 2) X(512, 3) X(640, 2) X(576, 5) X(640, 10)

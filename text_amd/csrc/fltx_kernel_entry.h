@@ -78,6 +78,14 @@ __global__ void __launch_bounds__(W) fltx_decode_kernel_wlane(DecodeParams P) {
   extern __shared__ __attribute__((aligned(16))) char fltx_smem[];
   wlaneUtterance<GT>(P, fltx_smem);
 }
+/* ... the frames of one decodeStep chunk of a word-piece stream on that engine: beam in and out in the generic engine's
+ * parked format, LM-state ids from its table; its kernels do decodeBegin / decodeEnd / prune / getBestHypothesis.  The
+ * token beams of the chunk's rows come from fltx_tokbeam_stream_kernel (fltx_api.cpp), launched ahead of it */
+template <int W, int GT>
+__global__ void __launch_bounds__(W) fltx_decode_kernel_wlane_stream(DecodeParams P) {
+  extern __shared__ __attribute__((aligned(16))) char fltx_smem[];
+  wlaneUtterance<GT, true>(P, fltx_smem);
+}
 /* the frames of one decodeStep chunk of a stream on the same engine: beam in and out in the parked format of the
  * lane-per-slot step, whose kernels do decodeBegin / decodeEnd / prune / getBestHypothesis */
 template <int W, int GT>

@@ -67,6 +67,66 @@ struct WlaneLds {
   uint32_t bloom[kWlBloomWords];
   uint8_t posOf[kWlMaxN];          /* token -> position in the newest list (the frame after the current one), 0xFF = not listed */
 };
+/* Stream chunks (wlaneUtterance<GT, true>): LM states are named through the generic engine's (epoch, parent id, token)
+ * -> id table in HBM (tlStreamChild), which is exact and says whether an edge had a child before -- no Bloom filter, no
+ * edge memo, no look-up in the history rows.  In their place: the emitting-model score of a lane's two hypotheses
+ * (getBestHypothesis reports an ancestor's) and the parked slots the restore found them in.  31 KB against 124 KB.
+ * The members both kernels use are WlaneLds's, by the same names (a struct of its own, not a shared base: the offline
+ * kernel's accesses keep the types, and so the code, they had). */
+struct WlStreamLds {
+  SlRec rec[2][64];
+  unsigned long long cmask[2][64];
+  uint32_t hist[2][kSlNB];
+  double eTok[2][64];
+  uint32_t tokTok[2][64];
+  WlRow row[2];
+  uint32_t off[32];
+  int32_t newLane[64];
+  uint32_t scal[16];
+  unsigned long long bKey[kSlBCap];
+  uint32_t bOrd[kSlBCap];
+  uint32_t evLane[64], evSpar[64], evTok[64];
+  uint32_t evSid[64];              /* always the state's id */
+  alignas(16) double amNB[2][64];  /* emitting-model score of a lane's two hypotheses */
+  double amB[2][64];
+  uint8_t rsNB[64], rsB[64];       /* restore: the parked slot of a lane's two hypotheses */
+  uint8_t posOf[kWlMaxN];          /* (16-byte aligned: the prologue wipes it four words at a time) */
+};
+/* What only a stream's frame computes: empty offline, and touched under `if constexpr (ST)` alone, so that the offline
+ * kernel's frame is the code it was (locals and lambdas both variants declared moved its registers and spills). */
+template <bool ST>
+struct WlStreamRegs {};
+template <>
+struct WlStreamRegs<true> {
+  int frame0, total0;                  /* rows already in the buffer; frames decoded since decodeBegin */
+  double amNB, amB, parAmNB, parAmB;   /* emitting-model score of the lane's two hypotheses, of its parent lane's */
+  double amM;                          /* ... of the better of the lane's two */
+  double amR;                          /* ... of the repeat group's winning member */
+  uint32_t prevR;                      /* ... and that member's token (ASG transition) */
+  double amNew;                        /* ... of the state newState() is about to make */
+};
+enum { WL_FRAME0 = 6, WL_TOTAL0 = 7 }; /* scal[], next to fltx_slane.h's SL_* */
+/* LexiconFreeDecoder.cpp:58-64: the ASG transition enters the emitting-model score only */
+FLTX_DEV double wlAmStep(const DecodeParams& P, bool first, double amPrev, double e, uint32_t n, uint32_t prevTok) {
+  double x = e;
+  if (P.criterion != 1 && P.transitions && !first) {
+    x = x + (double)P.transitions[(size_t)n * P.N + prevTok];
+  }
+  return amPrev + x;
+}
+/* the generic engine's plain record, and a record's {score, emitting-model score, 0.0} */
+FLTX_DEV int2 wlPlainRec(uint32_t hp, uint32_t n) { return make_int2(hp == kSlNoHyp ? -1 : (int)hp, (int)n); }
+FLTX_DEV void wlScoreRec(const DecodeParams& P, int64_t at, double c, double am) {
+  if (P.histS) {
+    double* hs = P.histS + 3 * at;
+    hs[0] = c;
+    hs[1] = am;
+    hs[2] = 0.0;
+  }
+}
+/* a lane's `spar` in a stream: bit 31 (no state id has it) = the state takes no arrival -- the start state, or a state
+ * whose parent a compaction has cut loose, whose number in gSPar is stale and must not be matched (fltx_xlane.h) */
+constexpr uint32_t kWlNoArrival = 0x80000000u;
 
 FLTX_DEV uint32_t wlHash(uint32_t sid, uint32_t tok, uint32_t seed) {
   uint32_t h = (sid * 0x9E3779B1u) ^ (tok * 0x85EBCA77u) ^ seed;
@@ -164,6 +224,31 @@ FLTX_DEV __attribute__((noinline)) void wlReenter(WlaneLds& S, const int2* histP
       }
     }
     ldsBarrier();
+  }
+  if (tid == 0) {
+    S.row[q].nev = 0u;
+  }
+  ldsBarrier();
+}
+
+/* ... in a stream: every re-entered state knows its id (the table gave it), so what is left is wlReenter's "known"
+ * branch -- the lanes whose parent a re-entered state is get their link back.  All waves. */
+FLTX_DEV __attribute__((noinline)) void wlRelink(WlStreamLds& S, int q, int nState) {
+  const int tid = (int)threadIdx.x;
+  const int nev = (int)S.row[q].nev;
+  ldsBarrier(); /* (everybody has read the count before it is reset) */
+  if (tid < nState) {
+    const uint32_t spar = S.rec[q][tid].spar; /* (kWlNoArrival set: equals no id) */
+    for (int e = 0; e < nev && e < 64; ++e) {
+      const int X = (int)S.evLane[e];
+      if (tid != X && spar == S.evSid[e]) {
+        const uint32_t info = S.rec[q][tid].info;
+        S.rec[q][tid].info = (info & ~0xFF00u) | ((uint32_t)(X + 1) << 8);
+        if ((info & 0xFFu) < 64u) {
+          atomOr64(&S.cmask[q][X], 1ull << (info & 0xFFu));
+        }
+      }
+    }
   }
   if (tid == 0) {
     S.row[q].nev = 0u;
@@ -445,6 +530,31 @@ FLTX_DEV void wlTokBeamRows(const DecodeParams& P, char* smem) {
   wlTokBeamRow(P, S, row, out, P.criterion == 1);
 }
 
+/* A stream's chunk: the records are indexed by the CALL's frames -- stream b's start at the number of frames the call
+ * gives the streams before it -- so the buffer is as large as the call, not as the streams' history.  One wave. */
+FLTX_DEV int64_t wlCallRowBase(const DecodeParams& P, int b) {
+  int s = 0;
+  for (int i = laneId(); i < b; i += 64) {
+    s += P.stepT[i];
+  }
+  return (int64_t)waveReadLane32((uint32_t)waveInclusiveScan(s), 63);
+}
+/* ... its front-end kernel: workgroup = stream * tokRowBlocks + row block, as above */
+FLTX_DEV void wlTokBeamRowsCall(const DecodeParams& P, char* smem) {
+  const int wave = waveUniform(waveId());
+  const int ub = (int)blockIdx.x / P.tokRowBlocks, rb = (int)blockIdx.x % P.tokRowBlocks;
+  const int b = P.uttMap ? P.uttMap[ub] : ub;
+  const int t = rb * ((int)blockDim.x >> 6) + wave;
+  const int T = P.stepT ? P.stepT[b] : 0;
+  if (t >= T) {
+    return;
+  }
+  WlFrontLds& S = ((WlFrontLds*)smem)[wave];
+  const float* row = P.emissions + P.emOff[b] + (size_t)t * P.N;
+  WlTokRow* out = (WlTokRow*)P.tokRows + (wlCallRowBase(P, b) + t);
+  wlTokBeamRow(P, S, row, out, P.criterion == 1);
+}
+
 struct WlFront {
   double bestChain; /* best candidate of the newest staged frame */
   /* the record of the row the next call stages, loaded a frame ahead: lane l holds list position l */
@@ -470,7 +580,8 @@ FLTX_DEV void wlRowPrefetch(const DecodeParams& P, WlFront& F, int64_t rowIdx, b
 }
 /* Stages the prefetched row into parity q: list (eTok / tokTok / posOf), blank's emission, the frame's best candidate.
  * One wave.  nListOld: the positions of parity q ^ 1's list are taken out of posOf first. */
-FLTX_DEV void wlStageRow(const DecodeParams& P, WlaneLds& S, WlFront& F, int64_t rowIdxNext, bool anyNext, int q,
+template <class LdsT>
+FLTX_DEV void wlStageRow(const DecodeParams& P, LdsT& S, WlFront& F, int64_t rowIdxNext, bool anyNext, int q,
                          double silScore, int nListOld) {
   const int lane = laneId();
   if (lane < nListOld) {
@@ -511,9 +622,15 @@ FLTX_DEV void wlStageRow(const DecodeParams& P, WlaneLds& S, WlFront& F, int64_t
   wlRowPrefetch(P, F, rowIdxNext, anyNext); /* the row after this one on its way into the registers */
 }
 
-template <int GT>
+/* ST: the frames of one decodeStep chunk of a LexiconFreeDecoder stream.  The beam comes from the slots the last launch
+ * (or the generic engine's begin / prune) parked and goes back there in that engine's format, so begin, end, prune,
+ * getBestHypothesis, finish and the partial transcripts stay the kernels they are; LM states are named through that
+ * engine's id table; history rows are its plain records with the token in a word of its own (tokens beyond a byte).
+ * The token beams of the chunk's rows come from fltx_tokbeam_stream_kernel, launched ahead on the same stream. */
+template <int GT, bool ST = false>
 FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
-  WlaneLds& S = *(WlaneLds*)smem;
+  using LdsT = typename std::conditional<ST, WlStreamLds, WlaneLds>::type;
+  LdsT& S = *(LdsT*)smem;
   const int b = P.uttMap ? P.uttMap[blockIdx.x] : (int)blockIdx.x;
   const int W = (int)blockDim.x, tid = (int)threadIdx.x;
   const int lane = laneId(), wave = waveUniform(waveId());
@@ -538,6 +655,15 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
   __asm__ volatile("" : "+v"(silScore)); /* (see fltx_slane.h) */
 #endif
 
+  if constexpr (ST) {
+    if (T == 0) { /* no frames for this stream in this chunk: its parked beam, counters and history stay as they are */
+      if (tid == 0 && P.statusHost) {
+        P.statusHost[b] = P.uttStatus[b];
+      }
+      return;
+    }
+  }
+
   /* ---- decodeBegin (LexiconFreeDecoder.cpp:20-28): the root state ------------------ */
   for (int i = tid; i < 2 * 64; i += W) {
     ((unsigned long long*)S.cmask)[i] = 0ull;
@@ -545,11 +671,13 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
   for (int i = tid; i < 2 * kSlNB; i += W) {
     ((uint32_t*)S.hist)[i] = 0u;
   }
+  if constexpr (!ST) {
   for (int i = tid; i < kWlBloomWords / 4; i += W) {
     ((uint4*)S.bloom)[i] = make_uint4(0u, 0u, 0u, 0u);
   }
   for (int i = tid; i < kWlEdgeSlots / 2; i += W) {
     ((uint4*)S.edge)[i] = make_uint4(0u, 0u, 0u, 0u);
+  }
   }
   for (int i = tid; i < kWlMaxN / 16; i += W) {
     ((uint4*)S.posOf)[i] = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
@@ -560,6 +688,14 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
   if (tid < 16) {
     S.scal[tid] = 0u;
   }
+  if constexpr (ST) {
+    if (tid == 0) {
+      S.row[0].nev = 0u;
+      S.row[1].nev = 0u;
+      S.row[0].dead = 0u;
+      S.row[1].dead = 0u;
+    }
+  } else {
   if (tid == 0) {
     SlRec r;
     r.nb = 0.0;
@@ -578,6 +714,7 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
   if (tid > 0 && tid < K) { /* unused slots of a row never look like the record of a new state (wlReenter) */
     P.histPT[hbase + tid] = make_int2((int)kSlNoHyp, -1);
   }
+  }
   ldsBarrier();
   WlFront F;
   F.bestChain = 0.0; /* decodeBegin: the root hypothesis, score 0 */
@@ -589,8 +726,16 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
   F.pFlags = 0u;
   F.pNList = 0;
   F.pSilPos = -4096;
-  const int64_t rowBase = hbase / K; /* this utterance's records of fltx_tokbeam_kernel */
+  int64_t rowBase; /* this utterance's records of the front-end kernel */
+  if constexpr (ST) {
+    rowBase = wlCallRowBase(P, b);
+  } else {
+    rowBase = hbase / K;
+  }
   if (wave == prepWave) {
+    if constexpr (ST) { /* (the parked beam is sorted: slot 0 is the best hypothesis) */
+      F.bestChain = P.uttNBeam[b] > 0 ? P.gScore[(size_t)b * K] : 0.0;
+    }
     wlRowPrefetch(P, F, rowBase, T > 0);
     if (T > 0) {
       wlStageRow(P, S, F, rowBase + 1, T > 1, 0, silScore, 0);
@@ -598,13 +743,91 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
       S.row[0].nList = 0;
     }
     waveSync();
-    if (lane == 0) { /* the root's token (sil) in the first list */
+    if (!ST && lane == 0) { /* the root's token (sil) in the first list */
       S.rec[0][0].info = (uint32_t)S.posOf[P.sil] | (0u << 8) | (0u << 16) | (kSlNoHyp << 24);
     }
   }
+  if constexpr (ST) {
+    if (tid == 0) {
+      S.scal[SL_NEXTID] = (uint32_t)P.uttNextId[b];
+      S.scal[WL_FRAME0] = (uint32_t)P.uttFrame[b]; /* rows already in the buffer */
+      S.scal[WL_TOTAL0] = (uint32_t)P.uttTotal[b]; /* frames decoded since decodeBegin */
+    }
+  }
   ldsBarrier();
+  if constexpr (ST) {
+    /* ---- restore: the beam parked by the last launch (sorted slots, one hypothesis each) -> lanes, one per LM state;
+     * a slot's number is its hypothesis's slot in the last history row.  After the first row is staged: a lane's record
+     * carries the position of its last token in THAT row's list ------------------------------------------------- */
+    if (wave == 0) {
+      const int nB = P.uttNBeam[b];
+      const bool valid = lane < nB;
+      const size_t g = (size_t)b * K + (valid ? lane : 0);
+      const double sc = P.gScore[g], amv = P.gAm[g];
+      const uint32_t sid = valid ? P.gState[g] : 0xFFFFFFFFu, spar = P.gSPar[g], tp = P.gTokPb[g];
+      const int32_t edge = P.gSEdge[g];
+      const bool isB = (tp & kPrevBlank) != 0u;
+      int leader = lane;
+      for (int i = 0; i < nB && i < 64; ++i) {
+        const uint32_t si = waveReadLane32(sid, i);
+        leader = (valid && si == sid && i < leader) ? i : leader;
+      }
+      const unsigned long long leaders = waveBallot(valid && leader == lane);
+      const int L = popc64(leaders & ((1ull << leader) - 1ull));
+      if (valid && leader == lane) {
+        /* (the start state, and a state whose parent a compaction has cut loose, take no arrival: fltx_xlane.h) */
+        const bool noArr = sid == 0u || P.idPar[(size_t)b * P.idCap + sid] == kNoParent32;
+        const uint32_t tok = sid == 0u ? (uint32_t)P.sil : (uint32_t)edge;
+        SlRec r;
+        r.nb = NEG;
+        r.b = NEG;
+        r.info = tok < (uint32_t)kWlMaxN ? (uint32_t)S.posOf[tok] : kWlNoPos;
+        r.sid = sid;
+        r.spar = noArr ? (spar | kWlNoArrival) : spar;
+        r.pad = tok;
+        S.rec[0][L] = r;
+        S.amNB[0][L] = 0.0;
+        S.amB[0][L] = 0.0;
+        S.rsNB[L] = (uint8_t)kSlNoHyp;
+        S.rsB[L] = (uint8_t)kSlNoHyp;
+      }
+      waveSync();
+      if (valid) {
+        if (isB) {
+          S.rec[0][L].b = sc;
+          S.amB[0][L] = amv;
+          S.rsB[L] = (uint8_t)lane;
+        } else {
+          S.rec[0][L].nb = sc;
+          S.amNB[0][L] = amv;
+          S.rsNB[L] = (uint8_t)lane;
+        }
+      }
+      waveSync();
+      const int nSt = popc64(leaders);
+      /* lane j: history slots of its hypotheses, the lane of its parent state */
+      const bool lv = lane < nSt;
+      const SlRec mine = S.rec[0][lv ? lane : 0];
+      int plr = -1;
+      for (int i = 0; i < nSt; ++i) {
+        const uint32_t si = waveReadLane32(mine.sid, i);
+        plr = (lv && si == mine.spar && i != lane) ? i : plr;
+      }
+      if (lv) {
+        S.rec[0][lane].info = (mine.info & 0xFFu) | ((uint32_t)(plr + 1) << 8) | ((uint32_t)S.rsNB[lane] << 16) |
+                              ((uint32_t)S.rsB[lane] << 24);
+        if (plr >= 0 && (mine.info & 0xFFu) < 64u) {
+          atomOr64(&S.cmask[0][plr], 1ull << (mine.info & 0xFFu));
+        }
+      }
+      if (lane == 0) {
+        S.scal[SL_NSTATE] = (uint32_t)nSt;
+      }
+    }
+    ldsBarrier();
+  }
 
-  int nState = 1;
+  int nState = ST ? (int)S.scal[SL_NSTATE] : 1;
   double endBest = 0.0; /* best hypothesis of the final beam (decodeEnd's threshold) */
   int winShift = kSlCoarseShift, winBase = kSlCoarseBase;
   bool dead = false; /* this utterance goes to the general engines */
@@ -633,7 +856,13 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
   auto frameStep = [&](auto PT, auto RL, const int t) {
     constexpr int p = decltype(PT)::value, q = p ^ 1;
     constexpr bool isSelf = decltype(RL)::value == 1, isSvc = decltype(RL)::value == 2;
-    const int frameOut = t + 1;
+    WlStreamRegs<ST> A;
+    int frameOut = t + 1;
+    if constexpr (ST) {
+      A.frame0 = (int)S.scal[WL_FRAME0];
+      A.total0 = (int)S.scal[WL_TOTAL0];
+      frameOut = A.frame0 + t + 1;
+    }
     const int64_t hrow = hbase + (int64_t)frameOut * K;
     /* ---- phase 1: own state, candidates, histogram ------------------------------------- */
     const double best = S.row[p].best, thr = S.row[p].thr;
@@ -671,7 +900,11 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
     }
 #endif
     if (nev != 0u) { /* rare: edges the filter had seen were taken in the previous build */
-      wlReenter(S, histPT, p, nState, hbase, (int64_t)frameOut * K);
+      if constexpr (ST) {
+        wlRelink(S, p, nState);
+      } else {
+        wlReenter(S, histPT, p, nState, hbase, (int64_t)frameOut * K);
+      }
       me = S.rec[p][lane];
       cm = S.cmask[p][lane];
     }
@@ -688,12 +921,26 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
     const bool whichB = bb > nb;
     const double m = whichB ? bb : nb;
     const uint32_t hypM = whichB ? hypB : hypNB;
+    if constexpr (ST) { /* streams carry the emitting-model score of every hypothesis (getBestHypothesis returns an ancestor's) */
+      A.amNB = isSvc ? 0.0 : S.amNB[p][lane];
+      A.amB = isSvc ? 0.0 : S.amB[p][lane];
+      A.amM = whichB ? A.amB : A.amNB;
+      A.parAmNB = 0.0;
+      A.parAmB = 0.0;
+      A.amR = 0.0;
+      A.prevR = 0u;
+      A.amNew = 0.0;
+    }
     /* self wave: what its groups need beyond the lane's own record (second LDS round trip) */
     SlRec par = {};
     double eLast = 0.0;
     if (isSelf) {
       par = S.rec[p][pl >= 0 ? pl : 0];
       eLast = S.eTok[p][lastPos < 64u ? lastPos : 0u];
+      if constexpr (ST) {
+        A.parAmNB = S.amNB[p][pl >= 0 ? pl : 0];
+        A.parAmB = S.amB[p][pl >= 0 ? pl : 0];
+      }
     }
     mark(0);
     double cs[GT];
@@ -764,6 +1011,10 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
       const bool t2 = has2 & ((r2 > cR) | ((r2 == cR) & (h2 < parR)));
       cR = t2 ? r2 : cR;
       parR = t2 ? h2 : parR;
+      if constexpr (ST) {
+        A.amR = t2 ? A.parAmB : (t1 ? A.parAmNB : A.amNB);
+        A.prevR = t2 ? (uint32_t)blank : (t1 ? lastP : last);
+      }
       const bool okR = lastOk && (has0 || has1 || has2) && cR >= thr;
       const bool okL = ctc && lastOk && hasB && ((cm >> (lastPos & 63u)) & 1ull) == 0ull && cL >= thr;
       cs[0] = cB;
@@ -986,6 +1237,24 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
       r.sid = (uint32_t)frameOut * (uint32_t)K + hyp;
       r.spar = me.sid;
       r.pad = n;
+      if constexpr (ST) {
+        /* the generic engine's (parent id, token) -> id table names the state and remembers that it did: `fresh` = false
+         * is LMState::child's memo.  One candidate per (lane, token) and frame: nobody asks about a pair twice */
+        bool fresh = false;
+        r.sid = tlStreamChild(P, b, me.sid, (int32_t)n, (uint32_t)(A.total0 + t + 1), &S.scal[SL_NEXTID], &S.scal[SL_STATUS], fresh);
+        S.amNB[q][nl] = A.amNew;
+        S.rec[q][nl] = r;
+        if (myNewLane >= 0 && np < 64u) {
+          atomOr64(&S.cmask[q][myNewLane], 1ull << np);
+        }
+        histPT[hrow + hyp] = wlPlainRec(hp, n);
+        wlScoreRec(P, hrow + hyp, c, A.amNew);
+        if (!fresh) { /* entered before: it may have descendants in the beam (wlRelink) */
+          const uint32_t e = atomAdd32(&S.row[q].nev, 1u);
+          S.evLane[e] = (uint32_t)nl;
+          S.evSid[e] = r.sid;
+        }
+      } else {
       const bool again = wlEdgeSeen(S, me.sid, n); /* this edge may have had a child before */
       const uint32_t eslot = wlEdgeSlot(me.sid, n);
       uint32_t known = kWlNoSid;
@@ -1010,11 +1279,13 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
         S.evTok[e] = n;
         S.evSid[e] = known;
       }
+      }
     };
     if (isSvc) {
       /* (its part of the build went ahead of the second barrier) */
     } else if (!isSelf) {
-      if (wave == 0 && lane >= nHSurv + nNew && lane < K) { /* unused slots of the history row: see wlReenter */
+      if (!ST && wave == 0 && lane >= nHSurv + nNew && lane < K) { /* unused slots of the history row: see wlReenter (a
+                                                                       stream's rows are read up to the parked count) */
         histPT[hrow + lane] = make_int2((int)kSlNoHyp, -1);
       }
 #pragma unroll
@@ -1022,6 +1293,9 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
         if (selMask[j] != 0ull) {
           const uint32_t np = nextPosOf(tk[j]);
           if ((selMask[j] >> lane) & 1ull) {
+            if constexpr (ST) {
+              A.amNew = wlAmStep(P, A.total0 + t == 0, A.amM, ev[j], tk[j], whichB ? (uint32_t)blank : last);
+            }
             newState(offW + myNew[j], cs[j], tk[j], np, hypM);
           }
         }
@@ -1042,14 +1316,32 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
         if (pln >= 0 && lastNext < 64u) {
           atomOr64(&S.cmask[q][pln], 1ull << lastNext);
         }
+        if constexpr (ST) {
+          if (sR) {
+            const double a = wlAmStep(P, A.total0 + t == 0, A.amR, eLast, last, A.prevR);
+            S.amNB[q][surv] = a;
+            histPT[hrow + hNB] = wlPlainRec(parR, last);
+            wlScoreRec(P, hrow + hNB, cs[1], a);
+          }
+          if (sB) {
+            const double a = A.amM + eBlank;
+            S.amB[q][surv] = a;
+            histPT[hrow + hB] = wlPlainRec(hypM, (uint32_t)blank);
+            wlScoreRec(P, hrow + hB, cs[0], a);
+          }
+        } else {
         if (sR) {
           histPT[hrow + hNB] = make_int2((int)parR, (int)last);
         }
         if (sB) {
           histPT[hrow + hB] = make_int2((int)hypM, blank);
         }
+        }
       }
       if ((selMask[2] >> lane) & 1ull) {
+        if constexpr (ST) {
+          A.amNew = wlAmStep(P, A.total0 + t == 0, A.amB, eLast, last, (uint32_t)blank);
+        }
         newState(offW + myNew[2], cs[2], last, lastNext, hypB);
       }
     }
@@ -1082,6 +1374,100 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
 
   /* ---- decodeEnd (LexiconFreeDecoder.cpp:127-158): finish() keeps the state, token = sil; the two
    * hypotheses of a state merge; sorted n-best (candidatesStore returnSorted) ------------------ */
+  if constexpr (ST) {
+    /* ---- park the beam for the next launch / prune / getBestHypothesis / decodeEnd: one slot per hypothesis, sorted by
+     * (score descending, history slot ascending), in the generic engine's format; the last history row rewritten in
+     * that order ------------------------------------------------------------------------------------------------ */
+#ifndef FLTX_EMU
+    __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* this wave's history records are in L2 */
+#endif
+    ldsBarrier();
+    /* (the id table full or the ids exhausted: the chunk cannot be finished here either) */
+    const bool failed = dead || S.scal[SL_STATUS] != 0u;
+    const int pe = T & 1;
+    const int frame0 = (int)S.scal[WL_FRAME0], total0 = (int)S.scal[WL_TOTAL0];
+    if (wave == 0 && !failed) {
+      const bool live = lane < nState;
+      const int li = live ? lane : 0;
+      const SlRec me = S.rec[pe][li];
+      const uint32_t sNB = live ? (me.info >> 16) & 0xFFu : kSlNoHyp, sB = live ? me.info >> 24 : kSlNoHyp;
+      const bool hasNB = sNB != kSlNoHyp, hasB = sB != kSlNoHyp;
+      const unsigned long long kNB = hasNB ? f64Key(me.nb) : 0ull, kB = hasB ? f64Key(me.b) : 0ull;
+      int rNB = 0, rB = 0;
+      for (int i = 0; i < nState; ++i) {
+        const unsigned long long k1 = ((unsigned long long)waveReadLane32((uint32_t)(kNB >> 32), i) << 32) |
+                                      waveReadLane32((uint32_t)kNB, i);
+        const unsigned long long k2 = ((unsigned long long)waveReadLane32((uint32_t)(kB >> 32), i) << 32) |
+                                      waveReadLane32((uint32_t)kB, i);
+        const uint32_t s1 = waveReadLane32(sNB, i), s2 = waveReadLane32(sB, i);
+        const bool e1 = s1 != kSlNoHyp, e2 = s2 != kSlNoHyp;
+        rNB += (e1 && (k1 > kNB || (k1 == kNB && s1 < sNB))) ? 1 : 0;
+        rNB += (e2 && (k2 > kNB || (k2 == kNB && s2 < sNB))) ? 1 : 0;
+        rB += (e1 && (k1 > kB || (k1 == kB && s1 < sB))) ? 1 : 0;
+        rB += (e2 && (k2 > kB || (k2 == kB && s2 < sB))) ? 1 : 0;
+      }
+      const int nHyp = popc64(waveBallot(hasNB)) + popc64(waveBallot(hasB));
+      const int64_t hlast = hbase + (int64_t)(frame0 + T) * K;
+      const unsigned long long* hrec = (const unsigned long long*)(histPT + hlast);
+      const unsigned long long recNB = hasNB ? loadCoherent64(hrec + sNB) : 0ull;
+      const unsigned long long recB = hasB ? loadCoherent64(hrec + sB) : 0ull;
+      const double aNB = S.amNB[pe][li], aB = S.amB[pe][li];
+      const uint32_t lastTok = me.pad; /* (the start state's: sil) */
+      const uint32_t sparOut = me.sid == 0u ? kNoParent : (me.spar & ~kWlNoArrival);
+      const int32_t edgeOut = me.sid == 0u ? 0 : (int32_t)lastTok;
+#ifndef FLTX_EMU
+      __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* every lane has its old records before any is rewritten */
+#endif
+      waveSync();
+      auto put = [&](int r, double sc, double am, uint32_t tokpb, unsigned long long rec) {
+        const size_t g = (size_t)b * K + r;
+        P.gScore[g] = sc;
+        P.gAm[g] = am;
+        P.gLm[g] = 0.0;
+        P.gState[g] = me.sid;
+        P.gSPar[g] = sparOut;
+        P.gSEdge[g] = edgeOut;
+        P.gLex[g] = 0u;
+        P.gLexMax[g] = 0.0f;
+        P.gTokPb[g] = tokpb;
+        ((unsigned long long*)(histPT + hlast))[r] = rec;
+        if (P.histS) {
+          double* hs = P.histS + 3 * (hlast + r);
+          hs[0] = sc;
+          hs[1] = am;
+          hs[2] = 0.0;
+        }
+      };
+      if (hasNB) {
+        put(rNB, me.nb, aNB, lastTok, recNB);
+      }
+      if (hasB) {
+        put(rB, me.b, aB, (uint32_t)blank | kPrevBlank, recB);
+      }
+      if (lane == 0) {
+        const int32_t stNow = P.uttStatus[b] | (int32_t)S.scal[SL_STATUS];
+        P.uttNBeam[b] = nHyp;
+        P.uttFrame[b] = frame0 + T;
+        P.uttTotal[b] = total0 + T;
+        P.uttNextId[b] = (int32_t)S.scal[SL_NEXTID];
+        P.uttStatus[b] = stNow;
+        if (P.statusHost) {
+          P.statusHost[b] = stNow;
+        }
+      }
+    }
+    if (failed && tid == 0) {
+      /* a row without a defined token beam or not finite, a select that did not converge, the id table full: this chunk
+       * cannot be finished here.  The beam the chunk started from is in the host layer's snapshot; it puts it back and
+       * decodes the chunk again on the general path (the ids named so far stay in the table: that pass names them too) */
+      const int32_t stNow = P.uttStatus[b] | (int32_t)S.scal[SL_STATUS] | ST_SELECT_FALLBACK;
+      P.uttNextId[b] = (int32_t)S.scal[SL_NEXTID];
+      P.uttStatus[b] = stNow;
+      if (P.statusHost) {
+        P.statusHost[b] = stNow;
+      }
+    }
+  } else {
   const int pe = T & 1;
   const int ff = T + 1;
   if (wave == 0 && !dead) {
@@ -1123,6 +1509,7 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
     P.uttFrame[b] = ff;
     P.uttTotal[b] = ff;
     P.uttStatus[b] = ST_SELECT_FALLBACK;
+  }
   }
   if (profMe) {
 #pragma unroll

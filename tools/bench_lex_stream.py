@@ -1,7 +1,9 @@
 """Lexicon stream chunks: the generic frame loop against a lane engine's stream kernel -- --shape C3 (the default):
 "xstream" = 0 against 1 (fltx_xlane.h); --shape C4: "ystream" = 0 against 1 (fltx_ylane.h, the LM terms), on bench.py's C4
 workload (the trie with label scores, the synthetic 4-gram, lm_weight 2, word_score 2, sil_score -1, beam 100, token beam
-29, T = 1500 unless --T says otherwise).  Below, `xstream` stands for the shape's tunable.
+29, T = 1500 unless --T says otherwise); --shape WP: "wstream" = 0 against 1 (fltx_wlane.h) on bench.py's WP workload
+(LexiconFreeDecoder + ZeroLM over 1 024 word pieces, beam 50, token beam 50, T = 1000).  Below, `xstream` stands for the
+shape's tunable.
 
 The shape bench.py streams as C3 (its workload table: LexiconDecoder + ZeroLM over the 90k-word trie, CTC, N = 29,
 beam 50, token beam 10): --B = 256 streams of --T = 1000 frames in --chunk = 50-frame chunks from host memory,
@@ -13,7 +15,7 @@ from stream_begin to a synchronise after stream_end.  One JSON line per run:
   other setting: must be true)
 and a last line with each setting's median, min and max and the ratio of the medians.
 
-    python tools/bench_lex_stream.py [--shape C3|C4] [--B 256] [--T 1000] [--chunk 50] [--repeat 3] [--sample 16]
+    python tools/bench_lex_stream.py [--shape C3|C4|WP] [--B 256] [--T 1000] [--chunk 50] [--repeat 3] [--sample 16]
 """
 import argparse
 import json
@@ -33,19 +35,19 @@ from text_amd import _capi, synth  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=256)
-    ap.add_argument("--shape", choices=["C3", "C4"], default="C3")
+    ap.add_argument("--shape", choices=["C3", "C4", "WP"], default="C3")
     ap.add_argument("--T", type=int, default=None, help="frames per stream (C3: 1000, C4: 1500)")
     ap.add_argument("--chunk", type=int, default=50)
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--sample", type=int, default=16)
     a = ap.parse_args()
-    c4 = a.shape == "C4"
-    key = "ystream" if c4 else "xstream"
-    B, T, CH, N = a.B, a.T or (1500 if c4 else 1000), a.chunk, 29
-    K, Kt = (100, 29) if c4 else (50, 10)
-    lexicon = synth.lexicon()
-    W = len(lexicon[1]) - 1
-    e_host = synth.batch("lexspell", B, T, N, lexicon=lexicon, u0=0)
+    c4, wp = a.shape == "C4", a.shape == "WP"
+    key = "wstream" if wp else ("ystream" if c4 else "xstream")
+    B, T, CH, N = a.B, a.T or (1500 if c4 else 1000), a.chunk, 1024 if wp else 29
+    K, Kt = (50, 50) if wp else ((100, 29) if c4 else (50, 10))
+    lexicon = None if wp else synth.lexicon()
+    W = 0 if wp else len(lexicon[1]) - 1
+    e_host = synth.batch("ctc" if wp else "lexspell", B, T, N, lexicon=lexicon, u0=0)
     ctx = _capi.Context(device=0)
     wscore = np.zeros(W, dtype=np.float32)
     if c4:  # (as bench.py sets C4 up: trie label scores = lm.score(start, word))
@@ -57,17 +59,22 @@ def main():
     else:
         lm = _capi.ZeroLM(ctx)
         opt = _capi.make_options(K, Kt, 25.0, 0.0, 0.0, float("-inf"), 0.0, False, "ctc")
-    ht = _capi.HostTrie(N, 0)
-    ht.insert_many(lexicon[0], lexicon[1], np.arange(W), wscore)
-    ht.smear(1)
-    trie = ht.upload(ctx)
+    trie = None
+    if not wp:
+        ht = _capi.HostTrie(N, 0)
+        ht.insert_many(lexicon[0], lexicon[1], np.arange(W), wscore)
+        ht.smear(1)
+        trie = ht.upload(ctx)
     nchunk = T // CH
     pieces = [np.ascontiguousarray(e_host[:, k * CH:(k + 1) * CH, :]) for k in range(nchunk)]
     Tc = np.full(B, CH, dtype=np.int32)
     sample = sorted(np.random.RandomState(4242).choice(B, min(a.sample, B), replace=False).tolist())
     decs = {}
     for x in (0, 1):
-        d = decs[x] = _capi.BatchDecoder(ctx, _capi.LEXICON, opt, lm, 0, N - 1, unk=W, trie=trie)
+        if wp:
+            d = decs[x] = _capi.BatchDecoder(ctx, _capi.LEXFREE, opt, lm, 0, N - 1)
+        else:
+            d = decs[x] = _capi.BatchDecoder(ctx, _capi.LEXICON, opt, lm, 0, N - 1, unk=W, trie=trie)
         d.set("stream_total_frames", T)
         d.set(key, x)
 
@@ -105,7 +112,8 @@ def main():
                       "ratio": med[1] / med[0], "nbest_equal": first[0] == first[1]}), flush=True)
     for d in decs.values():
         d.close()
-    trie.close()
+    if trie is not None:
+        trie.close()
     lm.close()
     ctx.close()
     if first[0] != first[1]:
