@@ -1078,7 +1078,11 @@ FLTX_API int fltx_decoder_profile(fltx_decoder* dec, uint64_t* out);
  * max-merge, up to 16 384 tokens, beam and token beam up to 64; the stream is then an optimistic one: a chunk that engine
  * cannot finish, such as one with a frame of equal values, is decoded again on the general path; default 0; set before
  * fltx_stream_begin; fltx_decoder_get "wstream" answers the positions per token wave chosen for the open stream, or 0;
- * results are the same bit for bit), "stream_optimistic" (0 = lexicon
+ * results are the same bit for bit), "wtlane" (1 = an offline lexicon-free decode over a token set beyond 64 with an
+ * n-gram LM over the tokens runs on that engine's token-LM variant where it takes it -- n-gram orders up to 6, max-merge,
+ * CTC and ASG, up to 16 384 tokens, beam and token beam up to 64; the LM is asked through its n-gram tables, filtered and
+ * memoised; default 0: such a decode stays on the generic engine and "why_not_lane" says FLTX_WHY_LM; fltx_decoder_get
+ * "wtlane" answers 1 when the last call ran on the variant; results are the same bit for bit), "stream_optimistic" (0 = lexicon
  * streams use the worst-case HBM workspace from the start instead of decoding an overflowing chunk again),
  * "stream_defer" (0 = fltx_stream_step of a lexicon stream waits for its chunk; default: the chunk is launched and whether
  * a stream has to decode it again is looked at by the next call that needs the beam -- the next chunk's upload runs

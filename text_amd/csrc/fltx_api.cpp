@@ -696,6 +696,8 @@ struct fltx_lm {
   int order = 0;
   int32_t bos = 0, eos = 0, unk = 0, nUsr = 0;
   uint32_t mask = 0;
+  /* bounds of what the n-gram look-up returns for any (context, word): DecodeParams::wtLmMax / wtLmMin */
+  float scoreMax = 0.0f, scoreMin = 0.0f;
   /* device copies of the tables, one set per context (= per device) that has a decoder using this LM */
   struct Dev {
     DBuf tab, backoff, usrToLm;
@@ -843,6 +845,9 @@ struct fltx_decoder {
    * stream an optimistic one: a chunk that engine cannot finish is decoded again): positions per token wave (0 = not
    * used) and threads of the chunks' launch */
   int wstreamAsked = 0, wstream = 0, wstreamThreads = 0;
+  /* ... and of the lexicon-free decoder over a large token set with a token n-gram LM on fltx_wlane.h's TL variant
+   * ("wtlane" = 1 asks for it; wtlaneFirst: the last call started on it) */
+  int wtlaneAsked = 0, wtlane = 0, wtlaneFirst = 0;
   /* streams of the lexicon decoder on the optimistic geometry (LDS workspace, cut-off generation): a chunk that
    * overflows is decoded again from the saved beam on the general path (HBM workspace) */
   int userStreamOpt = 1;
@@ -1358,6 +1363,24 @@ int fltx_lm_ngram_create(fltx_ctx* ctx, int32_t order, int64_t nNgrams, const in
     lm->hBackoff[i] = nodes[i].phantom ? 0.0f : nodes[i].backoff;
   }
   lm->hUsr.assign(usrToLm, usrToLm + (usrToLm ? nUsr : 0));
+  { /* what a look-up can return at most / at least: the extreme probability (-100: no <unk> in the model), then the
+       extreme back-off on that side of 0 once per context length, added in float as the look-up adds them */
+    float pMax = -100.0f, pMin = -100.0f, bMax = 0.0f, bMin = 0.0f;
+    for (size_t i = 1; i < nodes.size(); ++i) {
+      if (!nodes[i].phantom) {
+        pMax = std::max(pMax, nodes[i].prob);
+        pMin = std::min(pMin, nodes[i].prob);
+        bMax = std::max(bMax, nodes[i].backoff);
+        bMin = std::min(bMin, nodes[i].backoff);
+      }
+    }
+    for (int j = 1; j < order; ++j) {
+      pMax += bMax;
+      pMin += bMin;
+    }
+    lm->scoreMax = pMax;
+    lm->scoreMin = pMin;
+  }
   /* the tables go to HBM when a decoder is created on a context */
   {
     std::lock_guard<std::mutex> reg(g_lmRegMu);
@@ -2232,6 +2255,8 @@ int fltx_decoder_get(fltx_decoder* d, const char* key, int64_t* value) {
     *value = d->streamRedone;
   } else if (!strcmp(key, "wlane")) { /* 1: the last call ran on fltx_wlane.h (token sets beyond 64) */
     *value = d->wlaneFirst;
+  } else if (!strcmp(key, "wtlane")) { /* 1: ... on its token-LM variant */
+    *value = d->wtlaneFirst;
   } else if (!strcmp(key, "slane")) {
     *value = d->slaneFirst;
   } else if (!strcmp(key, "slane_m32")) { /* 1: the last call started on fltx_slane.h's kernel with 32-bit token masks */
@@ -2406,6 +2431,10 @@ int fltx_decoder_set(fltx_decoder* d, const char* key, int64_t value) {
     d->wstreamAsked = value ? 1 : 0;
     return FLTX_OK;
   }
+  if (!strcmp(key, "wtlane")) { /* 1: word pieces with a token n-gram LM run on fltx_wlane.h's TL variant where it takes them (default 0) */
+    d->wtlaneAsked = value ? 1 : 0;
+    return FLTX_OK;
+  }
   if (!strcmp(key, "stream_optimistic")) { /* 0: streams of the lexicon decoder start on the worst-case (HBM) workspace */
     d->userStreamOpt = (int)value;
     return FLTX_OK;
@@ -2532,6 +2561,7 @@ struct YstreamGeo {
 static const LaneGeo kSlaneGeo[] = {FLTX_SLANE_GEOS(FLTX_GEO2)};
 static const LaneGeo kSstreamGeo[] = {FLTX_SSTREAM_GEOS(FLTX_GEO2)};
 static const LaneGeo kWlaneGeo[] = {FLTX_WLANE_GEOS(FLTX_GEO2)};
+static const LaneGeo kWtlaneGeo[] = {FLTX_WTLANE_GEOS(FLTX_GEO2)};
 static const LaneGeo kXlaneGeo[] = {FLTX_XLANE_GEOS(FLTX_GEO2)};
 static const LaneGeo kXstreamGeo[] = {FLTX_XSTREAM_GEOS(FLTX_GEO2)};
 static const LaneGeo kWstreamGeo[] = {FLTX_WSTREAM_GEOS(FLTX_GEO2)};
@@ -2563,6 +2593,7 @@ void latchFirst(fltx_decoder* d) {
   d->engineFirst = engineOf(d);
   d->whyFirst = d->whyNotLane;
   d->wlaneFirst = d->wlane;
+  d->wtlaneFirst = d->wtlane;
   d->slaneFirst = d->slane;
   d->slaneM32First = slaneM32(d) ? 1 : 0;
   d->tlaneFirst = d->tlane;
@@ -2777,6 +2808,26 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
       if (nTok <= g.gt * (g.threads / 64 - 2)) {
         d->slane = g.gt;
         d->wlane = 1;
+        d->wlMaxT = maxT;
+        d->threads = g.threads;
+        break;
+      }
+    }
+  }
+  /* ... and with a token n-gram LM over the word pieces, when asked for (wlaneUtterance<.., TL>): the same terms with the
+   * n-gram tables in place of ZeroLM -- the LM is asked through ngScore, filtered and memoised (no dense table at N > 64) */
+  d->wtlane = 0;
+  if (d->wtlaneAsked && d->kind == FLTX_DECODER_LEXFREE && !d->noSlane && !d->noWlane && !d->genericAsked && d->offlineCall &&
+      !d->keepScores && !forceWorstCaseCap && !d->forceGlobalWs && !d->opt.log_add && d->lm->kind == 1 && !d->isLmToken &&
+      N > 64 && N <= kWlMaxN && K <= 64 && nTok <= 64 && optionsOk && (int64_t)K * (maxT + 2) < (1 << 23) - 1) {
+    for (const LaneGeo& g : kWtlaneGeo) {
+      if (d->userThreads && d->threads != g.threads) {
+        continue;
+      }
+      if (nTok <= g.gt * (g.threads / 64 - 2)) {
+        d->slane = g.gt;
+        d->wlane = 1;
+        d->wtlane = 1;
         d->wlMaxT = maxT;
         d->threads = g.threads;
         break;
@@ -3205,7 +3256,8 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
   }
   d->wsInLds = lds;
   if (d->slane) {
-    d->wsBytes = d->wlane          ? sizeof(WlaneLds)
+    d->wsBytes = d->wtlane         ? sizeof(WtLds)
+                 : d->wlane        ? sizeof(WlaneLds)
                  : d->mlaneNG == 2 ? sizeof(MlaneLds<2>)
                  : d->mlaneNG == 4 ? sizeof(MlaneLds<4>)
                  : d->mlaneNG == 8 ? sizeof(MlaneLds<8>)
@@ -3461,6 +3513,8 @@ void fillParams(fltx_decoder* d, DecodeParams& P) {
   P.lmCache = d->useLmCache ? d->lmCache.as<unsigned long long>() : nullptr;
   P.tokLm = d->tokLm; /* (null unless this is a lexicon-free decoder over an n-gram LM with a dense table) */
   P.tokLmStride = d->N + 1;
+  P.wtLmMax = d->lm->scoreMax;
+  P.wtLmMin = d->lm->scoreMin;
   P.tlEdgeSlots = d->tlEdgeSlots;
   P.tlMaskSlots = d->tlMaskSlots;
   P.yBound = d->trie ? std::max(0.0, std::max(d->opt.lm_weight * (double)d->trie->xDeltaMin,
@@ -3528,6 +3582,8 @@ struct LaneKernel {
   FLTX_LK(kTmlane, 0, WW, GG, NG, GPW, SPW, (fltx_decode_kernel_tmlane<WW, GG, NG, GPW, SPW, false>), (mlaneUtterance<GG, NG, GPW, SPW, false, true>)) \
   FLTX_LK(kTmlane, kVarLA, WW, GG, NG, GPW, SPW, (fltx_decode_kernel_tmlane<WW, GG, NG, GPW, SPW, true>), (mlaneUtterance<GG, NG, GPW, SPW, true, true>))
 #define FLTX_LK_WLANE(WW, GG) FLTX_LK(kWlane, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_wlane<WW, GG>), (wlaneUtterance<GG>))
+/* (the token-LM variant: family kWlane, geometry field 1 = 1) */
+#define FLTX_LK_WTLANE(WW, GG) FLTX_LK(kWlane, 0, WW, GG, 1, 0, 0, (fltx_decode_kernel_wtlane<WW, GG>), (wlaneUtterance<GG, false, true>))
 #define FLTX_LK_XLANE(WW, GG)                                                                                       \
   FLTX_LK(kXlane, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane<WW, GG, 0, false>), (xlaneUtterance<GG, 0, false>))  \
   FLTX_LK(kXlane, kVarProf, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane<WW, GG, 0, true>), (xlaneUtterance<GG, 0, false>)) \
@@ -3546,7 +3602,7 @@ struct LaneKernel {
   FLTX_LK(kYlane, (HM ? kVarHM : 0) | kVarProf, WW, NG, RR, LMK, 0, (fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, true>), (ylaneUtterance<NG, RR, LMK, HM, false>))
 static const LaneKernel kLaneKernels[] = {
     FLTX_SLANE_GEOS(FLTX_LK_SLANE) FLTX_TLANE_PROF_GEOS(FLTX_LK_TLANE_PROF) FLTX_SSTREAM_GEOS(FLTX_LK_SSTREAM)
-    FLTX_MLANE_GEOS(FLTX_LK_MLANE) FLTX_TMLANE_GEOS(FLTX_LK_TMLANE) FLTX_WLANE_GEOS(FLTX_LK_WLANE)
+    FLTX_MLANE_GEOS(FLTX_LK_MLANE) FLTX_TMLANE_GEOS(FLTX_LK_TMLANE) FLTX_WLANE_GEOS(FLTX_LK_WLANE) FLTX_WTLANE_GEOS(FLTX_LK_WTLANE)
     FLTX_XLANE_GEOS(FLTX_LK_XLANE) FLTX_XSTREAM_GEOS(FLTX_LK_XSTREAM) FLTX_WSTREAM_GEOS(FLTX_LK_WSTREAM) FLTX_YSTREAM_GEOS(FLTX_LK_YSTREAM) FLTX_YLANE_KERNELS(FLTX_LK_YLANE) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_LK_YLANE_PROF)};
 #undef FLTX_LK
 #undef FLTX_LK_SLANE
@@ -3555,6 +3611,7 @@ static const LaneKernel kLaneKernels[] = {
 #undef FLTX_LK_MLANE
 #undef FLTX_LK_TMLANE
 #undef FLTX_LK_WLANE
+#undef FLTX_LK_WTLANE
 #undef FLTX_LK_XLANE
 #undef FLTX_LK_XSTREAM
 #undef FLTX_LK_WSTREAM
@@ -3581,7 +3638,7 @@ LaneKey laneKeyOf(const fltx_decoder* d) {
   } else if (d->slane && d->mlaneNG > 1) {
     return {d->tlane ? kTmlane : kMlane, la | prof, W, {d->slane, d->mlaneNG, d->mlaneGPW, d->mlaneSPW}};
   } else if (d->slane && d->wlane) {
-    return {kWlane, prof, W, {d->slane, 0, 0, 0}};
+    return {kWlane, prof, W, {d->slane, d->wtlane, 0, 0}};
   } else if (d->slane) {
     return {d->tlane ? kTlane : kSlane, la | prof | (slaneM32(d) ? kVarM32 : 0), W, {d->slane, 0, 0, 0}};
   }

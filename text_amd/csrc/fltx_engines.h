@@ -39,6 +39,9 @@
 /* fltx_wlane.h, token beams over large token sets: X(threads, list positions per wave) */
 #define FLTX_WLANE_GEOS(X) X(576, 5) X(576, 8) X(576, 10)
 
+/* ... with a token n-gram LM over the word pieces (wlaneUtterance<.., TL>), in order of preference: the offline rows */
+#define FLTX_WTLANE_GEOS(X) X(576, 5) X(576, 8) X(576, 10)
+
 /* ... a word-piece stream's chunks (wlane_stream), in order of preference: the offline rows.  31 KB of LDS, but 9 waves
  * of 140 and more VGPRs each: no geometry is offered for two workgroups on a CU */
 #define FLTX_WSTREAM_GEOS(X) X(576, 5) X(576, 8) X(576, 10)

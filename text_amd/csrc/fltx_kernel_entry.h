@@ -78,6 +78,12 @@ __global__ void __launch_bounds__(W) fltx_decode_kernel_wlane(DecodeParams P) {
   extern __shared__ __attribute__((aligned(16))) char fltx_smem[];
   wlaneUtterance<GT>(P, fltx_smem);
 }
+/* ... with a token n-gram LM over the word pieces (TL: filtered, memoised ngScore look-ups; 145 KB of LDS) */
+template <int W, int GT>
+__global__ void __launch_bounds__(W) fltx_decode_kernel_wtlane(DecodeParams P) {
+  extern __shared__ __attribute__((aligned(16))) char fltx_smem[];
+  wlaneUtterance<GT, false, true>(P, fltx_smem);
+}
 /* ... the frames of one decodeStep chunk of a word-piece stream on that engine: beam in and out in the generic engine's
  * parked format, LM-state ids from its table; its kernels do decodeBegin / decodeEnd / prune / getBestHypothesis.  The
  * token beams of the chunk's rows come from fltx_tokbeam_stream_kernel (fltx_api.cpp), launched ahead of it */

@@ -239,6 +239,10 @@ struct DecodeParams {
    * breadth-first id (XNode index), and back; null when the trie has no breadth-first layout */
   const uint32_t* xOld2New;
   const uint32_t* xNew2Old;
+  /* fltx_wlane.h with a token n-gram LM (TL): bounds of what ngScore can return for any (context, word) of the model --
+   * the largest / smallest probability plus order - 1 times the largest back-off above 0 / smallest below 0, summed in
+   * float as ngScore sums (pruned ARPA files carry positive back-offs) */
+  float wtLmMax, wtLmMin;
 };
 
 struct Ws {

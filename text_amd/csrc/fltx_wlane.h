@@ -25,6 +25,9 @@
  *     4 096 edges in LDS, then in the history rows (slReenter's scan, which finds the new record itself when the hit
  *     was false) --, so the filter only has to be free of false negatives.
  *
+ * TL (wlaneUtterance<GT, false, true>, opt-in through "wtlane"): the same with a token n-gram LM over the word pieces,
+ * see the comment at WtLds below; one more barrier per frame (the frame's best is a reduction).
+ *
  * Roles and barriers as in fltx_slane.h: token waves (GT list positions each), one wave for the lanes' own groups
  * (blank, repeat + the parent state's extension, blank-then-last), the staging wave; three barriers per frame.
  */
@@ -106,6 +109,71 @@ struct WlStreamRegs<true> {
   double amNew;                        /* ... of the state newState() is about to make */
 };
 enum { WL_FRAME0 = 6, WL_TOTAL0 = 7 }; /* scal[], next to fltx_slane.h's SL_* */
+
+/* ---- TL: a token n-gram LM over the word pieces (wlaneUtterance<GT, false, true>) -------------------------------------
+ * fltx_slane.h's TL pattern (read the head comment there: an LM term per new-token candidate, the frame's best a
+ * reduction behind one more barrier, decodeEnd adds lmWeight x finish, the LM score of every path is returned) without
+ * its dense (context, token) table, which N > 64 has no room for.  A look-up is ngScore(context, usrToLm[token]), a
+ * chain of dependent probes of ~4 k clocks; what keeps them few:
+ *   filter   the candidates without a new LM term (a lane's blank and its own repeat) are priced by every wave from the
+ *            records it holds anyway; their maximum bounds the frame's best from below.  A (lane, position) pair whose
+ *            score with the LM's extreme term (DecodeParams::wtLmMax / wtLmMin, by lmWeight's sign) stays under that
+ *            bound - beamThreshold cannot pass the frame's threshold and asks nothing: rounding is monotone, so the
+ *            drop is exact;
+ *   memo     lmMemo: (state id, token) -> score, direct-mapped in LDS, slot and tag together hold the whole key (lmCache's
+ *            layout, fltx_kernels.h): a hit is exact.  One 64-bit word per entry, written and read whole by waves that
+ *            nothing orders: the exactness rests on the compiler emitting one 64-bit LDS operation per access (an
+ *            aligned unsigned long long; lmCache and `edge` assume the same of their 64-bit words);
+ *   drain    the misses of a wave are asked a lane at a time, every lane's next miss side by side (ngScoreT issues all
+ *            context lengths of a query at once);
+ *   context  a state's n-gram context (order - 1 suffix node ids) lives with its lane (ctx, double-buffered like rec): a
+ *            new state's is the ctxOut of the edge that entered it, asked for the survivors only, in the build;
+ *   lmIn     the LM score a state was entered with: the parent state's extension by last(S) joins S's repeat group with
+ *            exactly that term;
+ *   lmNB/lmB the LM score of a lane's two hypotheses, carried like a stream's emitting-model score (the winner of a
+ *            max-merge hands on its own): the back-trace has nothing to re-walk. */
+constexpr int kWtMemoSlots = 2048; /* 16 KB: with the members below 145 KB of the CU's 160 */
+constexpr int kWtCtx = kMaxNgramOrder - 1;
+struct WtLds : WlaneLds {
+  unsigned long long fbest[2];     /* order key of the frame's best candidate, 0 = none yet */
+  double lmNB[2][64], lmB[2][64];
+  float lmIn[2][64];
+  int32_t ctx[2][kWtCtx][64];
+  uint32_t stat[4];                /* profile: pairs, pairs the filter dropped, look-ups, memo hits */
+  unsigned long long lmMemo[kWtMemoSlots]; /* tag (state id << 3 | token >> 11) << 32 | float bits of the score */
+};
+static_assert(sizeof(WtLds) <= 160 * 1024, "one CU's LDS");
+template <bool TL, int GT>
+struct WlTokLmRegs {};
+template <int GT>
+struct WlTokLmRegs<true, GT> {
+  int32_t ctx[kWtCtx];   /* the lane's context */
+  double thrLB;          /* lower bound of the frame's threshold */
+  float lmv[GT];         /* LM score of the lane's candidates (self wave: [2] = blank-then-last) */
+  bool pre[GT];          /* ... which are candidates at all */
+  float lIn;             /* self wave: the score the state was entered with */
+  double lmNB, lmB, parLmNB, parLmB; /* LM score of the lane's two hypotheses, of its parent lane's */
+  double lmR;            /* ... of the repeat group's winning member */
+  float lmE;             /* the state newState() is about to make: the score it is entered with ... */
+  double lmNew;          /* ... and its hypothesis's LM score */
+};
+/* ... and what the utterance keeps across its frames */
+template <bool TL>
+struct WlTokLmUtt {};
+template <>
+struct WlTokLmUtt<true> {
+  double lmW;      /* lmWeight */
+  double wU;       /* lmWeight x the LM's extreme score on the side its sign makes the upper one (the filter's bound) */
+  bool prof;       /* the phase clocks are on: count */
+  uint32_t cnt[4]; /* ... this lane's pairs, pairs the filter dropped, look-ups, memo hits */
+};
+FLTX_DEV uint32_t wtMemoSlot(uint32_t sid, uint32_t tok) { return (tok ^ sid ^ (sid >> 11)) & (uint32_t)(kWtMemoSlots - 1); }
+FLTX_DEV uint32_t wtMemoTag(uint32_t sid, uint32_t tok) { return (sid << 3) | (tok >> 11); }
+/* lm.score(context, token) (KenLM.cpp:63-75): tokens outside the LM's vocabulary are <unk>, as lmScoreDev */
+FLTX_DEV float wtNgram(const DecodeParams& P, const int32_t* ctx, uint32_t tok, int32_t* ctxOut) {
+  const uint32_t word = tok < (uint32_t)P.nUsr ? (uint32_t)P.usrToLm[tok] : (uint32_t)P.lmUnk;
+  return P.lmOrder <= 3 ? ngScoreT<3>(P, ctx, word, ctxOut) : ngScoreT<kMaxNgramOrder>(P, ctx, word, ctxOut);
+}
 /* LexiconFreeDecoder.cpp:58-64: the ASG transition enters the emitting-model score only */
 FLTX_DEV double wlAmStep(const DecodeParams& P, bool first, double amPrev, double e, uint32_t n, uint32_t prevTok) {
   double x = e;
@@ -556,7 +624,10 @@ FLTX_DEV void wlTokBeamRowsCall(const DecodeParams& P, char* smem) {
 }
 
 struct WlFront {
-  double bestChain; /* best candidate of the newest staged frame */
+  double bestChain; /* best candidate of the newest staged frame.  With a token LM (TL) it is the chain of the rows' best
+                       emissions only, no frame's best candidate: `best` / `thr` staged from it are replaced behind
+                       barrier 0, and what it still decides is WlRow::dead -- a row whose best emissions do not add up to
+                       a finite number sends the utterance to the general engines, as a non-finite frame's best does */
   /* the record of the row the next call stages, loaded a frame ahead: lane l holds list position l */
   float pe;
   uint32_t ptok;
@@ -627,9 +698,10 @@ FLTX_DEV void wlStageRow(const DecodeParams& P, LdsT& S, WlFront& F, int64_t row
  * getBestHypothesis, finish and the partial transcripts stay the kernels they are; LM states are named through that
  * engine's id table; history rows are its plain records with the token in a word of its own (tokens beyond a byte).
  * The token beams of the chunk's rows come from fltx_tokbeam_stream_kernel, launched ahead on the same stream. */
-template <int GT, bool ST = false>
+template <int GT, bool ST = false, bool TL = false>
 FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
-  using LdsT = typename std::conditional<ST, WlStreamLds, WlaneLds>::type;
+  static_assert(!(ST && TL), "streams with a token LM stay on the generic engine");
+  using LdsT = typename std::conditional<ST, WlStreamLds, typename std::conditional<TL, WtLds, WlaneLds>::type>::type;
   LdsT& S = *(LdsT*)smem;
   const int b = P.uttMap ? P.uttMap[blockIdx.x] : (int)blockIdx.x;
   const int W = (int)blockDim.x, tid = (int)threadIdx.x;
@@ -714,6 +786,27 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
   if (tid > 0 && tid < K) { /* unused slots of a row never look like the record of a new state (wlReenter) */
     P.histPT[hbase + tid] = make_int2((int)kSlNoHyp, -1);
   }
+  }
+  if constexpr (TL) {
+    for (int i = tid; i < kWtMemoSlots; i += W) {
+      S.lmMemo[i] = ~0ull; /* (no state id reaches this tag) */
+    }
+    if (tid < 4) {
+      S.stat[tid] = 0u;
+    }
+    if (tid == 0) { /* KenLM::start(false): context = <s> (KenLM.cpp:57), as the generic engine's decodeBegin */
+      uint32_t node = 0u;
+      float pr;
+      const bool ok = ngFind(P, 0u, (uint32_t)P.lmBos, node, pr);
+      for (int k = 0; k < kWtCtx; ++k) {
+        S.ctx[0][k][0] = (k == 0 && ok) ? (int32_t)node : 0;
+      }
+      S.lmNB[0][0] = 0.0;
+      S.lmB[0][0] = 0.0;
+      S.lmIn[0][0] = 0.0f;
+      S.fbest[0] = 0ull;
+      S.fbest[1] = 0ull;
+    }
   }
   ldsBarrier();
   WlFront F;
@@ -852,6 +945,13 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
 #ifndef FLTX_EMU
   __asm__ volatile("" : "+v"(posBase));
 #endif
+  WlTokLmUtt<TL> U; /* (empty without a token LM, and touched under `if constexpr (TL)` alone) */
+  if constexpr (TL) {
+    U.lmW = P.lmWeight;
+    U.wU = U.lmW >= 0.0 ? U.lmW * (double)P.wtLmMax : U.lmW * (double)P.wtLmMin;
+    U.prof = P.prof != nullptr;
+    U.cnt[0] = U.cnt[1] = U.cnt[2] = U.cnt[3] = 0u;
+  }
 
   auto frameStep = [&](auto PT, auto RL, const int t) {
     constexpr int p = decltype(PT)::value, q = p ^ 1;
@@ -865,7 +965,8 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
     }
     const int64_t hrow = hbase + (int64_t)frameOut * K;
     /* ---- phase 1: own state, candidates, histogram ------------------------------------- */
-    const double best = S.row[p].best, thr = S.row[p].thr;
+    double best = S.row[p].best, thr = S.row[p].thr; /* (TL: the reduction behind barrier 0 replaces both) */
+    WlTokLmRegs<TL, GT> L;
     const int nList = S.row[p].nList, silPos = S.row[p].silPos;
     const uint32_t rowDead = S.row[p].dead;
     const uint32_t nev = S.row[p].nev;
@@ -942,6 +1043,44 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
         A.parAmB = S.amB[p][pl >= 0 ? pl : 0];
       }
     }
+    if constexpr (TL) {
+      L.thrLB = NEG;
+      L.lIn = 0.0f;
+      L.lmE = 0.0f;
+      L.lmNew = 0.0;
+      L.lmR = 0.0;
+      L.parLmNB = 0.0;
+      L.parLmB = 0.0;
+      if (!isSvc) {
+#pragma unroll
+        for (int k = 0; k < kWtCtx; ++k) {
+          L.ctx[k] = S.ctx[p][k][lane];
+        }
+        L.lmNB = S.lmNB[p][lane];
+        L.lmB = S.lmB[p][lane];
+        /* the filter's bound: the lanes' blank and own-repeat candidates carry no new LM term and are candidates of this
+         * frame, so their maximum is at most the frame's best; every wave prices them from the records it holds */
+        const double eB = S.row[p].eBlank; /* (NaN: blank is not in the token beam) */
+        const double eL0 = S.eTok[p][lastPos < 64u ? lastPos : 0u];
+        double cb = m + eB, r0 = nb + eL0;
+        if (blank == P.sil) {
+          cb = cb + silScore;
+        }
+        if ((int)lastPos == silPos) {
+          r0 = r0 + silScore;
+        }
+        unsigned long long k = (ctc && live && cb == cb) ? f64Key(cb) : 0ull;
+        const unsigned long long k2 = (live && lastPos < 64u && hypNB != kSlNoHyp && r0 == r0) ? f64Key(r0) : 0ull;
+        k = k2 > k ? k2 : k;
+        k = waveMax64(k);
+        L.thrLB = k != 0ull ? f64FromKey(k) - P.beamThreshold : NEG;
+      }
+      if (isSelf) {
+        L.lIn = S.lmIn[p][lane];
+        L.parLmNB = S.lmNB[p][pl >= 0 ? pl : 0];
+        L.parLmB = S.lmB[p][pl >= 0 ? pl : 0];
+      }
+    }
     mark(0);
     double cs[GT];
     int cbin[GT];
@@ -971,9 +1110,15 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
         if (pos == silPos) {
           c = c + silScore;
         }
+        if constexpr (TL) { /* (the LM term, the threshold and the bin follow below) */
+          L.pre[j] = pos < 64 && ((skip >> (pos & 63)) & 1ull) == 0ull && c == c;
+          cs[j] = c;
+          cbin[j] = kSlInvalid;
+        } else {
         const bool ok = pos < 64 && ((skip >> (pos & 63)) & 1ull) == 0ull && c >= thr;
         cs[j] = c;
         cbin[j] = ok ? slBin<false>(best, c, winShift, winBase) : kSlInvalid;
+        }
       }
     } else {
       const bool lastOk = live && lastPos < 64u; /* the last token is in the frame's token beam (never blank) */
@@ -1002,6 +1147,11 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
         r2 = lastSil ? r2 + silScore : r2;
         cL = lastSil ? cL + silScore : cL;
       }
+      if constexpr (TL) { /* the parent state's extension by last(S) is a new-token candidate: the term S was entered with */
+        const double wIn = U.lmW * (double)L.lIn;
+        r1 = r1 + wIn;
+        r2 = r2 + wIn;
+      }
       /* max-merge (Utils.h:194-196); a tie goes to the lower history slot */
       double cR = r0;
       parR = hypNB;
@@ -1028,6 +1178,93 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
         cs[j] = NEG;
         cbin[j] = kSlInvalid;
       }
+      if constexpr (TL) { /* (blank-then-last is a new-token candidate of the lane's own: position 2 asks the LM below) */
+        L.lmR = t2 ? L.parLmB + (double)L.lIn : (t1 ? L.parLmNB + (double)L.lIn : L.lmNB);
+#pragma unroll
+        for (int j = 0; j < GT; ++j) {
+          L.pre[j] = false;
+        }
+        L.pre[0] = ctc && live && cB == cB;
+        L.pre[1] = lastOk && (has0 || has1 || has2) && cR == cR;
+        L.pre[2] = ctc && lastOk && hasB && ((cm >> (lastPos & 63u)) & 1ull) == 0ull && cL == cL;
+        tk[2] = last;
+      }
+    }
+    if constexpr (TL) {
+      if (!isSvc) {
+        /* which of these candidates ask the LM: a token wave's all, the own-groups wave's third */
+        constexpr uint32_t lmSlots = isSelf ? 4u : (1u << GT) - 1u;
+        uint32_t need = 0u;
+#pragma unroll
+        for (int j = 0; j < GT; ++j) {
+          L.lmv[j] = 0.0f;
+          if (((lmSlots >> j) & 1u) != 0u && L.pre[j]) {
+            const bool ask = !(cs[j] + U.wU < L.thrLB); /* (below the bound with the LM's best term: cannot reach the threshold) */
+            L.pre[j] = ask;
+            bool hit = false;
+            if (ask) {
+              const unsigned long long e = S.lmMemo[wtMemoSlot(me.sid, tk[j])];
+              hit = (uint32_t)(e >> 32) == wtMemoTag(me.sid, tk[j]);
+              L.lmv[j] = hit ? __uint_as_float((uint32_t)e) : 0.0f;
+              need |= hit ? 0u : (1u << j);
+            }
+            if (U.prof) {
+              U.cnt[0] += 1u;
+              U.cnt[1] += ask ? 0u : 1u;
+              U.cnt[2] += ask ? 1u : 0u;
+              U.cnt[3] += hit ? 1u : 0u;
+            }
+          }
+        }
+        while (waveBallot(need != 0u) != 0ull) { /* the misses: every lane's next one side by side */
+          if (need != 0u) {
+            const int jj = __builtin_ctz(need);
+            need &= need - 1u;
+            uint32_t tok = 0u;
+#pragma unroll
+            for (int j = 0; j < GT; ++j) {
+              tok = j == jj ? tk[j] : tok;
+            }
+            const float v = wtNgram(P, L.ctx, tok, nullptr);
+            S.lmMemo[wtMemoSlot(me.sid, tok)] = ((unsigned long long)wtMemoTag(me.sid, tok) << 32) | (unsigned long long)__float_as_uint(v);
+#pragma unroll
+            for (int j = 0; j < GT; ++j) {
+              L.lmv[j] = j == jj ? v : L.lmv[j];
+            }
+          }
+        }
+        /* LexiconFreeDecoder.cpp:79: score + lmWeight * lmScore */
+        unsigned long long k = 0ull;
+#pragma unroll
+        for (int j = 0; j < GT; ++j) {
+          if (((lmSlots >> j) & 1u) != 0u) {
+            cs[j] = cs[j] + U.lmW * (double)L.lmv[j];
+          }
+          const unsigned long long kc = (L.pre[j] && cs[j] == cs[j]) ? f64Key(cs[j]) : 0ull;
+          k = kc > k ? kc : k;
+        }
+        /* the frame's best candidate (Utils.h:131-137) is a maximum over the candidates: one LDS max per wave */
+        if (waveBallot(k != 0ull) != 0ull) {
+          k = waveMax64(k);
+          if (lane == 0) {
+            atomMax64(&S.fbest[p], k);
+          }
+        }
+      }
+      ldsBarrier(); /* 0: the frame's best candidate */
+      const unsigned long long bk = S.fbest[p];
+      best = f64FromKey(bk);
+      thr = best - P.beamThreshold;
+      if (bk == 0ull || !(best - best == 0.0)) { /* no candidate at all, or not finite: the general engines */
+        dead = true;
+        return;
+      }
+      if (!isSvc) {
+#pragma unroll
+        for (int j = 0; j < GT; ++j) {
+          cbin[j] = (L.pre[j] && cs[j] >= thr) ? slBin<false>(best, cs[j], winShift, winBase) : kSlInvalid;
+        }
+      }
     }
     if (wave == 0) { /* housekeeping for everybody: what this frame's build adds to */
       S.cmask[q][lane] = 0ull;
@@ -1036,6 +1273,9 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
       }
       if (lane == 0) {
         S.scal[SL_BCNT] = 0u;
+        if constexpr (TL) {
+          S.fbest[q] = 0ull; /* (the next frame's; last read a frame ago) */
+        }
       }
     }
 #pragma unroll
@@ -1268,6 +1508,11 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
         S.edge[eslot] = wlEdgePack(me.sid, n, r.sid);
       }
       S.rec[q][nl] = r;
+      if constexpr (TL) {
+        S.lmNB[q][nl] = L.lmNew;
+        S.lmB[q][nl] = 0.0;
+        S.lmIn[q][nl] = L.lmE;
+      }
       if (myNewLane >= 0 && np < 64u) {
         atomOr64(&S.cmask[q][myNewLane], 1ull << np);
       }
@@ -1295,6 +1540,10 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
           if ((selMask[j] >> lane) & 1ull) {
             if constexpr (ST) {
               A.amNew = wlAmStep(P, A.total0 + t == 0, A.amM, ev[j], tk[j], whichB ? (uint32_t)blank : last);
+            }
+            if constexpr (TL) { /* LexiconFreeDecoder.cpp:85: prevHyp.lmScore + lmScore */
+              L.lmE = L.lmv[j];
+              L.lmNew = (whichB ? L.lmB : L.lmNB) + (double)L.lmv[j];
             }
             newState(offW + myNew[j], cs[j], tk[j], np, hypM);
           }
@@ -1337,12 +1586,61 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
           histPT[hrow + hB] = make_int2((int)hypM, blank);
         }
         }
+        if constexpr (TL) { /* the state keeps its context and the term it was entered with; blank adds no LM score */
+#pragma unroll
+          for (int k = 0; k < kWtCtx; ++k) {
+            S.ctx[q][k][surv] = L.ctx[k];
+          }
+          S.lmIn[q][surv] = L.lIn;
+          S.lmNB[q][surv] = sR ? L.lmR : 0.0;
+          S.lmB[q][surv] = sB ? (whichB ? L.lmB : L.lmNB) : 0.0;
+        }
       }
       if ((selMask[2] >> lane) & 1ull) {
         if constexpr (ST) {
           A.amNew = wlAmStep(P, A.total0 + t == 0, A.amB, eLast, last, (uint32_t)blank);
         }
+        if constexpr (TL) {
+          L.lmE = L.lmv[2];
+          L.lmNew = L.lmB + (double)L.lmv[2];
+        }
         newState(offW + myNew[2], cs[2], last, lastNext, hypB);
+      }
+    }
+    if constexpr (TL) {
+      if (!isSvc) {
+        /* the contexts of the new states: ctxOut of the edge that enters them, asked for the survivors only -- every
+         * lane's next one side by side */
+        constexpr uint32_t lmSlots = isSelf ? 4u : (1u << GT) - 1u;
+        uint32_t todo = 0u;
+#pragma unroll
+        for (int j = 0; j < GT; ++j) {
+          todo |= (((lmSlots >> j) & 1u) != 0u && ((selMask[j] >> lane) & 1ull) != 0ull) ? (1u << j) : 0u;
+        }
+        while (waveBallot(todo != 0u) != 0ull) {
+          if (todo != 0u) {
+            const int jj = __builtin_ctz(todo);
+            todo &= todo - 1u;
+            uint32_t tok = 0u;
+            int idx = 0;
+#pragma unroll
+            for (int j = 0; j < GT; ++j) {
+              tok = j == jj ? tk[j] : tok;
+              idx = j == jj ? myNew[j] : idx;
+            }
+            int32_t co[kWtCtx];
+#pragma unroll
+            for (int k = 0; k < kWtCtx; ++k) {
+              co[k] = 0;
+            }
+            wtNgram(P, L.ctx, tok, co);
+            const int nl = nSurv + offW + idx;
+#pragma unroll
+            for (int k = 0; k < kWtCtx; ++k) {
+              S.ctx[q][k][nl] = co[k];
+            }
+          }
+        }
       }
     }
     nState = nSurv + nNew;
@@ -1475,10 +1773,25 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
     const SlRec me = S.rec[pe][live ? lane : 0];
     const double nb = live ? me.nb : NEG, bb = live ? me.b : NEG;
     const bool whichB = bb > nb;
-    const double m = whichB ? bb : nb;
+    double m = whichB ? bb : nb;
     const uint32_t hp = whichB ? (me.info >> 24) : ((me.info >> 16) & 0xFFu);
+    float fin = 0.0f;
+    if constexpr (TL) {
+      /* lm->finish(state) (KenLM.cpp:77-83: </s> in the state's context): both hypotheses of a state add the same term;
+       * the best candidate of decodeEnd is a maximum again */
+      int32_t cx[kWtCtx];
+#pragma unroll
+      for (int k = 0; k < kWtCtx; ++k) {
+        cx[k] = S.ctx[pe][k][live ? lane : 0];
+      }
+      fin = P.lmOrder <= 3 ? ngScoreT<3>(P, cx, (uint32_t)P.lmEos, nullptr) : ngScoreT<kMaxNgramOrder>(P, cx, (uint32_t)P.lmEos, nullptr);
+      m = m + U.lmW * (double)fin;
+      const bool has = live && hp != kSlNoHyp && m == m;
+      const unsigned long long k = waveMax64(has ? f64Key(m) : 0ull);
+      endBest = k != 0ull ? f64FromKey(k) : 0.0;
+    }
     const double thr = endBest - P.beamThreshold;
-    const bool ok = live && m >= thr;
+    const bool ok = live && m >= thr && (!TL || hp != kSlNoHyp);
     const unsigned long long key = ok ? f64Key(m) : 0ull;
     int rank = 0;
     for (int i = 0; i < nState; ++i) {
@@ -1493,6 +1806,9 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
       P.outScores[g + 0] = m;
       P.outScores[g + 1] = 0.0; /* emitting-model score: the back-trace kernel fills it in */
       P.outScores[g + 2] = 0.0; /* ZeroLM */
+      if constexpr (TL) { /* LexiconFreeDecoder.cpp:146: prevHyp.lmScore + lmScore */
+        P.outScores[g + 2] = (whichB ? S.lmB[pe][lane] : S.lmNB[pe][lane]) + (double)fin;
+      }
       P.histPT[hbase + (int64_t)ff * K + rank] = make_int2((int)hp, P.sil);
     }
     if (lane == 0) {
@@ -1510,6 +1826,19 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
     P.uttTotal[b] = ff;
     P.uttStatus[b] = ST_SELECT_FALLBACK;
   }
+  }
+  if constexpr (TL) {
+    if (U.prof) { /* marks 6 / 7: pairs | pairs the filter dropped << 32, look-ups | memo hits << 32 */
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        if (U.cnt[i] != 0u) {
+          atomAdd32(&S.stat[i], U.cnt[i]);
+        }
+      }
+      ldsBarrier();
+      acc[6] = (unsigned long long)S.stat[0] | ((unsigned long long)S.stat[1] << 32);
+      acc[7] = (unsigned long long)S.stat[2] | ((unsigned long long)S.stat[3] << 32);
+    }
   }
   if (profMe) {
 #pragma unroll
