@@ -1082,7 +1082,12 @@ FLTX_API int fltx_decoder_profile(fltx_decoder* dec, uint64_t* out);
  * n-gram LM over the tokens runs on that engine's token-LM variant where it takes it -- n-gram orders up to 6, max-merge,
  * CTC and ASG, up to 16 384 tokens, beam and token beam up to 64; the LM is asked through its n-gram tables, filtered and
  * memoised; default 0: such a decode stays on the generic engine and "why_not_lane" says FLTX_WHY_LM; fltx_decoder_get
- * "wtlane" answers 1 when the last call ran on the variant; results are the same bit for bit), "stream_optimistic" (0 = lexicon
+ * "wtlane" answers 1 when the last call ran on the variant; results are the same bit for bit), "wtstream" (1 = "wstream" for a
+ * lexicon-free stream with an n-gram LM over the tokens: its chunks run on that engine's stream + token-LM variant where it
+ * takes them -- "wstream"'s terms and "wtlane"'s n-gram orders; an optimistic stream as under "wstream"; default 0: such a
+ * stream stays on the generic engine and "why_not_lane" says FLTX_WHY_STREAM; set before fltx_stream_begin;
+ * fltx_decoder_get "wtstream" answers the positions per token wave chosen for the open stream, or 0; "wstream" alone
+ * never takes a stream with an n-gram LM; results are the same bit for bit), "stream_optimistic" (0 = lexicon
  * streams use the worst-case HBM workspace from the start instead of decoding an overflowing chunk again),
  * "stream_defer" (0 = fltx_stream_step of a lexicon stream waits for its chunk; default: the chunk is launched and whether
  * a stream has to decode it again is looked at by the next call that needs the beam -- the next chunk's upload runs

@@ -845,6 +845,8 @@ struct fltx_decoder {
    * stream an optimistic one: a chunk that engine cannot finish is decoded again): positions per token wave (0 = not
    * used) and threads of the chunks' launch */
   int wstreamAsked = 0, wstream = 0, wstreamThreads = 0;
+  /* ... and the same with a token n-gram LM over the word pieces (ST + TL; "wtstream" = 1 asks for it, as "wstream") */
+  int wtstreamAsked = 0, wtstream = 0, wtstreamThreads = 0;
   /* ... and of the lexicon-free decoder over a large token set with a token n-gram LM on fltx_wlane.h's TL variant
    * ("wtlane" = 1 asks for it; wtlaneFirst: the last call started on it) */
   int wtlaneAsked = 0, wtlane = 0, wtlaneFirst = 0;
@@ -2233,6 +2235,8 @@ int fltx_decoder_get(fltx_decoder* d, const char* key, int64_t* value) {
     *value = d->ystream;
   } else if (!strcmp(key, "wstream")) { /* positions per token wave of fltx_wlane.h's stream kernel chosen for the open stream, or 0 */
     *value = d->wstream;
+  } else if (!strcmp(key, "wtstream")) { /* ... of its token-LM variant */
+    *value = d->wtstream;
   } else if (!strcmp(key, "tstream")) { /* 1: the stream's chunks run on the token-LM variant of fltx_slane.h */
     *value = d->tstream;
   } else if (!strcmp(key, "looks_dropped")) { /* defer_check = 2: batches that were overwritten without a look at their statuses */
@@ -2431,6 +2435,10 @@ int fltx_decoder_set(fltx_decoder* d, const char* key, int64_t value) {
     d->wstreamAsked = value ? 1 : 0;
     return FLTX_OK;
   }
+  if (!strcmp(key, "wtstream")) { /* 1: ... and so do those of a stream with a token n-gram LM, on its ST + TL variant (default 0) */
+    d->wtstreamAsked = value ? 1 : 0;
+    return FLTX_OK;
+  }
   if (!strcmp(key, "wtlane")) { /* 1: word pieces with a token n-gram LM run on fltx_wlane.h's TL variant where it takes them (default 0) */
     d->wtlaneAsked = value ? 1 : 0;
     return FLTX_OK;
@@ -2565,6 +2573,7 @@ static const LaneGeo kWtlaneGeo[] = {FLTX_WTLANE_GEOS(FLTX_GEO2)};
 static const LaneGeo kXlaneGeo[] = {FLTX_XLANE_GEOS(FLTX_GEO2)};
 static const LaneGeo kXstreamGeo[] = {FLTX_XSTREAM_GEOS(FLTX_GEO2)};
 static const LaneGeo kWstreamGeo[] = {FLTX_WSTREAM_GEOS(FLTX_GEO2)};
+static const LaneGeo kWtstreamGeo[] = {FLTX_WTSTREAM_GEOS(FLTX_GEO2)};
 static const YstreamGeo kYstreamGeo[] = {FLTX_YSTREAM_GEOS(FLTX_GEO3)};
 static const MlaneGeo kMlaneGeo[] = {FLTX_MLANE_GEOS(FLTX_GEO5)}; /* "mlane_geo" = row */
 static const MlaneGeo kTmlaneGeo[] = {FLTX_TMLANE_GEOS(FLTX_GEO5)};
@@ -3046,9 +3055,24 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
       }
     }
   }
+  /* ... and with a token n-gram LM over the word pieces (wlaneUtterance<.., ST, TL>), when asked for: "wstream"'s terms with
+   * the n-gram tables in place of ZeroLM (any order the tables hold, as "wtlane"); a state's context lives in its id's
+   * stateCtx row between chunks, and every id fits the score memo's tag (fltx_wlane.h kWtsMaxSid) */
+  d->wtstream = 0;
+  if (d->wtstreamAsked && d->kind == FLTX_DECODER_LEXFREE && !d->noSlane && !d->noWlane && !d->genericAsked && !d->offlineCall &&
+      d->keepScores && d->streamOpt && d->recycle && !d->forceGlobalWs && !d->opt.log_add && d->lm->kind == 1 &&
+      !d->isLmToken && N > 64 && N <= kWlMaxN && K <= 64 && nTok <= 64 && optionsOk && streamIds <= (int64_t)kWtsMaxSid) {
+    for (const LaneGeo& g : kWtstreamGeo) {
+      if (nTok <= g.gt * (g.threads / 64 - 2)) {
+        d->wtstream = g.gt;
+        d->wtstreamThreads = g.threads;
+        break;
+      }
+    }
+  }
   { /* which eligibility terms kept this call off the lane engines (fltx_decoder_get "why_not_lane") */
     int64_t why = 0;
-    if (!(d->slane || d->xlane || d->ylane || d->sstream || d->xstream || d->ystream || d->wstream)) {
+    if (!(d->slane || d->xlane || d->ylane || d->sstream || d->xstream || d->ystream || d->wstream || d->wtstream)) {
       const bool lexi = d->kind == FLTX_DECODER_LEXICON;
       const bool unkOn = d->opt.unk_score > -std::numeric_limits<double>::infinity();
       why |= (N > 64 && (lexi || N > kWlMaxN || nTok > 64)) ? FLTX_WHY_TOKENS : 0; /* (lexicon-free: the token BEAM has to fit, fltx_wlane.h) */
@@ -3466,7 +3490,7 @@ void fillParams(fltx_decoder* d, DecodeParams& P) {
   P.gLex = d->gLex.as<uint32_t>();
   P.gTokPb = d->gTokPb.as<uint32_t>();
   P.histPT = d->histPT.as<int2>();
-  P.tokRows = (d->wlane || d->wstream) ? d->tokRowsBuf.p : nullptr; /* (a stream's chunk: sized and blocked by fltx_stream_step) */
+  P.tokRows = (d->wlane || d->wstream || d->wtstream) ? d->tokRowsBuf.p : nullptr; /* (a stream's chunk: sized and blocked by fltx_stream_step) */
   P.tokRowBlocks = d->wlane ? std::max(1, (d->wlMaxT + 3) / 4) : 1;
   P.histW = d->histW.as<int32_t>();
   P.histS = d->keepScores ? d->histS.as<double>() : nullptr;
@@ -3594,6 +3618,9 @@ struct LaneKernel {
   FLTX_LK(kXstream, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane_stream<WW, GG>), (xlaneUtterance<GG, 0, false, false, true>))
 #define FLTX_LK_WSTREAM(WW, GG) \
   FLTX_LK(kWstream, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_wlane_stream<WW, GG>), (wlaneUtterance<GG, true>))
+/* (the token-LM variant: family kWstream, geometry field 1 = 1) */
+#define FLTX_LK_WTSTREAM(WW, GG) \
+  FLTX_LK(kWstream, 0, WW, GG, 1, 0, 0, (fltx_decode_kernel_wtlane_stream<WW, GG>), (wlaneUtterance<GG, true, true>))
 #define FLTX_LK_YSTREAM(WW, NG, RR) \
   FLTX_LK(kYstream, 0, WW, NG, RR, 0, 0, (fltx_decode_kernel_ylane_stream<WW, NG, RR>), (ylaneUtterance<NG, RR, 1, 0, false, true>))
 #define FLTX_LK_YLANE(WW, NG, RR, HM, LMK) \
@@ -3603,7 +3630,7 @@ struct LaneKernel {
 static const LaneKernel kLaneKernels[] = {
     FLTX_SLANE_GEOS(FLTX_LK_SLANE) FLTX_TLANE_PROF_GEOS(FLTX_LK_TLANE_PROF) FLTX_SSTREAM_GEOS(FLTX_LK_SSTREAM)
     FLTX_MLANE_GEOS(FLTX_LK_MLANE) FLTX_TMLANE_GEOS(FLTX_LK_TMLANE) FLTX_WLANE_GEOS(FLTX_LK_WLANE) FLTX_WTLANE_GEOS(FLTX_LK_WTLANE)
-    FLTX_XLANE_GEOS(FLTX_LK_XLANE) FLTX_XSTREAM_GEOS(FLTX_LK_XSTREAM) FLTX_WSTREAM_GEOS(FLTX_LK_WSTREAM) FLTX_YSTREAM_GEOS(FLTX_LK_YSTREAM) FLTX_YLANE_KERNELS(FLTX_LK_YLANE) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_LK_YLANE_PROF)};
+    FLTX_XLANE_GEOS(FLTX_LK_XLANE) FLTX_XSTREAM_GEOS(FLTX_LK_XSTREAM) FLTX_WSTREAM_GEOS(FLTX_LK_WSTREAM) FLTX_WTSTREAM_GEOS(FLTX_LK_WTSTREAM) FLTX_YSTREAM_GEOS(FLTX_LK_YSTREAM) FLTX_YLANE_KERNELS(FLTX_LK_YLANE) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_LK_YLANE_PROF)};
 #undef FLTX_LK
 #undef FLTX_LK_SLANE
 #undef FLTX_LK_TLANE_PROF
@@ -3615,13 +3642,14 @@ static const LaneKernel kLaneKernels[] = {
 #undef FLTX_LK_XLANE
 #undef FLTX_LK_XSTREAM
 #undef FLTX_LK_WSTREAM
+#undef FLTX_LK_WTSTREAM
 #undef FLTX_LK_YSTREAM
 #undef FLTX_LK_YLANE
 #undef FLTX_LK_YLANE_PROF
 
 /* what launchDecode runs: the lane engine's family, variant and geometry (kGeneric: the per-W kernels) */
 LaneKey laneKeyOf(const fltx_decoder* d) {
-  const int W = d->sstreamLaunch ? (d->xstream ? d->xstreamThreads : (d->ystream ? d->ystreamThreads : (d->wstream ? d->wstreamThreads : d->sstreamThreads))) : d->threads;
+  const int W = d->sstreamLaunch ? (d->xstream ? d->xstreamThreads : (d->ystream ? d->ystreamThreads : (d->wstream ? d->wstreamThreads : (d->wtstream ? d->wtstreamThreads : d->sstreamThreads)))) : d->threads;
   const int la = d->opt.log_add ? kVarLA : 0, prof = d->profile ? kVarProf : 0, hm = d->yshare ? kVarHM : 0;
   if (d->sstreamLaunch && d->xstream) {
     return {kXstream, 0, W, {d->xstream, 0, 0, 0}};
@@ -3629,6 +3657,8 @@ LaneKey laneKeyOf(const fltx_decoder* d) {
     return {kYstream, 0, W, {d->ystream, d->ystreamRounds, 0, 0}};
   } else if (d->sstreamLaunch && d->wstream) {
     return {kWstream, 0, W, {d->wstream, 0, 0, 0}};
+  } else if (d->sstreamLaunch && d->wtstream) {
+    return {kWstream, 0, W, {d->wtstream, 1, 0, 0}};
   } else if (d->sstreamLaunch) {
     return {d->tstream ? kTstream : kSstream, prof, W, {d->sstream, 0, 0, 0}};
   } else if (d->ylane) { /* (logAdd: LMK bit 3) */
@@ -3666,8 +3696,8 @@ size_t launchLds(const fltx_decoder* d, const LaneKey& k) {
     return sizeof(TlaneLds) + (size_t)(k.threads / 64) * kTlGatherBytes;
   } else if (k.fam == kXstream) { /* (the stream members take the LM-state memo's place) */
     return offsetof(XlaneLds, memo) + sizeof(XlStreamLds);
-  } else if (k.fam == kWstream) { /* (no Bloom filter, no edge memo: 31 KB) */
-    return sizeof(WlStreamLds);
+  } else if (k.fam == kWstream) { /* (no Bloom filter, no edge memo: 31 KB; with the token LM's members and score memo 54 KB) */
+    return k.g[1] ? sizeof(WtStreamLds) : sizeof(WlStreamLds);
   } else if (k.fam == kYstream) {
     /* YlaneLds up to the part of pscore the geometry's token waves use, then the stream members (no LM-state memo):
      * 82 KB with five token waves (512 threads, one lane group), 88 KB with eight (768, two); next to kXstream's 31 KB */
@@ -4268,7 +4298,7 @@ int streamRedoFlagged(fltx_decoder* d) {
      * other stream path raises this status, so the choice stands for "the launch that wrote the status"; a path that
      * comes to raise it for another reason needs a test of its own here) */
     /* (... and likewise a chunk fltx_ylane.h's stream variant could not finish, while d->ystream is set) */
-    if (status[b] & (ST_CAND_OVERFLOW | ST_CUT_RETRY | ((d->xstream || d->ystream || d->wstream) ? ST_SELECT_FALLBACK : 0))) {
+    if (status[b] & (ST_CAND_OVERFLOW | ST_CUT_RETRY | ((d->xstream || d->ystream || d->wstream || d->wtstream) ? ST_SELECT_FALLBACK : 0))) {
       again.push_back(b);
     }
   }
@@ -4969,14 +4999,15 @@ int fltx_stream_begin(fltx_decoder* d, int32_t B, int32_t N, int32_t maxFrames) 
    * overflow and number their states with a counter: always one pass.) */
   /* ("wstream": the chunks of a lexicon-free stream on fltx_wlane.h can be abandoned -- a row without a defined token
    * beam -- and are decoded again the same way; where that engine does not take the stream nothing optimistic is left) */
-  const bool wAsked = d->kind == FLTX_DECODER_LEXFREE && d->wstreamAsked != 0;
+  /* ("wtstream": the same with a token n-gram LM) */
+  const bool wAsked = d->kind == FLTX_DECODER_LEXFREE && (d->wstreamAsked != 0 || d->wtstreamAsked != 0);
   d->streamOpt = (d->kind == FLTX_DECODER_LEXICON || wAsked) && d->userStreamOpt != 0 && !d->forceGlobalWs && d->lm->kind != 2;
   d->streamRedone = 0;
   int rc = prepare(d, B, N, Tm.data(), !d->streamOpt);
   if (rc) {
     return rc;
   }
-  if (d->streamOpt && (d->kind == FLTX_DECODER_LEXFREE ? d->wstream == 0
+  if (d->streamOpt && (d->kind == FLTX_DECODER_LEXFREE ? (d->wstream == 0 && d->wtstream == 0)
                                                        : (d->lean || !(d->wsInLds || d->CAP2 > 0 || d->cutRecompute)))) {
     d->streamOpt = false; /* nothing optimistic came out of it */
     if ((rc = prepare(d, B, N, Tm.data(), true))) {
@@ -5104,7 +5135,7 @@ int fltx_stream_step(fltx_decoder* d, const float* emissions, int32_t onDevice, 
     d->idsUsedBound += want;
   }
   DecodeParams P;
-  if (d->wstream) { /* fltx_wlane.h's front end leaves one record per frame of this call: stream b's from sum(T[0 .. b)) on */
+  if (d->wstream || d->wtstream) { /* fltx_wlane.h's front end leaves one record per frame of this call: stream b's from sum(T[0 .. b)) on */
     int64_t rows = 0;
     for (int b = 0; b < d->B; ++b) {
       rows += T[b];
@@ -5117,7 +5148,7 @@ int fltx_stream_step(fltx_decoder* d, const float* emissions, int32_t onDevice, 
   P.emissions = up.emissions;
   P.doBegin = 0;
   P.doEnd = 0;
-  if (d->wstream) {
+  if (d->wstream || d->wtstream) {
     int maxT = 0;
     for (int b = 0; b < d->B; ++b) {
       maxT = std::max(maxT, T[b]);
@@ -5127,7 +5158,7 @@ int fltx_stream_step(fltx_decoder* d, const float* emissions, int32_t onDevice, 
   if (d->streamOpt && (rc = streamSnapshot(d, 0, nullptr, d->B))) {
     return rc;
   }
-  d->sstreamLaunch = d->sstream != 0 || d->xstream != 0 || d->ystream != 0 || d->wstream != 0;
+  d->sstreamLaunch = d->sstream != 0 || d->xstream != 0 || d->ystream != 0 || d->wstream != 0 || d->wtstream != 0;
   rc = d->lm->kind == 2 ? hostLmFrames(d, P, T) : launchDecode(d, P);
   d->sstreamLaunch = false;
   if (rc) {

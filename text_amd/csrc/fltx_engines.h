@@ -46,6 +46,10 @@
  * of 140 and more VGPRs each: no geometry is offered for two workgroups on a CU */
 #define FLTX_WSTREAM_GEOS(X) X(576, 5) X(576, 8) X(576, 10)
 
+/* ... and with a token n-gram LM over the word pieces (wtlane_stream: ST + TL), in order of preference: the offline rows.
+ * 54 KB of LDS; nine waves of 168 VGPRs: one workgroup per CU */
+#define FLTX_WTSTREAM_GEOS(X) X(576, 5) X(576, 8) X(576, 10)
+
 /* fltx_xlane.h, lane = (LM state, trie node): X(threads, list positions per wave), in order of preference; three waves
  * do not evaluate listed tokens */
 #define FLTX_XLANE_GEOS(X) X(512, 2) X(512, 3) X(640, 2) X(576, 5) X(640, 10)

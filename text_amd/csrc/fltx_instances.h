@@ -42,6 +42,7 @@
 #define FLTX_I_XSTREAM(WW, GG) FLTX_INST(fltx_decode_kernel_xlane_stream<WW, GG>)
 #define FLTX_I_WSTREAM(WW, GG) FLTX_INST(fltx_decode_kernel_wlane_stream<WW, GG>)
 #define FLTX_I_WTLANE(WW, GG) FLTX_INST(fltx_decode_kernel_wtlane<WW, GG>)
+#define FLTX_I_WTSTREAM(WW, GG) FLTX_INST(fltx_decode_kernel_wtlane_stream<WW, GG>)
 #define FLTX_I_YSTREAM(WW, NG, RR) FLTX_INST(fltx_decode_kernel_ylane_stream<WW, NG, RR>)
 #define FLTX_I_YLANE(WW, NG, RR, HM, LMK) FLTX_INST(fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, false>)
 #define FLTX_I_YLANE_PROF(WW, NG, RR, HM, LMK) FLTX_INST(fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, true>)
@@ -90,6 +91,7 @@
 #define FLTX_G44(W) FLTX_YSTREAM_GEOS(FLTX_I_YSTREAM) /* a lexicon stream's chunks with the LM terms */
 #define FLTX_G45(W) FLTX_WSTREAM_GEOS(FLTX_I_WSTREAM) /* a word-piece stream's chunks */
 #define FLTX_G46(W) FLTX_WTLANE_GEOS(FLTX_I_WTLANE) /* word pieces with a token n-gram LM */
+#define FLTX_G47(W) FLTX_WTSTREAM_GEOS(FLTX_I_WTSTREAM) /* a word-piece stream's chunks with a token n-gram LM */
 #define FLTX_G13(W) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_I_YLANE)
 #define FLTX_G14(W) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_I_YLANE_PROF)
 #define FLTX_G20(W) FLTX_YLANE4_GEOS(FLTX_YLMK_01, FLTX_I_YLANE) FLTX_YLANE4_GEOS(FLTX_YLMK_23, FLTX_I_YLANE)
@@ -149,6 +151,7 @@ FLTX_G43(0)
 FLTX_G44(0)
 FLTX_G45(0)
 FLTX_G46(0)
+FLTX_G47(0)
 #undef FLTX_ALLG
 #endif
 #undef FLTX_G1
@@ -191,6 +194,7 @@ FLTX_G46(0)
 #undef FLTX_G44
 #undef FLTX_G45
 #undef FLTX_G46
+#undef FLTX_G47
 #undef FLTX_G25
 #undef FLTX_G26
 #undef FLTX_G27
@@ -208,6 +212,7 @@ FLTX_G46(0)
 #undef FLTX_I_XSTREAM
 #undef FLTX_I_WSTREAM
 #undef FLTX_I_WTLANE
+#undef FLTX_I_WTSTREAM
 #undef FLTX_I_YSTREAM
 #undef FLTX_I_YLANE
 #undef FLTX_I_YLANE_PROF

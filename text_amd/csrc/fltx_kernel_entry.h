@@ -92,6 +92,13 @@ __global__ void __launch_bounds__(W) fltx_decode_kernel_wlane_stream(DecodeParam
   extern __shared__ __attribute__((aligned(16))) char fltx_smem[];
   wlaneUtterance<GT, true>(P, fltx_smem);
 }
+/* ... and with a token n-gram LM over the word pieces (ST + TL): LM scores and n-gram contexts restored from and parked in
+ * that engine's gLm / stateCtx; 54 KB of LDS */
+template <int W, int GT>
+__global__ void __launch_bounds__(W) fltx_decode_kernel_wtlane_stream(DecodeParams P) {
+  extern __shared__ __attribute__((aligned(16))) char fltx_smem[];
+  wlaneUtterance<GT, true, true>(P, fltx_smem);
+}
 /* the frames of one decodeStep chunk of a stream on the same engine: beam in and out in the parked format of the
  * lane-per-slot step, whose kernels do decodeBegin / decodeEnd / prune / getBestHypothesis */
 template <int W, int GT>

@@ -27,6 +27,7 @@
  *
  * TL (wlaneUtterance<GT, false, true>, opt-in through "wtlane"): the same with a token n-gram LM over the word pieces,
  * see the comment at WtLds below; one more barrier per frame (the frame's best is a reduction).
+ * ST + TL (wlaneUtterance<GT, true, true>, opt-in through "wtstream"): a stream's chunks with that LM, see WtStreamLds.
  *
  * Roles and barriers as in fltx_slane.h: token waves (GT list positions each), one wave for the lanes' own groups
  * (blank, repeat + the parent state's extension, blank-then-last), the staging wave; three barriers per frame.
@@ -107,6 +108,7 @@ struct WlStreamRegs<true> {
   double amR;                          /* ... of the repeat group's winning member */
   uint32_t prevR;                      /* ... and that member's token (ASG transition) */
   double amNew;                        /* ... of the state newState() is about to make */
+  uint32_t bit, fresh;                 /* ST + TL: the candidate slot newState() is called for; slots whose state's id is new */
 };
 enum { WL_FRAME0 = 6, WL_TOTAL0 = 7 }; /* scal[], next to fltx_slane.h's SL_* */
 
@@ -169,6 +171,49 @@ struct WlTokLmUtt<true> {
 };
 FLTX_DEV uint32_t wtMemoSlot(uint32_t sid, uint32_t tok) { return (tok ^ sid ^ (sid >> 11)) & (uint32_t)(kWtMemoSlots - 1); }
 FLTX_DEV uint32_t wtMemoTag(uint32_t sid, uint32_t tok) { return (sid << 3) | (tok >> 11); }
+/* ---- ST + TL: a stream's chunks with the token n-gram LM (wlaneUtterance<GT, true, true>, opt-in through "wtstream") ----
+ * WlStreamLds's members and the TL members of WtLds by the same names, so the frame's TL code is the offline variant's.
+ * The stream layout leaves room the offline one does not have (32 KB against 124 KB), and nine waves of 168 VGPRs keep a
+ * second workgroup off the CU whatever the LDS, so the score memo's slot count is a constant of this variant
+ * (kWtsMemoBits).  Measured at 2 048 and 8 192 slots: the same 1.2 % of the look-ups answered and rates
+ * whose ranges overlap -- on those rows a pair is rarely asked twice, whatever the memo holds -- so it stays at 2 048
+ * (16 KB; 54 KB in all, within the default launch limit).  Slot and tag hold the whole (state id, token) key as offline:
+ * tag = id << (14 - bits) | token >> bits, the slot gives the token's low bits back.  Ids are the generic table's (below
+ * 2^23: prepare() refuses what would not fit kWtsMaxSid); compactions renumber them between chunks, so the memo lives for
+ * one launch and starts empty in each.
+ * Restore: a lane's LM scores are its two slots' gLm, its context the id's stateCtx row (order - 1 suffix node ids: no dense
+ * table at N > 64), the term it was entered with one wtNgram(stateCtx row of its parent id, its last token) -- for every
+ * lane that takes arrivals, linked to its parent's lane or not: wlRelink may link it later in the chunk.
+ * A state whose id is new gets its context written to stateCtx (the generic engine's begin / end / prune / redo read it). */
+constexpr int kWtsMemoBits = 11;
+constexpr int kWtsMemoSlots = 1 << kWtsMemoBits;
+constexpr uint32_t kWtsMaxSid = (1u << (18 + kWtsMemoBits < 31 ? 18 + kWtsMemoBits : 31)) - 2u; /* (no id reaches the empty slot's tag) */
+static_assert(kWtsMemoBits <= 14 && kWlMaxN <= (1 << 14), "tag = id << (14 - bits) | token >> bits");
+struct WtStreamLds : WlStreamLds {
+  unsigned long long fbest[2];
+  double lmNB[2][64], lmB[2][64];
+  float lmIn[2][64];
+  int32_t ctx[2][kWtCtx][64];
+  uint32_t stat[4];
+  unsigned long long lmMemo[kWtsMemoSlots]; /* tag (state id << (14 - bits) | token >> bits) << 32 | float bits of the score */
+};
+static_assert(sizeof(WtStreamLds) <= 64 * 1024, "launched within the default limit, as every kWstream kernel");
+template <bool ST>
+FLTX_DEV uint32_t wtSlotOf(uint32_t sid, uint32_t tok) {
+  if constexpr (ST) {
+    return (tok ^ sid ^ (sid >> kWtsMemoBits)) & (uint32_t)(kWtsMemoSlots - 1);
+  } else {
+    return wtMemoSlot(sid, tok);
+  }
+}
+template <bool ST>
+FLTX_DEV uint32_t wtTagOf(uint32_t sid, uint32_t tok) {
+  if constexpr (ST) {
+    return (sid << (14 - kWtsMemoBits)) | (tok >> kWtsMemoBits);
+  } else {
+    return wtMemoTag(sid, tok);
+  }
+}
 /* lm.score(context, token) (KenLM.cpp:63-75): tokens outside the LM's vocabulary are <unk>, as lmScoreDev */
 FLTX_DEV float wtNgram(const DecodeParams& P, const int32_t* ctx, uint32_t tok, int32_t* ctxOut) {
   const uint32_t word = tok < (uint32_t)P.nUsr ? (uint32_t)P.usrToLm[tok] : (uint32_t)P.lmUnk;
@@ -190,6 +235,15 @@ FLTX_DEV void wlScoreRec(const DecodeParams& P, int64_t at, double c, double am)
     hs[0] = c;
     hs[1] = am;
     hs[2] = 0.0;
+  }
+}
+/* ... with a token LM: {score, emitting-model score, LM score} */
+FLTX_DEV void wlScoreRecLm(const DecodeParams& P, int64_t at, double c, double am, double lm) {
+  if (P.histS) {
+    double* hs = P.histS + 3 * at;
+    hs[0] = c;
+    hs[1] = am;
+    hs[2] = lm;
   }
 }
 /* a lane's `spar` in a stream: bit 31 (no state id has it) = the state takes no arrival -- the start state, or a state
@@ -700,8 +754,8 @@ FLTX_DEV void wlStageRow(const DecodeParams& P, LdsT& S, WlFront& F, int64_t row
  * The token beams of the chunk's rows come from fltx_tokbeam_stream_kernel, launched ahead on the same stream. */
 template <int GT, bool ST = false, bool TL = false>
 FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
-  static_assert(!(ST && TL), "streams with a token LM stay on the generic engine");
-  using LdsT = typename std::conditional<ST, WlStreamLds, typename std::conditional<TL, WtLds, WlaneLds>::type>::type;
+  using LdsT = typename std::conditional<ST, typename std::conditional<TL, WtStreamLds, WlStreamLds>::type,
+                                         typename std::conditional<TL, WtLds, WlaneLds>::type>::type;
   LdsT& S = *(LdsT*)smem;
   const int b = P.uttMap ? P.uttMap[blockIdx.x] : (int)blockIdx.x;
   const int W = (int)blockDim.x, tid = (int)threadIdx.x;
@@ -787,7 +841,18 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
     P.histPT[hbase + tid] = make_int2((int)kSlNoHyp, -1);
   }
   }
-  if constexpr (TL) {
+  if constexpr (ST && TL) { /* (ids are renumbered between chunks: the memo starts empty in every launch) */
+    for (int i = tid; i < kWtsMemoSlots / 2; i += W) {
+      ((uint4*)S.lmMemo)[i] = make_uint4(~0u, ~0u, ~0u, ~0u);
+    }
+    if (tid < 4) {
+      S.stat[tid] = 0u;
+    }
+    if (tid < 2) {
+      S.fbest[tid] = 0ull;
+    }
+  }
+  if constexpr (TL && !ST) {
     for (int i = tid; i < kWtMemoSlots; i += W) {
       S.lmMemo[i] = ~0ull; /* (no state id reaches this tag) */
     }
@@ -883,6 +948,16 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
         S.amB[0][L] = 0.0;
         S.rsNB[L] = (uint8_t)kSlNoHyp;
         S.rsB[L] = (uint8_t)kSlNoHyp;
+        if constexpr (TL) { /* the state's context: its id's stateCtx row (compactions move the rows with the ids) */
+          const int Lc = P.lmOrder - 1;
+          const int32_t* cx = P.stateCtx + ((size_t)b * P.stateCap + (sid < P.stateCap ? sid : 0u)) * (size_t)Lc;
+#pragma unroll
+          for (int k = 0; k < kWtCtx; ++k) {
+            S.ctx[0][k][L] = k < Lc ? cx[k] : 0;
+          }
+          S.lmNB[0][L] = 0.0;
+          S.lmB[0][L] = 0.0;
+        }
       }
       waveSync();
       if (valid) {
@@ -890,10 +965,16 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
           S.rec[0][L].b = sc;
           S.amB[0][L] = amv;
           S.rsB[L] = (uint8_t)lane;
+          if constexpr (TL) {
+            S.lmB[0][L] = P.gLm[g];
+          }
         } else {
           S.rec[0][L].nb = sc;
           S.amNB[0][L] = amv;
           S.rsNB[L] = (uint8_t)lane;
+          if constexpr (TL) {
+            S.lmNB[0][L] = P.gLm[g];
+          }
         }
       }
       waveSync();
@@ -911,6 +992,25 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
                               ((uint32_t)S.rsB[lane] << 24);
         if (plr >= 0 && (mine.info & 0xFFu) < 64u) {
           atomOr64(&S.cmask[0][plr], 1ull << (mine.info & 0xFFu));
+        }
+      }
+      if constexpr (TL) {
+        /* the LM score a state was entered with = its parent state's extension by its last token: one look-up per lane
+         * that takes arrivals, all lanes side by side, from the parent id's stateCtx row (the row of the parent's lane when
+         * it holds one; when it does not, wlRelink may still give the lane its parent back later in this chunk) */
+        float lin = 0.0f;
+        if (lv && (mine.spar & kWlNoArrival) == 0u && mine.spar < P.stateCap) {
+          const int Lc = P.lmOrder - 1;
+          const int32_t* px = P.stateCtx + ((size_t)b * P.stateCap + mine.spar) * (size_t)Lc;
+          int32_t pc[kWtCtx];
+#pragma unroll
+          for (int k = 0; k < kWtCtx; ++k) {
+            pc[k] = k < Lc ? px[k] : 0;
+          }
+          lin = wtNgram(P, pc, mine.pad, nullptr);
+        }
+        if (lv) {
+          S.lmIn[0][lane] = lin;
         }
       }
       if (lane == 0) {
@@ -1031,6 +1131,10 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
       A.amR = 0.0;
       A.prevR = 0u;
       A.amNew = 0.0;
+    }
+    if constexpr (ST && TL) {
+      A.bit = 0u;
+      A.fresh = 0u;
     }
     /* self wave: what its groups need beyond the lane's own record (second LDS round trip) */
     SlRec par = {};
@@ -1203,8 +1307,8 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
             L.pre[j] = ask;
             bool hit = false;
             if (ask) {
-              const unsigned long long e = S.lmMemo[wtMemoSlot(me.sid, tk[j])];
-              hit = (uint32_t)(e >> 32) == wtMemoTag(me.sid, tk[j]);
+              const unsigned long long e = S.lmMemo[wtSlotOf<ST>(me.sid, tk[j])];
+              hit = (uint32_t)(e >> 32) == wtTagOf<ST>(me.sid, tk[j]);
               L.lmv[j] = hit ? __uint_as_float((uint32_t)e) : 0.0f;
               need |= hit ? 0u : (1u << j);
             }
@@ -1226,7 +1330,7 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
               tok = j == jj ? tk[j] : tok;
             }
             const float v = wtNgram(P, L.ctx, tok, nullptr);
-            S.lmMemo[wtMemoSlot(me.sid, tok)] = ((unsigned long long)wtMemoTag(me.sid, tok) << 32) | (unsigned long long)__float_as_uint(v);
+            S.lmMemo[wtSlotOf<ST>(me.sid, tok)] = ((unsigned long long)wtTagOf<ST>(me.sid, tok) << 32) | (unsigned long long)__float_as_uint(v);
 #pragma unroll
             for (int j = 0; j < GT; ++j) {
               L.lmv[j] = j == jj ? v : L.lmv[j];
@@ -1488,7 +1592,15 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
           atomOr64(&S.cmask[q][myNewLane], 1ull << np);
         }
         histPT[hrow + hyp] = wlPlainRec(hp, n);
+        if constexpr (TL) {
+          S.lmNB[q][nl] = L.lmNew;
+          S.lmB[q][nl] = 0.0;
+          S.lmIn[q][nl] = L.lmE;
+          wlScoreRecLm(P, hrow + hyp, c, A.amNew, L.lmNew);
+          A.fresh |= (fresh && r.sid != 0u) ? A.bit : 0u; /* (id 0 under `fresh`: the ids ran out, the chunk is redone) */
+        } else {
         wlScoreRec(P, hrow + hyp, c, A.amNew);
+        }
         if (!fresh) { /* entered before: it may have descendants in the beam (wlRelink) */
           const uint32_t e = atomAdd32(&S.row[q].nev, 1u);
           S.evLane[e] = (uint32_t)nl;
@@ -1545,6 +1657,9 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
               L.lmE = L.lmv[j];
               L.lmNew = (whichB ? L.lmB : L.lmNB) + (double)L.lmv[j];
             }
+            if constexpr (ST && TL) {
+              A.bit = 1u << j;
+            }
             newState(offW + myNew[j], cs[j], tk[j], np, hypM);
           }
         }
@@ -1570,13 +1685,21 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
             const double a = wlAmStep(P, A.total0 + t == 0, A.amR, eLast, last, A.prevR);
             S.amNB[q][surv] = a;
             histPT[hrow + hNB] = wlPlainRec(parR, last);
+            if constexpr (TL) {
+              wlScoreRecLm(P, hrow + hNB, cs[1], a, L.lmR);
+            } else {
             wlScoreRec(P, hrow + hNB, cs[1], a);
+            }
           }
           if (sB) {
             const double a = A.amM + eBlank;
             S.amB[q][surv] = a;
             histPT[hrow + hB] = wlPlainRec(hypM, (uint32_t)blank);
+            if constexpr (TL) {
+              wlScoreRecLm(P, hrow + hB, cs[0], a, whichB ? L.lmB : L.lmNB);
+            } else {
             wlScoreRec(P, hrow + hB, cs[0], a);
+            }
           }
         } else {
         if (sR) {
@@ -1603,6 +1726,9 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
         if constexpr (TL) {
           L.lmE = L.lmv[2];
           L.lmNew = L.lmB + (double)L.lmv[2];
+        }
+        if constexpr (ST && TL) {
+          A.bit = 4u;
         }
         newState(offW + myNew[2], cs[2], last, lastNext, hypB);
       }
@@ -1638,6 +1764,19 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
 #pragma unroll
             for (int k = 0; k < kWtCtx; ++k) {
               S.ctx[q][k][nl] = co[k];
+            }
+            if constexpr (ST) { /* a new id: its context goes where the generic engine's kernels and the next restore look */
+              const uint32_t sidNew = S.rec[q][nl].sid; /* (this lane wrote the record) */
+              if (((A.fresh >> jj) & 1u) != 0u && sidNew < P.stateCap) {
+                const int Lc = P.lmOrder - 1;
+                int32_t* dst = P.stateCtx + ((size_t)b * P.stateCap + sidNew) * (size_t)Lc;
+#pragma unroll
+                for (int k = 0; k < kWtCtx; ++k) {
+                  if (k < Lc) {
+                    dst[k] = co[k];
+                  }
+                }
+              }
             }
           }
         }
@@ -1717,11 +1856,16 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
       __asm__ volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* every lane has its old records before any is rewritten */
 #endif
       waveSync();
-      auto put = [&](int r, double sc, double am, uint32_t tokpb, unsigned long long rec) {
+      double lNB = 0.0, lB = 0.0; /* the LM score of the lane's two hypotheses (ZeroLM: 0) */
+      if constexpr (TL) {
+        lNB = S.lmNB[pe][li];
+        lB = S.lmB[pe][li];
+      }
+      auto put = [&](int r, double sc, double am, double lm, uint32_t tokpb, unsigned long long rec) {
         const size_t g = (size_t)b * K + r;
         P.gScore[g] = sc;
         P.gAm[g] = am;
-        P.gLm[g] = 0.0;
+        P.gLm[g] = lm;
         P.gState[g] = me.sid;
         P.gSPar[g] = sparOut;
         P.gSEdge[g] = edgeOut;
@@ -1733,14 +1877,14 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
           double* hs = P.histS + 3 * (hlast + r);
           hs[0] = sc;
           hs[1] = am;
-          hs[2] = 0.0;
+          hs[2] = lm;
         }
       };
       if (hasNB) {
-        put(rNB, me.nb, aNB, lastTok, recNB);
+        put(rNB, me.nb, aNB, lNB, lastTok, recNB);
       }
       if (hasB) {
-        put(rB, me.b, aB, (uint32_t)blank | kPrevBlank, recB);
+        put(rB, me.b, aB, lB, (uint32_t)blank | kPrevBlank, recB);
       }
       if (lane == 0) {
         const int32_t stNow = P.uttStatus[b] | (int32_t)S.scal[SL_STATUS];
