@@ -1082,7 +1082,12 @@ FLTX_API int fltx_decoder_profile(fltx_decoder* dec, uint64_t* out);
  * n-gram LM over the tokens runs on that engine's token-LM variant where it takes it -- n-gram orders up to 6, max-merge,
  * CTC and ASG, up to 16 384 tokens, beam and token beam up to 64; the LM is asked through its n-gram tables, filtered and
  * memoised; default 0: such a decode stays on the generic engine and "why_not_lane" says FLTX_WHY_LM; fltx_decoder_get
- * "wtlane" answers 1 when the last call ran on the variant; results are the same bit for bit), "wtstream" (1 = "wstream" for a
+ * "wtlane" answers 1 when the last call ran on the variant; results are the same bit for bit), "wlogadd" (1 = an offline
+ * lexicon-free decode over a token set beyond 64 with DecoderOptions::logAdd runs on that engine's logAdd variants where
+ * they take it -- ZeroLM, and with "wtlane" = 1 an n-gram LM over the tokens; CTC and ASG, up to 16 384 tokens, beam and
+ * token beam up to 64; default 0: such a decode stays on the generic engine and "why_not_lane" says FLTX_WHY_LOGADD;
+ * fltx_decoder_get "wlogadd" answers 1 when the last call ran on one of them; tokens are the same, scores agree within
+ * the logAdd contract's 1e-5), "wtstream" (1 = "wstream" for a
  * lexicon-free stream with an n-gram LM over the tokens: its chunks run on that engine's stream + token-LM variant where it
  * takes them -- "wstream"'s terms and "wtlane"'s n-gram orders; an optimistic stream as under "wstream"; default 0: such a
  * stream stays on the generic engine and "why_not_lane" says FLTX_WHY_STREAM; set before fltx_stream_begin;

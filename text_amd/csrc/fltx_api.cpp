@@ -850,6 +850,9 @@ struct fltx_decoder {
   /* ... and of the lexicon-free decoder over a large token set with a token n-gram LM on fltx_wlane.h's TL variant
    * ("wtlane" = 1 asks for it; wtlaneFirst: the last call started on it) */
   int wtlaneAsked = 0, wtlane = 0, wtlaneFirst = 0;
+  /* ... and with logAdd merges on its LA variants ("wlogadd" = 1 lets logAdd onto that engine; wlogadd: this call runs on an
+   * LA kernel; wlogaddFirst: the last call started on one) */
+  int wlogaddAsked = 0, wlogadd = 0, wlogaddFirst = 0;
   /* streams of the lexicon decoder on the optimistic geometry (LDS workspace, cut-off generation): a chunk that
    * overflows is decoded again from the saved beam on the general path (HBM workspace) */
   int userStreamOpt = 1;
@@ -2261,6 +2264,8 @@ int fltx_decoder_get(fltx_decoder* d, const char* key, int64_t* value) {
     *value = d->wlaneFirst;
   } else if (!strcmp(key, "wtlane")) { /* 1: ... on its token-LM variant */
     *value = d->wtlaneFirst;
+  } else if (!strcmp(key, "wlogadd")) { /* 1: ... on one of its logAdd variants */
+    *value = d->wlogaddFirst;
   } else if (!strcmp(key, "slane")) {
     *value = d->slaneFirst;
   } else if (!strcmp(key, "slane_m32")) { /* 1: the last call started on fltx_slane.h's kernel with 32-bit token masks */
@@ -2443,6 +2448,10 @@ int fltx_decoder_set(fltx_decoder* d, const char* key, int64_t value) {
     d->wtlaneAsked = value ? 1 : 0;
     return FLTX_OK;
   }
+  if (!strcmp(key, "wlogadd")) { /* 1: word pieces with logAdd run on fltx_wlane.h's LA variants where they take them (default 0) */
+    d->wlogaddAsked = value ? 1 : 0;
+    return FLTX_OK;
+  }
   if (!strcmp(key, "stream_optimistic")) { /* 0: streams of the lexicon decoder start on the worst-case (HBM) workspace */
     d->userStreamOpt = (int)value;
     return FLTX_OK;
@@ -2570,6 +2579,8 @@ static const LaneGeo kSlaneGeo[] = {FLTX_SLANE_GEOS(FLTX_GEO2)};
 static const LaneGeo kSstreamGeo[] = {FLTX_SSTREAM_GEOS(FLTX_GEO2)};
 static const LaneGeo kWlaneGeo[] = {FLTX_WLANE_GEOS(FLTX_GEO2)};
 static const LaneGeo kWtlaneGeo[] = {FLTX_WTLANE_GEOS(FLTX_GEO2)};
+static const LaneGeo kWlaneLaGeo[] = {FLTX_WLANE_LA_GEOS(FLTX_GEO2)};
+static const LaneGeo kWtlaneLaGeo[] = {FLTX_WTLANE_LA_GEOS(FLTX_GEO2)};
 static const LaneGeo kXlaneGeo[] = {FLTX_XLANE_GEOS(FLTX_GEO2)};
 static const LaneGeo kXstreamGeo[] = {FLTX_XSTREAM_GEOS(FLTX_GEO2)};
 static const LaneGeo kWstreamGeo[] = {FLTX_WSTREAM_GEOS(FLTX_GEO2)};
@@ -2603,6 +2614,7 @@ void latchFirst(fltx_decoder* d) {
   d->whyFirst = d->whyNotLane;
   d->wlaneFirst = d->wlane;
   d->wtlaneFirst = d->wtlane;
+  d->wlogaddFirst = d->wlogadd;
   d->slaneFirst = d->slane;
   d->slaneM32First = slaneM32(d) ? 1 : 0;
   d->tlaneFirst = d->tlane;
@@ -2807,16 +2819,20 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
   /* ... for token sets beyond 64 (word pieces) when the token beam keeps at most 64 of them (fltx_wlane.h): masks and
    * lists by position in the frame's token beam, a front-end wave that cuts the row to it */
   d->wlane = 0;
+  d->wlogadd = 0;
+  /* (logAdd: the LA variants' rows, when "wlogadd" asks for them) */
+  const bool wLa = d->opt.log_add && d->wlogaddAsked;
   if (d->kind == FLTX_DECODER_LEXFREE && !d->noSlane && !d->noWlane && !d->genericAsked && d->offlineCall && !d->keepScores &&
-      !forceWorstCaseCap && !d->forceGlobalWs && !d->opt.log_add && d->lm->kind == 0 && !d->isLmToken && N > 64 &&
+      !forceWorstCaseCap && !d->forceGlobalWs && (!d->opt.log_add || wLa) && d->lm->kind == 0 && !d->isLmToken && N > 64 &&
       N <= kWlMaxN && K <= 64 && nTok <= 64 && optionsOk && (int64_t)K * (maxT + 2) < (1 << 23) - 1) {
-    for (const LaneGeo& g : kWlaneGeo) {
+    for (const LaneGeo& g : wLa ? kWlaneLaGeo : kWlaneGeo) {
       if (d->userThreads && d->threads != g.threads) {
         continue;
       }
       if (nTok <= g.gt * (g.threads / 64 - 2)) {
         d->slane = g.gt;
         d->wlane = 1;
+        d->wlogadd = wLa ? 1 : 0;
         d->wlMaxT = maxT;
         d->threads = g.threads;
         break;
@@ -2827,9 +2843,12 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
    * n-gram tables in place of ZeroLM -- the LM is asked through ngScore, filtered and memoised (no dense table at N > 64) */
   d->wtlane = 0;
   if (d->wtlaneAsked && d->kind == FLTX_DECODER_LEXFREE && !d->noSlane && !d->noWlane && !d->genericAsked && d->offlineCall &&
-      !d->keepScores && !forceWorstCaseCap && !d->forceGlobalWs && !d->opt.log_add && d->lm->kind == 1 && !d->isLmToken &&
+      !d->keepScores && !forceWorstCaseCap && !d->forceGlobalWs && (!d->opt.log_add || wLa) && d->lm->kind == 1 && !d->isLmToken &&
       N > 64 && N <= kWlMaxN && K <= 64 && nTok <= 64 && optionsOk && (int64_t)K * (maxT + 2) < (1 << 23) - 1) {
-    for (const LaneGeo& g : kWtlaneGeo) {
+    const LaneGeo* const geos = wLa ? kWtlaneLaGeo : kWtlaneGeo;
+    const size_t nGeos = wLa ? sizeof(kWtlaneLaGeo) / sizeof(LaneGeo) : sizeof(kWtlaneGeo) / sizeof(LaneGeo);
+    for (size_t gi = 0; gi < nGeos; ++gi) {
+      const LaneGeo& g = geos[gi];
       if (d->userThreads && d->threads != g.threads) {
         continue;
       }
@@ -2837,6 +2856,7 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
         d->slane = g.gt;
         d->wlane = 1;
         d->wtlane = 1;
+        d->wlogadd = wLa ? 1 : 0;
         d->wlMaxT = maxT;
         d->threads = g.threads;
         break;
@@ -3094,7 +3114,7 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
       why |= (d->noSlane || d->noXlane || d->noYlane || d->genericAsked || d->forceGlobalWs || d->noLean || d->noDense ||
               d->userLaneGroups < 0 || forceWorstCaseCap || (d->offlineCall && d->keepScores) ||
               (!lexi && N > 64 && d->noWlane) || (!lexi && d->lm->kind == 1 && d->noTlane)) ? FLTX_WHY_SWITCHED_OFF : 0;
-      why |= (!lexi && N > 64 && d->opt.log_add) ? FLTX_WHY_LOGADD : 0; /* (fltx_wlane.h has no logAdd variant) */
+      why |= (!lexi && N > 64 && d->opt.log_add) ? FLTX_WHY_LOGADD : 0; /* (fltx_wlane.h's logAdd variants are opt-in: "wlogadd") */
       why |= (!lexi && nList > 70) ? FLTX_WHY_GEOMETRY : 0;
       if (!why) {
         why = FLTX_WHY_GEOMETRY; /* (no compiled geometry covers this token list / thread count) */
@@ -3280,7 +3300,8 @@ int prepare(fltx_decoder* d, int B, int N, const int32_t* Tmax, bool forceWorstC
   }
   d->wsInLds = lds;
   if (d->slane) {
-    d->wsBytes = d->wtlane         ? sizeof(WtLds)
+    d->wsBytes = d->wtlane         ? sizeof(WtLds) /* (TL + LA: the same layout) */
+                 : d->wlogadd      ? sizeof(WlaLds)
                  : d->wlane        ? sizeof(WlaneLds)
                  : d->mlaneNG == 2 ? sizeof(MlaneLds<2>)
                  : d->mlaneNG == 4 ? sizeof(MlaneLds<4>)
@@ -3608,6 +3629,9 @@ struct LaneKernel {
 #define FLTX_LK_WLANE(WW, GG) FLTX_LK(kWlane, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_wlane<WW, GG>), (wlaneUtterance<GG>))
 /* (the token-LM variant: family kWlane, geometry field 1 = 1) */
 #define FLTX_LK_WTLANE(WW, GG) FLTX_LK(kWlane, 0, WW, GG, 1, 0, 0, (fltx_decode_kernel_wtlane<WW, GG>), (wlaneUtterance<GG, false, true>))
+/* (the logAdd variants: variant bit kVarLA) */
+#define FLTX_LK_WLANE_LA(WW, GG) FLTX_LK(kWlane, kVarLA, WW, GG, 0, 0, 0, (fltx_decode_kernel_wlane_la<WW, GG>), (wlaneUtterance<GG, false, false, true>))
+#define FLTX_LK_WTLANE_LA(WW, GG) FLTX_LK(kWlane, kVarLA, WW, GG, 1, 0, 0, (fltx_decode_kernel_wtlane_la<WW, GG>), (wlaneUtterance<GG, false, true, true>))
 #define FLTX_LK_XLANE(WW, GG)                                                                                       \
   FLTX_LK(kXlane, 0, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane<WW, GG, 0, false>), (xlaneUtterance<GG, 0, false>))  \
   FLTX_LK(kXlane, kVarProf, WW, GG, 0, 0, 0, (fltx_decode_kernel_xlane<WW, GG, 0, true>), (xlaneUtterance<GG, 0, false>)) \
@@ -3630,6 +3654,7 @@ struct LaneKernel {
 static const LaneKernel kLaneKernels[] = {
     FLTX_SLANE_GEOS(FLTX_LK_SLANE) FLTX_TLANE_PROF_GEOS(FLTX_LK_TLANE_PROF) FLTX_SSTREAM_GEOS(FLTX_LK_SSTREAM)
     FLTX_MLANE_GEOS(FLTX_LK_MLANE) FLTX_TMLANE_GEOS(FLTX_LK_TMLANE) FLTX_WLANE_GEOS(FLTX_LK_WLANE) FLTX_WTLANE_GEOS(FLTX_LK_WTLANE)
+    FLTX_WLANE_LA_GEOS(FLTX_LK_WLANE_LA) FLTX_WTLANE_LA_GEOS(FLTX_LK_WTLANE_LA)
     FLTX_XLANE_GEOS(FLTX_LK_XLANE) FLTX_XSTREAM_GEOS(FLTX_LK_XSTREAM) FLTX_WSTREAM_GEOS(FLTX_LK_WSTREAM) FLTX_WTSTREAM_GEOS(FLTX_LK_WTSTREAM) FLTX_YSTREAM_GEOS(FLTX_LK_YSTREAM) FLTX_YLANE_KERNELS(FLTX_LK_YLANE) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_LK_YLANE_PROF)};
 #undef FLTX_LK
 #undef FLTX_LK_SLANE
@@ -3639,6 +3664,8 @@ static const LaneKernel kLaneKernels[] = {
 #undef FLTX_LK_TMLANE
 #undef FLTX_LK_WLANE
 #undef FLTX_LK_WTLANE
+#undef FLTX_LK_WLANE_LA
+#undef FLTX_LK_WTLANE_LA
 #undef FLTX_LK_XLANE
 #undef FLTX_LK_XSTREAM
 #undef FLTX_LK_WSTREAM
@@ -3668,7 +3695,7 @@ LaneKey laneKeyOf(const fltx_decoder* d) {
   } else if (d->slane && d->mlaneNG > 1) {
     return {d->tlane ? kTmlane : kMlane, la | prof, W, {d->slane, d->mlaneNG, d->mlaneGPW, d->mlaneSPW}};
   } else if (d->slane && d->wlane) {
-    return {kWlane, prof, W, {d->slane, d->wtlane, 0, 0}};
+    return {kWlane, la | prof, W, {d->slane, d->wtlane, 0, 0}};
   } else if (d->slane) {
     return {d->tlane ? kTlane : kSlane, la | prof | (slaneM32(d) ? kVarM32 : 0), W, {d->slane, 0, 0, 0}};
   }

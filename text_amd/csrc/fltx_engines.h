@@ -42,6 +42,14 @@
 /* ... with a token n-gram LM over the word pieces (wlaneUtterance<.., TL>), in order of preference: the offline rows */
 #define FLTX_WTLANE_GEOS(X) X(576, 5) X(576, 8) X(576, 10)
 
+/* ... with logAdd merges (wlaneUtterance<.., LA>, opt-in through "wlogadd"), under ZeroLM and with the token n-gram LM
+ * (TL + LA), in order of preference: the offline rows.  TL + LA has no 576 x 10 row: that kernel (429 VGPR and 466 SGPR
+ * spills) returned wrong n-bests on the GPU at token beams of 64 where the emulator, compiling the same source, agreed
+ * with the oracle -- not understood, as the note at the pairwise rank in fltx_wlane.h; ten waves of eight positions cover
+ * the 64 and agree with the oracle on the whole grid */
+#define FLTX_WLANE_LA_GEOS(X) X(576, 5) X(576, 8) X(576, 10)
+#define FLTX_WTLANE_LA_GEOS(X) X(576, 5) X(576, 8) X(640, 8)
+
 /* ... a word-piece stream's chunks (wlane_stream), in order of preference: the offline rows.  31 KB of LDS, but 9 waves
  * of 140 and more VGPRs each: no geometry is offered for two workgroups on a CU */
 #define FLTX_WSTREAM_GEOS(X) X(576, 5) X(576, 8) X(576, 10)

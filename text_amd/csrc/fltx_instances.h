@@ -43,6 +43,8 @@
 #define FLTX_I_WSTREAM(WW, GG) FLTX_INST(fltx_decode_kernel_wlane_stream<WW, GG>)
 #define FLTX_I_WTLANE(WW, GG) FLTX_INST(fltx_decode_kernel_wtlane<WW, GG>)
 #define FLTX_I_WTSTREAM(WW, GG) FLTX_INST(fltx_decode_kernel_wtlane_stream<WW, GG>)
+#define FLTX_I_WLANE_LA(WW, GG) FLTX_INST(fltx_decode_kernel_wlane_la<WW, GG>)
+#define FLTX_I_WTLANE_LA(WW, GG) FLTX_INST(fltx_decode_kernel_wtlane_la<WW, GG>)
 #define FLTX_I_YSTREAM(WW, NG, RR) FLTX_INST(fltx_decode_kernel_ylane_stream<WW, NG, RR>)
 #define FLTX_I_YLANE(WW, NG, RR, HM, LMK) FLTX_INST(fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, false>)
 #define FLTX_I_YLANE_PROF(WW, NG, RR, HM, LMK) FLTX_INST(fltx_decode_kernel_ylane<WW, NG, RR, LMK, HM, true>)
@@ -92,6 +94,8 @@
 #define FLTX_G45(W) FLTX_WSTREAM_GEOS(FLTX_I_WSTREAM) /* a word-piece stream's chunks */
 #define FLTX_G46(W) FLTX_WTLANE_GEOS(FLTX_I_WTLANE) /* word pieces with a token n-gram LM */
 #define FLTX_G47(W) FLTX_WTSTREAM_GEOS(FLTX_I_WTSTREAM) /* a word-piece stream's chunks with a token n-gram LM */
+#define FLTX_G48(W) FLTX_WLANE_LA_GEOS(FLTX_I_WLANE_LA) /* word pieces, logAdd */
+#define FLTX_G49(W) FLTX_WTLANE_LA_GEOS(FLTX_I_WTLANE_LA) /* word pieces with a token n-gram LM, logAdd */
 #define FLTX_G13(W) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_I_YLANE)
 #define FLTX_G14(W) FLTX_YLANE_GEOS(FLTX_YLMK_01, FLTX_I_YLANE_PROF)
 #define FLTX_G20(W) FLTX_YLANE4_GEOS(FLTX_YLMK_01, FLTX_I_YLANE) FLTX_YLANE4_GEOS(FLTX_YLMK_23, FLTX_I_YLANE)
@@ -152,6 +156,8 @@ FLTX_G44(0)
 FLTX_G45(0)
 FLTX_G46(0)
 FLTX_G47(0)
+FLTX_G48(0)
+FLTX_G49(0)
 #undef FLTX_ALLG
 #endif
 #undef FLTX_G1
@@ -195,6 +201,8 @@ FLTX_G47(0)
 #undef FLTX_G45
 #undef FLTX_G46
 #undef FLTX_G47
+#undef FLTX_G48
+#undef FLTX_G49
 #undef FLTX_G25
 #undef FLTX_G26
 #undef FLTX_G27
@@ -213,6 +221,8 @@ FLTX_G47(0)
 #undef FLTX_I_WSTREAM
 #undef FLTX_I_WTLANE
 #undef FLTX_I_WTSTREAM
+#undef FLTX_I_WLANE_LA
+#undef FLTX_I_WTLANE_LA
 #undef FLTX_I_YSTREAM
 #undef FLTX_I_YLANE
 #undef FLTX_I_YLANE_PROF

@@ -84,6 +84,18 @@ __global__ void __launch_bounds__(W) fltx_decode_kernel_wtlane(DecodeParams P) {
   extern __shared__ __attribute__((aligned(16))) char fltx_smem[];
   wlaneUtterance<GT, false, true>(P, fltx_smem);
 }
+/* ... with logAdd merges (LA: the frame's best from the best surviving score; 124 KB of LDS), opt-in through "wlogadd" */
+template <int W, int GT>
+__global__ void __launch_bounds__(W) fltx_decode_kernel_wlane_la(DecodeParams P) {
+  extern __shared__ __attribute__((aligned(16))) char fltx_smem[];
+  wlaneUtterance<GT, false, false, true>(P, fltx_smem);
+}
+/* ... and both (TL + LA: the merges follow the barrier that publishes the frame's best; WtLds) */
+template <int W, int GT>
+__global__ void __launch_bounds__(W) fltx_decode_kernel_wtlane_la(DecodeParams P) {
+  extern __shared__ __attribute__((aligned(16))) char fltx_smem[];
+  wlaneUtterance<GT, false, true, true>(P, fltx_smem);
+}
 /* ... the frames of one decodeStep chunk of a word-piece stream on that engine: beam in and out in the generic engine's
  * parked format, LM-state ids from its table; its kernels do decodeBegin / decodeEnd / prune / getBestHypothesis.  The
  * token beams of the chunk's rows come from fltx_tokbeam_stream_kernel (fltx_api.cpp), launched ahead of it */

@@ -28,6 +28,8 @@
  * TL (wlaneUtterance<GT, false, true>, opt-in through "wtlane"): the same with a token n-gram LM over the word pieces,
  * see the comment at WtLds below; one more barrier per frame (the frame's best is a reduction).
  * ST + TL (wlaneUtterance<GT, true, true>, opt-in through "wtstream"): a stream's chunks with that LM, see WtStreamLds.
+ * LA (wlaneUtterance<GT, false, TL, true>, opt-in through "wlogadd"): the members of a merge group are log-added
+ * (DecoderOptions::logAdd), see the comment at WlaLds below; offline only.
  *
  * Roles and barriers as in fltx_slane.h: token waves (GT list positions each), one wave for the lanes' own groups
  * (blank, repeat + the parent state's extension, blank-then-last), the staging wave; three barriers per frame.
@@ -214,6 +216,65 @@ FLTX_DEV uint32_t wtTagOf(uint32_t sid, uint32_t tok) {
     return wtMemoTag(sid, tok);
   }
 }
+/* ---- LA: logAdd merges (wlaneUtterance<GT, false, TL, true>, opt-in through "wlogadd") -------------------------------
+ * fltx_slane.h's LA pattern, keyed by list position.  The merge groups keep their fixed shape; the members that pass the
+ * frame's threshold are log-added in descending order (Utils.h:167-198), the back-pointer -- and with it the
+ * emitting-model score, the LM score and the n-gram context -- stays the best member's:
+ *   token waves   a new-token candidate's second member is the state's other hypothesis + the same emission (+ silScore,
+ *                 + the same LM term): fl(a + e) is monotone, so it is the smaller one;
+ *   own groups    blank: nb and b; repeat: the lane's own repeat and the parent state's two extensions by last(S), sorted
+ *                 (three members); blank-then-last has one member;
+ *   decodeEnd     a state's two hypotheses finish into one.
+ * Without a token LM the frame's best candidate is no recurrence any more (a merged hypothesis can score above every
+ * candidate of its frame): the build raises mmaxKey to the best surviving score, and every wave prices the row at the head
+ * of the next frame as that + the row's largest listed emission, sil apart (silScore) -- eMax / eSil, which the staging
+ * wave leaves next to the row; WlRow::best / thr are not read, WlRow::dead says only whether the token beam could be cut.
+ * With a token LM the best is the reduction behind barrier 0 as it was (second members are never above first ones), the
+ * merges follow that barrier, and WtLds is the layout unchanged.
+ * sizeof(WlaLds) = sizeof(WlaneLds) + 48 = 126 536 bytes; TL + LA: WtLds, 148 024 bytes. */
+struct WlaLds : WlaneLds {
+  unsigned long long mmaxKey[2]; /* order key of the best hypothesis of the beam a frame starts from */
+  double eMax[2];                /* the row's largest listed emission other than sil's (blank's included), NaN: none */
+  double eSil[2];                /* sil's emission, NaN: sil is not in the token beam */
+};
+static_assert(sizeof(WlaLds) == 126536 && sizeof(WlaLds) < sizeof(WtLds), "one CU's LDS; the size the comment states");
+/* what a logAdd frame keeps of a lane's groups until the frame's threshold is known (TL: across barrier 0); empty
+ * otherwise, and touched under `if constexpr (LA)` alone */
+template <bool LA, int GT>
+struct WlLogAddRegs {};
+template <int GT>
+struct WlLogAddRegs<true, GT> {
+  double c2[GT];     /* second member of the group of slot j */
+  uint32_t two;      /* slots that have one */
+  double r0, r1, r2; /* own-groups wave: the repeat group's members ... */
+  uint32_t has;      /* ... which of them exist (bits 0 .. 2) */
+};
+/* the repeat group under logAdd: the members that exist and pass the threshold, added best first; false: none passes */
+FLTX_DEV bool wlRepeatLogAdd(double r0, double r1, double r2, uint32_t has, double thr, double& sum) {
+  const double NEG = slNegInf();
+  const bool v0 = (has & 1u) && r0 >= thr, v1 = (has & 2u) && r1 >= thr, v2 = (has & 4u) && r2 >= thr;
+  const double a = v0 ? r0 : NEG, bq = v1 ? r1 : NEG, cq = v2 ? r2 : NEG;
+  const double t0 = a > bq ? a : bq, t1 = a > bq ? bq : a; /* three-element sort, descending */
+  const double hi = t0 > cq ? t0 : cq;
+  const double mid = t0 > cq ? (t1 > cq ? t1 : cq) : t0;
+  const double lo = t0 > cq ? (t1 > cq ? cq : t1) : t1;
+  double acc = hi;
+  if (mid > NEG) {
+    acc = slLogAdd(acc, mid);
+  }
+  if (lo > NEG) {
+    acc = slLogAdd(acc, lo);
+  }
+  sum = acc;
+  return v0 || v1 || v2;
+}
+/* what the head of a logAdd frame prices the row with, left next to the row the staging wave has just staged.  One lane. */
+FLTX_DEV void wlStageLa(WlaLds& S, int q, uint32_t ek, float eSil, uint32_t flags) {
+  S.eMax[q] = ek != 0u ? (double)f32FromKey(ek) : __builtin_nan("");
+  S.eSil[q] = (flags & 1u) ? (double)eSil : __builtin_nan("");
+  S.row[q].dead = (flags & 2u) ? 1u : 0u;
+}
+
 /* lm.score(context, token) (KenLM.cpp:63-75): tokens outside the LM's vocabulary are <unk>, as lmScoreDev */
 FLTX_DEV float wtNgram(const DecodeParams& P, const int32_t* ctx, uint32_t tok, int32_t* ctxOut) {
   const uint32_t word = tok < (uint32_t)P.nUsr ? (uint32_t)P.usrToLm[tok] : (uint32_t)P.lmUnk;
@@ -752,10 +813,11 @@ FLTX_DEV void wlStageRow(const DecodeParams& P, LdsT& S, WlFront& F, int64_t row
  * getBestHypothesis, finish and the partial transcripts stay the kernels they are; LM states are named through that
  * engine's id table; history rows are its plain records with the token in a word of its own (tokens beyond a byte).
  * The token beams of the chunk's rows come from fltx_tokbeam_stream_kernel, launched ahead on the same stream. */
-template <int GT, bool ST = false, bool TL = false>
+template <int GT, bool ST = false, bool TL = false, bool LA = false>
 FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
+  static_assert(!(LA && ST), "streams with logAdd stay on the generic engine");
   using LdsT = typename std::conditional<ST, typename std::conditional<TL, WtStreamLds, WlStreamLds>::type,
-                                         typename std::conditional<TL, WtLds, WlaneLds>::type>::type;
+                                         typename std::conditional<TL, WtLds, typename std::conditional<LA, WlaLds, WlaneLds>::type>::type>::type;
   LdsT& S = *(LdsT*)smem;
   const int b = P.uttMap ? P.uttMap[blockIdx.x] : (int)blockIdx.x;
   const int W = (int)blockDim.x, tid = (int)threadIdx.x;
@@ -873,6 +935,12 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
       S.fbest[1] = 0ull;
     }
   }
+  if constexpr (LA && !TL) {
+    if (tid == 0) {
+      S.mmaxKey[0] = f64Key(0.0); /* decodeBegin: the root hypothesis, score 0 */
+      S.mmaxKey[1] = 0ull;
+    }
+  }
   ldsBarrier();
   WlFront F;
   F.bestChain = 0.0; /* decodeBegin: the root hypothesis, score 0 */
@@ -896,7 +964,16 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
     }
     wlRowPrefetch(P, F, rowBase, T > 0);
     if (T > 0) {
+      if constexpr (LA && !TL) { /* (the staging moves on to the next record: what the head prices the row with, first) */
+        const uint32_t ek = F.pEk, flags = F.pFlags;
+        const float es = F.pSil;
+        wlStageRow(P, S, F, rowBase + 1, T > 1, 0, silScore, 0);
+        if (lane == 0) {
+          wlStageLa(S, 0, ek, es, flags);
+        }
+      } else {
       wlStageRow(P, S, F, rowBase + 1, T > 1, 0, silScore, 0);
+      }
     } else if (lane == 0) {
       S.row[0].nList = 0;
     }
@@ -1070,6 +1147,23 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
     const int nList = S.row[p].nList, silPos = S.row[p].silPos;
     const uint32_t rowDead = S.row[p].dead;
     const uint32_t nev = S.row[p].nev;
+    WlLogAddRegs<LA, GT> G; /* (empty without logAdd) */
+    if constexpr (LA && !TL) { /* best candidate = best hypothesis of the beam + best listed token, sil priced apart */
+      const double mmax = f64FromKey(S.mmaxKey[p]);
+      const double eM = S.eMax[p];
+      const double sS = (mmax + S.eSil[p]) + silScore;
+      bool any = eM == eM;
+      best = any ? mmax + eM : 0.0;
+      if (sS == sS && (!any || sS > best)) {
+        best = sS;
+        any = true;
+      }
+      thr = best - P.beamThreshold;
+      if (!any || !(best - best == 0.0)) { /* no candidate at all, or not finite: the general engines (every wave alike) */
+        dead = true;
+        return;
+      }
+    }
     SlRec me = {};
     unsigned long long cm = 0ull;
     if (!isSvc) {
@@ -1199,14 +1293,50 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
        * best candidate, while the other waves evaluate this frame's candidates (everything written here belongs to
        * the next frame; the position table is read by the build below, after the second barrier, and by nothing
        * before that) */
+      if constexpr (LA && !TL) {
+        if (t + 1 < T) {
+          const uint32_t ek = F.pEk, flags = F.pFlags;
+          const float es = F.pSil;
+          wlStageRow(P, S, F, rowBase + t + 2, t + 2 < T, q, silScore, nList);
+          if (lane == 0) {
+            wlStageLa(S, q, ek, es, flags);
+          }
+        }
+        if (lane == 0) {
+          S.mmaxKey[q] = 0ull; /* (this frame's build raises it) */
+        }
+      } else {
       if (t + 1 < T) {
         wlStageRow(P, S, F, rowBase + t + 2, t + 2 < T, q, silScore, nList);
+      }
       }
     } else if (!isSelf) {
       /* positions this lane does not extend with here: its own last token's (the repeat and the blank-then-last case
        * belong to the self wave) and those whose child state holds a lane (that lane merges the extension into its
        * repeat).  A lane without a state skips all. */
       const unsigned long long skip = live ? (cm | (lastPos < 64u ? 1ull << lastPos : 0ull)) : ~0ull;
+      if constexpr (LA && !TL) {
+        /* the state's other hypothesis reaches the same child state: fl(a + e) is monotone, so it is the smaller member */
+        const bool hasOther = (whichB ? hypNB : hypB) != kSlNoHyp;
+        double c1[GT];
+#pragma unroll
+        for (int j = 0; j < GT; ++j) {
+          c1[j] = m + ev[j]; /* NaN past the end of the list */
+          G.c2[j] = (whichB ? nb : bb) + ev[j];
+        }
+        slSilAdd<GT, true>(c1, G.c2, silScore != 0.0, silPos, wave, silScore);
+#pragma unroll
+        for (int j = 0; j < GT; ++j) {
+          const int pos = posBase + j;
+          double c = c1[j];
+          const bool ok = pos < 64 && ((skip >> (pos & 63)) & 1ull) == 0ull && c >= thr;
+          if (ok && hasOther && G.c2[j] >= thr) {
+            c = slLogAdd(c, G.c2[j]);
+          }
+          cs[j] = c;
+          cbin[j] = ok ? slBin<true>(best, c, winShift, winBase) : kSlInvalid;
+        }
+      } else {
 #pragma unroll
       for (int j = 0; j < GT; ++j) {
         const int pos = posBase + j;
@@ -1218,11 +1348,20 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
           L.pre[j] = pos < 64 && ((skip >> (pos & 63)) & 1ull) == 0ull && c == c;
           cs[j] = c;
           cbin[j] = kSlInvalid;
+          if constexpr (LA) { /* the second member: the state's other hypothesis, the same emission (and LM term, below) */
+            double c2 = (whichB ? nb : bb) + ev[j];
+            if (pos == silPos) {
+              c2 = c2 + silScore;
+            }
+            G.c2[j] = c2;
+            G.two = (whichB ? hypNB : hypB) != kSlNoHyp ? (1u << GT) - 1u : 0u;
+          }
         } else {
         const bool ok = pos < 64 && ((skip >> (pos & 63)) & 1ull) == 0ull && c >= thr;
         cs[j] = c;
         cbin[j] = ok ? slBin<false>(best, c, winShift, winBase) : kSlInvalid;
         }
+      }
       }
     } else {
       const bool lastOk = live && lastPos < 64u; /* the last token is in the frame's token beam (never blank) */
@@ -1233,6 +1372,19 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
         cB = cB + silScore;
       }
       const bool okB = ctc && live && cB >= thr;
+      if constexpr (LA) { /* the blank group's second member: the state's other hypothesis */
+        double cB2 = (whichB ? nb : bb) + eBlank;
+        if (blank == P.sil) {
+          cB2 = cB2 + silScore;
+        }
+        G.c2[0] = cB2;
+        G.two = (whichB ? hypNB : hypB) != kSlNoHyp ? 1u : 0u;
+        if constexpr (!TL) {
+          if (okB && G.two != 0u && cB2 >= thr) {
+            cB = slLogAdd(cB, cB2);
+          }
+        }
+      }
       /* (S, last, false): the repeat (:98-110) and the parent state's extension by last (:69-85) */
       const uint32_t lastP = par.pad;
       const uint32_t h1 = (par.info >> 16) & 0xFFu, h2 = par.info >> 24;
@@ -1269,14 +1421,25 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
         A.amR = t2 ? A.parAmB : (t1 ? A.parAmNB : A.amNB);
         A.prevR = t2 ? (uint32_t)blank : (t1 ? lastP : last);
       }
-      const bool okR = lastOk && (has0 || has1 || has2) && cR >= thr;
+      bool okR = lastOk && (has0 || has1 || has2) && cR >= thr;
+      if constexpr (LA) { /* (the best member is cR, its slot parR) */
+        G.r0 = r0;
+        G.r1 = r1;
+        G.r2 = r2;
+        G.has = (has0 ? 1u : 0u) | (has1 ? 2u : 0u) | (has2 ? 4u : 0u);
+        if constexpr (!TL) {
+          double sum;
+          okR = wlRepeatLogAdd(r0, r1, r2, G.has, thr, sum) && lastOk;
+          cR = okR ? sum : cR;
+        }
+      }
       const bool okL = ctc && lastOk && hasB && ((cm >> (lastPos & 63u)) & 1ull) == 0ull && cL >= thr;
       cs[0] = cB;
       cs[1] = cR;
       cs[2] = cL;
-      cbin[0] = okB ? slBin<false>(best, cB, winShift, winBase) : kSlInvalid;
-      cbin[1] = okR ? slBin<false>(best, cR, winShift, winBase) : kSlInvalid;
-      cbin[2] = okL ? slBin<false>(best, cL, winShift, winBase) : kSlInvalid;
+      cbin[0] = okB ? slBin<LA>(best, cB, winShift, winBase) : kSlInvalid;
+      cbin[1] = okR ? slBin<LA>(best, cR, winShift, winBase) : kSlInvalid;
+      cbin[2] = okL ? slBin<LA>(best, cL, winShift, winBase) : kSlInvalid;
 #pragma unroll
       for (int j = 3; j < GT; ++j) {
         cs[j] = NEG;
@@ -1343,6 +1506,11 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
         for (int j = 0; j < GT; ++j) {
           if (((lmSlots >> j) & 1u) != 0u) {
             cs[j] = cs[j] + U.lmW * (double)L.lmv[j];
+            if constexpr (LA) { /* (the same edge, the same term) */
+              if constexpr (!isSelf) {
+                G.c2[j] = G.c2[j] + U.lmW * (double)L.lmv[j];
+              }
+            }
           }
           const unsigned long long kc = (L.pre[j] && cs[j] == cs[j]) ? f64Key(cs[j]) : 0ull;
           k = kc > k ? kc : k;
@@ -1363,11 +1531,28 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
         dead = true;
         return;
       }
+      if constexpr (LA) { /* the merges, now that the threshold is known: the members that pass it, best first */
+        if (!isSvc) {
+#pragma unroll
+          for (int j = 0; j < GT; ++j) {
+            bool ok = L.pre[j] && cs[j] >= thr;
+            if (isSelf && j == 1) {
+              double sum;
+              ok = wlRepeatLogAdd(G.r0, G.r1, G.r2, G.has, thr, sum) && L.pre[1];
+              cs[1] = ok ? sum : cs[1];
+            } else if (ok && ((G.two >> j) & 1u) != 0u && G.c2[j] >= thr) {
+              cs[j] = slLogAdd(cs[j], G.c2[j]);
+            }
+            cbin[j] = ok ? slBin<true>(best, cs[j], winShift, winBase) : kSlInvalid;
+          }
+        }
+      } else {
       if (!isSvc) {
 #pragma unroll
         for (int j = 0; j < GT; ++j) {
           cbin[j] = (L.pre[j] && cs[j] >= thr) ? slBin<false>(best, cs[j], winShift, winBase) : kSlInvalid;
         }
+      }
       }
     }
     if (wave == 0) { /* housekeeping for everybody: what this frame's build adds to */
@@ -1498,7 +1683,7 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
 #pragma unroll
         for (int j = 0; j < GT; ++j) {
           if (cbin[j] != kSlInvalid) {
-            cbin[j] = slBin<false>(best, cs[j], shift, base);
+            cbin[j] = slBin<LA>(best, cs[j], shift, base);
             atomAdd32(&S.hist[p][cbin[j]], 1u);
           }
         }
@@ -1560,6 +1745,22 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
       }
       if (lane == selfWave + 1 && nNewWave > 0) {
         atomAdd32(&S.off[lane], (uint32_t)nNewWave);
+      }
+    }
+    if constexpr (LA && !TL) {
+      if (!isSvc) { /* the best hypothesis of the next beam: the best surviving (merged) score */
+        unsigned long long k = 0ull;
+#pragma unroll
+        for (int j = 0; j < GT; ++j) {
+          const unsigned long long kj = ((selMask[j] >> lane) & 1ull) ? f64Key(cs[j]) : 0ull;
+          k = kj > k ? kj : k;
+        }
+        if (waveBallot(k != 0ull) != 0ull) {
+          k = waveMax64(k);
+          if (lane == 0) {
+            atomMax64(&S.mmaxKey[q], k);
+          }
+        }
       }
     }
     mark(3);
@@ -1934,8 +2135,21 @@ FLTX_DEV void wlaneUtterance(const DecodeParams& P, char* smem) {
       const unsigned long long k = waveMax64(has ? f64Key(m) : 0ull);
       endBest = k != 0ull ? f64FromKey(k) : 0.0;
     }
+    if constexpr (LA && !TL) { /* the best candidate of decodeEnd is the best hypothesis of the final beam */
+      endBest = f64FromKey(S.mmaxKey[pe]);
+    }
     const double thr = endBest - P.beamThreshold;
     const bool ok = live && m >= thr && (!TL || hp != kSlNoHyp);
+    if constexpr (LA) { /* the state's two hypotheses finish into one (LexiconFreeDecoder.cpp:127-158), best first */
+      double lo = whichB ? nb : bb;
+      if constexpr (TL) {
+        lo = lo + U.lmW * (double)fin;
+      }
+      const uint32_t hl = whichB ? ((me.info >> 16) & 0xFFu) : (me.info >> 24);
+      if (ok && hl != kSlNoHyp && lo >= thr) {
+        m = slLogAdd(m, lo);
+      }
+    }
     const unsigned long long key = ok ? f64Key(m) : 0ull;
     int rank = 0;
     for (int i = 0; i < nState; ++i) {
